@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 r"""Benchmark of the Bloch-simulation hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over the synthetic workload: ``rfgr2beff`` (K0, writes
 Beff) followed by ``sims.blochsim`` (K1, integrates it), through the drop-in Python API and the
@@ -16,12 +16,22 @@ Workload at N = 1: BASELINE.json configs[2], the 128^3 cube (2 097 152 spins) x 
 fp32, closed-form synthetic inputs (mrphy_amd/synth.py).  For N > 1 the same
 cube is sharded over the ranks (configs[3]: total work fixed => "scaling": "strong").
 
-Besides the contract fields the JSON line carries
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if
+``--dump-outputs DIR`` is given, and prints the JSON line.  Besides the contract fields that line carries
   roofline      of the dominant kernel K1 (HBM-bound, 12 B/spin-step algorithmic), its launch
                 duration measured live with HIP events on the launch stream;
-  kernels       K0 / K1 / fused-K2 durations and rates;
+  kernels       K0 / K1 durations and rates.
+What the headline does not need runs only with ``--full``:
+  kernels.K2_fused_rfgr_fwd  the fused kernel on the same workload (and its all-fp32 step);
+  placement     the streaming-write rate of this process's Beff block (N = 1);
+  arena_step, configs        the arena-probed step and BASELINE configs[1] / configs[4] (N = 1);
   cpu_baseline  the oracle's op-for-op restatement of the reference's CPU PyTorch path, timed
-                on this box's host cores on a bounded sample (rank 0, N = 1 only).
+                on this box's host cores on a bounded sample (rank 0, N = 1 only);
+and with ``--mode grad`` the materialised gradient routes and the CPU leg.
+
+``--dump-outputs DIR`` writes, after the timed steps, what the last timed step returned to its caller as
+``DIR/<name>.npy`` in float32: ``Mo`` (forward), or ``Mo``, ``grad_rf``, ``grad_gr`` (``--mode grad``).  The inputs
+are closed-form (mrphy_amd/synth.py): the same arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -139,6 +149,13 @@ def parse():
                          '(the `configs` object of the JSON line)')
     ap.add_argument('--cpu-chunks', type=int, default=3,
                     help='cpu_baseline: number of spin chunks timed (SURVEY 8d: >= 3, extrapolated)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run what the headline does not need: the fused K2 leg, the Beff block\'s fill rate, the '
+                         'arena step and BASELINE configs[1] / configs[4] (N = 1), the cpu_baseline leg, and with --mode '
+                         'grad the materialised routes; off by default (a plain run times the headline only)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last timed step returned (Mo; with --mode grad also '
+                         'grad_rf, grad_gr) as DIR/<name>.npy in float32')
     a = ap.parse_args()
     if a.config is not None:
         a.n, a.nT, a.mode = {1: (64, 1024, 'fwd'), 2: (128, 4096, 'fwd'), 4: (64, 2048, 'grad')}[a.config]
@@ -234,6 +251,20 @@ def emit(obj):
 
 
 T0 = time.perf_counter()
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    r"""``--dump-outputs``: every tensor of `arrays` (name -> tensor) as ``d/<name>.npy`` in float32, at most
+    DUMP_BYTES_MAX bytes in all (the headline's Mo is 25 MB)."""
+    import numpy as np
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(x.nbytes for x in host.values())
+    assert total <= DUMP_BYTES_MAX, f'--dump-outputs: {total} bytes of outputs, more than {DUMP_BYTES_MAX}'
+    os.makedirs(d, exist_ok=True)
+    for k, x in host.items():
+        np.save(os.path.join(d, k + '.npy'), x)
+    log(f'outputs written to {d}: ' + ', '.join(f'{k} {x.shape}' for k, x in host.items()))
 
 
 def cpu_baseline(n, nT, spins, chunks=3, budget_s=150.0):
@@ -306,7 +337,7 @@ def cpu_baseline_grad(n, nT, spins, chunks=3, budget_s=60.0):
         (g_rf, g_gr), idx[:done * spins]
 
 
-def grad_measure(n, nT, K, W, *, multi=True, fused_only=False, candidates=-1, log_=None, route='both'):
+def grad_measure(n, nT, K, W, *, multi=True, fused_only=False, candidates=-1, log_=None, route='both', outputs=None):
     r"""BASELINE configs[4]: multi-scale pulse design step on one GPU.  A coarse pulse (nT/2 samples
     at 2 dt) is resampled to nT samples with the differentiable on-device ``interpT``, simulated,
     and ``sum(Mo)`` is differentiated back to the coarse ``rf``/``gr`` -- through the materialised route
@@ -314,7 +345,8 @@ def grad_measure(n, nT, K, W, *, multi=True, fused_only=False, candidates=-1, lo
     signature), once with every block drawn from the caching allocator and once with the history, ``grad_Beff`` and
     ``Beff`` blocks of a placement-probed ``mrphy_amd.workspace.GradWorkspace`` (``candidates`` != 0; < 0: its own caps); and through the
     fused kernels (K2 with checkpoints + K2b), which is what ``install()`` makes ``SpinArray.applypulse`` run.
-    Returns the JSON object of the run (no cpu_baseline)."""
+    Returns the JSON object of the run (no cpu_baseline); a dict `outputs` receives what the last timed iteration of the
+    fused route returned (Mo and the gradients of the pulse)."""
     import mrphy_amd
     from mrphy_amd import beffective, sims, synth, interp, fused, workspace
     dev = torch.device('cuda', torch.cuda.current_device())
@@ -437,6 +469,8 @@ def grad_measure(n, nT, K, W, *, multi=True, fused_only=False, candidates=-1, lo
                 launches.setdefault('_fused_iter', []).append((e[0], e[1], e[2]))
             g_fused = (rf.grad, gr.grad)
         torch.cuda.synchronize()
+        if outputs is not None:
+            outputs.update(Mo=Mo, grad_rf=g_fused[0], grad_gr=g_fused[1])
         t_wall = time.perf_counter() - t_wall
         for e0, e1, e2 in launches.pop('_fused_iter'):
             f_fwd += e0.elapsed_time(e1)
@@ -519,10 +553,14 @@ def grad_mode(a):
     from mrphy_amd import synth, fused
     dev = torch.device('cuda', 0)
     n, nT = a.n, a.nT
-    out = grad_measure(n, nT, a.steps, a.warmup, multi=not a.no_interp, fused_only=a.fused_only,
-                       candidates=a.grad_candidates, log_=log, route=a.grad_route)
+    last = {}
+    out = grad_measure(n, nT, a.steps, a.warmup, multi=not a.no_interp, fused_only=a.fused_only or not a.full,
+                       candidates=a.grad_candidates, log_=log, route=a.grad_route, outputs=last)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, last)
+    del last
     rel_l2 = lambda x, y: float((x - y).norm() / y.norm())  # noqa: E731
-    if not a.no_cpu:
+    if a.full and not a.no_cpu:
         log(f'cpu baseline (forward + backward) on {host_cores()} cores')
         cb, (c_rf, c_gr), cidx = cpu_baseline_grad(n, nT, min(a.cpu_spins, 8192), a.cpu_chunks, min(a.cpu_budget, 60.0))
         # the same gradient contribution of the same spins through the GPU's fused route, fine pulse
@@ -773,10 +811,12 @@ def main():
         gathered_consistent = all(int(c) == int(allchk[0]) for c in allchk)
 
     log(f'{K} steps in {elapsed:.3f}s')
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {'Mo': Mo})
 
     # fused rf,gr -> Mo (K2): same workload, no Beff in HBM; VALU-bound, reported beside
     k2_ms = k2_fast_ms = None
-    if not a.no_fused:
+    if a.full and not a.no_fused:
         with torch.no_grad():
             f = lambda: fused.blochsim_rfgr(sp['M0'], p['rf'], p['gr'], sp['loc'], Δf=sp['Δf'],  # noqa
                                             γ_beff=sp['γ'], T1=sp['T1'], T2=sp['T2'], γ=sp['γ'],
@@ -808,7 +848,7 @@ def main():
     # the allocation (docs/LABNOTES.md "Placement"), which is what K0's and K1's
     # process-to-process spread comes from.
     placement = None
-    if world == 1:
+    if world == 1 and a.full:
         with torch.no_grad():
             blk = arena.block if arena is not None else torch.empty((1, nM, nT, 3), dtype=torch.float32, device=dev)
             tw = []
@@ -834,13 +874,12 @@ def main():
 
     # ---- beside the headline, in the same process and the same JSON line (N = 1): the step through the PLAIN
     # reference signature, and the other single-GPU BASELINE configs (VERDICT r4, items 2 and "weak 4/5") ----------
-    extra = arena_leg = None
-    if world == 1:
+    extra = arena_leg = extras_error = None
+    if world == 1 and a.full:
         fused_equal_main = fused_equal if k2_ms is not None else None
         Mo_keep, sp_keep = Mo, sp
         del arena
         torch.cuda.empty_cache()
-        extras_error = None
         try:          # the headline line must come out whatever happens to the additional legs
             if a.arena == 0 and not a.no_extra_configs:
                 log('arena step (the same step with a probed Beff block: rfgr2beff(..., out=, store=))')
@@ -1018,7 +1057,7 @@ def main():
         try:
             grp = next(e for e in json.load(open(bs))['groups'] if e.get('family') == 'K1' and e['grid_work_items'] == rows)
             out['roofline']['rocprof'] = {
-                'source': rel(bs) + ': rocprofv3 --kernel-trace of `bench.py --no-extra-configs`, launches of this kernel at '
+                'source': rel(bs) + ': rocprofv3 --kernel-trace of `bench.py --full --no-extra-configs`, launches of this kernel at '
                           'this grid size only -- a committed collection, not this run',
                 'calls': grp['calls'], 'mean_ms': grp['mean_ms'], 'median_ms': grp['median_ms'], 'min_ms': grp['min_ms'],
                 'frac_of_mean': grp['frac_hbm_of_mean'], 'frac_of_median': grp['frac_hbm_of_median'],
@@ -1026,7 +1065,7 @@ def main():
         except Exception:
             pass
     log('fused leg done' if k2_ms is not None else 'fused leg skipped')
-    if world == 1 and not a.no_cpu:
+    if world == 1 and a.full and not a.no_cpu:
         log(f'cpu baseline on {host_cores()} cores')
         cb, Mo_cpu, cidx = cpu_baseline(n, nT, a.cpu_spins, a.cpu_chunks, a.cpu_budget)
         d = (Mo[0, cidx.to(dev)].double().cpu() - Mo_cpu[0].double())

@@ -387,6 +387,36 @@ def gen_mobjs_calls(ref, out):
         out[f'mobjs_{tag}'] = rec
 
 
+def gen_refapi(ref, out):
+    r"""What the object-layer tests of tests/test_abi_and_host.py need of the reference without importing it: the
+    signatures of the methods install() replaces and of the Pulse constructor / ``to`` (tests/util.py:
+    signature_record), the attribute names of a real ``Pulse`` and ``SpinCube``, the values of
+    ``mobjs.Examples.pulse()`` / ``spincube()``, and the reference's own results of the CPU calls those tests route."""
+    from util import signature_record
+    mrphy, beffective, sims, slowsims, mobjs, utils = ref
+    p, cube = mobjs.Examples.pulse(), mobjs.Examples.spincube()
+    sigs = {'Pulse.__init__': mobjs.Pulse.__init__, 'Pulse.to': mobjs.Pulse.to, 'Pulse.interpT': mobjs.Pulse.interpT,
+            'SpinArray.applypulse': mobjs.SpinArray.applypulse, 'SpinArray.extract': mobjs.SpinArray.extract,
+            'SpinArray.embed': mobjs.SpinArray.embed}
+    q = p.to(dtype=torch.float64)
+    meta = {'signatures': {k: signature_record(f) for k, f in sigs.items()},
+            'pulse_attrs': sorted(a for a in dir(p) if hasattr(p, a)),
+            'spincube_attrs': sorted(a for a in dir(cube) if hasattr(cube, a)),
+            'pulse_desc': p.desc, 'pulse_device': str(p.device), 'pulse_dtype': str(p.dtype),
+            'to_same_is_self': p.to(device=p.device, dtype=p.dtype) is p, 'to_f64_dtype': str(q.dtype),
+            'cube_Δf_is_None': cube.Δf_ is None}
+    p2 = p.interpT(p.dt / 2)
+    rec = dict(meta=np.array(json.dumps(meta)),
+               **{f'pulse.{a}': np_(getattr(p, a)) for a in ('rf', 'gr', 'dt', 'gmax', 'smax', 'rfmax')},
+               **{f'pulse_f64.{a}': np_(getattr(q, a)) for a in ('rf', 'dt')},
+               **{f'cube.{a}': np_(getattr(cube, a)) for a in ('mask', 'M_', 'T1_', 'T2_', 'γ_', 'loc_')},
+               applypulse=np_(cube.applypulse(p)), freeprec=np_(cube.freeprec(torch.tensor(1e-3))),
+               rfgr2beff=np_(beffective.rfgr2beff(p.rf, p.gr, cube.loc_)), interpT_half_nT=np.array(p2.rf.shape[2]))
+    if cube.Δf_ is not None:
+        rec['cube.Δf_'] = np_(cube.Δf_)
+    out['refapi'] = rec
+
+
 # ---------------------------------------------------------------------------------------------
 def check_oracle(ref):
     r"""Function-by-function comparison oracle vs live reference (pinning)."""
@@ -527,7 +557,7 @@ def main():
     out = {}
     gens = dict(ref=gen_ref_cases, rfgr=gen_rfgr, bcast=gen_bcast, onestep=gen_1step,
                 uphi=gen_uphi, freeprec=gen_freeprec, interp=gen_interp, masks=gen_masks, ab=gen_ab,
-                mobjs=gen_mobjs_calls, big=gen_big, beffrows=gen_beffrows)
+                mobjs=gen_mobjs_calls, big=gen_big, beffrows=gen_beffrows, refapi=gen_refapi)
     for name, g in gens.items():
         if a.only and name not in a.only.split(','):
             continue

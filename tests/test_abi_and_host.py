@@ -224,24 +224,88 @@ def test_shard_bounds_cover_all_spins():
             assert max(sizes) - min(sizes) <= 1
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference/mrphy'), reason='reference only in the build container')
 def test_install_routes_the_reference_object_layer():
-    r"""With the reference importable (build container only): after install(), the function targets of mobjs are
-    routers (SURVEY 8b "Fallback"): a call whose tensors all live on the CPU is handed to the
-    reference's OWN saved function -- so a CPU ``cube.applypulse(p)`` after install() equals the uninstalled result
-    bit for bit -- and a call with any tensor elsewhere goes to the HIP path and never reaches the saved reference
-    callable (checked here with tensors on the 'meta' device and the saved callables replaced by tripwires; on the
-    GPU box by test_install_router_sends_device_tensors_to_the_kernels)."""
+    r"""After install(), the function targets of mobjs are routers (SURVEY 8b "Fallback"): a call
+    whose tensors all live on the CPU is handed to the user's OWN saved function -- so a CPU ``cube.applypulse(p)``
+    after install() equals the uninstalled result bit for bit -- and a call with any tensor elsewhere goes to the HIP
+    path and never reaches the saved callable (checked here with tensors on the 'meta' device and the saved callables
+    replaced by tripwires; on the GPU box by test_install_router_sends_device_tensors_to_the_kernels).  The ``mrphy``
+    installed into is a stand-in package laid out as the reference's (``mrphy.beffective / sims / slowsims / mobjs``),
+    whose CPU functions are the oracle's op-for-op restatement and whose objects hold ``mobjs.Examples.spincube()`` /
+    ``pulse()`` as ``tests/golden/refapi.npz`` recorded them; its CPU results are checked against the reference's own,
+    recorded there as well, bit for bit."""
     code = r'''
-import sys
-sys.path.insert(0, %r); sys.path.insert(0, '/root/reference')
+import sys, types
+sys.path.insert(0, %r); sys.path.insert(0, %r); sys.path.insert(0, %r)
 sys.dont_write_bytecode = True
-import torch, mrphy, mrphy_amd
+import torch, mrphy_amd
+from util import golden
+G = golden('refapi')
+c = lambda k: torch.from_numpy(G[k])
+
+
+def stand_in(name, src):
+    m = types.ModuleType(name)
+    exec(src, m.__dict__)
+    sys.modules[name] = m
+    return m
+
+
+mrphy = stand_in('mrphy', '')
+for sub, names in (('beffective', ('rfgr2beff', 'beff2ab')), ('sims', ('blochsim', 'freeprec')),
+                   ('slowsims', ('blochsim_1step', 'blochsim_ab'))):
+    setattr(mrphy, sub, stand_in('mrphy.' + sub, 'import bloch_oracle as O\n' + ''.join(
+        f'def {f}(*a, **k):\n    return O.{f}(*a, **k)\n' for f in names)))
+mrphy.mobjs = stand_in('mrphy.mobjs', """
+import torch
+import bloch_oracle as O
+from mrphy import beffective, sims
+
+
+class Pulse:
+    def __init__(self, rf, gr, *, dt, desc='generic pulse'):
+        self.rf, self.gr, self.dt, self.desc, self.device, self.dtype = rf, gr, dt, desc, rf.device, rf.dtype
+
+    def interpT(self, dt, *, kind='linear'):
+        n = round(self.rf.shape[2] * float(self.dt) / float(dt))
+        f = lambda w: torch.nn.functional.interpolate(w, size=n, mode='linear')
+        return Pulse(f(self.rf), f(self.gr), dt=dt, desc=f"{self.desc} + interpT'ed: dt = {float(dt)}")
+
+
+class SpinArray:
+    def __init__(self, mask, M_, T1_, T2_, γ_, loc_, Δf_):
+        self.mask, self.M_, self.T1_, self.T2_, self.γ_, self.loc_, self.Δf_ = mask, M_, T1_, T2_, γ_, loc_, Δf_
+        self.device, self.dtype = M_.device, M_.dtype
+
+    def extract(self, v, *, out_=None):
+        return O.mask_extract(v, self.mask)
+
+    def embed(self, v_, *, out=None):
+        return O.mask_embed(v_, self.mask, out)
+
+    def applypulse(self, pulse, *, doEmbed=False, doRelax=True, doUpdate=False, loc=None, loc_=None, Δf=None,
+                   Δf_=None, b1Map=None, b1Map_=None):
+        beff = beffective.rfgr2beff(pulse.rf, pulse.gr, self.loc_, Δf=self.Δf_, γ=self.γ_)
+        relax = dict(T1=self.T1_, T2=self.T2_) if doRelax else {}
+        M_ = sims.blochsim(self.M_, beff, γ=self.γ_, dt=pulse.dt, **relax)
+        return self.embed(M_) if doEmbed else M_
+
+    def freeprec(self, dur):
+        return sims.freeprec(self.M_, dur, T1=self.T1_, T2=self.T2_, Δf=self.Δf_)
+
+
+class SpinCube(SpinArray):
+    def _update_loc_(self):
+        pass
+""")
 from mrphy import mobjs
-cube, p = mobjs.Examples.spincube(), mobjs.Examples.pulse()
+cube = mobjs.SpinCube(c('cube.mask'), c('cube.M_'), c('cube.T1_'), c('cube.T2_'), c('cube.γ_'), c('cube.loc_'), c('cube.Δf_'))
+p = mobjs.Pulse(c('pulse.rf'), c('pulse.gr'), dt=c('pulse.dt'))
 want = cube.applypulse(p)                        # the reference, before install()
 want_fp = cube.freeprec(torch.tensor(1e-3))
 want_b = cube.pulse2beff(p) if False else mrphy.beffective.rfgr2beff(p.rf, p.gr, cube.loc_)
+# the stand-in computes what the reference computed on these objects, bit for bit
+assert torch.equal(want, c('applypulse')) and torch.equal(want_fp, c('freeprec')) and torch.equal(want_b, c('rfgr2beff'))
 mrphy_amd.install(mrphy)
 for name, fn, hip in (('blochsim', mrphy.sims.blochsim, mrphy_amd.sims.blochsim),
                       ('rfgr2beff', mrphy.beffective.rfgr2beff, mrphy_amd.beffective.rfgr2beff),
@@ -257,7 +321,7 @@ assert mobjs.SpinCube._update_loc_ is mrphy_amd._spincube_update_loc_
 assert mobjs.Pulse.interpT is mrphy_amd._pulse_interpT
 assert mobjs.SpinArray.applypulse is mrphy_amd._spinarray_applypulse
 p2 = p.interpT(p.dt / 2)
-assert p2.rf.shape[2] == 2 * p.rf.shape[2] and 'interpT' in p2.desc and p2.device == p.device
+assert p2.rf.shape[2] == 2 * p.rf.shape[2] == int(G['interpT_half_nT']) and 'interpT' in p2.desc and p2.device == p.device
 assert torch.equal(cube.extract(cube.embed(cube.M_)), cube.M_)
 # CPU objects after install(): the user's own reference, bit for bit
 assert torch.equal(cube.applypulse(p), want)
@@ -308,7 +372,7 @@ mrphy_amd.uninstall(mrphy)
 assert mobjs.SpinArray.applypulse.__module__ == 'mrphy.mobjs'
 assert torch.equal(cube.applypulse(p), want)          # the reference again
 print('routed')
-''' % ROOT
+''' % (ROOT, os.path.join(ROOT, 'tests'), os.path.join(ROOT, 'oracle'))
     out = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True)
     assert out.returncode == 0 and 'routed' in out.stdout, (out.stdout[-500:], out.stderr[-2000:])
 
@@ -559,77 +623,73 @@ def test_no_kernel_of_the_library_uses_scratch():
     assert k3 and max(k3) <= 256, k3
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference/mrphy'), reason='reference only in the build container')
 def test_gpu_suite_stand_ins_mirror_the_reference_classes():
     r"""The GPU suite replays the object layer on stand-ins (``tests/gpu_common.py``: ``PulseStandIn``,
-    ``SpinArrayStandIn``) because the reference cannot travel to the GPU box.  Here, where it imports, they are
-    tied to the real classes: constructor / ``to`` signatures (names, kinds, defaults) of ``mobjs.Pulse``, the
-    signatures of the methods ``install()`` binds (``Pulse.interpT``, ``SpinArray.applypulse / extract / embed``)
-    against the functions bound in their place, and every attribute those functions touch on a real ``Pulse`` /
-    ``SpinArray`` against what the stand-ins carry -- so that the stand-ins cannot drift from ``mobjs.py:56-99,
-    222-240, 394-450, 512-553`` unnoticed."""
-    code = r'''
-import sys, inspect, ast, textwrap
-sys.path.insert(0, %r); sys.path.insert(0, %r); sys.path.insert(0, %r); sys.path.insert(0, '/root/reference')
-sys.dont_write_bytecode = True
-import torch, mrphy, mrphy_amd
-from mrphy import mobjs
-import gpu_common as T3
+    ``SpinArrayStandIn``) because the reference does not travel with the repository.  They are tied to the real
+    classes through ``tests/golden/refapi.npz`` (recorded from the reference by ``tests/golden/make_golden.py``):
+    constructor / ``to`` signatures (names, kinds, defaults) of ``mobjs.Pulse``, the signatures of the methods
+    ``install()`` binds (``Pulse.interpT``, ``SpinArray.applypulse / extract / embed``) against the functions bound
+    in their place, and every attribute those functions touch on a real ``Pulse`` / ``SpinArray`` against what the
+    stand-ins carry -- so that the stand-ins cannot drift from ``mobjs.py:56-99, 222-240, 394-450, 512-553``
+    unnoticed."""
+    import ast
+    import inspect
+    import json
+    import textwrap
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import gpu_common as T3
+    from util import golden, signature_record
+    G = golden('refapi')
+    meta = json.loads(str(G['meta']))
+    ref = meta['signatures']
 
-def same_default(a, b):
-    if isinstance(a, torch.Tensor) or isinstance(b, torch.Tensor):
-        return isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor) and a.shape == b.shape and \
-            a.dtype == b.dtype and torch.equal(a, b)
-    return a == b
+    def same_signature(g, what):
+        got = json.loads(json.dumps(signature_record(g)))
+        assert [x[0] for x in got] == [x[0] for x in ref[what]], (what, got, ref[what])
+        for a, b in zip(got, ref[what]):
+            assert a[1:3] == b[1:3], (what, a, b)                 # kind, has a default
+            if b[2]:
+                assert a[3] == b[3], (what, a, b)                 # the default (a tensor: shape, dtype, values)
 
-def same_signature(f, g, what):
-    pf, pg = inspect.signature(f).parameters, inspect.signature(g).parameters
-    assert list(pf) == list(pg), (what, list(pf), list(pg))
-    for n in pf:
-        assert pf[n].kind == pg[n].kind, (what, n, pf[n].kind, pg[n].kind)
-        assert (pf[n].default is inspect._empty) == (pg[n].default is inspect._empty), (what, n)
-        if pf[n].default is not inspect._empty:
-            assert same_default(pf[n].default, pg[n].default), (what, n, pf[n].default, pg[n].default)
+    # constructor and .to of Pulse (mobjs.py:56-99, 222-240)
+    same_signature(T3.PulseStandIn.__init__, 'Pulse.__init__')
+    same_signature(T3.PulseStandIn.to, 'Pulse.to')
+    # the methods install() replaces, against their replacements (mobjs.py:177-220, 394-450, 512-553)
+    same_signature(mrphy_amd._pulse_interpT, 'Pulse.interpT')
+    same_signature(mrphy_amd._spinarray_applypulse, 'SpinArray.applypulse')
+    same_signature(mrphy_amd._spinarray_extract, 'SpinArray.extract')
+    same_signature(mrphy_amd._spinarray_embed, 'SpinArray.embed')
 
-# constructor and .to of Pulse (mobjs.py:56-99, 222-240)
-same_signature(mobjs.Pulse.__init__, T3.PulseStandIn.__init__, 'Pulse.__init__')
-same_signature(mobjs.Pulse.to, T3.PulseStandIn.to, 'Pulse.to')
-# the methods install() replaces, against their replacements (mobjs.py:177-220, 394-450, 512-553)
-same_signature(mobjs.Pulse.interpT, mrphy_amd._pulse_interpT, 'Pulse.interpT')
-same_signature(mobjs.SpinArray.applypulse, mrphy_amd._spinarray_applypulse, 'SpinArray.applypulse')
-same_signature(mobjs.SpinArray.extract, mrphy_amd._spinarray_extract, 'SpinArray.extract')
-same_signature(mobjs.SpinArray.embed, mrphy_amd._spinarray_embed, 'SpinArray.embed')
+    def touched(fn, obj='self'):
+        r"""attribute names read or written on `obj` in the source of fn"""
+        tree = ast.parse(textwrap.dedent(inspect.getsource(fn)))
+        return {n.attr for n in ast.walk(tree)
+                if isinstance(n, ast.Attribute) and isinstance(n.value, ast.Name) and n.value.id == obj}
 
-def touched(fn, obj='self'):
-    """attribute names read or written on `obj` in the source of fn"""
-    tree = ast.parse(textwrap.dedent(inspect.getsource(fn)))
-    return {n.attr for n in ast.walk(tree) if isinstance(n, ast.Attribute) and isinstance(n.value, ast.Name) and n.value.id == obj}
-
-p, cube = mobjs.Examples.pulse(), mobjs.Examples.spincube()
-# what the bound functions touch on the array / the pulse exists on the real objects AND on the stand-ins
-arr_attrs = (touched(mrphy_amd._spinarray_applypulse) | touched(mrphy_amd._spinarray_extract) | touched(mrphy_amd._spinarray_embed))
-pulse_attrs = touched(mrphy_amd._pulse_interpT) | touched(mrphy_amd._spinarray_applypulse, 'pulse') | touched(mrphy_amd._spinarray_applypulse, 'p')
-g = torch.Generator().manual_seed(0)
-sp = T3.SpinArrayStandIn(cube.mask, cube.M_, cube.T1_, cube.T2_, cube.γ_)
-ps = T3.PulseStandIn(p.rf, p.gr, dt=p.dt)
-for a in sorted(arr_attrs):
-    assert hasattr(cube, a), ('real SpinCube lacks', a)
-    assert hasattr(sp, a), ('SpinArrayStandIn lacks', a)
-for a in sorted(pulse_attrs):
-    assert hasattr(p, a), ('real Pulse lacks', a)
-    assert hasattr(ps, a), ('PulseStandIn lacks', a)
-# same values where both exist: the stand-in's constructor normalises as the real one does (mobjs.py:84-99)
-for a in ('rf', 'gr', 'dt', 'gmax', 'smax', 'rfmax'):
-    x, y = getattr(p, a), getattr(ps, a)
-    assert x.shape == y.shape and x.dtype == y.dtype and torch.equal(x, y), a
-assert (p.desc, p.device, p.dtype) == (ps.desc, ps.device, ps.dtype)
-q, qs = p.to(dtype=torch.float64), ps.to(dtype=torch.float64)
-assert q.dtype == qs.dtype == torch.float64 and torch.equal(q.rf, qs.rf) and torch.equal(q.dt, qs.dt)
-assert ps.to(device=ps.device, dtype=ps.dtype) is ps and p.to(device=p.device, dtype=p.dtype) is p
-print('tied', len(arr_attrs), len(pulse_attrs))
-''' % (ROOT, os.path.join(ROOT, 'tests'), os.path.join(ROOT, 'oracle'))
-    out = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True)
-    assert out.returncode == 0 and 'tied' in out.stdout, (out.stdout[-500:], out.stderr[-2500:])
+    # what the bound functions touch on the array / the pulse exists on the real objects AND on the stand-ins
+    arr_attrs = (touched(mrphy_amd._spinarray_applypulse) | touched(mrphy_amd._spinarray_extract)
+                 | touched(mrphy_amd._spinarray_embed))
+    pulse_attrs = (touched(mrphy_amd._pulse_interpT) | touched(mrphy_amd._spinarray_applypulse, 'pulse')
+                   | touched(mrphy_amd._spinarray_applypulse, 'p'))
+    c = lambda k: torch.from_numpy(G[k])  # noqa: E731
+    sp = T3.SpinArrayStandIn(c('cube.mask'), c('cube.M_'), c('cube.T1_'), c('cube.T2_'), c('cube.γ_'))
+    ps = T3.PulseStandIn(c('pulse.rf'), c('pulse.gr'), dt=c('pulse.dt'))
+    for a in sorted(arr_attrs):
+        assert a in meta['spincube_attrs'], ('real SpinCube lacks', a)
+        assert hasattr(sp, a), ('SpinArrayStandIn lacks', a)
+    for a in sorted(pulse_attrs):
+        assert a in meta['pulse_attrs'], ('real Pulse lacks', a)
+        assert hasattr(ps, a), ('PulseStandIn lacks', a)
+    # same values where both exist: the stand-in's constructor normalises as the real one does (mobjs.py:84-99)
+    for a in ('rf', 'gr', 'dt', 'gmax', 'smax', 'rfmax'):
+        x, y = c(f'pulse.{a}'), getattr(ps, a)
+        assert x.shape == y.shape and x.dtype == y.dtype and torch.equal(x, y), a
+    assert (meta['pulse_desc'], meta['pulse_device'], meta['pulse_dtype']) == (ps.desc, str(ps.device), str(ps.dtype))
+    qs = ps.to(dtype=torch.float64)
+    assert meta['to_f64_dtype'] == str(qs.dtype) == 'torch.float64'
+    assert torch.equal(c('pulse_f64.rf'), qs.rf) and torch.equal(c('pulse_f64.dt'), qs.dt)
+    assert meta['to_same_is_self'] and ps.to(device=ps.device, dtype=ps.dtype) is ps
+    print('tied', len(arr_attrs), len(pulse_attrs))
 
 
 def test_every_translation_unit_is_built_and_flags_name_real_units():

@@ -143,7 +143,7 @@ def test_bench_rank_path_prints_exactly_one_json_line(coll):
     env = dict(os.environ, RANK='0', LOCAL_RANK='0', WORLD_SIZE='1', MASTER_ADDR='127.0.0.1',
                MASTER_PORT=str(29700 + os.getpid() % 2000), HSA_ENABLE_IPC_MODE_LEGACY='0')
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--cube', '16', '--nT', '64',
-                        '--steps', '2', '--warmup', '1', '--no-cpu', '--collectives', coll], env=env, capture_output=True,
+                        '--steps', '2', '--warmup', '1', '--full', '--no-cpu', '--collectives', coll], env=env, capture_output=True,
                        text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = r.stdout.splitlines()
@@ -172,7 +172,7 @@ def test_bench_three_ranks_rehearsed_on_one_gpu():
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_PORT', 'MASTER_ADDR'):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '3', '--cube', '17', '--nT', '64',
-                        '--steps', '2', '--warmup', '1', '--no-cpu'], env=env, capture_output=True, text=True,
+                        '--steps', '2', '--warmup', '1', '--full', '--no-cpu'], env=env, capture_output=True, text=True,
                        timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = r.stdout.splitlines()

@@ -17,6 +17,21 @@ def golden(name):
         return {k: z[k] for k in z.files}
 
 
+def signature_record(fn):
+    r"""The parameters of `fn` as JSON-able data: [name, kind, has default, default], a tensor default as
+    [shape, dtype, values] and any other default by its repr -- what tests/golden/refapi.npz stores for the reference's
+    object-layer methods (tests/golden/make_golden.py: gen_refapi)."""
+    import inspect
+
+    def enc(v):
+        if isinstance(v, torch.Tensor):
+            return [list(v.shape), str(v.dtype), v.detach().cpu().double().flatten().tolist()]
+        return repr(v)
+    return [[n, int(q.kind), q.default is not inspect.Parameter.empty,
+             None if q.default is inspect.Parameter.empty else enc(q.default)]
+            for n, q in inspect.signature(fn).parameters.items()]
+
+
 def t(x, dtype=None, device='cpu'):
     y = torch.from_numpy(np.asarray(x))
     return y.to(device=device, dtype=dtype) if dtype is not None else y.to(device)

@@ -115,17 +115,17 @@ HEAD = ('128^3 x 4096 (configs[2], headline)', 128, 4096, ('K0', 'K1'))
 CFG1 = ('64^3 x 1024 (configs[1])', 64, 1024, ('K0', 'K1'))
 CFG4 = ('64^3 x 2048 (configs[4])', 64, 2048, ('K0', 'K1h', 'K3'))
 by_size('prof_cfg2', R + '_bench_cfg2_by_size.json', [HEAD],
-        'rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --warmup 2 --no-cpu --no-extra-configs')
+        'rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 20 --warmup 2 --no-cpu --no-extra-configs')
 by_size('prof_default', R + '_bench_default_by_size.json', [HEAD, CFG1, CFG4],
-        'rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --warmup 2 --no-cpu   (the driver\'s command: '
+        'rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 20 --warmup 2 --no-cpu   (the driver\'s command: '
         'configs[1] and configs[4] timed in the same process; the K1h / K3 groups hold both routes of configs[4] and the '
         'workspace probe\'s launches are the <prec_f64, false, ...> instances)')
 by_size('prof_cfg1', R + '_bench_cfg1_by_size.json', [CFG1],
-        'rocprofv3 --kernel-trace --stats -- python3 bench.py --config 1 --steps 20 --warmup 2 --no-cpu')
+        'rocprofv3 --kernel-trace --stats -- python3 bench.py --full --config 1 --steps 20 --warmup 2 --no-cpu')
 by_size('prof_cfg4', R + '_bench_cfg4_by_size.json', [CFG4],
-        'rocprofv3 --kernel-trace --stats -- python3 bench.py --config 4 --steps 30 --warmup 2 --no-cpu --grad-route allocator')
+        'rocprofv3 --kernel-trace --stats -- python3 bench.py --full --config 4 --steps 30 --warmup 2 --no-cpu --grad-route allocator')
 by_size('prof_cfg4_ws', R + '_bench_cfg4_workspace_by_size.json', [CFG4],
-        'rocprofv3 --kernel-trace --stats -- python3 bench.py --config 4 --steps 30 --warmup 2 --no-cpu --grad-route workspace')
+        'rocprofv3 --kernel-trace --stats -- python3 bench.py --full --config 4 --steps 30 --warmup 2 --no-cpu --grad-route workspace')
 stats('prof_cfg1', R + '_bench_cfg1_kernel_stats.csv')
 stats('prof_shard', R + '_shard_of_8_kernel_stats.csv')
 stats('prof_cfg4', R + '_bench_cfg4_kernel_stats.csv')

@@ -19,17 +19,17 @@ timeout -k 10 200 $P --pmc $SQ1 -d $O/k2b_sq1 -- python3 tools/run_kernels.py gr
 timeout -k 10 200 $P --pmc $SQ2 -d $O/k2b_sq2 -- python3 tools/run_kernels.py gradfused 64 2048 3 > $O/k2b_sq2.log 2>&1; rc=$?; echo "k2b sq2 rc=$rc"; chk $rc
 python3 tools/collect_profiles.py $O r06 > $O/collect1.txt 2>&1
 # bench lines: the driver's command (all single-GPU configs in one line), then each config alone
-timeout -k 10 600 python3 bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.log; rc=$?; echo "bench default rc=$rc"; chk $rc
-timeout -k 10 600 python3 bench.py --steps 20 --warmup 5 --shard-of 8 --no-cpu > $O/bench_cfg2.json 2> $O/bench_cfg2.log; rc=$?; echo "bench cfg2 + shard rc=$rc"; chk $rc
-timeout -k 10 300 python3 bench.py --config 1 --steps 20 --warmup 2 > $O/bench_cfg1.json 2> $O/bench_cfg1.log; rc=$?; echo "bench cfg1 rc=$rc"; chk $rc
-timeout -k 10 300 python3 bench.py --config 4 --steps 10 --warmup 2 > $O/bench_cfg4.json 2> $O/bench_cfg4.log; rc=$?; echo "bench cfg4 rc=$rc"; chk $rc
+timeout -k 10 600 python3 bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.log; rc=$?; echo "bench default rc=$rc"; chk $rc
+timeout -k 10 600 python3 bench.py --full --steps 20 --warmup 5 --shard-of 8 --no-cpu > $O/bench_cfg2.json 2> $O/bench_cfg2.log; rc=$?; echo "bench cfg2 + shard rc=$rc"; chk $rc
+timeout -k 10 300 python3 bench.py --full --config 1 --steps 20 --warmup 2 > $O/bench_cfg1.json 2> $O/bench_cfg1.log; rc=$?; echo "bench cfg1 rc=$rc"; chk $rc
+timeout -k 10 300 python3 bench.py --full --config 4 --steps 10 --warmup 2 > $O/bench_cfg4.json 2> $O/bench_cfg4.log; rc=$?; echo "bench cfg4 rc=$rc"; chk $rc
 # rocprofv3 kernel traces of the same commands; the headline ALONE (--no-extra-configs) and the driver's command
-timeout -k 10 300 $P --stats -d $O/prof_cfg2 -- python3 bench.py --steps 20 --warmup 2 --no-cpu --no-extra-configs > /dev/null 2> $O/prof_cfg2.log; rc=$?; echo "prof cfg2 rc=$rc"; chk $rc
-timeout -k 10 400 $P --stats -d $O/prof_default -- python3 bench.py --steps 20 --warmup 2 --no-cpu > /dev/null 2> $O/prof_default.log; rc=$?; echo "prof default rc=$rc"; chk $rc
-timeout -k 10 300 $P --stats -d $O/prof_cfg1 -- python3 bench.py --config 1 --steps 20 --warmup 2 --no-cpu > /dev/null 2> $O/prof_cfg1.log; rc=$?; echo "prof cfg1 rc=$rc"; chk $rc
+timeout -k 10 300 $P --stats -d $O/prof_cfg2 -- python3 bench.py --full --steps 20 --warmup 2 --no-cpu --no-extra-configs > /dev/null 2> $O/prof_cfg2.log; rc=$?; echo "prof cfg2 rc=$rc"; chk $rc
+timeout -k 10 400 $P --stats -d $O/prof_default -- python3 bench.py --full --steps 20 --warmup 2 --no-cpu > /dev/null 2> $O/prof_default.log; rc=$?; echo "prof default rc=$rc"; chk $rc
+timeout -k 10 300 $P --stats -d $O/prof_cfg1 -- python3 bench.py --full --config 1 --steps 20 --warmup 2 --no-cpu > /dev/null 2> $O/prof_cfg1.log; rc=$?; echo "prof cfg1 rc=$rc"; chk $rc
 timeout -k 10 300 $P --stats -d $O/prof_shard -- python3 tools/run_kernels.py fwd 128 4096 20 262144 > /dev/null 2> $O/prof_shard.log; rc=$?; echo "prof shard rc=$rc"; chk $rc
-timeout -k 10 300 $P --stats -d $O/prof_cfg4 -- python3 bench.py --config 4 --steps 30 --warmup 2 --no-cpu --grad-route allocator > /dev/null 2> $O/prof_cfg4.log; rc=$?; echo "prof cfg4 rc=$rc"; chk $rc
-timeout -k 10 300 $P --stats -d $O/prof_cfg4_ws -- python3 bench.py --config 4 --steps 30 --warmup 2 --no-cpu --grad-route workspace > /dev/null 2> $O/prof_cfg4_ws.log; rc=$?; echo "prof cfg4 ws rc=$rc"; chk $rc
+timeout -k 10 300 $P --stats -d $O/prof_cfg4 -- python3 bench.py --full --config 4 --steps 30 --warmup 2 --no-cpu --grad-route allocator > /dev/null 2> $O/prof_cfg4.log; rc=$?; echo "prof cfg4 rc=$rc"; chk $rc
+timeout -k 10 300 $P --stats -d $O/prof_cfg4_ws -- python3 bench.py --full --config 4 --steps 30 --warmup 2 --no-cpu --grad-route workspace > /dev/null 2> $O/prof_cfg4_ws.log; rc=$?; echo "prof cfg4 ws rc=$rc"; chk $rc
 timeout -k 10 300 $P --stats -d $O/prof_f64 -- python3 tools/run_kernels.py grad64 64 1024 10 > /dev/null 2> $O/prof_f64.log; rc=$?; echo "prof f64 rc=$rc"; chk $rc
 timeout -k 10 300 $P --stats -d $O/prof_f64fwd -- python3 tools/run_kernels.py fwd64 64 1024 10 > /dev/null 2> $O/prof_f64fwd.log; rc=$?; echo "prof f64 fwd rc=$rc"; chk $rc
 # PMC traffic, separate passes
