@@ -52,8 +52,8 @@ extern "C" {
  *      mrphy_rfgr2beff_bwd returns MRPHY_EINVAL for nC >= 2 without a b1 map; under codes 3 / 4 the
  *      adjoint entry points (blochsim_bwd, blochsim_rfgr_*bwd, beff2ab_bwd) carry the adjoint state
  *      with the compensated update as well (round 3) -- same arguments, different (better) bits.
- *      No environment variable changes what the shipped library runs (the development knobs of
- *      rounds 1-2 exist only in the -DMRPHY_DEV_KNOBS build of tools/).
+ *      No environment variable changes what the library runs (the development knobs of rounds 1-6
+ *      lived in a separate development build, since retired).
  *   3  round 4: mrphy_freeprec_bwd_consts and mrphy_beff2ab_bwd_consts (gradients w.r.t. the constants that the
  *      reference's autograd supplies through slowsims.freeprec and beffective.beff2ab); the gamma*2*pi*dt column of
  *      mrphy_blochsim_bwd_consts is finite for spins with gamma*2*pi*dt == 0 (it was 0/0); nothing else changed.

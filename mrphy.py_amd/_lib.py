@@ -186,10 +186,10 @@ def kernel_count(path: str) -> int:
         return len(set(re.findall(rb'[\x20-\x7e]{4,}\.kd\x00', f.read())))
 
 
-def build_library(out: str, objdir: str, extra=(), force: bool = False, verbose: bool = False,
-                  jobs: int = None) -> dict:
+def build_library(out: str, objdir: str, force: bool = False, verbose: bool = False, jobs: int = None) -> dict:
     r"""Compile the stale units in parallel (one hipcc process each) and link ``out``.  An object is stale if
-    it is missing or its stamp (command line + content hashes of its sources, ``_stamp``) no longer matches.  Returns
+    it is missing or its stamp (command line + content hashes of its sources, ``_stamp``) no longer matches.
+    ``jobs`` defaults to ``MAX_JOBS`` if set, else to the CPU count capped at 16.  Returns
     ``{'compiled': n, 'seconds': wall, 'units': {object name: seconds}}``."""
     import concurrent.futures
     import time
@@ -197,7 +197,7 @@ def build_library(out: str, objdir: str, extra=(), force: bool = False, verbose:
     todo, objs = [], []
     for src, mask in UNITS:
         obj = unit_object(objdir, src, mask)
-        cmd = unit_command(src, mask, obj, extra)
+        cmd = unit_command(src, mask, obj)
         objs.append(obj)
         tag = ' '.join(os.path.relpath(c, _HERE) if os.path.isabs(c) else c for c in cmd[1:])
         try:
@@ -222,7 +222,8 @@ def build_library(out: str, objdir: str, extra=(), force: bool = False, verbose:
         times[os.path.basename(obj)] = round(time.time() - t, 1)
 
     if todo:
-        with concurrent.futures.ThreadPoolExecutor(max_workers=jobs or max(1, os.cpu_count() or 1)) as ex:
+        jobs = jobs or int(os.environ.get('MAX_JOBS') or 0) or min(os.cpu_count() or 1, 16)
+        with concurrent.futures.ThreadPoolExecutor(max_workers=max(1, jobs)) as ex:
             list(ex.map(run, todo))
     # The link has a stamp of its own: the objects' stamps, in link order.  A link that failed or was killed after the
     # objects were stamped, or a unit dropped from UNITS, leaves it stale although no object is.

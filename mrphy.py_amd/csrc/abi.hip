@@ -2,13 +2,6 @@
 // dtype code to the launchers of the tu_*.hip units (internal.hpp).  No kernel is defined here.
 #include "host_common.hpp"
 
-#ifdef MRPHY_DEV_KNOBS
-namespace mrphy_i {
-unsigned long long* g_dev_stamps = nullptr;        // 4 x uint64 per workgroup, or null
-int64_t g_dev_stamps_cap = 0;                      // workgroups the buffer holds
-}
-#endif
-
 using namespace mrphy_i;
 
 namespace {
@@ -47,17 +40,6 @@ int make_hist_parts(int dtype, void* const* parts, int64_t n_parts, int layout, 
 extern "C" {
 
 int mrphy_abi_version(void) { return MRPHY_ABI_VERSION; }
-
-#ifdef MRPHY_DEV_KNOBS
-// dev build only: device buffer of 4 x uint64 per workgroup that the line kernels (K1, K1h, K3) fill
-// with start / end / HW_ID / blockIdx; `cap` = workgroups it holds; null turns stamping off.
-int mrphy_dev_set_stamps(void* buf, int64_t cap)
-{
-    g_dev_stamps = (unsigned long long*)buf;
-    g_dev_stamps_cap = buf ? cap : 0;
-    return 0;
-}
-#endif
 
 const char* mrphy_arch(void) { return "gfx950"; }
 
@@ -110,18 +92,10 @@ size_t mrphy_rfgr2beff_bwd_workspace(int dtype, int64_t N, int64_t nM, int64_t n
     // -- grad_gr's three rows and a re and an im row per coil -- followed by the packed coefficient rows of
     // the SGPR pass, (2 MC + 4) per spin for the padded coil count MC the launcher picks (the query cannot see
     // whether a b1 map will be passed; mrphy_rfgr2beff_bwd rejects nC >= 2 without one).  More coils: the
-    // generic passes, (3 + 2 nC) x nT.  (The dev build also carries round 2's element-per-thread pass:
-    // 2 MC sums x 3 nT per spin group.)
-    const int cap = bwd_capacity(nC, true);
-    if (cap) {
-        size_t need = bwd_pack_offset(tsize(dtype), N, nM, nT, nC) +
-                      (size_t)(N * nM * (2 * bwd_padded_coils(nC, true) + 4)) * tsize(dtype);
-#ifdef MRPHY_DEV_KNOBS
-        const size_t old_pass = (size_t)(bwd_spin_groups(nM) * N * (3 * 2 * cap) * nT) * tsize(dtype);
-        if (old_pass > need) need = old_pass;
-#endif
-        return need;
-    }
+    // generic passes, (3 + 2 nC) x nT.
+    if (bwd_capacity(nC, true))
+        return bwd_pack_offset(tsize(dtype), N, nM, nT, nC) +
+               (size_t)(N * nM * (2 * bwd_padded_coils(nC, true) + 4)) * tsize(dtype);
     const int64_t rows = (nC == 1) ? 9 : (3 + 2 * nC);
     return (size_t)(bwd_spin_groups(nM) * N * rows * nT) * tsize(dtype);
 }

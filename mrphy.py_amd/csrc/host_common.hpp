@@ -6,7 +6,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
-#include <stdlib.h>
 #include <type_traits>
 
 #include "../../include/mrphy_hip.h"
@@ -39,46 +38,6 @@ inline size_t csize(int dtype) { return (dtype == MRPHY_F32 || dtype == MRPHY_F3
 // kernels was tried too: the call's register convention spilled the HOT path (fused K2 0.78 -> 2.58 ms).
 template <typename T> constexpr int TC_FWD = sizeof(T) == 8 ? 8 : 16;
 template <typename T> constexpr int TC_BWD = 16;
-
-// Development knobs exist only in the -DMRPHY_DEV_KNOBS build (tools/build_dev.py ->
-// tools/libmrphy_hip_dev.so): environment variables that select alternative builds / block orders
-// for A/B measurements (re-read at every launch, so one process can sweep them), and a
-// per-workgroup time-stamp buffer.  The shipped library reads no
-// environment variable and instantiates none of the alternatives.
-#ifdef MRPHY_DEV_KNOBS
-inline int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-// MRPHY_K0_VARIANT = order*1000 + rows_per_block/8*10 + nt
-inline int k0_variant() { return env_int("MRPHY_K0_VARIANT", 0); }
-// MRPHY_BWD_VARIANT = waves per SIMD the K3 build is bounded for (2, 3, 4)
-inline int bwd_variant() { return env_int("MRPHY_BWD_VARIANT", 0); }
-// MRPHY_XCD_SWEEP=0 turns the XCD-contiguous tile order of the line kernels off
-inline bool xcd_sweep() { return env_int("MRPHY_XCD_SWEEP", 1) != 0; }
-// MRPHY_K1_XCD=0|1: XCD-contiguous tile order for the no-history K1 as well (each XCD reads the eighth of Beff
-// that the same XCD slot of K0 wrote)
-inline int k1_xcd(int dflt) { return env_int("MRPHY_K1_XCD", dflt); }      // 0 off, 1 forward, 2 reversed
-// MRPHY_FWD_VARIANT = OCC*100 + SPLIT*10 + NT selects an alternative K1 build
-inline int fwd_variant() { return env_int("MRPHY_FWD_VARIANT", 0); }
-// MRPHY_K0_STEPS=0: multi-coil rfgr2beff on the element-per-thread builds instead of k_rfgr2beff_steps
-inline bool k0_steps() { return env_int("MRPHY_K0_STEPS", 1) != 0; }
-// MRPHY_K0_PK=0: exact coil counts on k_rfgr2beff_steps instead of the packed-scalar kernel k_rfgr2beff_pk
-inline bool k0_pk() { return env_int("MRPHY_K0_PK", 1) != 0; }
-// MRPHY_K0ADJ_TP: alternative multi-coil K0 adjoints (1|2|4: DPP pass, 0: element-per-thread pass, 12: SGPR pass, TP = 2)
-inline int k0adj_tp() { return env_int("MRPHY_K0ADJ_TP", -1); }
-// MRPHY_PRIO_ROT=N (re-read at every launch): rotate s_setprio with progress in the line kernels
-inline int prio_rot() { return env_int("MRPHY_PRIO_ROT", 0); }
-// MRPHY_LDS_PAD=bytes of dynamic LDS added to the line kernels' launches: caps the workgroups per CU
-// (160 KB / (9216 + pad)) without touching the code -- occupancy experiments
-inline unsigned lds_pad() { return (unsigned)env_int("MRPHY_LDS_PAD", 0); }
-#else
-constexpr int k0_variant() { return 0; }
-constexpr int bwd_variant() { return 0; }
-constexpr bool xcd_sweep() { return true; }
-constexpr int fwd_variant() { return 0; }
-constexpr int k1_xcd(int dflt) { return dflt; }
-constexpr bool k0_steps() { return true; }
-constexpr bool k0_pk() { return true; }
-constexpr unsigned lds_pad() { return 0; }
-#endif
 
 inline int check_common(int dtype, int64_t N, int64_t nM, int64_t nT)
 {

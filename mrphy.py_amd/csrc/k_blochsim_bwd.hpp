@@ -19,7 +19,6 @@ struct BwdArgs {
     int vec_ok;
     unsigned per_xcd;
     T* gC;                 // (rows, 4) [dL/dg, dL/dE1, dL/dE2, dL/dE1m1] per spin, or null (GC builds)
-    MRPHY_STAMP_FIELD
 };
 
 // GC: also accumulate the gradients w.r.t. the per-spin constants (adj_const_accumulate) into a.gC.
@@ -200,8 +199,8 @@ __device__ __forceinline__ void lines_adj_carry(const SpinConst<T, CT>& k, T b0,
     if (PIN) pin_state(hx, hy, hz);
 }
 
-template <typename CT, bool RELAX, int OCC, bool NT, bool PIN = false>
-__global__ __launch_bounds__(WAVE, OCC) void k_bloch_bwd_lines(BwdArgs<float> a)
+template <typename CT, bool RELAX>
+__global__ __launch_bounds__(WAVE, 3) void k_bloch_bwd_lines(BwdArgs<float> a)
 {
     using T = float;
     constexpr int PF = 32;
@@ -211,7 +210,6 @@ __global__ __launch_bounds__(WAVE, OCC) void k_bloch_bwd_lines(BwdArgs<float> a)
     const int lane = threadIdx.x;
     const int64_t tile_id = xcd_tile(a.per_xcd);
     if (tile_id * WAVE >= a.rows) return;
-    MRPHY_STAMP_BEGIN()
     const int64_t row0 = tile_id * WAVE;
     const int64_t r = row0 + lane;
     const bool valid = r < a.rows;
@@ -245,7 +243,7 @@ __global__ __launch_bounds__(WAVE, OCC) void k_bloch_bwd_lines(BwdArgs<float> a)
 #define MRPHY_FETCH(p)                                                                     \
     { unsigned o0 = off0; asm volatile("" : "+v"(o0));                                     \
     _Pragma("unroll") for (int i = 0; i < 8; ++i)                                          \
-        st[i] = ldv<NT>(reinterpret_cast<const f32x4*>(                                     \
+        st[i] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(                 \
             reinterpret_cast<const char*>(base + (p) * PF) + MRPHY_OFF(i))); }
 #define MRPHY_STAGE()                                                                      \
     __syncthreads();                                                                       \
@@ -268,16 +266,14 @@ __global__ __launch_bounds__(WAVE, OCC) void k_bloch_bwd_lines(BwdArgs<float> a)
     //   piece p  : [7,3] [4,3] [0,4]
     // H0/H1 alternate: each batch issues the history loads of the NEXT one before it computes.
     // First in a turn the order is: stage, next batch's history, next piece's Beff, compute.
-#define LA(NA_, Q_, H_) lines_adj<RELAX, PIN, CT, NA_>(k, my_ + (Q_), H_, hx, hy, hz)
+#define LA(NA_, Q_, H_) lines_adj<RELAX, false, CT, NA_>(k, my_ + (Q_), H_, hx, hy, hz)
     HistBatch H0, H1;
     if (npieces > 0) {
         MRPHY_FETCH(npieces - 1)
         hist_fetch<3, float>(hp, (npieces / 3 - 1) * 32 + 29, H0);
     }
-    MRPHY_PRIO_INIT(a)
     for (int64_t p = npieces - 3; p >= 0; p -= 3) {
         const int64_t t0 = (p / 3) * 32;
-        MRPHY_PRIO_TICK(a, p / 3)
         T g0, g1, g2;
         // ---- piece p+2: floats 64..95 of the period.  steps 31..22 (from float 2), then the
         //      straddling step 21 = (tail float 63 | floats 0, 1)
@@ -289,7 +285,7 @@ __global__ __launch_bounds__(WAVE, OCC) void k_bloch_bwd_lines(BwdArgs<float> a)
         hist_fetch<4, float>(hp, t0 + 21, H0);
         LA(4, 11, H1);
         hist_fetch<3, float>(hp, t0 + 18, H1);
-        lines_adj_carry<RELAX, PIN, CT, 3>(k, tl63, my_[0], my_[1], my_ + 2, H0, hx, hy, hz, g0, g1, g2);
+        lines_adj_carry<RELAX, false, CT, 3>(k, tl63, my_[0], my_[1], my_ + 2, H0, hx, hy, hz, g0, g1, g2);
         my_[0] = g1; my_[1] = g2;
         T cg31 = g0;                                       // -> float 31 of piece p+1
         MRPHY_STORE(p + 2)
@@ -304,7 +300,7 @@ __global__ __launch_bounds__(WAVE, OCC) void k_bloch_bwd_lines(BwdArgs<float> a)
         hist_fetch<4, float>(hp, t0 + 10, H1);
         LA(4, 10, H0);
         hist_fetch<3, float>(hp, t0 + 7, H0);
-        lines_adj_carry<RELAX, PIN, CT, 3>(k, tl30, tl31, my_[0], my_ + 1, H1, hx, hy, hz, g0, g1, g2);
+        lines_adj_carry<RELAX, false, CT, 3>(k, tl30, tl31, my_[0], my_ + 1, H1, hx, hy, hz, g0, g1, g2);
         my_[0] = g2;
         MRPHY_STORE(p + 1)
         // ---- piece p: floats 0..31.  floats 30, 31 <- carried gradient of step 10; steps 9..0
@@ -327,7 +323,6 @@ __global__ __launch_bounds__(WAVE, OCC) void k_bloch_bwd_lines(BwdArgs<float> a)
 #undef LA
     adj_end<RELAX, T, CT>(k, hx, hy, hz);
     if (valid && a.gMi) { a.gMi[r * 3] = hx; a.gMi[r * 3 + 1] = hy; a.gMi[r * 3 + 2] = hz; }
-    MRPHY_STAMP_END(a, tile_id)
 }
 
 
@@ -344,8 +339,8 @@ __global__ __launch_bounds__(WAVE, OCC) void k_bloch_bwd_lines(BwdArgs<float> a)
 // batch ahead, as in the fp32 kernel: 244-248 VGPRs, two waves per SIMD, no scratch (the chunked fp64 adjoint:
 // 430-456 VGPRs, one wave).
 // =============================================================================================
-template <typename CT, bool RELAX, int OCC, bool NT, bool PIN>
-__global__ __launch_bounds__(WAVE, OCC) void k_bloch_bwd_lines_f64(BwdArgs<double> a)
+template <typename CT, bool RELAX>
+__global__ __launch_bounds__(WAVE, 2) void k_bloch_bwd_lines_f64(BwdArgs<double> a)
 {
     using T = double;
     constexpr int PF = 16;
@@ -384,7 +379,7 @@ __global__ __launch_bounds__(WAVE, OCC) void k_bloch_bwd_lines_f64(BwdArgs<doubl
 #define MRPHY_FETCH(p)                                                                     \
     { unsigned o0 = off0; asm volatile("" : "+v"(o0));                                     \
     _Pragma("unroll") for (int i = 0; i < 8; ++i)                                          \
-        st[i] = ldv<NT>(reinterpret_cast<const f64x2*>(                                     \
+        st[i] = __builtin_nontemporal_load(reinterpret_cast<const f64x2*>(                 \
             reinterpret_cast<const char*>(base + (p) * PF) + MRPHY_OFF(i))); }
 #define MRPHY_STAGE()                                                                      \
     __syncthreads();                                                                       \
@@ -402,9 +397,7 @@ __global__ __launch_bounds__(WAVE, OCC) void k_bloch_bwd_lines_f64(BwdArgs<doubl
                     reinterpret_cast<char*>(obase + (p) * PF) + MRPHY_OFF(i)));            \
         }                                                                                  \
     }
-    // Batches of a 16-step period in processing order, steps [first, count]:
-    //   piece p+2: [13,3] [10,3: carry 10 + 11, 12]   piece p+1: [8,2] [5,3: carry 5 + 6, 7]   piece p: [3,2] [0,3]
-#define LA(NA_, Q_, H_) lines_adj<RELAX, PIN, CT, NA_, T>(k, my_ + (Q_), H_, hx, hy, hz)
+#define LA(NA_, Q_, H_) lines_adj<RELAX, true, CT, NA_, T>(k, my_ + (Q_), H_, hx, hy, hz)
     // Batches of at most two steps, processing order, steps [first, count]:
     //   piece p+2: [14,2] [12,2] [10,2: carry 10 + 11]   piece p+1: [8,2] [7,1] [5,2: carry 5 + 6]   piece p: [3,2] [1,2] [0,1]
     HistBatchT<T> H0, H1;
@@ -424,7 +417,7 @@ __global__ __launch_bounds__(WAVE, OCC) void k_bloch_bwd_lines_f64(BwdArgs<doubl
         hist_fetch<2, T>(hp, t0 + 10, H0);
         LA(2, 4, H1);                                      // steps 12, 13
         hist_fetch<2, T>(hp, t0 + 8, H1);
-        lines_adj_carry<RELAX, PIN, CT, 1, T>(k, tl14, tl15, my_[0], my_ + 1, H0, hx, hy, hz, g0, g1, g2);
+        lines_adj_carry<RELAX, true, CT, 1, T>(k, tl14, tl15, my_[0], my_ + 1, H0, hx, hy, hz, g0, g1, g2);
         my_[0] = g2;
         const T cg14 = g0, cg15 = g1;
         MRPHY_STORE(p + 2)
@@ -438,7 +431,7 @@ __global__ __launch_bounds__(WAVE, OCC) void k_bloch_bwd_lines_f64(BwdArgs<doubl
         hist_fetch<2, T>(hp, t0 + 5, H1);
         LA(1, 5, H0);                                      // step 7
         hist_fetch<2, T>(hp, t0 + 3, H0);
-        lines_adj_carry<RELAX, PIN, CT, 1, T>(k, tp15, my_[0], my_[1], my_ + 2, H1, hx, hy, hz, g0, g1, g2);
+        lines_adj_carry<RELAX, true, CT, 1, T>(k, tp15, my_[0], my_[1], my_ + 2, H1, hx, hy, hz, g0, g1, g2);
         my_[0] = g1; my_[1] = g2;
         const T cgp15 = g0;
         MRPHY_STORE(p + 1)

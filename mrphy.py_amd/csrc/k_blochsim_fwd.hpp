@@ -18,7 +18,6 @@ struct FwdArgs {
     int vec_ok;
     unsigned per_xcd;      // line kernels: > 0 -> block b works on spin tile (b % 8) * per_xcd + b / 8
     int xcd_rev;           // ... or on (b % 8) * per_xcd + per_xcd - 1 - b / 8: each XCD walks its eighth from the end
-    MRPHY_STAMP_FIELD
 };
 
 template <typename T, typename CT, int TC, bool SAVE>
@@ -144,12 +143,12 @@ __device__ __forceinline__ void lines_steps_carry(const SpinConst<T, CT>& k, T b
     if (PIN) pin_state(mx, my, mz);
 }
 
-// OCC: waves per SIMD the register allocation is bounded for.  SPLIT: sub-batches per piece
-// (2: 5/6 steps prepared at once, 3: 3/4 steps -- fewer live registers).  NT: non-temporal loads.
+// Bounded for 3 waves per SIMD.  SPLIT: sub-batches per piece (2: 5/6 steps prepared at once, 3: 3/4 steps --
+// fewer live registers).
 // (Tried: three pieces in flight per wave instead of one -- 96 prefetch VGPRs, 2 waves/SIMD -- no
 // gain at any grid size.)
-template <typename CT, bool RELAX, int OCC, int SPLIT, bool NT, bool SAVE, bool PIN = false>
-__global__ __launch_bounds__(WAVE, OCC) void k_bloch_fwd_lines(FwdArgs<float> a)
+template <typename CT, bool RELAX, int SPLIT, bool SAVE, bool PIN>
+__global__ __launch_bounds__(WAVE, 3) void k_bloch_fwd_lines(FwdArgs<float> a)
 {
     using T = float;
     constexpr int PF = 32;                 // floats per piece = one 128-B line
@@ -159,7 +158,6 @@ __global__ __launch_bounds__(WAVE, OCC) void k_bloch_fwd_lines(FwdArgs<float> a)
     const int lane = threadIdx.x;
     const int64_t tile_id = xcd_tile(a.per_xcd, a.xcd_rev != 0);
     if (tile_id * WAVE >= a.rows) return;
-    MRPHY_STAMP_BEGIN()
     const int64_t row0 = tile_id * WAVE;
     const int64_t r = row0 + lane;
     const bool valid = r < a.rows;
@@ -190,7 +188,7 @@ __global__ __launch_bounds__(WAVE, OCC) void k_bloch_fwd_lines(FwdArgs<float> a)
 #define MRPHY_FETCH(S, p)                                                                  \
     { unsigned o0 = off0; asm volatile("" : "+v"(o0));                                     \
     _Pragma("unroll") for (int i = 0; i < 8; ++i)                                          \
-        S[i] = ldv<NT>(reinterpret_cast<const f32x4*>(                                      \
+        S[i] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(                  \
             reinterpret_cast<const char*>(base + (p) * PF) + MRPHY_OFF(i))); }
 #define MRPHY_STAGE(S)                                                                     \
     __syncthreads();                                                                       \
@@ -204,31 +202,26 @@ __global__ __launch_bounds__(WAVE, OCC) void k_bloch_fwd_lines(FwdArgs<float> a)
     lines_steps_carry<RELAX, SAVE, PIN, CT, NA_>(k, B0_, B1_, B2_, my_ + (Q_), hp, t0 + (TH_), mx, my, mz)
     if (npieces > 0) { MRPHY_FETCH(st0, 0) }
     T c0, c1;
-    MRPHY_PRIO_INIT(a)
     for (int64_t p = 0; p < npieces; p += 3) {
         const int64_t t0 = (p / 3) * 32;
-        MRPHY_PRIO_TICK(a, p / 3)
         const bool more = p + 3 < npieces;
         // piece 0: steps 0..9 (floats 0..29), carry floats 30, 31
         MRPHY_STAGE(st0)
         MRPHY_FETCH(st0, p + 1)
-        if (SPLIT == 2)      { LS(5, 0, 0); LS(5, 15, 5); }
-        else if (SPLIT == 3) { LS(4, 0, 0); LS(3, 12, 4); LS(3, 21, 7); }
-        else                 { LS(3, 0, 0); LS(3, 9, 3); LS(2, 18, 6); LS(2, 24, 8); }
+        if (SPLIT == 2) { LS(5, 0, 0); LS(5, 15, 5); }
+        else            { LS(4, 0, 0); LS(3, 12, 4); LS(3, 21, 7); }
         c0 = my_[30]; c1 = my_[31];
         // piece 1: step 10 = (c0, c1, f0); steps 11..20 from float 1; carry float 31
         MRPHY_STAGE(st0)
         MRPHY_FETCH(st0, p + 2)
-        if (SPLIT == 2)      { LC(5, c0, c1, my_[0], 1, 10); LS(5, 16, 16); }
-        else if (SPLIT == 3) { LC(3, c0, c1, my_[0], 1, 10); LS(4, 10, 14); LS(3, 22, 18); }
-        else { LC(2, c0, c1, my_[0], 1, 10); LS(3, 7, 13); LS(3, 16, 16); LS(2, 25, 19); }
+        if (SPLIT == 2) { LC(5, c0, c1, my_[0], 1, 10); LS(5, 16, 16); }
+        else            { LC(3, c0, c1, my_[0], 1, 10); LS(4, 10, 14); LS(3, 22, 18); }
         c0 = my_[31];
         // piece 2: step 21 = (c0, f0, f1); steps 22..31 from float 2
         MRPHY_STAGE(st0)
         if (more) { MRPHY_FETCH(st0, p + 3) }
-        if (SPLIT == 2)      { LC(5, c0, my_[0], my_[1], 2, 21); LS(5, 17, 27); }
-        else if (SPLIT == 3) { LC(3, c0, my_[0], my_[1], 2, 21); LS(4, 11, 25); LS(3, 23, 29); }
-        else { LC(2, c0, my_[0], my_[1], 2, 21); LS(3, 8, 24); LS(3, 17, 27); LS(2, 26, 30); }
+        if (SPLIT == 2) { LC(5, c0, my_[0], my_[1], 2, 21); LS(5, 17, 27); }
+        else            { LC(3, c0, my_[0], my_[1], 2, 21); LS(4, 11, 25); LS(3, 23, 29); }
     }
 #undef LS
 #undef LC
@@ -236,7 +229,6 @@ __global__ __launch_bounds__(WAVE, OCC) void k_bloch_fwd_lines(FwdArgs<float> a)
 #undef MRPHY_STAGE
 #undef MRPHY_OFF
     if (valid) { a.Mo[r * 3] = mx; a.Mo[r * 3 + 1] = my; a.Mo[r * 3 + 2] = mz; }
-    MRPHY_STAMP_END(a, tile_id)
 }
 
 
@@ -253,8 +245,8 @@ __global__ __launch_bounds__(WAVE, OCC) void k_bloch_fwd_lines(FwdArgs<float> a)
 // A wave-load is still 8 rows x one whole line (lane l: row 8i + l/8, 16 B at byte 16 (l % 8)); LDS
 // tile 64 x (16 + 2) doubles = 9 KB, pitch 9 x 16 B (odd: conflict-free row reads).
 // =============================================================================================
-template <typename CT, bool RELAX, int OCC, bool NT, bool SAVE, bool PIN>
-__global__ __launch_bounds__(WAVE, OCC) void k_bloch_fwd_lines_f64(FwdArgs<double> a)
+template <typename CT, bool RELAX, bool SAVE>
+__global__ __launch_bounds__(WAVE, 3) void k_bloch_fwd_lines_f64(FwdArgs<double> a)
 {
     using T = double;
     constexpr int PF = 16;                 // doubles per piece = one 128-B line
@@ -288,7 +280,7 @@ __global__ __launch_bounds__(WAVE, OCC) void k_bloch_fwd_lines_f64(FwdArgs<doubl
 #define MRPHY_FETCH(S, p)                                                                  \
     { unsigned o0 = off0; asm volatile("" : "+v"(o0));                                     \
     _Pragma("unroll") for (int i = 0; i < 8; ++i)                                          \
-        S[i] = ldv<NT>(reinterpret_cast<const f64x2*>(                                      \
+        S[i] = __builtin_nontemporal_load(reinterpret_cast<const f64x2*>(                  \
             reinterpret_cast<const char*>(base + (p) * PF) + MRPHY_OFF(i))); }
 #define MRPHY_STAGE(S)                                                                     \
     __syncthreads();                                                                       \
@@ -297,9 +289,9 @@ __global__ __launch_bounds__(WAVE, OCC) void k_bloch_fwd_lines_f64(FwdArgs<doubl
     __syncthreads();
 
     T* hp = SAVE ? hist_tile_base<T>(a.hist, tile_id, a.nT) + lane : nullptr;
-#define LS(NA_, Q_, TH_) lines_steps<RELAX, SAVE, PIN, CT, NA_, T>(k, my_ + (Q_), hp, t0 + (TH_), mx, my, mz)
+#define LS(NA_, Q_, TH_) lines_steps<RELAX, SAVE, true, CT, NA_, T>(k, my_ + (Q_), hp, t0 + (TH_), mx, my, mz)
 #define LC(NA_, B0_, B1_, B2_, Q_, TH_) \
-    lines_steps_carry<RELAX, SAVE, PIN, CT, NA_, T>(k, B0_, B1_, B2_, my_ + (Q_), hp, t0 + (TH_), mx, my, mz)
+    lines_steps_carry<RELAX, SAVE, true, CT, NA_, T>(k, B0_, B1_, B2_, my_ + (Q_), hp, t0 + (TH_), mx, my, mz)
     if (npieces > 0) { MRPHY_FETCH(st0, 0) }
     T c0, c1;
     for (int64_t p = 0; p < npieces; p += 3) {

@@ -3,42 +3,6 @@
 // Fragment: included INSIDE a translation unit's anonymous namespace, after host_common.hpp (HIP runtime,
 // include/mrphy_hip.h, geom.hpp, bloch_math.hpp, this file first).  Not a standalone header.
 
-
-// -DMRPHY_DEV_KNOBS build only (tools/): per-workgroup time stamps for the wave timeline of the
-// line kernels.  stamps[4 id + {0, 1, 2, 3}] = start, end (s_memrealtime: 100 MHz), HW_ID | XCC_ID << 32,
-// blockIdx.x.  The shipped library has neither the argument field nor the code.
-#ifdef MRPHY_DEV_KNOBS
-#define MRPHY_STAMP_FIELD unsigned long long* stamps; int prio_rot; int prio_shift;
-#define MRPHY_STAMP_BEGIN() const unsigned long long stamp_t0_ = __builtin_amdgcn_s_memrealtime();
-#define MRPHY_STAMP_END(a_, id_)                                                                  \
-    if ((a_).stamps && (threadIdx.x & 63) == 0) {                                                 \
-        unsigned long long* q_ = (a_).stamps + 4 * (id_);                                          \
-        q_[0] = stamp_t0_;                                                                         \
-        q_[1] = __builtin_amdgcn_s_memrealtime();                                                  \
-        q_[2] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) |                    \
-                ((unsigned long long)(__builtin_amdgcn_s_getreg((3 << 11) | 20) & 0xf) << 32);     \
-        q_[3] = blockIdx.x;                                                                        \
-    }
-// experiment: rotate the wave's issue priority with its progress, (period + wave slot on the SIMD) & 3,
-// so that the waves sharing a SIMD advance at the same average rate (the arbiter prefers the oldest)
-#define MRPHY_PRIO_INIT(a_) const unsigned prio_slot_ = (a_).prio_rot == 1 ? (__builtin_amdgcn_s_getreg((3 << 11) | 4) & 0xfu) : 0u;
-#define MRPHY_PRIO_TICK(a_, period_)                                                             \
-    if ((a_).prio_rot) {                                                                          \
-        switch ((prio_slot_ + (unsigned)(period_)) & 3u) {                                        \
-        case 0: __builtin_amdgcn_s_setprio(0); break;                                             \
-        case 1: __builtin_amdgcn_s_setprio(1); break;                                             \
-        case 2: __builtin_amdgcn_s_setprio(2); break;                                             \
-        default: __builtin_amdgcn_s_setprio(3); break;                                            \
-        }                                                                                         \
-    }
-#else
-#define MRPHY_STAMP_FIELD
-#define MRPHY_STAMP_BEGIN()
-#define MRPHY_STAMP_END(a_, id_)
-#define MRPHY_PRIO_INIT(a_)
-#define MRPHY_PRIO_TICK(a_, period_)
-#endif
-
 // (Bc, the broadcastable per-spin constant of mrphy_hip.h, is in geom.hpp)
 #define MRPHY_XCD_SLOT(b_) ((b_) & 7u)
 
@@ -208,20 +172,6 @@ __device__ __forceinline__ int64_t xcd_tile(unsigned per_xcd, bool reversed = fa
     return (int64_t)MRPHY_XCD_SLOT(blockIdx.x) * per_xcd + (reversed ? per_xcd - 1 - k : k);
 }
 
-template <bool NT>
-__device__ __forceinline__ f32x4 ldv(const f32x4* p)
-{
-    if (NT) return __builtin_nontemporal_load(p);
-    return *p;
-}
-
-template <bool NT>
-__device__ __forceinline__ f64x2 ldv(const f64x2* p)
-{
-    if (NT) return __builtin_nontemporal_load(p);
-    return *p;
-}
-
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef f32x2 f32x2_u __attribute__((aligned(4)));
 
@@ -232,31 +182,20 @@ typedef f32x2 f32x2_u __attribute__((aligned(4)));
 // 8 GB): with plain or nt stores its eight XCD streams end with their last 32 MB each resident and dirty there, and
 // the K1 that follows pays for their eviction -- 0.59 instead of 0.78 of HBM peak at 64^3 x 1024, 0.68 instead of
 // 0.82 on a 1/8 shard (tools/k0var_step_ab.py, profiles/r04_k0_store_policy.json).  The encoding has no builtin
-// (__builtin_nontemporal_store gives `nt` alone; scoped atomics are 4 bytes wide): one inline instruction per width.
+// (__builtin_nontemporal_store gives `nt` alone; scoped atomics are 4 bytes wide): an inline instruction.
 // ---------------------------------------------------------------------------------------------
-// Only 16-B stores take the write-through encodings: a narrower `sc1` store is one fabric write each (the guide: dwordx2 2.7 x,
+// Only 16-B stores take the write-through encoding: a narrower `sc1` store is one fabric write each (the guide: dwordx2 2.7 x,
 // dword ~6 x the dwordx4 time per byte; measured here: the 8-coil K0 with 8-B `sc1 nt` stores 0.74 -> 4.7 ms at 64^3 x 1024),
 // so 4- and 8-B stores fall back to the plain `nt` hint whatever the policy says.
 // The instruction is invisible to LLVM's hazard recogniser: gfx940+ wants two wait states between a VMEM store of more than 64 bits
 // and a VALU write of its data VGPRs.  The `s_nop 1` that follows it inside the same asm statement supplies them wherever the
 // statement is inlined (round 4 was safe only because a branch happened to follow every such store: ADVICE r4).
-#define MRPHY_STORE_ASM(BITS)                                                                                         \
-    do {                                                                                                          \
-        if constexpr (sizeof(V) == 16)      asm volatile("global_store_dwordx4 %0, %1, off " BITS "\n\ts_nop 1" : : "v"(dst), "v"(v) : "memory"); \
-        else __builtin_nontemporal_store(v, dst);                                                                 \
-    } while (0)
 template <typename V>
 __device__ __forceinline__ void store_pol(V* dst, const V v, int pol)
 {
     if (pol == 2) {
-        MRPHY_STORE_ASM("sc1 nt");
-#ifdef MRPHY_DEV_KNOBS
-    } else if (pol == 3) { MRPHY_STORE_ASM("sc1");
-    } else if (pol == 4) { MRPHY_STORE_ASM("sc0 sc1");
-    } else if (pol == 5) { MRPHY_STORE_ASM("sc0 sc1 nt");
-    } else if (pol == 6) { MRPHY_STORE_ASM("sc0 nt");
-    } else if (pol == 7) { MRPHY_STORE_ASM("sc0");
-#endif
+        if constexpr (sizeof(V) == 16) asm volatile("global_store_dwordx4 %0, %1, off sc1 nt\n\ts_nop 1" : : "v"(dst), "v"(v) : "memory");
+        else __builtin_nontemporal_store(v, dst);
     } else if (pol) {
         __builtin_nontemporal_store(v, dst);
     } else {

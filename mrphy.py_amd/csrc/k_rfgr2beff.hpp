@@ -219,8 +219,8 @@ struct K0StepGeom {
     static constexpr int TP = MC <= 32 ? 32 / MC : 1;
     static constexpr int VW = 3 * TP;                // elements per thread
     // rows per block: the thread's 64 rf registers are filled with strided (uncoalesced) loads once per
-    // block, so a block must walk far more rows than the 16 of the single-coil kernel to amortise them
-    // (dev knob MRPHY_K0_VARIANT picks fewer for A/B); LDS: ROWS (2 MC + 4) words <= 34 KB
+    // block, so a block must walk far more rows than the 16 of the single-coil kernel to amortise them;
+    // LDS: ROWS (2 MC + 4) words <= 34 KB
     static constexpr int ROWS = MC <= 32 ? 128 : 64;
 };
 

@@ -34,60 +34,8 @@ int run_rfgr2beff_bwd(const void* gB, const void* loc, const void* b1, void* grf
         hipLaunchKernelGGL((k_rfgr2beff_bwd_p2v<T>), dim3(tx, 1, (unsigned)N), dim3(256), 0, st, a);
         return launch_status();
     }
-    if (const int cap = bwd_capacity(nC, b1 != nullptr)) {   // 2..32 coils: one pass over gB
+    if (bwd_capacity(nC, b1 != nullptr)) {             // 2..32 coils: one pass over gB
         using std::integral_constant;
-        (void)cap;
-#ifdef MRPHY_DEV_KNOBS
-        // A/B baselines of the dev build (MRPHY_K0ADJ_TP): 1 / 2 / 4 = the DPP pass with that many time points
-        // per thread, 0 = round 2's element-per-thread pass, 12 = the SGPR pass with two time points per thread
-        int tp = k0adj_tp();
-        if (tp > nT) tp = 1;                           // the DPP kernel reads TP whole time points per row
-        auto launch_steps = [&](auto mc_tag, auto tp_tag) -> int {
-            constexpr int MC = decltype(mc_tag)::value, TP = decltype(tp_tag)::value;
-            const int64_t per_block = 256 * (int64_t)TP;
-            const dim3 g1((unsigned)((nT + per_block - 1) / per_block), (unsigned)a.nSG, (unsigned)N);
-            hipLaunchKernelGGL((k_rfgr2beff_bwd_steps<T, MC, TP>), g1, dim3(256), 0, st, a);
-            int e = launch_status();
-            if (e) return e;
-            hipLaunchKernelGGL((k_rfgr2beff_bwd_p2<T>), dim3(tx, (unsigned)(3 + 2 * nC), (unsigned)N),
-                               dim3(256), 0, st, a);
-            return launch_status();
-        };
-        switch (cap * 10 + tp) {
-        case 81:  return launch_steps(integral_constant<int, 8>{}, integral_constant<int, 1>{});
-        case 82:  return launch_steps(integral_constant<int, 8>{}, integral_constant<int, 2>{});
-        case 84:  return launch_steps(integral_constant<int, 8>{}, integral_constant<int, 4>{});
-        case 161: return launch_steps(integral_constant<int, 16>{}, integral_constant<int, 1>{});
-        case 162: return launch_steps(integral_constant<int, 16>{}, integral_constant<int, 2>{});
-        case 164: return launch_steps(integral_constant<int, 16>{}, integral_constant<int, 4>{});
-        case 321: return launch_steps(integral_constant<int, 32>{}, integral_constant<int, 1>{});
-        case 322: return launch_steps(integral_constant<int, 32>{}, integral_constant<int, 2>{});
-        default: break;
-        }
-        if (tp == 0) {
-            const int64_t L = 3 * nT;
-            const bool vec = aligned_to(gB, sizeof(T));
-            auto launch = [&](auto mc_tag) -> int {
-                constexpr int MC = decltype(mc_tag)::value;
-                using G = BwdGeom<T, MC>;
-                const int vw = vec ? G::VW : 1;
-                const dim3 g1((unsigned)((L + 256 * (int64_t)vw - 1) / (256 * (int64_t)vw)), (unsigned)a.nSG,
-                              (unsigned)N);
-                if (vec) hipLaunchKernelGGL((k_rfgr2beff_bwd_p1mc<T, G::VW, MC>), g1, dim3(256), 0, st, a);
-                else     hipLaunchKernelGGL((k_rfgr2beff_bwd_p1mc<T, 1, MC>), g1, dim3(256), 0, st, a);
-                int e = launch_status();
-                if (e) return e;
-                hipLaunchKernelGGL((k_rfgr2beff_bwd_p2mc<T, MC>), dim3(tx, (unsigned)(3 + 2 * nC), (unsigned)N),
-                                   dim3(256), 0, st, a);
-                return launch_status();
-            };
-            switch (cap) {
-            case 8:  return launch(integral_constant<int, 8>{});
-            case 16: return launch(integral_constant<int, 16>{});
-            default: return launch(integral_constant<int, 32>{});
-            }
-        }
-#endif
         // The step-per-thread pass with the spins' coefficients in SGPRs: a pre-pass packs b1 and loc,
         // zero-padded to the padded coil count, behind the partial sums in the workspace (bwd_pack_offset:
         // launcher and query agree by construction); the partial sums have the layout of the generic pass 2.
@@ -107,16 +55,8 @@ int run_rfgr2beff_bwd(const void* gB, const void* loc, const void* b1, void* grf
             b.gB = a.gB; b.pk = pk; b.work = a.work; b.N = N; b.nM = nM; b.nT = nT; b.nC = nCb;
             b.spins_per_group = a.spins_per_group;
             b.K = (int)(3 + 2 * nC); b.rowR = (int)(3 + c0); b.rowI = (int)(3 + nC + c0);
-#ifdef MRPHY_DEV_KNOBS
-            if (k0adj_tp() == 12 && nT >= 2) {
-                const dim3 g2((unsigned)((nT + 511) / 512), (unsigned)a.nSG, (unsigned)N);
-                hipLaunchKernelGGL((k_rfgr2beff_bwd_sgpr<T, MC, 2>), g2, dim3(256), 0, st, b);
-            } else
-#endif
-            {
-                const dim3 g1((unsigned)((nT + 255) / 256), (unsigned)a.nSG, (unsigned)N);
-                hipLaunchKernelGGL((k_rfgr2beff_bwd_sgpr<T, MC, 1>), g1, dim3(256), 0, st, b);
-            }
+            const dim3 g1((unsigned)((nT + 255) / 256), (unsigned)a.nSG, (unsigned)N);
+            hipLaunchKernelGGL((k_rfgr2beff_bwd_sgpr<T, MC>), g1, dim3(256), 0, st, b);
             return launch_status();
         };
         auto launch_block = [&](int64_t c0, int64_t nCb) -> int {

@@ -8,7 +8,6 @@ import csv
 import glob
 import json
 import os
-import re
 import shutil
 import subprocess
 import sys
@@ -45,6 +44,15 @@ def _short(name):
     return name.replace('void ', '').replace('(anonymous namespace)::', '').replace('mrphy::', '')
 
 
+def _saves(name):
+    r"""Whether a forward line kernel writes the history (K1h), read from its SAVE template argument: the last but one
+    where a PIN argument follows it (the fp32 kernel, 5 arguments, 7 while it still carried OCC and NT; the fp64 kernel
+    with OCC and NT, 6), the last otherwise (the fp64 kernel, 3; the fp32 kernel before PIN, 6)."""
+    a = name[name.index('<') + 1:-1].split(', ')
+    pin = len(a) == 6 if '_f64' in name else len(a) % 2 == 1
+    return a[-2 if pin else -1] == 'true'
+
+
 # VERDICT r5 item 1: `--stats` averages per kernel NAME, and one process launches K0 / K1 at several problem sizes
 # (bench.py without --config: 128^3 x 4096, 64^3 x 1024, 64^3 x 2048; a workspace probe; warm-ups), so the r05 stats row
 # of K1 averaged three sizes.  Here the kernel trace of the same run is split by (kernel, grid size): calls, mean,
@@ -69,7 +77,7 @@ def by_size(d, dst, workloads, note=''):
             continue
         g = int(r['Grid_Size_X']) if 'Grid_Size_X' in r else int(r['Grid_Size'])
         groups.setdefault((n.split('(')[0], g), []).append((int(r['End_Timestamp']) - int(r['Start_Timestamp'])) / 1e6)
-    fam = lambda n: ('K1h' if n.startswith('k_bloch_fwd_lines') and re.search(r', true, (true|false)>$', n) else  # noqa: E731
+    fam = lambda n: ('K1h' if n.startswith('k_bloch_fwd_lines') and _saves(n) else  # noqa: E731
                      'K1' if n.startswith('k_bloch_fwd_lines') else 'K3' if n.startswith('k_bloch_bwd_lines') else
                      'K0' if n.startswith('k_rfgr2beff') and 'bwd' not in n else None)
     out = {'what': 'rocprofv3 --kernel-trace of the command below, launches grouped by (kernel, grid size in work-items); '

@@ -4,7 +4,7 @@ unit objects `mrphy_amd.build()` leaves under mrphy.py_amd/build/ (no recompilat
     python tools/kregs.py [filter] [--scratch] [--objdir DIR]
 
 `--scratch` lists only kernels with a private segment (spills); the exit code is then the number found.
-`--objdir tools/build_dev` reads the development build instead.
+`--objdir DIR` reads the unit objects of another build instead.
 """
 import glob
 import os
