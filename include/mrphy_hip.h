@@ -66,7 +66,9 @@ extern "C" {
  *   5  round 6: the history of the blochsim forward / adjoint may live in 1..8 separately allocated parts
  *      (mrphy_blochsim_hist_part_bytes, mrphy_blochsim_fwd_parts, mrphy_blochsim_bwd_parts); the single-pointer entry
  *      points are the one-part case, unchanged.  RCCL helpers for a ctypes-only multi-GPU consumer
- *      live in a library of their own beside this one (include/mrphy_comm.h, libmrphy_comm.so).  Same bits. */
+ *      live in a library of their own beside this one (include/mrphy_comm.h, libmrphy_comm.so).  Same bits.
+ *      Added later under the same version, changing no existing call: mrphy_blochsim_rfgr_traj_fwd,
+ *      mrphy_blochsim_rfgr_traj_bwd, mrphy_blochsim_rfgr_mc_traj_bwd (the magnetisation trajectory of K2). */
 #define MRPHY_ABI_VERSION 5
 
 #define MRPHY_F32      0  /* T = float,  CT = float                                          */
@@ -481,6 +483,76 @@ int mrphy_blochsim_rfgr_mc_bwd(int dtype,
                                void* work, size_t work_bytes,
                                int64_t N, int64_t nM, int64_t nT, int64_t nC,
                                void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * K2t  trajectory of the fused simulation: K2 that also records M after steps
+ *     e_j = min((j+1) * every, nT) - 1,   j = 0 .. nRec-1,   nRec = ceil(nT / every),
+ * into Mt (nRec, N, nM, 3), time-major (record j is one (N, nM, 3) block: 768 B per wave and record, the
+ * checkpoint layout).  The reference keeps the whole history Mhst (N, *Nd, nT, xyz) in BlochSim.forward and
+ * returns only its last step (sims.py:83,131); every == 1 gives that history, and the last record is always Mo
+ * bit for bit (a record is the state the step loop holds; nothing else changes).
+ * Operands as mrphy_blochsim_rfgr_fwd; Mo may be NULL (it equals record nRec-1).  Mck / ck_every as there
+ * (checkpoints for the adjoint below).  MRPHY_EINVAL: every < 1, Mt NULL, a coil count K2 rejects.
+ * ------------------------------------------------------------------------------------------- */
+int mrphy_blochsim_rfgr_traj_fwd(int dtype,
+                                 const void* Mi,
+                                 const void* rf, int64_t rf_sn,
+                                 const void* gr, int64_t gr_sn,
+                                 const void* loc,
+                                 const void* df, int64_t df_sn, int64_t df_sm,
+                                 const void* gamma, int64_t gamma_sn, int64_t gamma_sm,
+                                 const void* b1,
+                                 const void* g,  int64_t g_sn,  int64_t g_sm,
+                                 const void* E1, int64_t E1_sn, int64_t E1_sm,
+                                 const void* E2, int64_t E2_sn, int64_t E2_sm,
+                                 const void* E1m1,
+                                 void* Mo, void* Mck, int64_t ck_every,
+                                 void* Mt, int64_t every,
+                                 int64_t N, int64_t nM, int64_t nT, int64_t nC,
+                                 void* stream);
+
+/* K2bt  adjoint of K2t: as mrphy_blochsim_rfgr_bwd / mrphy_blochsim_rfgr_mc_bwd, with grad_Mt (nRec, N, nM, 3)
+ * (time-major, as Mt) in place of grad_Mo -- its last record is the cotangent of Mo.  The sweep adds grad_Mt[j]
+ * to the adjoint state as it passes step e_j backwards: what the reference's autograd does with a loss on Mhst
+ * (BlochSim.backward, sims.py:135-269, run once per recorded step).  Same checkpoints (nT a multiple of
+ * mrphy_blochsim_rfgr_ck_every()), same workspace (mrphy_blochsim_rfgr_bwd_workspace /
+ * mrphy_blochsim_rfgr_mc_bwd_workspace), same deterministic reduction.  MRPHY_EINVAL: every < 1, nT not a
+ * whole number of segments, a coil count outside 1 .. mrphy_blochsim_rfgr_mc_max_coils() (mc); MRPHY_ENOSPC:
+ * workspace too small. */
+int mrphy_blochsim_rfgr_traj_bwd(int dtype,
+                                 const void* Mck,
+                                 const void* rf, int64_t rf_sn,
+                                 const void* gr, int64_t gr_sn,
+                                 const void* loc,
+                                 const void* df, int64_t df_sn, int64_t df_sm,
+                                 const void* gamma, int64_t gamma_sn, int64_t gamma_sm,
+                                 const void* b1,
+                                 const void* g,  int64_t g_sn,  int64_t g_sm,
+                                 const void* E1, int64_t E1_sn, int64_t E1_sm,
+                                 const void* E2, int64_t E2_sn, int64_t E2_sm,
+                                 const void* E1m1,
+                                 const void* grad_Mt, int64_t every,
+                                 void* grad_Mi, void* grad_rf, void* grad_gr,
+                                 void* work, size_t work_bytes,
+                                 int64_t N, int64_t nM, int64_t nT,
+                                 void* stream);
+int mrphy_blochsim_rfgr_mc_traj_bwd(int dtype,
+                                    const void* Mck,
+                                    const void* rf, int64_t rf_sn,
+                                    const void* gr, int64_t gr_sn,
+                                    const void* loc,
+                                    const void* df, int64_t df_sn, int64_t df_sm,
+                                    const void* gamma, int64_t gamma_sn, int64_t gamma_sm,
+                                    const void* b1,
+                                    const void* g,  int64_t g_sn,  int64_t g_sm,
+                                    const void* E1, int64_t E1_sn, int64_t E1_sm,
+                                    const void* E2, int64_t E2_sn, int64_t E2_sm,
+                                    const void* E1m1,
+                                    const void* grad_Mt, int64_t every,
+                                    void* grad_Mi, void* grad_rf, void* grad_gr,
+                                    void* work, size_t work_bytes,
+                                    int64_t N, int64_t nM, int64_t nT, int64_t nC,
+                                    void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * the steps either side of the path in SpinArray.applypulse (mobjs.py:427-433,449).

@@ -59,6 +59,13 @@ PROTOTYPES = {
     'mrphy_blochsim_rfgr_mc_bwd_workspace': (_sz, [_int] + [_i64] * 4),
     'mrphy_blochsim_rfgr_mc_bwd': (_int, [_int, _vp, _vp, _i64, _vp, _i64, _vp] + _BC + _BC + [_vp]
                                    + _BC * 3 + [_vp, _vp, _vp, _vp, _vp, _vp, _sz] + [_i64] * 4 + [_vp]),
+    'mrphy_blochsim_rfgr_traj_fwd': (_int, [_int, _vp, _vp, _i64, _vp, _i64, _vp] + _BC + _BC + [_vp]
+                                     + _BC * 3 + [_vp, _vp, _vp, _i64, _vp, _i64] + [_i64] * 4 + [_vp]),
+    'mrphy_blochsim_rfgr_traj_bwd': (_int, [_int, _vp, _vp, _i64, _vp, _i64, _vp] + _BC + _BC + [_vp]
+                                     + _BC * 3 + [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _sz] + [_i64] * 3 + [_vp]),
+    'mrphy_blochsim_rfgr_mc_traj_bwd': (_int, [_int, _vp, _vp, _i64, _vp, _i64, _vp] + _BC + _BC + [_vp]
+                                        + _BC * 3 + [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _sz] + [_i64] * 4
+                                        + [_vp]),
     'mrphy_freeprec_fwd': (_int, [_int, _vp, _vp, _i64] + _BC * 3 + [_vp, _i64, _i64, _vp]),
     'mrphy_freeprec_bwd': (_int, [_int, _vp, _vp, _i64] + _BC * 3 + [_vp, _i64, _i64, _vp]),
     'mrphy_freeprec_bwd_consts': (_int, [_int, _vp, _vp, _vp, _i64] + _BC * 3 + [_vp, _i64, _i64, _vp]),
@@ -95,6 +102,9 @@ UNITS = [(f, m) for f, masks in (
     ('tu_fused_fwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_fused_fwd1.hip', (_F32, _C64, _P, _PC64)),
     ('tu_fused_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
+    ('tu_fused_traj_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
+    ('tu_fused_traj_fwd.hip', (_F32, _F64, _C64, _P, _PC64)),
+    ('tu_fused_traj_fwd1.hip', (_F32, _C64, _P, _PC64)),
     ('tu_blochsim_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_blochsim_fwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_beff2ab.hip', (_F32, _F64, _C64, _P, _PC64)),
@@ -132,7 +142,7 @@ def unit_object(objdir: str, src: str, mask) -> str:
 # 15 % (64^3 x 2048: 0.81 -> 0.69 ms; tools/ab_libs_valu.py, profiles/r04_sched_ilp_ab.txt, r04_k2_ilp_ab.json).
 # The multi-coil and fp64 builds lose with it (registers), K2b is indifferent: they keep the default.
 _ILP = ('-mllvm', '-amdgpu-sched-strategy=max-ilp')
-UNIT_FLAGS = {'tu_fused_fwd1.hip': _ILP}
+UNIT_FLAGS = {'tu_fused_fwd1.hip': _ILP, 'tu_fused_traj_fwd1.hip': _ILP}
 
 
 def unit_command(src: str, mask, obj: str, extra=()) -> list:

@@ -306,6 +306,81 @@ int mrphy_blochsim_rfgr_mc_bwd(int dtype, const void* Mck, const void* rf, int64
                                                   work, N, nM, nT, nC, st)));
 }
 
+int mrphy_blochsim_rfgr_traj_fwd(int dtype, const void* Mi, const void* rf, int64_t rf_sn,
+                                 const void* gr, int64_t gr_sn, const void* loc, const void* df,
+                                 int64_t df_sn, int64_t df_sm, const void* gamma, int64_t gamma_sn,
+                                 int64_t gamma_sm, const void* b1, const void* g, int64_t g_sn,
+                                 int64_t g_sm, const void* E1, int64_t E1_sn, int64_t E1_sm,
+                                 const void* E2, int64_t E2_sn, int64_t E2_sm, const void* E1m1,
+                                 void* Mo, void* Mck, int64_t ck_every, void* Mt, int64_t every,
+                                 int64_t N, int64_t nM, int64_t nT, int64_t nC, void* stream)
+{
+    if (int e = check_common(dtype, N, nM, nT)) return e;
+    if (every < 1 || nC < 1 || (!b1 && nC != 1) || (Mck && (ck_every < 8 || ck_every % 8 != 0)))
+        return MRPHY_EINVAL;
+    if (N * nM * nT == 0) return 0;
+    if (!Mi || !Mt || !loc || !g || !rf || !gr || (df && !gamma)) return MRPHY_EINVAL;
+    if ((E1 == nullptr) != (E2 == nullptr) || (E1 == nullptr) != (E1m1 == nullptr))
+        return MRPHY_EINVAL;
+    const Bc bdf = {df, df_sn, df_sm}, bgam = {gamma, gamma_sn, gamma_sm};
+    const Bc bg = {g, g_sn, g_sm}, be1 = {E1, E1_sn, E1_sm}, be2 = {E2, E2_sn, E2_sm};
+    hipStream_t st = (hipStream_t)stream;
+    MRPHY_DISPATCH(dtype, (run_rfgr_traj_fwd<T, CT>(Mi, rf, rf_sn, gr, gr_sn, loc, bdf, bgam, b1, bg,
+                                                    be1, be2, E1m1, Mo, Mck, ck_every, Mt, every, N, nM,
+                                                    nT, nC, st)));
+}
+
+int mrphy_blochsim_rfgr_traj_bwd(int dtype, const void* Mck, const void* rf, int64_t rf_sn,
+                                 const void* gr, int64_t gr_sn, const void* loc, const void* df,
+                                 int64_t df_sn, int64_t df_sm, const void* gamma, int64_t gamma_sn,
+                                 int64_t gamma_sm, const void* b1, const void* g, int64_t g_sn,
+                                 int64_t g_sm, const void* E1, int64_t E1_sn, int64_t E1_sm,
+                                 const void* E2, int64_t E2_sn, int64_t E2_sm, const void* E1m1,
+                                 const void* grad_Mt, int64_t every, void* grad_Mi, void* grad_rf,
+                                 void* grad_gr, void* work, size_t work_bytes, int64_t N, int64_t nM,
+                                 int64_t nT, void* stream)
+{
+    if (int e = check_common(dtype, N, nM, nT)) return e;
+    if (nT % SEG != 0 || every < 1) return MRPHY_EINVAL;
+    if (N * nM * nT == 0) return 0;
+    if (!Mck || !rf || !gr || !loc || !g || !grad_Mt || !work || (df && !gamma)) return MRPHY_EINVAL;
+    if ((E1 == nullptr) != (E2 == nullptr) || (E1 == nullptr) != (E1m1 == nullptr))
+        return MRPHY_EINVAL;
+    if (work_bytes < mrphy_blochsim_rfgr_bwd_workspace(dtype, N, nM, nT)) return MRPHY_ENOSPC;
+    const Bc bdf = {df, df_sn, df_sm}, bgam = {gamma, gamma_sn, gamma_sm};
+    const Bc bg = {g, g_sn, g_sm}, be1 = {E1, E1_sn, E1_sm}, be2 = {E2, E2_sn, E2_sm};
+    hipStream_t st = (hipStream_t)stream;
+    MRPHY_DISPATCH(dtype, (run_rfgr_traj_bwd<T, CT>(Mck, rf, rf_sn, gr, gr_sn, loc, bdf, bgam, b1, bg, be1,
+                                                    be2, E1m1, grad_Mt, every, grad_Mi, grad_rf, grad_gr,
+                                                    work, N, nM, nT, st)));
+}
+
+int mrphy_blochsim_rfgr_mc_traj_bwd(int dtype, const void* Mck, const void* rf, int64_t rf_sn,
+                                    const void* gr, int64_t gr_sn, const void* loc, const void* df,
+                                    int64_t df_sn, int64_t df_sm, const void* gamma, int64_t gamma_sn,
+                                    int64_t gamma_sm, const void* b1, const void* g, int64_t g_sn,
+                                    int64_t g_sm, const void* E1, int64_t E1_sn, int64_t E1_sm,
+                                    const void* E2, int64_t E2_sn, int64_t E2_sm, const void* E1m1,
+                                    const void* grad_Mt, int64_t every, void* grad_Mi, void* grad_rf,
+                                    void* grad_gr, void* work, size_t work_bytes, int64_t N, int64_t nM,
+                                    int64_t nT, int64_t nC, void* stream)
+{
+    if (int e = check_common(dtype, N, nM, nT)) return e;
+    if (nT % SEG != 0 || every < 1 || nC < 1 || nC > K2B_MAXC) return MRPHY_EINVAL;
+    if (N * nM * nT == 0) return 0;
+    if (!Mck || !rf || !gr || !loc || !b1 || !g || !grad_Mt || !work || (df && !gamma))
+        return MRPHY_EINVAL;
+    if ((E1 == nullptr) != (E2 == nullptr) || (E1 == nullptr) != (E1m1 == nullptr))
+        return MRPHY_EINVAL;
+    if (work_bytes < mrphy_blochsim_rfgr_mc_bwd_workspace(dtype, N, nM, nT, nC)) return MRPHY_ENOSPC;
+    const Bc bdf = {df, df_sn, df_sm}, bgam = {gamma, gamma_sn, gamma_sm};
+    const Bc bg = {g, g_sn, g_sm}, be1 = {E1, E1_sn, E1_sm}, be2 = {E2, E2_sn, E2_sm};
+    hipStream_t st = (hipStream_t)stream;
+    MRPHY_DISPATCH(dtype, (run_rfgr_mc_traj_bwd<T, CT>(Mck, rf, rf_sn, gr, gr_sn, loc, bdf, bgam, b1, bg,
+                                                       be1, be2, E1m1, grad_Mt, every, grad_Mi, grad_rf,
+                                                       grad_gr, work, N, nM, nT, nC, st)));
+}
+
 int mrphy_beff2ab(int dtype, const void* Beff,
                   const void* g, int64_t g_sn, int64_t g_sm,
                   const void* E1, int64_t E1_sn, int64_t E1_sm,

@@ -52,6 +52,36 @@ struct FusedBwdArgs {
     int64_t N, nM, nT, P;
 };
 
+// MRPHY_K2B_TRAJ: a unit that defines it to 1 before including k_fused_bwd.hpp / k_fused_mc_bwd.hpp
+// (tu_fused_traj_bwd.hip) gets K2bt instead, k_bloch_rfgr_traj_bwd / k_bloch_rfgr_traj_bwd_mc -- the adjoints of the
+// trajectory (mrphy_blochsim_rfgr_traj_bwd / _mc_traj_bwd).  The additions sit in `#if` blocks, so the units of the
+// shipped K2b compile exactly the tokens they always did.
+// The cotangent of a record taken after step e enters the carried state just before the sweep passes step e
+// backwards.  In the plain modes the state is h = dL/dM and the cotangent adds as it is; in the precise fp32 t-state
+// mode (bloch_math.hpp: AdjMode) the state is t = E h, so it enters as t += (E2, E2, E1) . g, rounded as adj_begin
+// rounds the first cotangent (a raw add there would be off by a factor E per record).
+// INJ: 1 = every < SEG (up to SEG records per segment, staged in the reduction tile: see k_fused_bwd.hpp; correct for
+// any stride, and what the fp64 8-coil pTx build takes for every stride);
+// 2 = every >= SEG (at most one record per segment besides the last, in registers).  The last record's cotangent
+// starts the sweep, as grad_Mo does in K2b.
+#ifndef MRPHY_K2B_TRAJ
+#define MRPHY_K2B_TRAJ 0
+#endif
+#if MRPHY_K2B_TRAJ
+template <typename T>
+struct FusedBwdTrajArgs : FusedBwdArgs<T> {
+    int64_t every, nRec;             // gMo is grad_Mt (nRec, N*nM, 3)
+};
+
+template <bool RELAX, typename T, typename CT>
+__device__ __forceinline__ void adj_inject(const SpinConst<T, CT>& k, T& hx, T& hy, T& hz, T gx, T gy, T gz)
+{
+#pragma clang fp contract(off)
+    adj_begin<RELAX, T, CT>(k, gx, gy, gz);
+    hx += gx; hy += gy; hz += gz;
+}
+#endif
+
 // Pass 2: sum the P workspace rows per (n, quantity, t) in a fixed order.  Block = 32 time points
 // x 8 row groups (group g takes rows g, g+8, ...: 128-B coalesced reads per row), then the eight
 // partial sums are combined through LDS in group order -- deterministic, and nT/32 * 5 blocks

@@ -24,6 +24,22 @@ struct FusedArgs {
     int64_t N, nM, nT, nC;
 };
 
+// MRPHY_K2_TRAJ: a unit that defines it to 1 before including this fragment (tu_fused_traj_fwd*.hip) gets K2t instead,
+// k_bloch_rfgr_traj_fwd -- the trajectory builds of mrphy_blochsim_rfgr_traj_fwd.  The additions sit in `#if` blocks,
+// so the units of the shipped K2 compile exactly the tokens they always did (same code, register for register).
+// TR: 1 = M after EVERY step into Mt, stored inside the unrolled step batch; 2 = M after steps every-1, 2 every-1, ...
+// (a running destination and the next step, as the checkpoints: no 64-bit division in the loop) and after step nT-1.
+// Record j is M after step min((j+1) every, nT) - 1, time-major: Mt[j] is (N*nM, 3), 768 B per wave and record.
+#ifndef MRPHY_K2_TRAJ
+#define MRPHY_K2_TRAJ 0
+#endif
+#if MRPHY_K2_TRAJ
+template <typename T>
+struct FusedTrajArgs : FusedArgs<T> {
+    T* Mt;   int64_t every;                              // (nRec, N*nM, 3), nRec = ceil(nT / every)
+};
+#endif
+
 // CK: write checkpoints (every ck_every steps, a multiple of the 8-step chunk).  Kept out of the
 // plain instantiation so that its step loop contains no store: the pulse loads are then provably
 // unclobbered and become (batched) scalar loads.
@@ -39,8 +55,13 @@ constexpr int K2_MAXC = 64;                              // largest register/LDS
 // the product returns rf bit for bit anyway, so results are unchanged.  A template parameter, not a
 // run-time test: a wave-uniform branch in the field assembly broke the batching of the pulse's scalar
 // loads (round 1: 6.6 -> 7.2 ms).
+#if MRPHY_K2_TRAJ
+template <typename T, typename CT, int NCM, bool CK, bool RELAX, bool HB1, int TR>
+__global__ __launch_bounds__(WAVE) void k_bloch_rfgr_traj_fwd(FusedTrajArgs<T> a)
+#else
 template <typename T, typename CT, int NCM, bool CK, bool RELAX, bool HB1 = true>
 __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_fwd(FusedArgs<T> a)
+#endif
 {
     constexpr int NS = (sizeof(T) == 8 && NCM == 1) ? 4 : 8;   // fp64, one coil: 8 steps' pulse samples (80 SGPRs) spill to VGPR lanes
     constexpr bool NC1 = (NCM == 1);
@@ -131,6 +152,23 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_fwd(FusedArgs<T> a)
     T* ckp = CK ? a.Mck + row * 3 : nullptr;
     const int64_t ck_pitch = rows * 3;
     int64_t t0 = 0;
+#if MRPHY_K2_TRAJ
+    // trajectory records: running destination, and (TR == 2) the step after which the next one is taken
+    T* mtp = a.Mt + row * 3;
+    const int64_t tr_every = a.every;
+    int64_t tr_next = tr_every - 1;
+    auto record = [&](int64_t t) {
+        if constexpr (TR == 1) {
+            if (valid) { mtp[0] = mx; mtp[1] = my; mtp[2] = mz; }
+            mtp += ck_pitch;
+        } else {
+            if (t == tr_next) {                               // wave-uniform
+                if (valid) { mtp[0] = mx; mtp[1] = my; mtp[2] = mz; }
+                mtp += ck_pitch; tr_next += tr_every;
+            }
+        }
+    };
+#endif
     for (; t0 + NS <= nT; t0 += NS) {
         if (NCR) { tstage = t0; stage_rf(t0, NS); }
         if (CK && t0 == ck_next) {
@@ -143,7 +181,11 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_fwd(FusedArgs<T> a)
         Rot<T> r[NS];
         rot_prepare<T, CT, NS>(k, Bx, By, Bz, r);
 #pragma unroll
+#if MRPHY_K2_TRAJ
+        for (int j = 0; j < NS; ++j) { rot_apply<RELAX, T, CT>(k, r[j], mx, my, mz); record(t0 + j); }
+#else
         for (int j = 0; j < NS; ++j) rot_apply<RELAX, T, CT>(k, r[j], mx, my, mz);
+#endif
     }
     if (NCR && t0 < nT) { tstage = t0; stage_rf(t0, (int)(nT - t0)); }
     for (; t0 < nT; ++t0) {                                   // nT % 8 tail
@@ -156,7 +198,17 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_fwd(FusedArgs<T> a)
         Rot<T> r[1];
         rot_prepare<T, CT, 1>(k, Bx, By, Bz, r);
         rot_apply<RELAX, T, CT>(k, r[0], mx, my, mz);
+#if MRPHY_K2_TRAJ
+        record(t0);
+#endif
     }
+#if MRPHY_K2_TRAJ
+    // the last record is M after step nT - 1 whatever `every` is: TR == 2 took it in the loop iff every | nT.  Mo is
+    // optional here (it equals that record)
+    if (TR == 2 && tr_next - tr_every != nT - 1 && valid) { mtp[0] = mx; mtp[1] = my; mtp[2] = mz; }
+    if (valid && a.Mo) { a.Mo[row * 3] = mx; a.Mo[row * 3 + 1] = my; a.Mo[row * 3 + 2] = mz; }
+#else
     if (valid) { a.Mo[row * 3] = mx; a.Mo[row * 3 + 1] = my; a.Mo[row * 3 + 2] = mz; }
+#endif
 }
 
