@@ -98,13 +98,10 @@ _ALL, _F32, _F64, _C64, _P, _PC64 = 0x1f, 1 << F32, 1 << F64, 1 << F32_C64, 1 <<
 # The translation units of the library: (source, dtype mask or None).  One hipcc job each, run in parallel;
 # sorted by compile time, longest first (seconds on the 8-core build container, see build()).
 UNITS = [(f, m) for f, masks in (
-    ('tu_fused_mc_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_fused_fwd.hip', (_F32, _F64, _C64, _P, _PC64)),
+    ('tu_fused_mc_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_fused_fwd1.hip', (_F32, _C64, _P, _PC64)),
     ('tu_fused_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
-    ('tu_fused_traj_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
-    ('tu_fused_traj_fwd.hip', (_F32, _F64, _C64, _P, _PC64)),
-    ('tu_fused_traj_fwd1.hip', (_F32, _C64, _P, _PC64)),
     ('tu_blochsim_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_blochsim_fwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_beff2ab.hip', (_F32, _F64, _C64, _P, _PC64)),
@@ -142,7 +139,7 @@ def unit_object(objdir: str, src: str, mask) -> str:
 # 15 % (64^3 x 2048: 0.81 -> 0.69 ms; tools/ab_libs_valu.py, profiles/r04_sched_ilp_ab.txt, r04_k2_ilp_ab.json).
 # The multi-coil and fp64 builds lose with it (registers), K2b is indifferent: they keep the default.
 _ILP = ('-mllvm', '-amdgpu-sched-strategy=max-ilp')
-UNIT_FLAGS = {'tu_fused_fwd1.hip': _ILP, 'tu_fused_traj_fwd1.hip': _ILP}
+UNIT_FLAGS = {'tu_fused_fwd1.hip': _ILP}
 
 
 def unit_command(src: str, mask, obj: str, extra=()) -> list:

@@ -32,6 +32,78 @@ int make_hist_parts(int dtype, void* const* parts, int64_t n_parts, int layout, 
     h.tiles_per_part = (uint32_t)hist_tiles_per_part(N, nM, n_parts);
     return 0;
 }
+
+// The fused simulation (K2 / K2b) and its trajectory builds: each plain entry point and its `_traj_` twin share one
+// validation and dispatch.  `traj` tells them apart; what differs is written out where it differs.  The launchers take
+// a null Mt / grad_Mt for the plain kernels.
+int rfgr_fwd(bool traj, int dtype, const void* Mi, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
+             const void* loc, const void* df, int64_t df_sn, int64_t df_sm, const void* gamma, int64_t gamma_sn,
+             int64_t gamma_sm, const void* b1, const void* g, int64_t g_sn, int64_t g_sm, const void* E1,
+             int64_t E1_sn, int64_t E1_sm, const void* E2, int64_t E2_sn, int64_t E2_sm, const void* E1m1, void* Mo,
+             void* Mck, int64_t ck_every, void* Mt, int64_t every, int64_t N, int64_t nM, int64_t nT, int64_t nC,
+             void* stream)
+{
+    if (int e = check_common(dtype, N, nM, nT)) return e;
+    if ((traj && every < 1) || nC < 1 || (!b1 && nC != 1) || (Mck && (ck_every < 8 || ck_every % 8 != 0)))
+        return MRPHY_EINVAL;
+    if (N * nM * (traj ? nT : 1) == 0) return 0;          // the plain forward runs at nT == 0: Mo = Mi
+    // the trajectory's Mo is optional (it equals the last record)
+    if (!Mi || !(traj ? Mt : Mo) || !loc || !g || (nT > 0 && (!rf || !gr)) || (df && !gamma))
+        return MRPHY_EINVAL;
+    if ((E1 == nullptr) != (E2 == nullptr) || (E1 == nullptr) != (E1m1 == nullptr))
+        return MRPHY_EINVAL;
+    const Bc bdf = {df, df_sn, df_sm}, bgam = {gamma, gamma_sn, gamma_sm};
+    const Bc bg = {g, g_sn, g_sm}, be1 = {E1, E1_sn, E1_sm}, be2 = {E2, E2_sn, E2_sm};
+    hipStream_t st = (hipStream_t)stream;
+    MRPHY_DISPATCH(dtype, (run_rfgr_fwd<T, CT>(Mi, rf, rf_sn, gr, gr_sn, loc, bdf, bgam, b1, bg, be1, be2, E1m1, Mo,
+                                               Mck, ck_every, Mt, every, N, nM, nT, nC, st)));
+}
+
+// grad_M: grad_Mo, or (traj) grad_Mt
+int rfgr_bwd(bool traj, int dtype, const void* Mck, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
+             const void* loc, const void* df, int64_t df_sn, int64_t df_sm, const void* gamma, int64_t gamma_sn,
+             int64_t gamma_sm, const void* b1, const void* g, int64_t g_sn, int64_t g_sm, const void* E1,
+             int64_t E1_sn, int64_t E1_sm, const void* E2, int64_t E2_sn, int64_t E2_sm, const void* E1m1,
+             const void* grad_M, int64_t every, void* grad_Mi, void* grad_rf, void* grad_gr, void* work,
+             size_t work_bytes, int64_t N, int64_t nM, int64_t nT, void* stream)
+{
+    if (int e = check_common(dtype, N, nM, nT)) return e;
+    if (nT % SEG != 0 || (traj && every < 1)) return MRPHY_EINVAL;   // whole checkpoint segments only
+    if (N * nM * nT == 0) return 0;
+    if (!Mck || !rf || !gr || !loc || !g || !grad_M || !work || (df && !gamma)) return MRPHY_EINVAL;
+    if ((E1 == nullptr) != (E2 == nullptr) || (E1 == nullptr) != (E1m1 == nullptr))
+        return MRPHY_EINVAL;
+    if (work_bytes < mrphy_blochsim_rfgr_bwd_workspace(dtype, N, nM, nT)) return MRPHY_ENOSPC;
+    const Bc bdf = {df, df_sn, df_sm}, bgam = {gamma, gamma_sn, gamma_sm};
+    const Bc bg = {g, g_sn, g_sm}, be1 = {E1, E1_sn, E1_sm}, be2 = {E2, E2_sn, E2_sm};
+    hipStream_t st = (hipStream_t)stream;
+    MRPHY_DISPATCH(dtype, (run_rfgr_bwd<T, CT>(Mck, rf, rf_sn, gr, gr_sn, loc, bdf, bgam, b1, bg, be1, be2, E1m1,
+                                               traj ? nullptr : grad_M, traj ? grad_M : nullptr, every, grad_Mi,
+                                               grad_rf, grad_gr, work, N, nM, nT, st)));
+}
+
+int rfgr_mc_bwd(bool traj, int dtype, const void* Mck, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
+                const void* loc, const void* df, int64_t df_sn, int64_t df_sm, const void* gamma, int64_t gamma_sn,
+                int64_t gamma_sm, const void* b1, const void* g, int64_t g_sn, int64_t g_sm, const void* E1,
+                int64_t E1_sn, int64_t E1_sm, const void* E2, int64_t E2_sn, int64_t E2_sm, const void* E1m1,
+                const void* grad_M, int64_t every, void* grad_Mi, void* grad_rf, void* grad_gr, void* work,
+                size_t work_bytes, int64_t N, int64_t nM, int64_t nT, int64_t nC, void* stream)
+{
+    if (int e = check_common(dtype, N, nM, nT)) return e;
+    if (nT % SEG != 0 || (traj && every < 1) || nC < 1 || nC > K2B_MAXC) return MRPHY_EINVAL;
+    if (N * nM * nT == 0) return 0;
+    if (!Mck || !rf || !gr || !loc || !b1 || !g || !grad_M || !work || (df && !gamma))
+        return MRPHY_EINVAL;
+    if ((E1 == nullptr) != (E2 == nullptr) || (E1 == nullptr) != (E1m1 == nullptr))
+        return MRPHY_EINVAL;
+    if (work_bytes < mrphy_blochsim_rfgr_mc_bwd_workspace(dtype, N, nM, nT, nC)) return MRPHY_ENOSPC;
+    const Bc bdf = {df, df_sn, df_sm}, bgam = {gamma, gamma_sn, gamma_sm};
+    const Bc bg = {g, g_sn, g_sm}, be1 = {E1, E1_sn, E1_sm}, be2 = {E2, E2_sn, E2_sm};
+    hipStream_t st = (hipStream_t)stream;
+    MRPHY_DISPATCH(dtype, (run_rfgr_mc_bwd<T, CT>(Mck, rf, rf_sn, gr, gr_sn, loc, bdf, bgam, b1, bg, be1, be2, E1m1,
+                                                  traj ? nullptr : grad_M, traj ? grad_M : nullptr, every, grad_Mi,
+                                                  grad_rf, grad_gr, work, N, nM, nT, nC, st)));
+}
 }  // namespace
 
 // =============================================================================================
@@ -223,20 +295,9 @@ int mrphy_blochsim_rfgr_fwd(int dtype, const void* Mi, const void* rf, int64_t r
                             void* Mo, void* Mck, int64_t ck_every, int64_t N, int64_t nM,
                             int64_t nT, int64_t nC, void* stream)
 {
-    if (int e = check_common(dtype, N, nM, nT)) return e;
-    if (nC < 1 || (!b1 && nC != 1) || (Mck && (ck_every < 8 || ck_every % 8 != 0)))
-        return MRPHY_EINVAL;
-    if (N * nM == 0) return 0;
-    if (!Mi || !Mo || !loc || !g || (nT > 0 && (!rf || !gr)) || (df && !gamma))
-        return MRPHY_EINVAL;
-    if ((E1 == nullptr) != (E2 == nullptr) || (E1 == nullptr) != (E1m1 == nullptr))
-        return MRPHY_EINVAL;
-    const Bc bdf = {df, df_sn, df_sm}, bgam = {gamma, gamma_sn, gamma_sm};
-    const Bc bg = {g, g_sn, g_sm}, be1 = {E1, E1_sn, E1_sm}, be2 = {E2, E2_sn, E2_sm};
-    hipStream_t st = (hipStream_t)stream;
-    MRPHY_DISPATCH(dtype, (run_rfgr_fwd<T, CT>(Mi, rf, rf_sn, gr, gr_sn, loc, bdf, bgam, b1, bg,
-                                               be1, be2, E1m1, Mo, Mck, ck_every, N, nM, nT, nC,
-                                               st)));
+    return rfgr_fwd(false, dtype, Mi, rf, rf_sn, gr, gr_sn, loc, df, df_sn, df_sm, gamma, gamma_sn, gamma_sm, b1, g,
+                    g_sn, g_sm, E1, E1_sn, E1_sm, E2, E2_sn, E2_sm, E1m1, Mo, Mck, ck_every, nullptr, 0, N, nM, nT,
+                    nC, stream);
 }
 
 int64_t mrphy_blochsim_rfgr_ck_every(void) { return SEG; }
@@ -257,19 +318,9 @@ int mrphy_blochsim_rfgr_bwd(int dtype, const void* Mck, const void* rf, int64_t 
                             void* work, size_t work_bytes, int64_t N, int64_t nM, int64_t nT,
                             void* stream)
 {
-    if (int e = check_common(dtype, N, nM, nT)) return e;
-    if (nT % SEG != 0) return MRPHY_EINVAL;               // whole checkpoint segments only
-    if (N * nM * nT == 0) return 0;
-    if (!Mck || !rf || !gr || !loc || !g || !grad_Mo || !work || (df && !gamma)) return MRPHY_EINVAL;
-    if ((E1 == nullptr) != (E2 == nullptr) || (E1 == nullptr) != (E1m1 == nullptr))
-        return MRPHY_EINVAL;
-    if (work_bytes < mrphy_blochsim_rfgr_bwd_workspace(dtype, N, nM, nT)) return MRPHY_ENOSPC;
-    const Bc bdf = {df, df_sn, df_sm}, bgam = {gamma, gamma_sn, gamma_sm};
-    const Bc bg = {g, g_sn, g_sm}, be1 = {E1, E1_sn, E1_sm}, be2 = {E2, E2_sn, E2_sm};
-    hipStream_t st = (hipStream_t)stream;
-    MRPHY_DISPATCH(dtype, (run_rfgr_bwd<T, CT>(Mck, rf, rf_sn, gr, gr_sn, loc, bdf, bgam, b1, bg, be1,
-                                               be2, E1m1, grad_Mo, grad_Mi, grad_rf, grad_gr, work,
-                                               N, nM, nT, st)));
+    return rfgr_bwd(false, dtype, Mck, rf, rf_sn, gr, gr_sn, loc, df, df_sn, df_sm, gamma, gamma_sn, gamma_sm, b1,
+                    g, g_sn, g_sm, E1, E1_sn, E1_sm, E2, E2_sn, E2_sm, E1m1, grad_Mo, 0, grad_Mi, grad_rf, grad_gr,
+                    work, work_bytes, N, nM, nT, stream);
 }
 
 int64_t mrphy_blochsim_rfgr_mc_max_coils(void) { return K2B_MAXC; }
@@ -290,20 +341,9 @@ int mrphy_blochsim_rfgr_mc_bwd(int dtype, const void* Mck, const void* rf, int64
                                void* work, size_t work_bytes, int64_t N, int64_t nM, int64_t nT,
                                int64_t nC, void* stream)
 {
-    if (int e = check_common(dtype, N, nM, nT)) return e;
-    if (nT % SEG != 0 || nC < 1 || nC > K2B_MAXC) return MRPHY_EINVAL;
-    if (N * nM * nT == 0) return 0;
-    if (!Mck || !rf || !gr || !loc || !b1 || !g || !grad_Mo || !work || (df && !gamma))
-        return MRPHY_EINVAL;
-    if ((E1 == nullptr) != (E2 == nullptr) || (E1 == nullptr) != (E1m1 == nullptr))
-        return MRPHY_EINVAL;
-    if (work_bytes < mrphy_blochsim_rfgr_mc_bwd_workspace(dtype, N, nM, nT, nC)) return MRPHY_ENOSPC;
-    const Bc bdf = {df, df_sn, df_sm}, bgam = {gamma, gamma_sn, gamma_sm};
-    const Bc bg = {g, g_sn, g_sm}, be1 = {E1, E1_sn, E1_sm}, be2 = {E2, E2_sn, E2_sm};
-    hipStream_t st = (hipStream_t)stream;
-    MRPHY_DISPATCH(dtype, (run_rfgr_mc_bwd<T, CT>(Mck, rf, rf_sn, gr, gr_sn, loc, bdf, bgam, b1, bg,
-                                                  be1, be2, E1m1, grad_Mo, grad_Mi, grad_rf, grad_gr,
-                                                  work, N, nM, nT, nC, st)));
+    return rfgr_mc_bwd(false, dtype, Mck, rf, rf_sn, gr, gr_sn, loc, df, df_sn, df_sm, gamma, gamma_sn, gamma_sm,
+                       b1, g, g_sn, g_sm, E1, E1_sn, E1_sm, E2, E2_sn, E2_sm, E1m1, grad_Mo, 0, grad_Mi, grad_rf,
+                       grad_gr, work, work_bytes, N, nM, nT, nC, stream);
 }
 
 int mrphy_blochsim_rfgr_traj_fwd(int dtype, const void* Mi, const void* rf, int64_t rf_sn,
@@ -315,19 +355,9 @@ int mrphy_blochsim_rfgr_traj_fwd(int dtype, const void* Mi, const void* rf, int6
                                  void* Mo, void* Mck, int64_t ck_every, void* Mt, int64_t every,
                                  int64_t N, int64_t nM, int64_t nT, int64_t nC, void* stream)
 {
-    if (int e = check_common(dtype, N, nM, nT)) return e;
-    if (every < 1 || nC < 1 || (!b1 && nC != 1) || (Mck && (ck_every < 8 || ck_every % 8 != 0)))
-        return MRPHY_EINVAL;
-    if (N * nM * nT == 0) return 0;
-    if (!Mi || !Mt || !loc || !g || !rf || !gr || (df && !gamma)) return MRPHY_EINVAL;
-    if ((E1 == nullptr) != (E2 == nullptr) || (E1 == nullptr) != (E1m1 == nullptr))
-        return MRPHY_EINVAL;
-    const Bc bdf = {df, df_sn, df_sm}, bgam = {gamma, gamma_sn, gamma_sm};
-    const Bc bg = {g, g_sn, g_sm}, be1 = {E1, E1_sn, E1_sm}, be2 = {E2, E2_sn, E2_sm};
-    hipStream_t st = (hipStream_t)stream;
-    MRPHY_DISPATCH(dtype, (run_rfgr_traj_fwd<T, CT>(Mi, rf, rf_sn, gr, gr_sn, loc, bdf, bgam, b1, bg,
-                                                    be1, be2, E1m1, Mo, Mck, ck_every, Mt, every, N, nM,
-                                                    nT, nC, st)));
+    return rfgr_fwd(true, dtype, Mi, rf, rf_sn, gr, gr_sn, loc, df, df_sn, df_sm, gamma, gamma_sn, gamma_sm, b1, g,
+                    g_sn, g_sm, E1, E1_sn, E1_sm, E2, E2_sn, E2_sm, E1m1, Mo, Mck, ck_every, Mt, every, N, nM, nT,
+                    nC, stream);
 }
 
 int mrphy_blochsim_rfgr_traj_bwd(int dtype, const void* Mck, const void* rf, int64_t rf_sn,
@@ -340,19 +370,9 @@ int mrphy_blochsim_rfgr_traj_bwd(int dtype, const void* Mck, const void* rf, int
                                  void* grad_gr, void* work, size_t work_bytes, int64_t N, int64_t nM,
                                  int64_t nT, void* stream)
 {
-    if (int e = check_common(dtype, N, nM, nT)) return e;
-    if (nT % SEG != 0 || every < 1) return MRPHY_EINVAL;
-    if (N * nM * nT == 0) return 0;
-    if (!Mck || !rf || !gr || !loc || !g || !grad_Mt || !work || (df && !gamma)) return MRPHY_EINVAL;
-    if ((E1 == nullptr) != (E2 == nullptr) || (E1 == nullptr) != (E1m1 == nullptr))
-        return MRPHY_EINVAL;
-    if (work_bytes < mrphy_blochsim_rfgr_bwd_workspace(dtype, N, nM, nT)) return MRPHY_ENOSPC;
-    const Bc bdf = {df, df_sn, df_sm}, bgam = {gamma, gamma_sn, gamma_sm};
-    const Bc bg = {g, g_sn, g_sm}, be1 = {E1, E1_sn, E1_sm}, be2 = {E2, E2_sn, E2_sm};
-    hipStream_t st = (hipStream_t)stream;
-    MRPHY_DISPATCH(dtype, (run_rfgr_traj_bwd<T, CT>(Mck, rf, rf_sn, gr, gr_sn, loc, bdf, bgam, b1, bg, be1,
-                                                    be2, E1m1, grad_Mt, every, grad_Mi, grad_rf, grad_gr,
-                                                    work, N, nM, nT, st)));
+    return rfgr_bwd(true, dtype, Mck, rf, rf_sn, gr, gr_sn, loc, df, df_sn, df_sm, gamma, gamma_sn, gamma_sm, b1, g,
+                    g_sn, g_sm, E1, E1_sn, E1_sm, E2, E2_sn, E2_sm, E1m1, grad_Mt, every, grad_Mi, grad_rf, grad_gr,
+                    work, work_bytes, N, nM, nT, stream);
 }
 
 int mrphy_blochsim_rfgr_mc_traj_bwd(int dtype, const void* Mck, const void* rf, int64_t rf_sn,
@@ -365,20 +385,9 @@ int mrphy_blochsim_rfgr_mc_traj_bwd(int dtype, const void* Mck, const void* rf, 
                                     void* grad_gr, void* work, size_t work_bytes, int64_t N, int64_t nM,
                                     int64_t nT, int64_t nC, void* stream)
 {
-    if (int e = check_common(dtype, N, nM, nT)) return e;
-    if (nT % SEG != 0 || every < 1 || nC < 1 || nC > K2B_MAXC) return MRPHY_EINVAL;
-    if (N * nM * nT == 0) return 0;
-    if (!Mck || !rf || !gr || !loc || !b1 || !g || !grad_Mt || !work || (df && !gamma))
-        return MRPHY_EINVAL;
-    if ((E1 == nullptr) != (E2 == nullptr) || (E1 == nullptr) != (E1m1 == nullptr))
-        return MRPHY_EINVAL;
-    if (work_bytes < mrphy_blochsim_rfgr_mc_bwd_workspace(dtype, N, nM, nT, nC)) return MRPHY_ENOSPC;
-    const Bc bdf = {df, df_sn, df_sm}, bgam = {gamma, gamma_sn, gamma_sm};
-    const Bc bg = {g, g_sn, g_sm}, be1 = {E1, E1_sn, E1_sm}, be2 = {E2, E2_sn, E2_sm};
-    hipStream_t st = (hipStream_t)stream;
-    MRPHY_DISPATCH(dtype, (run_rfgr_mc_traj_bwd<T, CT>(Mck, rf, rf_sn, gr, gr_sn, loc, bdf, bgam, b1, bg,
-                                                       be1, be2, E1m1, grad_Mt, every, grad_Mi, grad_rf,
-                                                       grad_gr, work, N, nM, nT, nC, st)));
+    return rfgr_mc_bwd(true, dtype, Mck, rf, rf_sn, gr, gr_sn, loc, df, df_sn, df_sm, gamma, gamma_sn, gamma_sm, b1,
+                       g, g_sn, g_sm, E1, E1_sn, E1_sm, E2, E2_sn, E2_sm, E1m1, grad_Mt, every, grad_Mi, grad_rf,
+                       grad_gr, work, work_bytes, N, nM, nT, nC, stream);
 }
 
 int mrphy_beff2ab(int dtype, const void* Beff,

@@ -29,56 +29,33 @@ template <typename T>
 int run_rfgr2beff_bwd(const void* gB, const void* loc, const void* b1, void* grf, void* ggr,
                       void* work, int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st);
 
+// K2 / K2b and their trajectory builds K2t / K2bt (the same kernels, trailing mode parameter): a null Mt / gMt runs
+// the plain kernel, which writes Mo / reads gMo; otherwise Mt / gMt hold the records taken every `every` steps
 template <typename T, typename CT>
 int run_rfgr_fwd(const void* Mi, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
                  const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2,
-                 const void* E1m1, void* Mo, void* Mck, int64_t ck_every, int64_t N, int64_t nM,
-                 int64_t nT, int64_t nC, hipStream_t st);
+                 const void* E1m1, void* Mo, void* Mck, int64_t ck_every, void* Mt, int64_t every,
+                 int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st);
 
 // the one-coil float builds of K2 live in a unit of their own (tu_fused_fwd1.hip: compiled with the max-ILP
-// scheduling strategy, which the multi-coil and fp64 builds pay for in registers)
+// scheduling strategy, which the multi-coil and fp64 builds pay for in registers); called by run_rfgr_fwd
 template <typename T, typename CT>
 int run_rfgr_fwd1(const void* Mi, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
                   const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2,
-                  const void* E1m1, void* Mo, void* Mck, int64_t ck_every, int64_t N, int64_t nM,
-                  int64_t nT, hipStream_t st);
+                  const void* E1m1, void* Mo, void* Mck, int64_t ck_every, void* Mt, int64_t every,
+                  int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st);
 
 template <typename T, typename CT>
 int run_rfgr_bwd(const void* Mck, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
                  const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2,
-                 const void* E1m1, const void* gMo, void* gMi, void* grf, void* ggr, void* work,
-                 int64_t N, int64_t nM, int64_t nT, hipStream_t st);
+                 const void* E1m1, const void* gMo, const void* gMt, int64_t every, void* gMi, void* grf,
+                 void* ggr, void* work, int64_t N, int64_t nM, int64_t nT, hipStream_t st);
 
 template <typename T, typename CT>
 int run_rfgr_mc_bwd(const void* Mck, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
                     const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2,
-                    const void* E1m1, const void* gMo, void* gMi, void* grf, void* ggr, void* work,
-                    int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st);
-
-// trajectory builds of K2 / K2b (tu_fused_traj_fwd.hip, tu_fused_traj_fwd1.hip, tu_fused_traj_bwd.hip)
-template <typename T, typename CT>
-int run_rfgr_traj_fwd(const void* Mi, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
-                      const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2,
-                      const void* E1m1, void* Mo, void* Mck, int64_t ck_every, void* Mt, int64_t every,
-                      int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st);
-
-template <typename T, typename CT>
-int run_rfgr_traj_fwd1(const void* Mi, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
-                       const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2,
-                       const void* E1m1, void* Mo, void* Mck, int64_t ck_every, void* Mt, int64_t every,
-                       int64_t N, int64_t nM, int64_t nT, hipStream_t st);
-
-template <typename T, typename CT>
-int run_rfgr_traj_bwd(const void* Mck, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
-                      const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2,
-                      const void* E1m1, const void* gMt, int64_t every, void* gMi, void* grf, void* ggr,
-                      void* work, int64_t N, int64_t nM, int64_t nT, hipStream_t st);
-
-template <typename T, typename CT>
-int run_rfgr_mc_traj_bwd(const void* Mck, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
-                         const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2,
-                         const void* E1m1, const void* gMt, int64_t every, void* gMi, void* grf, void* ggr,
-                         void* work, int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st);
+                    const void* E1m1, const void* gMo, const void* gMt, int64_t every, void* gMi, void* grf,
+                    void* ggr, void* work, int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st);
 
 template <typename T, typename CT>
 int run_beff2ab(const void* Beff, Bc g, Bc E1, Bc E2, const void* E1m1, void* A, void* B, void* hist,

@@ -4,13 +4,8 @@
 #pragma once
 #include "k_fused_bwd_common.hpp"
 
-#if MRPHY_K2B_TRAJ
 template <typename T, typename CT, bool RELAX, bool HB1, int INJ>
-__global__ __launch_bounds__(WAVE) void k_bloch_rfgr_traj_bwd(FusedBwdTrajArgs<T> a)
-#else
-template <typename T, typename CT, bool RELAX, bool HB1 = true>
-__global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdArgs<T> a)
-#endif
+__global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdArgsT<T, INJ> a)
 {
     __shared__ __attribute__((aligned(16))) T red[5 * SEG * RED_PITCH];
     const int lane = threadIdx.x;
@@ -42,15 +37,13 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdArgs<T> a)
         // lanes past nM (they hold a copy of the last valid spin) start from a zero cotangent: the adjoint state and every
         // dL/dB they form stay exact zeros (all of it is linear in the state), so they add nothing to the row sums --
         // round 6: masked here, once per tile, instead of three multiplications per step
-#if MRPHY_K2B_TRAJ
-        const T* gM = a.gMo + (a.nRec - 1) * rows * 3;             // the last record is Mo
+        // grad_Mo; in the trajectory builds grad_Mt, whose last record is Mo
+        const T* gM = a.gMo;
+        if constexpr (INJ != 0) gM += (a.nRec - 1) * rows * 3;
         T hx = gM[row * 3] * vmask, hy = gM[row * 3 + 1] * vmask, hz = gM[row * 3 + 2] * vmask;
-        // the latest record not yet injected: index jr, taken after step er (both wave-uniform)
-        const int64_t every = a.every;
-        int64_t jr = a.nRec - 2, er = (a.nRec - 1) * every - 1;
-#else
-        T hx = a.gMo[row * 3] * vmask, hy = a.gMo[row * 3 + 1] * vmask, hz = a.gMo[row * 3 + 2] * vmask;
-#endif
+        // trajectory: the latest record not yet injected, index jr, taken after step er (both wave-uniform)
+        int64_t every = 0, jr = 0, er = 0;
+        if constexpr (INJ != 0) { every = a.every; jr = a.nRec - 2; er = (a.nRec - 1) * every - 1; }
         adj_begin<RELAX, T, CT>(k, hx, hy, hz);
 
         auto field = [&](int64_t t, T& Bx, T& By, T& Bz) {
@@ -79,7 +72,6 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdArgs<T> a)
                 const T* ck = a.Mck + ((seg - 1) * rows + row) * 3;
                 cx = ck[0]; cy = ck[1]; cz = ck[2];
             }
-#if MRPHY_K2B_TRAJ
             // the trajectory cotangents of this segment.  INJ == 2: at most one, at step ist of the segment (-1: none),
             // in registers, requested here and used in the sweep after the recompute.  INJ == 1: the lane's cotangent of
             // step st goes to the slots red[(0|1|2) SEG + st][lane] that the sweep overwrites at that very step with
@@ -94,7 +86,7 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdArgs<T> a)
                     ijx = q[0] * vmask; ijy = q[1] * vmask; ijz = q[2] * vmask;
                     ist = (int)(er - t0); --jr; er -= every;
                 }
-            } else {
+            } else if constexpr (INJ == 1) {
                 T gv[SEG][3];
 #pragma unroll
                 for (int st = SEG - 1; st >= 0; --st) {
@@ -112,7 +104,6 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdArgs<T> a)
                     red[red_idx(2 * SEG + st, lane)] = gv[st][2];
                 }
             }
-#endif
             T* dst0 = wsrow + (lane / SEG) * nT + t0 + (lane % SEG);
             T* dst1 = wsrow + (r1 / SEG) * nT + t0 + (r1 % SEG);
             T old0 = T(0), old1 = T(0);
@@ -147,13 +138,12 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdArgs<T> a)
 #pragma unroll
                 for (int j = 3; j >= 0; --j) {
                     const int st = sb * 4 + j;
-#if MRPHY_K2B_TRAJ
                     if constexpr (INJ == 1)
                         adj_inject<RELAX, T, CT>(k, hx, hy, hz, red[red_idx(0 * SEG + st, lane)],
                                                  red[red_idx(1 * SEG + st, lane)], red[red_idx(2 * SEG + st, lane)]);
-                    else if (st == ist)
-                        adj_inject<RELAX, T, CT>(k, hx, hy, hz, ijx, ijy, ijz);
-#endif
+                    else if constexpr (INJ == 2) {
+                        if (st == ist) adj_inject<RELAX, T, CT>(k, hx, hy, hz, ijx, ijy, ijz);
+                    }
                     T g0, g1, g2;
                     rot_apply_adj<RELAX, T, CT>(k, ra[j], M0[st], M1[st], M2[st], hx, hy, hz,
                                                 g0, g1, g2);

@@ -52,10 +52,9 @@ struct FusedBwdArgs {
     int64_t N, nM, nT, P;
 };
 
-// MRPHY_K2B_TRAJ: a unit that defines it to 1 before including k_fused_bwd.hpp / k_fused_mc_bwd.hpp
-// (tu_fused_traj_bwd.hip) gets K2bt instead, k_bloch_rfgr_traj_bwd / k_bloch_rfgr_traj_bwd_mc -- the adjoints of the
-// trajectory (mrphy_blochsim_rfgr_traj_bwd / _mc_traj_bwd).  The additions sit in `#if` blocks, so the units of the
-// shipped K2b compile exactly the tokens they always did.
+// The trajectory adjoints (K2bt: mrphy_blochsim_rfgr_traj_bwd / _mc_traj_bwd) are the same kernels with INJ > 0 and
+// FusedBwdTrajArgs; INJ == 0 is the plain K2b, whose sweep holds none of the additions (`if constexpr`) and whose
+// kernarg layout stays FusedBwdArgs.
 // The cotangent of a record taken after step e enters the carried state just before the sweep passes step e
 // backwards.  In the plain modes the state is h = dL/dM and the cotangent adds as it is; in the precise fp32 t-state
 // mode (bloch_math.hpp: AdjMode) the state is t = E h, so it enters as t += (E2, E2, E1) . g, rounded as adj_begin
@@ -64,14 +63,29 @@ struct FusedBwdArgs {
 // any stride, and what the fp64 8-coil pTx build takes for every stride);
 // 2 = every >= SEG (at most one record per segment besides the last, in registers).  The last record's cotangent
 // starts the sweep, as grad_Mo does in K2b.
-#ifndef MRPHY_K2B_TRAJ
-#define MRPHY_K2B_TRAJ 0
-#endif
-#if MRPHY_K2B_TRAJ
 template <typename T>
 struct FusedBwdTrajArgs : FusedBwdArgs<T> {
     int64_t every, nRec;             // gMo is grad_Mt (nRec, N*nM, 3)
 };
+template <typename T, int INJ>
+using FusedBwdArgsT = std::conditional_t<INJ == 0, FusedBwdArgs<T>, FusedBwdTrajArgs<T>>;
+
+// the arguments of K2b / K2bt (host side, shared by tu_fused_bwd.hip and tu_fused_mc_bwd.hip): a null gMt selects the
+// plain kernel (INJ == 0), which takes the FusedBwdArgs part; otherwise gMt is the cotangent the kernel reads
+template <typename T>
+FusedBwdTrajArgs<T> fused_bwd_args(const void* Mck, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
+                                   const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2,
+                                   const void* E1m1, const void* gMo, const void* gMt, int64_t every, void* gMi,
+                                   void* work, int64_t N, int64_t nM, int64_t nT, int64_t P)
+{
+    FusedBwdTrajArgs<T> a;
+    a.Mck = (const T*)Mck; a.rf = (const T*)rf; a.rf_sn = rf_sn; a.gr = (const T*)gr;
+    a.gr_sn = gr_sn; a.loc = (const T*)loc; a.df = df; a.gam = gam; a.b1 = (const T*)b1;
+    a.g = g; a.E1 = E1; a.E2 = E2; a.E1m1 = E1m1; a.gMo = (const T*)(gMt ? gMt : gMo); a.gMi = (T*)gMi;
+    a.work = (T*)work; a.N = N; a.nM = nM; a.nT = nT; a.P = P;
+    a.every = every; a.nRec = gMt ? (nT + every - 1) / every : 0;
+    return a;
+}
 
 template <bool RELAX, typename T, typename CT>
 __device__ __forceinline__ void adj_inject(const SpinConst<T, CT>& k, T& hx, T& hy, T& hz, T gx, T gy, T gz)
@@ -80,7 +94,6 @@ __device__ __forceinline__ void adj_inject(const SpinConst<T, CT>& k, T& hx, T& 
     adj_begin<RELAX, T, CT>(k, gx, gy, gz);
     hx += gx; hy += gy; hz += gz;
 }
-#endif
 
 // Pass 2: sum the P workspace rows per (n, quantity, t) in a fixed order.  Block = 32 time points
 // x 8 row groups (group g takes rows g, g+8, ...: 128-B coalesced reads per row), then the eight

@@ -24,21 +24,18 @@ struct FusedArgs {
     int64_t N, nM, nT, nC;
 };
 
-// MRPHY_K2_TRAJ: a unit that defines it to 1 before including this fragment (tu_fused_traj_fwd*.hip) gets K2t instead,
-// k_bloch_rfgr_traj_fwd -- the trajectory builds of mrphy_blochsim_rfgr_traj_fwd.  The additions sit in `#if` blocks,
-// so the units of the shipped K2 compile exactly the tokens they always did (same code, register for register).
+// The trajectory builds (K2t, mrphy_blochsim_rfgr_traj_fwd) are the same kernel with TR > 0 and FusedTrajArgs;
+// TR == 0 is the plain K2, whose step loop holds none of the additions (`if constexpr`) and whose kernarg layout
+// stays FusedArgs.
 // TR: 1 = M after EVERY step into Mt, stored inside the unrolled step batch; 2 = M after steps every-1, 2 every-1, ...
 // (a running destination and the next step, as the checkpoints: no 64-bit division in the loop) and after step nT-1.
 // Record j is M after step min((j+1) every, nT) - 1, time-major: Mt[j] is (N*nM, 3), 768 B per wave and record.
-#ifndef MRPHY_K2_TRAJ
-#define MRPHY_K2_TRAJ 0
-#endif
-#if MRPHY_K2_TRAJ
 template <typename T>
 struct FusedTrajArgs : FusedArgs<T> {
     T* Mt;   int64_t every;                              // (nRec, N*nM, 3), nRec = ceil(nT / every)
 };
-#endif
+template <typename T, int TR>
+using FusedArgsT = std::conditional_t<TR == 0, FusedArgs<T>, FusedTrajArgs<T>>;
 
 // CK: write checkpoints (every ck_every steps, a multiple of the 8-step chunk).  Kept out of the
 // plain instantiation so that its step loop contains no store: the pulse loads are then provably
@@ -55,14 +52,31 @@ constexpr int K2_MAXC = 64;                              // largest register/LDS
 // the product returns rf bit for bit anyway, so results are unchanged.  A template parameter, not a
 // run-time test: a wave-uniform branch in the field assembly broke the batching of the pulse's scalar
 // loads (round 1: 6.6 -> 7.2 ms).
-#if MRPHY_K2_TRAJ
-template <typename T, typename CT, int NCM, bool CK, bool RELAX, bool HB1, int TR>
-__global__ __launch_bounds__(WAVE) void k_bloch_rfgr_traj_fwd(FusedTrajArgs<T> a)
-#else
-template <typename T, typename CT, int NCM, bool CK, bool RELAX, bool HB1 = true>
-__global__ __launch_bounds__(WAVE) void k_bloch_rfgr_fwd(FusedArgs<T> a)
-#endif
+// K2t: M after step t into the running record destination mtp if a record is taken there (TR == 1: after every step;
+// TR == 2: after the step `next`, which then moves on by `every`)
+template <int TR, typename T>
+__device__ __forceinline__ void traj_record(int64_t t, bool valid, T mx, T my, T mz, T*& mtp, int64_t pitch,
+                                            int64_t& next, int64_t every)
 {
+    if constexpr (TR == 1) {
+        if (valid) { mtp[0] = mx; mtp[1] = my; mtp[2] = mz; }
+        mtp += pitch;
+    } else {
+        if (t == next) {                                      // wave-uniform
+            if (valid) { mtp[0] = mx; mtp[1] = my; mtp[2] = mz; }
+            mtp += pitch; next += every;
+        }
+    }
+}
+
+template <typename T, typename CT, int NCM, bool CK, bool RELAX, bool HB1, int TR>
+__global__ __launch_bounds__(WAVE) void k_bloch_rfgr_fwd(FusedArgsT<T, TR> a)
+{
+    // trajectory state (TR > 0, set before the loop): running destination, and (TR == 2) the step after which the next
+    // record is taken.  Declared first and left uninitialised: dead locals further down reorder LLVM's promotion of the
+    // others in the plain build, and with it the register assignment of nearly every TR == 0 kernel
+    T* mtp;
+    int64_t tr_every, tr_next;
     constexpr int NS = (sizeof(T) == 8 && NCM == 1) ? 4 : 8;   // fp64, one coil: 8 steps' pulse samples (80 SGPRs) spill to VGPR lanes
     constexpr bool NC1 = (NCM == 1);
     constexpr bool NCR = (NCM >= 2);                     // coils in registers / LDS
@@ -147,28 +161,12 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_fwd(FusedArgs<T> a)
     // The checkpoint build: all of the prologue's vector loads are awaited HERE, before the loop.  Otherwise the
     // wait for them lands in the loop header (the join of the prologue and the back edge) as s_waitcnt
     // vmcnt(0), where it also waits, every 8 steps, for the checkpoint store of the iteration before.
+    if constexpr (TR != 0) { mtp = a.Mt + row * 3; tr_every = a.every; tr_next = tr_every - 1; }
     if (CK) __builtin_amdgcn_s_waitcnt(0x0F70);         // vmcnt(0), expcnt / lgkmcnt untouched (gfx9 encoding)
     int64_t ck_next = 0;
     T* ckp = CK ? a.Mck + row * 3 : nullptr;
     const int64_t ck_pitch = rows * 3;
     int64_t t0 = 0;
-#if MRPHY_K2_TRAJ
-    // trajectory records: running destination, and (TR == 2) the step after which the next one is taken
-    T* mtp = a.Mt + row * 3;
-    const int64_t tr_every = a.every;
-    int64_t tr_next = tr_every - 1;
-    auto record = [&](int64_t t) {
-        if constexpr (TR == 1) {
-            if (valid) { mtp[0] = mx; mtp[1] = my; mtp[2] = mz; }
-            mtp += ck_pitch;
-        } else {
-            if (t == tr_next) {                               // wave-uniform
-                if (valid) { mtp[0] = mx; mtp[1] = my; mtp[2] = mz; }
-                mtp += ck_pitch; tr_next += tr_every;
-            }
-        }
-    };
-#endif
     for (; t0 + NS <= nT; t0 += NS) {
         if (NCR) { tstage = t0; stage_rf(t0, NS); }
         if (CK && t0 == ck_next) {
@@ -181,11 +179,10 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_fwd(FusedArgs<T> a)
         Rot<T> r[NS];
         rot_prepare<T, CT, NS>(k, Bx, By, Bz, r);
 #pragma unroll
-#if MRPHY_K2_TRAJ
-        for (int j = 0; j < NS; ++j) { rot_apply<RELAX, T, CT>(k, r[j], mx, my, mz); record(t0 + j); }
-#else
-        for (int j = 0; j < NS; ++j) rot_apply<RELAX, T, CT>(k, r[j], mx, my, mz);
-#endif
+        for (int j = 0; j < NS; ++j) {
+            rot_apply<RELAX, T, CT>(k, r[j], mx, my, mz);
+            if constexpr (TR != 0) traj_record<TR>(t0 + j, valid, mx, my, mz, mtp, ck_pitch, tr_next, tr_every);
+        }
     }
     if (NCR && t0 < nT) { tstage = t0; stage_rf(t0, (int)(nT - t0)); }
     for (; t0 < nT; ++t0) {                                   // nT % 8 tail
@@ -198,17 +195,53 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_fwd(FusedArgs<T> a)
         Rot<T> r[1];
         rot_prepare<T, CT, 1>(k, Bx, By, Bz, r);
         rot_apply<RELAX, T, CT>(k, r[0], mx, my, mz);
-#if MRPHY_K2_TRAJ
-        record(t0);
-#endif
+        if constexpr (TR != 0) traj_record<TR>(t0, valid, mx, my, mz, mtp, ck_pitch, tr_next, tr_every);
     }
-#if MRPHY_K2_TRAJ
     // the last record is M after step nT - 1 whatever `every` is: TR == 2 took it in the loop iff every | nT.  Mo is
-    // optional here (it equals that record)
-    if (TR == 2 && tr_next - tr_every != nT - 1 && valid) { mtp[0] = mx; mtp[1] = my; mtp[2] = mz; }
-    if (valid && a.Mo) { a.Mo[row * 3] = mx; a.Mo[row * 3 + 1] = my; a.Mo[row * 3 + 2] = mz; }
-#else
-    if (valid) { a.Mo[row * 3] = mx; a.Mo[row * 3 + 1] = my; a.Mo[row * 3 + 2] = mz; }
-#endif
+    // optional in the trajectory builds (it equals that record)
+    if constexpr (TR == 2) {
+        if (tr_next - tr_every != nT - 1 && valid) { mtp[0] = mx; mtp[1] = my; mtp[2] = mz; }
+    }
+    if (valid && (TR == 0 || a.Mo)) { a.Mo[row * 3] = mx; a.Mo[row * 3 + 1] = my; a.Mo[row * 3 + 2] = mz; }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Host side of K2, shared by the launchers of tu_fused_fwd.hip and tu_fused_fwd1.hip.  A null Mt selects the plain
+// kernel (TR == 0), which takes the FusedArgs part of the arguments; otherwise `every` picks TR.
+// ---------------------------------------------------------------------------------------------
+template <typename T>
+FusedTrajArgs<T> fused_args(const void* Mi, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
+                            const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2,
+                            const void* E1m1, void* Mo, void* Mck, int64_t ck_every, void* Mt, int64_t every,
+                            int64_t N, int64_t nM, int64_t nT, int64_t nC)
+{
+    FusedTrajArgs<T> a;
+    a.Mi = (const T*)Mi; a.rf = (const T*)rf; a.rf_sn = rf_sn; a.gr = (const T*)gr;
+    a.gr_sn = gr_sn; a.loc = (const T*)loc; a.df = df; a.gam = gam; a.b1 = (const T*)b1;
+    a.g = g; a.E1 = E1; a.E2 = E2; a.E1m1 = E1m1; a.Mo = (T*)Mo; a.Mck = (T*)Mck;
+    a.ck_every = ck_every > 0 ? ck_every : 1;
+    a.N = N; a.nM = nM; a.nT = nT; a.nC = nC;
+    a.Mt = (T*)Mt; a.every = every;
+    return a;
+}
+
+// the build of coil capacity NCM for the checkpoint, relaxation and trajectory modes of `a`
+template <typename T, typename CT, int NCM, bool HB1>
+void launch_k2(const FusedTrajArgs<T>& a, hipStream_t st)
+{
+    const dim3 grid((unsigned)((a.nM + WAVE - 1) / WAVE), (unsigned)a.N);
+#define MRPHY_K2(CK_, RX_, TR_)                                                                         \
+    hipLaunchKernelGGL((k_bloch_rfgr_fwd<T, CT, NCM, CK_, RX_, HB1, TR_>), grid, dim3(WAVE), 0, st, \
+                       (static_cast<const FusedArgsT<T, TR_>&>(a)))
+#define MRPHY_K2T(CK_, RX_)                                                                                 \
+    do {                                                                                                    \
+        if (!a.Mt) MRPHY_K2(CK_, RX_, 0);                                                                   \
+        else if (a.every == 1) MRPHY_K2(CK_, RX_, 1);                                                       \
+        else MRPHY_K2(CK_, RX_, 2);                                                                         \
+    } while (0)
+    const bool ck = (a.Mck != nullptr), rx = (a.E1.p != nullptr);
+    if (ck) { if (rx) MRPHY_K2T(true, true); else MRPHY_K2T(true, false); }
+    else    { if (rx) MRPHY_K2T(false, true); else MRPHY_K2T(false, false); }
+#undef MRPHY_K2T
+#undef MRPHY_K2
+}

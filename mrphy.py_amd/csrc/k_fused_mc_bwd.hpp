@@ -22,13 +22,8 @@
 // wave-uniform branch and an exposed LDS round trip per coil, twice per step in the field alone; K0 and
 // K2 had been rid of that in round 2).  Adding exact zeros changes nothing (at most the sign of a zero
 // sum): the recomputed states stay those of K2's forward.
-#if MRPHY_K2B_TRAJ
 template <typename T, typename CT, bool RELAX, int MC, int INJ>
-__global__ __launch_bounds__(WAVE) void k_bloch_rfgr_traj_bwd_mc(FusedBwdTrajArgs<T> a, int nC)
-#else
-template <typename T, typename CT, bool RELAX, int MC>
-__global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd_mc(FusedBwdArgs<T> a, int nC)
-#endif
+__global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd_mc(FusedBwdArgsT<T, INJ> a, int nC)
 {
     constexpr int K2B_NCF = 2 * MC + 3;             // coefficient rows: b1r[c], b1i[c], loc x y z
     // NOT generic in SEG: the workspace update and the dot products below take their step from the lane as
@@ -81,15 +76,13 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd_mc(FusedBwdArgs<T> a, i
         cfs[(2 * MC + 0) * WAVE + lane] = lx * vmask;
         cfs[(2 * MC + 1) * WAVE + lane] = ly * vmask;
         cfs[(2 * MC + 2) * WAVE + lane] = lz * vmask;
-#if MRPHY_K2B_TRAJ
-        const T* gM = a.gMo + (a.nRec - 1) * rows * 3;             // the last record is Mo
+        // grad_Mo; in the trajectory builds grad_Mt, whose last record is Mo
+        const T* gM = a.gMo;
+        if constexpr (INJ != 0) gM += (a.nRec - 1) * rows * 3;
         T hx = gM[row * 3], hy = gM[row * 3 + 1], hz = gM[row * 3 + 2];
-        // the latest record not yet injected: index jr, taken after step er (both wave-uniform)
-        const int64_t every = a.every;
-        int64_t jr = a.nRec - 2, er = (a.nRec - 1) * every - 1;
-#else
-        T hx = a.gMo[row * 3], hy = a.gMo[row * 3 + 1], hz = a.gMo[row * 3 + 2];
-#endif
+        // trajectory: the latest record not yet injected, index jr, taken after step er (both wave-uniform)
+        int64_t every = 0, jr = 0, er = 0;
+        if constexpr (INJ != 0) { every = a.every; jr = a.nRec - 2; er = (a.nRec - 1) * every - 1; }
         adj_begin<RELAX, T, CT>(k, hx, hy, hz);
 
         int64_t tstage = 0;
@@ -125,7 +118,6 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd_mc(FusedBwdArgs<T> a, i
                 const T* ck = a.Mck + ((seg - 1) * rows + row) * 3;
                 cx = ck[0]; cy = ck[1]; cz = ck[2];
             }
-#if MRPHY_K2B_TRAJ
             // the trajectory cotangents of this segment.  INJ == 2: at most one, at step ist of the segment (-1: none),
             // in registers, requested here and used in the sweep after the recompute.  INJ == 1: the lane's cotangent of
             // step st goes to the slots raw[(0|1|2) SEG + st][lane] that the sweep overwrites at that very step with
@@ -140,7 +132,7 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd_mc(FusedBwdArgs<T> a, i
                     ijx = q[0]; ijy = q[1]; ijz = q[2];
                     ist = (int)(er - t0); --jr; er -= every;
                 }
-            } else {
+            } else if constexpr (INJ == 1) {
                 T gv[SEG][3];
 #pragma unroll
                 for (int st = SEG - 1; st >= 0; --st) {
@@ -158,7 +150,6 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd_mc(FusedBwdArgs<T> a, i
                     raw[red_idx(2 * SEG + st, lane)] = gv[st][2];
                 }
             }
-#endif
             // old workspace values of the rows this lane updates at the end of the segment
             const int st_w = lane >> 2, ri_w = (lane >> 1) & 1;
             const bool wr_w = (lane & 1) == 0;
@@ -197,13 +188,12 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd_mc(FusedBwdArgs<T> a, i
 #pragma unroll
                 for (int j = 3; j >= 0; --j) {
                     const int st = sb * 4 + j;
-#if MRPHY_K2B_TRAJ
                     if constexpr (INJ == 1)
                         adj_inject<RELAX, T, CT>(k, hx, hy, hz, raw[red_idx(0 * SEG + st, lane)],
                                                  raw[red_idx(1 * SEG + st, lane)], raw[red_idx(2 * SEG + st, lane)]);
-                    else if (st == ist)
-                        adj_inject<RELAX, T, CT>(k, hx, hy, hz, ijx, ijy, ijz);
-#endif
+                    else if constexpr (INJ == 2) {
+                        if (st == ist) adj_inject<RELAX, T, CT>(k, hx, hy, hz, ijx, ijy, ijz);
+                    }
                     T g0, g1, g2;
                     rot_apply_adj<RELAX, T, CT>(k, ra[j], M0[st], M1[st], M2[st], hx, hy, hz,
                                                 g0, g1, g2);

@@ -1,4 +1,5 @@
-// tu_fused_bwd.hip -- K2b: launcher of mrphy_blochsim_rfgr_bwd (one transmit coil)
+// tu_fused_bwd.hip -- K2b and its trajectory builds K2bt: launcher of mrphy_blochsim_rfgr_bwd and _traj_bwd
+// (one transmit coil)
 #include "host_common.hpp"
 
 namespace {
@@ -10,24 +11,27 @@ namespace mrphy_i {
 template <typename T, typename CT>
 int run_rfgr_bwd(const void* Mck, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
                  const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2,
-                 const void* E1m1, const void* gMo, void* gMi, void* grf, void* ggr, void* work,
-                 int64_t N, int64_t nM, int64_t nT, hipStream_t st)
+                 const void* E1m1, const void* gMo, const void* gMt, int64_t every, void* gMi, void* grf,
+                 void* ggr, void* work, int64_t N, int64_t nM, int64_t nT, hipStream_t st)
 {
-    FusedBwdArgs<T> a;
-    a.Mck = (const T*)Mck; a.rf = (const T*)rf; a.rf_sn = rf_sn; a.gr = (const T*)gr;
-    a.gr_sn = gr_sn; a.loc = (const T*)loc; a.df = df; a.gam = gam; a.b1 = (const T*)b1;
-    a.g = g; a.E1 = E1; a.E2 = E2; a.E1m1 = E1m1; a.gMo = (const T*)gMo; a.gMi = (T*)gMi;
-    a.work = (T*)work; a.N = N; a.nM = nM; a.nT = nT; a.P = k2b_waves(nM);
     if (N * nM * nT == 0) return 0;
     if (N > 65535) return MRPHY_EINVAL;
+    const FusedBwdTrajArgs<T> a = fused_bwd_args<T>(Mck, rf, rf_sn, gr, gr_sn, loc, df, gam, b1, g, E1, E2, E1m1, gMo,
+                                                    gMt, every, gMi, work, N, nM, nT, k2b_waves(nM));
     const dim3 grid((unsigned)a.P, (unsigned)N);
-    if (b1) {
-        if (E1.p) hipLaunchKernelGGL((k_bloch_rfgr_bwd<T, CT, true, true>), grid, dim3(WAVE), 0, st, a);
-        else      hipLaunchKernelGGL((k_bloch_rfgr_bwd<T, CT, false, true>), grid, dim3(WAVE), 0, st, a);
-    } else {                                             // no b1 map: Bxy = rf
-        if (E1.p) hipLaunchKernelGGL((k_bloch_rfgr_bwd<T, CT, true, false>), grid, dim3(WAVE), 0, st, a);
-        else      hipLaunchKernelGGL((k_bloch_rfgr_bwd<T, CT, false, false>), grid, dim3(WAVE), 0, st, a);
-    }
+#define MRPHY_K2B(RX_, HB_, INJ_)                                                               \
+    hipLaunchKernelGGL((k_bloch_rfgr_bwd<T, CT, RX_, HB_, INJ_>), grid, dim3(WAVE), 0, st, \
+                       (static_cast<const FusedBwdArgsT<T, INJ_>&>(a)))
+#define MRPHY_K2BT(RX_, HB_)                                                                    \
+    do {                                                                                        \
+        if (!gMt) MRPHY_K2B(RX_, HB_, 0);                                                       \
+        else if (every < SEG) MRPHY_K2B(RX_, HB_, 1);                                           \
+        else MRPHY_K2B(RX_, HB_, 2);                                                            \
+    } while (0)
+    if (b1) { if (E1.p) MRPHY_K2BT(true, true);  else MRPHY_K2BT(false, true); }
+    else    { if (E1.p) MRPHY_K2BT(true, false); else MRPHY_K2BT(false, false); }   // no b1 map: Bxy = rf
+#undef MRPHY_K2BT
+#undef MRPHY_K2B
     int e = launch_status();
     if (e) return e;
     if (grf || ggr) {
@@ -41,6 +45,6 @@ int run_rfgr_bwd(const void* Mck, const void* rf, int64_t rf_sn, const void* gr,
 
 }  // namespace mrphy_i
 
-#define MRPHY_INST(T_, CT_) template int mrphy_i::run_rfgr_bwd<T_, CT_>(const void* Mck, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn, const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2, const void* E1m1, const void* gMo, void* gMi, void* grf, void* ggr, void* work, int64_t N, int64_t nM, int64_t nT, hipStream_t st);
+#define MRPHY_INST(T_, CT_) template int mrphy_i::run_rfgr_bwd<T_, CT_>(const void* Mck, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn, const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2, const void* E1m1, const void* gMo, const void* gMt, int64_t every, void* gMi, void* grf, void* ggr, void* work, int64_t N, int64_t nM, int64_t nT, hipStream_t st);
 MRPHY_FOR_DTYPES(MRPHY_INST)
 #undef MRPHY_INST

@@ -1,4 +1,4 @@
-// tu_fused_mc_bwd.hip -- K2b, 2..8 transmit coils: launcher of mrphy_blochsim_rfgr_mc_bwd
+// tu_fused_mc_bwd.hip -- K2b and K2bt, 2..8 transmit coils: launcher of mrphy_blochsim_rfgr_mc_bwd and _mc_traj_bwd
 #include "host_common.hpp"
 
 namespace {
@@ -10,26 +10,33 @@ namespace mrphy_i {
 template <typename T, typename CT>
 int run_rfgr_mc_bwd(const void* Mck, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
                     const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2,
-                    const void* E1m1, const void* gMo, void* gMi, void* grf, void* ggr, void* work,
-                    int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st)
+                    const void* E1m1, const void* gMo, const void* gMt, int64_t every, void* gMi, void* grf,
+                    void* ggr, void* work, int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st)
 {
-    FusedBwdArgs<T> a;
-    a.Mck = (const T*)Mck; a.rf = (const T*)rf; a.rf_sn = rf_sn; a.gr = (const T*)gr;
-    a.gr_sn = gr_sn; a.loc = (const T*)loc; a.df = df; a.gam = gam; a.b1 = (const T*)b1;
-    a.g = g; a.E1 = E1; a.E2 = E2; a.E1m1 = E1m1; a.gMo = (const T*)gMo; a.gMi = (T*)gMi;
-    a.work = (T*)work; a.N = N; a.nM = nM; a.nT = nT; a.P = k2b_mc_waves(nM);
     if (N * nM * nT == 0) return 0;
     if (N > 65535) return MRPHY_EINVAL;
+    const FusedBwdTrajArgs<T> a = fused_bwd_args<T>(Mck, rf, rf_sn, gr, gr_sn, loc, df, gam, b1, g, E1, E2, E1m1, gMo,
+                                                    gMt, every, gMi, work, N, nM, nT, k2b_mc_waves(nM));
     const dim3 grid((unsigned)a.P, (unsigned)N);
-    // the smallest coil capacity (2 / 4 / 8) that holds nC: the build's loops run over all of it, on zeros
-#define MRPHY_K2BMC(MC_)                                                                                       \
-    do {                                                                                                       \
-        if (E1.p) hipLaunchKernelGGL((k_bloch_rfgr_bwd_mc<T, CT, true, MC_>), grid, dim3(WAVE), 0, st, a, (int)nC); \
-        else      hipLaunchKernelGGL((k_bloch_rfgr_bwd_mc<T, CT, false, MC_>), grid, dim3(WAVE), 0, st, a, (int)nC); \
+#define MRPHY_K2BMC(RX_, MC_, INJ_)                                                                 \
+    hipLaunchKernelGGL((k_bloch_rfgr_bwd_mc<T, CT, RX_, MC_, INJ_>), grid, dim3(WAVE), 0, st, \
+                       (static_cast<const FusedBwdArgsT<T, INJ_>&>(a)), (int)nC)
+    // fp64 at 8 coils: the register build of INJ == 2 (three cotangents held across the recompute) spills -- that one
+    // takes the LDS-staged injection, which is correct for any stride
+#define MRPHY_K2BMCT(RX_, MC_)                                                                      \
+    do {                                                                                            \
+        constexpr bool lds_only = sizeof(T) == 8 && MC_ == 8;                                       \
+        if (!gMt) MRPHY_K2BMC(RX_, MC_, 0);                                                         \
+        else if (lds_only || every < SEG) MRPHY_K2BMC(RX_, MC_, 1);                                 \
+        else if constexpr (!lds_only) MRPHY_K2BMC(RX_, MC_, 2);                                     \
     } while (0)
-    if (nC <= 2) MRPHY_K2BMC(2);
-    else if (nC <= 4) MRPHY_K2BMC(4);
-    else MRPHY_K2BMC(8);
+    // the smallest coil capacity (2 / 4 / 8) that holds nC: the build's loops run over all of it, on zeros
+#define MRPHY_K2BMCR(MC_) do { if (E1.p) MRPHY_K2BMCT(true, MC_); else MRPHY_K2BMCT(false, MC_); } while (0)
+    if (nC <= 2) MRPHY_K2BMCR(2);
+    else if (nC <= 4) MRPHY_K2BMCR(4);
+    else MRPHY_K2BMCR(8);
+#undef MRPHY_K2BMCR
+#undef MRPHY_K2BMCT
 #undef MRPHY_K2BMC
     int e = launch_status();
     if (e) return e;
@@ -45,6 +52,6 @@ int run_rfgr_mc_bwd(const void* Mck, const void* rf, int64_t rf_sn, const void* 
 
 }  // namespace mrphy_i
 
-#define MRPHY_INST(T_, CT_) template int mrphy_i::run_rfgr_mc_bwd<T_, CT_>(const void* Mck, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn, const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2, const void* E1m1, const void* gMo, void* gMi, void* grf, void* ggr, void* work, int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st);
+#define MRPHY_INST(T_, CT_) template int mrphy_i::run_rfgr_mc_bwd<T_, CT_>(const void* Mck, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn, const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2, const void* E1m1, const void* gMo, const void* gMt, int64_t every, void* gMi, void* grf, void* ggr, void* work, int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st);
 MRPHY_FOR_DTYPES(MRPHY_INST)
 #undef MRPHY_INST
