@@ -18,7 +18,9 @@ int run_rfgr2beff_bwd(const void* gB, const void* loc, const void* b1, void* grf
     a.nSG = bwd_spin_groups(nM);
     a.spins_per_group = (nM + a.nSG - 1) / a.nSG;
     if (N * nT == 0) return 0;
-    if (N * (nC + 1) > 65535 || 3 + 2 * nC > 65535) return MRPHY_EINVAL;
+    // grid limits (65535 in y and z): the batch entry is blockIdx.z of every pass -- N <= 65535, the documented limit --
+    // and pass 2 has one row of blocks per partial row; only the generic pass 1 below folds the coil part into z
+    if (N > 65535 || 3 + 2 * nC > 65535) return MRPHY_EINVAL;
     const unsigned tx = (unsigned)((nT + 255) / 256);
     if (nC == 1) {                                       // vector-load path
         const int64_t L = 3 * nT;
@@ -78,6 +80,7 @@ int run_rfgr2beff_bwd(const void* gB, const void* loc, const void* b1, void* grf
                            dim3(256), 0, st, a);
         return launch_status();
     }
+    if (N * (nC + 1) > 65535) return MRPHY_EINVAL;
     hipLaunchKernelGGL((k_rfgr2beff_bwd_p1<T>), dim3(tx, (unsigned)a.nSG, (unsigned)(N * (nC + 1))),
                        dim3(256), 0, st, a);
     int e = launch_status();

@@ -197,3 +197,138 @@ def mask_case(dtype, Nd=(5, 6, 7), N: int = 2):
     ofst = torch.tensor([[0., 0.5, -1.25], [2., 0., 0.125]], dtype=f64)[:N].to(dtype)
     return dict(shape=(N,) + Nd, Nd=Nd, N=N, nV=nV, nM=nM, mask=mask, spatial=spatial,
                 compact=compact, fov=fov, ofst=ofst)
+
+
+# ---------------------------------------------------------------------------------------------
+# The fused route's operand zoo and the zero-field case (tests/test_fused_operands.py; goldens:
+# make_golden.py gen_fusedops)
+# ---------------------------------------------------------------------------------------------
+FUSED_N, FUSED_ND = 2, (5, 4, 7)
+FUSED_NM = 140                        # two full waves plus a ragged 12
+FUSED_COILS = (0, 1, 4)               # 0: one coil, no b1Map; 1: one coil with a map; 4: parallel transmit
+FUSED_NT53 = ('compact_mixed', 'cube_planes', 'views')       # repeated at nT = 53: fused part + 5 composed steps
+
+
+def _after(x, n: int = 1):
+    r"""The same contiguous values starting ``n`` elements into a larger buffer."""
+    buf = torch.zeros(x.numel() + n + 3, dtype=x.dtype)
+    y = buf[n:n + x.numel()].view(x.shape)
+    y.copy_(x)
+    return y
+
+
+def fused_dense(v: dict):
+    r"""Every operand of a variant materialised over ``(N, nM[, ...])``, contiguous: ``.expand(...).contiguous()``
+    of the given form, so the numbers are the given ones (a cube's spins flattened in row-major order)."""
+    N, Nd = v['loc'].shape[0], tuple(v['loc'].shape[1:-1])
+    N = max(N, v['M0'].shape[0])
+    nM, lead = 1, 1 + len(Nd)
+    for d in Nd:
+        nM *= d
+    out = dict(v)
+    for k in ('Δf', 'γ_beff', 'T1', 'T2', 'γ'):
+        x = v.get(k)
+        if x is not None:
+            x = x.reshape(tuple(x.shape) + (lead - x.ndim) * (1,))
+            out[k] = x.expand((N,) + Nd).reshape(N, nM).contiguous()
+    if v.get('b1Map') is not None:
+        b = v['b1Map']
+        tail = tuple(b.shape[lead:])
+        out['b1Map'] = b.expand((N,) + Nd + tail).reshape((N, nM) + tail).contiguous()
+    for k in ('M0', 'loc', 'w'):
+        out[k] = v[k].expand((N,) + Nd + (3,)).reshape(N, nM, 3).contiguous()
+    for k in ('rf', 'gr'):
+        out[k] = v[k].expand((N,) + tuple(v[k].shape[1:])).contiguous()
+    out['dt'] = v['dt'].reshape(-1).expand(N).contiguous()
+    return out
+
+
+def fused_operand_variants(dtype, nC: int, nT: int = 48, seed: int = 29):
+    r"""One problem class, many spellings: ``{name: (as_given, dense)}`` for ``fused.blochsim_rfgr`` / ``_traj``.
+    N = 2, 140 spins per batch entry, ``nC`` in :data:`FUSED_COILS`.  A variant is a dict ``M0, rf, gr, loc, Δf, b1Map,
+    γ_beff, T1, T2, γ, dt`` and the loss cotangent ``w``; ``dense`` is :func:`fused_dense` of it.  CPU tensors; a view
+    keeps its strides and storage offset on a device through ``tests/gpu_common.py: place``."""
+    assert nC in FUSED_COILS
+    gen = torch.Generator(device='cpu').manual_seed(seed + 100 * nC + nT)
+    u = lambda *s: torch.rand(s, generator=gen, dtype=torch.float64)        # noqa: E731
+    N, nM, Nd = FUSED_N, FUSED_NM, FUSED_ND
+    cd = (nC,) if nC > 1 else ()
+    c = lambda x: x.to(dtype)                                                # noqa: E731
+    M0 = lambda *s: c(u(*s, 3) * 2 - 1)                                      # noqa: E731
+    loc = lambda *s: c((u(*s, 3) * 2 - 1) * 6)                               # noqa: E731
+    rf = lambda n, T=nT: c((u(n, 2, T, *cd) * 2 - 1) * (1.5 if nC > 1 else 3))   # noqa: E731
+    gr = lambda n, T=nT: c(u(n, 3, T) * 2 - 1)                               # noqa: E731
+    df = lambda *s: c((u(*s) * 2 - 1) * 200)                                 # noqa: E731
+    t1 = lambda *s: c(0.5 + u(*s))                                           # noqa: E731
+    t2 = lambda *s: c(0.02 + 0.1 * u(*s))                                    # noqa: E731
+    gm = lambda *s: c(γH_val * (0.9 + 0.2 * u(*s)))                          # noqa: E731
+    b1 = lambda *s, coil=True: (None if nC == 0 else                         # noqa: E731
+                                c((u(*s, 2, *((max(nC, 1),) if coil else ())) * 2 - 1) * (0.7 if nC > 1 else 1)))
+    wt = lambda *s: c(u(*s, 3) * 2 - 1)                                      # noqa: E731
+    dt1 = tensor([dt0_val], dtype=dtype)
+    dtN = c(dt0_val * (1 + u(N)))
+    v = {}
+    v['compact_mixed'] = dict(M0=M0(N, nM), rf=rf(1), gr=gr(N), loc=loc(N, nM), Δf=df(N, 1), γ_beff=gm(1, nM),
+                              b1Map=b1(1, nM, coil=nC > 1), T1=t1(N, 1), T2=t2(N, 1), γ=gm(1, nM), dt=dtN, w=wt(N, nM))
+    v['scalars'] = dict(M0=M0(N, nM), rf=rf(N), gr=gr(1), loc=loc(N, nM), Δf=df().reshape(()),
+                        γ_beff=tensor(γH_val, dtype=torch.float64), b1Map=b1(N, 1), T1=t1(1, 1), T2=t2(1, 1),
+                        γ=gm().reshape(()), dt=tensor(dt0_val, dtype=dtype), w=wt(N, nM))
+    ex = lambda x: None if x is None else x.expand((N, nM) + tuple(x.shape[2:]))   # noqa: E731
+    v['expanded'] = dict(M0=M0(N, nM), rf=rf(N), gr=gr(N), loc=ex(loc(1, nM)), Δf=ex(df(N, 1)), γ_beff=ex(gm(1, 1)),
+                         b1Map=ex(b1(1, nM)), T1=ex(t1(N, 1)), T2=ex(t2(1, 1)), γ=ex(gm(1, nM)), dt=dt1, w=wt(N, nM))
+    v['cube'] = dict(M0=M0(N, *Nd), rf=rf(N), gr=gr(N), loc=loc(N, *Nd), Δf=df(N, 1, 1, 1), γ_beff=gm(1, *Nd),
+                     b1Map=b1(N, *Nd), T1=t1(1, *Nd), T2=t2(1, *Nd), γ=gm(N, 1, 1, 1), dt=dtN, w=wt(N, *Nd))
+    v['cube_planes'] = dict(M0=M0(N, *Nd), rf=rf(1), gr=gr(1), loc=loc(N, *Nd), Δf=df(N, 5, 1, 1),
+                            γ_beff=gm(1, 1, 4, 7), b1Map=b1(1, *Nd), T1=t1(N, 5), T2=t2(N, 5), γ=gm().reshape(()),
+                            dt=dt1, w=wt(N, *Nd))
+    v['gamma_split'] = dict(M0=M0(N, nM), rf=rf(N), gr=gr(N), loc=loc(N, nM), Δf=df(N, nM), γ_beff=gm(N, nM),
+                            b1Map=b1(N, nM), T1=t1(N, 1), T2=t2(N, 1), γ=gm(N, nM), dt=dt1, w=wt(N, nM))
+    long_rf, long_gr = rf(N, nT + 9), gr(N, nT + 9)
+    # permuted views, time slices of a longer pulse, a non-contiguous cotangent
+    v['views'] = dict(M0=c(u(3, N, nM) * 2 - 1).permute(1, 2, 0), rf=long_rf[:, :, 4:4 + nT], gr=long_gr[:, :, 4:4 + nT],
+                      loc=c((u(3, nM, N) * 2 - 1) * 6).permute(2, 1, 0), Δf=df(nM, N).t(), γ_beff=gm(N, nM),
+                      b1Map=b1(N, nM), T1=t1(N, nM), T2=t2(N, nM), γ=gm(1, 1), dt=dt1,
+                      w=c(u(N, 3, nM) * 2 - 1).transpose(1, 2))
+    v['offset'] = dict(M0=_after(M0(N, nM)), rf=_after(rf(N)), gr=_after(gr(N)), loc=_after(loc(N, nM)), Δf=df(N, nM),
+                       γ_beff=gm(1, 1), b1Map=b1(N, nM), T1=t1(N, nM), T2=t2(N, nM), γ=gm(1, 1), dt=dt1,
+                       w=_after(wt(N, nM)))
+    return {k: (d, fused_dense(d)) for k, d in v.items()}
+
+
+# zero-field steps (0-based, inclusive): every batch entry; batch entry 1 also a whole checkpoint segment
+ZERO_STEPS = tuple(range(0, 5)) + tuple(range(14, 19)) + tuple(range(44, 48))
+ZERO_SEGMENT = tuple(range(16, 32))
+ZERO_RF_ONLY = (8, 9, 10)              # rf = 0, gr live: only the spins at loc = 0 are at zero field
+ZERO_SPINS = ((0, 7), (1, 64))         # (batch entry, spin) at loc = 0: mid-wave; first lane of the second tile
+
+
+def zero_field_case(dtype, nC: int, nT: int = 48, seed: int = 31):
+    r"""Dead time through the fused adjoints, sizes as :func:`fused_operand_variants`, no ``Δf``: ``rf = gr = 0`` on
+    :data:`ZERO_STEPS` (leading, straddling the checkpoint boundary at 16, trailing), batch entry 1 also on the whole
+    segment :data:`ZERO_SEGMENT`; ``rf = 0`` alone on :data:`ZERO_RF_ONLY`, where the two spins at ``loc = 0``
+    (:data:`ZERO_SPINS`) are the only lanes of their waves at zero field; with a map, ``b1Map = 0`` for spin 64 of
+    entry 1, which then never rotates.  Returns the operand dict (keys as the variants') and ``zero``, the boolean
+    `(N, nT)` mask of the steps where a batch entry's whole pulse sample is zero."""
+    assert nC in FUSED_COILS
+    gen = torch.Generator(device='cpu').manual_seed(seed + 100 * nC + nT)
+    u = lambda *s: torch.rand(s, generator=gen, dtype=torch.float64)        # noqa: E731
+    N, nM = FUSED_N, FUSED_NM
+    cd = (nC,) if nC > 1 else ()
+    rf = (u(N, 2, nT, *cd) * 2 - 1) * (1.5 if nC > 1 else 3)
+    gr = u(N, 3, nT) * 2 - 1
+    loc = (u(N, nM, 3) * 2 - 1) * 6
+    b1 = None if nC == 0 else (u(N, nM, 2, *cd) * 2 - 1) * (0.7 if nC > 1 else 1)
+    zero = torch.zeros((N, nT), dtype=torch.bool)
+    zero[:, list(ZERO_STEPS)] = True
+    zero[1, list(ZERO_SEGMENT)] = True
+    rf[:, :, list(ZERO_RF_ONLY)] = 0
+    rf.movedim(2, 1)[zero] = 0
+    gr.movedim(2, 1)[zero] = 0
+    for n, s in ZERO_SPINS:
+        loc[n, s] = 0
+    if b1 is not None:
+        b1[1, 64] = 0
+    d = dict(M0=(u(N, nM, 3) * 2 - 1), rf=rf, gr=gr, loc=loc, Δf=None, γ_beff=tensor(γH_val), b1Map=b1,
+             T1=0.5 + u(N, nM), T2=0.02 + 0.1 * u(N, nM), γ=tensor(γH_val), dt=tensor([dt0_val]),
+             w=u(N, nM, 3) * 2 - 1)
+    return {k: (None if x is None else x.to(dtype)) for k, x in d.items()}, zero

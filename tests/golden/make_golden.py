@@ -417,6 +417,61 @@ def gen_refapi(ref, out):
     out['refapi'] = rec
 
 
+def fusedops_entries(dtype):
+    r"""``(key, operands)`` of every fused-operand variant and zero-field case the goldens cover (tests/cases.py)."""
+    for nC in cases.FUSED_COILS:
+        for nT in (48, 53):
+            for name, (given, _) in cases.fused_operand_variants(dtype, nC, nT).items():
+                if nT == 48 or name in cases.FUSED_NT53:
+                    yield f'c{nC}.nT{nT}.{name}', given
+            yield f'c{nC}.nT{nT}.zero_field', cases.zero_field_case(dtype, nC, nT)[0]
+
+
+def run_rfgr_blochsim(rfgr2beff, blochsim, v, grad_Mi=True):
+    r"""``Mo, grad_Mi, grad_rf, grad_gr`` of ``<w, blochsim(Mi, rfgr2beff(rf, gr, loc, ...))>`` on a variant's operands
+    AS GIVEN (views stay views: the leaves are detached aliases, not copies)."""
+    leaf = lambda x, on=True: x.detach().requires_grad_(on)  # noqa: E731
+    Mi, rf, gr = leaf(v['M0'], grad_Mi), leaf(v['rf']), leaf(v['gr'])
+    beff = rfgr2beff(rf, gr, v['loc'], Δf=v['Δf'], b1Map=v['b1Map'], γ=v['γ_beff'])
+    Mo = blochsim(Mi, beff, T1=v['T1'], T2=v['T2'], γ=v['γ'], dt=v['dt'])
+    (Mo * v['w']).sum().backward()
+    return Mo.detach(), Mi.grad, rf.grad, gr.grad
+
+
+def fusedops_reference(ref, v):
+    r"""What the live reference gives on a variant, or why it gives nothing.  It raises ``IndexError`` for any
+    ``b1Map`` on a general ``*Nd`` grid (beffective.py:163-164), and its backward fails where ``γ2πdt`` varies over a
+    cube (the ``γ2πdt[0, ...]`` division of sims.py:267): those variants get NO golden -- their yardsticks are the
+    oracle and the spelling invariance against the compact call (tests/test_fused_operands.py).  ``grad_Mi`` is kept
+    only where that division is right: ``γ`` and ``dt`` uniform (as gen_bcast)."""
+    _, beffective, sims, *_ = ref
+    ok_gMi = v['γ'].numel() == 1 and v['dt'].numel() == 1
+    try:
+        Mo, gMi, grf, ggr = run_rfgr_blochsim(beffective.rfgr2beff, sims.blochsim, v, ok_gMi)
+    except (IndexError, RuntimeError) as e:
+        return None, f'{type(e).__name__}: {str(e).splitlines()[0][:70]}'
+    out = dict(Mo=Mo, grad_rf=grf, grad_gr=ggr)
+    if ok_gMi:
+        out['grad_Mi'] = gMi
+    return out, None
+
+
+def gen_fusedops(ref, out):
+    r"""The reference's own ``rfgr2beff`` + ``sims.blochsim`` on every fused-operand variant and zero-field case it
+    accepts, with the constants of the run (outputs only: a few KB)."""
+    for tag, dtype in DT.items():
+        rec, none = {}, []
+        for key, v in fusedops_entries(dtype):
+            res, why = fusedops_reference(ref, v)
+            if res is None:
+                none.append(f'{key} ({why})')
+                continue
+            rec.update({f'{key}.{k}': np_(x) for k, x in res.items()})
+            put_consts(rec, f'{key}.', v['T1'], v['T2'], v['γ'], v['dt'], v['loc'].ndim + 1)
+        out[f'fusedops_{tag}'] = rec
+        print(f'  fusedops[{tag}]: no golden for', '; '.join(none))
+
+
 # ---------------------------------------------------------------------------------------------
 def check_oracle(ref):
     r"""Function-by-function comparison oracle vs live reference (pinning)."""
@@ -489,6 +544,14 @@ def check_oracle(ref):
             cmp(f'bcast.gB[{tag}]', B2.grad, B.grad, tol)
             if ok_gMi:
                 cmp(f'bcast.gMi[{tag}]', Mi2.grad, Mi.grad, tol)
+        # the fused-operand zoo and the zero-field case: forward bit for bit, the explicit adjoint within `tol`
+        for key, v in fusedops_entries(dtype):
+            res, _ = fusedops_reference(ref, v)
+            if res is None:
+                continue
+            got = dict(zip(('Mo', 'grad_Mi', 'grad_rf', 'grad_gr'), run_rfgr_blochsim(O.rfgr2beff, O.blochsim, v)))
+            for k, x in res.items():
+                cmp(f'fusedops.{k}[{tag}]', got[k], x, exact if k == 'Mo' else tol * max(1.0, float(x.abs().max())))
         # 8f-4: Hargreaves A/B
         c = cases.ref_case(3, dtype)
         E1, E2 = torch.exp(-c['dt'] / c['T1']), torch.exp(-c['dt'] / c['T2'])
@@ -557,7 +620,8 @@ def main():
     out = {}
     gens = dict(ref=gen_ref_cases, rfgr=gen_rfgr, bcast=gen_bcast, onestep=gen_1step,
                 uphi=gen_uphi, freeprec=gen_freeprec, interp=gen_interp, masks=gen_masks, ab=gen_ab,
-                mobjs=gen_mobjs_calls, big=gen_big, beffrows=gen_beffrows, refapi=gen_refapi)
+                mobjs=gen_mobjs_calls, big=gen_big, beffrows=gen_beffrows, refapi=gen_refapi,
+                fusedops=gen_fusedops)
     for name, g in gens.items():
         if a.only and name not in a.only.split(','):
             continue

@@ -41,6 +41,16 @@ def dev(x):
     return None if x is None else x.to(DEV)
 
 
+def place(x, device=DEV):
+    r"""``x`` on the device in the FORM it has on the host: the same shape, strides and storage offset over a copy of its
+    whole storage -- a stride-0 expanded view stays one, a permuted view stays permuted, a slice stays a slice, a tensor
+    that starts one element into its buffer does so there (``.to(device)`` would compact the last two)."""
+    if not isinstance(x, torch.Tensor):
+        return x
+    whole = torch.empty(0, dtype=x.dtype).set_(x.untyped_storage())
+    return whole.to(device).as_strided(tuple(x.shape), x.stride(), x.storage_offset())
+
+
 @pytest.fixture
 def host_constants():
     r"""Golden vectors and the oracle are CPU results: form γ2πdt, E1, E2, E1-1 with the same

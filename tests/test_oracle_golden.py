@@ -339,3 +339,103 @@ def test_oracle_single_precision_field_is_the_reference_beff(cfg):
     sl = slice(0, idx.numel())
     f = C.field_f32(pulse['rf'], pulse['gr'], sp['loc'][:, sl], Δf=sp['Δf'][:, sl], γ_beff=sp['γ'])
     assert torch.equal(f, want)
+
+
+# ---------------------------------------------------------------------------------------------
+# The fused route's operand zoo and the zero-field case (tests/cases.py; GPU side: test_fused_operands.py)
+# ---------------------------------------------------------------------------------------------
+def fusedops_entries(dtype):
+    r"""``(key, operands)`` in the order and naming of ``make_golden.py: fusedops_entries``."""
+    for nC in cases.FUSED_COILS:
+        for nT in (48, 53):
+            for name, (given, _) in cases.fused_operand_variants(dtype, nC, nT).items():
+                if nT == 48 or name in cases.FUSED_NT53:
+                    yield f'c{nC}.nT{nT}.{name}', given
+            yield f'c{nC}.nT{nT}.zero_field', cases.zero_field_case(dtype, nC, nT)[0]
+
+
+def oracle_rfgr_grads(v, blochsim=None):
+    r"""``Mo, grad_Mi, grad_rf, grad_gr`` of ``<w, blochsim(Mi, rfgr2beff(rf, gr, loc, ...))>`` by the oracle, on a
+    variant's operands as given."""
+    leaf = lambda x: x.detach().requires_grad_(True)  # noqa: E731
+    Mi, rf, gr = leaf(v['M0']), leaf(v['rf']), leaf(v['gr'])
+    beff = O.rfgr2beff(rf, gr, v['loc'], Δf=v['Δf'], b1Map=v['b1Map'], γ=v['γ_beff'])
+    Mo = (blochsim or O.blochsim)(Mi, beff, T1=v['T1'], T2=v['T2'], γ=v['γ'], dt=v['dt'])
+    (Mo * v['w']).sum().backward()
+    return dict(Mo=Mo.detach(), grad_Mi=Mi.grad, grad_rf=rf.grad, grad_gr=gr.grad)
+
+
+@pytest.mark.parametrize('tag', ['f64', 'f32'])
+def test_fusedops_golden(tag):
+    r"""The oracle on every operand spelling and on the zero-field case against the reference's own outputs
+    (``fusedops_*.npz``).  The reference gives nothing for a ``b1Map`` on a general ``*Nd`` grid (``IndexError``): those
+    variants have no golden, and the count below pins which."""
+    G = golden(f'fusedops_{tag}')
+    seen = 0
+    for key, v in fusedops_entries(DT[tag]):
+        if f'{key}.Mo' not in G:
+            assert '.cube' in key and not key.startswith('c0.'), key
+            continue
+        seen += 1
+        got = oracle_rfgr_grads(v)
+        assert max_abs(got['Mo'], G[f'{key}.Mo']) == 0.0, key
+        for k in ('grad_Mi', 'grad_rf', 'grad_gr'):
+            if f'{key}.{k}' in G:
+                assert got[k].shape == G[f'{key}.{k}'].shape, (key, k)
+                assert_close(got[k], G[f'{key}.{k}'], tag, f'{key}.{k}')
+    assert seen == 3 * (8 + 3 + 2) - 6
+
+
+@pytest.mark.parametrize('nC', cases.FUSED_COILS)
+@pytest.mark.parametrize('nT', [48, 53])
+def test_zero_field_adjoint_yardsticks_agree(nC, nT):
+    r"""WHICH gradient is right at exactly zero field (dead time: ``rf = gr = 0``; a spin at the iso-centre)?  The
+    reference's two simulators disagree there.  Its explicit adjoint (``sims.py:229-259``, restated as ``O.blochsim``
+    and, independently, ``oracle/bloch_c.c``) returns the analytic limit ``-γ2πdt (m x h̃)``; autograd through its
+    ``slowsims`` form returns EXACTLY 0 for ``grad_rf`` / ``grad_gr`` on every step whose field is zero (the
+    ``torch.any(ϕ != 0)`` skip, and ``norm()``'s zero subgradient under the clamp).  The function is smooth in the
+    field, so finite differences decide: a central difference of the fp64 loss along a random direction supported on
+    the zero-field steps agrees with the explicit adjoint to 1e-8 relative at h = 1e-5 (measured 7e-11 .. 2e-10; the
+    error falls as h^2 from h = 1e-3), and the two restatements agree to 1e-12 (measured 5e-15).  The product follows
+    ``sims``; the GPU suite holds the fused adjoints to this yardstick on those very steps."""
+    import bloch_c as C
+    v, zero = cases.zero_field_case(torch.float64, nC, nT)
+    ex = oracle_rfgr_grads(v)
+    Mo, gMi, grf, ggr = C.blochsim_rfgr_grad(v['M0'], v['rf'], v['gr'], v['loc'], v['w'], b1Map=v['b1Map'],
+                                             γ_beff=v['γ_beff'], T1=v['T1'], T2=v['T2'], γ=v['γ'], dt=v['dt'])
+    for a, b, nm in ((Mo, ex['Mo'], 'Mo'), (gMi, ex['grad_Mi'], 'grad_Mi'),
+                     (grf.reshape(ex['grad_rf'].shape), ex['grad_rf'], 'grad_rf'), (ggr, ex['grad_gr'], 'grad_gr')):
+        assert max_abs(a, b) <= 1e-12, (nm, max_abs(a, b))
+    # the gradients at the zero-field steps are O(1), not a rounding-level quantity
+    zr = ex['grad_rf'].movedim(2, 1)[zero]
+    assert float(zr.abs().max()) > 0.1
+    # central finite difference along a random direction that lives on the zero-field steps only
+    gen = torch.Generator().manual_seed(41 + nC)
+    d_rf = torch.rand(v['rf'].shape, generator=gen, dtype=torch.float64) * 2 - 1
+    d_gr = torch.rand(v['gr'].shape, generator=gen, dtype=torch.float64) * 2 - 1
+    d_rf.movedim(2, 1)[~zero] = 0
+    d_gr.movedim(2, 1)[~zero] = 0
+
+    def loss(s):
+        b = O.rfgr2beff(v['rf'] + s * d_rf, v['gr'] + s * d_gr, v['loc'], b1Map=v['b1Map'], γ=v['γ_beff'])
+        return float((O.blochsim(v['M0'], b, T1=v['T1'], T2=v['T2'], γ=v['γ'], dt=v['dt']) * v['w']).sum())
+    h = 1e-5
+    fd = (loss(h) - loss(-h)) / (2 * h)
+    an = float((ex['grad_rf'] * d_rf).sum() + (ex['grad_gr'] * d_gr).sum())
+    print(f'zero-field yardstick nC={nC} nT={nT}: analytic {an:.12e}, finite difference {fd:.12e}, '
+          f'relative {abs(fd - an) / abs(an):.2e}')
+    assert abs(an) > 1.0 and abs(fd - an) <= 1e-8 * abs(an), (an, fd)
+    # ... and the slowsims form's autograd: exactly zero there
+    # (its leading steps are all-zero ones, which relax their input IN PLACE, slowsims.py:44-47: not on a leaf)
+    sl = oracle_rfgr_grads(v, lambda Mi, b, **kw: O.blochsim_slow(Mi * 1, b, **kw))
+    assert max_abs(sl['Mo'], ex['Mo']) <= 1e-12
+    assert float(sl['grad_rf'].movedim(2, 1)[zero].abs().max()) == 0.0
+    assert float(sl['grad_gr'].movedim(2, 1)[zero].abs().max()) == 0.0
+    # ... and it loses the share of the spins at loc = 0 on the steps where only rf is zero; elsewhere the two agree
+    live = ~zero
+    live[:, list(cases.ZERO_RF_ONLY)] = False
+    for k in ('grad_rf', 'grad_gr'):
+        assert max_abs(sl[k].movedim(2, 1)[live], ex[k].movedim(2, 1)[live]) <= 1e-9, k
+    only = list(cases.ZERO_RF_ONLY)                  # (d Bz / d gr = loc = 0 for those spins: grad_gr loses nothing)
+    assert max_abs(sl['grad_gr'][:, :, only], ex['grad_gr'][:, :, only]) <= 1e-9
+    assert max_abs(sl['grad_rf'][:, :, only], ex['grad_rf'][:, :, only]) > 1e-4
