@@ -68,7 +68,9 @@ extern "C" {
  *      points are the one-part case, unchanged.  RCCL helpers for a ctypes-only multi-GPU consumer
  *      live in a library of their own beside this one (include/mrphy_comm.h, libmrphy_comm.so).  Same bits.
  *      Added later under the same version, changing no existing call: mrphy_blochsim_rfgr_traj_fwd,
- *      mrphy_blochsim_rfgr_traj_bwd, mrphy_blochsim_rfgr_mc_traj_bwd (the magnetisation trajectory of K2). */
+ *      mrphy_blochsim_rfgr_traj_bwd, mrphy_blochsim_rfgr_mc_traj_bwd (the magnetisation trajectory of K2);
+ *      mrphy_signal_rfgr_fwd_workspace, mrphy_signal_rfgr_fwd, mrphy_signal_rfgr_bwd (the received signal of K2:
+ *      the transverse magnetisation summed over the spins, sample by sample). */
 #define MRPHY_ABI_VERSION 5
 
 #define MRPHY_F32      0  /* T = float,  CT = float                                          */
@@ -553,6 +555,72 @@ int mrphy_blochsim_rfgr_mc_traj_bwd(int dtype,
                                     void* work, size_t work_bytes,
                                     int64_t N, int64_t nM, int64_t nT, int64_t nC,
                                     void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * K2s  received signal of the fused simulation: K2 that, instead of keeping M, sums what a receive coil sees over the
+ * spins of each batch entry at the trajectory's record steps
+ *     e_j = min((j+1) * every, nT) - 1,   j = 0 .. nRec-1,   nRec = ceil(nT / every):
+ *     sig[n, 0, j] = sum_s  rx_re[n,s] Mx[n,s] - rx_im[n,s] My[n,s]
+ *     sig[n, 1, j] = sum_s  rx_re[n,s] My[n,s] + rx_im[n,s] Mx[n,s]           (M after step e_j)
+ * -- the complex product of b1Map . rf in rfgr2beff (beffective.py:160-165), no conjugate.  sig (N, 2, nRec), the layout
+ * of rf; rx (N, nM, 2), the layout of a one-coil b1, or NULL = (1, 0): the plain sums of Mx and My.  The reference has no
+ * counterpart: it forms the history Mhst inside BlochSim.forward and drops it (sims.py:83,131); this is the sum over
+ * the spins of what mrphy_blochsim_rfgr_traj_fwd records, without the records in memory.  The order of summation is
+ * fixed (64 spins in LDS, a wave's tiles in its own workspace row, the rows in a second pass): the same inputs give the
+ * same bits, no float atomics.
+ * Operands and constants as mrphy_blochsim_rfgr_fwd, ONE transmit coil (nC == 1; b1 (N, nM, 2) or NULL).  Mo (N, nM, 3)
+ * may be NULL; where given it is mrphy_blochsim_rfgr_fwd's bit for bit.  Mck / ck_every as there (checkpoints for the
+ * adjoint below; Mck may be NULL).  Any nT.  `work` must hold mrphy_signal_rfgr_fwd_workspace() bytes.
+ * MRPHY_EINVAL: every < 1, sig NULL, nC != 1, N > 65535, an unknown dtype; MRPHY_ENOSPC: workspace too small; an empty
+ * problem (N nM nT == 0) returns 0 and touches nothing.
+ * ------------------------------------------------------------------------------------------- */
+size_t mrphy_signal_rfgr_fwd_workspace(int dtype, int64_t N, int64_t nM, int64_t nT, int64_t every);
+int mrphy_signal_rfgr_fwd(int dtype,
+                          const void* Mi,
+                          const void* rf, int64_t rf_sn,
+                          const void* gr, int64_t gr_sn,
+                          const void* loc,
+                          const void* df, int64_t df_sn, int64_t df_sm,
+                          const void* gamma, int64_t gamma_sn, int64_t gamma_sm,
+                          const void* b1,
+                          const void* g,  int64_t g_sn,  int64_t g_sm,
+                          const void* E1, int64_t E1_sn, int64_t E1_sm,
+                          const void* E2, int64_t E2_sn, int64_t E2_sm,
+                          const void* E1m1,
+                          const void* rx,
+                          void* Mo, void* Mck, int64_t ck_every,
+                          void* sig, int64_t every,
+                          void* work, size_t work_bytes,
+                          int64_t N, int64_t nM, int64_t nT, int64_t nC,
+                          void* stream);
+
+/* K2bs  adjoint of K2s: as mrphy_blochsim_rfgr_bwd, with the cotangents of BOTH outputs -- grad_Mo (N, nM, 3) and
+ * grad_sig (N, 2, nRec); either may be NULL (= zero), not both.  The sweep starts from grad_Mo and, as it passes step e_j
+ * backwards, adds the cotangent of sample j, the same for every spin up to its receive weight:
+ *     (rx_re g0 + rx_im g1,  rx_re g1 - rx_im g0,  0),   g0, g1 = grad_sig[n, :, j]
+ * -- what the reference's autograd would do with a loss on the spin sum of Mhst (BlochSim.backward, sims.py:135-269).
+ * Without grad_sig it is mrphy_blochsim_rfgr_bwd.  Same checkpoints (nT a multiple of mrphy_blochsim_rfgr_ck_every()),
+ * same workspace (mrphy_blochsim_rfgr_bwd_workspace), same deterministic reduction; no gradient w.r.t. rx.
+ * MRPHY_EINVAL: every < 1, nT not a whole number of segments, both cotangents NULL, N > 65535, an unknown dtype;
+ * MRPHY_ENOSPC: workspace too small. */
+int mrphy_signal_rfgr_bwd(int dtype,
+                          const void* Mck,
+                          const void* rf, int64_t rf_sn,
+                          const void* gr, int64_t gr_sn,
+                          const void* loc,
+                          const void* df, int64_t df_sn, int64_t df_sm,
+                          const void* gamma, int64_t gamma_sn, int64_t gamma_sm,
+                          const void* b1,
+                          const void* g,  int64_t g_sn,  int64_t g_sm,
+                          const void* E1, int64_t E1_sn, int64_t E1_sm,
+                          const void* E2, int64_t E2_sn, int64_t E2_sm,
+                          const void* E1m1,
+                          const void* rx,
+                          const void* grad_Mo, const void* grad_sig, int64_t every,
+                          void* grad_Mi, void* grad_rf, void* grad_gr,
+                          void* work, size_t work_bytes,
+                          int64_t N, int64_t nM, int64_t nT,
+                          void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * the steps either side of the path in SpinArray.applypulse (mobjs.py:427-433,449).

@@ -66,6 +66,11 @@ PROTOTYPES = {
     'mrphy_blochsim_rfgr_mc_traj_bwd': (_int, [_int, _vp, _vp, _i64, _vp, _i64, _vp] + _BC + _BC + [_vp]
                                         + _BC * 3 + [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _sz] + [_i64] * 4
                                         + [_vp]),
+    'mrphy_signal_rfgr_fwd_workspace': (_sz, [_int] + [_i64] * 4),
+    'mrphy_signal_rfgr_fwd': (_int, [_int, _vp, _vp, _i64, _vp, _i64, _vp] + _BC + _BC + [_vp]
+                              + _BC * 3 + [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _sz] + [_i64] * 4 + [_vp]),
+    'mrphy_signal_rfgr_bwd': (_int, [_int, _vp, _vp, _i64, _vp, _i64, _vp] + _BC + _BC + [_vp]
+                              + _BC * 3 + [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _sz] + [_i64] * 3 + [_vp]),
     'mrphy_freeprec_fwd': (_int, [_int, _vp, _vp, _i64] + _BC * 3 + [_vp, _i64, _i64, _vp]),
     'mrphy_freeprec_bwd': (_int, [_int, _vp, _vp, _i64] + _BC * 3 + [_vp, _i64, _i64, _vp]),
     'mrphy_freeprec_bwd_consts': (_int, [_int, _vp, _vp, _vp, _i64] + _BC * 3 + [_vp, _i64, _i64, _vp]),
@@ -102,6 +107,7 @@ UNITS = [(f, m) for f, masks in (
     ('tu_fused_mc_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_fused_fwd1.hip', (_F32, _C64, _P, _PC64)),
     ('tu_fused_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
+    ('tu_signal.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_blochsim_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_blochsim_fwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_beff2ab.hip', (_F32, _F64, _C64, _P, _PC64)),

@@ -78,8 +78,8 @@ int rfgr_bwd(bool traj, int dtype, const void* Mck, const void* rf, int64_t rf_s
     const Bc bg = {g, g_sn, g_sm}, be1 = {E1, E1_sn, E1_sm}, be2 = {E2, E2_sn, E2_sm};
     hipStream_t st = (hipStream_t)stream;
     MRPHY_DISPATCH(dtype, (run_rfgr_bwd<T, CT>(Mck, rf, rf_sn, gr, gr_sn, loc, bdf, bgam, b1, bg, be1, be2, E1m1,
-                                               traj ? nullptr : grad_M, traj ? grad_M : nullptr, every, grad_Mi,
-                                               grad_rf, grad_gr, work, N, nM, nT, st)));
+                                               traj ? nullptr : grad_M, traj ? grad_M : nullptr, every, nullptr,
+                                               nullptr, grad_Mi, grad_rf, grad_gr, work, N, nM, nT, st)));
 }
 
 int rfgr_mc_bwd(bool traj, int dtype, const void* Mck, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
@@ -388,6 +388,63 @@ int mrphy_blochsim_rfgr_mc_traj_bwd(int dtype, const void* Mck, const void* rf, 
     return rfgr_mc_bwd(true, dtype, Mck, rf, rf_sn, gr, gr_sn, loc, df, df_sn, df_sm, gamma, gamma_sn, gamma_sm, b1,
                        g, g_sn, g_sm, E1, E1_sn, E1_sm, E2, E2_sn, E2_sm, E1m1, grad_Mt, every, grad_Mi, grad_rf,
                        grad_gr, work, work_bytes, N, nM, nT, nC, stream);
+}
+
+size_t mrphy_signal_rfgr_fwd_workspace(int dtype, int64_t N, int64_t nM, int64_t nT, int64_t every)
+{
+    if (N <= 0 || nM <= 0 || nT <= 0 || every < 1) return 0;
+    return (size_t)(sig_waves(nM) * N * 2 * sig_records(nT, every)) * tsize(dtype);
+}
+
+int mrphy_signal_rfgr_fwd(int dtype, const void* Mi, const void* rf, int64_t rf_sn,
+                          const void* gr, int64_t gr_sn, const void* loc, const void* df,
+                          int64_t df_sn, int64_t df_sm, const void* gamma, int64_t gamma_sn,
+                          int64_t gamma_sm, const void* b1, const void* g, int64_t g_sn,
+                          int64_t g_sm, const void* E1, int64_t E1_sn, int64_t E1_sm,
+                          const void* E2, int64_t E2_sn, int64_t E2_sm, const void* E1m1,
+                          const void* rx, void* Mo, void* Mck, int64_t ck_every, void* sig, int64_t every,
+                          void* work, size_t work_bytes, int64_t N, int64_t nM, int64_t nT, int64_t nC,
+                          void* stream)
+{
+    if (int e = check_common(dtype, N, nM, nT)) return e;
+    if (every < 1 || nC != 1 || N > 65535 || (Mck && (ck_every < 8 || ck_every % 8 != 0))) return MRPHY_EINVAL;
+    if (N * nM * nT == 0) return 0;
+    if (!Mi || !sig || !rf || !gr || !loc || !g || !work || (df && !gamma)) return MRPHY_EINVAL;
+    if ((E1 == nullptr) != (E2 == nullptr) || (E1 == nullptr) != (E1m1 == nullptr))
+        return MRPHY_EINVAL;
+    if (work_bytes < mrphy_signal_rfgr_fwd_workspace(dtype, N, nM, nT, every)) return MRPHY_ENOSPC;
+    const Bc bdf = {df, df_sn, df_sm}, bgam = {gamma, gamma_sn, gamma_sm};
+    const Bc bg = {g, g_sn, g_sm}, be1 = {E1, E1_sn, E1_sm}, be2 = {E2, E2_sn, E2_sm};
+    hipStream_t st = (hipStream_t)stream;
+    MRPHY_DISPATCH(dtype, (run_signal_fwd<T, CT>(Mi, rf, rf_sn, gr, gr_sn, loc, bdf, bgam, b1, bg, be1, be2, E1m1, rx,
+                                                 Mo, Mck, ck_every, sig, every, work, N, nM, nT, st)));
+}
+
+int mrphy_signal_rfgr_bwd(int dtype, const void* Mck, const void* rf, int64_t rf_sn,
+                          const void* gr, int64_t gr_sn, const void* loc, const void* df,
+                          int64_t df_sn, int64_t df_sm, const void* gamma, int64_t gamma_sn,
+                          int64_t gamma_sm, const void* b1, const void* g, int64_t g_sn,
+                          int64_t g_sm, const void* E1, int64_t E1_sn, int64_t E1_sm,
+                          const void* E2, int64_t E2_sn, int64_t E2_sm, const void* E1m1,
+                          const void* rx, const void* grad_Mo, const void* grad_sig, int64_t every,
+                          void* grad_Mi, void* grad_rf, void* grad_gr, void* work, size_t work_bytes,
+                          int64_t N, int64_t nM, int64_t nT, void* stream)
+{
+    if (int e = check_common(dtype, N, nM, nT)) return e;
+    // whole checkpoint segments only; at least one of the two cotangents
+    if (nT % SEG != 0 || every < 1 || N > 65535 || (!grad_Mo && !grad_sig)) return MRPHY_EINVAL;
+    if (N * nM * nT == 0) return 0;
+    if (!Mck || !rf || !gr || !loc || !g || !work || (df && !gamma)) return MRPHY_EINVAL;
+    if ((E1 == nullptr) != (E2 == nullptr) || (E1 == nullptr) != (E1m1 == nullptr))
+        return MRPHY_EINVAL;
+    if (work_bytes < mrphy_blochsim_rfgr_bwd_workspace(dtype, N, nM, nT)) return MRPHY_ENOSPC;
+    const Bc bdf = {df, df_sn, df_sm}, bgam = {gamma, gamma_sn, gamma_sm};
+    const Bc bg = {g, g_sn, g_sm}, be1 = {E1, E1_sn, E1_sm}, be2 = {E2, E2_sn, E2_sm};
+    hipStream_t st = (hipStream_t)stream;
+    // without grad_sig this is K2b on grad_Mo
+    MRPHY_DISPATCH(dtype, (run_rfgr_bwd<T, CT>(Mck, rf, rf_sn, gr, gr_sn, loc, bdf, bgam, b1, bg, be1, be2, E1m1,
+                                               grad_Mo, nullptr, every, rx, grad_sig, grad_Mi, grad_rf, grad_gr, work,
+                                               N, nM, nT, st)));
 }
 
 int mrphy_beff2ab(int dtype, const void* Beff,

@@ -14,6 +14,7 @@ constexpr int SEG = 16;                           // K2 / K2b: steps per checkpo
 // NOT generic: k_bloch_rfgr_bwd_mc (step = lane >> 2, needs SEG * 4 == WAVE) and the reduction tile of both fused
 // adjoints (red_idx).  Both carry a static_assert; change SEG only together with them.
 constexpr int64_t K2B_MAX_WAVES = 256 * 8;        // K2b: resident waves, 8 per CU
+constexpr int64_t SIG_MAX_WAVES = 256 * 16;       // K2s (signal forward): 8 / 16 KB of LDS per wave, 16 waves per CU as K2 runs
 constexpr int K2B_MAXC = 8;                       // fused adjoint: largest coil capacity
 constexpr int64_t K2B_MC_MAX_WAVES = 256 * 8;     // 18 KB of LDS per wave -> 8 per CU = 2 per SIMD
 constexpr int BWD_MAXC = 32;                      // K0 adjoint: largest coil capacity of the one-pass kernels
@@ -60,6 +61,14 @@ inline int64_t k2b_waves(int64_t nM)
     const int64_t tiles = (nM + WAVE - 1) / WAVE;
     return tiles < K2B_MAX_WAVES ? tiles : K2B_MAX_WAVES;
 }
+
+// K2s: persistent waves of the signal forward, and the records it takes at stride `every`
+inline int64_t sig_waves(int64_t nM)
+{
+    const int64_t tiles = (nM + WAVE - 1) / WAVE;
+    return tiles < SIG_MAX_WAVES ? tiles : SIG_MAX_WAVES;
+}
+inline int64_t sig_records(int64_t nT, int64_t every) { return nT / every + (nT % every != 0); }
 
 inline int64_t k2b_mc_waves(int64_t nM)
 {

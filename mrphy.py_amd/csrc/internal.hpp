@@ -48,8 +48,17 @@ int run_rfgr_fwd1(const void* Mi, const void* rf, int64_t rf_sn, const void* gr,
 template <typename T, typename CT>
 int run_rfgr_bwd(const void* Mck, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
                  const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2,
-                 const void* E1m1, const void* gMo, const void* gMt, int64_t every, void* gMi, void* grf,
-                 void* ggr, void* work, int64_t N, int64_t nM, int64_t nT, hipStream_t st);
+                 const void* E1m1, const void* gMo, const void* gMt, int64_t every, const void* rx,
+                 const void* gsig, void* gMi, void* grf, void* ggr, void* work, int64_t N, int64_t nM, int64_t nT,
+                 hipStream_t st);
+
+// K2s: the received signal of the fused simulation (tu_signal.hip; one transmit coil).  Its adjoint is run_rfgr_bwd
+// with a non-null gsig (the cotangent of the samples) and the receive map rx; gMo may then be null
+template <typename T, typename CT>
+int run_signal_fwd(const void* Mi, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
+                   const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2,
+                   const void* E1m1, const void* rx, void* Mo, void* Mck, int64_t ck_every, void* sig,
+                   int64_t every, void* work, int64_t N, int64_t nM, int64_t nT, hipStream_t st);
 
 template <typename T, typename CT>
 int run_rfgr_mc_bwd(const void* Mck, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,

@@ -39,11 +39,22 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdArgsT<T, INJ> a
         // round 6: masked here, once per tile, instead of three multiplications per step
         // grad_Mo; in the trajectory builds grad_Mt, whose last record is Mo
         const T* gM = a.gMo;
-        if constexpr (INJ != 0) gM += (a.nRec - 1) * rows * 3;
-        T hx = gM[row * 3] * vmask, hy = gM[row * 3 + 1] * vmask, hz = gM[row * 3 + 2] * vmask;
+        if constexpr (INJ == 1 || INJ == 2) gM += (a.nRec - 1) * rows * 3;
+        T hx = T(0), hy = T(0), hz = T(0);
+        if (INJ != 3 || gM) { hx = gM[row * 3] * vmask; hy = gM[row * 3 + 1] * vmask; hz = gM[row * 3 + 2] * vmask; }
         // trajectory: the latest record not yet injected, index jr, taken after step er (both wave-uniform)
         int64_t every = 0, jr = 0, er = 0;
-        if constexpr (INJ != 0) { every = a.every; jr = a.nRec - 2; er = (a.nRec - 1) * every - 1; }
+        if constexpr (INJ == 1 || INJ == 2) { every = a.every; jr = a.nRec - 2; er = (a.nRec - 1) * every - 1; }
+        // signal (INJ == 3): every record is injected, the last one (after step nT - 1) included; the lane's receive
+        // weight, zero past nM; the cotangents of the samples through the constant address space, as the pulse
+        T rxr = vmask, rxi = T(0);
+        CP gs0 = nullptr, gs1 = nullptr;
+        if constexpr (INJ == 3) {
+            every = a.every; jr = a.nRec - 1; er = nT - 1;
+            if (a.rx) { rxr = a.rx[row * 2] * vmask; rxi = a.rx[row * 2 + 1] * vmask; }
+            gs0 = (CP)(a.gsig + n * 2 * a.nRec);
+            gs1 = gs0 + a.nRec;
+        }
         adj_begin<RELAX, T, CT>(k, hx, hy, hz);
 
         auto field = [&](int64_t t, T& Bx, T& By, T& Bz) {
@@ -143,6 +154,13 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdArgsT<T, INJ> a
                                                  red[red_idx(1 * SEG + st, lane)], red[red_idx(2 * SEG + st, lane)]);
                     else if constexpr (INJ == 2) {
                         if (st == ist) adj_inject<RELAX, T, CT>(k, hx, hy, hz, ijx, ijy, ijz);
+                    } else if constexpr (INJ == 3) {
+                        if (t0 + st == er) {                            // wave-uniform
+                            const T g0 = gs0[jr], g1 = gs1[jr];
+                            adj_inject<RELAX, T, CT>(k, hx, hy, hz, rxr * g0 + rxi * g1, rxr * g1 - rxi * g0, T(0));
+                            er = (jr == a.nRec - 1) ? jr * every - 1 : er - every;
+                            --jr;
+                        }
                     }
                     T g0, g1, g2;
                     rot_apply_adj<RELAX, T, CT>(k, ra[j], M0[st], M1[st], M2[st], hx, hy, hz,

@@ -67,8 +67,20 @@ template <typename T>
 struct FusedBwdTrajArgs : FusedBwdArgs<T> {
     int64_t every, nRec;             // gMo is grad_Mt (nRec, N*nM, 3)
 };
+// INJ == 3 (one coil only: k_fused_bwd.hpp) is the adjoint of the signal kernel K2s (k_signal_fwd.hpp,
+// mrphy_signal_rfgr_bwd): the cotangent of record j is the same for every spin -- gsig[n, :, j], two wave-uniform
+// numbers read with scalar loads as the pulse is -- scaled by the lane's own receive weight,
+//     g = (rx_re g0 + rx_im g1,  rx_re g1 - rx_im g0,  0),
+// and enters like a trajectory record's.  No per-spin cotangent loads and no staging; the last record is injected like
+// any other (the sweep starts from grad_Mo, or from zero when that is null).
+template <typename T>
+struct FusedBwdSigArgs : FusedBwdTrajArgs<T> {
+    const T* rx;                     // (N, nM, 2) or null = (1, 0)
+    const T* gsig;                   // (N, 2, nRec)
+};
 template <typename T, int INJ>
-using FusedBwdArgsT = std::conditional_t<INJ == 0, FusedBwdArgs<T>, FusedBwdTrajArgs<T>>;
+using FusedBwdArgsT = std::conditional_t<INJ == 0, FusedBwdArgs<T>,
+                                         std::conditional_t<INJ == 3, FusedBwdSigArgs<T>, FusedBwdTrajArgs<T>>>;
 
 // the arguments of K2b / K2bt (host side, shared by tu_fused_bwd.hip and tu_fused_mc_bwd.hip): a null gMt selects the
 // plain kernel (INJ == 0), which takes the FusedBwdArgs part; otherwise gMt is the cotangent the kernel reads

@@ -1,0 +1,184 @@
+// k_signal_fwd.hpp -- K2s (fused rf,gr -> received signal: the transverse magnetisation summed over the spins)
+// Fragment: included INSIDE a translation unit's anonymous namespace, after host_common.hpp (HIP runtime,
+// include/mrphy_hip.h, geom.hpp, bloch_math.hpp, k_common.hpp).  Not a standalone header.
+#pragma once
+#include "k_fused_bwd_common.hpp"                             // red_idx / RED_PITCH, P2_T / P2_G
+
+// =============================================================================================
+// K2s: K2's step loop (one block = one wave = 64 spins of ONE batch entry, the pulse through scalar loads, the same
+// field / rot_prepare / rot_apply and therefore the same bits of M), but instead of M the wave keeps what a receive
+// coil sees: at each record step (the trajectory's convention: after steps min((j+1) every, nT) - 1) the lane forms
+//     s0 = rx_re Mx - rx_im My,   s1 = rx_re My + rx_im Mx                    (the product of b1Map . rf, no conjugate)
+// and puts the two numbers into an LDS tile of 2 SEG rows x 64 lanes (K2b's swizzle).  When the tile holds SEG records
+// (or the pulse ends) the 2 SEG rows are summed over the lanes in K2b's fixed four-chain order and added into the
+// wave's OWN workspace row; waves are persistent over the tiles w, w + P, ... as in K2b, so every row is accumulated in
+// a fixed order, and a second pass sums the P rows in fixed order: deterministic, no float atomics, and no per-spin
+// record ever reaches HBM.  A stride of SEG or more fills the tile over several segments and reduces once per SEG
+// records, so it costs next to nothing over K2.
+// =============================================================================================
+template <typename T>
+struct SignalArgs {
+    const T* Mi;
+    const T* rf;  int64_t rf_sn;
+    const T* gr;  int64_t gr_sn;
+    const T* loc;
+    Bc df, gam;
+    const T* b1;                     // (N, nM, 2) or null
+    Bc g, E1, E2;
+    const void* E1m1;
+    const T* rx;                     // (N, nM, 2) or null = (1, 0)
+    T* Mo;                           // may be null
+    T* Mck;  int64_t ck_every;       // may be null
+    T* work;                         // (P, N, 2, nRec)
+    int64_t every, nRec;
+    int64_t N, nM, nT, P;
+};
+
+// CK, RELAX, HB1: as K2.  EV1: every == 1 -- a record after every step, its slot known at compile time inside the
+// unrolled step batch; otherwise the step of the next record is carried (wave-uniform) and compared, as in K2t.
+template <typename T, typename CT, bool CK, bool RELAX, bool HB1, bool EV1>
+__global__ __launch_bounds__(WAVE) void k_signal_fwd(SignalArgs<T> a)
+{
+    constexpr int NS = sizeof(T) == 8 ? 4 : 8;               // steps per batch, as K2's one-coil builds
+    static_assert(SEG % NS == 0, "a batch of records must fit the tile");
+    __shared__ __attribute__((aligned(16))) T red[2 * SEG * RED_PITCH];
+    const int lane = threadIdx.x;
+    const int64_t w = blockIdx.x, n = blockIdx.y;
+    const int64_t nT = a.nT, rows = a.N * a.nM, nRec = a.nRec, every = a.every;
+    const int64_t ntiles = (a.nM + WAVE - 1) / WAVE;
+    // read-only, wave-uniform pulse through the constant address space: scalar loads (see K2)
+    using CP = const T __attribute__((address_space(4)))*;
+    CP rfr = (CP)(a.rf + n * a.rf_sn);
+    CP rfi = rfr + nT;
+    CP gx = (CP)(a.gr + n * a.gr_sn);
+    CP gy = gx + nT;
+    CP gz = gy + nT;
+    // row sums: lane (r, h) forms chains 2h and 2h + 1 of row r = q SEG + slot; the two halves meet as
+    // (p0 + p1) + (p2 + p3), K2b's order
+    const int rr = lane >> 1, rh = lane & 1;
+    T* wdst = a.work + ((w * a.N + n) * 2 + rr / SEG) * nRec + (rr % SEG);
+    // the most records a batch of NS steps can take: those of the stride, and the one after the last step
+    const int maxrec = EV1 ? NS : (int)((NS - 1) / every + 2 < NS ? (NS - 1) / every + 2 : NS);
+    const int64_t ck_pitch = rows * 3;
+    bool first = true;
+
+    for (int64_t tile = w; tile < ntiles; tile += a.P) {
+        const int64_t s_ = tile * WAVE + lane;
+        const bool valid = s_ < a.nM;
+        const int64_t s = valid ? s_ : a.nM - 1;
+        const int64_t row = n * a.nM + s;
+        const SpinConst<T, CT> k = load_consts<T, CT>(a.g, a.E1, a.E2, a.E1m1, n, s);
+        T mx = a.Mi[row * 3], my = a.Mi[row * 3 + 1], mz = a.Mi[row * 3 + 2];
+        const T lx = a.loc[row * 3], ly = a.loc[row * 3 + 1], lz = a.loc[row * 3 + 2];
+        T delta = T(0);
+        if (a.df.p) delta = bc_load<T>(a.df, n, s) / bc_load<T>(a.gam, n, s);
+        T br = T(1), bi = T(0);
+        if (HB1 && a.b1) { br = a.b1[row * 2]; bi = a.b1[row * 2 + 1]; }
+        // lanes past nM (they hold a copy of the last valid spin) receive with weight zero: their two products are
+        // exact zeros -- masked here, once per tile
+        T rxr = valid ? T(1) : T(0), rxi = T(0);
+        if (a.rx && valid) { rxr = a.rx[row * 2]; rxi = a.rx[row * 2 + 1]; }
+
+        auto field = [&](int64_t t, T& Bx, T& By, T& Bz) {
+            Bx = T(0); By = T(0);
+            if (HB1) field_xy_acc<T>(br, bi, rfr[t], rfi[t], Bx, By);
+            else     { Bx = rfr[t]; By = rfi[t]; }               // no b1 map: Bxy = rf (as K2 / K0)
+            Bz = field_z<T>(gx[t], gy[t], gz[t], lx, ly, lz, delta);
+        };
+        int cnt = 0;                                             // records in the tile (wave-uniform)
+        int64_t jbase = 0;                                       // records of this spin tile already reduced
+        int64_t next = every - 1 < nT - 1 ? every - 1 : nT - 1;  // the step after which the next record is taken
+        auto rec = [&](int slot) {
+            red[red_idx(slot, lane)] = rxr * mx - rxi * my;
+            red[red_idx(SEG + slot, lane)] = rxr * my + rxi * mx;
+        };
+        auto take = [&](int64_t t) {                             // the record after step t, if one is due
+            if (t == next) {
+                rec(cnt); ++cnt;
+                next = every < nT - 1 - next ? next + every : nT - 1;   // the last one: after step nT - 1
+            }
+        };
+        // reduce the cnt records of the tile into the workspace rows of records jbase .. jbase + cnt - 1 (rows past
+        // cnt hold stale numbers: summed, never stored).  The old workspace value is requested before the row sums.
+        auto flush = [&]() {
+            const bool mine = rh == 0 && (rr % SEG) < cnt;
+            T old = T(0);
+            if (!first && mine) old = wdst[jbase];
+            __syncthreads();
+            T p0 = T(0), p1 = T(0);
+#pragma unroll
+            for (int i = 0; i < WAVE; i += 4) {
+                const T* q = red + red_idx(rr, i) + 2 * rh;
+                p0 += q[0]; p1 += q[1];
+            }
+            T p = p0 + p1;
+            p += __shfl_xor(p, 1);
+            if (mine) wdst[jbase] = old + p;
+            __syncthreads();
+            jbase += cnt; cnt = 0;
+        };
+
+        // (checkpoints as in K2: a running destination; the prologue's vector loads are awaited before the loop)
+        if (CK) __builtin_amdgcn_s_waitcnt(0x0F70);         // vmcnt(0), expcnt / lgkmcnt untouched (gfx9 encoding)
+        int64_t ck_next = 0;
+        T* ckp = CK ? a.Mck + row * 3 : nullptr;
+        int64_t t0 = 0;
+        for (; t0 + NS <= nT; t0 += NS) {
+            if (cnt + maxrec > SEG) flush();
+            if (CK && t0 == ck_next) {
+                if (valid) { ckp[0] = mx; ckp[1] = my; ckp[2] = mz; }
+                ckp += ck_pitch; ck_next += a.ck_every;
+            }
+            T Bx[NS], By[NS], Bz[NS];
+#pragma unroll
+            for (int j = 0; j < NS; ++j) field(t0 + j, Bx[j], By[j], Bz[j]);
+            Rot<T> r[NS];
+            rot_prepare<T, CT, NS>(k, Bx, By, Bz, r);
+#pragma unroll
+            for (int j = 0; j < NS; ++j) {
+                rot_apply<RELAX, T, CT>(k, r[j], mx, my, mz);
+                if constexpr (EV1) rec(cnt + j);
+                else take(t0 + j);
+            }
+            if constexpr (EV1) cnt += NS;
+        }
+        for (; t0 < nT; ++t0) {                                   // nT % NS tail
+            if (cnt == SEG) flush();
+            if (CK && t0 == ck_next) {
+                if (valid) { ckp[0] = mx; ckp[1] = my; ckp[2] = mz; }
+                ckp += ck_pitch; ck_next += a.ck_every;
+            }
+            T Bx[1], By[1], Bz[1];
+            field(t0, Bx[0], By[0], Bz[0]);
+            Rot<T> r[1];
+            rot_prepare<T, CT, 1>(k, Bx, By, Bz, r);
+            rot_apply<RELAX, T, CT>(k, r[0], mx, my, mz);
+            if constexpr (EV1) { rec(cnt); ++cnt; }
+            else take(t0);
+        }
+        if (cnt > 0) flush();
+        if (valid && a.Mo) { a.Mo[row * 3] = mx; a.Mo[row * 3 + 1] = my; a.Mo[row * 3 + 2] = mz; }
+        first = false;
+    }
+}
+
+// Pass 2: sig[n, q, j] = the sum of the P workspace rows in fixed order -- K2b's second pass (k_bloch_rfgr_bwd_p2:
+// 32 records x 8 row groups per block, the eight partial sums combined in group order) over 2 rows per batch entry.
+template <typename T>
+__global__ __launch_bounds__(P2_T * P2_G) void k_signal_p2(const T* work, T* sig, int64_t N, int64_t nRec, int64_t P)
+{
+    __shared__ T part[P2_G][P2_T];
+    const int tl = threadIdx.x % P2_T, g = threadIdx.x / P2_T;
+    const int64_t t = (int64_t)blockIdx.x * P2_T + tl;
+    const int64_t q = blockIdx.y, n = blockIdx.z;
+    T acc = T(0);
+    if (t < nRec)
+        for (int64_t w = g; w < P; w += P2_G) acc += work[((w * N + n) * 2 + q) * nRec + t];
+    part[g][tl] = acc;
+    __syncthreads();
+    if (g != 0 || t >= nRec) return;
+    T sum = part[0][tl];
+#pragma unroll
+    for (int i = 1; i < P2_G; ++i) sum += part[i][tl];
+    sig[(n * 2 + q) * nRec + t] = sum;
+}

@@ -1,5 +1,5 @@
-// tu_fused_bwd.hip -- K2b and its trajectory builds K2bt: launcher of mrphy_blochsim_rfgr_bwd and _traj_bwd
-// (one transmit coil)
+// tu_fused_bwd.hip -- K2b, its trajectory builds K2bt and its signal build K2bs: launcher of mrphy_blochsim_rfgr_bwd,
+// _traj_bwd and mrphy_signal_rfgr_bwd (one transmit coil)
 #include "host_common.hpp"
 
 namespace {
@@ -11,20 +11,27 @@ namespace mrphy_i {
 template <typename T, typename CT>
 int run_rfgr_bwd(const void* Mck, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
                  const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2,
-                 const void* E1m1, const void* gMo, const void* gMt, int64_t every, void* gMi, void* grf,
-                 void* ggr, void* work, int64_t N, int64_t nM, int64_t nT, hipStream_t st)
+                 const void* E1m1, const void* gMo, const void* gMt, int64_t every, const void* rx,
+                 const void* gsig, void* gMi, void* grf, void* ggr, void* work, int64_t N, int64_t nM, int64_t nT,
+                 hipStream_t st)
 {
     if (N * nM * nT == 0) return 0;
     if (N > 65535) return MRPHY_EINVAL;
-    const FusedBwdTrajArgs<T> a = fused_bwd_args<T>(Mck, rf, rf_sn, gr, gr_sn, loc, df, gam, b1, g, E1, E2, E1m1, gMo,
-                                                    gMt, every, gMi, work, N, nM, nT, k2b_waves(nM));
+    // gsig (the cotangent of the signal's samples, with the receive map rx) selects the signal build, which may have no
+    // gMo; its records are counted as the trajectory's
+    FusedBwdSigArgs<T> a;
+    static_cast<FusedBwdTrajArgs<T>&>(a) = fused_bwd_args<T>(Mck, rf, rf_sn, gr, gr_sn, loc, df, gam, b1, g, E1, E2, E1m1,
+                                                             gMo, gMt, every, gMi, work, N, nM, nT, k2b_waves(nM));
+    a.rx = (const T*)rx; a.gsig = (const T*)gsig;
+    if (gsig) a.nRec = sig_records(nT, every);
     const dim3 grid((unsigned)a.P, (unsigned)N);
 #define MRPHY_K2B(RX_, HB_, INJ_)                                                               \
     hipLaunchKernelGGL((k_bloch_rfgr_bwd<T, CT, RX_, HB_, INJ_>), grid, dim3(WAVE), 0, st, \
                        (static_cast<const FusedBwdArgsT<T, INJ_>&>(a)))
 #define MRPHY_K2BT(RX_, HB_)                                                                    \
     do {                                                                                        \
-        if (!gMt) MRPHY_K2B(RX_, HB_, 0);                                                       \
+        if (gsig) MRPHY_K2B(RX_, HB_, 3);                                                       \
+        else if (!gMt) MRPHY_K2B(RX_, HB_, 0);                                                  \
         else if (every < SEG) MRPHY_K2B(RX_, HB_, 1);                                           \
         else MRPHY_K2B(RX_, HB_, 2);                                                            \
     } while (0)
@@ -45,6 +52,6 @@ int run_rfgr_bwd(const void* Mck, const void* rf, int64_t rf_sn, const void* gr,
 
 }  // namespace mrphy_i
 
-#define MRPHY_INST(T_, CT_) template int mrphy_i::run_rfgr_bwd<T_, CT_>(const void* Mck, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn, const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2, const void* E1m1, const void* gMo, const void* gMt, int64_t every, void* gMi, void* grf, void* ggr, void* work, int64_t N, int64_t nM, int64_t nT, hipStream_t st);
+#define MRPHY_INST(T_, CT_) template int mrphy_i::run_rfgr_bwd<T_, CT_>(const void* Mck, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn, const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2, const void* E1m1, const void* gMo, const void* gMt, int64_t every, const void* rx, const void* gsig, void* gMi, void* grf, void* ggr, void* work, int64_t N, int64_t nM, int64_t nT, hipStream_t st);
 MRPHY_FOR_DTYPES(MRPHY_INST)
 #undef MRPHY_INST

@@ -19,6 +19,10 @@ into a fused part and a tail of at most 15 composed steps.
 :func:`blochsim_rfgr_traj` is the same simulation with the magnetisation recorded during the pulse (the history
 ``Mhst`` the reference forms inside ``BlochSim.forward`` and drops, ``sims.py:83,131``), differentiable through the
 trajectory kernels K2t / K2bt.
+
+:func:`signal_rfgr` is the same simulation again, returning what a receive coil measures: the transverse
+magnetisation summed over the spins at the trajectory's record steps (K2s, and the signal mode of K2b), without the
+per-spin records in memory.
 """
 from math import pi as π, prod  # noqa: F401
 from typing import Optional
@@ -30,7 +34,7 @@ from torch.autograd import Function
 from . import _lib, _host
 from ._consts import γH, dt0
 
-__all__ = ['blochsim_rfgr', 'blochsim_rfgr_traj']
+__all__ = ['blochsim_rfgr', 'blochsim_rfgr_traj', 'signal_rfgr']
 
 
 class BlochSimRfGrHIP(Function):
@@ -112,12 +116,84 @@ class BlochSimRfGrHIP(Function):
                 None, None, None, None, None, None, None)
 
 
-def _route(Mi, rf, gr, loc, every, kw):
-    r"""The routing :func:`blochsim_rfgr` (``every = None``) and :func:`blochsim_rfgr_traj` share.  Returns
+class SignalRfGrHIP(Function):
+    r"""``sig, Mo = SignalRfGrHIP.apply(Mi, rf, gr, pulse_on_spins, rx, γ2πdt, E1, E2, E1_1, want_ckpt, every)``
+
+    ``sig`` `(N, xy, nRec)`: the received signal (``mrphy_signal_rfgr_fwd`` / ``_bwd``), ``rx`` `(N, nM, xy)` contiguous
+    or ``None``; one transmit coil.  Both outputs may carry a cotangent; an output the loss does not use costs nothing
+    (its cotangent stays ``None``).  ``want_ckpt`` as in :class:`BlochSimRfGrHIP`."""
+
+    @staticmethod
+    def forward(ctx, Mi, rf, gr, p, rx, γ2πdt, E1, E2, E1_1, want_ckpt=False, every=1):
+        from . import sims
+        lib = _lib.require_library()
+        device, dtype = Mi.device, Mi.dtype
+        code, g, e1, e2, e1m1 = sims._prep_constants(γ2πdt, E1, E2, E1_1, p.N, p.Nd, dtype, device)
+        Mi_c = Mi.detach().contiguous()
+        sig = torch.empty((p.N, 2, -(-p.nT // every)), dtype=dtype, device=device)
+        Mo = torch.empty_like(Mi_c)
+        need = bool(want_ckpt)
+        ck = int(lib.mrphy_blochsim_rfgr_ck_every())
+        Mck = (torch.empty((-(-p.nT // ck), p.N * p.nM, 3), dtype=dtype, device=device)
+               if need else None)
+        nul = _host.NULL_BC
+        consts = (*g.args, *(e1.args if e1 else nul), *(e2.args if e2 else nul),
+                  e1m1.t.data_ptr() if e1m1 else None, None if rx is None else rx.data_ptr())
+        ckpt = (Mck.data_ptr() if need else None, ck if need else 0)
+        nbytes = int(lib.mrphy_signal_rfgr_fwd_workspace(code, p.N, p.nM, p.nT, every))
+        work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+        if p.nT == 0:
+            Mo.copy_(Mi_c)                      # no step, no record
+        with torch.cuda.device(device):
+            rc = lib.mrphy_signal_rfgr_fwd(code, Mi_c.data_ptr(), *p.k0_args(), *consts, Mo.data_ptr(), *ckpt,
+                                           sig.data_ptr(), every, work.data_ptr(), work.numel(),
+                                           p.N, p.nM, p.nT, p.nC, _host.current_stream(device))
+        _lib.check(rc, 'mrphy_signal_rfgr_fwd')
+        ctx.set_materialize_grads(False)
+        if need:
+            ctx.save_for_backward(Mck)
+            ctx.keep = (p, code, consts, (g, e1, e2, e1m1, rx), rf.shape, gr.shape, rf.dtype, gr.dtype, every)
+        return sig, Mo
+
+    @staticmethod
+    def backward(ctx, grad_sig, grad_Mo):
+        from .beffective import _fold_pulse_grad
+        need_Mi, need_rf, need_gr = ctx.needs_input_grad[0:3]
+        if not (need_Mi or need_rf or need_gr) or (grad_sig is None and grad_Mo is None):
+            return (None,) * 11
+        lib = _lib.require_library()
+        (Mck,) = ctx.saved_tensors
+        p, code, consts, _alive, rf_shape, gr_shape, rf_dtype, gr_dtype, every = ctx.keep
+        _host.require_invertible_relaxation(code, _alive[1], _alive[2], 'fused.signal_rfgr')
+        device, dtype = Mck.device, Mck.dtype
+        gs = None if grad_sig is None else grad_sig.to(dtype).contiguous()
+        gM = None if grad_Mo is None else grad_Mo.to(dtype).contiguous()
+        gMi = torch.empty((p.N,) + p.Nd + (3,), dtype=dtype, device=device) if need_Mi else None
+        g_rf = torch.empty((p.N, 2, p.nT, 1), dtype=dtype, device=device) if need_rf else None
+        g_gr = torch.empty((p.N, 3, p.nT), dtype=dtype, device=device) if need_gr else None
+        nbytes = int(lib.mrphy_blochsim_rfgr_bwd_workspace(code, p.N, p.nM, p.nT))
+        work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        with torch.cuda.device(device):
+            rc = lib.mrphy_signal_rfgr_bwd(code, Mck.data_ptr(), *p.k0_args(), *consts, ptr(gM), ptr(gs), every,
+                                           ptr(gMi), ptr(g_rf), ptr(g_gr), work.data_ptr(), work.numel(),
+                                           p.N, p.nM, p.nT, _host.current_stream(device))
+        _lib.check(rc, 'mrphy_signal_rfgr_bwd')
+        return (gMi,
+                _fold_pulse_grad(g_rf, rf_shape, rf_dtype, p.b1 is None) if need_rf else None,
+                _fold_pulse_grad(g_gr, gr_shape, gr_dtype, False) if need_gr else None,
+                None, None, None, None, None, None, None, None)
+
+
+def _route(Mi, rf, gr, loc, every, kw, signal=False, rx=None):
+    r"""The routing :func:`blochsim_rfgr` (``every = None``), :func:`blochsim_rfgr_traj` and (``signal``, with its
+    receive map ``rx``) :func:`signal_rfgr` share.  Returns
     ``('split', n1)``: a pulse gradient through the fused adjoint, but a length that is not a whole number of
     checkpoint segments -- the caller runs the first ``n1`` steps fused and composes the tail; ``('composed', None)``:
     a case the fused kernels do not cover (gradients w.r.t. the spin-side maps, fp64 with more than 8 coils, a pulse
-    gradient the fused adjoint cannot form); or ``('fused', M)``, the result of :class:`BlochSimRfGrHIP`."""
+    gradient the fused adjoint cannot form); or ``('fused', M)``, the result of :class:`BlochSimRfGrHIP` -- for the
+    signal the list of :class:`SignalRfGrHIP`'s ``(sig, Mo)``, one per receive coil.  The signal kernels take one
+    transmit coil and form no gradient w.r.t. ``rx``: parallel transmit and that gradient are composed."""
     from . import beffective, sims
     _host.require_device_tensor(Mi, 'Mi')
     Δf, b1Map, T1, T2 = kw['Δf'], kw['b1Map'], kw['T1'], kw['T2']
@@ -125,7 +201,7 @@ def _route(Mi, rf, gr, loc, every, kw):
     lib = _lib.require_library()
     grad_on = torch.is_grad_enabled()
     rq = lambda x: grad_on and isinstance(x, Tensor) and x.requires_grad  # noqa: E731
-    maps_grad = any(rq(x) for x in (loc, Δf, b1Map))
+    maps_grad = any(rq(x) for x in (loc, Δf, b1Map)) or (signal and rq(rx))
     pulse_grad = any(rq(x) for x in (Mi, rf, gr))
     p = beffective._PulseOnSpins(rf.detach(), gr.detach(), loc.detach(),
                                  None if Δf is None else Δf.detach(),
@@ -133,14 +209,14 @@ def _route(Mi, rf, gr, loc, every, kw):
     seg = int(lib.mrphy_blochsim_rfgr_ck_every())
     seg_ok = p.nT % seg == 0
     one_coil = p.nC == 1 and (rf.ndim == 3 or b1Map is not None or rf.shape[-1] == 1)
-    ptx = 1 < p.nC <= int(lib.mrphy_blochsim_rfgr_mc_max_coils()) and p.b1 is not None
+    ptx = 1 < p.nC <= int(lib.mrphy_blochsim_rfgr_mc_max_coils()) and p.b1 is not None and not signal
     fused_adjoint_ok = seg_ok and (one_coil or ptx)
     if pulse_grad and not maps_grad and not seg_ok and (one_coil or ptx) and p.nT > seg:
         return 'split', (p.nT // seg) * seg
     # fp64 with more than 8 transmit coils: the fused forward has no register build for it (it would spill),
     # the composed route does (k_rfgr2beff_steps / _pk + K1) and gives the same bits
     wide_f64 = (p.dtype == torch.float64 and p.nC > 8) or (p.b1 is not None and p.nC > 64)   # (> 64: coil-blocked K0 + K1)
-    if maps_grad or wide_f64 or (pulse_grad and not fused_adjoint_ok):
+    if maps_grad or wide_f64 or (pulse_grad and not fused_adjoint_ok) or (signal and p.nC != 1):
         return 'composed', None
 
     device, dtype = Mi.device, Mi.dtype
@@ -150,7 +226,15 @@ def _route(Mi, rf, gr, loc, every, kw):
         γ2πdt, E1, E2, E1_1 = (kw['consts'].get(k) for k in ('γ2πdt', 'E1', 'E2', 'E1_1'))
     else:
         γ2πdt, E1, E2, E1_1 = sims.relax_constants(T1, T2, kw['γ'], kw['dt'], 1 + len(p.Nd) + 2, device)
-    return 'fused', BlochSimRfGrHIP.apply(Mi, rf, gr, p, γ2πdt, E1, E2, E1_1, pulse_grad and fused_adjoint_ok, every)
+    want = pulse_grad and fused_adjoint_ok
+    if signal:
+        # one launch per receive coil ((N, *Nd, xy, nRx) -> nRx maps (N, nM, xy)); no rx: the plain sums
+        rxs = [None] if rx is None else \
+            list(rx.detach().to(device=device, dtype=dtype).expand((p.N,) + p.Nd + tuple(rx.shape[1 + len(p.Nd):]))
+                 .reshape(p.N, p.nM, 2, -1).unbind(-1))
+        return 'fused', [SignalRfGrHIP.apply(Mi, rf, gr, p, None if r is None else r.contiguous(), γ2πdt, E1, E2, E1_1,
+                                             want, every) for r in rxs]
+    return 'fused', BlochSimRfGrHIP.apply(Mi, rf, gr, p, γ2πdt, E1, E2, E1_1, want, every)
 
 
 @_host.half_via_float
@@ -243,3 +327,85 @@ def blochsim_rfgr_traj(
         Mt2 = _traj_by_segments(Mt1[-1], rf[:, :, n1:], gr[:, :, n1:], loc, tail, kw)
         return torch.cat((Mt1[:keep], Mt2)).movedim(0, -2)
     return _traj_by_segments(Mi, rf, gr, loc, ends, kw).movedim(0, -2)
+
+
+def _signal_of(Mt, rx):
+    r"""The signal of a time-major trajectory ``Mt`` `(nRec, N, *Nd, xyz)` in torch: `(N, xy, nRec)`, or
+    `(N, xy, nRec, nRx)` for ``rx`` `(N, *Nd, xy, nRx)` -- the complex product ``rx · (Mx + i My)`` (no conjugate) summed
+    over ``*Nd``."""
+    nRec, N, Nd = Mt.shape[0], Mt.shape[1], tuple(Mt.shape[2:-1])
+    Mx, My = Mt[..., 0].reshape(nRec, N, -1), Mt[..., 1].reshape(nRec, N, -1)
+    if rx is None:
+        return torch.stack((Mx.sum(-1), My.sum(-1)), dim=0).permute(2, 0, 1)
+    coils = rx.ndim == Mt.ndim
+    r = rx.to(device=Mt.device, dtype=Mt.dtype).expand((N,) + Nd + tuple(rx.shape[1 + len(Nd):])) \
+        .reshape(N, -1, 2, rx.shape[-1] if coils else 1)
+    rr, ri = r[:, :, 0], r[:, :, 1]
+    ein = lambda m, c: torch.einsum('jns,nsc->njc', m, c)  # noqa: E731
+    sig = torch.stack((ein(Mx, rr) - ein(My, ri), ein(My, rr) + ein(Mx, ri)), dim=1)
+    return sig if coils else sig[..., 0]
+
+
+def _signal_composed(Mi, rf, gr, loc, every, rx, kw):
+    r"""``(sig, Mo)`` as :func:`blochsim_rfgr_traj` followed by the product with ``rx`` and the sum over spins in torch:
+    correct and differentiable wherever the trajectory is (parallel transmit, gradients w.r.t. the spin-side maps and
+    w.r.t. ``rx``), at the price of the trajectory in memory -- the route of the cases the signal kernels do not cover,
+    and the tests' yardstick."""
+    Mt = blochsim_rfgr_traj(Mi, rf, gr, loc, every=every, **kw).movedim(-2, 0)
+    return _signal_of(Mt, rx), Mt[-1]
+
+
+@_host.half_via_float
+def signal_rfgr(
+    Mi: Tensor, rf: Tensor, gr: Tensor, loc: Tensor, *, every: int = 1, rx: Optional[Tensor] = None,
+    return_Mo: bool = False,
+    Δf: Optional[Tensor] = None, b1Map: Optional[Tensor] = None, γ_beff: Tensor = γH,
+    T1: Optional[Tensor] = None, T2: Optional[Tensor] = None,
+    γ: Tensor = γH, dt: Tensor = dt0, consts: Optional[dict] = None
+):
+    r"""The signal a receive coil measures during the pulse of :func:`blochsim_rfgr`: the transverse magnetisation
+    summed over the spins ``*Nd`` at the record steps of :func:`blochsim_rfgr_traj` (``nRec = ceil(nT / every)``,
+    record ``j`` from M after step ``min((j+1)·every, nT) - 1``), weighted by the receive map ``rx`` as ``b1Map``
+    weights ``rf`` (a complex product, no conjugate):
+
+        ``sig[n, 0, j] = Σ_s rx_re·Mx − rx_im·My``,  ``sig[n, 1, j] = Σ_s rx_re·My + rx_im·Mx``.
+
+    ``rx``: `(N, *Nd, xy)` or `(N, *Nd, xy, nRx)`, the layout of ``b1Map``; ``None`` is ``(1, 0)``, the plain sums of
+    ``Mx`` and ``My``.  Returns ``sig`` `(N, xy, nRec)` -- `(N, xy, nRec, nRx)` when ``rx`` has a coil axis -- the layout
+    of ``rf``; with ``return_Mo=True`` ``(sig, Mo)``, where ``Mo`` equals ``blochsim_rfgr(...)`` bit for bit, so a
+    sequence can carry on from it.  Differentiable w.r.t. ``Mi``, ``rf``, ``gr`` through both outputs; the other
+    arguments, the dtypes, ``consts`` and the precision mode as :func:`blochsim_rfgr_traj`.  The reference has no
+    counterpart (it forms ``Mhst`` and drops it, ``sims.py:83,131``): this is an extension.
+
+    The sum is formed inside the kernel (K2s; the adjoint is a mode of K2b): no trajectory is written to memory, the
+    order of summation is fixed, and the same inputs give the same bits.  Covered: one transmit coil with or without
+    ``b1Map``, fp32 in both precision modes and fp64.  Several receive coils run one launch per coil and the results
+    are stacked -- a multi-coil reduction in one launch is a follow-up.  A gradient with a pulse length that is not a
+    multiple of the 16-step checkpoint segment is split as :func:`blochsim_rfgr_traj` splits it.  Parallel transmit,
+    gradients w.r.t. ``loc``/``Δf``/``b1Map``/``rx`` and fp64 above 8 coils compose :func:`blochsim_rfgr_traj` with
+    the product and the sum in torch.  On a spin axis sharded over GPUs the signal is the sum of the ranks' signals
+    (``dist.all_reduce_pulse_grads`` reduces tensors of this size).
+    """
+    if isinstance(every, bool) or not isinstance(every, int) or every < 1:
+        raise ValueError(f"mrphy_amd: `every` must be an int >= 1, got {every!r}")
+    kw = dict(Δf=Δf, b1Map=b1Map, γ_beff=γ_beff, T1=T1, T2=T2, γ=γ, dt=dt, consts=consts)
+    _host.require_device_tensor(Mi, 'Mi')
+    if rx is not None:
+        assert rx.ndim in (Mi.ndim, Mi.ndim + 1) and rx.shape[Mi.ndim - 1] == 2, "rx must be (N, *Nd, xy[, nRx])"
+    route, out = _route(Mi, rf, gr, loc, every, kw, signal=True, rx=rx)
+    if route == 'fused':
+        if rx is not None and rx.ndim == Mi.ndim + 1:
+            sig, Mo = torch.stack([o[0] for o in out], dim=-1), out[0][1]
+        else:
+            sig, Mo = out[0]
+    elif route == 'split':
+        # fused part of floor(nT/16)*16 steps + composed tail of <= 15: the part's records up to n1 (its own last record
+        # is one of them only if it falls on one), its final state carries on into the tail's records
+        n1, ends = out, _traj_ends(gr.shape[2], every)
+        sig1, M1 = signal_rfgr(Mi, rf[:, :, :n1], gr[:, :, :n1], loc, every=every, rx=rx, return_Mo=True, **kw)
+        keep = sum(1 for e in ends if e <= n1)
+        Mt2 = _traj_by_segments(M1, rf[:, :, n1:], gr[:, :, n1:], loc, [e - n1 for e in ends if e > n1], kw)
+        sig, Mo = torch.cat((sig1[:, :, :keep], _signal_of(Mt2, rx)), dim=2), Mt2[-1]
+    else:
+        sig, Mo = _signal_composed(Mi, rf, gr, loc, every, rx, kw)
+    return (sig, Mo) if return_Mo else sig
