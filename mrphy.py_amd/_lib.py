@@ -23,6 +23,9 @@ F32, F64, F32_C64, F32P, F32P_C64 = 0, 1, 2, 3, 4
 _c = ctypes
 _vp, _i64, _int, _sz = _c.c_void_p, _c.c_int64, _c.c_int, _c.c_size_t
 _BC = [_vp, _i64, _i64]            # broadcastable per-spin constant: ptr, stride_n, stride_m
+# the operands of the fused family, rf .. E1m1 of mrphy_hip.h: rf, rf_sn, gr, gr_sn, loc, df, gamma, b1, g, E1, E2, E1m1
+_PULSE_OPS = [_vp, _i64, _vp, _i64, _vp] + _BC + _BC + [_vp] + _BC * 3 + [_vp]
+_FUSED = [_int, _vp] + _PULSE_OPS  # how its eight entry points begin: dtype, Mi (the adjoints: Mck), the operands
 
 # name -> (restype, argtypes); MUST list every function declared in include/mrphy_hip.h
 PROTOTYPES = {
@@ -49,28 +52,19 @@ PROTOTYPES = {
     'mrphy_blochsim_bwd_parts': (_int, [_int, _vp, _i64, _int, _vp] + _BC * 3 + [_vp, _vp, _vp, _vp] + [_i64] * 3
                                  + [_vp]),
     'mrphy_blochsim_1step': (_int, [_int, _vp, _vp] + _BC * 3 + [_vp, _vp] + [_i64] * 2 + [_vp]),
-    'mrphy_blochsim_rfgr_fwd': (_int, [_int, _vp, _vp, _i64, _vp, _i64, _vp] + _BC + _BC + [_vp]
-                                + _BC * 3 + [_vp, _vp, _vp, _i64] + [_i64] * 4 + [_vp]),
+    'mrphy_blochsim_rfgr_fwd': (_int, _FUSED + [_vp, _vp, _i64] + [_i64] * 4 + [_vp]),
     'mrphy_blochsim_rfgr_ck_every': (_i64, []),
     'mrphy_blochsim_rfgr_bwd_workspace': (_sz, [_int] + [_i64] * 3),
-    'mrphy_blochsim_rfgr_bwd': (_int, [_int, _vp, _vp, _i64, _vp, _i64, _vp] + _BC + _BC + [_vp]
-                                + _BC * 3 + [_vp, _vp, _vp, _vp, _vp, _vp, _sz] + [_i64] * 3 + [_vp]),
+    'mrphy_blochsim_rfgr_bwd': (_int, _FUSED + [_vp, _vp, _vp, _vp, _vp, _sz] + [_i64] * 3 + [_vp]),
     'mrphy_blochsim_rfgr_mc_max_coils': (_i64, []),
     'mrphy_blochsim_rfgr_mc_bwd_workspace': (_sz, [_int] + [_i64] * 4),
-    'mrphy_blochsim_rfgr_mc_bwd': (_int, [_int, _vp, _vp, _i64, _vp, _i64, _vp] + _BC + _BC + [_vp]
-                                   + _BC * 3 + [_vp, _vp, _vp, _vp, _vp, _vp, _sz] + [_i64] * 4 + [_vp]),
-    'mrphy_blochsim_rfgr_traj_fwd': (_int, [_int, _vp, _vp, _i64, _vp, _i64, _vp] + _BC + _BC + [_vp]
-                                     + _BC * 3 + [_vp, _vp, _vp, _i64, _vp, _i64] + [_i64] * 4 + [_vp]),
-    'mrphy_blochsim_rfgr_traj_bwd': (_int, [_int, _vp, _vp, _i64, _vp, _i64, _vp] + _BC + _BC + [_vp]
-                                     + _BC * 3 + [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _sz] + [_i64] * 3 + [_vp]),
-    'mrphy_blochsim_rfgr_mc_traj_bwd': (_int, [_int, _vp, _vp, _i64, _vp, _i64, _vp] + _BC + _BC + [_vp]
-                                        + _BC * 3 + [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _sz] + [_i64] * 4
-                                        + [_vp]),
+    'mrphy_blochsim_rfgr_mc_bwd': (_int, _FUSED + [_vp, _vp, _vp, _vp, _vp, _sz] + [_i64] * 4 + [_vp]),
+    'mrphy_blochsim_rfgr_traj_fwd': (_int, _FUSED + [_vp, _vp, _i64, _vp, _i64] + [_i64] * 4 + [_vp]),
+    'mrphy_blochsim_rfgr_traj_bwd': (_int, _FUSED + [_vp, _i64, _vp, _vp, _vp, _vp, _sz] + [_i64] * 3 + [_vp]),
+    'mrphy_blochsim_rfgr_mc_traj_bwd': (_int, _FUSED + [_vp, _i64, _vp, _vp, _vp, _vp, _sz] + [_i64] * 4 + [_vp]),
     'mrphy_signal_rfgr_fwd_workspace': (_sz, [_int] + [_i64] * 4),
-    'mrphy_signal_rfgr_fwd': (_int, [_int, _vp, _vp, _i64, _vp, _i64, _vp] + _BC + _BC + [_vp]
-                              + _BC * 3 + [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _sz] + [_i64] * 4 + [_vp]),
-    'mrphy_signal_rfgr_bwd': (_int, [_int, _vp, _vp, _i64, _vp, _i64, _vp] + _BC + _BC + [_vp]
-                              + _BC * 3 + [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _sz] + [_i64] * 3 + [_vp]),
+    'mrphy_signal_rfgr_fwd': (_int, _FUSED + [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _sz] + [_i64] * 4 + [_vp]),
+    'mrphy_signal_rfgr_bwd': (_int, _FUSED + [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _sz] + [_i64] * 3 + [_vp]),
     'mrphy_freeprec_fwd': (_int, [_int, _vp, _vp, _i64] + _BC * 3 + [_vp, _i64, _i64, _vp]),
     'mrphy_freeprec_bwd': (_int, [_int, _vp, _vp, _i64] + _BC * 3 + [_vp, _i64, _i64, _vp]),
     'mrphy_freeprec_bwd_consts': (_int, [_int, _vp, _vp, _vp, _i64] + _BC * 3 + [_vp, _i64, _i64, _vp]),

@@ -1,5 +1,6 @@
 // abi.hip -- the C ABI of libmrphy_hip.so (include/mrphy_hip.h): argument validation and dispatch on the
-// dtype code to the launchers of the tu_*.hip units (internal.hpp).  No kernel is defined here.
+// dtype code to the launchers of the tu_*.hip units (internal.hpp).  No kernel is defined here.  The operands of the
+// fused family are packed into one struct at the entry point (MRPHY_PULSE_OPS below) and travel as that struct.
 #include "host_common.hpp"
 
 using namespace mrphy_i;
@@ -33,76 +34,78 @@ int make_hist_parts(int dtype, void* const* parts, int64_t n_parts, int layout, 
     return 0;
 }
 
-// The fused simulation (K2 / K2b) and its trajectory builds: each plain entry point and its `_traj_` twin share one
-// validation and dispatch.  `traj` tells them apart; what differs is written out where it differs.  The launchers take
-// a null Mt / grad_Mt for the plain kernels.
-int rfgr_fwd(bool traj, int dtype, const void* Mi, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
-             const void* loc, const void* df, int64_t df_sn, int64_t df_sm, const void* gamma, int64_t gamma_sn,
-             int64_t gamma_sm, const void* b1, const void* g, int64_t g_sn, int64_t g_sm, const void* E1,
-             int64_t E1_sn, int64_t E1_sm, const void* E2, int64_t E2_sn, int64_t E2_sm, const void* E1m1, void* Mo,
-             void* Mck, int64_t ck_every, void* Mt, int64_t every, int64_t N, int64_t nM, int64_t nT, int64_t nC,
-             void* stream)
+// The fused family (K2, K2b, K2s, their trajectory and multi-coil builds).  Every entry point takes the same 24 scalars
+// -- the pulse on the spins plus the step constants, rf .. E1m1 of include/mrphy_hip.h -- under the same names:
+// MRPHY_PULSE_OPS packs them, once per entry point, into the PulseOps (geom.hpp) that the checks, the launchers and
+// the kernel arguments take from there on.
+#define MRPHY_PULSE_OPS_PARAMS                                                                                     \
+    const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn, const void* loc, const void* df, int64_t df_sn,  \
+    int64_t df_sm, const void* gamma, int64_t gamma_sn, int64_t gamma_sm, const void* b1, const void* g,           \
+    int64_t g_sn, int64_t g_sm, const void* E1, int64_t E1_sn, int64_t E1_sm, const void* E2, int64_t E2_sn,       \
+    int64_t E2_sm, const void* E1m1
+#define MRPHY_PULSE_OPS                                                                                            \
+    PulseOps{rf, rf_sn, gr, gr_sn, loc, {df, df_sn, df_sm}, {gamma, gamma_sn, gamma_sm}, b1, {g, g_sn, g_sm},      \
+             {E1, E1_sn, E1_sm}, {E2, E2_sn, E2_sm}, E1m1}
+
+// The null checks of the operands, shared by all eight: loc and g always; df only with gamma; E1, E2 and E1m1 all or
+// none.  What differs is a parameter: the plain forward runs without a pulse at nT == 0 (need_pulse), the multi-coil
+// adjoint cannot do without a b1 map (need_b1).  No alignment checks: the fused entry points have none.
+int check_ops(const PulseOps& in, bool need_pulse, bool need_b1)
+{
+    if (!in.loc || !in.g.p || (need_pulse && (!in.rf || !in.gr)) || (need_b1 && !in.b1) || (in.df.p && !in.gam.p))
+        return MRPHY_EINVAL;
+    if ((in.E1.p == nullptr) != (in.E2.p == nullptr) || (in.E1.p == nullptr) != (in.E1m1 == nullptr))
+        return MRPHY_EINVAL;
+    return 0;
+}
+
+// Each plain entry point and its `_traj_` twin share one validation and dispatch.  `traj` tells them apart; what
+// differs is written out where it differs.  The launchers take a null Mt / grad_Mt for the plain kernels.  Order of
+// the checks, everywhere: dtype and sizes, the mode arguments, the empty problem (0), null pointers, the workspace.
+int rfgr_fwd(bool traj, int dtype, const void* Mi, const PulseOps& in, void* Mo, void* Mck, int64_t ck_every, void* Mt,
+             int64_t every, int64_t N, int64_t nM, int64_t nT, int64_t nC, void* stream)
 {
     if (int e = check_common(dtype, N, nM, nT)) return e;
-    if ((traj && every < 1) || nC < 1 || (!b1 && nC != 1) || (Mck && (ck_every < 8 || ck_every % 8 != 0)))
+    // (a forward of several coils needs their b1 map: a mode argument, rejected on an empty problem too)
+    if ((traj && every < 1) || nC < 1 || (!in.b1 && nC != 1) || (Mck && (ck_every < 8 || ck_every % 8 != 0)))
         return MRPHY_EINVAL;
     if (N * nM * (traj ? nT : 1) == 0) return 0;          // the plain forward runs at nT == 0: Mo = Mi
     // the trajectory's Mo is optional (it equals the last record)
-    if (!Mi || !(traj ? Mt : Mo) || !loc || !g || (nT > 0 && (!rf || !gr)) || (df && !gamma))
-        return MRPHY_EINVAL;
-    if ((E1 == nullptr) != (E2 == nullptr) || (E1 == nullptr) != (E1m1 == nullptr))
-        return MRPHY_EINVAL;
-    const Bc bdf = {df, df_sn, df_sm}, bgam = {gamma, gamma_sn, gamma_sm};
-    const Bc bg = {g, g_sn, g_sm}, be1 = {E1, E1_sn, E1_sm}, be2 = {E2, E2_sn, E2_sm};
+    if (!Mi || !(traj ? Mt : Mo)) return MRPHY_EINVAL;
+    if (int e = check_ops(in, nT > 0, false)) return e;
     hipStream_t st = (hipStream_t)stream;
-    MRPHY_DISPATCH(dtype, (run_rfgr_fwd<T, CT>(Mi, rf, rf_sn, gr, gr_sn, loc, bdf, bgam, b1, bg, be1, be2, E1m1, Mo,
-                                               Mck, ck_every, Mt, every, N, nM, nT, nC, st)));
+    MRPHY_DISPATCH(dtype, (run_rfgr_fwd<T, CT>(Mi, in, Mo, Mck, ck_every, Mt, every, N, nM, nT, nC, st)));
 }
 
 // grad_M: grad_Mo, or (traj) grad_Mt
-int rfgr_bwd(bool traj, int dtype, const void* Mck, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
-             const void* loc, const void* df, int64_t df_sn, int64_t df_sm, const void* gamma, int64_t gamma_sn,
-             int64_t gamma_sm, const void* b1, const void* g, int64_t g_sn, int64_t g_sm, const void* E1,
-             int64_t E1_sn, int64_t E1_sm, const void* E2, int64_t E2_sn, int64_t E2_sm, const void* E1m1,
-             const void* grad_M, int64_t every, void* grad_Mi, void* grad_rf, void* grad_gr, void* work,
-             size_t work_bytes, int64_t N, int64_t nM, int64_t nT, void* stream)
+int rfgr_bwd(bool traj, int dtype, const void* Mck, const PulseOps& in, const void* grad_M, int64_t every,
+             void* grad_Mi, void* grad_rf, void* grad_gr, void* work, size_t work_bytes, int64_t N, int64_t nM,
+             int64_t nT, void* stream)
 {
     if (int e = check_common(dtype, N, nM, nT)) return e;
     if (nT % SEG != 0 || (traj && every < 1)) return MRPHY_EINVAL;   // whole checkpoint segments only
     if (N * nM * nT == 0) return 0;
-    if (!Mck || !rf || !gr || !loc || !g || !grad_M || !work || (df && !gamma)) return MRPHY_EINVAL;
-    if ((E1 == nullptr) != (E2 == nullptr) || (E1 == nullptr) != (E1m1 == nullptr))
-        return MRPHY_EINVAL;
+    if (!Mck || !grad_M || !work) return MRPHY_EINVAL;
+    if (int e = check_ops(in, true, false)) return e;
     if (work_bytes < mrphy_blochsim_rfgr_bwd_workspace(dtype, N, nM, nT)) return MRPHY_ENOSPC;
-    const Bc bdf = {df, df_sn, df_sm}, bgam = {gamma, gamma_sn, gamma_sm};
-    const Bc bg = {g, g_sn, g_sm}, be1 = {E1, E1_sn, E1_sm}, be2 = {E2, E2_sn, E2_sm};
     hipStream_t st = (hipStream_t)stream;
-    MRPHY_DISPATCH(dtype, (run_rfgr_bwd<T, CT>(Mck, rf, rf_sn, gr, gr_sn, loc, bdf, bgam, b1, bg, be1, be2, E1m1,
-                                               traj ? nullptr : grad_M, traj ? grad_M : nullptr, every, nullptr,
-                                               nullptr, grad_Mi, grad_rf, grad_gr, work, N, nM, nT, st)));
+    MRPHY_DISPATCH(dtype, (run_rfgr_bwd<T, CT>(Mck, in, traj ? nullptr : grad_M, traj ? grad_M : nullptr, every,
+                                               nullptr, nullptr, grad_Mi, grad_rf, grad_gr, work, N, nM, nT, st)));
 }
 
-int rfgr_mc_bwd(bool traj, int dtype, const void* Mck, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
-                const void* loc, const void* df, int64_t df_sn, int64_t df_sm, const void* gamma, int64_t gamma_sn,
-                int64_t gamma_sm, const void* b1, const void* g, int64_t g_sn, int64_t g_sm, const void* E1,
-                int64_t E1_sn, int64_t E1_sm, const void* E2, int64_t E2_sn, int64_t E2_sm, const void* E1m1,
-                const void* grad_M, int64_t every, void* grad_Mi, void* grad_rf, void* grad_gr, void* work,
-                size_t work_bytes, int64_t N, int64_t nM, int64_t nT, int64_t nC, void* stream)
+int rfgr_mc_bwd(bool traj, int dtype, const void* Mck, const PulseOps& in, const void* grad_M, int64_t every,
+                void* grad_Mi, void* grad_rf, void* grad_gr, void* work, size_t work_bytes, int64_t N, int64_t nM,
+                int64_t nT, int64_t nC, void* stream)
 {
     if (int e = check_common(dtype, N, nM, nT)) return e;
     if (nT % SEG != 0 || (traj && every < 1) || nC < 1 || nC > K2B_MAXC) return MRPHY_EINVAL;
     if (N * nM * nT == 0) return 0;
-    if (!Mck || !rf || !gr || !loc || !b1 || !g || !grad_M || !work || (df && !gamma))
-        return MRPHY_EINVAL;
-    if ((E1 == nullptr) != (E2 == nullptr) || (E1 == nullptr) != (E1m1 == nullptr))
-        return MRPHY_EINVAL;
+    if (!Mck || !grad_M || !work) return MRPHY_EINVAL;
+    if (int e = check_ops(in, true, true)) return e;
     if (work_bytes < mrphy_blochsim_rfgr_mc_bwd_workspace(dtype, N, nM, nT, nC)) return MRPHY_ENOSPC;
-    const Bc bdf = {df, df_sn, df_sm}, bgam = {gamma, gamma_sn, gamma_sm};
-    const Bc bg = {g, g_sn, g_sm}, be1 = {E1, E1_sn, E1_sm}, be2 = {E2, E2_sn, E2_sm};
     hipStream_t st = (hipStream_t)stream;
-    MRPHY_DISPATCH(dtype, (run_rfgr_mc_bwd<T, CT>(Mck, rf, rf_sn, gr, gr_sn, loc, bdf, bgam, b1, bg, be1, be2, E1m1,
-                                                  traj ? nullptr : grad_M, traj ? grad_M : nullptr, every, grad_Mi,
-                                                  grad_rf, grad_gr, work, N, nM, nT, nC, st)));
+    MRPHY_DISPATCH(dtype, (run_rfgr_mc_bwd<T, CT>(Mck, in, traj ? nullptr : grad_M, traj ? grad_M : nullptr, every,
+                                                  grad_Mi, grad_rf, grad_gr, work, N, nM, nT, nC, st)));
 }
 }  // namespace
 
@@ -286,18 +289,10 @@ int mrphy_blochsim_1step(int dtype, const void* M, const void* b, const void* g,
                               E1m1, Mout, nullptr, N, nM, 1, stream);
 }
 
-int mrphy_blochsim_rfgr_fwd(int dtype, const void* Mi, const void* rf, int64_t rf_sn,
-                            const void* gr, int64_t gr_sn, const void* loc, const void* df,
-                            int64_t df_sn, int64_t df_sm, const void* gamma, int64_t gamma_sn,
-                            int64_t gamma_sm, const void* b1, const void* g, int64_t g_sn,
-                            int64_t g_sm, const void* E1, int64_t E1_sn, int64_t E1_sm,
-                            const void* E2, int64_t E2_sn, int64_t E2_sm, const void* E1m1,
-                            void* Mo, void* Mck, int64_t ck_every, int64_t N, int64_t nM,
-                            int64_t nT, int64_t nC, void* stream)
+int mrphy_blochsim_rfgr_fwd(int dtype, const void* Mi, MRPHY_PULSE_OPS_PARAMS, void* Mo, void* Mck, int64_t ck_every,
+                            int64_t N, int64_t nM, int64_t nT, int64_t nC, void* stream)
 {
-    return rfgr_fwd(false, dtype, Mi, rf, rf_sn, gr, gr_sn, loc, df, df_sn, df_sm, gamma, gamma_sn, gamma_sm, b1, g,
-                    g_sn, g_sm, E1, E1_sn, E1_sm, E2, E2_sn, E2_sm, E1m1, Mo, Mck, ck_every, nullptr, 0, N, nM, nT,
-                    nC, stream);
+    return rfgr_fwd(false, dtype, Mi, MRPHY_PULSE_OPS, Mo, Mck, ck_every, nullptr, 0, N, nM, nT, nC, stream);
 }
 
 int64_t mrphy_blochsim_rfgr_ck_every(void) { return SEG; }
@@ -308,19 +303,12 @@ size_t mrphy_blochsim_rfgr_bwd_workspace(int dtype, int64_t N, int64_t nM, int64
     return (size_t)(k2b_waves(nM) * N * 5 * nT) * tsize(dtype);
 }
 
-int mrphy_blochsim_rfgr_bwd(int dtype, const void* Mck, const void* rf, int64_t rf_sn,
-                            const void* gr, int64_t gr_sn, const void* loc, const void* df,
-                            int64_t df_sn, int64_t df_sm, const void* gamma, int64_t gamma_sn,
-                            int64_t gamma_sm, const void* b1, const void* g, int64_t g_sn,
-                            int64_t g_sm, const void* E1, int64_t E1_sn, int64_t E1_sm,
-                            const void* E2, int64_t E2_sn, int64_t E2_sm, const void* E1m1,
-                            const void* grad_Mo, void* grad_Mi, void* grad_rf, void* grad_gr,
-                            void* work, size_t work_bytes, int64_t N, int64_t nM, int64_t nT,
-                            void* stream)
+int mrphy_blochsim_rfgr_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PARAMS, const void* grad_Mo, void* grad_Mi,
+                            void* grad_rf, void* grad_gr, void* work, size_t work_bytes, int64_t N, int64_t nM,
+                            int64_t nT, void* stream)
 {
-    return rfgr_bwd(false, dtype, Mck, rf, rf_sn, gr, gr_sn, loc, df, df_sn, df_sm, gamma, gamma_sn, gamma_sm, b1,
-                    g, g_sn, g_sm, E1, E1_sn, E1_sm, E2, E2_sn, E2_sm, E1m1, grad_Mo, 0, grad_Mi, grad_rf, grad_gr,
-                    work, work_bytes, N, nM, nT, stream);
+    return rfgr_bwd(false, dtype, Mck, MRPHY_PULSE_OPS, grad_Mo, 0, grad_Mi, grad_rf, grad_gr, work, work_bytes, N, nM,
+                    nT, stream);
 }
 
 int64_t mrphy_blochsim_rfgr_mc_max_coils(void) { return K2B_MAXC; }
@@ -331,63 +319,35 @@ size_t mrphy_blochsim_rfgr_mc_bwd_workspace(int dtype, int64_t N, int64_t nM, in
     return (size_t)(k2b_mc_waves(nM) * N * (3 + 2 * nC) * nT) * tsize(dtype);
 }
 
-int mrphy_blochsim_rfgr_mc_bwd(int dtype, const void* Mck, const void* rf, int64_t rf_sn,
-                               const void* gr, int64_t gr_sn, const void* loc, const void* df,
-                               int64_t df_sn, int64_t df_sm, const void* gamma, int64_t gamma_sn,
-                               int64_t gamma_sm, const void* b1, const void* g, int64_t g_sn,
-                               int64_t g_sm, const void* E1, int64_t E1_sn, int64_t E1_sm,
-                               const void* E2, int64_t E2_sn, int64_t E2_sm, const void* E1m1,
-                               const void* grad_Mo, void* grad_Mi, void* grad_rf, void* grad_gr,
-                               void* work, size_t work_bytes, int64_t N, int64_t nM, int64_t nT,
-                               int64_t nC, void* stream)
+int mrphy_blochsim_rfgr_mc_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PARAMS, const void* grad_Mo, void* grad_Mi,
+                               void* grad_rf, void* grad_gr, void* work, size_t work_bytes, int64_t N, int64_t nM,
+                               int64_t nT, int64_t nC, void* stream)
 {
-    return rfgr_mc_bwd(false, dtype, Mck, rf, rf_sn, gr, gr_sn, loc, df, df_sn, df_sm, gamma, gamma_sn, gamma_sm,
-                       b1, g, g_sn, g_sm, E1, E1_sn, E1_sm, E2, E2_sn, E2_sm, E1m1, grad_Mo, 0, grad_Mi, grad_rf,
-                       grad_gr, work, work_bytes, N, nM, nT, nC, stream);
+    return rfgr_mc_bwd(false, dtype, Mck, MRPHY_PULSE_OPS, grad_Mo, 0, grad_Mi, grad_rf, grad_gr, work, work_bytes, N,
+                       nM, nT, nC, stream);
 }
 
-int mrphy_blochsim_rfgr_traj_fwd(int dtype, const void* Mi, const void* rf, int64_t rf_sn,
-                                 const void* gr, int64_t gr_sn, const void* loc, const void* df,
-                                 int64_t df_sn, int64_t df_sm, const void* gamma, int64_t gamma_sn,
-                                 int64_t gamma_sm, const void* b1, const void* g, int64_t g_sn,
-                                 int64_t g_sm, const void* E1, int64_t E1_sn, int64_t E1_sm,
-                                 const void* E2, int64_t E2_sn, int64_t E2_sm, const void* E1m1,
-                                 void* Mo, void* Mck, int64_t ck_every, void* Mt, int64_t every,
-                                 int64_t N, int64_t nM, int64_t nT, int64_t nC, void* stream)
+int mrphy_blochsim_rfgr_traj_fwd(int dtype, const void* Mi, MRPHY_PULSE_OPS_PARAMS, void* Mo, void* Mck,
+                                 int64_t ck_every, void* Mt, int64_t every, int64_t N, int64_t nM, int64_t nT,
+                                 int64_t nC, void* stream)
 {
-    return rfgr_fwd(true, dtype, Mi, rf, rf_sn, gr, gr_sn, loc, df, df_sn, df_sm, gamma, gamma_sn, gamma_sm, b1, g,
-                    g_sn, g_sm, E1, E1_sn, E1_sm, E2, E2_sn, E2_sm, E1m1, Mo, Mck, ck_every, Mt, every, N, nM, nT,
-                    nC, stream);
+    return rfgr_fwd(true, dtype, Mi, MRPHY_PULSE_OPS, Mo, Mck, ck_every, Mt, every, N, nM, nT, nC, stream);
 }
 
-int mrphy_blochsim_rfgr_traj_bwd(int dtype, const void* Mck, const void* rf, int64_t rf_sn,
-                                 const void* gr, int64_t gr_sn, const void* loc, const void* df,
-                                 int64_t df_sn, int64_t df_sm, const void* gamma, int64_t gamma_sn,
-                                 int64_t gamma_sm, const void* b1, const void* g, int64_t g_sn,
-                                 int64_t g_sm, const void* E1, int64_t E1_sn, int64_t E1_sm,
-                                 const void* E2, int64_t E2_sn, int64_t E2_sm, const void* E1m1,
-                                 const void* grad_Mt, int64_t every, void* grad_Mi, void* grad_rf,
-                                 void* grad_gr, void* work, size_t work_bytes, int64_t N, int64_t nM,
-                                 int64_t nT, void* stream)
+int mrphy_blochsim_rfgr_traj_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PARAMS, const void* grad_Mt, int64_t every,
+                                 void* grad_Mi, void* grad_rf, void* grad_gr, void* work, size_t work_bytes, int64_t N,
+                                 int64_t nM, int64_t nT, void* stream)
 {
-    return rfgr_bwd(true, dtype, Mck, rf, rf_sn, gr, gr_sn, loc, df, df_sn, df_sm, gamma, gamma_sn, gamma_sm, b1, g,
-                    g_sn, g_sm, E1, E1_sn, E1_sm, E2, E2_sn, E2_sm, E1m1, grad_Mt, every, grad_Mi, grad_rf, grad_gr,
-                    work, work_bytes, N, nM, nT, stream);
+    return rfgr_bwd(true, dtype, Mck, MRPHY_PULSE_OPS, grad_Mt, every, grad_Mi, grad_rf, grad_gr, work, work_bytes, N,
+                    nM, nT, stream);
 }
 
-int mrphy_blochsim_rfgr_mc_traj_bwd(int dtype, const void* Mck, const void* rf, int64_t rf_sn,
-                                    const void* gr, int64_t gr_sn, const void* loc, const void* df,
-                                    int64_t df_sn, int64_t df_sm, const void* gamma, int64_t gamma_sn,
-                                    int64_t gamma_sm, const void* b1, const void* g, int64_t g_sn,
-                                    int64_t g_sm, const void* E1, int64_t E1_sn, int64_t E1_sm,
-                                    const void* E2, int64_t E2_sn, int64_t E2_sm, const void* E1m1,
-                                    const void* grad_Mt, int64_t every, void* grad_Mi, void* grad_rf,
-                                    void* grad_gr, void* work, size_t work_bytes, int64_t N, int64_t nM,
-                                    int64_t nT, int64_t nC, void* stream)
+int mrphy_blochsim_rfgr_mc_traj_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PARAMS, const void* grad_Mt,
+                                    int64_t every, void* grad_Mi, void* grad_rf, void* grad_gr, void* work,
+                                    size_t work_bytes, int64_t N, int64_t nM, int64_t nT, int64_t nC, void* stream)
 {
-    return rfgr_mc_bwd(true, dtype, Mck, rf, rf_sn, gr, gr_sn, loc, df, df_sn, df_sm, gamma, gamma_sn, gamma_sm, b1,
-                       g, g_sn, g_sm, E1, E1_sn, E1_sm, E2, E2_sn, E2_sm, E1m1, grad_Mt, every, grad_Mi, grad_rf,
-                       grad_gr, work, work_bytes, N, nM, nT, nC, stream);
+    return rfgr_mc_bwd(true, dtype, Mck, MRPHY_PULSE_OPS, grad_Mt, every, grad_Mi, grad_rf, grad_gr, work, work_bytes,
+                       N, nM, nT, nC, stream);
 }
 
 size_t mrphy_signal_rfgr_fwd_workspace(int dtype, int64_t N, int64_t nM, int64_t nT, int64_t every)
@@ -396,55 +356,37 @@ size_t mrphy_signal_rfgr_fwd_workspace(int dtype, int64_t N, int64_t nM, int64_t
     return (size_t)(sig_waves(nM) * N * 2 * sig_records(nT, every)) * tsize(dtype);
 }
 
-int mrphy_signal_rfgr_fwd(int dtype, const void* Mi, const void* rf, int64_t rf_sn,
-                          const void* gr, int64_t gr_sn, const void* loc, const void* df,
-                          int64_t df_sn, int64_t df_sm, const void* gamma, int64_t gamma_sn,
-                          int64_t gamma_sm, const void* b1, const void* g, int64_t g_sn,
-                          int64_t g_sm, const void* E1, int64_t E1_sn, int64_t E1_sm,
-                          const void* E2, int64_t E2_sn, int64_t E2_sm, const void* E1m1,
-                          const void* rx, void* Mo, void* Mck, int64_t ck_every, void* sig, int64_t every,
-                          void* work, size_t work_bytes, int64_t N, int64_t nM, int64_t nT, int64_t nC,
-                          void* stream)
+int mrphy_signal_rfgr_fwd(int dtype, const void* Mi, MRPHY_PULSE_OPS_PARAMS, const void* rx, void* Mo, void* Mck,
+                          int64_t ck_every, void* sig, int64_t every, void* work, size_t work_bytes, int64_t N,
+                          int64_t nM, int64_t nT, int64_t nC, void* stream)
 {
     if (int e = check_common(dtype, N, nM, nT)) return e;
     if (every < 1 || nC != 1 || N > 65535 || (Mck && (ck_every < 8 || ck_every % 8 != 0))) return MRPHY_EINVAL;
     if (N * nM * nT == 0) return 0;
-    if (!Mi || !sig || !rf || !gr || !loc || !g || !work || (df && !gamma)) return MRPHY_EINVAL;
-    if ((E1 == nullptr) != (E2 == nullptr) || (E1 == nullptr) != (E1m1 == nullptr))
-        return MRPHY_EINVAL;
+    const PulseOps in = MRPHY_PULSE_OPS;
+    if (!Mi || !sig || !work) return MRPHY_EINVAL;
+    if (int e = check_ops(in, true, false)) return e;
     if (work_bytes < mrphy_signal_rfgr_fwd_workspace(dtype, N, nM, nT, every)) return MRPHY_ENOSPC;
-    const Bc bdf = {df, df_sn, df_sm}, bgam = {gamma, gamma_sn, gamma_sm};
-    const Bc bg = {g, g_sn, g_sm}, be1 = {E1, E1_sn, E1_sm}, be2 = {E2, E2_sn, E2_sm};
     hipStream_t st = (hipStream_t)stream;
-    MRPHY_DISPATCH(dtype, (run_signal_fwd<T, CT>(Mi, rf, rf_sn, gr, gr_sn, loc, bdf, bgam, b1, bg, be1, be2, E1m1, rx,
-                                                 Mo, Mck, ck_every, sig, every, work, N, nM, nT, st)));
+    MRPHY_DISPATCH(dtype, (run_signal_fwd<T, CT>(Mi, in, rx, Mo, Mck, ck_every, sig, every, work, N, nM, nT, st)));
 }
 
-int mrphy_signal_rfgr_bwd(int dtype, const void* Mck, const void* rf, int64_t rf_sn,
-                          const void* gr, int64_t gr_sn, const void* loc, const void* df,
-                          int64_t df_sn, int64_t df_sm, const void* gamma, int64_t gamma_sn,
-                          int64_t gamma_sm, const void* b1, const void* g, int64_t g_sn,
-                          int64_t g_sm, const void* E1, int64_t E1_sn, int64_t E1_sm,
-                          const void* E2, int64_t E2_sn, int64_t E2_sm, const void* E1m1,
-                          const void* rx, const void* grad_Mo, const void* grad_sig, int64_t every,
-                          void* grad_Mi, void* grad_rf, void* grad_gr, void* work, size_t work_bytes,
-                          int64_t N, int64_t nM, int64_t nT, void* stream)
+int mrphy_signal_rfgr_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PARAMS, const void* rx, const void* grad_Mo,
+                          const void* grad_sig, int64_t every, void* grad_Mi, void* grad_rf, void* grad_gr, void* work,
+                          size_t work_bytes, int64_t N, int64_t nM, int64_t nT, void* stream)
 {
     if (int e = check_common(dtype, N, nM, nT)) return e;
     // whole checkpoint segments only; at least one of the two cotangents
     if (nT % SEG != 0 || every < 1 || N > 65535 || (!grad_Mo && !grad_sig)) return MRPHY_EINVAL;
     if (N * nM * nT == 0) return 0;
-    if (!Mck || !rf || !gr || !loc || !g || !work || (df && !gamma)) return MRPHY_EINVAL;
-    if ((E1 == nullptr) != (E2 == nullptr) || (E1 == nullptr) != (E1m1 == nullptr))
-        return MRPHY_EINVAL;
+    const PulseOps in = MRPHY_PULSE_OPS;
+    if (!Mck || !work) return MRPHY_EINVAL;
+    if (int e = check_ops(in, true, false)) return e;
     if (work_bytes < mrphy_blochsim_rfgr_bwd_workspace(dtype, N, nM, nT)) return MRPHY_ENOSPC;
-    const Bc bdf = {df, df_sn, df_sm}, bgam = {gamma, gamma_sn, gamma_sm};
-    const Bc bg = {g, g_sn, g_sm}, be1 = {E1, E1_sn, E1_sm}, be2 = {E2, E2_sn, E2_sm};
     hipStream_t st = (hipStream_t)stream;
     // without grad_sig this is K2b on grad_Mo
-    MRPHY_DISPATCH(dtype, (run_rfgr_bwd<T, CT>(Mck, rf, rf_sn, gr, gr_sn, loc, bdf, bgam, b1, bg, be1, be2, E1m1,
-                                               grad_Mo, nullptr, every, rx, grad_sig, grad_Mi, grad_rf, grad_gr, work,
-                                               N, nM, nT, st)));
+    MRPHY_DISPATCH(dtype, (run_rfgr_bwd<T, CT>(Mck, in, grad_Mo, nullptr, every, rx, grad_sig, grad_Mi, grad_rf, grad_gr,
+                                               work, N, nM, nT, st)));
 }
 
 int mrphy_beff2ab(int dtype, const void* Beff,

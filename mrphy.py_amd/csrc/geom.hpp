@@ -25,6 +25,26 @@ struct Bc {
     int64_t sn, sm;
 };
 
+// The operands every member of the fused family (K2, K2b, K2s and their trajectory / multi-coil builds) takes: the
+// pulse on the spins plus the step constants, in the order of include/mrphy_hip.h.  abi.hip packs an entry point's
+// scalars into PulseOps = PulseOpsT<void> once; the launchers take it by value and the kernel argument structs embed
+// PulseOpsT<T> -- the same bytes with the arrays of the data type typed -- at the place of these twelve fields.
+template <typename T>
+struct PulseOpsT {
+    const T* rf;   int64_t rf_sn;     // (N, 2, nT, nC), batch stride
+    const T* gr;   int64_t gr_sn;     // (N, 3, nT), batch stride
+    const T* loc;                     // (N, nM, 3)
+    Bc df, gam;                       // null df: no off-resonance
+    const T* b1;                      // (N, nM, 2, nC) or null
+    Bc g, E1, E2;
+    const void* E1m1;                 // E1, E2, E1m1: all or none (no relaxation)
+};
+using PulseOps = PulseOpsT<void>;
+static_assert(sizeof(PulseOps) == 176 && sizeof(PulseOpsT<float>) == 176 && sizeof(PulseOpsT<double>) == 176,
+              "PulseOps: 7 pointers and strides of 8 bytes, 5 Bc of 24");
+template <typename T>
+inline PulseOpsT<T> typed(const PulseOps& o) { return __builtin_bit_cast(PulseOpsT<T>, o); }
+
 inline int64_t hist_tiles(int64_t N, int64_t nM) { return (N * nM + WAVE - 1) / WAVE; }
 inline int64_t hist_elems(int64_t N, int64_t nM, int64_t nT)
 {

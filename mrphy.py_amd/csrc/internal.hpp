@@ -10,6 +10,7 @@
 #pragma GCC visibility push(hidden)
 namespace mrphy_i {
 using mrphy::Bc;
+using mrphy::PulseOps;
 using mrphy::HistParts;
 
 template <typename T, typename CT>
@@ -29,41 +30,34 @@ template <typename T>
 int run_rfgr2beff_bwd(const void* gB, const void* loc, const void* b1, void* grf, void* ggr,
                       void* work, int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st);
 
+// The fused family.  Its operands -- the pulse on the spins and the step constants -- travel as ONE struct, PulseOps
+// (geom.hpp): abi.hip packs and checks it, every launcher below takes it by value and hands it on to its kernel's
+// argument struct in one assignment.  What differs between the members follows it.
 // K2 / K2b and their trajectory builds K2t / K2bt (the same kernels, trailing mode parameter): a null Mt / gMt runs
 // the plain kernel, which writes Mo / reads gMo; otherwise Mt / gMt hold the records taken every `every` steps
 template <typename T, typename CT>
-int run_rfgr_fwd(const void* Mi, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
-                 const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2,
-                 const void* E1m1, void* Mo, void* Mck, int64_t ck_every, void* Mt, int64_t every,
+int run_rfgr_fwd(const void* Mi, PulseOps in, void* Mo, void* Mck, int64_t ck_every, void* Mt, int64_t every,
                  int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st);
 
 // the one-coil float builds of K2 live in a unit of their own (tu_fused_fwd1.hip: compiled with the max-ILP
 // scheduling strategy, which the multi-coil and fp64 builds pay for in registers); called by run_rfgr_fwd
 template <typename T, typename CT>
-int run_rfgr_fwd1(const void* Mi, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
-                  const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2,
-                  const void* E1m1, void* Mo, void* Mck, int64_t ck_every, void* Mt, int64_t every,
+int run_rfgr_fwd1(const void* Mi, PulseOps in, void* Mo, void* Mck, int64_t ck_every, void* Mt, int64_t every,
                   int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st);
 
 template <typename T, typename CT>
-int run_rfgr_bwd(const void* Mck, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
-                 const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2,
-                 const void* E1m1, const void* gMo, const void* gMt, int64_t every, const void* rx,
+int run_rfgr_bwd(const void* Mck, PulseOps in, const void* gMo, const void* gMt, int64_t every, const void* rx,
                  const void* gsig, void* gMi, void* grf, void* ggr, void* work, int64_t N, int64_t nM, int64_t nT,
                  hipStream_t st);
 
 // K2s: the received signal of the fused simulation (tu_signal.hip; one transmit coil).  Its adjoint is run_rfgr_bwd
 // with a non-null gsig (the cotangent of the samples) and the receive map rx; gMo may then be null
 template <typename T, typename CT>
-int run_signal_fwd(const void* Mi, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
-                   const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2,
-                   const void* E1m1, const void* rx, void* Mo, void* Mck, int64_t ck_every, void* sig,
+int run_signal_fwd(const void* Mi, PulseOps in, const void* rx, void* Mo, void* Mck, int64_t ck_every, void* sig,
                    int64_t every, void* work, int64_t N, int64_t nM, int64_t nT, hipStream_t st);
 
 template <typename T, typename CT>
-int run_rfgr_mc_bwd(const void* Mck, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
-                    const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2,
-                    const void* E1m1, const void* gMo, const void* gMt, int64_t every, void* gMi, void* grf,
+int run_rfgr_mc_bwd(const void* Mck, PulseOps in, const void* gMo, const void* gMt, int64_t every, void* gMi, void* grf,
                     void* ggr, void* work, int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st);
 
 template <typename T, typename CT>

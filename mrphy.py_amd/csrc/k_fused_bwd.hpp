@@ -14,9 +14,9 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdArgsT<T, INJ> a
     const int64_t ntiles = (a.nM + WAVE - 1) / WAVE;
     // read-only, wave-uniform pulse through the constant address space: scalar loads (see K2)
     using CP = const T __attribute__((address_space(4)))*;
-    CP rfr = (CP)(a.rf + n * a.rf_sn);
+    CP rfr = (CP)(a.in.rf + n * a.in.rf_sn);
     CP rfi = rfr + nT;
-    CP gx = (CP)(a.gr + n * a.gr_sn);
+    CP gx = (CP)(a.in.gr + n * a.in.gr_sn);
     CP gy = gx + nT;
     CP gz = gy + nT;
     T* wsrow = a.work + ((w * a.N + n) * 5) * nT;
@@ -27,12 +27,12 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdArgsT<T, INJ> a
         const bool valid = s_ < a.nM;
         const int64_t s = valid ? s_ : a.nM - 1;
         const int64_t row = n * a.nM + s;
-        const SpinConst<T, CT> k = load_consts<T, CT>(a.g, a.E1, a.E2, a.E1m1, n, s);
-        const T lx = a.loc[row * 3], ly = a.loc[row * 3 + 1], lz = a.loc[row * 3 + 2];
+        const SpinConst<T, CT> k = load_consts<T, CT>(a.in.g, a.in.E1, a.in.E2, a.in.E1m1, n, s);
+        const T lx = a.in.loc[row * 3], ly = a.in.loc[row * 3 + 1], lz = a.in.loc[row * 3 + 2];
         T delta = T(0);
-        if (a.df.p) delta = bc_load<T>(a.df, n, s) / bc_load<T>(a.gam, n, s);
+        if (a.in.df.p) delta = bc_load<T>(a.in.df, n, s) / bc_load<T>(a.in.gam, n, s);
         T br = T(1), bi = T(0);
-        if (HB1 && a.b1) { br = a.b1[row * 2]; bi = a.b1[row * 2 + 1]; }
+        if (HB1 && a.in.b1) { br = a.in.b1[row * 2]; bi = a.in.b1[row * 2 + 1]; }
         const T vmask = valid ? T(1) : T(0);
         // lanes past nM (they hold a copy of the last valid spin) start from a zero cotangent: the adjoint state and every
         // dL/dB they form stay exact zeros (all of it is linear in the state), so they add nothing to the row sums --

@@ -39,13 +39,7 @@ __device__ __forceinline__ int red_idx(int row, int l)
 template <typename T>
 struct FusedBwdArgs {
     const T* Mck;                    // (nT/SEG, N*nM, 3)
-    const T* rf;  int64_t rf_sn;
-    const T* gr;  int64_t gr_sn;
-    const T* loc;
-    Bc df, gam;
-    const T* b1;                     // (N, nM, 2) or null
-    Bc g, E1, E2;
-    const void* E1m1;
+    PulseOpsT<T> in;                 // b1: (N, nM, 2) or null; the multi-coil kernel's (N, nM, 2, nC)
     const T* gMo;
     T* gMi;                          // may be null
     T* work;                         // (P, N, 5, nT)
@@ -81,19 +75,27 @@ struct FusedBwdSigArgs : FusedBwdTrajArgs<T> {
 template <typename T, int INJ>
 using FusedBwdArgsT = std::conditional_t<INJ == 0, FusedBwdArgs<T>,
                                          std::conditional_t<INJ == 3, FusedBwdSigArgs<T>, FusedBwdTrajArgs<T>>>;
+// the kernarg layout is part of the kernels' machine code: `in` sits where its twelve fields were written out
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"
+template <typename T>
+constexpr bool fused_bwd_args_layout =
+    offsetof(FusedBwdArgs<T>, in) == 8 && offsetof(FusedBwdArgs<T>, gMo) == 184 && offsetof(FusedBwdArgs<T>, P) == 232 &&
+    sizeof(FusedBwdArgs<T>) == 240 && offsetof(FusedBwdTrajArgs<T>, every) == 240 &&
+    offsetof(FusedBwdTrajArgs<T>, nRec) == 248 && sizeof(FusedBwdTrajArgs<T>) == 256 &&
+    offsetof(FusedBwdSigArgs<T>, rx) == 256 && offsetof(FusedBwdSigArgs<T>, gsig) == 264 &&
+    sizeof(FusedBwdSigArgs<T>) == 272;
+#pragma clang diagnostic pop
+static_assert(fused_bwd_args_layout<float> && fused_bwd_args_layout<double>, "K2b's kernel arguments moved");
 
 // the arguments of K2b / K2bt (host side, shared by tu_fused_bwd.hip and tu_fused_mc_bwd.hip): a null gMt selects the
 // plain kernel (INJ == 0), which takes the FusedBwdArgs part; otherwise gMt is the cotangent the kernel reads
 template <typename T>
-FusedBwdTrajArgs<T> fused_bwd_args(const void* Mck, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
-                                   const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2,
-                                   const void* E1m1, const void* gMo, const void* gMt, int64_t every, void* gMi,
-                                   void* work, int64_t N, int64_t nM, int64_t nT, int64_t P)
+FusedBwdTrajArgs<T> fused_bwd_args(const void* Mck, const PulseOps& in, const void* gMo, const void* gMt,
+                                   int64_t every, void* gMi, void* work, int64_t N, int64_t nM, int64_t nT, int64_t P)
 {
     FusedBwdTrajArgs<T> a;
-    a.Mck = (const T*)Mck; a.rf = (const T*)rf; a.rf_sn = rf_sn; a.gr = (const T*)gr;
-    a.gr_sn = gr_sn; a.loc = (const T*)loc; a.df = df; a.gam = gam; a.b1 = (const T*)b1;
-    a.g = g; a.E1 = E1; a.E2 = E2; a.E1m1 = E1m1; a.gMo = (const T*)(gMt ? gMt : gMo); a.gMi = (T*)gMi;
+    a.Mck = (const T*)Mck; a.in = typed<T>(in); a.gMo = (const T*)(gMt ? gMt : gMo); a.gMi = (T*)gMi;
     a.work = (T*)work; a.N = N; a.nM = nM; a.nT = nT; a.P = P;
     a.every = every; a.nRec = gMt ? (nT + every - 1) / every : 0;
     return a;

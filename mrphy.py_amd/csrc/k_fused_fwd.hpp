@@ -12,13 +12,7 @@
 template <typename T>
 struct FusedArgs {
     const T* Mi;
-    const T* rf;  int64_t rf_sn;
-    const T* gr;  int64_t gr_sn;
-    const T* loc;
-    Bc df, gam;
-    const T* b1;
-    Bc g, E1, E2;
-    const void* E1m1;
+    PulseOpsT<T> in;
     T* Mo;
     T* Mck;  int64_t ck_every;
     int64_t N, nM, nT, nC;
@@ -36,6 +30,16 @@ struct FusedTrajArgs : FusedArgs<T> {
 };
 template <typename T, int TR>
 using FusedArgsT = std::conditional_t<TR == 0, FusedArgs<T>, FusedTrajArgs<T>>;
+// the kernarg layout is part of the kernels' machine code: `in` sits where its twelve fields were written out
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"
+template <typename T>
+constexpr bool fused_args_layout =
+    offsetof(FusedArgs<T>, in) == 8 && offsetof(FusedArgs<T>, Mo) == 184 && offsetof(FusedArgs<T>, nC) == 232 &&
+    sizeof(FusedArgs<T>) == 240 && offsetof(FusedTrajArgs<T>, Mt) == 240 && offsetof(FusedTrajArgs<T>, every) == 248 &&
+    sizeof(FusedTrajArgs<T>) == 256;
+#pragma clang diagnostic pop
+static_assert(fused_args_layout<float> && fused_args_layout<double>, "K2's kernel arguments moved");
 
 // CK: write checkpoints (every ck_every steps, a multiple of the 8-step chunk).  Kept out of the
 // plain instantiation so that its step loop contains no store: the pulse loads are then provably
@@ -91,14 +95,14 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_fwd(FusedArgsT<T, TR> a)
     const bool valid = s_ < a.nM;
     const int64_t s = valid ? s_ : a.nM - 1;
     const int64_t row = n * a.nM + s;
-    const SpinConst<T, CT> k = load_consts<T, CT>(a.g, a.E1, a.E2, a.E1m1, n, s);
+    const SpinConst<T, CT> k = load_consts<T, CT>(a.in.g, a.in.E1, a.in.E2, a.in.E1m1, n, s);
 
     T mx = a.Mi[row * 3], my = a.Mi[row * 3 + 1], mz = a.Mi[row * 3 + 2];
-    const T lx = a.loc[row * 3], ly = a.loc[row * 3 + 1], lz = a.loc[row * 3 + 2];
+    const T lx = a.in.loc[row * 3], ly = a.in.loc[row * 3 + 1], lz = a.in.loc[row * 3 + 2];
     T delta = T(0);
-    if (a.df.p) delta = bc_load<T>(a.df, n, s) / bc_load<T>(a.gam, n, s);
+    if (a.in.df.p) delta = bc_load<T>(a.in.df, n, s) / bc_load<T>(a.in.gam, n, s);
     T br = T(1), bi = T(0);
-    if (NC1 && HB1 && a.b1) { br = a.b1[row * 2]; bi = a.b1[row * 2 + 1]; }
+    if (NC1 && HB1 && a.in.b1) { br = a.in.b1[row * 2]; bi = a.in.b1[row * 2 + 1]; }
 
     const int64_t nT = a.nT, nC = a.nC;
     // The pulse is read-only for the whole launch and its addresses are wave-uniform: pointers into the
@@ -107,12 +111,12 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_fwd(FusedArgsT<T, TR> a)
     // alone and fetched the samples with vector loads + v_readfirstlane (K2 with checkpoints: 0.82 ms
     // where the plain build's rate gives 0.60 at 64^3 x 2048).
     using CP = const T __attribute__((address_space(4)))*;
-    CP rfr = (CP)(a.rf + n * a.rf_sn);                       // [nT][nC]
+    CP rfr = (CP)(a.in.rf + n * a.in.rf_sn);                 // [nT][nC]
     CP rfi = rfr + nT * nC;
-    CP gx = (CP)(a.gr + n * a.gr_sn);
+    CP gx = (CP)(a.in.gr + n * a.in.gr_sn);
     CP gy = gx + nT;
     CP gz = gy + nT;
-    const T* b1 = a.b1 ? a.b1 + row * 2 * nC : nullptr;
+    const T* b1 = a.in.b1 ? a.in.b1 + row * 2 * nC : nullptr;
     const int64_t rows = a.N * a.nM;
     T b1r[MC], b1i[MC];
     if (NCR) {
@@ -210,15 +214,11 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_fwd(FusedArgsT<T, TR> a)
 // kernel (TR == 0), which takes the FusedArgs part of the arguments; otherwise `every` picks TR.
 // ---------------------------------------------------------------------------------------------
 template <typename T>
-FusedTrajArgs<T> fused_args(const void* Mi, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
-                            const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2,
-                            const void* E1m1, void* Mo, void* Mck, int64_t ck_every, void* Mt, int64_t every,
-                            int64_t N, int64_t nM, int64_t nT, int64_t nC)
+FusedTrajArgs<T> fused_args(const void* Mi, const PulseOps& in, void* Mo, void* Mck, int64_t ck_every, void* Mt,
+                            int64_t every, int64_t N, int64_t nM, int64_t nT, int64_t nC)
 {
     FusedTrajArgs<T> a;
-    a.Mi = (const T*)Mi; a.rf = (const T*)rf; a.rf_sn = rf_sn; a.gr = (const T*)gr;
-    a.gr_sn = gr_sn; a.loc = (const T*)loc; a.df = df; a.gam = gam; a.b1 = (const T*)b1;
-    a.g = g; a.E1 = E1; a.E2 = E2; a.E1m1 = E1m1; a.Mo = (T*)Mo; a.Mck = (T*)Mck;
+    a.Mi = (const T*)Mi; a.in = typed<T>(in); a.Mo = (T*)Mo; a.Mck = (T*)Mck;
     a.ck_every = ck_every > 0 ? ck_every : 1;
     a.N = N; a.nM = nM; a.nT = nT; a.nC = nC;
     a.Mt = (T*)Mt; a.every = every;
@@ -239,7 +239,7 @@ void launch_k2(const FusedTrajArgs<T>& a, hipStream_t st)
         else if (a.every == 1) MRPHY_K2(CK_, RX_, 1);                                                       \
         else MRPHY_K2(CK_, RX_, 2);                                                                         \
     } while (0)
-    const bool ck = (a.Mck != nullptr), rx = (a.E1.p != nullptr);
+    const bool ck = (a.Mck != nullptr), rx = (a.in.E1.p != nullptr);
     if (ck) { if (rx) MRPHY_K2T(true, true); else MRPHY_K2T(true, false); }
     else    { if (rx) MRPHY_K2T(false, true); else MRPHY_K2T(false, false); }
 #undef MRPHY_K2T

@@ -42,10 +42,10 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd_mc(FusedBwdArgsT<T, INJ
     const int64_t nT = a.nT, rows = a.N * a.nM;
     const int64_t ntiles = (a.nM + WAVE - 1) / WAVE;
     const int nQ = 3 + 2 * nC;
-    const T* __restrict__ rfr = a.rf + n * a.rf_sn;            // [nT][nC]
+    const T* __restrict__ rfr = a.in.rf + n * a.in.rf_sn;      // [nT][nC]
     const T* __restrict__ rfi = rfr + nT * nC;
     using CP = const T __attribute__((address_space(4)))*;     // wave-uniform gradient samples: scalar loads
-    CP gx = (CP)(a.gr + n * a.gr_sn);
+    CP gx = (CP)(a.in.gr + n * a.in.gr_sn);
     CP gy = gx + nT;
     CP gz = gy + nT;
     T* wsrow = a.work + ((w * a.N + n) * nQ) * nT;
@@ -56,15 +56,15 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd_mc(FusedBwdArgsT<T, INJ
         const bool valid = s_ < a.nM;
         const int64_t s = valid ? s_ : a.nM - 1;
         const int64_t row = n * a.nM + s;
-        const SpinConst<T, CT> k = load_consts<T, CT>(a.g, a.E1, a.E2, a.E1m1, n, s);
-        const T lx = a.loc[row * 3], ly = a.loc[row * 3 + 1], lz = a.loc[row * 3 + 2];
+        const SpinConst<T, CT> k = load_consts<T, CT>(a.in.g, a.in.E1, a.in.E2, a.in.E1m1, n, s);
+        const T lx = a.in.loc[row * 3], ly = a.in.loc[row * 3 + 1], lz = a.in.loc[row * 3 + 2];
         T delta = T(0);
-        if (a.df.p) delta = bc_load<T>(a.df, n, s) / bc_load<T>(a.gam, n, s);
+        if (a.in.df.p) delta = bc_load<T>(a.in.df, n, s) / bc_load<T>(a.in.gam, n, s);
         T br[MC], bi[MC];
 #pragma unroll
         for (int c = 0; c < MC; ++c) {
-            br[c] = (c < nC) ? a.b1[row * 2 * nC + c] : T(0);
-            bi[c] = (c < nC) ? a.b1[row * 2 * nC + nC + c] : T(0);
+            br[c] = (c < nC) ? a.in.b1[row * 2 * nC + c] : T(0);
+            bi[c] = (c < nC) ? a.in.b1[row * 2 * nC + nC + c] : T(0);
         }
         const T vmask = valid ? T(1) : T(0);
         __syncthreads();                                   // previous tile's coefficients released

@@ -19,13 +19,7 @@
 template <typename T>
 struct SignalArgs {
     const T* Mi;
-    const T* rf;  int64_t rf_sn;
-    const T* gr;  int64_t gr_sn;
-    const T* loc;
-    Bc df, gam;
-    const T* b1;                     // (N, nM, 2) or null
-    Bc g, E1, E2;
-    const void* E1m1;
+    PulseOpsT<T> in;                 // b1: (N, nM, 2) or null
     const T* rx;                     // (N, nM, 2) or null = (1, 0)
     T* Mo;                           // may be null
     T* Mck;  int64_t ck_every;       // may be null
@@ -33,6 +27,11 @@ struct SignalArgs {
     int64_t every, nRec;
     int64_t N, nM, nT, P;
 };
+// the kernarg layout is part of the kernel's machine code: `in` sits where its twelve fields were written out
+static_assert(offsetof(SignalArgs<float>, in) == 8 && offsetof(SignalArgs<float>, rx) == 184 &&
+              offsetof(SignalArgs<float>, P) == 264 && sizeof(SignalArgs<float>) == 272 &&
+              offsetof(SignalArgs<double>, rx) == 184 && offsetof(SignalArgs<double>, P) == 264 &&
+              sizeof(SignalArgs<double>) == 272, "K2s's kernel arguments moved");
 
 // CK, RELAX, HB1: as K2.  EV1: every == 1 -- a record after every step, its slot known at compile time inside the
 // unrolled step batch; otherwise the step of the next record is carried (wave-uniform) and compared, as in K2t.
@@ -48,9 +47,9 @@ __global__ __launch_bounds__(WAVE) void k_signal_fwd(SignalArgs<T> a)
     const int64_t ntiles = (a.nM + WAVE - 1) / WAVE;
     // read-only, wave-uniform pulse through the constant address space: scalar loads (see K2)
     using CP = const T __attribute__((address_space(4)))*;
-    CP rfr = (CP)(a.rf + n * a.rf_sn);
+    CP rfr = (CP)(a.in.rf + n * a.in.rf_sn);
     CP rfi = rfr + nT;
-    CP gx = (CP)(a.gr + n * a.gr_sn);
+    CP gx = (CP)(a.in.gr + n * a.in.gr_sn);
     CP gy = gx + nT;
     CP gz = gy + nT;
     // row sums: lane (r, h) forms chains 2h and 2h + 1 of row r = q SEG + slot; the two halves meet as
@@ -67,13 +66,13 @@ __global__ __launch_bounds__(WAVE) void k_signal_fwd(SignalArgs<T> a)
         const bool valid = s_ < a.nM;
         const int64_t s = valid ? s_ : a.nM - 1;
         const int64_t row = n * a.nM + s;
-        const SpinConst<T, CT> k = load_consts<T, CT>(a.g, a.E1, a.E2, a.E1m1, n, s);
+        const SpinConst<T, CT> k = load_consts<T, CT>(a.in.g, a.in.E1, a.in.E2, a.in.E1m1, n, s);
         T mx = a.Mi[row * 3], my = a.Mi[row * 3 + 1], mz = a.Mi[row * 3 + 2];
-        const T lx = a.loc[row * 3], ly = a.loc[row * 3 + 1], lz = a.loc[row * 3 + 2];
+        const T lx = a.in.loc[row * 3], ly = a.in.loc[row * 3 + 1], lz = a.in.loc[row * 3 + 2];
         T delta = T(0);
-        if (a.df.p) delta = bc_load<T>(a.df, n, s) / bc_load<T>(a.gam, n, s);
+        if (a.in.df.p) delta = bc_load<T>(a.in.df, n, s) / bc_load<T>(a.in.gam, n, s);
         T br = T(1), bi = T(0);
-        if (HB1 && a.b1) { br = a.b1[row * 2]; bi = a.b1[row * 2 + 1]; }
+        if (HB1 && a.in.b1) { br = a.in.b1[row * 2]; bi = a.in.b1[row * 2 + 1]; }
         // lanes past nM (they hold a copy of the last valid spin) receive with weight zero: their two products are
         // exact zeros -- masked here, once per tile
         T rxr = valid ? T(1) : T(0), rxi = T(0);

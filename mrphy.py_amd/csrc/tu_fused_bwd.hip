@@ -9,9 +9,7 @@ namespace {
 namespace mrphy_i {
 
 template <typename T, typename CT>
-int run_rfgr_bwd(const void* Mck, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
-                 const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2,
-                 const void* E1m1, const void* gMo, const void* gMt, int64_t every, const void* rx,
+int run_rfgr_bwd(const void* Mck, PulseOps in, const void* gMo, const void* gMt, int64_t every, const void* rx,
                  const void* gsig, void* gMi, void* grf, void* ggr, void* work, int64_t N, int64_t nM, int64_t nT,
                  hipStream_t st)
 {
@@ -20,8 +18,8 @@ int run_rfgr_bwd(const void* Mck, const void* rf, int64_t rf_sn, const void* gr,
     // gsig (the cotangent of the signal's samples, with the receive map rx) selects the signal build, which may have no
     // gMo; its records are counted as the trajectory's
     FusedBwdSigArgs<T> a;
-    static_cast<FusedBwdTrajArgs<T>&>(a) = fused_bwd_args<T>(Mck, rf, rf_sn, gr, gr_sn, loc, df, gam, b1, g, E1, E2, E1m1,
-                                                             gMo, gMt, every, gMi, work, N, nM, nT, k2b_waves(nM));
+    static_cast<FusedBwdTrajArgs<T>&>(a) = fused_bwd_args<T>(Mck, in, gMo, gMt, every, gMi, work, N, nM, nT,
+                                                             k2b_waves(nM));
     a.rx = (const T*)rx; a.gsig = (const T*)gsig;
     if (gsig) a.nRec = sig_records(nT, every);
     const dim3 grid((unsigned)a.P, (unsigned)N);
@@ -35,8 +33,8 @@ int run_rfgr_bwd(const void* Mck, const void* rf, int64_t rf_sn, const void* gr,
         else if (every < SEG) MRPHY_K2B(RX_, HB_, 1);                                           \
         else MRPHY_K2B(RX_, HB_, 2);                                                            \
     } while (0)
-    if (b1) { if (E1.p) MRPHY_K2BT(true, true);  else MRPHY_K2BT(false, true); }
-    else    { if (E1.p) MRPHY_K2BT(true, false); else MRPHY_K2BT(false, false); }   // no b1 map: Bxy = rf
+    if (in.b1) { if (in.E1.p) MRPHY_K2BT(true, true);  else MRPHY_K2BT(false, true); }
+    else       { if (in.E1.p) MRPHY_K2BT(true, false); else MRPHY_K2BT(false, false); }   // no b1 map: Bxy = rf
 #undef MRPHY_K2BT
 #undef MRPHY_K2B
     int e = launch_status();
@@ -52,6 +50,6 @@ int run_rfgr_bwd(const void* Mck, const void* rf, int64_t rf_sn, const void* gr,
 
 }  // namespace mrphy_i
 
-#define MRPHY_INST(T_, CT_) template int mrphy_i::run_rfgr_bwd<T_, CT_>(const void* Mck, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn, const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2, const void* E1m1, const void* gMo, const void* gMt, int64_t every, const void* rx, const void* gsig, void* gMi, void* grf, void* ggr, void* work, int64_t N, int64_t nM, int64_t nT, hipStream_t st);
+#define MRPHY_INST(T_, CT_) template int mrphy_i::run_rfgr_bwd<T_, CT_>(const void* Mck, PulseOps in, const void* gMo, const void* gMt, int64_t every, const void* rx, const void* gsig, void* gMi, void* grf, void* ggr, void* work, int64_t N, int64_t nM, int64_t nT, hipStream_t st);
 MRPHY_FOR_DTYPES(MRPHY_INST)
 #undef MRPHY_INST

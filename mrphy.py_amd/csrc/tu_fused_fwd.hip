@@ -8,21 +8,17 @@ namespace {
 namespace mrphy_i {
 
 template <typename T, typename CT>
-int run_rfgr_fwd(const void* Mi, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
-                 const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2,
-                 const void* E1m1, void* Mo, void* Mck, int64_t ck_every, void* Mt, int64_t every,
+int run_rfgr_fwd(const void* Mi, PulseOps in, void* Mo, void* Mck, int64_t ck_every, void* Mt, int64_t every,
                  int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st)
 {
     // the plain kernel runs at nT == 0 too (it writes Mo = Mi); a trajectory then has no record
     if (N * nM * (Mt ? nT : 1) == 0) return 0;
     if (N > 65535) return MRPHY_EINVAL;
     if constexpr (sizeof(T) == 4) {
-        if (nC == 1)
-            return run_rfgr_fwd1<T, CT>(Mi, rf, rf_sn, gr, gr_sn, loc, df, gam, b1, g, E1, E2, E1m1, Mo, Mck, ck_every,
-                                        Mt, every, N, nM, nT, nC, st);
+        if (nC == 1) return run_rfgr_fwd1<T, CT>(Mi, in, Mo, Mck, ck_every, Mt, every, N, nM, nT, nC, st);
     }
-    const FusedTrajArgs<T> a = fused_args<T>(Mi, rf, rf_sn, gr, gr_sn, loc, df, gam, b1, g, E1, E2, E1m1, Mo, Mck,
-                                             ck_every, Mt, every, N, nM, nT, nC);
+    const FusedTrajArgs<T> a = fused_args<T>(Mi, in, Mo, Mck, ck_every, Mt, every, N, nM, nT, nC);
+    const void* b1 = in.b1;
 #define MRPHY_K2C(NCM_) launch_k2<T, CT, NCM_, true>(a, st)
     // the smallest register/LDS coil capacity that holds nC (each build sizes its b1 registers and
     // its LDS rf buffer for exactly that capacity: never launch one with more coils than it holds)
@@ -46,6 +42,6 @@ int run_rfgr_fwd(const void* Mi, const void* rf, int64_t rf_sn, const void* gr, 
 
 }  // namespace mrphy_i
 
-#define MRPHY_INST(T_, CT_) template int mrphy_i::run_rfgr_fwd<T_, CT_>(const void* Mi, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn, const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2, const void* E1m1, void* Mo, void* Mck, int64_t ck_every, void* Mt, int64_t every, int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st);
+#define MRPHY_INST(T_, CT_) template int mrphy_i::run_rfgr_fwd<T_, CT_>(const void* Mi, PulseOps in, void* Mo, void* Mck, int64_t ck_every, void* Mt, int64_t every, int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st);
 MRPHY_FOR_DTYPES(MRPHY_INST)
 #undef MRPHY_INST

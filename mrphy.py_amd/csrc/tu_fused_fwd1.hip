@@ -12,17 +12,14 @@ namespace {
 namespace mrphy_i {
 
 template <typename T, typename CT>
-int run_rfgr_fwd1(const void* Mi, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
-                  const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2,
-                  const void* E1m1, void* Mo, void* Mck, int64_t ck_every, void* Mt, int64_t every,
+int run_rfgr_fwd1(const void* Mi, PulseOps in, void* Mo, void* Mck, int64_t ck_every, void* Mt, int64_t every,
                   int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st)
 {
     if constexpr (sizeof(T) != 4) {
         return MRPHY_EINVAL;                             // fp64 stays in tu_fused_fwd.hip
     } else {
-        const FusedTrajArgs<T> a = fused_args<T>(Mi, rf, rf_sn, gr, gr_sn, loc, df, gam, b1, g, E1, E2, E1m1, Mo, Mck,
-                                                 ck_every, Mt, every, N, nM, nT, nC);
-        if (b1) launch_k2<T, CT, 1, true>(a, st);
+        const FusedTrajArgs<T> a = fused_args<T>(Mi, in, Mo, Mck, ck_every, Mt, every, N, nM, nT, nC);
+        if (in.b1) launch_k2<T, CT, 1, true>(a, st);
         else    launch_k2<T, CT, 1, false>(a, st);       // no b1 map: Bxy = rf, no complex product
         return launch_status();
     }
@@ -30,6 +27,6 @@ int run_rfgr_fwd1(const void* Mi, const void* rf, int64_t rf_sn, const void* gr,
 
 }  // namespace mrphy_i
 
-#define MRPHY_INST(T_, CT_) template int mrphy_i::run_rfgr_fwd1<T_, CT_>(const void* Mi, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn, const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2, const void* E1m1, void* Mo, void* Mck, int64_t ck_every, void* Mt, int64_t every, int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st);
+#define MRPHY_INST(T_, CT_) template int mrphy_i::run_rfgr_fwd1<T_, CT_>(const void* Mi, PulseOps in, void* Mo, void* Mck, int64_t ck_every, void* Mt, int64_t every, int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st);
 MRPHY_FOR_DTYPES(MRPHY_INST)
 #undef MRPHY_INST

@@ -8,15 +8,12 @@ namespace {
 namespace mrphy_i {
 
 template <typename T, typename CT>
-int run_rfgr_mc_bwd(const void* Mck, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
-                    const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2,
-                    const void* E1m1, const void* gMo, const void* gMt, int64_t every, void* gMi, void* grf,
+int run_rfgr_mc_bwd(const void* Mck, PulseOps in, const void* gMo, const void* gMt, int64_t every, void* gMi, void* grf,
                     void* ggr, void* work, int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st)
 {
     if (N * nM * nT == 0) return 0;
     if (N > 65535) return MRPHY_EINVAL;
-    const FusedBwdTrajArgs<T> a = fused_bwd_args<T>(Mck, rf, rf_sn, gr, gr_sn, loc, df, gam, b1, g, E1, E2, E1m1, gMo,
-                                                    gMt, every, gMi, work, N, nM, nT, k2b_mc_waves(nM));
+    const FusedBwdTrajArgs<T> a = fused_bwd_args<T>(Mck, in, gMo, gMt, every, gMi, work, N, nM, nT, k2b_mc_waves(nM));
     const dim3 grid((unsigned)a.P, (unsigned)N);
 #define MRPHY_K2BMC(RX_, MC_, INJ_)                                                                 \
     hipLaunchKernelGGL((k_bloch_rfgr_bwd_mc<T, CT, RX_, MC_, INJ_>), grid, dim3(WAVE), 0, st, \
@@ -31,7 +28,7 @@ int run_rfgr_mc_bwd(const void* Mck, const void* rf, int64_t rf_sn, const void* 
         else if constexpr (!lds_only) MRPHY_K2BMC(RX_, MC_, 2);                                     \
     } while (0)
     // the smallest coil capacity (2 / 4 / 8) that holds nC: the build's loops run over all of it, on zeros
-#define MRPHY_K2BMCR(MC_) do { if (E1.p) MRPHY_K2BMCT(true, MC_); else MRPHY_K2BMCT(false, MC_); } while (0)
+#define MRPHY_K2BMCR(MC_) do { if (in.E1.p) MRPHY_K2BMCT(true, MC_); else MRPHY_K2BMCT(false, MC_); } while (0)
     if (nC <= 2) MRPHY_K2BMCR(2);
     else if (nC <= 4) MRPHY_K2BMCR(4);
     else MRPHY_K2BMCR(8);
@@ -52,6 +49,6 @@ int run_rfgr_mc_bwd(const void* Mck, const void* rf, int64_t rf_sn, const void* 
 
 }  // namespace mrphy_i
 
-#define MRPHY_INST(T_, CT_) template int mrphy_i::run_rfgr_mc_bwd<T_, CT_>(const void* Mck, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn, const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2, const void* E1m1, const void* gMo, const void* gMt, int64_t every, void* gMi, void* grf, void* ggr, void* work, int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st);
+#define MRPHY_INST(T_, CT_) template int mrphy_i::run_rfgr_mc_bwd<T_, CT_>(const void* Mck, PulseOps in, const void* gMo, const void* gMt, int64_t every, void* gMi, void* grf, void* ggr, void* work, int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st);
 MRPHY_FOR_DTYPES(MRPHY_INST)
 #undef MRPHY_INST

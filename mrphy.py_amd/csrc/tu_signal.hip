@@ -9,17 +9,14 @@ namespace {
 namespace mrphy_i {
 
 template <typename T, typename CT>
-int run_signal_fwd(const void* Mi, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn,
-                   const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2,
-                   const void* E1m1, const void* rx, void* Mo, void* Mck, int64_t ck_every, void* sig,
+int run_signal_fwd(const void* Mi, PulseOps in, const void* rx, void* Mo, void* Mck, int64_t ck_every, void* sig,
                    int64_t every, void* work, int64_t N, int64_t nM, int64_t nT, hipStream_t st)
 {
     if (N * nM * nT == 0) return 0;
     if (N > 65535) return MRPHY_EINVAL;
     SignalArgs<T> a;
-    a.Mi = (const T*)Mi; a.rf = (const T*)rf; a.rf_sn = rf_sn; a.gr = (const T*)gr; a.gr_sn = gr_sn;
-    a.loc = (const T*)loc; a.df = df; a.gam = gam; a.b1 = (const T*)b1; a.g = g; a.E1 = E1; a.E2 = E2;
-    a.E1m1 = E1m1; a.rx = (const T*)rx; a.Mo = (T*)Mo; a.Mck = (T*)Mck; a.ck_every = ck_every > 0 ? ck_every : 1;
+    a.Mi = (const T*)Mi; a.in = typed<T>(in); a.rx = (const T*)rx; a.Mo = (T*)Mo; a.Mck = (T*)Mck;
+    a.ck_every = ck_every > 0 ? ck_every : 1;
     a.work = (T*)work; a.every = every; a.nRec = sig_records(nT, every);
     a.N = N; a.nM = nM; a.nT = nT; a.P = sig_waves(nM);
     const dim3 grid((unsigned)a.P, (unsigned)N);
@@ -31,9 +28,9 @@ int run_signal_fwd(const void* Mi, const void* rf, int64_t rf_sn, const void* gr
     } while (0)
 #define MRPHY_K2S_HB(CK_, RX_)                                                                   \
     do {                                                                                         \
-        if (b1) MRPHY_K2S_EV(CK_, RX_, true); else MRPHY_K2S_EV(CK_, RX_, false);                \
+        if (in.b1) MRPHY_K2S_EV(CK_, RX_, true); else MRPHY_K2S_EV(CK_, RX_, false);             \
     } while (0)
-    const bool ck = (Mck != nullptr), rlx = (E1.p != nullptr);
+    const bool ck = (Mck != nullptr), rlx = (in.E1.p != nullptr);
     if (ck) { if (rlx) MRPHY_K2S_HB(true, true); else MRPHY_K2S_HB(true, false); }
     else    { if (rlx) MRPHY_K2S_HB(false, true); else MRPHY_K2S_HB(false, false); }
 #undef MRPHY_K2S_HB
@@ -48,6 +45,6 @@ int run_signal_fwd(const void* Mi, const void* rf, int64_t rf_sn, const void* gr
 
 }  // namespace mrphy_i
 
-#define MRPHY_INST(T_, CT_) template int mrphy_i::run_signal_fwd<T_, CT_>(const void* Mi, const void* rf, int64_t rf_sn, const void* gr, int64_t gr_sn, const void* loc, Bc df, Bc gam, const void* b1, Bc g, Bc E1, Bc E2, const void* E1m1, const void* rx, void* Mo, void* Mck, int64_t ck_every, void* sig, int64_t every, void* work, int64_t N, int64_t nM, int64_t nT, hipStream_t st);
+#define MRPHY_INST(T_, CT_) template int mrphy_i::run_signal_fwd<T_, CT_>(const void* Mi, PulseOps in, const void* rx, void* Mo, void* Mck, int64_t ck_every, void* sig, int64_t every, void* work, int64_t N, int64_t nM, int64_t nT, hipStream_t st);
 MRPHY_FOR_DTYPES(MRPHY_INST)
 #undef MRPHY_INST

@@ -37,6 +37,46 @@ from ._consts import γH, dt0
 __all__ = ['blochsim_rfgr', 'blochsim_rfgr_traj', 'signal_rfgr']
 
 
+def _forward_prep(lib, p, γ2πdt, E1, E2, E1_1, dtype, device, need):
+    r"""What the two forwards share: the step constants and, if ``need``, the checkpoints the fused adjoint recomputes
+    from.  Returns ``(code, alive, consts, Mck, ckpt)``: the dtype code, the constants' tensors (kept alive with
+    ``consts``, their arguments ``g .. E1m1``) and the arguments ``(Mck, ck_every)``, ``(None, 0)`` without ``need``."""
+    from . import sims
+    code, g, e1, e2, e1m1 = sims._prep_constants(γ2πdt, E1, E2, E1_1, p.N, p.Nd, dtype, device)
+    ck = int(lib.mrphy_blochsim_rfgr_ck_every())
+    # one checkpoint per started segment: nCk = ceil(nT / ck_every) (include/mrphy_hip.h)
+    Mck = torch.empty((-(-p.nT // ck), p.N * p.nM, 3), dtype=dtype, device=device) if need else None
+    nul = _host.NULL_BC
+    consts = (*g.args, *(e1.args if e1 else nul), *(e2.args if e2 else nul),
+              e1m1.t.data_ptr() if e1m1 else None)
+    ckpt = (Mck.data_ptr() if need else None, ck if need else 0)
+    return code, (g, e1, e2, e1m1), consts, Mck, ckpt
+
+
+def _backward_prep(lib, p, code, needs, dtype, device):
+    r"""The gradient-output side the two adjoints share: ``(gMi, g_rf, g_gr)`` -- ``None`` where ``needs`` says so --
+    their pointers, and the workspace of the adjoint for ``p.nC`` coils."""
+    need_Mi, need_rf, need_gr = needs
+    gMi = torch.empty((p.N,) + p.Nd + (3,), dtype=dtype, device=device) if need_Mi else None
+    g_rf = torch.empty((p.N, 2, p.nT, p.nC), dtype=dtype, device=device) if need_rf else None
+    g_gr = torch.empty((p.N, 3, p.nT), dtype=dtype, device=device) if need_gr else None
+    if p.nC == 1:
+        nbytes = int(lib.mrphy_blochsim_rfgr_bwd_workspace(code, p.N, p.nM, p.nT))
+    else:                                       # parallel transmit: per-coil sums in the kernel
+        nbytes = int(lib.mrphy_blochsim_rfgr_mc_bwd_workspace(code, p.N, p.nM, p.nT, p.nC))
+    work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+    grads = (gMi, g_rf, g_gr)
+    return grads, tuple(None if x is None else x.data_ptr() for x in grads), work
+
+
+def _fold_grads(gMi, g_rf, g_gr, p, rf_shape, gr_shape, rf_dtype, gr_dtype):
+    r"""``(grad_Mi, grad_rf, grad_gr)`` in the shapes and dtypes the caller's ``rf`` and ``gr`` had."""
+    from .beffective import _fold_pulse_grad
+    return (gMi,
+            None if g_rf is None else _fold_pulse_grad(g_rf, rf_shape, rf_dtype, p.b1 is None),
+            None if g_gr is None else _fold_pulse_grad(g_gr, gr_shape, gr_dtype, False))
+
+
 class BlochSimRfGrHIP(Function):
     r"""``M = BlochSimRfGrHIP.apply(Mi, rf, gr, pulse_on_spins, γ2πdt, E1, E2, E1_1, want_ckpt, every)``
 
@@ -47,23 +87,14 @@ class BlochSimRfGrHIP(Function):
 
     @staticmethod
     def forward(ctx, Mi, rf, gr, p, γ2πdt, E1, E2, E1_1, want_ckpt=False, every=None):
-        from . import sims
         lib = _lib.require_library()
         device, dtype = Mi.device, Mi.dtype
-        code, g, e1, e2, e1m1 = sims._prep_constants(γ2πdt, E1, E2, E1_1, p.N, p.Nd, dtype, device)
+        need = bool(want_ckpt)
+        code, alive, consts, Mck, ckpt = _forward_prep(lib, p, γ2πdt, E1, E2, E1_1, dtype, device, need)
         Mi_c = Mi.detach().contiguous()
         traj = every is not None
         M = (torch.empty((-(-p.nT // every), p.N) + p.Nd + (3,), dtype=dtype, device=device) if traj
              else torch.empty_like(Mi_c))
-        need = bool(want_ckpt)
-        ck = int(lib.mrphy_blochsim_rfgr_ck_every())
-        # one checkpoint per started segment: nCk = ceil(nT / ck_every) (include/mrphy_hip.h)
-        Mck = (torch.empty((-(-p.nT // ck), p.N * p.nM, 3), dtype=dtype, device=device)
-               if need else None)
-        nul = _host.NULL_BC
-        consts = (*g.args, *(e1.args if e1 else nul), *(e2.args if e2 else nul),
-                  e1m1.t.data_ptr() if e1m1 else None)
-        ckpt = (Mck.data_ptr() if need else None, ck if need else 0)
         # the trajectory's Mo is optional (it equals the last record): not asked for
         name, outs = (('mrphy_blochsim_rfgr_traj_fwd', (None, *ckpt, M.data_ptr(), every)) if traj
                       else ('mrphy_blochsim_rfgr_fwd', (M.data_ptr(), *ckpt)))
@@ -73,14 +104,13 @@ class BlochSimRfGrHIP(Function):
         _lib.check(rc, name)
         if need:
             ctx.save_for_backward(Mck)
-            ctx.keep = (p, code, consts, (g, e1, e2, e1m1), rf.shape, gr.shape, rf.dtype, gr.dtype, every)
+            ctx.keep = (p, code, consts, alive, rf.shape, gr.shape, rf.dtype, gr.dtype, every)
         return M
 
     @staticmethod
     def backward(ctx, grad_M):
-        from .beffective import _fold_pulse_grad
-        need_Mi, need_rf, need_gr = ctx.needs_input_grad[0:3]
-        if not (need_Mi or need_rf or need_gr):
+        needs = ctx.needs_input_grad[0:3]
+        if not any(needs):
             return (None,) * 10
         lib = _lib.require_library()
         (Mck,) = ctx.saved_tensors
@@ -92,28 +122,18 @@ class BlochSimRfGrHIP(Function):
                                             'fused.blochsim_rfgr_traj' if traj else 'fused.blochsim_rfgr')
         device, dtype = Mck.device, Mck.dtype
         gM = grad_M.to(dtype).contiguous()      # the trajectory's: time-major, as the forward returned it -- free if so
-        gMi = torch.empty((p.N,) + p.Nd + (3,), dtype=dtype, device=device) if need_Mi else None
-        g_rf = torch.empty((p.N, 2, p.nT, p.nC), dtype=dtype, device=device) if need_rf else None
-        g_gr = torch.empty((p.N, 3, p.nT), dtype=dtype, device=device) if need_gr else None
-        outs = (gMi.data_ptr() if need_Mi else None, g_rf.data_ptr() if need_rf else None,
-                g_gr.data_ptr() if need_gr else None)
+        grads, outs, work = _backward_prep(lib, p, code, needs, dtype, device)
         tr = (every,) if traj else ()
         if p.nC == 1:
-            nbytes = int(lib.mrphy_blochsim_rfgr_bwd_workspace(code, p.N, p.nM, p.nT))
             name, nc = ('mrphy_blochsim_rfgr_traj_bwd' if traj else 'mrphy_blochsim_rfgr_bwd'), ()
-        else:                                   # parallel transmit: per-coil sums in the kernel
-            nbytes = int(lib.mrphy_blochsim_rfgr_mc_bwd_workspace(code, p.N, p.nM, p.nT, p.nC))
+        else:                                   # parallel transmit
             name, nc = ('mrphy_blochsim_rfgr_mc_traj_bwd' if traj else 'mrphy_blochsim_rfgr_mc_bwd'), (p.nC,)
-        work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
         with torch.cuda.device(device):
             rc = getattr(lib, name)(code, Mck.data_ptr(), *p.k0_args(), *consts, gM.data_ptr(), *tr, *outs,
                                     work.data_ptr(), work.numel(), p.N, p.nM, p.nT, *nc,
                                     _host.current_stream(device))
         _lib.check(rc, name)
-        return (gMi,
-                _fold_pulse_grad(g_rf, rf_shape, rf_dtype, p.b1 is None) if need_rf else None,
-                _fold_pulse_grad(g_gr, gr_shape, gr_dtype, False) if need_gr else None,
-                None, None, None, None, None, None, None)
+        return (*_fold_grads(*grads, p, rf_shape, gr_shape, rf_dtype, gr_dtype), *(None,) * 7)
 
 
 class SignalRfGrHIP(Function):
@@ -125,21 +145,14 @@ class SignalRfGrHIP(Function):
 
     @staticmethod
     def forward(ctx, Mi, rf, gr, p, rx, γ2πdt, E1, E2, E1_1, want_ckpt=False, every=1):
-        from . import sims
         lib = _lib.require_library()
         device, dtype = Mi.device, Mi.dtype
-        code, g, e1, e2, e1m1 = sims._prep_constants(γ2πdt, E1, E2, E1_1, p.N, p.Nd, dtype, device)
+        need = bool(want_ckpt)
+        code, alive, consts, Mck, ckpt = _forward_prep(lib, p, γ2πdt, E1, E2, E1_1, dtype, device, need)
+        consts = (*consts, None if rx is None else rx.data_ptr())
         Mi_c = Mi.detach().contiguous()
         sig = torch.empty((p.N, 2, -(-p.nT // every)), dtype=dtype, device=device)
         Mo = torch.empty_like(Mi_c)
-        need = bool(want_ckpt)
-        ck = int(lib.mrphy_blochsim_rfgr_ck_every())
-        Mck = (torch.empty((-(-p.nT // ck), p.N * p.nM, 3), dtype=dtype, device=device)
-               if need else None)
-        nul = _host.NULL_BC
-        consts = (*g.args, *(e1.args if e1 else nul), *(e2.args if e2 else nul),
-                  e1m1.t.data_ptr() if e1m1 else None, None if rx is None else rx.data_ptr())
-        ckpt = (Mck.data_ptr() if need else None, ck if need else 0)
         nbytes = int(lib.mrphy_signal_rfgr_fwd_workspace(code, p.N, p.nM, p.nT, every))
         work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
         if p.nT == 0:
@@ -152,14 +165,13 @@ class SignalRfGrHIP(Function):
         ctx.set_materialize_grads(False)
         if need:
             ctx.save_for_backward(Mck)
-            ctx.keep = (p, code, consts, (g, e1, e2, e1m1, rx), rf.shape, gr.shape, rf.dtype, gr.dtype, every)
+            ctx.keep = (p, code, consts, (*alive, rx), rf.shape, gr.shape, rf.dtype, gr.dtype, every)
         return sig, Mo
 
     @staticmethod
     def backward(ctx, grad_sig, grad_Mo):
-        from .beffective import _fold_pulse_grad
-        need_Mi, need_rf, need_gr = ctx.needs_input_grad[0:3]
-        if not (need_Mi or need_rf or need_gr) or (grad_sig is None and grad_Mo is None):
+        needs = ctx.needs_input_grad[0:3]
+        if not any(needs) or (grad_sig is None and grad_Mo is None):
             return (None,) * 11
         lib = _lib.require_library()
         (Mck,) = ctx.saved_tensors
@@ -168,21 +180,14 @@ class SignalRfGrHIP(Function):
         device, dtype = Mck.device, Mck.dtype
         gs = None if grad_sig is None else grad_sig.to(dtype).contiguous()
         gM = None if grad_Mo is None else grad_Mo.to(dtype).contiguous()
-        gMi = torch.empty((p.N,) + p.Nd + (3,), dtype=dtype, device=device) if need_Mi else None
-        g_rf = torch.empty((p.N, 2, p.nT, 1), dtype=dtype, device=device) if need_rf else None
-        g_gr = torch.empty((p.N, 3, p.nT), dtype=dtype, device=device) if need_gr else None
-        nbytes = int(lib.mrphy_blochsim_rfgr_bwd_workspace(code, p.N, p.nM, p.nT))
-        work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+        grads, outs, work = _backward_prep(lib, p, code, needs, dtype, device)      # one transmit coil: K2b's workspace
         ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
         with torch.cuda.device(device):
             rc = lib.mrphy_signal_rfgr_bwd(code, Mck.data_ptr(), *p.k0_args(), *consts, ptr(gM), ptr(gs), every,
-                                           ptr(gMi), ptr(g_rf), ptr(g_gr), work.data_ptr(), work.numel(),
+                                           *outs, work.data_ptr(), work.numel(),
                                            p.N, p.nM, p.nT, _host.current_stream(device))
         _lib.check(rc, 'mrphy_signal_rfgr_bwd')
-        return (gMi,
-                _fold_pulse_grad(g_rf, rf_shape, rf_dtype, p.b1 is None) if need_rf else None,
-                _fold_pulse_grad(g_gr, gr_shape, gr_dtype, False) if need_gr else None,
-                None, None, None, None, None, None, None, None)
+        return (*_fold_grads(*grads, p, rf_shape, gr_shape, rf_dtype, gr_dtype), *(None,) * 8)
 
 
 def _route(Mi, rf, gr, loc, every, kw, signal=False, rx=None):

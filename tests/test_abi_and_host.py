@@ -12,6 +12,7 @@ import torch
 
 import mrphy_amd
 from mrphy_amd import _host, _lib
+from util import FAKE, FUSED_OPS_NULL, fused_ops
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, 'include', 'mrphy_hip.h')
@@ -430,11 +431,81 @@ def test_argument_errors_of_the_newer_entry_points():
     assert lib.mrphy_blochsim_rfgr_mc_bwd_workspace(0, 1, 64 * 5000, 2 * ck, 4) == \
         2048 * 1 * (3 + 2 * 4) * 2 * ck * 4                    # persistent waves x rows x nT x 4 B
     assert lib.mrphy_blochsim_rfgr_mc_bwd_workspace(1, 1, 100, ck, 2) == 2 * 7 * ck * 8
-    args = [None, None, 0, None, 0, None] + [None, 0, 0] * 2 + [None] + [None, 0, 0] * 3 + [None]
+    args = [None] + FUSED_OPS_NULL                            # Mck, rf .. E1m1
     tail = [None, None, None, None, None, 0]
     assert lib.mrphy_blochsim_rfgr_mc_bwd(0, *args, *tail, 1, 64, ck, 9, None) == EINVAL    # 9 coils
     assert lib.mrphy_blochsim_rfgr_mc_bwd(0, *args, *tail, 1, 64, ck + 1, 4, None) == EINVAL  # nT % 16
     assert lib.mrphy_blochsim_rfgr_mc_bwd(0, *args, *tail, 1, 0, ck, 4, None) == 0
+
+
+# The eight entry points of the fused family, as the table below calls them: name -> (its own workspace query or
+# None, call(lib, first, ops, work_bytes, N, nM, nT, nC) with every other pointer fake).  nC where the entry point
+# takes one; the plain and trajectory adjoints and the signal adjoint have no such parameter.
+def _fused_entry_points(lib):
+    F = FAKE
+    k2b_ws = lambda N, nM, nT, nC: lib.mrphy_blochsim_rfgr_bwd_workspace(0, N, nM, nT)  # noqa: E731
+    mc_ws = lambda N, nM, nT, nC: lib.mrphy_blochsim_rfgr_mc_bwd_workspace(0, N, nM, nT, nC)  # noqa: E731
+    sig_ws = lambda N, nM, nT, nC: lib.mrphy_signal_rfgr_fwd_workspace(0, N, nM, nT, 1)  # noqa: E731
+    return {
+        'mrphy_blochsim_rfgr_fwd': (None, lambda ops, wb, N, nM, nT, nC: lib.mrphy_blochsim_rfgr_fwd(
+            0, F, *ops, F, None, 0, N, nM, nT, nC, None)),
+        'mrphy_blochsim_rfgr_traj_fwd': (None, lambda ops, wb, N, nM, nT, nC: lib.mrphy_blochsim_rfgr_traj_fwd(
+            0, F, *ops, None, None, 0, F, 1, N, nM, nT, nC, None)),
+        'mrphy_blochsim_rfgr_bwd': (k2b_ws, lambda ops, wb, N, nM, nT, nC: lib.mrphy_blochsim_rfgr_bwd(
+            0, F, *ops, F, None, None, None, F, wb, N, nM, nT, None)),
+        'mrphy_blochsim_rfgr_traj_bwd': (k2b_ws, lambda ops, wb, N, nM, nT, nC: lib.mrphy_blochsim_rfgr_traj_bwd(
+            0, F, *ops, F, 1, None, None, None, F, wb, N, nM, nT, None)),
+        'mrphy_blochsim_rfgr_mc_bwd': (mc_ws, lambda ops, wb, N, nM, nT, nC: lib.mrphy_blochsim_rfgr_mc_bwd(
+            0, F, *ops, F, None, None, None, F, wb, N, nM, nT, nC, None)),
+        'mrphy_blochsim_rfgr_mc_traj_bwd': (mc_ws, lambda ops, wb, N, nM, nT, nC: lib.mrphy_blochsim_rfgr_mc_traj_bwd(
+            0, F, *ops, F, 1, None, None, None, F, wb, N, nM, nT, nC, None)),
+        'mrphy_signal_rfgr_fwd': (sig_ws, lambda ops, wb, N, nM, nT, nC: lib.mrphy_signal_rfgr_fwd(
+            0, F, *ops, None, None, None, 0, F, 1, F, wb, N, nM, nT, nC, None)),
+        'mrphy_signal_rfgr_bwd': (k2b_ws, lambda ops, wb, N, nM, nT, nC: lib.mrphy_signal_rfgr_bwd(
+            0, F, *ops, None, F, F, 1, None, None, None, F, wb, N, nM, nT, None)),
+    }
+
+
+def test_fused_entry_points_check_their_operands_alike():
+    r"""All eight entry points of the fused family on N = 1, nM = 64, nT = 16, every = 1 with fake pointers and exactly
+    one operand at fault: MRPHY_EINVAL from each of them -- also with the workspace one byte short (the null checks come
+    before MRPHY_ENOSPC) -- and 0 for an empty problem whatever the operands are (it comes before the null checks).
+    No call here is fully valid, so nothing is launched."""
+    lib = mrphy_amd.require_library()
+    EINVAL = -1
+    N, nM, nT = 1, 64, 16
+    assert nT % lib.mrphy_blochsim_rfgr_ck_every() == 0
+    F = FAKE
+    faults = {
+        'loc null': dict(loc=None),
+        'g null': dict(g=None),
+        'rf null': dict(rf=None),
+        'gr null': dict(gr=None),
+        'df without gamma': dict(df=F),
+        'E1 without E2': dict(E1=F, E1m1=F),
+        'E2 without E1': dict(E2=F, E1m1=F),
+        'E1 and E2 without E1m1': dict(E1=F, E2=F),
+        'E1m1 alone': dict(E1m1=F),
+    }
+    multi_coil = ('mrphy_blochsim_rfgr_mc_bwd', 'mrphy_blochsim_rfgr_mc_traj_bwd')
+    n = 0
+    for name, (query, call) in _fused_entry_points(lib).items():
+        # the multi-coil adjoints: two coils and their b1 map; everything else: one coil, no map
+        nC, base = (2, dict(b1=F)) if name in multi_coil else (1, {})
+        need = query(N, nM, nT, nC) if query else 0
+        assert not query or need > 0, name
+        cases = {k: {**base, **v} for k, v in faults.items()}
+        if name in multi_coil:
+            cases['b1 null'] = {}
+        for what, ptrs in cases.items():
+            for wb in ((need, need - 1) if query else (0,)):
+                assert call(fused_ops(**ptrs), wb, N, nM, nT, nC) == EINVAL, (name, what, wb)
+                n += 1
+        if name in ('mrphy_blochsim_rfgr_fwd', 'mrphy_blochsim_rfgr_traj_fwd'):
+            assert call(fused_ops(), 0, N, nM, nT, 2) == EINVAL, (name, 'two coils without b1')
+            n += 1
+        assert call(fused_ops(**{**base, 'loc': None}), need, N, 0, nT, nC) == 0, (name, 'empty problem')
+    assert n == 2 * 9 + 2 + 6 * 2 * 9 + 2 * 2
 
 
 def test_mask_index_is_keyed_by_identity(monkeypatch):

@@ -5,6 +5,7 @@ import torch
 
 import mrphy_amd
 from mrphy_amd import fused
+from util import FAKE, FUSED_OPS_NULL as _OPS, fused_ops
 
 EINVAL, ENOSPC = -1, -3
 
@@ -13,18 +14,9 @@ def _lib():
     return mrphy_amd.require_library()
 
 
-# operand lists in the order of include/mrphy_hip.h, all null, with the sizes and the trailing arguments chosen per call
-_OPS = [None, 0, None, 0, None] + [None, 0, 0] * 2 + [None] + [None, 0, 0] * 3 + [None]   # rf .. E1m1
-
-
-FAKE = 4096                                            # never dereferenced: every call returns before a launch
-# rf, gr, loc and g present (fake), the optional operands absent: only the argument a call gets wrong is wrong
-_OPS_SET = [FAKE, 0, FAKE, 0, FAKE] + [None, 0, 0] * 2 + [None] + [FAKE, 0, 0] + [None, 0, 0] * 2 + [None]
-
-
+# (the operand lists rf .. E1m1, all null or with fake pointers: util.py; sizes and trailing arguments chosen per call)
 def _fwd(dtype=0, Mi=FAKE, Mt=FAKE, every=1, N=1, nM=64, nT=16, nC=1, b1=None):
-    ops = list(_OPS_SET)
-    ops[11] = b1                                       # b1
+    ops = fused_ops(b1=b1)
     return _lib().mrphy_blochsim_rfgr_traj_fwd(dtype, Mi, *ops, None, None, 0, Mt, every, N, nM, nT, nC, None)
 
 
@@ -68,13 +60,12 @@ def test_traj_bwd_workspace_too_small_is_enospc():
     lib = _lib()
     ck = lib.mrphy_blochsim_rfgr_ck_every()
     fake = FAKE
-    ops = list(_OPS_SET)
+    ops = fused_ops()
     need = lib.mrphy_blochsim_rfgr_bwd_workspace(0, 1, 64, ck)
     assert need > 0
     tail = [fake, 1, None, None, None, fake, need - 1, 1, 64, ck]
     assert lib.mrphy_blochsim_rfgr_traj_bwd(0, fake, *ops, *tail, None) == ENOSPC
-    ops_mc = list(ops)
-    ops_mc[11] = fake                                                       # b1
+    ops_mc = fused_ops(b1=fake)
     need = lib.mrphy_blochsim_rfgr_mc_bwd_workspace(0, 1, 64, ck, 4)
     tail = [fake, 1, None, None, None, fake, need - 1, 1, 64, ck]
     assert lib.mrphy_blochsim_rfgr_mc_traj_bwd(0, fake, *ops_mc, *tail, 4, None) == ENOSPC

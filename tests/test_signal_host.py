@@ -5,11 +5,9 @@ import torch
 
 import mrphy_amd
 from mrphy_amd import fused
+from util import FAKE, FUSED_OPS_SET as _OPS_SET         # rf .. E1m1: rf, gr, loc and g present (fake), the rest absent
 
 EINVAL, ENOSPC = -1, -3
-FAKE = 4096                                            # never dereferenced: every call returns before a launch
-# rf .. E1m1 in the order of include/mrphy_hip.h: rf, gr, loc and g present (fake), the optional operands absent
-_OPS_SET = [FAKE, 0, FAKE, 0, FAKE] + [None, 0, 0] * 2 + [None] + [FAKE, 0, 0] + [None, 0, 0] * 2 + [None]
 
 
 def _lib():

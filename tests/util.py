@@ -64,6 +64,26 @@ def to_dev(d, device):
 
 
 # ---------------------------------------------------------------------------------------------
+# The operands of the fused family's C entry points (rf .. E1m1 of include/mrphy_hip.h, 22 arguments) for the host
+# tests, which check what the ABI returns BEFORE any launch: the pointers are fake and never dereferenced.
+# ---------------------------------------------------------------------------------------------
+FAKE = 4096
+FUSED_OP_AT = {'rf': 0, 'gr': 2, 'loc': 4, 'df': 5, 'gamma': 8, 'b1': 11, 'g': 12, 'E1': 15, 'E2': 18, 'E1m1': 21}
+# every pointer null
+FUSED_OPS_NULL = [None, 0, None, 0, None] + [None, 0, 0] * 2 + [None] + [None, 0, 0] * 3 + [None]
+# rf, gr, loc and g present, the optional operands absent: only the argument a call gets wrong is wrong
+FUSED_OPS_SET = [FAKE, 0, FAKE, 0, FAKE] + [None, 0, 0] * 2 + [None] + [FAKE, 0, 0] + [None, 0, 0] * 2 + [None]
+
+
+def fused_ops(**pointers):
+    r"""A copy of ``FUSED_OPS_SET`` with the named pointers (``FUSED_OP_AT``) replaced: ``fused_ops(b1=FAKE, g=None)``."""
+    ops = list(FUSED_OPS_SET)
+    for name, p in pointers.items():
+        ops[FUSED_OP_AT[name]] = p
+    return ops
+
+
+# ---------------------------------------------------------------------------------------------
 # Parity ledger: every distance a GPU test measures goes through record(); at the end of the
 # session tests/conftest.py writes them to gpurun_out/parity_ledger.json (scratch; the judged copy
 # is committed as profiles/rNN_parity.json).  Bounds in the tests cite these numbers.
