@@ -12,27 +12,19 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdArgsT<T, INJ> a
     const int64_t w = blockIdx.x, n = blockIdx.y;
     const int64_t nT = a.nT, rows = a.N * a.nM;
     const int64_t ntiles = (a.nM + WAVE - 1) / WAVE;
-    // read-only, wave-uniform pulse through the constant address space: scalar loads (see K2)
-    using CP = const T __attribute__((address_space(4)))*;
-    CP rfr = (CP)(a.in.rf + n * a.in.rf_sn);
-    CP rfi = rfr + nT;
-    CP gx = (CP)(a.in.gr + n * a.in.gr_sn);
-    CP gy = gx + nT;
-    CP gz = gy + nT;
+    const PulseCP<T> pc = pulse_cp<T>(a.in, n, nT, 1);
+    using CP = typename PulseCP<T>::CP;
     T* wsrow = a.work + ((w * a.N + n) * 5) * nT;
     bool first = true;
 
     for (int64_t tile = w; tile < ntiles; tile += a.P) {
-        const int64_t s_ = tile * WAVE + lane;
-        const bool valid = s_ < a.nM;
-        const int64_t s = valid ? s_ : a.nM - 1;
+        bool valid;
+        const int64_t s = lane_spin(tile, lane, a.nM, valid);
         const int64_t row = n * a.nM + s;
         const SpinConst<T, CT> k = load_consts<T, CT>(a.in.g, a.in.E1, a.in.E2, a.in.E1m1, n, s);
-        const T lx = a.in.loc[row * 3], ly = a.in.loc[row * 3 + 1], lz = a.in.loc[row * 3 + 2];
-        T delta = T(0);
-        if (a.in.df.p) delta = bc_load<T>(a.in.df, n, s) / bc_load<T>(a.in.gam, n, s);
-        T br = T(1), bi = T(0);
-        if (HB1 && a.in.b1) { br = a.in.b1[row * 2]; bi = a.in.b1[row * 2 + 1]; }
+        const Spin<T> sp = load_spin<T>(a.in, n, s, row);
+        T br, bi;
+        load_b1<HB1>(a.in.b1, row, br, bi);
         const T vmask = valid ? T(1) : T(0);
         // lanes past nM (they hold a copy of the last valid spin) start from a zero cotangent: the adjoint state and every
         // dL/dB they form stay exact zeros (all of it is linear in the state), so they add nothing to the row sums --
@@ -57,38 +49,25 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdArgsT<T, INJ> a
         }
         adj_begin<RELAX, T, CT>(k, hx, hy, hz);
 
-        auto field = [&](int64_t t, T& Bx, T& By, T& Bz) {
-            Bx = T(0); By = T(0);
-            if (HB1) field_xy_acc<T>(br, bi, rfr[t], rfi[t], Bx, By);
-            else     { Bx = rfr[t]; By = rfi[t]; }               // no b1 map: Bxy = rf (as K2 / K0)
-            Bz = field_z<T>(gx[t], gy[t], gz[t], lx, ly, lz, delta);
-        };
+        auto field = [&](int64_t t, T& Bx, T& By, T& Bz) { field_1coil<HB1>(br, bi, pc, t, sp, Bx, By, Bz); };
 
-        // Two global round trips per segment used to sit on the critical path: the checkpoint (used
-        // at once by the recompute) and the read-modify-write of the workspace rows.  Both are now
-        // issued a segment's worth of work ahead: the next checkpoint at the top of the current
-        // segment, the old workspace values before the sweep that produces what is added to them.
+        // (the checkpoint and the old workspace values are fetched a segment ahead: ck_before, k_fused_bwd_common.hpp)
         const int64_t nseg = nT / SEG;
         T cx = T(0), cy = T(0), cz = T(0);
-        if (nseg > 0) {
-            const T* ck = a.Mck + ((nseg - 1) * rows + row) * 3;
-            cx = ck[0]; cy = ck[1]; cz = ck[2];
-        }
+        if (nseg > 0) { const T* ck = ck_before(a.Mck, nseg, rows, row); cx = ck[0]; cy = ck[1]; cz = ck[2]; }
         // rows 64..79 (the second pass of the row sums): four lanes per row, one of the four chains each
         const int r1 = WAVE + (lane >> 2);
         for (int64_t seg = nseg - 1; seg >= 0; --seg) {
             const int64_t t0 = seg * SEG;
             T mx = cx, my = cy, mz = cz;
-            if (seg > 0) {
-                const T* ck = a.Mck + ((seg - 1) * rows + row) * 3;
-                cx = ck[0]; cy = ck[1]; cz = ck[2];
-            }
+            if (seg > 0) { const T* ck = ck_before(a.Mck, seg, rows, row); cx = ck[0]; cy = ck[1]; cz = ck[2]; }
             // the trajectory cotangents of this segment.  INJ == 2: at most one, at step ist of the segment (-1: none),
             // in registers, requested here and used in the sweep after the recompute.  INJ == 1: the lane's cotangent of
             // step st goes to the slots red[(0|1|2) SEG + st][lane] that the sweep overwrites at that very step with
             // its own contributions -- the same lane reads it just before (lane-private: no barrier; the previous
             // segment's reduction released the tile at the barrier that ended it); zero where no record is taken.
             // No LDS beyond K2b's, no registers beyond the staging loads.
+            // (the staging and its injection are written out in both adjoints: shared helpers cost registers, LABNOTES)
             int ist = -1;
             T ijx = T(0), ijy = T(0), ijz = T(0);
             if constexpr (INJ == 2) {
@@ -120,22 +99,8 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdArgsT<T, INJ> a
             T old0 = T(0), old1 = T(0);
             if (!first) { old0 = *dst0; old1 = *dst1; }
             // 1. forward recompute, keeping the state before each step
-            T M0[SEG], M1[SEG], M2[SEG], Sv[SEG], Cv[SEG];
-#pragma unroll
-            for (int sb = 0; sb < SEG / 4; ++sb) {
-                T Bx[4], By[4], Bz[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) field(t0 + sb * 4 + j, Bx[j], By[j], Bz[j]);
-                Rot<T> r[4];
-                rot_prepare<T, CT, 4>(k, Bx, By, Bz, r);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int st = sb * 4 + j;
-                    M0[st] = mx; M1[st] = my; M2[st] = mz;
-                    Sv[st] = r[j].S; Cv[st] = r[j].C;     // reused by the sweep
-                    rot_apply<RELAX, T, CT>(k, r[j], mx, my, mz);
-                }
-            }
+            SegStates<T> h;
+            seg_recompute<RELAX>(k, t0, mx, my, mz, field, h);
             // 2. adjoint sweep, contributions to LDS
 #pragma unroll
             for (int sb = SEG / 4 - 1; sb >= 0; --sb) {
@@ -143,8 +108,8 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdArgsT<T, INJ> a
 #pragma unroll
                 for (int j = 0; j < 4; ++j) field(t0 + sb * 4 + j, Bx[j], By[j], Bz[j]);
                 RotAdj<T> ra[4];
-                const T S4[4] = {Sv[sb * 4], Sv[sb * 4 + 1], Sv[sb * 4 + 2], Sv[sb * 4 + 3]};
-                const T C4[4] = {Cv[sb * 4], Cv[sb * 4 + 1], Cv[sb * 4 + 2], Cv[sb * 4 + 3]};
+                const T S4[4] = {h.Sv[sb * 4], h.Sv[sb * 4 + 1], h.Sv[sb * 4 + 2], h.Sv[sb * 4 + 3]};
+                const T C4[4] = {h.Cv[sb * 4], h.Cv[sb * 4 + 1], h.Cv[sb * 4 + 2], h.Cv[sb * 4 + 3]};
                 rot_prepare_adj_given<T, CT, 4>(k, Bx, By, Bz, S4, C4, ra);
 #pragma unroll
                 for (int j = 3; j >= 0; --j) {
@@ -163,11 +128,10 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdArgsT<T, INJ> a
                         }
                     }
                     T g0, g1, g2;
-                    rot_apply_adj<RELAX, T, CT>(k, ra[j], M0[st], M1[st], M2[st], hx, hy, hz,
-                                                g0, g1, g2);
-                    red[red_idx(0 * SEG + st, lane)] = lx * g2;
-                    red[red_idx(1 * SEG + st, lane)] = ly * g2;
-                    red[red_idx(2 * SEG + st, lane)] = lz * g2;
+                    rot_apply_adj<RELAX, T, CT>(k, ra[j], h.M0[st], h.M1[st], h.M2[st], hx, hy, hz, g0, g1, g2);
+                    red[red_idx(0 * SEG + st, lane)] = sp.lx * g2;
+                    red[red_idx(1 * SEG + st, lane)] = sp.ly * g2;
+                    red[red_idx(2 * SEG + st, lane)] = sp.lz * g2;
                     red[red_idx(3 * SEG + st, lane)] = HB1 ? br * g0 + bi * g1 : g0;
                     red[red_idx(4 * SEG + st, lane)] = HB1 ? br * g1 - bi * g0 : g1;
                 }
@@ -206,25 +170,4 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdArgsT<T, INJ> a
         if (valid && a.gMi) { a.gMi[row * 3] = hx; a.gMi[row * 3 + 1] = hy; a.gMi[row * 3 + 2] = hz; }
         first = false;
     }
-}
-
-template <typename T>
-__global__ __launch_bounds__(P2_T * P2_G) void k_bloch_rfgr_bwd_p2(const T* work, T* grf, T* ggr,
-                                                                   int64_t N, int64_t nT, int64_t P)
-{
-    __shared__ T part[P2_G][P2_T];
-    const int tl = threadIdx.x % P2_T, g = threadIdx.x / P2_T;
-    const int64_t t = (int64_t)blockIdx.x * P2_T + tl;
-    const int64_t q = blockIdx.y, n = blockIdx.z;
-    T acc = T(0);
-    if (t < nT)
-        for (int64_t w = g; w < P; w += P2_G) acc += work[((w * N + n) * 5 + q) * nT + t];
-    part[g][tl] = acc;
-    __syncthreads();
-    if (g != 0 || t >= nT) return;
-    T sum = part[0][tl];
-#pragma unroll
-    for (int i = 1; i < P2_G; ++i) sum += part[i][tl];
-    if (q < 3) { if (ggr) ggr[(n * 3 + q) * nT + t] = sum; }
-    else if (grf) grf[(n * 2 + (q - 3)) * nT + t] = sum;
 }

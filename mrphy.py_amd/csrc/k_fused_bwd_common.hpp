@@ -2,6 +2,7 @@
 // Fragment: included INSIDE a translation unit's anonymous namespace, after host_common.hpp (HIP runtime,
 // include/mrphy_hip.h, geom.hpp, bloch_math.hpp, k_common.hpp).  Not a standalone header.
 #pragma once
+#include "k_fused_common.hpp"
 
 // =============================================================================================
 // K2b: adjoint of the fused kernel -- grad_Mo -> grad_Mi, grad_rf, grad_gr without Beff, history
@@ -19,22 +20,12 @@
 // deterministic, no float atomics.
 // =============================================================================================
 // (SEG = 16 steps per checkpoint segment: geom.hpp)
-// Reduction tile: 80 rows x 64 lanes, NO padding (20480 B = exactly 1/8 of a CU's LDS, so 8 waves
-// = 2 per SIMD are resident; with a padded pitch of 68 it was 21760 B -> 7 per CU, SIMD load
-// 2:2:2:1).  Conflict-free row reads come from an XOR swizzle of the 16-B slot index instead:
-// element (row, lane) lives in slot (lane/4) ^ (row & 15).
-constexpr int RED_PITCH = WAVE;
+// (the reduction tile's index red_idx, RED_PITCH, and the second pass over the workspace rows: k_fused_common.hpp)
 // (K2B_MAX_WAVES = 256 * 8 resident waves, 8 per CU: geom.hpp)
-// The swizzle is a bijection of the 16 slots of a row for ANY row count, so red_idx is correct for every SEG; it
-// is conflict-free for the 16-row groups of SEG = 16 it was laid out for.  The single-coil kernel needs
-// 5 * SEG <= 2 * WAVE rows (two passes of row sums) and batches of 4 steps; the multi-coil kernel needs SEG == 16
-// outright (k_fused_mc_bwd.hpp).
+// The single-coil kernel needs 5 * SEG <= 2 * WAVE rows (two passes of row sums) and batches of 4 steps; the
+// multi-coil kernel needs SEG == 16 outright (k_fused_mc_bwd.hpp).
 static_assert(SEG % 4 == 0 && 5 * SEG <= 2 * WAVE, "K2b: 4-step batches, 5 * SEG reduction rows in two passes");
 static_assert(SEG == 16, "K2b's reduction tile (red_idx: row & 15, 20480 B = 1/8 of a CU's LDS) is laid out for SEG = 16");
-__device__ __forceinline__ int red_idx(int row, int l)
-{
-    return row * RED_PITCH + ((((l >> 2) ^ (row & 15)) << 2) | (l & 3));
-}
 
 template <typename T>
 struct FusedBwdArgs {
@@ -109,8 +100,38 @@ __device__ __forceinline__ void adj_inject(const SpinConst<T, CT>& k, T& hx, T& 
     hx += gx; hy += gy; hz += gz;
 }
 
-// Pass 2: sum the P workspace rows per (n, quantity, t) in a fixed order.  Block = 32 time points
-// x 8 row groups (group g takes rows g, g+8, ...: 128-B coalesced reads per row), then the eight
-// partial sums are combined through LDS in group order -- deterministic, and nT/32 * 5 blocks
-// instead of nT/256 * 5 (40 blocks at nT = 2048 took 0.45 ms for 73 MB).
-constexpr int P2_T = 32, P2_G = 8;
+// Two global round trips per segment used to sit on the critical path: the checkpoint (used
+// at once by the recompute) and the read-modify-write of the workspace rows.  Both are now
+// issued a segment's worth of work ahead: the next checkpoint at the top of the current
+// segment, the old workspace values before the sweep that produces what is added to them.
+// The lane's checkpoint that segment `seg` - 1 starts from:
+template <typename T>
+__device__ __forceinline__ const T* ck_before(const T* Mck, int64_t seg, int64_t rows, int64_t row)
+{
+    return Mck + ((seg - 1) * rows + row) * 3;
+}
+
+// The SEG states before each step of the segment at t0, recomputed from its checkpoint (mx, my, mz; the very states the forward
+// pass went through), with the S, C of each rotation
+template <typename T> struct SegStates { T M0[SEG], M1[SEG], M2[SEG], Sv[SEG], Cv[SEG]; };
+
+template <bool RELAX, typename T, typename CT, typename F>
+__device__ __forceinline__ void seg_recompute(const SpinConst<T, CT>& k, int64_t t0, T& mx, T& my, T& mz, F&& field,
+                                              SegStates<T>& h)
+{
+#pragma unroll
+    for (int sb = 0; sb < SEG / 4; ++sb) {
+        T Bx[4], By[4], Bz[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) field(t0 + sb * 4 + j, Bx[j], By[j], Bz[j]);
+        Rot<T> r[4];
+        rot_prepare<T, CT, 4>(k, Bx, By, Bz, r);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int st = sb * 4 + j;
+            h.M0[st] = mx; h.M1[st] = my; h.M2[st] = mz;
+            h.Sv[st] = r[j].S; h.Cv[st] = r[j].C;     // reused by the sweep
+            rot_apply<RELAX, T, CT>(k, r[j], mx, my, mz);
+        }
+    }
+}

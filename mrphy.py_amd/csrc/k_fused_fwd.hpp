@@ -2,6 +2,7 @@
 // Fragment: included INSIDE a translation unit's anonymous namespace, after host_common.hpp (HIP runtime,
 // include/mrphy_hip.h, geom.hpp, bloch_math.hpp, k_common.hpp).  Not a standalone header.
 #pragma once
+#include "k_fused_common.hpp"
 
 // =============================================================================================
 // K2: fused rf,gr -> Mo.  No Beff in HBM: the pulse sample of step t is wave-uniform (one block
@@ -51,11 +52,7 @@ static_assert(fused_args_layout<float> && fused_args_layout<double>, "K2's kerne
 // Measured at 64^3 x 1024 before the 16 / 32 capacities existed: 8 coils 0.75 ms, 9 coils 5.85 ms,
 // 16 coils 20.8 ms on the memory path (tools/ptx_timing.py).
 constexpr int K2_MAXC = 64;                              // largest register/LDS coil capacity (48 / 64: float only)
-// HB1 (one-coil builds): the coil has a b1 map.  Without one Bxy = rf (beffective.py:147-151): the
-// build then skips the complex product -- 6 of the ~50 VALU instructions of a step; with b1 = (1, 0)
-// the product returns rf bit for bit anyway, so results are unchanged.  A template parameter, not a
-// run-time test: a wave-uniform branch in the field assembly broke the batching of the pulse's scalar
-// loads (round 1: 6.6 -> 7.2 ms).
+// HB1 (one-coil builds): the coil has a b1 map (load_b1, k_fused_common.hpp).
 // K2t: M after step t into the running record destination mtp if a record is taken there (TR == 1: after every step;
 // TR == 2: after the step `next`, which then moves on by `every`)
 template <int TR, typename T>
@@ -66,10 +63,7 @@ __device__ __forceinline__ void traj_record(int64_t t, bool valid, T mx, T my, T
         if (valid) { mtp[0] = mx; mtp[1] = my; mtp[2] = mz; }
         mtp += pitch;
     } else {
-        if (t == next) {                                      // wave-uniform
-            if (valid) { mtp[0] = mx; mtp[1] = my; mtp[2] = mz; }
-            mtp += pitch; next += every;
-        }
+        ck_store(t, valid, mx, my, mz, mtp, pitch, next, every);
     }
 }
 
@@ -91,31 +85,21 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_fwd(FusedArgsT<T, TR> a)
     __shared__ __attribute__((aligned(16))) T srf[NCR ? 2 * NS * MC : 4];  // [re|im][j][c]
     const int lane = threadIdx.x;
     const int64_t n = blockIdx.y;
-    const int64_t s_ = (int64_t)blockIdx.x * WAVE + lane;
-    const bool valid = s_ < a.nM;
-    const int64_t s = valid ? s_ : a.nM - 1;
+    bool valid;
+    const int64_t s = lane_spin(blockIdx.x, lane, a.nM, valid);
     const int64_t row = n * a.nM + s;
     const SpinConst<T, CT> k = load_consts<T, CT>(a.in.g, a.in.E1, a.in.E2, a.in.E1m1, n, s);
-
     T mx = a.Mi[row * 3], my = a.Mi[row * 3 + 1], mz = a.Mi[row * 3 + 2];
-    const T lx = a.in.loc[row * 3], ly = a.in.loc[row * 3 + 1], lz = a.in.loc[row * 3 + 2];
-    T delta = T(0);
-    if (a.in.df.p) delta = bc_load<T>(a.in.df, n, s) / bc_load<T>(a.in.gam, n, s);
-    T br = T(1), bi = T(0);
-    if (NC1 && HB1 && a.in.b1) { br = a.in.b1[row * 2]; bi = a.in.b1[row * 2 + 1]; }
+    // (load_spin's loads, written out: through the helper every build of K2 gains or loses an s_waitcnt, LABNOTES)
+    Spin<T> sp;
+    sp.lx = a.in.loc[row * 3]; sp.ly = a.in.loc[row * 3 + 1]; sp.lz = a.in.loc[row * 3 + 2];
+    sp.delta = T(0);
+    if (a.in.df.p) sp.delta = bc_load<T>(a.in.df, n, s) / bc_load<T>(a.in.gam, n, s);
+    T br, bi;
+    load_b1<NC1 && HB1>(a.in.b1, row, br, bi);
 
     const int64_t nT = a.nT, nC = a.nC;
-    // The pulse is read-only for the whole launch and its addresses are wave-uniform: pointers into the
-    // CONSTANT address space make the loads scalar (s_load, batched) whatever else the loop does.  With
-    // plain global pointers the checkpoint-writing build could not prove that its stores leave the pulse
-    // alone and fetched the samples with vector loads + v_readfirstlane (K2 with checkpoints: 0.82 ms
-    // where the plain build's rate gives 0.60 at 64^3 x 2048).
-    using CP = const T __attribute__((address_space(4)))*;
-    CP rfr = (CP)(a.in.rf + n * a.in.rf_sn);                 // [nT][nC]
-    CP rfi = rfr + nT * nC;
-    CP gx = (CP)(a.in.gr + n * a.in.gr_sn);
-    CP gy = gx + nT;
-    CP gz = gy + nT;
+    const PulseCP<T> pc = pulse_cp<T>(a.in, n, nT, nC);
     const T* b1 = a.in.b1 ? a.in.b1 + row * 2 * nC : nullptr;
     const int64_t rows = a.N * a.nM;
     T b1r[MC], b1i[MC];
@@ -127,7 +111,7 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_fwd(FusedArgsT<T, TR> a)
         }
     }
     // NCR: rf samples of steps [tb, tb + cnt) -> LDS as [step][MC], ZERO beyond nC: the coil loop
-    // below then needs no `c < nC` test (b1r/b1i are zero there too; adding exact zeros changes
+    // of field_staged then needs no `c < nC` test (b1r/b1i are zero there too; adding exact zeros changes
     // nothing), stays one basic block, and its broadcast reads are batched.  With the test it compiled
     // to a branch and an exposed LDS round trip per coil, as in K0 (8 coils: 0.81 ms at 64^3 x 1024).
     auto stage_rf = [&](int64_t tb, int cnt) {
@@ -135,33 +119,24 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_fwd(FusedArgsT<T, TR> a)
         for (int i = lane; i < cnt * MC; i += WAVE) {
             const int j = i / MC, c = i - j * MC;
             const bool on = c < (int)nC;
-            srf[i] = on ? rfr[(tb + j) * nC + c] : T(0);
-            srf[NS * MC + i] = on ? rfi[(tb + j) * nC + c] : T(0);
+            srf[i] = on ? pc.rfr[(tb + j) * nC + c] : T(0);
+            srf[NS * MC + i] = on ? pc.rfi[(tb + j) * nC + c] : T(0);
         }
         __syncthreads();
     };
     int64_t tstage = 0;                                       // first step held in srf
 
     auto field = [&](int64_t t, T& Bx, T& By, T& Bz) {
-        Bx = T(0); By = T(0);
-        if (NC1) {
-            if (HB1) field_xy_acc<T>(br, bi, rfr[t], rfi[t], Bx, By);
-            else     { Bx = rfr[t]; By = rfi[t]; }
-        } else if (NCR) {
-            const T* qr = srf + (t - tstage) * MC;
-            const T* qi = qr + NS * MC;
-#pragma unroll
-            for (int c = 0; c < MC; ++c) field_xy_fma<T>(b1r[c], b1i[c], qr[c], qi[c], Bx, By);
-        } else {
+        if (NC1) field_1coil<HB1>(br, bi, pc, t, sp, Bx, By, Bz);
+        else if (NCR) field_staged<MC>(b1r, b1i, srf + (t - tstage) * MC, NS * MC, pc, t, sp, Bx, By, Bz);
+        else {                                                // any number of coils, from memory
+            Bx = T(0); By = T(0);
             for (int64_t c = 0; c < nC; ++c)
-                field_xy_fma<T>(b1[c], b1[nC + c], rfr[t * nC + c], rfi[t * nC + c], Bx, By);
+                field_xy_fma<T>(b1[c], b1[nC + c], pc.rfr[t * nC + c], pc.rfi[t * nC + c], Bx, By);
+            Bz = field_z<T>(pc.gx[t], pc.gy[t], pc.gz[t], sp.lx, sp.ly, sp.lz, sp.delta);
         }
-        Bz = field_z<T>(gx[t], gy[t], gz[t], lx, ly, lz, delta);
     };
 
-    // checkpoints: a running destination and the step of the next one -- `t0 % ck_every`, `t0 / ck_every` on
-    // 64-bit run-time values were a software division on the scalar unit every 8 steps (round 3: +200 scalar
-    // instructions per 16 steps in the ISA of the checkpoint build)
     // The checkpoint build: all of the prologue's vector loads are awaited HERE, before the loop.  Otherwise the
     // wait for them lands in the loop header (the join of the prologue and the back edge) as s_waitcnt
     // vmcnt(0), where it also waits, every 8 steps, for the checkpoint store of the iteration before.
@@ -173,10 +148,7 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_fwd(FusedArgsT<T, TR> a)
     int64_t t0 = 0;
     for (; t0 + NS <= nT; t0 += NS) {
         if (NCR) { tstage = t0; stage_rf(t0, NS); }
-        if (CK && t0 == ck_next) {
-            if (valid) { ckp[0] = mx; ckp[1] = my; ckp[2] = mz; }
-            ckp += ck_pitch; ck_next += a.ck_every;
-        }
+        if (CK) ck_store(t0, valid, mx, my, mz, ckp, ck_pitch, ck_next, a.ck_every);
         T Bx[NS], By[NS], Bz[NS];
 #pragma unroll
         for (int j = 0; j < NS; ++j) field(t0 + j, Bx[j], By[j], Bz[j]);
@@ -190,10 +162,7 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_fwd(FusedArgsT<T, TR> a)
     }
     if (NCR && t0 < nT) { tstage = t0; stage_rf(t0, (int)(nT - t0)); }
     for (; t0 < nT; ++t0) {                                   // nT % 8 tail
-        if (CK && t0 == ck_next) {
-            if (valid) { ckp[0] = mx; ckp[1] = my; ckp[2] = mz; }
-            ckp += ck_pitch; ck_next += a.ck_every;
-        }
+        if (CK) ck_store(t0, valid, mx, my, mz, ckp, ck_pitch, ck_next, a.ck_every);
         T Bx[1], By[1], Bz[1];
         field(t0, Bx[0], By[0], Bz[0]);
         Rot<T> r[1];
@@ -227,9 +196,12 @@ FusedTrajArgs<T> fused_args(const void* Mi, const PulseOps& in, void* Mo, void* 
 
 // the build of coil capacity NCM for the checkpoint, relaxation and trajectory modes of `a`
 template <typename T, typename CT, int NCM, bool HB1>
-void launch_k2(const FusedTrajArgs<T>& a, hipStream_t st)
+int launch_k2(const FusedTrajArgs<T>& a, hipStream_t st)
 {
-    const dim3 grid((unsigned)((a.nM + WAVE - 1) / WAVE), (unsigned)a.N);
+    // the plain kernel runs at nT == 0 too (it writes Mo = Mi); a trajectory then has no record
+    dim3 grid;
+    int rc;
+    if (!fused_grid(a.N * a.nM * (a.Mt ? a.nT : 1), (a.nM + WAVE - 1) / WAVE, a.N, grid, rc)) return rc;
 #define MRPHY_K2(CK_, RX_, TR_)                                                                         \
     hipLaunchKernelGGL((k_bloch_rfgr_fwd<T, CT, NCM, CK_, RX_, HB1, TR_>), grid, dim3(WAVE), 0, st, \
                        (static_cast<const FusedArgsT<T, TR_>&>(a)))
@@ -244,4 +216,5 @@ void launch_k2(const FusedTrajArgs<T>& a, hipStream_t st)
     else    { if (rx) MRPHY_K2T(false, true); else MRPHY_K2T(false, false); }
 #undef MRPHY_K2T
 #undef MRPHY_K2
+    return launch_status();
 }

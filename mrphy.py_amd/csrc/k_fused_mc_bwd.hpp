@@ -44,22 +44,16 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd_mc(FusedBwdArgsT<T, INJ
     const int nQ = 3 + 2 * nC;
     const T* __restrict__ rfr = a.in.rf + n * a.in.rf_sn;      // [nT][nC]
     const T* __restrict__ rfi = rfr + nT * nC;
-    using CP = const T __attribute__((address_space(4)))*;     // wave-uniform gradient samples: scalar loads
-    CP gx = (CP)(a.in.gr + n * a.in.gr_sn);
-    CP gy = gx + nT;
-    CP gz = gy + nT;
+    const PulseCP<T> pc = pulse_cp<T>(a.in, n, nT, nC);        // wave-uniform gradient samples: scalar loads
     T* wsrow = a.work + ((w * a.N + n) * nQ) * nT;
     bool first = true;
 
     for (int64_t tile = w; tile < ntiles; tile += a.P) {
-        const int64_t s_ = tile * WAVE + lane;
-        const bool valid = s_ < a.nM;
-        const int64_t s = valid ? s_ : a.nM - 1;
+        bool valid;
+        const int64_t s = lane_spin(tile, lane, a.nM, valid);
         const int64_t row = n * a.nM + s;
         const SpinConst<T, CT> k = load_consts<T, CT>(a.in.g, a.in.E1, a.in.E2, a.in.E1m1, n, s);
-        const T lx = a.in.loc[row * 3], ly = a.in.loc[row * 3 + 1], lz = a.in.loc[row * 3 + 2];
-        T delta = T(0);
-        if (a.in.df.p) delta = bc_load<T>(a.in.df, n, s) / bc_load<T>(a.in.gam, n, s);
+        const Spin<T> sp = load_spin<T>(a.in, n, s, row);
         T br[MC], bi[MC];
 #pragma unroll
         for (int c = 0; c < MC; ++c) {
@@ -73,9 +67,9 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd_mc(FusedBwdArgsT<T, INJ
             cfs[c * WAVE + lane] = br[c] * vmask;
             cfs[(MC + c) * WAVE + lane] = bi[c] * vmask;
         }
-        cfs[(2 * MC + 0) * WAVE + lane] = lx * vmask;
-        cfs[(2 * MC + 1) * WAVE + lane] = ly * vmask;
-        cfs[(2 * MC + 2) * WAVE + lane] = lz * vmask;
+        cfs[(2 * MC + 0) * WAVE + lane] = sp.lx * vmask;
+        cfs[(2 * MC + 1) * WAVE + lane] = sp.ly * vmask;
+        cfs[(2 * MC + 2) * WAVE + lane] = sp.lz * vmask;
         // grad_Mo; in the trajectory builds grad_Mt, whose last record is Mo
         const T* gM = a.gMo;
         if constexpr (INJ != 0) gM += (a.nRec - 1) * rows * 3;
@@ -87,20 +81,12 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd_mc(FusedBwdArgsT<T, INJ
 
         int64_t tstage = 0;
         auto field = [&](int64_t t, T& Bx, T& By, T& Bz) {
-            Bx = T(0); By = T(0);
-            const T* qr = srf + (t - tstage) * MC;          // broadcast reads, batched: no test in the loop
-            const T* qi = qr + SEG * MC;
-#pragma unroll
-            for (int c = 0; c < MC; ++c) field_xy_fma<T>(br[c], bi[c], qr[c], qi[c], Bx, By);
-            Bz = field_z<T>(gx[t], gy[t], gz[t], lx, ly, lz, delta);
+            field_staged<MC>(br, bi, srf + (t - tstage) * MC, SEG * MC, pc, t, sp, Bx, By, Bz);
         };
 
         const int64_t nseg = nT / SEG;                      // checkpoint and workspace values are
-        T cx = T(0), cy = T(0), cz = T(0);                  // fetched a segment ahead (see K2b)
-        if (nseg > 0) {
-            const T* ck = a.Mck + ((nseg - 1) * rows + row) * 3;
-            cx = ck[0]; cy = ck[1]; cz = ck[2];
-        }
+        T cx = T(0), cy = T(0), cz = T(0);                  // fetched a segment ahead (ck_before)
+        if (nseg > 0) { const T* ck = ck_before(a.Mck, nseg, rows, row); cx = ck[0]; cy = ck[1]; cz = ck[2]; }
         for (int64_t seg = nseg - 1; seg >= 0; --seg) {
             const int64_t t0 = seg * SEG;
             // the segment's rf samples (SEG * MC <= 128 floats per part) -> LDS; the barrier at the
@@ -114,16 +100,14 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd_mc(FusedBwdArgsT<T, INJ
             }
             __syncthreads();
             T mx = cx, my = cy, mz = cz;
-            if (seg > 0) {
-                const T* ck = a.Mck + ((seg - 1) * rows + row) * 3;
-                cx = ck[0]; cy = ck[1]; cz = ck[2];
-            }
+            if (seg > 0) { const T* ck = ck_before(a.Mck, seg, rows, row); cx = ck[0]; cy = ck[1]; cz = ck[2]; }
             // the trajectory cotangents of this segment.  INJ == 2: at most one, at step ist of the segment (-1: none),
             // in registers, requested here and used in the sweep after the recompute.  INJ == 1: the lane's cotangent of
             // step st goes to the slots raw[(0|1|2) SEG + st][lane] that the sweep overwrites at that very step with
             // its own contributions -- the same lane reads it just before (lane-private: no barrier; the previous
             // segment's reduction released the tile at the barrier that ended it); zero where no record is taken.
             // No LDS beyond K2b's, no registers beyond the staging loads.
+            // (the staging and its injection are written out in both adjoints: shared helpers cost registers, LABNOTES)
             int ist = -1;
             T ijx = T(0), ijy = T(0), ijz = T(0);
             if constexpr (INJ == 2) {
@@ -161,29 +145,16 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd_mc(FusedBwdArgsT<T, INJ
             for (int c = 0; c < MC; ++c)
                 old[c] = (!first && wr_w && c < nC) ? dst0[2 * c * nT] : T(0);
             if (!first && wr_w) { oldg0 = *dg0; if (ri_w == 0) oldg2 = *dg2; }
-            T M0[SEG], M1[SEG], M2[SEG], Sv[SEG], Cv[SEG];
-#pragma unroll
-            for (int sb = 0; sb < SEG / 4; ++sb) {
-                T Bx[4], By[4], Bz[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) field(t0 + sb * 4 + j, Bx[j], By[j], Bz[j]);
-                Rot<T> r[4];
-                rot_prepare<T, CT, 4>(k, Bx, By, Bz, r);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    M0[sb * 4 + j] = mx; M1[sb * 4 + j] = my; M2[sb * 4 + j] = mz;
-                    Sv[sb * 4 + j] = r[j].S; Cv[sb * 4 + j] = r[j].C;     // reused by the sweep
-                    rot_apply<RELAX, T, CT>(k, r[j], mx, my, mz);
-                }
-            }
+            SegStates<T> h;
+            seg_recompute<RELAX>(k, t0, mx, my, mz, field, h);
 #pragma unroll
             for (int sb = SEG / 4 - 1; sb >= 0; --sb) {
                 T Bx[4], By[4], Bz[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) field(t0 + sb * 4 + j, Bx[j], By[j], Bz[j]);
                 RotAdj<T> ra[4];
-                const T S4[4] = {Sv[sb * 4], Sv[sb * 4 + 1], Sv[sb * 4 + 2], Sv[sb * 4 + 3]};
-                const T C4[4] = {Cv[sb * 4], Cv[sb * 4 + 1], Cv[sb * 4 + 2], Cv[sb * 4 + 3]};
+                const T S4[4] = {h.Sv[sb * 4], h.Sv[sb * 4 + 1], h.Sv[sb * 4 + 2], h.Sv[sb * 4 + 3]};
+                const T C4[4] = {h.Cv[sb * 4], h.Cv[sb * 4 + 1], h.Cv[sb * 4 + 2], h.Cv[sb * 4 + 3]};
                 rot_prepare_adj_given<T, CT, 4>(k, Bx, By, Bz, S4, C4, ra);
 #pragma unroll
                 for (int j = 3; j >= 0; --j) {
@@ -195,8 +166,7 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd_mc(FusedBwdArgsT<T, INJ
                         if (st == ist) adj_inject<RELAX, T, CT>(k, hx, hy, hz, ijx, ijy, ijz);
                     }
                     T g0, g1, g2;
-                    rot_apply_adj<RELAX, T, CT>(k, ra[j], M0[st], M1[st], M2[st], hx, hy, hz,
-                                                g0, g1, g2);
+                    rot_apply_adj<RELAX, T, CT>(k, ra[j], h.M0[st], h.M1[st], h.M2[st], hx, hy, hz, g0, g1, g2);
                     raw[red_idx(0 * SEG + st, lane)] = g0;   // lanes past nM: zero coefficients
                     raw[red_idx(1 * SEG + st, lane)] = g1;
                     raw[red_idx(2 * SEG + st, lane)] = g2;
@@ -267,31 +237,3 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd_mc(FusedBwdArgsT<T, INJ
         first = false;
     }
 }
-
-// Pass 2 for nQ = 3 + 2 nC quantities; grad_rf is (N, 2, nT, nC).
-template <typename T>
-__global__ __launch_bounds__(P2_T * P2_G) void k_bloch_rfgr_bwd_mc_p2(const T* work, T* grf, T* ggr,
-                                                                      int64_t N, int64_t nT,
-                                                                      int64_t P, int nC)
-{
-    __shared__ T part[P2_G][P2_T];
-    const int tl = threadIdx.x % P2_T, g = threadIdx.x / P2_T;
-    const int64_t t = (int64_t)blockIdx.x * P2_T + tl;
-    const int64_t q = blockIdx.y, n = blockIdx.z;
-    const int nQ = 3 + 2 * nC;
-    T acc = T(0);
-    if (t < nT)
-        for (int64_t w = g; w < P; w += P2_G) acc += work[((w * N + n) * nQ + q) * nT + t];
-    part[g][tl] = acc;
-    __syncthreads();
-    if (g != 0 || t >= nT) return;
-    T sum = part[0][tl];
-#pragma unroll
-    for (int i = 1; i < P2_G; ++i) sum += part[i][tl];
-    if (q < 3) { if (ggr) ggr[(n * 3 + q) * nT + t] = sum; }
-    else if (grf) {
-        const int64_t c = (q - 3) / 2, ri = (q - 3) % 2;
-        grf[((n * 2 + ri) * nT + t) * nC + c] = sum;
-    }
-}
-

@@ -2,7 +2,7 @@
 // Fragment: included INSIDE a translation unit's anonymous namespace, after host_common.hpp (HIP runtime,
 // include/mrphy_hip.h, geom.hpp, bloch_math.hpp, k_common.hpp).  Not a standalone header.
 #pragma once
-#include "k_fused_bwd_common.hpp"                             // red_idx / RED_PITCH, P2_T / P2_G
+#include "k_fused_common.hpp"
 
 // =============================================================================================
 // K2s: K2's step loop (one block = one wave = 64 spins of ONE batch entry, the pulse through scalar loads, the same
@@ -45,13 +45,7 @@ __global__ __launch_bounds__(WAVE) void k_signal_fwd(SignalArgs<T> a)
     const int64_t w = blockIdx.x, n = blockIdx.y;
     const int64_t nT = a.nT, rows = a.N * a.nM, nRec = a.nRec, every = a.every;
     const int64_t ntiles = (a.nM + WAVE - 1) / WAVE;
-    // read-only, wave-uniform pulse through the constant address space: scalar loads (see K2)
-    using CP = const T __attribute__((address_space(4)))*;
-    CP rfr = (CP)(a.in.rf + n * a.in.rf_sn);
-    CP rfi = rfr + nT;
-    CP gx = (CP)(a.in.gr + n * a.in.gr_sn);
-    CP gy = gx + nT;
-    CP gz = gy + nT;
+    const PulseCP<T> pc = pulse_cp<T>(a.in, n, nT, 1);
     // row sums: lane (r, h) forms chains 2h and 2h + 1 of row r = q SEG + slot; the two halves meet as
     // (p0 + p1) + (p2 + p3), K2b's order
     const int rr = lane >> 1, rh = lane & 1;
@@ -62,28 +56,24 @@ __global__ __launch_bounds__(WAVE) void k_signal_fwd(SignalArgs<T> a)
     bool first = true;
 
     for (int64_t tile = w; tile < ntiles; tile += a.P) {
-        const int64_t s_ = tile * WAVE + lane;
-        const bool valid = s_ < a.nM;
-        const int64_t s = valid ? s_ : a.nM - 1;
+        bool valid;
+        const int64_t s = lane_spin(tile, lane, a.nM, valid);
         const int64_t row = n * a.nM + s;
         const SpinConst<T, CT> k = load_consts<T, CT>(a.in.g, a.in.E1, a.in.E2, a.in.E1m1, n, s);
         T mx = a.Mi[row * 3], my = a.Mi[row * 3 + 1], mz = a.Mi[row * 3 + 2];
-        const T lx = a.in.loc[row * 3], ly = a.in.loc[row * 3 + 1], lz = a.in.loc[row * 3 + 2];
-        T delta = T(0);
-        if (a.in.df.p) delta = bc_load<T>(a.in.df, n, s) / bc_load<T>(a.in.gam, n, s);
-        T br = T(1), bi = T(0);
-        if (HB1 && a.in.b1) { br = a.in.b1[row * 2]; bi = a.in.b1[row * 2 + 1]; }
+        // (load_spin's loads, written out as in K2: through the helper the checkpoint builds gain an s_waitcnt, LABNOTES)
+        Spin<T> sp;
+        sp.lx = a.in.loc[row * 3]; sp.ly = a.in.loc[row * 3 + 1]; sp.lz = a.in.loc[row * 3 + 2];
+        sp.delta = T(0);
+        if (a.in.df.p) sp.delta = bc_load<T>(a.in.df, n, s) / bc_load<T>(a.in.gam, n, s);
+        T br, bi;
+        load_b1<HB1>(a.in.b1, row, br, bi);
         // lanes past nM (they hold a copy of the last valid spin) receive with weight zero: their two products are
         // exact zeros -- masked here, once per tile
         T rxr = valid ? T(1) : T(0), rxi = T(0);
         if (a.rx && valid) { rxr = a.rx[row * 2]; rxi = a.rx[row * 2 + 1]; }
 
-        auto field = [&](int64_t t, T& Bx, T& By, T& Bz) {
-            Bx = T(0); By = T(0);
-            if (HB1) field_xy_acc<T>(br, bi, rfr[t], rfi[t], Bx, By);
-            else     { Bx = rfr[t]; By = rfi[t]; }               // no b1 map: Bxy = rf (as K2 / K0)
-            Bz = field_z<T>(gx[t], gy[t], gz[t], lx, ly, lz, delta);
-        };
+        auto field = [&](int64_t t, T& Bx, T& By, T& Bz) { field_1coil<HB1>(br, bi, pc, t, sp, Bx, By, Bz); };
         int cnt = 0;                                             // records in the tile (wave-uniform)
         int64_t jbase = 0;                                       // records of this spin tile already reduced
         int64_t next = every - 1 < nT - 1 ? every - 1 : nT - 1;  // the step after which the next record is taken
@@ -124,10 +114,7 @@ __global__ __launch_bounds__(WAVE) void k_signal_fwd(SignalArgs<T> a)
         int64_t t0 = 0;
         for (; t0 + NS <= nT; t0 += NS) {
             if (cnt + maxrec > SEG) flush();
-            if (CK && t0 == ck_next) {
-                if (valid) { ckp[0] = mx; ckp[1] = my; ckp[2] = mz; }
-                ckp += ck_pitch; ck_next += a.ck_every;
-            }
+            if (CK) ck_store(t0, valid, mx, my, mz, ckp, ck_pitch, ck_next, a.ck_every);
             T Bx[NS], By[NS], Bz[NS];
 #pragma unroll
             for (int j = 0; j < NS; ++j) field(t0 + j, Bx[j], By[j], Bz[j]);
@@ -143,10 +130,7 @@ __global__ __launch_bounds__(WAVE) void k_signal_fwd(SignalArgs<T> a)
         }
         for (; t0 < nT; ++t0) {                                   // nT % NS tail
             if (cnt == SEG) flush();
-            if (CK && t0 == ck_next) {
-                if (valid) { ckp[0] = mx; ckp[1] = my; ckp[2] = mz; }
-                ckp += ck_pitch; ck_next += a.ck_every;
-            }
+            if (CK) ck_store(t0, valid, mx, my, mz, ckp, ck_pitch, ck_next, a.ck_every);
             T Bx[1], By[1], Bz[1];
             field(t0, Bx[0], By[0], Bz[0]);
             Rot<T> r[1];
@@ -159,25 +143,4 @@ __global__ __launch_bounds__(WAVE) void k_signal_fwd(SignalArgs<T> a)
         if (valid && a.Mo) { a.Mo[row * 3] = mx; a.Mo[row * 3 + 1] = my; a.Mo[row * 3 + 2] = mz; }
         first = false;
     }
-}
-
-// Pass 2: sig[n, q, j] = the sum of the P workspace rows in fixed order -- K2b's second pass (k_bloch_rfgr_bwd_p2:
-// 32 records x 8 row groups per block, the eight partial sums combined in group order) over 2 rows per batch entry.
-template <typename T>
-__global__ __launch_bounds__(P2_T * P2_G) void k_signal_p2(const T* work, T* sig, int64_t N, int64_t nRec, int64_t P)
-{
-    __shared__ T part[P2_G][P2_T];
-    const int tl = threadIdx.x % P2_T, g = threadIdx.x / P2_T;
-    const int64_t t = (int64_t)blockIdx.x * P2_T + tl;
-    const int64_t q = blockIdx.y, n = blockIdx.z;
-    T acc = T(0);
-    if (t < nRec)
-        for (int64_t w = g; w < P; w += P2_G) acc += work[((w * N + n) * 2 + q) * nRec + t];
-    part[g][tl] = acc;
-    __syncthreads();
-    if (g != 0 || t >= nRec) return;
-    T sum = part[0][tl];
-#pragma unroll
-    for (int i = 1; i < P2_G; ++i) sum += part[i][tl];
-    sig[(n * 2 + q) * nRec + t] = sum;
 }

@@ -13,16 +13,16 @@ int run_rfgr_bwd(const void* Mck, PulseOps in, const void* gMo, const void* gMt,
                  const void* gsig, void* gMi, void* grf, void* ggr, void* work, int64_t N, int64_t nM, int64_t nT,
                  hipStream_t st)
 {
-    if (N * nM * nT == 0) return 0;
-    if (N > 65535) return MRPHY_EINVAL;
+    dim3 grid;
+    int e;
+    if (!fused_grid(N * nM * nT, k2b_waves(nM), N, grid, e)) return e;
     // gsig (the cotangent of the signal's samples, with the receive map rx) selects the signal build, which may have no
     // gMo; its records are counted as the trajectory's
     FusedBwdSigArgs<T> a;
     static_cast<FusedBwdTrajArgs<T>&>(a) = fused_bwd_args<T>(Mck, in, gMo, gMt, every, gMi, work, N, nM, nT,
-                                                             k2b_waves(nM));
+                                                             grid.x);
     a.rx = (const T*)rx; a.gsig = (const T*)gsig;
     if (gsig) a.nRec = sig_records(nT, every);
-    const dim3 grid((unsigned)a.P, (unsigned)N);
 #define MRPHY_K2B(RX_, HB_, INJ_)                                                               \
     hipLaunchKernelGGL((k_bloch_rfgr_bwd<T, CT, RX_, HB_, INJ_>), grid, dim3(WAVE), 0, st, \
                        (static_cast<const FusedBwdArgsT<T, INJ_>&>(a)))
@@ -37,15 +37,9 @@ int run_rfgr_bwd(const void* Mck, PulseOps in, const void* gMo, const void* gMt,
     else       { if (in.E1.p) MRPHY_K2BT(true, false); else MRPHY_K2BT(false, false); }   // no b1 map: Bxy = rf
 #undef MRPHY_K2BT
 #undef MRPHY_K2B
-    int e = launch_status();
-    if (e) return e;
-    if (grf || ggr) {
-        hipLaunchKernelGGL((k_bloch_rfgr_bwd_p2<T>),
-                           dim3((unsigned)((nT + P2_T - 1) / P2_T), 5, (unsigned)N),
-                           dim3(P2_T * P2_G), 0, st, (const T*)work, (T*)grf, (T*)ggr, N, nT, a.P);
-        e = launch_status();
-    }
-    return e;
+    e = launch_status();
+    if (e || !(grf || ggr)) return e;
+    return launch_p2<T>(work, ggr, 3, grf, 1, N, nT, a.P, st);
 }
 
 }  // namespace mrphy_i

@@ -11,20 +11,19 @@ template <typename T, typename CT>
 int run_rfgr_fwd(const void* Mi, PulseOps in, void* Mo, void* Mck, int64_t ck_every, void* Mt, int64_t every,
                  int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st)
 {
-    // the plain kernel runs at nT == 0 too (it writes Mo = Mi); a trajectory then has no record
-    if (N * nM * (Mt ? nT : 1) == 0) return 0;
-    if (N > 65535) return MRPHY_EINVAL;
+    // (the empty problem and the batch limit: launch_k2)
     if constexpr (sizeof(T) == 4) {
         if (nC == 1) return run_rfgr_fwd1<T, CT>(Mi, in, Mo, Mck, ck_every, Mt, every, N, nM, nT, nC, st);
     }
     const FusedTrajArgs<T> a = fused_args<T>(Mi, in, Mo, Mck, ck_every, Mt, every, N, nM, nT, nC);
     const void* b1 = in.b1;
-#define MRPHY_K2C(NCM_) launch_k2<T, CT, NCM_, true>(a, st)
+    int e = 0;
+#define MRPHY_K2C(NCM_) e = launch_k2<T, CT, NCM_, true>(a, st)
     // the smallest register/LDS coil capacity that holds nC (each build sizes its b1 registers and
     // its LDS rf buffer for exactly that capacity: never launch one with more coils than it holds)
     // (one coil in float: tu_fused_fwd1.hip, above)
     if (nC == 1 && b1) { if constexpr (sizeof(T) == 8) MRPHY_K2C(1); }
-    else if (nC == 1) { if constexpr (sizeof(T) == 8) launch_k2<T, CT, 1, false>(a, st); }   // no b1 map: Bxy = rf, no complex product
+    else if (nC == 1) { if constexpr (sizeof(T) == 8) e = launch_k2<T, CT, 1, false>(a, st); }   // no b1 map: Bxy = rf, no complex product
     else if (nC <= 2 && b1) MRPHY_K2C(2);                // (round 3: 2 coils no longer pay for 8)
     else if (nC <= 4 && b1) MRPHY_K2C(4);
     else if (nC <= 8 && b1) MRPHY_K2C(8);
@@ -37,7 +36,7 @@ int run_rfgr_fwd(const void* Mi, PulseOps in, void* Mo, void* Mck, int64_t ck_ev
     // double precision; the host routes those to rfgr2beff + blochsim, and a direct caller gets the generic build)
     else MRPHY_K2C(0);
 #undef MRPHY_K2C
-    return launch_status();
+    return e;
 }
 
 }  // namespace mrphy_i

@@ -19,9 +19,8 @@ int run_rfgr_fwd1(const void* Mi, PulseOps in, void* Mo, void* Mck, int64_t ck_e
         return MRPHY_EINVAL;                             // fp64 stays in tu_fused_fwd.hip
     } else {
         const FusedTrajArgs<T> a = fused_args<T>(Mi, in, Mo, Mck, ck_every, Mt, every, N, nM, nT, nC);
-        if (in.b1) launch_k2<T, CT, 1, true>(a, st);
-        else    launch_k2<T, CT, 1, false>(a, st);       // no b1 map: Bxy = rf, no complex product
-        return launch_status();
+        if (in.b1) return launch_k2<T, CT, 1, true>(a, st);
+        return launch_k2<T, CT, 1, false>(a, st);        // no b1 map: Bxy = rf, no complex product
     }
 }
 

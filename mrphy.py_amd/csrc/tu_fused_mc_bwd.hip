@@ -11,10 +11,10 @@ template <typename T, typename CT>
 int run_rfgr_mc_bwd(const void* Mck, PulseOps in, const void* gMo, const void* gMt, int64_t every, void* gMi, void* grf,
                     void* ggr, void* work, int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st)
 {
-    if (N * nM * nT == 0) return 0;
-    if (N > 65535) return MRPHY_EINVAL;
-    const FusedBwdTrajArgs<T> a = fused_bwd_args<T>(Mck, in, gMo, gMt, every, gMi, work, N, nM, nT, k2b_mc_waves(nM));
-    const dim3 grid((unsigned)a.P, (unsigned)N);
+    dim3 grid;
+    int e;
+    if (!fused_grid(N * nM * nT, k2b_mc_waves(nM), N, grid, e)) return e;
+    const FusedBwdTrajArgs<T> a = fused_bwd_args<T>(Mck, in, gMo, gMt, every, gMi, work, N, nM, nT, grid.x);
 #define MRPHY_K2BMC(RX_, MC_, INJ_)                                                                 \
     hipLaunchKernelGGL((k_bloch_rfgr_bwd_mc<T, CT, RX_, MC_, INJ_>), grid, dim3(WAVE), 0, st, \
                        (static_cast<const FusedBwdArgsT<T, INJ_>&>(a)), (int)nC)
@@ -35,16 +35,9 @@ int run_rfgr_mc_bwd(const void* Mck, PulseOps in, const void* gMo, const void* g
 #undef MRPHY_K2BMCR
 #undef MRPHY_K2BMCT
 #undef MRPHY_K2BMC
-    int e = launch_status();
-    if (e) return e;
-    if (grf || ggr) {
-        hipLaunchKernelGGL((k_bloch_rfgr_bwd_mc_p2<T>),
-                           dim3((unsigned)((nT + P2_T - 1) / P2_T), (unsigned)(3 + 2 * nC), (unsigned)N),
-                           dim3(P2_T * P2_G), 0, st, (const T*)work, (T*)grf, (T*)ggr, N, nT, a.P,
-                           (int)nC);
-        e = launch_status();
-    }
-    return e;
+    e = launch_status();
+    if (e || !(grf || ggr)) return e;
+    return launch_p2<T>(work, ggr, 3, grf, nC, N, nT, a.P, st);
 }
 
 }  // namespace mrphy_i

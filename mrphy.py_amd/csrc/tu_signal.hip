@@ -12,14 +12,14 @@ template <typename T, typename CT>
 int run_signal_fwd(const void* Mi, PulseOps in, const void* rx, void* Mo, void* Mck, int64_t ck_every, void* sig,
                    int64_t every, void* work, int64_t N, int64_t nM, int64_t nT, hipStream_t st)
 {
-    if (N * nM * nT == 0) return 0;
-    if (N > 65535) return MRPHY_EINVAL;
+    dim3 grid;
+    int e;
+    if (!fused_grid(N * nM * nT, sig_waves(nM), N, grid, e)) return e;
     SignalArgs<T> a;
     a.Mi = (const T*)Mi; a.in = typed<T>(in); a.rx = (const T*)rx; a.Mo = (T*)Mo; a.Mck = (T*)Mck;
     a.ck_every = ck_every > 0 ? ck_every : 1;
     a.work = (T*)work; a.every = every; a.nRec = sig_records(nT, every);
-    a.N = N; a.nM = nM; a.nT = nT; a.P = sig_waves(nM);
-    const dim3 grid((unsigned)a.P, (unsigned)N);
+    a.N = N; a.nM = nM; a.nT = nT; a.P = grid.x;
 #define MRPHY_K2S(CK_, RX_, HB_, EV_) \
     hipLaunchKernelGGL((k_signal_fwd<T, CT, CK_, RX_, HB_, EV_>), grid, dim3(WAVE), 0, st, a)
 #define MRPHY_K2S_EV(CK_, RX_, HB_)                                                              \
@@ -36,11 +36,9 @@ int run_signal_fwd(const void* Mi, PulseOps in, const void* rx, void* Mo, void* 
 #undef MRPHY_K2S_HB
 #undef MRPHY_K2S_EV
 #undef MRPHY_K2S
-    int e = launch_status();
+    e = launch_status();
     if (e) return e;
-    hipLaunchKernelGGL((k_signal_p2<T>), dim3((unsigned)((a.nRec + P2_T - 1) / P2_T), 2, (unsigned)N),
-                       dim3(P2_T * P2_G), 0, st, (const T*)work, (T*)sig, N, a.nRec, a.P);
-    return launch_status();
+    return launch_p2<T>(work, nullptr, 0, sig, 1, N, a.nRec, a.P, st);   // sig (N, 2, nRec): one coil's (re, im)
 }
 
 }  // namespace mrphy_i

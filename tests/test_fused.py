@@ -69,6 +69,54 @@ def test_fused_adjoint(tag, variant):
     assert max_abs(r2.grad, fu[2]) == 0.0 and max_abs(g2.grad, fu[3]) == 0.0
 
 
+def test_ptx_adjoint_wave_takes_a_second_tile():
+    r"""More spin tiles (2050) than the pTx adjoint has persistent waves (2048): waves 0 and 1 take a second tile and
+    add its sums to the workspace rows of their first (`first == false`, `old[c]` in k_bloch_rfgr_bwd_mc) -- the plain
+    kernel and the per-step injection of the trajectory (every = 1).  fp32 precise, 2 coils, one segment, a ragged last
+    tile.  Against the two-kernel route with test_fused_adjoint's gates: grad_Mi bit for bit (the trajectory's, whose
+    records enter the t-state rounded, to the fp32 gate), the pulse gradients to the fp32 gate; twice the same bits."""
+    N, nM, nT, nC = 1, 2048 * 64 + 100, 16, 2
+    gen = torch.Generator().manual_seed(31)
+    rnd = lambda *s: torch.rand(s, generator=gen, dtype=torch.float64).float()  # noqa: E731
+    M0, loc, df = dev(rnd(N, nM, 3)), dev((rnd(N, nM, 3) * 2 - 1) * 6), dev((rnd(N, nM) * 2 - 1) * 200)
+    rf, gr = dev((rnd(N, 2, nT, nC) * 2 - 1) * 1.5), dev(rnd(N, 3, nT) * 2 - 1)
+    b1 = dev((rnd(N, nM, 2, nC) * 2 - 1) * 0.7)
+    kw = dict(T1=dev(0.5 + rnd(N, nM)), T2=dev(0.02 + 0.1 * rnd(N, nM)), γ=dev(torch.tensor(4257.6)),
+              dt=dev(torch.tensor([4e-6])))
+    w = dev(torch.sin(torch.arange(N * nM * nT * 3, dtype=torch.float64) * 0.61 + 1).float().reshape(N, nM, nT, 3))
+
+    def run(kind, traj):
+        Mi, r, g = (x.clone().requires_grad_(True) for x in (M0, rf, gr))
+        if kind == 'two':
+            be = beffective.rfgr2beff(r, g, loc, Δf=df, b1Map=b1, γ=kw['γ'])
+            if traj:                                           # M after every step: one-step runs of K1
+                Ms, M = [], Mi
+                for t in range(nT):
+                    M = sims.blochsim(M, be[:, :, t:t + 1], **kw)
+                    Ms.append(M)
+                out = torch.stack(Ms, dim=-2)
+            else:
+                out = sims.blochsim(Mi, be, **kw)
+        elif traj:
+            out = fused.blochsim_rfgr_traj(Mi, r, g, loc, every=1, Δf=df, b1Map=b1, γ_beff=kw['γ'], **kw)
+        else:
+            out = fused.blochsim_rfgr(Mi, r, g, loc, Δf=df, b1Map=b1, γ_beff=kw['γ'], **kw)
+        (out * (w if traj else w[..., -1, :])).sum().backward()
+        return Mi.grad, r.grad, g.grad
+
+    with mrphy_amd.precision('precise'):
+        for traj in (False, True):
+            fu, two, again = run('fused', traj), run('two', traj), run('fused', traj)
+            if traj:
+                assert_close(fu[0], two[0], 'f32', 'trajectory grad_Mi vs two-kernel')
+            else:
+                assert max_abs(fu[0], two[0]) == 0.0           # same states, same adjoint arithmetic
+            assert_close(fu[1], two[1], 'f32', f'grad_rf vs two-kernel (traj={traj})')
+            assert_close(fu[2], two[2], 'f32', f'grad_gr vs two-kernel (traj={traj})')
+            for a, b in zip(fu, again):
+                assert max_abs(a, b) == 0.0                    # deterministic reduction over two tiles per row
+
+
 @pytest.mark.usefixtures('host_constants')
 def test_config5_interpT_forward_backward():
     r"""64^3 x 2048 after interpT (configs[4]): fine pulse = the reference's own interpT output

@@ -1,9 +1,25 @@
 """The VALU-bound kernels for several builds of the library, one child process each, twice (alternating):
     python tools/ab_libs_valu.py LIB_A.so LIB_B.so ...
 fp32 precise: fused forward K2 (64^3 x 2048, 128^3 x 1024), fused forward + adjoint K2 + K2b (64^3 x 2048), 8 transmit coils
-fused forward + adjoint (64^3 x 1024); fp64: K2 and K2 + K2b (64^3 x 1024).  Norms printed to compare bits."""
+fused forward + adjoint (64^3 x 1024); fp64: K2 and K2 + K2b (64^3 x 1024).  Norms printed to compare bits.
+    python tools/ab_libs_valu.py --bits LIB_A.so LIB_B.so ...
+no timing: the integer-view sums of the outputs and of grad_Mi, grad_rf, grad_gr of fused.blochsim_rfgr_traj (every 1, 5,
+16; one coil and 2 coils) and fused.signal_rfgr (every 1, 16, with a receive map) at 2048 * 64 + 100 spins x 48 steps --
+a ragged last tile and more tiles than the adjoints have persistent waves -- in fp32 precise and fp64, one child process
+per library; the last line says whether every library gave the same sums."""
 import os, subprocess, sys
-if len(sys.argv) >= 3 and sys.argv[1] != '--child':
+if len(sys.argv) >= 2 and sys.argv[1] == '--bits':
+    if len(sys.argv) < 4:
+        sys.exit('--bits compares libraries: give at least two')
+    outs = []
+    for lib in sys.argv[2:]:
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), '--child-bits', lib], capture_output=True, text=True)
+        outs.append(r.stdout.strip() if r.returncode == 0 else None)
+        print(os.path.basename(lib) + ':\n' + (outs[-1] if outs[-1] is not None else 'FAILED ' + r.stderr[-600:]), flush=True)
+    same = outs[0] is not None and all(o == outs[0] for o in outs)
+    print('fingerprints EQUAL' if same else 'fingerprints DIFFER')
+    sys.exit(0 if same else 1)
+if len(sys.argv) >= 3 and not sys.argv[1].startswith('--child'):
     for rep in range(2):
         for lib in sys.argv[1:]:
             r = subprocess.run([sys.executable, os.path.abspath(__file__), '--child', lib], capture_output=True, text=True)
@@ -17,6 +33,38 @@ from mrphy_amd import _lib, fused, synth
 _lib.library_path = lambda: os.path.abspath(lib)
 dev = torch.device('cuda', 0)
 ev = lambda: torch.cuda.Event(enable_timing=True)
+bits = lambda x: int(x.contiguous().view(torch.int32 if x.dtype == torch.float32 else torch.int64).to(torch.int64).sum())  # noqa: E731
+
+
+def fingerprints():
+    nM, nT = 2048 * 64 + 100, 48
+    for dt, mode in ((torch.float32, 'precise'), (torch.float64, 'fast')):
+        g = torch.Generator(device='cpu').manual_seed(11)
+        rnd = lambda *sh: torch.rand(sh, generator=g, dtype=torch.float64).to(dt).to(dev)  # noqa: E731
+        M0, loc, df = rnd(1, nM, 3), (rnd(1, nM, 3) * 2 - 1) * 6, (rnd(1, nM) * 2 - 1) * 200
+        kw = dict(Δf=df, T1=0.5 + rnd(1, nM), T2=0.02 + 0.1 * rnd(1, nM), γ=torch.tensor(4257.6, dtype=dt, device=dev),
+                  dt=torch.tensor([4e-6], dtype=dt, device=dev))
+        kw['γ_beff'] = kw['γ']
+        gr, rxm = rnd(1, 3, nT) * 2 - 1, rnd(1, nM, 2) * 2 - 1
+        cases = [(f'traj every={e} nC={nC}', nC, e, None) for nC in (1, 2) for e in (1, 5, 16)] + \
+                [(f'signal every={e}', 1, e, rxm) for e in (1, 16)]
+        with mrphy_amd.precision(mode):
+            for label, nC, every, rx in cases:
+                rf = (rnd(1, 2, nT) * 2 - 1) * 3 if nC == 1 else (rnd(1, 2, nT, nC) * 2 - 1) * 1.5
+                b1 = rnd(1, nM, 2) * 2 - 1 if nC == 1 else (rnd(1, nM, 2, nC) * 2 - 1) * 0.7
+                Mi, r_, g_ = (x.clone().requires_grad_(True) for x in (M0, rf, gr))
+                if rx is None:
+                    outs = (fused.blochsim_rfgr_traj(Mi, r_, g_, loc, every=every, b1Map=b1, **kw),)
+                else:
+                    outs = fused.signal_rfgr(Mi, r_, g_, loc, every=every, rx=rx, return_Mo=True, b1Map=b1, **kw)
+                sum((o * torch.sin(torch.arange(o.numel(), device=dev) * 0.61 + 1).to(dt).reshape(o.shape)).sum() for o in outs).backward()
+                print(f'{str(dt)[6:]} {mode} {label}: out {" ".join(str(bits(o.detach())) for o in outs)} '
+                      f'gMi {bits(Mi.grad)} grf {bits(r_.grad)} ggr {bits(g_.grad)}', flush=True)
+
+
+if sys.argv[1] == '--child-bits':
+    fingerprints()
+    sys.exit(0)
 
 
 def t_of(fn, reps=6, inner=6):
@@ -56,7 +104,6 @@ for label, dt, n, nT, nC in (('f32 64^3x2048', torch.float32, 64, 2048, 1), ('f3
         r_, g_ = rf.clone().requires_grad_(True), p['gr'].clone().requires_grad_(True)
         Mo_ = f(r_, g_)
         t_b, _ = t_of(lambda: torch.autograd.grad(Mo_, (r_, g_), torch.ones_like(Mo_), retain_graph=True), 5, 3)
-        bits = lambda x: int(x.contiguous().view(torch.int32 if x.dtype == torch.float32 else torch.int64).to(torch.int64).sum())  # noqa: E731
         r2_, g2_ = rf.clone().requires_grad_(True), p['gr'].clone().requires_grad_(True)
         M2_ = sp['M0'].clone().requires_grad_(True)
         fused.blochsim_rfgr(M2_, r2_, g2_, sp['loc'], Δf=sp['Δf'], γ_beff=sp['γ'], b1Map=b1, **kw).sum().backward()

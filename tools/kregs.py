@@ -2,10 +2,15 @@
 unit objects `mrphy_amd.build()` leaves under mrphy.py_amd/build/ (no recompilation):
 
     python tools/kregs.py [filter] [--scratch] [--objdir DIR]
+    python tools/kregs.py [filter] --diff DIR_A DIR_B
 
 `--scratch` lists only kernels with a private segment (spills); the exit code is then the number found.
 `--objdir DIR` reads the unit objects of another build instead.
+`--diff` compares two builds kernel by kernel (by unit object and kernel name): the register / LDS / scratch figures
+and the count of every opcode of the disassembly; it names each kernel that differs with the opcodes and counts, and
+the kernels only one build has.  The exit code is the number of kernels whose figures differ.
 """
+import collections
 import glob
 import os
 import re
@@ -17,9 +22,11 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')
 LLVM = os.path.join(os.environ.get('ROCM_PATH', '/opt/rocm'), 'lib', 'llvm', 'bin')
 
 
-def kernels(objdir):
-    r"""[(object, demangled kernel name, {metadata})] for every kernel of every unit object in `objdir`."""
-    out = []
+def kernels(objdir, flt=None):
+    r"""[(object, demangled kernel name, {metadata})] for every kernel of every unit object in `objdir`.  With a
+    filter `flt` on the demangled name the metadata also holds the kernel's instructions ('text': the lines of the
+    disassembly) and their opcode counts ('ops')."""
+    out, asm = [], {}
     with tempfile.TemporaryDirectory(prefix='kregs_') as d:
         for obj in sorted(glob.glob(os.path.join(objdir, '*.o'))):
             b = os.path.basename(obj)
@@ -34,13 +41,61 @@ def kernels(objdir):
                     out.append((b, g('name'), {k: int(g(k)) for k in (
                         'vgpr_count', 'sgpr_count', 'group_segment_fixed_size', 'private_segment_fixed_size',
                         'vgpr_spill_count')}))
+                if flt is not None:
+                    dis = subprocess.run([os.path.join(LLVM, 'llvm-objdump'), '-d', '--no-show-raw-insn',
+                                          '--no-leading-addr', co], check=True, capture_output=True, text=True).stdout
+                    for blk in re.split(r'\n(?=\S* ?<[^>]+>:\n)', dis)[1:]:
+                        head, *lines = blk.splitlines()
+                        asm[(b, re.search(r'<([^>]+)>', head).group(1))] = [
+                            ln.split('//')[0].strip() for ln in lines
+                            if ln.startswith(('\t', ' ')) and ln.strip() and ln.strip() != '...']   # '...': padding
     names = subprocess.run(['c++filt'] + [k[1] for k in out], capture_output=True, text=True).stdout.splitlines()
-    return [(o, n.replace('(anonymous namespace)::', '').replace('mrphy::', '').replace('void ', '').split('(')[0], m)
-            for (o, _, m), n in zip(out, names)]
+    res = []
+    for (o, mangled, m), n in zip(out, names):
+        n = n.replace('(anonymous namespace)::', '').replace('mrphy::', '').replace('void ', '').split('(')[0]
+        if flt is not None and flt in n:
+            m['text'] = asm[(o, mangled)]
+            m['ops'] = collections.Counter(ln.split()[0] for ln in m['text'])
+        res.append((o, n, m))
+    return res
+
+
+FIGURES = ('vgpr_count', 'sgpr_count', 'group_segment_fixed_size', 'private_segment_fixed_size')
+
+
+def diff(dir_a, dir_b, flt):
+    r"""Compare the kernels of two builds whose name holds `flt`; returns how many differ in a register figure."""
+    a, b = ({(o, n): m for o, n, m in kernels(d, flt) if flt in n} for d in (dir_a, dir_b))
+    both = sorted(set(a) & set(b))
+    same_text = [k for k in both if a[k]['text'] == b[k]['text']]
+    same_ops = [k for k in both if a[k]['ops'] == b[k]['ops']]
+    bad = 0
+    for k in both:
+        fa, fb = ([m[k][f] for f in FIGURES] for m in (a, b))
+        if fa != fb:
+            bad += 1
+            print(f'FIGURES {k[1]} [{k[0]}]: vgpr/sgpr/lds/scratch {fa} -> {fb}')
+        if a[k]['ops'] != b[k]['ops']:
+            d = {op: (a[k]['ops'][op], b[k]['ops'][op]) for op in sorted(set(a[k]['ops']) | set(b[k]['ops']))
+                 if a[k]['ops'][op] != b[k]['ops'][op]}
+            print(f'OPCODES {k[1]} [{k[0]}]: ' + ', '.join(f'{op} {x} -> {y}' for op, (x, y) in d.items()))
+    for tag, only in (('only in A', sorted(set(a) - set(b))), ('only in B', sorted(set(b) - set(a)))):
+        for k in only:
+            m = (a if k in a else b)[k]
+            print(f'{tag}: {k[1]} [{k[0]}] vgpr/sgpr/lds/scratch {[m[f] for f in FIGURES]} '
+                  f'{sum(m["ops"].values())} instructions')
+    print(f'{len(both)} kernels compared: {len(same_text)} with identical text, {len(same_ops)} with an identical '
+          f'opcode histogram, {bad} with other register / LDS / scratch figures; scratch > 0 in B: '
+          f'{sum(1 for m in b.values() if m["private_segment_fixed_size"])}')
+    return bad
 
 
 if __name__ == '__main__':
     args = [a for a in sys.argv[1:] if not a.startswith('--')]
+    if '--diff' in sys.argv:
+        i = sys.argv.index('--diff')
+        dirs = sys.argv[i + 1:i + 3]
+        sys.exit(diff(dirs[0], dirs[1], ([a for a in args if a not in dirs] or [''])[0]))
     objdir = os.path.join(ROOT, 'mrphy.py_amd', 'build')
     if '--objdir' in sys.argv:
         objdir = sys.argv[sys.argv.index('--objdir') + 1]

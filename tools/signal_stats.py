@@ -112,12 +112,18 @@ def summarize(d, plan):
     for (cfg, e), (_, ours) in zip(plan, procs):
         if cfg in ('comp', 'compb'):
             continue
-        by = {}
-        for r in ours:
+        # both directions end in the same second pass (k_bloch_rfgr_p2): a launch of it belongs to the main kernel that
+        # ran before it, and is listed under that kernel's direction
+        by, after = {}, ''
+        fwd = lambda k: '_fwd' in k  # noqa: E731
+        for r in sorted(ours, key=lambda r: int(r['Start_Timestamp'])):
             name = r['Kernel_Name'].replace('(anonymous namespace)::', '').replace('void ', '').split('(')[0]
+            if '_p2' in name:
+                name += after
+            else:
+                after = ' after_fwd' if fwd(name) else ' after_bwd'
             by.setdefault(name, []).append((int(r['End_Timestamp']) - int(r['Start_Timestamp'])) * 1e-6)
         ks = {k: dict(calls=len(v), median_ms=statistics.median(v), min_ms=min(v)) for k, v in by.items()}
-        fwd = lambda k: '_fwd' in k or 'k_signal' in k  # noqa: E731
         mine = [k for k in ks if fwd(k) == (cfg in FWD)]
         rec = dict(cfg=cfg, every=e or None, kernels=ks,
                    main_ms=sum(ks[k]['median_ms'] for k in mine if '_p2' not in k),
