@@ -69,6 +69,18 @@ def _backward_prep(lib, p, code, needs, dtype, device):
     return grads, tuple(None if x is None else x.data_ptr() for x in grads), work
 
 
+def _empty_problem_grads(grads, gMo):
+    r"""No spin or no step (``N·nM·nT == 0``): the library's adjoints are no-ops then (``include/mrphy_hip.h``: an empty
+    problem is a success that writes nothing), so the gradients are written here -- ``Mo`` is ``Mi`` (``gMo``: its
+    cotangent, or ``None``) and nothing depends on the pulse."""
+    gMi, g_rf, g_gr = grads
+    if gMi is not None:
+        gMi.zero_() if gMo is None else gMi.copy_(gMo.reshape(gMi.shape))
+    for g in (g_rf, g_gr):
+        if g is not None:
+            g.zero_()
+
+
 def _fold_grads(gMi, g_rf, g_gr, p, rf_shape, gr_shape, rf_dtype, gr_dtype):
     r"""``(grad_Mi, grad_rf, grad_gr)`` in the shapes and dtypes the caller's ``rf`` and ``gr`` had."""
     from .beffective import _fold_pulse_grad
@@ -124,6 +136,9 @@ class BlochSimRfGrHIP(Function):
         gM = grad_M.to(dtype).contiguous()      # the trajectory's: time-major, as the forward returned it -- free if so
         grads, outs, work = _backward_prep(lib, p, code, needs, dtype, device)
         tr = (every,) if traj else ()
+        if p.N * p.nM * p.nT == 0:
+            _empty_problem_grads(grads, None if traj else gM)
+            return (*_fold_grads(*grads, p, rf_shape, gr_shape, rf_dtype, gr_dtype), *(None,) * 7)
         if p.nC == 1:
             name, nc = ('mrphy_blochsim_rfgr_traj_bwd' if traj else 'mrphy_blochsim_rfgr_bwd'), ()
         else:                                   # parallel transmit
@@ -157,6 +172,8 @@ class SignalRfGrHIP(Function):
         work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
         if p.nT == 0:
             Mo.copy_(Mi_c)                      # no step, no record
+        if p.N * p.nM * p.nT == 0:
+            sig.zero_()                         # no spin: empty sums (the library writes nothing for an empty problem)
         with torch.cuda.device(device):
             rc = lib.mrphy_signal_rfgr_fwd(code, Mi_c.data_ptr(), *p.k0_args(), *consts, Mo.data_ptr(), *ckpt,
                                            sig.data_ptr(), every, work.data_ptr(), work.numel(),
@@ -182,6 +199,9 @@ class SignalRfGrHIP(Function):
         gM = None if grad_Mo is None else grad_Mo.to(dtype).contiguous()
         grads, outs, work = _backward_prep(lib, p, code, needs, dtype, device)      # one transmit coil: K2b's workspace
         ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        if p.N * p.nM * p.nT == 0:
+            _empty_problem_grads(grads, gM)
+            return (*_fold_grads(*grads, p, rf_shape, gr_shape, rf_dtype, gr_dtype), *(None,) * 8)
         with torch.cuda.device(device):
             rc = lib.mrphy_signal_rfgr_bwd(code, Mck.data_ptr(), *p.k0_args(), *consts, ptr(gM), ptr(gs), every,
                                            *outs, work.data_ptr(), work.numel(),
@@ -234,9 +254,10 @@ def _route(Mi, rf, gr, loc, every, kw, signal=False, rx=None):
     want = pulse_grad and fused_adjoint_ok
     if signal:
         # one launch per receive coil ((N, *Nd, xy, nRx) -> nRx maps (N, nM, xy)); no rx: the plain sums
+        # (the coil count spelled out: a `-1` is ambiguous for a map without spins, nM == 0)
         rxs = [None] if rx is None else \
             list(rx.detach().to(device=device, dtype=dtype).expand((p.N,) + p.Nd + tuple(rx.shape[1 + len(p.Nd):]))
-                 .reshape(p.N, p.nM, 2, -1).unbind(-1))
+                 .reshape(p.N, p.nM, 2, rx.shape[-1] if rx.ndim == Mi.ndim + 1 else 1).unbind(-1))
         return 'fused', [SignalRfGrHIP.apply(Mi, rf, gr, p, None if r is None else r.contiguous(), γ2πdt, E1, E2, E1_1,
                                              want, every) for r in rxs]
     return 'fused', BlochSimRfGrHIP.apply(Mi, rf, gr, p, γ2πdt, E1, E2, E1_1, want, every)

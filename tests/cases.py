@@ -235,6 +235,10 @@ def fused_dense(v: dict):
         b = v['b1Map']
         tail = tuple(b.shape[lead:])
         out['b1Map'] = b.expand((N,) + Nd + tail).reshape((N, nM) + tail).contiguous()
+    if v.get('rx') is not None:           # the receive map of fused.signal_rfgr: the layout of b1Map
+        r = v['rx']
+        tail = tuple(r.shape[lead:])
+        out['rx'] = r.expand((N,) + Nd + tail).reshape((N, nM) + tail).contiguous()
     for k in ('M0', 'loc', 'w'):
         out[k] = v[k].expand((N,) + Nd + (3,)).reshape(N, nM, 3).contiguous()
     for k in ('rf', 'gr'):
@@ -247,7 +251,11 @@ def fused_operand_variants(dtype, nC: int, nT: int = 48, seed: int = 29):
     r"""One problem class, many spellings: ``{name: (as_given, dense)}`` for ``fused.blochsim_rfgr`` / ``_traj``.
     N = 2, 140 spins per batch entry, ``nC`` in :data:`FUSED_COILS`.  A variant is a dict ``M0, rf, gr, loc, Δf, b1Map,
     γ_beff, T1, T2, γ, dt`` and the loss cotangent ``w``; ``dense`` is :func:`fused_dense` of it.  CPU tensors; a view
-    keeps its strides and storage offset on a device through ``tests/gpu_common.py: place``."""
+    keeps its strides and storage offset on a device through ``tests/gpu_common.py: place``.
+
+    ``rx``: the receive map of ``fused.signal_rfgr``, one spelling per variant (batch-1, absent, stride-0, three coils on
+    the grid, one weight per plane, fp64 meant to stay on the CPU, a permuted view, off the 16-B grid).  It is drawn from
+    a generator of its own, so the other operands keep the bits ``golden/fusedops_*.npz`` was recorded on."""
     assert nC in FUSED_COILS
     gen = torch.Generator(device='cpu').manual_seed(seed + 100 * nC + nT)
     u = lambda *s: torch.rand(s, generator=gen, dtype=torch.float64)        # noqa: E731
@@ -267,6 +275,8 @@ def fused_operand_variants(dtype, nC: int, nT: int = 48, seed: int = 29):
     wt = lambda *s: c(u(*s, 3) * 2 - 1)                                      # noqa: E731
     dt1 = tensor([dt0_val], dtype=dtype)
     dtN = c(dt0_val * (1 + u(N)))
+    gen_rx = torch.Generator(device='cpu').manual_seed(7919 + seed + 100 * nC + nT)
+    rx64 = lambda *s: torch.rand(s, generator=gen_rx, dtype=torch.float64) * 2 - 1   # noqa: E731
     v = {}
     v['compact_mixed'] = dict(M0=M0(N, nM), rf=rf(1), gr=gr(N), loc=loc(N, nM), Δf=df(N, 1), γ_beff=gm(1, nM),
                               b1Map=b1(1, nM, coil=nC > 1), T1=t1(N, 1), T2=t2(N, 1), γ=gm(1, nM), dt=dtN, w=wt(N, nM))
@@ -292,6 +302,14 @@ def fused_operand_variants(dtype, nC: int, nT: int = 48, seed: int = 29):
     v['offset'] = dict(M0=_after(M0(N, nM)), rf=_after(rf(N)), gr=_after(gr(N)), loc=_after(loc(N, nM)), Δf=df(N, nM),
                        γ_beff=gm(1, 1), b1Map=b1(N, nM), T1=t1(N, nM), T2=t2(N, nM), γ=gm(1, 1), dt=dt1,
                        w=_after(wt(N, nM)))
+    v['compact_mixed']['rx'] = c(rx64(1, nM, 2))                             # broadcast over the batch
+    v['scalars']['rx'] = None                                                # the plain sums of Mx, My
+    v['expanded']['rx'] = c(rx64(N, 1, 2)).expand(N, nM, 2)                  # stride 0 over the spins
+    v['cube']['rx'] = c(rx64(N, *Nd, 2, 3))                                  # three receive coils on the grid
+    v['cube_planes']['rx'] = c(rx64(1, 5, 1, 1, 2))                          # one weight per plane
+    v['gamma_split']['rx'] = rx64(N, nM, 2)                                  # fp64 whatever `dtype`; the tests leave it on the CPU
+    v['views']['rx'] = c(rx64(2, nM, N)).permute(2, 1, 0)
+    v['offset']['rx'] = _after(c(rx64(N, nM, 2)))
     return {k: (d, fused_dense(d)) for k, d in v.items()}
 
 

@@ -8,6 +8,7 @@ fp32, ``grad_Mi`` against the two-kernel route cut at the same step, see ``_inva
 (``tests/util.py``) of the CPU oracle on the operands as given, and of the reference's own recorded outputs
 (``golden/fusedops_*.npz``) where the reference accepts the form; (4) a second run gives the same bits.  ``precision('fast')`` is held to (1), (2) and (4); its
 distance to the oracle goes to the ledger (``fusedops.*``) -- the project has no small-problem bound for it.
+``fused.signal_rfgr`` on the same cases, each with a receive map: ``test_signal_operands.py``.
 """
 import pytest
 
@@ -31,11 +32,12 @@ def _cotangent(v, every, nT):
     return v['w'].unsqueeze(-2) * c[:, None]
 
 
-def _run(route, v, every=None, consts=None, sim=None, cut=None):
+def _run(route, v, every=None, consts=None, sim=None, cut=None, cot=None):
     r"""``out, grad_Mi, grad_rf, grad_gr`` of ``<cotangent, out>``; ``out`` is ``Mo`` (``every = None``) or the trajectory
     `(N, *Nd, nRec, 3)`.  ``route``: 'fused' (``fused.blochsim_rfgr[_traj]``), 'two' (``rfgr2beff`` + ``sims.blochsim``,
     one call per record segment for a trajectory; with ``cut``, ``Mo`` by two such calls, steps ``[0, cut)`` and
-    ``[cut, nT)``) or 'oracle' (the same composition on the CPU).  The operands go in AS GIVEN: ``place`` keeps their
+    ``[cut, nT)``) or 'oracle' (the same composition on the CPU).  ``cot``: the cotangent of ``out`` in place of
+    :func:`_cotangent` (CPU; ``test_signal_operands.py``).  The operands go in AS GIVEN: ``place`` keeps their
     strides and offsets, and the leaves are detached aliases, not copies."""
     on = (lambda x: x) if route == 'oracle' else place
     leaf = lambda x: on(x).detach().requires_grad_(True)  # noqa: E731
@@ -66,7 +68,7 @@ def _run(route, v, every=None, consts=None, sim=None, cut=None):
                 recs.append(M)
                 t0 = e
             out = torch.stack(recs, dim=-2)
-    torch.autograd.backward([out], [on(_cotangent(v, every, nT))])
+    torch.autograd.backward([out], [on(_cotangent(v, every, nT) if cot is None else cot)])
     return dict(out=out.detach(), grad_Mi=Mi.grad, grad_rf=rf.grad, grad_gr=gr.grad)
 
 

@@ -117,12 +117,39 @@ def _check_grads(P, every, tag, with_oracle=True):
 @pytest.mark.usefixtures('host_constants')
 @pytest.mark.parametrize('tag', ['f64', 'f32'])
 @pytest.mark.parametrize('variant', VARIANTS)
-@pytest.mark.parametrize('nT,every', [(48, 1), (48, 3), (48, 16), (48, 40), (48, 48), (50, 3), (50, 16)])
+@pytest.mark.parametrize('nT,every', [(48, 1), (48, 3), (48, 16), (48, 40), (48, 48), (50, 3), (50, 16),
+                                      (16, 1), (16, 5), (16, 16), (16, 21)])
 def test_traj_gradients(tag, variant, nT, every):
     r"""Loss (Mt * w).sum(): grad_Mi, grad_rf, grad_gr of the trajectory kernels == autograd through the per-segment
     composition == the oracle; twice the same bits.  every < 16 takes the per-step injection, every >= 16 the
-    per-segment one; nT = 50 the fused part + composed tail."""
+    per-segment one; nT = 50 the fused part + composed tail; nT = 16 one checkpoint segment."""
     _check_grads(_problem(tag, variant, nT), every, tag)
+
+
+@pytest.mark.parametrize('tag', ['f64', 'f32'])
+@pytest.mark.parametrize('empty', ['nT', 'nM'])
+def test_traj_empty_problem(tag, empty):
+    r"""No step (nT = 0) or no spin (nM = 0) through the Python API: ``Mt`` is `(N, nM, 0, 3)` / `(N, 0, nRec, 3)` and
+    ``blochsim_rfgr``'s ``Mo`` is ``Mi``; the backward runs -- ``grad_Mi`` is the cotangent of ``Mo`` (zero for the
+    trajectory without a record), the pulse gradients are zeros of the shapes of ``rf`` and ``gr``."""
+    nT, nM, every = (0, 100, 3) if empty == 'nT' else (32, 0, 5)
+    P = _problem(tag, 'plain', 32, nM=nM)
+    P['rf'], P['gr'] = P['rf'][:, :, :nT], P['gr'][:, :, :nT]
+    nRec = len(_traj_ends(nT, every))
+    for traj in (True, False):
+        Mi, rf, gr = (dev(P[k]).clone().requires_grad_(True) for k in ('M0', 'rf', 'gr'))
+        if traj:
+            out = fused.blochsim_rfgr_traj(Mi, rf, gr, dev(P['loc']), every=every, **_kw(P, dev))
+            assert out.shape == (2, nM, nRec, 3) and out.dtype == DT[tag]
+        else:
+            out = fused.blochsim_rfgr(Mi, rf, gr, dev(P['loc']), **_kw(P, dev))
+            assert out.shape == Mi.shape and (nT > 0 or torch.equal(out, Mi.detach()))
+        w = dev(_weights(tuple(out.shape), out.dtype))
+        (out * w).sum().backward()
+        assert Mi.grad.shape == Mi.shape
+        assert torch.equal(Mi.grad, torch.zeros_like(Mi) if traj else w), traj
+        for g, x in ((rf.grad, rf), (gr.grad, gr)):
+            assert g is not None and g.shape == x.shape and g.dtype == x.dtype and bool((g == 0).all()), traj
 
 
 @pytest.mark.parametrize('mode,wide', [('fast', False), ('fast', True), ('precise', False), ('precise', True)])

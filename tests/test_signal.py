@@ -174,13 +174,39 @@ def _check_grads(P, rx, every, tag, with_oracle=True):
 
 @pytest.mark.usefixtures('host_constants')
 @pytest.mark.parametrize('tag', ['f64', 'f32'])
-@pytest.mark.parametrize('variant', ['plain', 'b1map', 'norelax'])
-@pytest.mark.parametrize('nT,every', [(48, 1), (48, 3), (48, 16), (48, 40), (48, 48), (50, 3), (50, 16)])
+@pytest.mark.parametrize('variant', ['plain', 'b1map', 'norelax', 'plain_batch1_pulse'])
+@pytest.mark.parametrize('nT,every', [(48, 1), (48, 3), (48, 16), (48, 40), (48, 48), (50, 3), (50, 16),
+                                      (16, 1), (16, 5), (16, 16), (16, 21)])
 def test_signal_gradients(tag, variant, nT, every):
     r"""Loss (sig·w).sum() + (Mo·v).sum(), and each term alone: grad_Mi, grad_rf, grad_gr of the signal kernels ==
     autograd through the composed route == the oracle (the gates of test_traj_gradients on the same problems); twice
-    the same bits; with the Mo term alone they are blochsim_rfgr's.  nT = 50: the fused part + composed tail."""
+    the same bits; with the Mo term alone they are blochsim_rfgr's.  nT = 50: the fused part + composed tail; nT = 16:
+    one checkpoint segment (no previous checkpoint to fetch ahead); a batch-1 pulse: its gradients summed over N."""
     _check_grads(_problem(tag, variant, nT), _rx(tag, 'coil'), every, tag)
+
+
+@pytest.mark.parametrize('tag', ['f64', 'f32'])
+@pytest.mark.parametrize('empty', ['nT', 'nM'])
+@pytest.mark.parametrize('rxk', ['none', 'coil'])
+def test_signal_empty_problem(tag, empty, rxk):
+    r"""No step (nT = 0) or no spin (nM = 0) through the Python API: ``sig`` is `(N, 2, 0)`, or zeros `(N, 2, nRec)`
+    without spins; ``Mo`` is ``Mi``; the backward runs -- ``grad_Mi`` is the cotangent of ``Mo``, the pulse gradients are
+    zeros of the shapes of ``rf`` and ``gr``."""
+    nT, nM, every = (0, NM, 3) if empty == 'nT' else (32, 0, 5)
+    P = _problem(tag, 'plain', 32, nM=nM)
+    P['rf'], P['gr'] = P['rf'][:, :, :nT], P['gr'][:, :, :nT]
+    rx = _rx(tag, rxk, nM=nM)
+    Mi, rf, gr = (dev(P[k]).clone().requires_grad_(True) for k in ('M0', 'rf', 'gr'))
+    sig, Mo = fused.signal_rfgr(Mi, rf, gr, dev(P['loc']), every=every, rx=dev(rx), return_Mo=True, **_kw(P, dev))
+    nRec = len(_traj_ends(nT, every))
+    assert sig.shape == (N, 2, nRec) and sig.dtype == DT[tag] and Mo.shape == Mi.shape
+    assert nRec == (0 if empty == 'nT' else 7)
+    assert bool((sig == 0).all()) and torch.equal(Mo, Mi.detach())
+    v = dev(_weights(tuple(Mo.shape), Mo.dtype))
+    ((sig * dev(_weights(tuple(sig.shape), sig.dtype))).sum() + (Mo * v).sum()).backward()
+    assert Mi.grad.shape == Mi.shape and torch.equal(Mi.grad, v)
+    for g, x in ((rf.grad, rf), (gr.grad, gr)):
+        assert g is not None and g.shape == x.shape and g.dtype == x.dtype and bool((g == 0).all())
 
 
 # =============================================================================================
