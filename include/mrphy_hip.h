@@ -70,7 +70,9 @@ extern "C" {
  *      Added later under the same version, changing no existing call: mrphy_blochsim_rfgr_traj_fwd,
  *      mrphy_blochsim_rfgr_traj_bwd, mrphy_blochsim_rfgr_mc_traj_bwd (the magnetisation trajectory of K2);
  *      mrphy_signal_rfgr_fwd_workspace, mrphy_signal_rfgr_fwd, mrphy_signal_rfgr_bwd (the received signal of K2:
- *      the transverse magnetisation summed over the spins, sample by sample). */
+ *      the transverse magnetisation summed over the spins, sample by sample); mrphy_signal_rfgr_max_rx,
+ *      mrphy_signal_rfgr_mrx_fwd_workspace, mrphy_signal_rfgr_mrx_fwd, mrphy_signal_rfgr_mrx_bwd (the same for the coils
+ *      of a receive array from ONE simulation per launch). */
 #define MRPHY_ABI_VERSION 5
 
 #define MRPHY_F32      0  /* T = float,  CT = float                                          */
@@ -621,6 +623,69 @@ int mrphy_signal_rfgr_bwd(int dtype,
                           void* work, size_t work_bytes,
                           int64_t N, int64_t nM, int64_t nT,
                           void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * K2s-mrx  K2s for the nRx coils of a receive array in ONE launch: one simulation, every coil's samples.
+ *     sig[n, 0, j, c] = sum_s  rx_re[n,s,c] Mx[n,s] - rx_im[n,s,c] My[n,s]
+ *     sig[n, 1, j, c] = sum_s  rx_re[n,s,c] My[n,s] + rx_im[n,s,c] Mx[n,s]    (M after step e_j)
+ * rx (N, nM, 2, nRx) contiguous, the layout of a multi-coil b1, required; sig (N, 2, nRec, nRx), the layout of a
+ * multi-coil rf.  1 <= nRx <= mrphy_signal_rfgr_max_rx(dtype) (8 for every code; 0 for an unknown code): a caller with
+ * more coils launches once per block of that many.  Every (record, coil) sum is formed on its own, in the lane, tile
+ * and row order of K2s: sig[..., c] is bit for bit what mrphy_signal_rfgr_fwd returns for rx[..., c] alone, and Mo is
+ * the same bits as well.  Everything else -- operands, ONE transmit coil, Mo, Mck / ck_every, any nT -- as
+ * mrphy_signal_rfgr_fwd.  `work` must hold mrphy_signal_rfgr_mrx_fwd_workspace() bytes: sig_waves(nM) N 2 nRx nRec
+ * elements, nRx times mrphy_signal_rfgr_fwd_workspace().
+ * MRPHY_EINVAL: nRx < 1 or above the capacity, rx or sig NULL, every < 1, nC != 1, N > 65535, an unknown dtype;
+ * MRPHY_ENOSPC: workspace too small; an empty problem (N nM nT == 0) returns 0 and touches nothing.
+ * ------------------------------------------------------------------------------------------- */
+int mrphy_signal_rfgr_max_rx(int dtype);
+size_t mrphy_signal_rfgr_mrx_fwd_workspace(int dtype, int64_t N, int64_t nM, int64_t nT, int64_t every, int64_t nRx);
+int mrphy_signal_rfgr_mrx_fwd(int dtype,
+                              const void* Mi,
+                              const void* rf, int64_t rf_sn,
+                              const void* gr, int64_t gr_sn,
+                              const void* loc,
+                              const void* df, int64_t df_sn, int64_t df_sm,
+                              const void* gamma, int64_t gamma_sn, int64_t gamma_sm,
+                              const void* b1,
+                              const void* g,  int64_t g_sn,  int64_t g_sm,
+                              const void* E1, int64_t E1_sn, int64_t E1_sm,
+                              const void* E2, int64_t E2_sn, int64_t E2_sm,
+                              const void* E1m1,
+                              const void* rx, int64_t nRx,
+                              void* Mo, void* Mck, int64_t ck_every,
+                              void* sig, int64_t every,
+                              void* work, size_t work_bytes,
+                              int64_t N, int64_t nM, int64_t nT, int64_t nC,
+                              void* stream);
+
+/* K2bs-mrx  adjoint of K2s-mrx: mrphy_signal_rfgr_bwd with rx (N, nM, 2, nRx) and grad_sig (N, 2, nRec, nRx), in ONE
+ * sweep.  As it passes step e_j backwards the sweep adds the coils' cotangents of sample j, summed in ascending c and
+ * injected once:
+ *     (sum_c rx_re,c g0,c + rx_im,c g1,c,  sum_c rx_re,c g1,c - rx_im,c g0,c,  0),   g0,c, g1,c = grad_sig[n, :, j, c]
+ * The gradients equal the sum of the one-coil calls' up to the association of that sum.  Without grad_sig it is
+ * mrphy_blochsim_rfgr_bwd.  Checkpoints, workspace (mrphy_blochsim_rfgr_bwd_workspace) and reduction as
+ * mrphy_signal_rfgr_bwd; no gradient w.r.t. rx.
+ * MRPHY_EINVAL: nRx < 1 or above the capacity, rx NULL, every < 1, nT not a whole number of segments, both cotangents
+ * NULL, N > 65535, an unknown dtype; MRPHY_ENOSPC: workspace too small; an empty problem returns 0. */
+int mrphy_signal_rfgr_mrx_bwd(int dtype,
+                              const void* Mck,
+                              const void* rf, int64_t rf_sn,
+                              const void* gr, int64_t gr_sn,
+                              const void* loc,
+                              const void* df, int64_t df_sn, int64_t df_sm,
+                              const void* gamma, int64_t gamma_sn, int64_t gamma_sm,
+                              const void* b1,
+                              const void* g,  int64_t g_sn,  int64_t g_sm,
+                              const void* E1, int64_t E1_sn, int64_t E1_sm,
+                              const void* E2, int64_t E2_sn, int64_t E2_sm,
+                              const void* E1m1,
+                              const void* rx, int64_t nRx,
+                              const void* grad_Mo, const void* grad_sig, int64_t every,
+                              void* grad_Mi, void* grad_rf, void* grad_gr,
+                              void* work, size_t work_bytes,
+                              int64_t N, int64_t nM, int64_t nT,
+                              void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * the steps either side of the path in SpinArray.applypulse (mobjs.py:427-433,449).

@@ -65,6 +65,11 @@ PROTOTYPES = {
     'mrphy_signal_rfgr_fwd_workspace': (_sz, [_int] + [_i64] * 4),
     'mrphy_signal_rfgr_fwd': (_int, _FUSED + [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _sz] + [_i64] * 4 + [_vp]),
     'mrphy_signal_rfgr_bwd': (_int, _FUSED + [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _sz] + [_i64] * 3 + [_vp]),
+    'mrphy_signal_rfgr_max_rx': (_int, [_int]),
+    'mrphy_signal_rfgr_mrx_fwd_workspace': (_sz, [_int] + [_i64] * 5),
+    'mrphy_signal_rfgr_mrx_fwd': (_int, _FUSED + [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _sz] + [_i64] * 4 + [_vp]),
+    'mrphy_signal_rfgr_mrx_bwd': (_int, _FUSED + [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _sz] + [_i64] * 3
+                                  + [_vp]),
     'mrphy_freeprec_fwd': (_int, [_int, _vp, _vp, _i64] + _BC * 3 + [_vp, _i64, _i64, _vp]),
     'mrphy_freeprec_bwd': (_int, [_int, _vp, _vp, _i64] + _BC * 3 + [_vp, _i64, _i64, _vp]),
     'mrphy_freeprec_bwd_consts': (_int, [_int, _vp, _vp, _vp, _i64] + _BC * 3 + [_vp, _i64, _i64, _vp]),
@@ -102,6 +107,10 @@ UNITS = [(f, m) for f, masks in (
     ('tu_fused_fwd1.hip', (_F32, _C64, _P, _PC64)),
     ('tu_fused_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_signal.hip', (_F32, _F64, _C64, _P, _PC64)),
+    ('tu_fused_mrx_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
+    ('tu_signal_mrx8.hip', (_F32, _F64, _C64, _P, _PC64)),
+    ('tu_signal_mrx4.hip', (_F32, _F64, _C64, _P, _PC64)),
+    ('tu_signal_mrx2.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_blochsim_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_blochsim_fwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_beff2ab.hip', (_F32, _F64, _C64, _P, _PC64)),

@@ -389,6 +389,64 @@ int mrphy_signal_rfgr_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PARAMS, co
                                                work, N, nM, nT, st)));
 }
 
+int mrphy_signal_rfgr_max_rx(int dtype)
+{
+    if (check_common(dtype, 0, 0, 0)) return 0;
+    return sig_max_rx(tsize(dtype));
+}
+
+size_t mrphy_signal_rfgr_mrx_fwd_workspace(int dtype, int64_t N, int64_t nM, int64_t nT, int64_t every, int64_t nRx)
+{
+    if (nRx < 1) return 0;
+    return mrphy_signal_rfgr_fwd_workspace(dtype, N, nM, nT, every) * (size_t)nRx;
+}
+
+int mrphy_signal_rfgr_mrx_fwd(int dtype, const void* Mi, MRPHY_PULSE_OPS_PARAMS, const void* rx, int64_t nRx, void* Mo,
+                              void* Mck, int64_t ck_every, void* sig, int64_t every, void* work, size_t work_bytes,
+                              int64_t N, int64_t nM, int64_t nT, int64_t nC, void* stream)
+{
+    if (int e = check_common(dtype, N, nM, nT)) return e;
+    if (every < 1 || nC != 1 || N > 65535 || (Mck && (ck_every < 8 || ck_every % 8 != 0))) return MRPHY_EINVAL;
+    if (nRx < 1 || nRx > sig_max_rx(tsize(dtype))) return MRPHY_EINVAL;
+    if (N * nM * nT == 0) return 0;
+    const PulseOps in = MRPHY_PULSE_OPS;
+    if (!Mi || !rx || !sig || !work) return MRPHY_EINVAL;
+    if (int e = check_ops(in, true, false)) return e;
+    if (work_bytes < mrphy_signal_rfgr_mrx_fwd_workspace(dtype, N, nM, nT, every, nRx)) return MRPHY_ENOSPC;
+    hipStream_t st = (hipStream_t)stream;
+    // the smallest coil capacity that holds nRx
+    if (nRx <= 2)
+        MRPHY_DISPATCH(dtype, (run_signal_mrx_fwd<T, CT, 2>(Mi, in, rx, nRx, Mo, Mck, ck_every, sig, every, work, N, nM,
+                                                            nT, st)));
+    if (nRx <= 4)
+        MRPHY_DISPATCH(dtype, (run_signal_mrx_fwd<T, CT, 4>(Mi, in, rx, nRx, Mo, Mck, ck_every, sig, every, work, N, nM,
+                                                            nT, st)));
+    MRPHY_DISPATCH(dtype, (run_signal_mrx_fwd<T, CT, 8>(Mi, in, rx, nRx, Mo, Mck, ck_every, sig, every, work, N, nM, nT,
+                                                        st)));
+}
+
+int mrphy_signal_rfgr_mrx_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PARAMS, const void* rx, int64_t nRx,
+                              const void* grad_Mo, const void* grad_sig, int64_t every, void* grad_Mi, void* grad_rf,
+                              void* grad_gr, void* work, size_t work_bytes, int64_t N, int64_t nM, int64_t nT,
+                              void* stream)
+{
+    if (int e = check_common(dtype, N, nM, nT)) return e;
+    // whole checkpoint segments only; at least one of the two cotangents
+    if (nT % SEG != 0 || every < 1 || N > 65535 || (!grad_Mo && !grad_sig)) return MRPHY_EINVAL;
+    if (nRx < 1 || nRx > sig_max_rx(tsize(dtype))) return MRPHY_EINVAL;
+    if (N * nM * nT == 0) return 0;
+    const PulseOps in = MRPHY_PULSE_OPS;
+    if (!Mck || !rx || !work) return MRPHY_EINVAL;
+    if (int e = check_ops(in, true, false)) return e;
+    if (work_bytes < mrphy_blochsim_rfgr_bwd_workspace(dtype, N, nM, nT)) return MRPHY_ENOSPC;
+    hipStream_t st = (hipStream_t)stream;
+    if (!grad_sig)                          // nothing of the signal to inject: K2b on grad_Mo
+        MRPHY_DISPATCH(dtype, (run_rfgr_bwd<T, CT>(Mck, in, grad_Mo, nullptr, every, nullptr, nullptr, grad_Mi, grad_rf,
+                                                   grad_gr, work, N, nM, nT, st)));
+    MRPHY_DISPATCH(dtype, (run_rfgr_mrx_bwd<T, CT>(Mck, in, grad_Mo, every, rx, nRx, grad_sig, grad_Mi, grad_rf, grad_gr,
+                                                   work, N, nM, nT, st)));
+}
+
 int mrphy_beff2ab(int dtype, const void* Beff,
                   const void* g, int64_t g_sn, int64_t g_sm,
                   const void* E1, int64_t E1_sn, int64_t E1_sm,

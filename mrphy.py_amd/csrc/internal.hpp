@@ -56,6 +56,18 @@ template <typename T, typename CT>
 int run_signal_fwd(const void* Mi, PulseOps in, const void* rx, void* Mo, void* Mck, int64_t ck_every, void* sig,
                    int64_t every, void* work, int64_t N, int64_t nM, int64_t nT, hipStream_t st);
 
+// K2s-mrx / K2bs-mrx: nRx <= sig_max_rx receive coils in one launch, rx (N, nM, 2, nRx), sig / gsig (N, 2, nRec, nRx).
+// The forward has one unit per coil capacity R (tu_signal_mrx2 / 4 / 8.hip); the adjoint (tu_fused_mrx_bwd.hip) picks
+// the capacity itself and needs a non-null gsig
+template <typename T, typename CT, int R>
+int run_signal_mrx_fwd(const void* Mi, PulseOps in, const void* rx, int64_t nRx, void* Mo, void* Mck, int64_t ck_every,
+                       void* sig, int64_t every, void* work, int64_t N, int64_t nM, int64_t nT, hipStream_t st);
+
+template <typename T, typename CT>
+int run_rfgr_mrx_bwd(const void* Mck, PulseOps in, const void* gMo, int64_t every, const void* rx, int64_t nRx,
+                     const void* gsig, void* gMi, void* grf, void* ggr, void* work, int64_t N, int64_t nM, int64_t nT,
+                     hipStream_t st);
+
 template <typename T, typename CT>
 int run_rfgr_mc_bwd(const void* Mck, PulseOps in, const void* gMo, const void* gMt, int64_t every, void* gMi, void* grf,
                     void* ggr, void* work, int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st);

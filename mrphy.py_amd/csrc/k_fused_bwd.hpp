@@ -33,7 +33,7 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdArgsT<T, INJ> a
         const T* gM = a.gMo;
         if constexpr (INJ == 1 || INJ == 2) gM += (a.nRec - 1) * rows * 3;
         T hx = T(0), hy = T(0), hz = T(0);
-        if (INJ != 3 || gM) { hx = gM[row * 3] * vmask; hy = gM[row * 3 + 1] * vmask; hz = gM[row * 3 + 2] * vmask; }
+        if (INJ < 3 || gM) { hx = gM[row * 3] * vmask; hy = gM[row * 3 + 1] * vmask; hz = gM[row * 3 + 2] * vmask; }
         // trajectory: the latest record not yet injected, index jr, taken after step er (both wave-uniform)
         int64_t every = 0, jr = 0, er = 0;
         if constexpr (INJ == 1 || INJ == 2) { every = a.every; jr = a.nRec - 2; er = (a.nRec - 1) * every - 1; }
@@ -46,6 +46,25 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdArgsT<T, INJ> a
             if (a.rx) { rxr = a.rx[row * 2] * vmask; rxi = a.rx[row * 2 + 1] * vmask; }
             gs0 = (CP)(a.gsig + n * 2 * a.nRec);
             gs1 = gs0 + a.nRec;
+        }
+        // several receive coils (INJ >= 4, capacity R = inj_rx_cap(INJ)): the lane's R weights in registers (zero past
+        // nM and for the pad coils c >= nRx); the cotangents gsig (N, 2, nRec, nRx), a record's nRx values contiguous
+        // (declared in every mode because the sweep below reads them: one unused element each in modes 0-3, which
+        // compile to the instructions they had without them)
+        constexpr int R = inj_rx_cap(INJ);
+        T wr[R], wi[R];
+        int nrx = 0;
+        if constexpr (INJ >= 4) {
+            every = a.every; jr = a.nRec - 1; er = nT - 1;
+            nrx = (int)a.nRx;
+            const T* q = a.rx + row * 2 * a.nRx;
+#pragma unroll
+            for (int c = 0; c < R; ++c) {
+                wr[c] = wi[c] = T(0);
+                if (c < nrx) { wr[c] = q[c] * vmask; wi[c] = q[a.nRx + c] * vmask; }
+            }
+            gs0 = (CP)(a.gsig + n * 2 * a.nRec * a.nRx);
+            gs1 = gs0 + a.nRec * a.nRx;
         }
         adj_begin<RELAX, T, CT>(k, hx, hy, hz);
 
@@ -123,6 +142,23 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdArgsT<T, INJ> a
                         if (t0 + st == er) {                            // wave-uniform
                             const T g0 = gs0[jr], g1 = gs1[jr];
                             adj_inject<RELAX, T, CT>(k, hx, hy, hz, rxr * g0 + rxi * g1, rxr * g1 - rxi * g0, T(0));
+                            er = (jr == a.nRec - 1) ? jr * every - 1 : er - every;
+                            --jr;
+                        }
+                    } else if constexpr (INJ >= 4) {
+                        if (t0 + st == er) {                            // wave-uniform
+                            // the coils' cotangents summed in ascending c, then ONE injection: in the t = E h state of
+                            // the precise modes the sum is scaled and rounded once
+                            const CP q0 = gs0 + jr * nrx, q1 = gs1 + jr * nrx;
+                            T ix = wr[0] * q0[0] + wi[0] * q1[0], iy = wr[0] * q1[0] - wi[0] * q0[0];
+#pragma unroll
+                            for (int c = 1; c < R; ++c)
+                                if (c < nrx) {                          // wave-uniform: no load past the record's nRx
+                                    const T g0 = q0[c], g1 = q1[c];
+                                    ix += wr[c] * g0 + wi[c] * g1;
+                                    iy += wr[c] * g1 - wi[c] * g0;
+                                }
+                            adj_inject<RELAX, T, CT>(k, hx, hy, hz, ix, iy, T(0));
                             er = (jr == a.nRec - 1) ? jr * every - 1 : er - every;
                             --jr;
                         }

@@ -33,6 +33,18 @@ static_assert(offsetof(SignalArgs<float>, in) == 8 && offsetof(SignalArgs<float>
               offsetof(SignalArgs<double>, rx) == 184 && offsetof(SignalArgs<double>, P) == 264 &&
               sizeof(SignalArgs<double>) == 272, "K2s's kernel arguments moved");
 
+// What a coil with weight (rxr, rxi) sees of the lane's (mx, my): s0 = rxr mx - rxi my, s1 = rxr my + rxi mx, with the
+// roundings spelled out -- one product rounded, the other fused into the sum.  K2s and the multi-coil kernel
+// (k_signal_mrx_fwd.hpp) both form their records here, so a coil's terms are the same bits in both whatever a compiler
+// would have made of the plain expressions (these are the forms K2s was compiled to when the choice was the compiler's).
+template <typename T>
+__device__ __forceinline__ void rx_products(T rxr, T rxi, T mx, T my, T& s0, T& s1)
+{
+#pragma clang fp contract(off)
+    s0 = fma_(rxr, mx, -(rxi * my));
+    s1 = fma_(rxi, mx, rxr * my);
+}
+
 // CK, RELAX, HB1: as K2.  EV1: every == 1 -- a record after every step, its slot known at compile time inside the
 // unrolled step batch; otherwise the step of the next record is carried (wave-uniform) and compared, as in K2t.
 template <typename T, typename CT, bool CK, bool RELAX, bool HB1, bool EV1>
@@ -78,8 +90,10 @@ __global__ __launch_bounds__(WAVE) void k_signal_fwd(SignalArgs<T> a)
         int64_t jbase = 0;                                       // records of this spin tile already reduced
         int64_t next = every - 1 < nT - 1 ? every - 1 : nT - 1;  // the step after which the next record is taken
         auto rec = [&](int slot) {
-            red[red_idx(slot, lane)] = rxr * mx - rxi * my;
-            red[red_idx(SEG + slot, lane)] = rxr * my + rxi * mx;
+            T s0, s1;
+            rx_products(rxr, rxi, mx, my, s0, s1);
+            red[red_idx(slot, lane)] = s0;
+            red[red_idx(SEG + slot, lane)] = s1;
         };
         auto take = [&](int64_t t) {                             // the record after step t, if one is due
             if (t == next) {

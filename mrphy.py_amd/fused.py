@@ -22,7 +22,7 @@ trajectory kernels K2t / K2bt.
 
 :func:`signal_rfgr` is the same simulation again, returning what a receive coil measures: the transverse
 magnetisation summed over the spins at the trajectory's record steps (K2s, and the signal mode of K2b), without the
-per-spin records in memory.
+per-spin records in memory; the coils of a receive array share one simulation per launch.
 """
 from math import pi as π, prod  # noqa: F401
 from typing import Optional
@@ -155,8 +155,11 @@ class SignalRfGrHIP(Function):
     r"""``sig, Mo = SignalRfGrHIP.apply(Mi, rf, gr, pulse_on_spins, rx, γ2πdt, E1, E2, E1_1, want_ckpt, every)``
 
     ``sig`` `(N, xy, nRec)`: the received signal (``mrphy_signal_rfgr_fwd`` / ``_bwd``), ``rx`` `(N, nM, xy)` contiguous
-    or ``None``; one transmit coil.  Both outputs may carry a cotangent; an output the loss does not use costs nothing
-    (its cotangent stays ``None``).  ``want_ckpt`` as in :class:`BlochSimRfGrHIP`."""
+    or ``None``; one transmit coil.  With ``rx`` `(N, nM, xy, nRx)` contiguous, ``nRx`` up to
+    ``mrphy_signal_rfgr_max_rx(code)``, ``sig`` is `(N, xy, nRec, nRx)`: every coil from one simulation, forward and
+    adjoint (``mrphy_signal_rfgr_mrx_fwd`` / ``_mrx_bwd``), each coil's samples the bits the one-coil call gives.  Both
+    outputs may carry a cotangent; an output the loss does not use costs nothing (its cotangent stays ``None``).
+    ``want_ckpt`` as in :class:`BlochSimRfGrHIP`."""
 
     @staticmethod
     def forward(ctx, Mi, rf, gr, p, rx, γ2πdt, E1, E2, E1_1, want_ckpt=False, every=1):
@@ -164,25 +167,28 @@ class SignalRfGrHIP(Function):
         device, dtype = Mi.device, Mi.dtype
         need = bool(want_ckpt)
         code, alive, consts, Mck, ckpt = _forward_prep(lib, p, γ2πdt, E1, E2, E1_1, dtype, device, need)
-        consts = (*consts, None if rx is None else rx.data_ptr())
+        mrx = (rx.shape[-1],) if rx is not None and rx.ndim == 4 else ()      # the coil count, for the _mrx_ entry points
+        consts = (*consts, None if rx is None else rx.data_ptr(), *mrx)
         Mi_c = Mi.detach().contiguous()
-        sig = torch.empty((p.N, 2, -(-p.nT // every)), dtype=dtype, device=device)
+        sig = torch.empty((p.N, 2, -(-p.nT // every), *mrx), dtype=dtype, device=device)
         Mo = torch.empty_like(Mi_c)
-        nbytes = int(lib.mrphy_signal_rfgr_fwd_workspace(code, p.N, p.nM, p.nT, every))
+        nbytes = int(lib.mrphy_signal_rfgr_mrx_fwd_workspace(code, p.N, p.nM, p.nT, every, *mrx) if mrx else
+                     lib.mrphy_signal_rfgr_fwd_workspace(code, p.N, p.nM, p.nT, every))
         work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
         if p.nT == 0:
             Mo.copy_(Mi_c)                      # no step, no record
         if p.N * p.nM * p.nT == 0:
             sig.zero_()                         # no spin: empty sums (the library writes nothing for an empty problem)
+        name = 'mrphy_signal_rfgr_mrx_fwd' if mrx else 'mrphy_signal_rfgr_fwd'
         with torch.cuda.device(device):
-            rc = lib.mrphy_signal_rfgr_fwd(code, Mi_c.data_ptr(), *p.k0_args(), *consts, Mo.data_ptr(), *ckpt,
-                                           sig.data_ptr(), every, work.data_ptr(), work.numel(),
-                                           p.N, p.nM, p.nT, p.nC, _host.current_stream(device))
-        _lib.check(rc, 'mrphy_signal_rfgr_fwd')
+            rc = getattr(lib, name)(code, Mi_c.data_ptr(), *p.k0_args(), *consts, Mo.data_ptr(), *ckpt,
+                                    sig.data_ptr(), every, work.data_ptr(), work.numel(),
+                                    p.N, p.nM, p.nT, p.nC, _host.current_stream(device))
+        _lib.check(rc, name)
         ctx.set_materialize_grads(False)
         if need:
             ctx.save_for_backward(Mck)
-            ctx.keep = (p, code, consts, (*alive, rx), rf.shape, gr.shape, rf.dtype, gr.dtype, every)
+            ctx.keep = (p, code, consts, (*alive, rx), rf.shape, gr.shape, rf.dtype, gr.dtype, every, bool(mrx))
         return sig, Mo
 
     @staticmethod
@@ -192,7 +198,7 @@ class SignalRfGrHIP(Function):
             return (None,) * 11
         lib = _lib.require_library()
         (Mck,) = ctx.saved_tensors
-        p, code, consts, _alive, rf_shape, gr_shape, rf_dtype, gr_dtype, every = ctx.keep
+        p, code, consts, _alive, rf_shape, gr_shape, rf_dtype, gr_dtype, every, mrx = ctx.keep
         _host.require_invertible_relaxation(code, _alive[1], _alive[2], 'fused.signal_rfgr')
         device, dtype = Mck.device, Mck.dtype
         gs = None if grad_sig is None else grad_sig.to(dtype).contiguous()
@@ -202,11 +208,12 @@ class SignalRfGrHIP(Function):
         if p.N * p.nM * p.nT == 0:
             _empty_problem_grads(grads, gM)
             return (*_fold_grads(*grads, p, rf_shape, gr_shape, rf_dtype, gr_dtype), *(None,) * 8)
+        name = 'mrphy_signal_rfgr_mrx_bwd' if mrx else 'mrphy_signal_rfgr_bwd'
         with torch.cuda.device(device):
-            rc = lib.mrphy_signal_rfgr_bwd(code, Mck.data_ptr(), *p.k0_args(), *consts, ptr(gM), ptr(gs), every,
-                                           *outs, work.data_ptr(), work.numel(),
-                                           p.N, p.nM, p.nT, _host.current_stream(device))
-        _lib.check(rc, 'mrphy_signal_rfgr_bwd')
+            rc = getattr(lib, name)(code, Mck.data_ptr(), *p.k0_args(), *consts, ptr(gM), ptr(gs), every,
+                                    *outs, work.data_ptr(), work.numel(),
+                                    p.N, p.nM, p.nT, _host.current_stream(device))
+        _lib.check(rc, name)
         return (*_fold_grads(*grads, p, rf_shape, gr_shape, rf_dtype, gr_dtype), *(None,) * 8)
 
 
@@ -217,8 +224,11 @@ def _route(Mi, rf, gr, loc, every, kw, signal=False, rx=None):
     checkpoint segments -- the caller runs the first ``n1`` steps fused and composes the tail; ``('composed', None)``:
     a case the fused kernels do not cover (gradients w.r.t. the spin-side maps, fp64 with more than 8 coils, a pulse
     gradient the fused adjoint cannot form); or ``('fused', M)``, the result of :class:`BlochSimRfGrHIP` -- for the
-    signal the list of :class:`SignalRfGrHIP`'s ``(sig, Mo)``, one per receive coil.  The signal kernels take one
-    transmit coil and form no gradient w.r.t. ``rx``: parallel transmit and that gradient are composed."""
+    signal :class:`SignalRfGrHIP`'s ``(sig, Mo)``.  An ``rx`` with a coil axis of two or more runs one application per
+    block of up to ``mrphy_signal_rfgr_max_rx(code)`` coils -- one forward and one backward launch for all of a
+    block's coils; ``sig`` is the blocks' concatenated on the coil axis, ``Mo`` the first block's, and autograd adds the
+    blocks' gradients.  The signal kernels take one transmit coil and form no gradient w.r.t. ``rx``: parallel transmit
+    and that gradient are composed."""
     from . import beffective, sims
     _host.require_device_tensor(Mi, 'Mi')
     Δf, b1Map, T1, T2 = kw['Δf'], kw['b1Map'], kw['T1'], kw['T2']
@@ -253,13 +263,21 @@ def _route(Mi, rf, gr, loc, every, kw, signal=False, rx=None):
         γ2πdt, E1, E2, E1_1 = sims.relax_constants(T1, T2, kw['γ'], kw['dt'], 1 + len(p.Nd) + 2, device)
     want = pulse_grad and fused_adjoint_ok
     if signal:
-        # one launch per receive coil ((N, *Nd, xy, nRx) -> nRx maps (N, nM, xy)); no rx: the plain sums
-        # (the coil count spelled out: a `-1` is ambiguous for a map without spins, nM == 0)
-        rxs = [None] if rx is None else \
-            list(rx.detach().to(device=device, dtype=dtype).expand((p.N,) + p.Nd + tuple(rx.shape[1 + len(p.Nd):]))
-                 .reshape(p.N, p.nM, 2, rx.shape[-1] if rx.ndim == Mi.ndim + 1 else 1).unbind(-1))
-        return 'fused', [SignalRfGrHIP.apply(Mi, rf, gr, p, None if r is None else r.contiguous(), γ2πdt, E1, E2, E1_1,
-                                             want, every) for r in rxs]
+        apply = lambda r: SignalRfGrHIP.apply(Mi, rf, gr, p, r, γ2πdt, E1, E2, E1_1, want, every)  # noqa: E731
+        if rx is None:
+            return 'fused', apply(None)         # the plain sums
+        # (N, *Nd, xy[, nRx]) -> (N, nM, xy, nRx), without a copy if it is contiguous already (the coil count spelled
+        # out: a `-1` is ambiguous for a map without spins, nM == 0)
+        nrx = rx.shape[-1] if rx.ndim == Mi.ndim + 1 else 1
+        r = rx.detach().to(device=device, dtype=dtype).expand((p.N,) + p.Nd + tuple(rx.shape[1 + len(p.Nd):])) \
+            .reshape(p.N, p.nM, 2, nrx)
+        if nrx == 1:                            # one coil: the one-coil kernels, a coil axis kept if there was one
+            sig, Mo = apply(r[..., 0].contiguous())
+            return 'fused', (sig.unsqueeze(-1) if rx.ndim == Mi.ndim + 1 else sig, Mo)
+        # (the capacity depends on the data type alone, not on the constants' precision)
+        cap = int(lib.mrphy_signal_rfgr_max_rx(_lib.F64 if dtype == torch.float64 else _lib.F32))
+        outs = [apply(r[..., c:c + cap].contiguous()) for c in range(0, nrx, cap)]
+        return 'fused', (outs[0][0] if len(outs) == 1 else torch.cat([o[0] for o in outs], dim=-1), outs[0][1])
     return 'fused', BlochSimRfGrHIP.apply(Mi, rf, gr, p, γ2πdt, E1, E2, E1_1, want, every)
 
 
@@ -405,8 +423,9 @@ def signal_rfgr(
 
     The sum is formed inside the kernel (K2s; the adjoint is a mode of K2b): no trajectory is written to memory, the
     order of summation is fixed, and the same inputs give the same bits.  Covered: one transmit coil with or without
-    ``b1Map``, fp32 in both precision modes and fp64.  Several receive coils run one launch per coil and the results
-    are stacked -- a multi-coil reduction in one launch is a follow-up.  A gradient with a pulse length that is not a
+    ``b1Map``, fp32 in both precision modes and fp64.  Several receive coils share one simulation, forward and
+    adjoint: up to ``mrphy_signal_rfgr_max_rx`` coils (8) per launch, more in blocks of that many, and every coil's
+    samples are the bits a call with that coil alone gives.  A gradient with a pulse length that is not a
     multiple of the 16-step checkpoint segment is split as :func:`blochsim_rfgr_traj` splits it.  Parallel transmit,
     gradients w.r.t. ``loc``/``Δf``/``b1Map``/``rx`` and fp64 above 8 coils compose :func:`blochsim_rfgr_traj` with
     the product and the sum in torch.  On a spin axis sharded over GPUs the signal is the sum of the ranks' signals
@@ -420,10 +439,7 @@ def signal_rfgr(
         assert rx.ndim in (Mi.ndim, Mi.ndim + 1) and rx.shape[Mi.ndim - 1] == 2, "rx must be (N, *Nd, xy[, nRx])"
     route, out = _route(Mi, rf, gr, loc, every, kw, signal=True, rx=rx)
     if route == 'fused':
-        if rx is not None and rx.ndim == Mi.ndim + 1:
-            sig, Mo = torch.stack([o[0] for o in out], dim=-1), out[0][1]
-        else:
-            sig, Mo = out[0]
+        sig, Mo = out
     elif route == 'split':
         # fused part of floor(nT/16)*16 steps + composed tail of <= 15: the part's records up to n1 (its own last record
         # is one of them only if it falls on one), its final state carries on into the tail's records

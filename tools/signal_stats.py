@@ -2,14 +2,15 @@ r"""K2s / K2bs (the signal kernels of ``fused.signal_rfgr``) next to the shipped
 kernels K2t / K2bt and the composed route (trajectory + the torch reduction over the spins), each configuration in a
 fresh process, timed with HIP events:
 
-    python tools/signal_stats.py [--n 64] [--nT 2048] [--every 1,16,2048] [--reps 10] [--out FILE.json]
+    python tools/signal_stats.py [--n 64] [--nT 2048] [--every 1,16,2048] [--nrx R] [--reps 10] [--out FILE.json]
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/signal_stats.py ...
     python tools/signal_stats.py --rocprof DIR [--every ...] [--out FILE.json]     # the kernel rows of that run
 
 Configurations: ``k2ck`` (K2 writing checkpoints) and ``k2b`` (its adjoint), and per stride ``k2t`` / ``k2bt`` (the
 trajectory kernels), ``sig`` / ``sigb`` (the signal forward with checkpoints and its adjoint, cotangents on both outputs)
 and ``comp`` / ``compb`` (``fused._signal_composed``: forward, and forward + backward end to end).  fp32, the default
-(precise) mode, the synthetic cube and pulse, one receive map.  The forward is timed around the call, the adjoint around
+(precise) mode, the synthetic cube and pulse, one receive map -- with ``--nrx R`` a receive array of ``R`` coils (``rx`` gets
+a coil axis; nothing else changes, so the same file times a checkout that runs one launch per coil).  The forward is timed around the call, the adjoint around
 ``torch.autograd.grad`` (``compb`` around both).  ``--rocprof DIR`` pairs the traced processes with the configurations
 in start order and reports the kernel-only medians of the main kernel (and with its second pass).
 Each line printed is one JSON record; ``--out`` writes them all with the derived ratios."""
@@ -23,7 +24,7 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')
 FWD = ('k2ck', 'k2t', 'sig', 'comp')
 
 
-def child(cfg, n, nT, every, reps):
+def child(cfg, n, nT, every, reps, nrx=0):
     sys.path.insert(0, ROOT)
     import torch
     import mrphy_amd
@@ -35,7 +36,7 @@ def child(cfg, n, nT, every, reps):
     gr = p['gr'].clone().requires_grad_(True)
     kw = dict(Δf=sp['Δf'], γ_beff=sp['γ'], T1=sp['T1'], T2=sp['T2'], γ=sp['γ'], dt=p['dt'])
     gen = torch.Generator().manual_seed(1)
-    rx = (torch.rand(tuple(sp['M0'].shape[:-1]) + (2,), generator=gen) * 2 - 1).to(dev)
+    rx = (torch.rand(tuple(sp['M0'].shape[:-1]) + (2,) + ((nrx,) if nrx else ()), generator=gen) * 2 - 1).to(dev)
     args = (sp['M0'], rf, gr, sp['loc'])
 
     def forward():
@@ -71,7 +72,7 @@ def child(cfg, n, nT, every, reps):
         del out
     torch.cuda.synchronize()
     times = sorted(a.elapsed_time(b) for a, b in ev)
-    rec = dict(cfg=cfg, every=every or None, n=n, nT=nT, spins=n ** 3, reps=reps,
+    rec = dict(cfg=cfg, every=every or None, n=n, nT=nT, spins=n ** 3, reps=reps, nrx=nrx or None,
                median_ms=times[len(times) // 2], min_ms=times[0], max_ms=times[-1],
                peak_bytes=torch.cuda.max_memory_allocated(), precision=mrphy_amd.precision.get())
     print(json.dumps(rec), flush=True)
@@ -140,13 +141,14 @@ def main():
     ap.add_argument('--nT', type=int, default=2048)
     ap.add_argument('--every', default='1,16,2048')
     ap.add_argument('--reps', type=int, default=10)
+    ap.add_argument('--nrx', type=int, default=0, help='receive coils: rx gets a coil axis of this length (0: none)')
     ap.add_argument('--skip', default='', help='comma-separated configurations to leave out (e.g. comp,compb)')
     ap.add_argument('--out')
     ap.add_argument('--child', nargs=2, metavar=('CFG', 'EVERY'))
     ap.add_argument('--rocprof', metavar='DIR')
     a = ap.parse_args()
     if a.child:
-        return child(a.child[0], a.n, a.nT, int(a.child[1]), a.reps)
+        return child(a.child[0], a.n, a.nT, int(a.child[1]), a.reps, a.nrx)
     skip = set(a.skip.split(','))
     plan = [('k2ck', 0), ('k2b', 0)]
     for e in (int(x) for x in a.every.split(',')):
@@ -161,7 +163,7 @@ def main():
     recs = []
     for cfg, e in plan:
         cmd = [sys.executable, os.path.abspath(__file__), '--child', cfg, str(e), '--n', str(a.n), '--nT', str(a.nT),
-               '--reps', str(a.reps)]
+               '--reps', str(a.reps), '--nrx', str(a.nrx)]
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
         if r.returncode != 0:
             sys.stderr.write(r.stderr[-2000:])
