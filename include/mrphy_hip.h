@@ -625,7 +625,8 @@ int mrphy_signal_rfgr_bwd(int dtype,
                           void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * K2s-mrx  K2s for the nRx coils of a receive array in ONE launch: one simulation, every coil's samples.
+ * K2s, receive arrays  K2s for the nRx coils of a receive array in ONE launch: one simulation, every coil's samples
+ * (the same kernel at a coil capacity of nRx or more; mrphy_signal_rfgr_fwd runs it at capacity 1).
  *     sig[n, 0, j, c] = sum_s  rx_re[n,s,c] Mx[n,s] - rx_im[n,s,c] My[n,s]
  *     sig[n, 1, j, c] = sum_s  rx_re[n,s,c] My[n,s] + rx_im[n,s,c] Mx[n,s]    (M after step e_j)
  * rx (N, nM, 2, nRx) contiguous, the layout of a multi-coil b1, required; sig (N, 2, nRec, nRx), the layout of a
@@ -659,9 +660,9 @@ int mrphy_signal_rfgr_mrx_fwd(int dtype,
                               int64_t N, int64_t nM, int64_t nT, int64_t nC,
                               void* stream);
 
-/* K2bs-mrx  adjoint of K2s-mrx: mrphy_signal_rfgr_bwd with rx (N, nM, 2, nRx) and grad_sig (N, 2, nRec, nRx), in ONE
- * sweep.  As it passes step e_j backwards the sweep adds the coils' cotangents of sample j, summed in ascending c and
- * injected once:
+/* K2bs, receive arrays  adjoint of the above: mrphy_signal_rfgr_bwd with rx (N, nM, 2, nRx) and
+ * grad_sig (N, 2, nRec, nRx), in ONE sweep.  As it passes step e_j backwards the sweep adds the coils' cotangents of
+ * sample j, summed in ascending c and injected once:
  *     (sum_c rx_re,c g0,c + rx_im,c g1,c,  sum_c rx_re,c g1,c - rx_im,c g0,c,  0),   g0,c, g1,c = grad_sig[n, :, j, c]
  * The gradients equal the sum of the one-coil calls' up to the association of that sum.  Without grad_sig it is
  * mrphy_blochsim_rfgr_bwd.  Checkpoints, workspace (mrphy_blochsim_rfgr_bwd_workspace) and reduction as

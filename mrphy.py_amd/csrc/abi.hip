@@ -107,6 +107,51 @@ int rfgr_mc_bwd(bool traj, int dtype, const void* Mck, const PulseOps& in, const
     MRPHY_DISPATCH(dtype, (run_rfgr_mc_bwd<T, CT>(Mck, in, traj ? nullptr : grad_M, traj ? grad_M : nullptr, every,
                                                   grad_Mi, grad_rf, grad_gr, work, N, nM, nT, nC, st)));
 }
+
+// The signal entry points and their `_mrx_` twins (a receive array: rx with a coil axis of nRx, never null) likewise; the
+// one-coil ones pass nRx = 1.  The forward runs the smallest coil capacity that holds nRx.
+int signal_fwd(bool mrx, int dtype, const void* Mi, const PulseOps& in, const void* rx, int64_t nRx, void* Mo, void* Mck,
+               int64_t ck_every, void* sig, int64_t every, void* work, size_t work_bytes, int64_t N, int64_t nM,
+               int64_t nT, int64_t nC, void* stream)
+{
+    if (int e = check_common(dtype, N, nM, nT)) return e;
+    if (every < 1 || nC != 1 || N > 65535 || (Mck && (ck_every < 8 || ck_every % 8 != 0))) return MRPHY_EINVAL;
+    if (nRx < 1 || nRx > sig_max_rx(tsize(dtype))) return MRPHY_EINVAL;
+    if (N * nM * nT == 0) return 0;
+    if (!Mi || (mrx && !rx) || !sig || !work) return MRPHY_EINVAL;
+    if (int e = check_ops(in, true, false)) return e;
+    if (work_bytes < mrphy_signal_rfgr_mrx_fwd_workspace(dtype, N, nM, nT, every, nRx)) return MRPHY_ENOSPC;
+    hipStream_t st = (hipStream_t)stream;
+#define MRPHY_SIGNAL_FWD(R_) \
+    MRPHY_DISPATCH(dtype, (run_signal_fwd<T, CT, R_>(Mi, in, rx, nRx, Mo, Mck, ck_every, sig, every, work, N, nM, nT, st)))
+    if (nRx == 1) MRPHY_SIGNAL_FWD(1);
+    if (nRx <= 2) MRPHY_SIGNAL_FWD(2);
+    if (nRx <= 4) MRPHY_SIGNAL_FWD(4);
+    MRPHY_SIGNAL_FWD(8);
+#undef MRPHY_SIGNAL_FWD
+}
+
+int signal_bwd(bool mrx, int dtype, const void* Mck, const PulseOps& in, const void* rx, int64_t nRx, const void* grad_Mo,
+               const void* grad_sig, int64_t every, void* grad_Mi, void* grad_rf, void* grad_gr, void* work,
+               size_t work_bytes, int64_t N, int64_t nM, int64_t nT, void* stream)
+{
+    if (int e = check_common(dtype, N, nM, nT)) return e;
+    // whole checkpoint segments only; at least one of the two cotangents
+    if (nT % SEG != 0 || every < 1 || N > 65535 || (!grad_Mo && !grad_sig)) return MRPHY_EINVAL;
+    if (nRx < 1 || nRx > sig_max_rx(tsize(dtype))) return MRPHY_EINVAL;
+    if (N * nM * nT == 0) return 0;
+    if (!Mck || (mrx && !rx) || !work) return MRPHY_EINVAL;
+    if (int e = check_ops(in, true, false)) return e;
+    if (work_bytes < mrphy_blochsim_rfgr_bwd_workspace(dtype, N, nM, nT)) return MRPHY_ENOSPC;
+    hipStream_t st = (hipStream_t)stream;
+    // a receive array: the capacities 2 .. 8 are a unit of their own, which picks the smallest that holds nRx.  Without
+    // grad_sig there is nothing of the signal to inject: K2b on grad_Mo
+    if (grad_sig && nRx > 1)
+        MRPHY_DISPATCH(dtype, (run_rfgr_mrx_bwd<T, CT>(Mck, in, grad_Mo, every, rx, nRx, grad_sig, grad_Mi, grad_rf,
+                                                       grad_gr, work, N, nM, nT, st)));
+    MRPHY_DISPATCH(dtype, (run_rfgr_bwd<T, CT>(Mck, in, grad_Mo, nullptr, every, rx, grad_sig, grad_Mi, grad_rf, grad_gr,
+                                               work, N, nM, nT, st)));
+}
 }  // namespace
 
 // =============================================================================================
@@ -360,33 +405,16 @@ int mrphy_signal_rfgr_fwd(int dtype, const void* Mi, MRPHY_PULSE_OPS_PARAMS, con
                           int64_t ck_every, void* sig, int64_t every, void* work, size_t work_bytes, int64_t N,
                           int64_t nM, int64_t nT, int64_t nC, void* stream)
 {
-    if (int e = check_common(dtype, N, nM, nT)) return e;
-    if (every < 1 || nC != 1 || N > 65535 || (Mck && (ck_every < 8 || ck_every % 8 != 0))) return MRPHY_EINVAL;
-    if (N * nM * nT == 0) return 0;
-    const PulseOps in = MRPHY_PULSE_OPS;
-    if (!Mi || !sig || !work) return MRPHY_EINVAL;
-    if (int e = check_ops(in, true, false)) return e;
-    if (work_bytes < mrphy_signal_rfgr_fwd_workspace(dtype, N, nM, nT, every)) return MRPHY_ENOSPC;
-    hipStream_t st = (hipStream_t)stream;
-    MRPHY_DISPATCH(dtype, (run_signal_fwd<T, CT>(Mi, in, rx, Mo, Mck, ck_every, sig, every, work, N, nM, nT, st)));
+    return signal_fwd(false, dtype, Mi, MRPHY_PULSE_OPS, rx, 1, Mo, Mck, ck_every, sig, every, work, work_bytes, N, nM,
+                      nT, nC, stream);
 }
 
 int mrphy_signal_rfgr_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PARAMS, const void* rx, const void* grad_Mo,
                           const void* grad_sig, int64_t every, void* grad_Mi, void* grad_rf, void* grad_gr, void* work,
                           size_t work_bytes, int64_t N, int64_t nM, int64_t nT, void* stream)
 {
-    if (int e = check_common(dtype, N, nM, nT)) return e;
-    // whole checkpoint segments only; at least one of the two cotangents
-    if (nT % SEG != 0 || every < 1 || N > 65535 || (!grad_Mo && !grad_sig)) return MRPHY_EINVAL;
-    if (N * nM * nT == 0) return 0;
-    const PulseOps in = MRPHY_PULSE_OPS;
-    if (!Mck || !work) return MRPHY_EINVAL;
-    if (int e = check_ops(in, true, false)) return e;
-    if (work_bytes < mrphy_blochsim_rfgr_bwd_workspace(dtype, N, nM, nT)) return MRPHY_ENOSPC;
-    hipStream_t st = (hipStream_t)stream;
-    // without grad_sig this is K2b on grad_Mo
-    MRPHY_DISPATCH(dtype, (run_rfgr_bwd<T, CT>(Mck, in, grad_Mo, nullptr, every, rx, grad_sig, grad_Mi, grad_rf, grad_gr,
-                                               work, N, nM, nT, st)));
+    return signal_bwd(false, dtype, Mck, MRPHY_PULSE_OPS, rx, 1, grad_Mo, grad_sig, every, grad_Mi, grad_rf, grad_gr,
+                      work, work_bytes, N, nM, nT, stream);
 }
 
 int mrphy_signal_rfgr_max_rx(int dtype)
@@ -405,24 +433,8 @@ int mrphy_signal_rfgr_mrx_fwd(int dtype, const void* Mi, MRPHY_PULSE_OPS_PARAMS,
                               void* Mck, int64_t ck_every, void* sig, int64_t every, void* work, size_t work_bytes,
                               int64_t N, int64_t nM, int64_t nT, int64_t nC, void* stream)
 {
-    if (int e = check_common(dtype, N, nM, nT)) return e;
-    if (every < 1 || nC != 1 || N > 65535 || (Mck && (ck_every < 8 || ck_every % 8 != 0))) return MRPHY_EINVAL;
-    if (nRx < 1 || nRx > sig_max_rx(tsize(dtype))) return MRPHY_EINVAL;
-    if (N * nM * nT == 0) return 0;
-    const PulseOps in = MRPHY_PULSE_OPS;
-    if (!Mi || !rx || !sig || !work) return MRPHY_EINVAL;
-    if (int e = check_ops(in, true, false)) return e;
-    if (work_bytes < mrphy_signal_rfgr_mrx_fwd_workspace(dtype, N, nM, nT, every, nRx)) return MRPHY_ENOSPC;
-    hipStream_t st = (hipStream_t)stream;
-    // the smallest coil capacity that holds nRx
-    if (nRx <= 2)
-        MRPHY_DISPATCH(dtype, (run_signal_mrx_fwd<T, CT, 2>(Mi, in, rx, nRx, Mo, Mck, ck_every, sig, every, work, N, nM,
-                                                            nT, st)));
-    if (nRx <= 4)
-        MRPHY_DISPATCH(dtype, (run_signal_mrx_fwd<T, CT, 4>(Mi, in, rx, nRx, Mo, Mck, ck_every, sig, every, work, N, nM,
-                                                            nT, st)));
-    MRPHY_DISPATCH(dtype, (run_signal_mrx_fwd<T, CT, 8>(Mi, in, rx, nRx, Mo, Mck, ck_every, sig, every, work, N, nM, nT,
-                                                        st)));
+    return signal_fwd(true, dtype, Mi, MRPHY_PULSE_OPS, rx, nRx, Mo, Mck, ck_every, sig, every, work, work_bytes, N, nM,
+                      nT, nC, stream);
 }
 
 int mrphy_signal_rfgr_mrx_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PARAMS, const void* rx, int64_t nRx,
@@ -430,21 +442,8 @@ int mrphy_signal_rfgr_mrx_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PARAMS
                               void* grad_gr, void* work, size_t work_bytes, int64_t N, int64_t nM, int64_t nT,
                               void* stream)
 {
-    if (int e = check_common(dtype, N, nM, nT)) return e;
-    // whole checkpoint segments only; at least one of the two cotangents
-    if (nT % SEG != 0 || every < 1 || N > 65535 || (!grad_Mo && !grad_sig)) return MRPHY_EINVAL;
-    if (nRx < 1 || nRx > sig_max_rx(tsize(dtype))) return MRPHY_EINVAL;
-    if (N * nM * nT == 0) return 0;
-    const PulseOps in = MRPHY_PULSE_OPS;
-    if (!Mck || !rx || !work) return MRPHY_EINVAL;
-    if (int e = check_ops(in, true, false)) return e;
-    if (work_bytes < mrphy_blochsim_rfgr_bwd_workspace(dtype, N, nM, nT)) return MRPHY_ENOSPC;
-    hipStream_t st = (hipStream_t)stream;
-    if (!grad_sig)                          // nothing of the signal to inject: K2b on grad_Mo
-        MRPHY_DISPATCH(dtype, (run_rfgr_bwd<T, CT>(Mck, in, grad_Mo, nullptr, every, nullptr, nullptr, grad_Mi, grad_rf,
-                                                   grad_gr, work, N, nM, nT, st)));
-    MRPHY_DISPATCH(dtype, (run_rfgr_mrx_bwd<T, CT>(Mck, in, grad_Mo, every, rx, nRx, grad_sig, grad_Mi, grad_rf, grad_gr,
-                                                   work, N, nM, nT, st)));
+    return signal_bwd(true, dtype, Mck, MRPHY_PULSE_OPS, rx, nRx, grad_Mo, grad_sig, every, grad_Mi, grad_rf, grad_gr,
+                      work, work_bytes, N, nM, nT, stream);
 }
 
 int mrphy_beff2ab(int dtype, const void* Beff,

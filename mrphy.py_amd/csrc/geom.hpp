@@ -15,7 +15,7 @@ constexpr int SEG = 16;                           // K2 / K2b: steps per checkpo
 // adjoints (red_idx).  Both carry a static_assert; change SEG only together with them.
 constexpr int64_t K2B_MAX_WAVES = 256 * 8;        // K2b: resident waves, 8 per CU
 constexpr int64_t SIG_MAX_WAVES = 256 * 16;       // K2s (signal forward): 8 / 16 KB of LDS per wave, 16 waves per CU as K2 runs
-constexpr int SIG_MAX_RX_F32 = 8, SIG_MAX_RX_F64 = 8;   // receive coils per launch of the multi-coil signal kernels
+constexpr int SIG_MAX_RX_F32 = 8, SIG_MAX_RX_F64 = 8;   // receive coils per launch of the signal kernels
 constexpr int K2B_MAXC = 8;                       // fused adjoint: largest coil capacity
 constexpr int64_t K2B_MC_MAX_WAVES = 256 * 8;     // 18 KB of LDS per wave -> 8 per CU = 2 per SIMD
 constexpr int BWD_MAXC = 32;                      // K0 adjoint: largest coil capacity of the one-pass kernels
@@ -90,8 +90,8 @@ inline int64_t sig_waves(int64_t nM)
     return tiles < SIG_MAX_WAVES ? tiles : SIG_MAX_WAVES;
 }
 inline int64_t sig_records(int64_t nT, int64_t every) { return nT / every + (nT % every != 0); }
-// K2s-mrx / K2bs-mrx: the most receive coils one launch takes for a data type of `tsize` bytes -- the largest coil
-// capacity the kernels are built at (2, 4, 8), forward and adjoint alike (DESIGN.md section 3 has the register readings)
+// K2s / K2bs: the most receive coils one launch takes for a data type of `tsize` bytes -- the largest coil capacity the
+// kernels are built at (1, 2, 4, 8), forward and adjoint alike (DESIGN.md section 3 has the register readings)
 constexpr int sig_max_rx(size_t tsize) { return tsize == 8 ? SIG_MAX_RX_F64 : SIG_MAX_RX_F32; }
 
 inline int64_t k2b_mc_waves(int64_t nM)

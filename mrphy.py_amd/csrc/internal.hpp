@@ -50,18 +50,14 @@ int run_rfgr_bwd(const void* Mck, PulseOps in, const void* gMo, const void* gMt,
                  const void* gsig, void* gMi, void* grf, void* ggr, void* work, int64_t N, int64_t nM, int64_t nT,
                  hipStream_t st);
 
-// K2s: the received signal of the fused simulation (tu_signal.hip; one transmit coil).  Its adjoint is run_rfgr_bwd
-// with a non-null gsig (the cotangent of the samples) and the receive map rx; gMo may then be null
-template <typename T, typename CT>
-int run_signal_fwd(const void* Mi, PulseOps in, const void* rx, void* Mo, void* Mck, int64_t ck_every, void* sig,
-                   int64_t every, void* work, int64_t N, int64_t nM, int64_t nT, hipStream_t st);
-
-// K2s-mrx / K2bs-mrx: nRx <= sig_max_rx receive coils in one launch, rx (N, nM, 2, nRx), sig / gsig (N, 2, nRec, nRx).
-// The forward has one unit per coil capacity R (tu_signal_mrx2 / 4 / 8.hip); the adjoint (tu_fused_mrx_bwd.hip) picks
-// the capacity itself and needs a non-null gsig
+// K2s / K2bs: the received signal of the fused simulation (one transmit coil) for nRx <= sig_max_rx receive coils in one
+// launch, rx (N, nM, 2, nRx), sig / gsig (N, 2, nRec, nRx).  The forward has one unit per coil capacity R >= nRx
+// (tu_signal.hip: 1, where rx may be null = (1, 0); tu_signal_mrx2 / 4 / 8.hip).  Its adjoint takes a non-null
+// gsig (the cotangent of the samples) and the receive map rx, and gMo may then be null: run_rfgr_bwd for one coil,
+// run_rfgr_mrx_bwd (tu_fused_mrx_bwd.hip: the capacities 2 .. 8, the smallest that holds nRx) for more
 template <typename T, typename CT, int R>
-int run_signal_mrx_fwd(const void* Mi, PulseOps in, const void* rx, int64_t nRx, void* Mo, void* Mck, int64_t ck_every,
-                       void* sig, int64_t every, void* work, int64_t N, int64_t nM, int64_t nT, hipStream_t st);
+int run_signal_fwd(const void* Mi, PulseOps in, const void* rx, int64_t nRx, void* Mo, void* Mck, int64_t ck_every,
+                   void* sig, int64_t every, void* work, int64_t N, int64_t nM, int64_t nT, hipStream_t st);
 
 template <typename T, typename CT>
 int run_rfgr_mrx_bwd(const void* Mck, PulseOps in, const void* gMo, int64_t every, const void* rx, int64_t nRx,

@@ -37,34 +37,29 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdArgsT<T, INJ> a
         // trajectory: the latest record not yet injected, index jr, taken after step er (both wave-uniform)
         int64_t every = 0, jr = 0, er = 0;
         if constexpr (INJ == 1 || INJ == 2) { every = a.every; jr = a.nRec - 2; er = (a.nRec - 1) * every - 1; }
-        // signal (INJ == 3): every record is injected, the last one (after step nT - 1) included; the lane's receive
-        // weight, zero past nM; the cotangents of the samples through the constant address space, as the pulse
-        T rxr = vmask, rxi = T(0);
-        CP gs0 = nullptr, gs1 = nullptr;
-        if constexpr (INJ == 3) {
-            every = a.every; jr = a.nRec - 1; er = nT - 1;
-            if (a.rx) { rxr = a.rx[row * 2] * vmask; rxi = a.rx[row * 2 + 1] * vmask; }
-            gs0 = (CP)(a.gsig + n * 2 * a.nRec);
-            gs1 = gs0 + a.nRec;
-        }
-        // several receive coils (INJ >= 4, capacity R = inj_rx_cap(INJ)): the lane's R weights in registers (zero past
-        // nM and for the pad coils c >= nRx); the cotangents gsig (N, 2, nRec, nRx), a record's nRx values contiguous
-        // (declared in every mode because the sweep below reads them: one unused element each in modes 0-3, which
+        // signal (INJ >= 3, capacity R = inj_rx_cap(INJ)): every record is injected, the last one (after step nT - 1)
+        // included; the lane's R receive weights in registers (zero past nM and for the pad coils c >= nRx; no map, R = 1
+        // only: (1, 0)); the cotangents gsig (N, 2, nRec, nRx), a record's nRx values contiguous, through the constant
+        // address space, as the pulse
+        // (declared in every mode because the sweep below reads them: one unused element each in modes 0-2, which
         // compile to the instructions they had without them)
         constexpr int R = inj_rx_cap(INJ);
         T wr[R], wi[R];
-        int nrx = 0;
-        if constexpr (INJ >= 4) {
+        int nrx = 1;
+        CP gs0 = nullptr, gs1 = nullptr;
+        if constexpr (INJ >= 3) {
             every = a.every; jr = a.nRec - 1; er = nT - 1;
-            nrx = (int)a.nRx;
-            const T* q = a.rx + row * 2 * a.nRx;
+            int64_t nRx = 1;                                    // 1 <= nRx <= R
+            if constexpr (R > 1) nRx = a.nRx;
+            nrx = (int)nRx;
+            const T* q = a.rx + row * 2 * nRx;                  // (from a null rx at R = 1: formed, never dereferenced)
 #pragma unroll
             for (int c = 0; c < R; ++c) {
-                wr[c] = wi[c] = T(0);
-                if (c < nrx) { wr[c] = q[c] * vmask; wi[c] = q[a.nRx + c] * vmask; }
+                wr[c] = R == 1 ? vmask : T(0); wi[c] = T(0);
+                if ((R > 1 || a.rx) && c < nrx) { wr[c] = q[c] * vmask; wi[c] = q[nRx + c] * vmask; }
             }
-            gs0 = (CP)(a.gsig + n * 2 * a.nRec * a.nRx);
-            gs1 = gs0 + a.nRec * a.nRx;
+            gs0 = (CP)(a.gsig + n * 2 * a.nRec * nRx);
+            gs1 = gs0 + a.nRec * nRx;
         }
         adj_begin<RELAX, T, CT>(k, hx, hy, hz);
 
@@ -138,14 +133,7 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdArgsT<T, INJ> a
                                                  red[red_idx(1 * SEG + st, lane)], red[red_idx(2 * SEG + st, lane)]);
                     else if constexpr (INJ == 2) {
                         if (st == ist) adj_inject<RELAX, T, CT>(k, hx, hy, hz, ijx, ijy, ijz);
-                    } else if constexpr (INJ == 3) {
-                        if (t0 + st == er) {                            // wave-uniform
-                            const T g0 = gs0[jr], g1 = gs1[jr];
-                            adj_inject<RELAX, T, CT>(k, hx, hy, hz, rxr * g0 + rxi * g1, rxr * g1 - rxi * g0, T(0));
-                            er = (jr == a.nRec - 1) ? jr * every - 1 : er - every;
-                            --jr;
-                        }
-                    } else if constexpr (INJ >= 4) {
+                    } else if constexpr (INJ >= 3) {
                         if (t0 + st == er) {                            // wave-uniform
                             // the coils' cotangents summed in ascending c, then ONE injection: in the t = E h state of
                             // the precise modes the sum is scaled and rounded once
@@ -206,4 +194,46 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdArgsT<T, INJ> a
         if (valid && a.gMi) { a.gMi[row * 3] = hx; a.gMi[row * 3 + 1] = hy; a.gMi[row * 3 + 2] = hz; }
         first = false;
     }
+}
+
+// Host: the launcher of both units that compile this kernel.  MRX picks the unit's instantiations: false (tu_fused_bwd.hip)
+// the plain and the trajectory modes and the signal mode at capacity 1, true (tu_fused_mrx_bwd.hip) the signal mode at
+// the smallest capacity 2, 4, 8 that holds nRx (abi.hip has refused nRx > sig_max_rx = 8).  gsig (the cotangent of the
+// signal's samples, with the receive map rx) selects the signal mode, which may have no gMo; its records are counted
+// as the trajectory's.  Otherwise a null gMt runs the plain kernel.
+template <typename T, typename CT, bool MRX>
+int launch_rfgr_bwd(const void* Mck, const PulseOps& in, const void* gMo, const void* gMt, int64_t every, const void* rx,
+                    int64_t nRx, const void* gsig, void* gMi, void* grf, void* ggr, void* work, int64_t N, int64_t nM,
+                    int64_t nT, hipStream_t st)
+{
+    dim3 grid;
+    int e;
+    if (!fused_grid(N * nM * nT, k2b_waves(nM), N, grid, e)) return e;
+    FusedBwdSigArgs<T> a;
+    static_cast<FusedBwdTrajArgs<T>&>(a) = fused_bwd_args<T>(Mck, in, gMo, gMt, every, gMi, work, N, nM, nT,
+                                                             grid.x);
+    a.rx = (const T*)rx; a.gsig = (const T*)gsig; a.nRx = nRx;
+    if (gsig) a.nRec = sig_records(nT, every);
+#define MRPHY_K2B(RX_, HB_, INJ_)                                                               \
+    hipLaunchKernelGGL((k_bloch_rfgr_bwd<T, CT, RX_, HB_, INJ_>), grid, dim3(WAVE), 0, st, \
+                       (static_cast<const FusedBwdArgsT<T, INJ_>&>(a)))
+#define MRPHY_K2BT(RX_, HB_)                                                                    \
+    do {                                                                                        \
+        if constexpr (MRX) {                                                                    \
+            if (nRx <= 2) MRPHY_K2B(RX_, HB_, 4);                                               \
+            else if (nRx <= 4) MRPHY_K2B(RX_, HB_, 5);                                          \
+            else MRPHY_K2B(RX_, HB_, 6);                                                        \
+        }                                                                                       \
+        else if (gsig) MRPHY_K2B(RX_, HB_, 3);                                                  \
+        else if (!gMt) MRPHY_K2B(RX_, HB_, 0);                                                  \
+        else if (every < SEG) MRPHY_K2B(RX_, HB_, 1);                                           \
+        else MRPHY_K2B(RX_, HB_, 2);                                                            \
+    } while (0)
+    if (in.b1) { if (in.E1.p) MRPHY_K2BT(true, true);  else MRPHY_K2BT(false, true); }
+    else       { if (in.E1.p) MRPHY_K2BT(true, false); else MRPHY_K2BT(false, false); }   // no b1 map: Bxy = rf
+#undef MRPHY_K2BT
+#undef MRPHY_K2B
+    e = launch_status();
+    if (e || !(grf || ggr)) return e;
+    return launch_p2<T>(work, ggr, 3, grf, 1, N, nT, a.P, st);
 }

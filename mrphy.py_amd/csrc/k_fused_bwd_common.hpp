@@ -52,31 +52,24 @@ template <typename T>
 struct FusedBwdTrajArgs : FusedBwdArgs<T> {
     int64_t every, nRec;             // gMo is grad_Mt (nRec, N*nM, 3)
 };
-// INJ == 3 (one coil only: k_fused_bwd.hpp) is the adjoint of the signal kernel K2s (k_signal_fwd.hpp,
-// mrphy_signal_rfgr_bwd): the cotangent of record j is the same for every spin -- gsig[n, :, j], two wave-uniform
-// numbers read with scalar loads as the pulse is -- scaled by the lane's own receive weight,
-//     g = (rx_re g0 + rx_im g1,  rx_re g1 - rx_im g0,  0),
-// and enters like a trajectory record's.  No per-spin cotangent loads and no staging; the last record is injected like
-// any other (the sweep starts from grad_Mo, or from zero when that is null).
+// INJ >= 3 (one transmit coil only: k_fused_bwd.hpp) is the adjoint of the signal kernel K2s (k_signal_fwd.hpp,
+// mrphy_signal_rfgr_bwd / _mrx_bwd) at the coil capacity R = inj_rx_cap(INJ) = 1, 2, 4, 8 for INJ = 3, 4, 5, 6 (nRx <= R
+// receive coils).  The cotangent of record j is the same for every spin -- gsig[n, :, j, :], 2 nRx wave-uniform numbers
+// read with scalar loads as the pulse is -- scaled by the lane's own receive weights and summed over the coils,
+//     g = (sum_c rx_re,c g0,c + rx_im,c g1,c,  sum_c rx_re,c g1,c - rx_im,c g0,c,  0),
+// formed in ascending c (R = 1: the one term) and injected once, like a trajectory record's.  No per-spin cotangent
+// loads and no staging; the last record is injected like any other (the sweep starts from grad_Mo, or from zero when
+// that is null).
 template <typename T>
 struct FusedBwdSigArgs : FusedBwdTrajArgs<T> {
-    const T* rx;                     // (N, nM, 2) or null = (1, 0)
-    const T* gsig;                   // (N, 2, nRec)
-};
-// INJ >= 4 (one transmit coil only: k_fused_bwd.hpp, launched from tu_fused_mrx_bwd.hip) is the adjoint of the
-// multi-coil signal kernel (k_signal_mrx_fwd.hpp, mrphy_signal_rfgr_mrx_bwd): nRx <= R receive coils, R = 2, 4, 8 for
-// INJ = 4, 5, 6.  The lane injects the sum over the coils of what INJ == 3 injects for one,
-//     g = (sum_c rx_re,c g0,c + rx_im,c g1,c,  sum_c rx_re,c g1,c - rx_im,c g0,c,  0),
-// formed in ascending c and injected once.
-template <typename T>
-struct FusedBwdMrxArgs : FusedBwdSigArgs<T> {   // rx (N, nM, 2, nRx), gsig (N, 2, nRec, nRx)
+    const T* rx;                     // (N, nM, 2, nRx); R = 1 only: or null = (1, 0)
+    const T* gsig;                   // (N, 2, nRec, nRx)
     int64_t nRx;
 };
-constexpr int inj_rx_cap(int INJ) { return INJ == 4 ? 2 : INJ == 5 ? 4 : INJ == 6 ? 8 : 1; }
+constexpr int inj_rx_cap(int INJ) { return INJ < 3 ? 1 : 1 << (INJ - 3); }
 template <typename T, int INJ>
 using FusedBwdArgsT = std::conditional_t<INJ == 0, FusedBwdArgs<T>,
-                      std::conditional_t<INJ == 3, FusedBwdSigArgs<T>,
-                      std::conditional_t<(INJ >= 4), FusedBwdMrxArgs<T>, FusedBwdTrajArgs<T>>>>;
+                      std::conditional_t<(INJ >= 3), FusedBwdSigArgs<T>, FusedBwdTrajArgs<T>>>;
 // the kernarg layout is part of the kernels' machine code: `in` sits where its twelve fields were written out
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winvalid-offsetof"
@@ -86,8 +79,7 @@ constexpr bool fused_bwd_args_layout =
     sizeof(FusedBwdArgs<T>) == 240 && offsetof(FusedBwdTrajArgs<T>, every) == 240 &&
     offsetof(FusedBwdTrajArgs<T>, nRec) == 248 && sizeof(FusedBwdTrajArgs<T>) == 256 &&
     offsetof(FusedBwdSigArgs<T>, rx) == 256 && offsetof(FusedBwdSigArgs<T>, gsig) == 264 &&
-    sizeof(FusedBwdSigArgs<T>) == 272 && offsetof(FusedBwdMrxArgs<T>, gsig) == 264 &&
-    offsetof(FusedBwdMrxArgs<T>, nRx) == 272 && sizeof(FusedBwdMrxArgs<T>) == 280;
+    offsetof(FusedBwdSigArgs<T>, nRx) == 272 && sizeof(FusedBwdSigArgs<T>) == 280;
 #pragma clang diagnostic pop
 static_assert(fused_bwd_args_layout<float> && fused_bwd_args_layout<double>, "K2b's kernel arguments moved");
 

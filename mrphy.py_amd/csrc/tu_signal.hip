@@ -1,48 +1,3 @@
-// tu_signal.hip -- K2s: launcher of mrphy_signal_rfgr_fwd (the received signal of the fused simulation, one transmit
-// coil, no or one receive coil) and its second pass
-#include "host_common.hpp"
-
-namespace {
-#include "k_signal_fwd.hpp"
-}  // namespace
-
-namespace mrphy_i {
-
-template <typename T, typename CT>
-int run_signal_fwd(const void* Mi, PulseOps in, const void* rx, void* Mo, void* Mck, int64_t ck_every, void* sig,
-                   int64_t every, void* work, int64_t N, int64_t nM, int64_t nT, hipStream_t st)
-{
-    dim3 grid;
-    int e;
-    if (!fused_grid(N * nM * nT, sig_waves(nM), N, grid, e)) return e;
-    SignalArgs<T> a;
-    a.Mi = (const T*)Mi; a.in = typed<T>(in); a.rx = (const T*)rx; a.Mo = (T*)Mo; a.Mck = (T*)Mck;
-    a.ck_every = ck_every > 0 ? ck_every : 1;
-    a.work = (T*)work; a.every = every; a.nRec = sig_records(nT, every);
-    a.N = N; a.nM = nM; a.nT = nT; a.P = grid.x;
-#define MRPHY_K2S(CK_, RX_, HB_, EV_) \
-    hipLaunchKernelGGL((k_signal_fwd<T, CT, CK_, RX_, HB_, EV_>), grid, dim3(WAVE), 0, st, a)
-#define MRPHY_K2S_EV(CK_, RX_, HB_)                                                              \
-    do {                                                                                         \
-        if (every == 1) MRPHY_K2S(CK_, RX_, HB_, true); else MRPHY_K2S(CK_, RX_, HB_, false);    \
-    } while (0)
-#define MRPHY_K2S_HB(CK_, RX_)                                                                   \
-    do {                                                                                         \
-        if (in.b1) MRPHY_K2S_EV(CK_, RX_, true); else MRPHY_K2S_EV(CK_, RX_, false);             \
-    } while (0)
-    const bool ck = (Mck != nullptr), rlx = (in.E1.p != nullptr);
-    if (ck) { if (rlx) MRPHY_K2S_HB(true, true); else MRPHY_K2S_HB(true, false); }
-    else    { if (rlx) MRPHY_K2S_HB(false, true); else MRPHY_K2S_HB(false, false); }
-#undef MRPHY_K2S_HB
-#undef MRPHY_K2S_EV
-#undef MRPHY_K2S
-    e = launch_status();
-    if (e) return e;
-    return launch_p2<T>(work, nullptr, 0, sig, 1, N, a.nRec, a.P, st);   // sig (N, 2, nRec): one coil's (re, im)
-}
-
-}  // namespace mrphy_i
-
-#define MRPHY_INST(T_, CT_) template int mrphy_i::run_signal_fwd<T_, CT_>(const void* Mi, PulseOps in, const void* rx, void* Mo, void* Mck, int64_t ck_every, void* sig, int64_t every, void* work, int64_t N, int64_t nM, int64_t nT, hipStream_t st);
-MRPHY_FOR_DTYPES(MRPHY_INST)
-#undef MRPHY_INST
+// tu_signal.hip -- K2s at a capacity of 1 receive coil (or none): launcher of mrphy_signal_rfgr_fwd
+#define MRPHY_RX_CAP 1
+#include "tu_signal.hpp"

@@ -1,3 +1,3 @@
-// tu_signal_mrx4.hip -- K2s-mrx at a capacity of 4 receive coils: launcher of mrphy_signal_rfgr_mrx_fwd
-#define MRPHY_MRX_CAP 4
-#include "tu_signal_mrx.hpp"
+// tu_signal_mrx4.hip -- K2s at a capacity of 4 receive coils: launcher of mrphy_signal_rfgr_mrx_fwd
+#define MRPHY_RX_CAP 4
+#include "tu_signal.hpp"

@@ -1,8 +1,8 @@
-r"""K2s-mrx / the multi-coil signal mode of K2b: ``fused.signal_rfgr`` with a receive array -- every coil from one launch per
-block of ``mrphy_signal_rfgr_max_rx`` coils.  The forward against the one-coil launches (bit for bit) and the fp64
-reduction of the trajectory's own records; the number of launches; gradients against the composed route, the oracle and
-the sum of the one-coil calls' gradients; more tiles than persistent waves; the C ABI called directly; empty problems;
-hipGraph capture."""
+r"""K2s / the signal mode of K2b at the coil capacities 2, 4, 8: ``fused.signal_rfgr`` with a receive array -- every coil from
+one launch per block of ``mrphy_signal_rfgr_max_rx`` coils.  The forward against the one-coil launches (capacity 1 of the
+same kernel: bit for bit) and the fp64 reduction of the trajectory's own records; the number of launches; gradients
+against the composed route, the oracle and the sum of the one-coil calls' gradients; more tiles than persistent waves; the
+C ABI called directly, also with one coil; empty problems; hipGraph capture; where the tile is flushed, at every capacity."""
 import collections
 import contextlib
 
@@ -10,7 +10,7 @@ import pytest
 
 from gpu_common import *  # noqa: F401,F403
 from mrphy_amd import _host, _lib as L, beffective
-from mrphy_amd.fused import _forward_prep, _signal_composed, _traj_ends
+from mrphy_amd.fused import _forward_prep, _signal_composed, _signal_of, _traj_ends
 from test_fused_traj import _problem, _kw, _weights
 from test_signal import _sig64, _grad_run, _check_grads, NAMES
 
@@ -314,3 +314,90 @@ def test_signal_mrx_hipgraph_capture():
     g.replay()
     torch.cuda.synchronize()
     assert torch.equal(a0, a1) and torch.equal(b0, b1)
+
+
+# =============================================================================================
+# 8. the `_mrx_` entry points with one coil: capacity 1, the one-coil entry points' bits
+# =============================================================================================
+@pytest.mark.parametrize('tag_mode', ['f64', 'f32-precise', 'f32-fast'])
+def test_signal_mrx_entry_points_with_one_coil_are_the_one_coil_entry_points(tag_mode):
+    r"""mrphy_signal_rfgr_mrx_fwd / _mrx_bwd at nRx = 1 against mrphy_signal_rfgr_fwd / _bwd through ctypes on the same
+    device buffers (N = 1, nM = 100: a tail tile with masked lanes, nT = 48, every = 1, 3, 16, with checkpoints): all
+    return 0, and ``sig``, ``Mo``, the checkpoints, ``grad_Mi``, ``grad_rf`` and ``grad_gr`` are the same bits.  Outputs
+    start as NaN, so an element left unwritten fails the comparison."""
+    from mrphy_amd import sims
+    tag, mode = _mode(tag_mode)
+    lib = mrphy_amd.require_library()
+    n, nT, dt_ = 1, 48, DT[tag]
+    P = _problem(tag, 'b1map', nT, N=n)
+    rxd = dev(_rxn(tag, 1, n=n)).contiguous()              # (1, nM, 2, 1): the memory of a one-coil (1, nM, 2)
+    kw = _kw(P, dev)
+    new = lambda *s: torch.full(s, float('nan'), dtype=dt_, device=DEV)  # noqa: E731
+    with mode:
+        p = beffective._PulseOnSpins(dev(P['rf']), dev(P['gr']), dev(P['loc']), kw['Δf'], kw['b1Map'], kw['γ_beff'])
+        cs = sims.relax_constants(kw['T1'], kw['T2'], kw['γ'], kw['dt'], 4, DEV)
+        code, alive, consts, Mck, (_, ck) = _forward_prep(lib, p, *cs, dt_, DEV, True)
+    Mi = dev(P['M0']).contiguous()
+    st = _host.current_stream(DEV)
+    nbb = lib.mrphy_blochsim_rfgr_bwd_workspace(code, n, NM, nT)
+    for every in (1, 3, 16):
+        nRec = len(_traj_ends(nT, every))
+        nb = lib.mrphy_signal_rfgr_fwd_workspace(code, n, NM, nT, every)
+        assert nb == lib.mrphy_signal_rfgr_mrx_fwd_workspace(code, n, NM, nT, every, 1)
+        w, v = dev(_weights((n, 2, nRec), dt_)), dev(_weights((n, NM, 3), dt_))
+        got = []
+        for mrx in ((), (1,)):
+            sig, Mo, Mck_ = new(n, 2, nRec, *mrx), new(n, NM, 3), torch.full_like(Mck, float('nan'))
+            work = torch.empty(nb, dtype=torch.uint8, device=DEV)
+            fwd = lib.mrphy_signal_rfgr_mrx_fwd if mrx else lib.mrphy_signal_rfgr_fwd
+            rc = fwd(code, Mi.data_ptr(), *p.k0_args(), *consts, rxd.data_ptr(), *mrx, Mo.data_ptr(), Mck_.data_ptr(),
+                     ck, sig.data_ptr(), every, work.data_ptr(), nb, n, NM, nT, 1, st)
+            assert rc == 0, (every, mrx)
+            gMi, grf, ggr = new(n, NM, 3), new(n, 2, nT, 1), new(n, 3, nT)
+            work = torch.empty(nbb, dtype=torch.uint8, device=DEV)
+            bwd = lib.mrphy_signal_rfgr_mrx_bwd if mrx else lib.mrphy_signal_rfgr_bwd
+            rc = bwd(code, Mck_.data_ptr(), *p.k0_args(), *consts, rxd.data_ptr(), *mrx, v.data_ptr(), w.data_ptr(), every,
+                     gMi.data_ptr(), grf.data_ptr(), ggr.data_ptr(), work.data_ptr(), nbb, n, NM, nT, st)
+            assert rc == 0, (every, mrx)
+            torch.cuda.synchronize()
+            got.append((sig.reshape(n, 2, nRec), Mo, Mck_, gMi, grf, ggr))
+        for a, b, nm in zip(*got, ('sig', 'Mo', 'Mck', 'grad_Mi', 'grad_rf', 'grad_gr')):
+            assert torch.equal(a, b), (every, nm)
+    del alive
+
+
+# =============================================================================================
+# 9. where the tile is flushed, at every capacity
+# =============================================================================================
+@pytest.mark.parametrize('tag_mode', ['f64', 'f32-precise', 'f32-fast'])
+@pytest.mark.parametrize('nT', [40, 35])
+def test_signal_flush_rule_at_every_capacity(tag_mode, nT):
+    r"""N = 1, nM = 64 + 36, nRx = 1, 2, 3, 8 (the capacities 1, 2, 4, 8) x every = 1, 2, 5, 16, 17, forward only: at the
+    small strides a tile of 16 / R records fills and is flushed during the pulse, before a step batch or inside it
+    according to the capacity and the data type; nT = 35 adds the nT % 8 (fp64: nT % 4) tail loop.  ``sig[..., c]`` is the
+    bits of the one-coil call for coil ``c``, and is held to ``_signal_of`` of ``blochsim_rfgr_traj``'s records (formed
+    in fp64) at test_signal_forward's gates: assert_close and, in fp32, the elementwise (nM + 3) 2^-24 Σ|terms| bound."""
+    tag, mode = _mode(tag_mode)
+    n = 1
+    P = _problem(tag, 'b1map', nT, N=n)
+    rx = _rxn(tag, 8, n=n)
+    kw = _kw(P, dev)
+    args = (dev(P['M0']), dev(P['rf']), dev(P['gr']), dev(P['loc']))
+    with mode, torch.no_grad():
+        for every in (1, 2, 5, 16, 17):
+            nRec = len(_traj_ends(nT, every))
+            Mt = fused.blochsim_rfgr_traj(*args, every=every, **kw)
+            ref = _signal_of(Mt.movedim(-2, 0).double(), dev(rx).double()).cpu()       # (1, 2, nRec, 8), fp64
+            A64 = torch.stack([_sig64(Mt, rx[..., c])[1] for c in range(8)], dim=-1)
+            one = [fused.signal_rfgr(*args, every=every, rx=dev(rx[..., c]), **kw) for c in range(8)]
+            for nRx in (1, 2, 3, 8):
+                sig = fused.signal_rfgr(*args, every=every, rx=dev(rx[..., :nRx]), **kw)
+                assert sig.shape == (n, 2, nRec, nRx), (every, nRx)
+                for c in range(nRx):
+                    assert torch.equal(sig[..., c], one[c]), (every, nRx, c, 'sig vs the one-coil call')
+                    assert_close(sig[..., c], ref[..., c], tag, f'sig vs _signal_of (every={every}, nRx={nRx}, coil {c})')
+                if tag == 'f32':                     # the worst element of the nRx coils, as a fraction of its bound
+                    ratio = float(((sig.double().cpu() - ref[..., :nRx]).abs()
+                                   / ((NM + 3) * 2.0 ** -24 * A64[..., :nRx])).max())
+                    record(f'signal.flush.{tag_mode}.nT{nT}.every{every}.nRx{nRx}.elementwise_over_bound', ratio, 1.0)
+                    assert ratio <= 1.0, (every, nRx, ratio)

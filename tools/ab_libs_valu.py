@@ -4,7 +4,8 @@ fp32 precise: fused forward K2 (64^3 x 2048, 128^3 x 1024), fused forward + adjo
 fused forward + adjoint (64^3 x 1024); fp64: K2 and K2 + K2b (64^3 x 1024).  Norms printed to compare bits.
     python tools/ab_libs_valu.py --bits LIB_A.so LIB_B.so ...
 no timing: the integer-view sums of the outputs and of grad_Mi, grad_rf, grad_gr of fused.blochsim_rfgr_traj (every 1, 5,
-16; one coil and 2 coils) and fused.signal_rfgr (every 1, 16, with a receive map) at 2048 * 64 + 100 spins x 48 steps --
+16; one coil and 2 coils) and fused.signal_rfgr (every 1, 16, with a receive map and with a receive array of 3 coils) at
+2048 * 64 + 100 spins x 48 steps --
 a ragged last tile and more tiles than the adjoints have persistent waves -- in fp32 precise and fp64, one child process
 per library; the last line says whether every library gave the same sums."""
 import os, subprocess, sys
@@ -45,9 +46,10 @@ def fingerprints():
         kw = dict(Δf=df, T1=0.5 + rnd(1, nM), T2=0.02 + 0.1 * rnd(1, nM), γ=torch.tensor(4257.6, dtype=dt, device=dev),
                   dt=torch.tensor([4e-6], dtype=dt, device=dev))
         kw['γ_beff'] = kw['γ']
-        gr, rxm = rnd(1, 3, nT) * 2 - 1, rnd(1, nM, 2) * 2 - 1
+        gr, rxm, rxm3 = rnd(1, 3, nT) * 2 - 1, rnd(1, nM, 2) * 2 - 1, rnd(1, nM, 2, 3) * 2 - 1
         cases = [(f'traj every={e} nC={nC}', nC, e, None) for nC in (1, 2) for e in (1, 5, 16)] + \
-                [(f'signal every={e}', 1, e, rxm) for e in (1, 16)]
+                [(f'signal every={e}', 1, e, rxm) for e in (1, 16)] + \
+                [(f'signal every={e} 3 receive coils', 1, e, rxm3) for e in (1, 16)]
         with mrphy_amd.precision(mode):
             for label, nC, every, rx in cases:
                 rf = (rnd(1, 2, nT) * 2 - 1) * 3 if nC == 1 else (rnd(1, 2, nT, nC) * 2 - 1) * 1.5
