@@ -72,7 +72,8 @@ extern "C" {
  *      mrphy_signal_rfgr_fwd_workspace, mrphy_signal_rfgr_fwd, mrphy_signal_rfgr_bwd (the received signal of K2:
  *      the transverse magnetisation summed over the spins, sample by sample); mrphy_signal_rfgr_max_rx,
  *      mrphy_signal_rfgr_mrx_fwd_workspace, mrphy_signal_rfgr_mrx_fwd, mrphy_signal_rfgr_mrx_bwd (the same for the coils
- *      of a receive array from ONE simulation per launch). */
+ *      of a receive array from ONE simulation per launch); mrphy_blochsim_rfgr_maps_bwd (K2b / K2bt of one transmit
+ *      coil, which also returns the gradients w.r.t. loc, df and b1). */
 #define MRPHY_ABI_VERSION 5
 
 #define MRPHY_F32      0  /* T = float,  CT = float                                          */
@@ -537,6 +538,39 @@ int mrphy_blochsim_rfgr_traj_bwd(int dtype,
                                  const void* E1m1,
                                  const void* grad_Mt, int64_t every,
                                  void* grad_Mi, void* grad_rf, void* grad_gr,
+                                 void* work, size_t work_bytes,
+                                 int64_t N, int64_t nM, int64_t nT,
+                                 void* stream);
+/* K2b / K2bt with the gradients w.r.t. the spin-side operands (one transmit coil): mrphy_blochsim_rfgr_bwd (a null
+ * grad_Mt; grad_Mo is read) or mrphy_blochsim_rfgr_traj_bwd (a null grad_Mo; grad_Mt and `every` are read), and in the
+ * same sweep
+ *     grad_loc (N, nM, 3)   dL/dloc[n,s,i]      = sum_t gBz[n,s,t] * gr[n,i,t]
+ *     grad_Bz  (N, nM)      dL/d(df/gamma)[n,s] = sum_t gBz[n,s,t]        (the caller divides by gamma for dL/d df)
+ *     grad_b1  (N, nM, 2)   dL/db1[n,s,0] = sum_t gBx*rf_re + gBy*rf_im,  dL/db1[n,s,1] = sum_t gBy*rf_re - gBx*rf_im
+ * where (gBx, gBy, gBz)[n,s,t] is the dL/dBeff that the two-kernel route would have written to memory.  Each of the
+ * three is optional (null: not wanted), as grad_Mi, grad_rf, grad_gr are -- which come out bit for bit as the entry
+ * points above give them.  The sums over time are lane-private, in a fixed order (the 16 steps of a checkpoint segment,
+ * then the segments, both descending): the same inputs give the same bits.  Same checkpoints, same workspace
+ * (mrphy_blochsim_rfgr_bwd_workspace).  The entry point has no coil count: rf is (N|1, 2, nT, 1) and b1 (N, nM, 2) or
+ * null, as for mrphy_blochsim_rfgr_bwd; parallel transmit has no such build.  MRPHY_EINVAL: what
+ * mrphy_blochsim_rfgr_traj_bwd refuses (every < 1 with a grad_Mt, nT not a whole number of segments, null operands),
+ * both or neither of grad_Mo and grad_Mt, a grad_b1 without a b1 map; MRPHY_ENOSPC: workspace too small.  An empty
+ * problem is a success that writes nothing. */
+int mrphy_blochsim_rfgr_maps_bwd(int dtype,
+                                 const void* Mck,
+                                 const void* rf, int64_t rf_sn,
+                                 const void* gr, int64_t gr_sn,
+                                 const void* loc,
+                                 const void* df, int64_t df_sn, int64_t df_sm,
+                                 const void* gamma, int64_t gamma_sn, int64_t gamma_sm,
+                                 const void* b1,
+                                 const void* g,  int64_t g_sn,  int64_t g_sm,
+                                 const void* E1, int64_t E1_sn, int64_t E1_sm,
+                                 const void* E2, int64_t E2_sn, int64_t E2_sm,
+                                 const void* E1m1,
+                                 const void* grad_Mo, const void* grad_Mt, int64_t every,
+                                 void* grad_Mi, void* grad_rf, void* grad_gr,
+                                 void* grad_loc, void* grad_Bz, void* grad_b1,
                                  void* work, size_t work_bytes,
                                  int64_t N, int64_t nM, int64_t nT,
                                  void* stream);

@@ -25,7 +25,7 @@ _vp, _i64, _int, _sz = _c.c_void_p, _c.c_int64, _c.c_int, _c.c_size_t
 _BC = [_vp, _i64, _i64]            # broadcastable per-spin constant: ptr, stride_n, stride_m
 # the operands of the fused family, rf .. E1m1 of mrphy_hip.h: rf, rf_sn, gr, gr_sn, loc, df, gamma, b1, g, E1, E2, E1m1
 _PULSE_OPS = [_vp, _i64, _vp, _i64, _vp] + _BC + _BC + [_vp] + _BC * 3 + [_vp]
-_FUSED = [_int, _vp] + _PULSE_OPS  # how its eight entry points begin: dtype, Mi (the adjoints: Mck), the operands
+_FUSED = [_int, _vp] + _PULSE_OPS  # how the fused entry points begin: dtype, Mi (the adjoints: Mck), the operands
 
 # name -> (restype, argtypes); MUST list every function declared in include/mrphy_hip.h
 PROTOTYPES = {
@@ -61,6 +61,7 @@ PROTOTYPES = {
     'mrphy_blochsim_rfgr_mc_bwd': (_int, _FUSED + [_vp, _vp, _vp, _vp, _vp, _sz] + [_i64] * 4 + [_vp]),
     'mrphy_blochsim_rfgr_traj_fwd': (_int, _FUSED + [_vp, _vp, _i64, _vp, _i64] + [_i64] * 4 + [_vp]),
     'mrphy_blochsim_rfgr_traj_bwd': (_int, _FUSED + [_vp, _i64, _vp, _vp, _vp, _vp, _sz] + [_i64] * 3 + [_vp]),
+    'mrphy_blochsim_rfgr_maps_bwd': (_int, _FUSED + [_vp, _vp, _i64] + [_vp] * 6 + [_vp, _sz] + [_i64] * 3 + [_vp]),
     'mrphy_blochsim_rfgr_mc_traj_bwd': (_int, _FUSED + [_vp, _i64, _vp, _vp, _vp, _vp, _sz] + [_i64] * 4 + [_vp]),
     'mrphy_signal_rfgr_fwd_workspace': (_sz, [_int] + [_i64] * 4),
     'mrphy_signal_rfgr_fwd': (_int, _FUSED + [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _sz] + [_i64] * 4 + [_vp]),
@@ -106,6 +107,7 @@ UNITS = [(f, m) for f, masks in (
     ('tu_fused_mc_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_fused_fwd1.hip', (_F32, _C64, _P, _PC64)),
     ('tu_fused_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
+    ('tu_fused_maps_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_signal.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_fused_mrx_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_signal_mrx8.hip', (_F32, _F64, _C64, _P, _PC64)),

@@ -93,6 +93,23 @@ int rfgr_bwd(bool traj, int dtype, const void* Mck, const PulseOps& in, const vo
                                                nullptr, nullptr, grad_Mi, grad_rf, grad_gr, work, N, nM, nT, st)));
 }
 
+// The MAPS builds: grad_Mo (mode 0) or grad_Mt (modes 1, 2), exactly one of them; refuses what rfgr_bwd refuses, and a
+// grad_b1 without a b1 map to differentiate
+int rfgr_maps_bwd(int dtype, const void* Mck, const PulseOps& in, const void* grad_Mo, const void* grad_Mt, int64_t every,
+                  void* grad_Mi, void* grad_rf, void* grad_gr, void* grad_loc, void* grad_Bz, void* grad_b1, void* work,
+                  size_t work_bytes, int64_t N, int64_t nM, int64_t nT, void* stream)
+{
+    if (int e = check_common(dtype, N, nM, nT)) return e;
+    if (nT % SEG != 0 || (grad_Mt && every < 1) || (grad_Mo && grad_Mt) || (grad_b1 && !in.b1)) return MRPHY_EINVAL;
+    if (N * nM * nT == 0) return 0;
+    if (!Mck || !(grad_Mo || grad_Mt) || !work) return MRPHY_EINVAL;
+    if (int e = check_ops(in, true, false)) return e;
+    if (work_bytes < mrphy_blochsim_rfgr_bwd_workspace(dtype, N, nM, nT)) return MRPHY_ENOSPC;
+    hipStream_t st = (hipStream_t)stream;
+    MRPHY_DISPATCH(dtype, (run_rfgr_maps_bwd<T, CT>(Mck, in, grad_Mo, grad_Mt, every, grad_Mi, grad_rf, grad_gr, grad_loc,
+                                                    grad_Bz, grad_b1, work, N, nM, nT, st)));
+}
+
 int rfgr_mc_bwd(bool traj, int dtype, const void* Mck, const PulseOps& in, const void* grad_M, int64_t every,
                 void* grad_Mi, void* grad_rf, void* grad_gr, void* work, size_t work_bytes, int64_t N, int64_t nM,
                 int64_t nT, int64_t nC, void* stream)
@@ -385,6 +402,15 @@ int mrphy_blochsim_rfgr_traj_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PAR
 {
     return rfgr_bwd(true, dtype, Mck, MRPHY_PULSE_OPS, grad_Mt, every, grad_Mi, grad_rf, grad_gr, work, work_bytes, N,
                     nM, nT, stream);
+}
+
+int mrphy_blochsim_rfgr_maps_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PARAMS, const void* grad_Mo,
+                                 const void* grad_Mt, int64_t every, void* grad_Mi, void* grad_rf, void* grad_gr,
+                                 void* grad_loc, void* grad_Bz, void* grad_b1, void* work, size_t work_bytes, int64_t N,
+                                 int64_t nM, int64_t nT, void* stream)
+{
+    return rfgr_maps_bwd(dtype, Mck, MRPHY_PULSE_OPS, grad_Mo, grad_Mt, every, grad_Mi, grad_rf, grad_gr, grad_loc,
+                         grad_Bz, grad_b1, work, work_bytes, N, nM, nT, stream);
 }
 
 int mrphy_blochsim_rfgr_mc_traj_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PARAMS, const void* grad_Mt,

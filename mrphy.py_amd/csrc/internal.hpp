@@ -50,6 +50,13 @@ int run_rfgr_bwd(const void* Mck, PulseOps in, const void* gMo, const void* gMt,
                  const void* gsig, void* gMi, void* grf, void* ggr, void* work, int64_t N, int64_t nM, int64_t nT,
                  hipStream_t st);
 
+// the MAPS builds of K2b / K2bt (tu_fused_maps_bwd.hip): run_rfgr_bwd's plain and trajectory modes, which also return
+// the gradients w.r.t. the spin-side operands -- gloc (N, nM, 3), gBz (N, nM), gb1 (N, nM, 2), each may be null
+template <typename T, typename CT>
+int run_rfgr_maps_bwd(const void* Mck, PulseOps in, const void* gMo, const void* gMt, int64_t every, void* gMi, void* grf,
+                      void* ggr, void* gloc, void* gBz, void* gb1, void* work, int64_t N, int64_t nM, int64_t nT,
+                      hipStream_t st);
+
 // K2s / K2bs: the received signal of the fused simulation (one transmit coil) for nRx <= sig_max_rx receive coils in one
 // launch, rx (N, nM, 2, nRx), sig / gsig (N, 2, nRec, nRx).  The forward has one unit per coil capacity R >= nRx
 // (tu_signal.hip: 1, where rx may be null = (1, 0); tu_signal_mrx2 / 4 / 8.hip).  Its adjoint takes a non-null

@@ -4,9 +4,17 @@
 #pragma once
 #include "k_fused_bwd_common.hpp"
 
-template <typename T, typename CT, bool RELAX, bool HB1, int INJ>
-__global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdArgsT<T, INJ> a)
+// MAPS (modes 0 .. 2 only; tu_fused_maps_bwd.hip): the same sweep also gives the gradients w.r.t. the lane's own
+// loc, df / gamma and b1.  They are the (g0, g1, g2) = dL/dB that every step forms for grad_gr / grad_rf, summed over
+// TIME instead of over the wave's spins: lane-private running sums, no LDS, no workspace, no second pass, and a fixed
+// order of summation.  Two levels: the 16 steps of a segment go into partials that start at zero (steps descending),
+// the partials into the running sums once per segment (segments descending) -- the sequential sum's rounding error then
+// grows with 16 + nT / 16 terms, not nT.  Lanes past nM carry a zero cotangent, so their sums are exact zeros; their
+// stores are guarded by `valid`.  Everything the MAPS = false build computes is computed by the same expressions.
+template <typename T, typename CT, bool RELAX, bool HB1, int INJ, bool MAPS = false>
+__global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdKArgsT<T, INJ, MAPS> a)
 {
+    static_assert(!MAPS || INJ < 3, "the map gradients are built for the plain and the trajectory modes");
     __shared__ __attribute__((aligned(16))) T red[5 * SEG * RED_PITCH];
     const int lane = threadIdx.x;
     const int64_t w = blockIdx.x, n = blockIdx.y;
@@ -62,6 +70,10 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdArgsT<T, INJ> a
             gs1 = gs0 + a.nRec * nRx;
         }
         adj_begin<RELAX, T, CT>(k, hx, hy, hz);
+        // MAPS: the running sums over time, reset per tile -- aZ = sum g2, aL = sum g2 gr_i, and with a b1 map
+        // (aBr, aBi) = sum (g0 rf_re + g1 rf_im, g1 rf_re - g0 rf_im), the transpose of field_xy_acc's product
+        // (one unused element each without MAPS, as wr / wi above)
+        T aZ = T(0), aL[3] = {T(0), T(0), T(0)}, aBr = T(0), aBi = T(0);
 
         auto field = [&](int64_t t, T& Bx, T& By, T& Bz) { field_1coil<HB1>(br, bi, pc, t, sp, Bx, By, Bz); };
 
@@ -115,6 +127,7 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdArgsT<T, INJ> a
             // 1. forward recompute, keeping the state before each step
             SegStates<T> h;
             seg_recompute<RELAX>(k, t0, mx, my, mz, field, h);
+            T pZ = T(0), pL[3] = {T(0), T(0), T(0)}, pBr = T(0), pBi = T(0);      // MAPS: this segment's partial sums
             // 2. adjoint sweep, contributions to LDS
 #pragma unroll
             for (int sb = SEG / 4 - 1; sb >= 0; --sb) {
@@ -158,7 +171,22 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdArgsT<T, INJ> a
                     red[red_idx(2 * SEG + st, lane)] = sp.lz * g2;
                     red[red_idx(3 * SEG + st, lane)] = HB1 ? br * g0 + bi * g1 : g0;
                     red[red_idx(4 * SEG + st, lane)] = HB1 ? br * g1 - bi * g0 : g1;
+                    if constexpr (MAPS) {
+                        // the step's pulse sample: the wave-uniform scalars `field` read above
+                        const int64_t t = t0 + st;
+                        pZ += g2;
+                        pL[0] += g2 * pc.gx[t]; pL[1] += g2 * pc.gy[t]; pL[2] += g2 * pc.gz[t];
+                        if constexpr (HB1) {
+                            const T rr = pc.rfr[t], ri = pc.rfi[t];
+                            pBr += g0 * rr + g1 * ri;
+                            pBi += g1 * rr - g0 * ri;
+                        }
+                    }
                 }
+            }
+            if constexpr (MAPS) {
+                aZ += pZ; aL[0] += pL[0]; aL[1] += pL[1]; aL[2] += pL[2];
+                if constexpr (HB1) { aBr += pBr; aBi += pBi; }
             }
             __syncthreads();
             // 3. 80 row sums: lanes 0..63 take rows 0..63, then lane (r, j) chain j of row 64 + r
@@ -192,6 +220,14 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdArgsT<T, INJ> a
         }
         adj_end<RELAX, T, CT>(k, hx, hy, hz);
         if (valid && a.gMi) { a.gMi[row * 3] = hx; a.gMi[row * 3 + 1] = hy; a.gMi[row * 3 + 2] = hz; }
+        if constexpr (MAPS) {
+            // once per spin; each output optional.  gBz is dL/d(df / gamma): the division by gamma and the folds to
+            // the operands' own shapes are the host's
+            if (valid && a.gloc) { a.gloc[row * 3] = aL[0]; a.gloc[row * 3 + 1] = aL[1]; a.gloc[row * 3 + 2] = aL[2]; }
+            if (valid && a.gBz) a.gBz[row] = aZ;
+            if constexpr (HB1)
+                if (valid && a.gb1) { a.gb1[row * 2] = aBr; a.gb1[row * 2 + 1] = aBi; }
+        }
         first = false;
     }
 }
@@ -233,6 +269,38 @@ int launch_rfgr_bwd(const void* Mck, const PulseOps& in, const void* gMo, const 
     else       { if (in.E1.p) MRPHY_K2BT(true, false); else MRPHY_K2BT(false, false); }   // no b1 map: Bxy = rf
 #undef MRPHY_K2BT
 #undef MRPHY_K2B
+    e = launch_status();
+    if (e || !(grf || ggr)) return e;
+    return launch_p2<T>(work, ggr, 3, grf, 1, N, nT, a.P, st);
+}
+
+// Host: the launcher of the MAPS builds (tu_fused_maps_bwd.hip): modes 0 .. 2 chosen as launch_rfgr_bwd chooses them,
+// the same grid, workspace and second pass; gloc (N, nM, 3), gBz (N, nM), gb1 (N, nM, 2) each optional (abi.hip has
+// refused a gb1 without a b1 map).
+template <typename T, typename CT>
+int launch_rfgr_maps_bwd(const void* Mck, const PulseOps& in, const void* gMo, const void* gMt, int64_t every, void* gMi,
+                         void* grf, void* ggr, void* gloc, void* gBz, void* gb1, void* work, int64_t N, int64_t nM,
+                         int64_t nT, hipStream_t st)
+{
+    dim3 grid;
+    int e;
+    if (!fused_grid(N * nM * nT, k2b_waves(nM), N, grid, e)) return e;
+    FusedBwdMapsArgs<T> a;
+    static_cast<FusedBwdTrajArgs<T>&>(a) = fused_bwd_args<T>(Mck, in, gMo, gMt, every, gMi, work, N, nM, nT,
+                                                             grid.x);
+    a.gloc = (T*)gloc; a.gBz = (T*)gBz; a.gb1 = (T*)gb1;
+#define MRPHY_K2BM(RX_, HB_, INJ_) \
+    hipLaunchKernelGGL((k_bloch_rfgr_bwd<T, CT, RX_, HB_, INJ_, true>), grid, dim3(WAVE), 0, st, a)
+#define MRPHY_K2BMT(RX_, HB_)                                                                   \
+    do {                                                                                        \
+        if (!gMt) MRPHY_K2BM(RX_, HB_, 0);                                                      \
+        else if (every < SEG) MRPHY_K2BM(RX_, HB_, 1);                                          \
+        else MRPHY_K2BM(RX_, HB_, 2);                                                           \
+    } while (0)
+    if (in.b1) { if (in.E1.p) MRPHY_K2BMT(true, true);  else MRPHY_K2BMT(false, true); }
+    else       { if (in.E1.p) MRPHY_K2BMT(true, false); else MRPHY_K2BMT(false, false); }
+#undef MRPHY_K2BMT
+#undef MRPHY_K2BM
     e = launch_status();
     if (e || !(grf || ggr)) return e;
     return launch_p2<T>(work, ggr, 3, grf, 1, N, nT, a.P, st);

@@ -70,6 +70,17 @@ constexpr int inj_rx_cap(int INJ) { return INJ < 3 ? 1 : 1 << (INJ - 3); }
 template <typename T, int INJ>
 using FusedBwdArgsT = std::conditional_t<INJ == 0, FusedBwdArgs<T>,
                       std::conditional_t<(INJ >= 3), FusedBwdSigArgs<T>, FusedBwdTrajArgs<T>>>;
+// MAPS builds of the one-coil kernel in modes 0 .. 2 (k_fused_bwd.hpp; mrphy_blochsim_rfgr_maps_bwd): the gradients
+// w.r.t. the spin-side operands, one value set per spin, each pointer may be null (not wanted).  Mode 0 takes this
+// struct as well (every, nRec unused): one argument type per build family.
+template <typename T>
+struct FusedBwdMapsArgs : FusedBwdTrajArgs<T> {
+    T* gloc;                         // (N, nM, 3): dL/dloc
+    T* gBz;                          // (N, nM): dL/d(df / gamma) = sum over time of dL/dBz
+    T* gb1;                          // (N, nM, 2): dL/db1; builds with a b1 map only
+};
+template <typename T, int INJ, bool MAPS>
+using FusedBwdKArgsT = std::conditional_t<MAPS, FusedBwdMapsArgs<T>, FusedBwdArgsT<T, INJ>>;
 // the kernarg layout is part of the kernels' machine code: `in` sits where its twelve fields were written out
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winvalid-offsetof"
@@ -80,8 +91,15 @@ constexpr bool fused_bwd_args_layout =
     offsetof(FusedBwdTrajArgs<T>, nRec) == 248 && sizeof(FusedBwdTrajArgs<T>) == 256 &&
     offsetof(FusedBwdSigArgs<T>, rx) == 256 && offsetof(FusedBwdSigArgs<T>, gsig) == 264 &&
     offsetof(FusedBwdSigArgs<T>, nRx) == 272 && sizeof(FusedBwdSigArgs<T>) == 280;
+template <typename T>
+constexpr bool fused_bwd_maps_args_layout =
+    offsetof(FusedBwdMapsArgs<T>, every) == 240 && offsetof(FusedBwdMapsArgs<T>, nRec) == 248 &&
+    offsetof(FusedBwdMapsArgs<T>, gloc) == 256 && offsetof(FusedBwdMapsArgs<T>, gBz) == 264 &&
+    offsetof(FusedBwdMapsArgs<T>, gb1) == 272 && sizeof(FusedBwdMapsArgs<T>) == 280;
 #pragma clang diagnostic pop
 static_assert(fused_bwd_args_layout<float> && fused_bwd_args_layout<double>, "K2b's kernel arguments moved");
+static_assert(fused_bwd_maps_args_layout<float> && fused_bwd_maps_args_layout<double>,
+              "the MAPS builds' kernel arguments moved");
 
 // the arguments of K2b / K2bt (host side, shared by tu_fused_bwd.hip and tu_fused_mc_bwd.hip): a null gMt selects the
 // plain kernel (INJ == 0), which takes the FusedBwdArgs part; otherwise gMt is the cotangent the kernel reads

@@ -11,10 +11,14 @@ adjoint ``mrphy_blochsim_rfgr_bwd``: the forward leaves a checkpoint of ``M`` ev
 (0.75 B per spin-step instead of the 12 B/spin-step history plus the 24 B/spin-step of ``Beff`` and
 ``grad_Beff`` of the two-kernel path), each segment is recomputed in registers and swept backwards,
 and ``grad_rf``/``grad_gr`` come out of a deterministic reduction over spins; parallel transmit
-(``rf`` `(N,xy,nT,nCoils)` with a ``b1Map``, up to 8 coils) has its own kernel.  Cases the fused
-adjoint does not cover (more coils, gradients w.r.t. the spin-side maps) compose ``rfgr2beff`` and
-``blochsim`` instead -- HIP kernels as well; a pulse length that is not a multiple of 16 is split
-into a fused part and a tail of at most 15 composed steps.
+(``rf`` `(N,xy,nT,nCoils)` with a ``b1Map``, up to 8 coils) has its own kernel.  With one transmit coil
+the same sweep also gives the gradients w.r.t. the spin-side maps ``loc``, ``Δf`` and ``b1Map``
+(``mrphy_blochsim_rfgr_maps_bwd``): they are the per-step ``dL/dBeff`` the sweep holds in registers,
+summed over time per spin in a fixed order, so neither ``Beff`` nor ``grad_Beff`` is ever written.
+Cases the fused adjoint does not cover (more coils, map gradients under parallel transmit, pulses
+shorter than 16 steps with a map gradient) compose ``rfgr2beff`` and ``blochsim`` instead -- HIP
+kernels as well; a pulse length that is not a multiple of 16 is split into a fused part and a tail
+of at most 15 composed steps.
 
 :func:`blochsim_rfgr_traj` is the same simulation with the magnetisation recorded during the pulse (the history
 ``Mhst`` the reference forms inside ``BlochSim.forward`` and drops, ``sims.py:83,131``), differentiable through the
@@ -81,6 +85,38 @@ def _empty_problem_grads(grads, gMo):
             g.zero_()
 
 
+def _like(x):
+    r"""What the backward needs of an operand to shape its gradient: ``(shape, dtype, device)``."""
+    return tuple(x.shape), x.dtype, x.device
+
+
+def _maps_backward_prep(p, needs, dtype, device):
+    r"""The per-spin outputs of ``mrphy_blochsim_rfgr_maps_bwd`` that ``needs`` (loc, Δf, b1Map) asks for:
+    ``(gloc (N, *Nd, 3), gBz (N, *Nd), gb1 (N, *Nd, 2))`` -- ``None`` where not wanted -- and their pointers."""
+    full = (p.N,) + p.Nd
+    outs = tuple(torch.empty(full + tail, dtype=dtype, device=device) if want else None
+                 for want, tail in zip(needs, ((3,), (), (2,))))
+    return outs, tuple(None if x is None else x.data_ptr() for x in outs)
+
+
+def _fold_map_grads(gloc, gBz, gb1, p, likes):
+    r"""``(grad_loc, grad_Δf, grad_b1Map)`` in the shapes, dtypes and on the devices the caller's operands had
+    (``likes``: their :func:`_like`, ``None`` for an absent one): ``grad_Δf = gBz / γ_beff`` summed over the axes
+    ``Δf`` was broadcast along (``beffective.py:161-165``); ``grad_b1Map`` likewise, with the trailing coil axis of
+    length 1 if the map had one."""
+    from .beffective import _sum_to
+    out = [None, None, None]
+    if gloc is not None:
+        out[0] = gloc.to(device=likes[0][2], dtype=likes[0][1])
+    if gBz is not None:
+        out[1] = _sum_to(gBz / p.gam_v, likes[1][0]).to(device=likes[1][2], dtype=likes[1][1])
+    if gb1 is not None:
+        shape = likes[2][0]
+        g = gb1[..., None] if len(shape) == 1 + len(p.Nd) + 2 else gb1
+        out[2] = _sum_to(g, shape).to(device=likes[2][2], dtype=likes[2][1])
+    return tuple(out)
+
+
 def _fold_grads(gMi, g_rf, g_gr, p, rf_shape, gr_shape, rf_dtype, gr_dtype):
     r"""``(grad_Mi, grad_rf, grad_gr)`` in the shapes and dtypes the caller's ``rf`` and ``gr`` had."""
     from .beffective import _fold_pulse_grad
@@ -90,15 +126,20 @@ def _fold_grads(gMi, g_rf, g_gr, p, rf_shape, gr_shape, rf_dtype, gr_dtype):
 
 
 class BlochSimRfGrHIP(Function):
-    r"""``M = BlochSimRfGrHIP.apply(Mi, rf, gr, pulse_on_spins, γ2πdt, E1, E2, E1_1, want_ckpt, every)``
+    r"""``M = BlochSimRfGrHIP.apply(Mi, rf, gr, pulse_on_spins, γ2πdt, E1, E2, E1_1, want_ckpt, every[, loc, Δf, b1Map])``
 
     ``every = None``: ``M`` is ``Mo`` (``mrphy_blochsim_rfgr_fwd`` / ``_bwd``); an int: the trajectory, time-major
     ``(nRec, N, *Nd, 3)`` (the ``_traj_`` entry points).  ``want_ckpt`` is decided by the caller
     (:func:`_route`: a gradient w.r.t. ``Mi``, ``rf`` or ``gr`` is wanted, grad mode is on and the fused adjoint
-    covers the case) -- NOT re-derived from ``ctx.needs_input_grad``, which stays ``True`` under ``torch.no_grad()``."""
+    covers the case) -- NOT re-derived from ``ctx.needs_input_grad``, which stays ``True`` under ``torch.no_grad()``.
+
+    ``loc``, ``Δf``, ``b1Map``: the caller's own tensors, handed over only when one of them wants a gradient through
+    the fused adjoint (one transmit coil; ``pulse_on_spins`` holds their detached, normalised copies, which is what
+    the kernels read).  The backward then runs ``mrphy_blochsim_rfgr_maps_bwd`` in place of the two entry points
+    above -- the same sweep, the same bits for ``grad_Mi``, ``grad_rf``, ``grad_gr``."""
 
     @staticmethod
-    def forward(ctx, Mi, rf, gr, p, γ2πdt, E1, E2, E1_1, want_ckpt=False, every=None):
+    def forward(ctx, Mi, rf, gr, p, γ2πdt, E1, E2, E1_1, want_ckpt=False, every=None, loc=None, Δf=None, b1Map=None):
         lib = _lib.require_library()
         device, dtype = Mi.device, Mi.dtype
         need = bool(want_ckpt)
@@ -117,13 +158,15 @@ class BlochSimRfGrHIP(Function):
         if need:
             ctx.save_for_backward(Mck)
             ctx.keep = (p, code, consts, alive, rf.shape, gr.shape, rf.dtype, gr.dtype, every)
+            ctx.maps_like = tuple(None if x is None else _like(x) for x in (loc, Δf, b1Map))
         return M
 
     @staticmethod
     def backward(ctx, grad_M):
         needs = ctx.needs_input_grad[0:3]
-        if not any(needs):
-            return (None,) * 10
+        needs_maps = tuple(ctx.needs_input_grad[10:13])     # loc, Δf, b1Map: all False where they were not handed over
+        if not any(needs) and not any(needs_maps):
+            return (None,) * 13
         lib = _lib.require_library()
         (Mck,) = ctx.saved_tensors
         p, code, consts, _alive, rf_shape, gr_shape, rf_dtype, gr_dtype, every = ctx.keep
@@ -136,9 +179,26 @@ class BlochSimRfGrHIP(Function):
         gM = grad_M.to(dtype).contiguous()      # the trajectory's: time-major, as the forward returned it -- free if so
         grads, outs, work = _backward_prep(lib, p, code, needs, dtype, device)
         tr = (every,) if traj else ()
+        pulse_grads = lambda: _fold_grads(*grads, p, rf_shape, gr_shape, rf_dtype, gr_dtype)  # noqa: E731
+        if any(needs_maps):                     # one transmit coil (_route): the MAPS builds of K2b / K2bt
+            mgrads, mouts = _maps_backward_prep(p, needs_maps, dtype, device)
+            if p.N * p.nM * p.nT == 0:          # nothing depends on the maps either
+                _empty_problem_grads(grads, None if traj else gM)
+                for g in mgrads:
+                    if g is not None:
+                        g.zero_()
+            else:
+                name = 'mrphy_blochsim_rfgr_maps_bwd'
+                gMo, gMt, ev = (None, gM.data_ptr(), every) if traj else (gM.data_ptr(), None, 0)
+                with torch.cuda.device(device):
+                    rc = lib.mrphy_blochsim_rfgr_maps_bwd(code, Mck.data_ptr(), *p.k0_args(), *consts, gMo, gMt, ev,
+                                                          *outs, *mouts, work.data_ptr(), work.numel(),
+                                                          p.N, p.nM, p.nT, _host.current_stream(device))
+                _lib.check(rc, name)
+            return (*pulse_grads(), *(None,) * 7, *_fold_map_grads(*mgrads, p, ctx.maps_like))
         if p.N * p.nM * p.nT == 0:
             _empty_problem_grads(grads, None if traj else gM)
-            return (*_fold_grads(*grads, p, rf_shape, gr_shape, rf_dtype, gr_dtype), *(None,) * 7)
+            return (*pulse_grads(), *(None,) * 10)
         if p.nC == 1:
             name, nc = ('mrphy_blochsim_rfgr_traj_bwd' if traj else 'mrphy_blochsim_rfgr_bwd'), ()
         else:                                   # parallel transmit
@@ -148,7 +208,7 @@ class BlochSimRfGrHIP(Function):
                                     work.data_ptr(), work.numel(), p.N, p.nM, p.nT, *nc,
                                     _host.current_stream(device))
         _lib.check(rc, name)
-        return (*_fold_grads(*grads, p, rf_shape, gr_shape, rf_dtype, gr_dtype), *(None,) * 7)
+        return (*pulse_grads(), *(None,) * 10)
 
 
 class SignalRfGrHIP(Function):
@@ -220,10 +280,11 @@ class SignalRfGrHIP(Function):
 def _route(Mi, rf, gr, loc, every, kw, signal=False, rx=None):
     r"""The routing :func:`blochsim_rfgr` (``every = None``), :func:`blochsim_rfgr_traj` and (``signal``, with its
     receive map ``rx``) :func:`signal_rfgr` share.  Returns
-    ``('split', n1)``: a pulse gradient through the fused adjoint, but a length that is not a whole number of
-    checkpoint segments -- the caller runs the first ``n1`` steps fused and composes the tail; ``('composed', None)``:
-    a case the fused kernels do not cover (gradients w.r.t. the spin-side maps, fp64 with more than 8 coils, a pulse
-    gradient the fused adjoint cannot form); or ``('fused', M)``, the result of :class:`BlochSimRfGrHIP` -- for the
+    ``('split', n1)``: a gradient through the fused adjoint, but a length that is not a whole number of
+    checkpoint segments -- the caller runs the first ``n1`` steps fused and composes the tail (autograd adds the two
+    parts' gradients w.r.t. the maps); ``('composed', None)``: a case the fused kernels do not cover (gradients w.r.t.
+    the spin-side maps under parallel transmit, in the signal call or with fewer than 16 steps, fp64 with more than 8
+    coils, a pulse gradient the fused adjoint cannot form); or ``('fused', M)``, the result of :class:`BlochSimRfGrHIP` -- for the
     signal :class:`SignalRfGrHIP`'s ``(sig, Mo)``.  An ``rx`` with a coil axis of two or more runs one application per
     block of up to ``mrphy_signal_rfgr_max_rx(code)`` coils -- one forward and one backward launch for all of a
     block's coils; ``sig`` is the blocks' concatenated on the coil axis, ``Mo`` the first block's, and autograd adds the
@@ -236,7 +297,8 @@ def _route(Mi, rf, gr, loc, every, kw, signal=False, rx=None):
     lib = _lib.require_library()
     grad_on = torch.is_grad_enabled()
     rq = lambda x: grad_on and isinstance(x, Tensor) and x.requires_grad  # noqa: E731
-    maps_grad = any(rq(x) for x in (loc, Δf, b1Map)) or (signal and rq(rx))
+    maps_grad = any(rq(x) for x in (loc, Δf, b1Map))
+    rx_grad = signal and rq(rx)
     pulse_grad = any(rq(x) for x in (Mi, rf, gr))
     p = beffective._PulseOnSpins(rf.detach(), gr.detach(), loc.detach(),
                                  None if Δf is None else Δf.detach(),
@@ -246,12 +308,17 @@ def _route(Mi, rf, gr, loc, every, kw, signal=False, rx=None):
     one_coil = p.nC == 1 and (rf.ndim == 3 or b1Map is not None or rf.shape[-1] == 1)
     ptx = 1 < p.nC <= int(lib.mrphy_blochsim_rfgr_mc_max_coils()) and p.b1 is not None and not signal
     fused_adjoint_ok = seg_ok and (one_coil or ptx)
-    if pulse_grad and not maps_grad and not seg_ok and (one_coil or ptx) and p.nT > seg:
+    # the map gradients come out of the one-coil adjoint's sweep (the MAPS builds of K2b / K2bt); the signal call keeps
+    # its composed route for them, whose trajectory takes this one
+    maps_fused = maps_grad and one_coil and not signal
+    if not seg_ok and p.nT > seg and not rx_grad and \
+            (maps_fused or (pulse_grad and not maps_grad and (one_coil or ptx))):
         return 'split', (p.nT // seg) * seg
     # fp64 with more than 8 transmit coils: the fused forward has no register build for it (it would spill),
     # the composed route does (k_rfgr2beff_steps / _pk + K1) and gives the same bits
     wide_f64 = (p.dtype == torch.float64 and p.nC > 8) or (p.b1 is not None and p.nC > 64)   # (> 64: coil-blocked K0 + K1)
-    if maps_grad or wide_f64 or (pulse_grad and not fused_adjoint_ok) or (signal and p.nC != 1):
+    if (maps_grad and not (maps_fused and seg_ok)) or rx_grad or wide_f64 or (pulse_grad and not fused_adjoint_ok) \
+            or (signal and p.nC != 1):
         return 'composed', None
 
     device, dtype = Mi.device, Mi.dtype
@@ -261,7 +328,7 @@ def _route(Mi, rf, gr, loc, every, kw, signal=False, rx=None):
         γ2πdt, E1, E2, E1_1 = (kw['consts'].get(k) for k in ('γ2πdt', 'E1', 'E2', 'E1_1'))
     else:
         γ2πdt, E1, E2, E1_1 = sims.relax_constants(T1, T2, kw['γ'], kw['dt'], 1 + len(p.Nd) + 2, device)
-    want = pulse_grad and fused_adjoint_ok
+    want = (pulse_grad or maps_fused) and fused_adjoint_ok
     if signal:
         apply = lambda r: SignalRfGrHIP.apply(Mi, rf, gr, p, r, γ2πdt, E1, E2, E1_1, want, every)  # noqa: E731
         if rx is None:
@@ -278,6 +345,8 @@ def _route(Mi, rf, gr, loc, every, kw, signal=False, rx=None):
         cap = int(lib.mrphy_signal_rfgr_max_rx(_lib.F64 if dtype == torch.float64 else _lib.F32))
         outs = [apply(r[..., c:c + cap].contiguous()) for c in range(0, nrx, cap)]
         return 'fused', (outs[0][0] if len(outs) == 1 else torch.cat([o[0] for o in outs], dim=-1), outs[0][1])
+    if maps_fused:
+        return 'fused', BlochSimRfGrHIP.apply(Mi, rf, gr, p, γ2πdt, E1, E2, E1_1, want, every, loc, Δf, b1Map)
     return 'fused', BlochSimRfGrHIP.apply(Mi, rf, gr, p, γ2πdt, E1, E2, E1_1, want, every)
 
 
@@ -289,7 +358,10 @@ def blochsim_rfgr(
     γ: Tensor = γH, dt: Tensor = dt0, consts: Optional[dict] = None
 ) -> Tensor:
     r"""``blochsim(Mi, rfgr2beff(rf, gr, loc, Δf=Δf, b1Map=b1Map, γ=γ_beff), T1=T1, T2=T2,
-    γ=γ, dt=dt)`` without the intermediate tensor, differentiable w.r.t. ``Mi``, ``rf``, ``gr``.
+    γ=γ, dt=dt)`` without the intermediate tensor, differentiable w.r.t. ``Mi``, ``rf``, ``gr`` and the spin-side
+    maps ``loc``, ``Δf``, ``b1Map`` (with one transmit coil through the fused adjoint, which sums the sweep's
+    ``dL/dBeff`` over time per spin; parallel transmit and pulses shorter than 16 steps through ``rfgr2beff`` +
+    ``blochsim``).  ``γ_beff`` is not differentiated here.
 
     ``Mi``: `(N, *Nd, xyz)`; the other arguments as in
     :func:`mrphy_amd.beffective.rfgr2beff` and :func:`mrphy_amd.sims.blochsim`.  ``consts``
@@ -342,15 +414,17 @@ def blochsim_rfgr_traj(
     r"""The magnetisation trajectory of :func:`blochsim_rfgr`: ``Mt`` `(N, *Nd, nRec, xyz)`, ``nRec =
     ceil(nT / every)``, where ``Mt[..., j, :]`` is M after step ``min((j+1)·every, nT) - 1`` -- so the last record
     is the final state, equal to ``blochsim_rfgr(...)`` bit for bit, and ``every = 1`` gives the reference's
-    history ``Mhst`` (``sims.py:83``).  Differentiable w.r.t. ``Mi``, ``rf``, ``gr`` (and, through the composed
-    route, the spin-side maps); operands, dtypes, ``consts`` and the precision mode as :func:`blochsim_rfgr`.
+    history ``Mhst`` (``sims.py:83``).  Differentiable w.r.t. ``Mi``, ``rf``, ``gr`` and the spin-side maps ``loc``,
+    ``Δf``, ``b1Map`` (one transmit coil: the fused adjoint, one launch whatever ``every`` is); operands, dtypes,
+    ``consts`` and the precision mode as :func:`blochsim_rfgr`.
 
     Layout: the result is a view ``.movedim(0, -2)`` of time-major storage `(nRec, N, *Nd, 3)` -- each record is
     one contiguous block, which the kernel writes with coalesced per-wave stores.  ``Mt.movedim(-2, 0)`` gives the
     contiguous tensor back; a loss that keeps that layout hands its gradient to the adjoint without a copy.
 
-    The cases the fused adjoint does not cover (gradients w.r.t. ``loc``/``Δf``/``b1Map``, a parallel-transmit
-    gradient with more coils than ``mrphy_blochsim_rfgr_mc_max_coils()``, fp64 with more than 8 coils) run one
+    The cases the fused adjoint does not cover (gradients w.r.t. ``loc``/``Δf``/``b1Map`` under parallel transmit or
+    with fewer than 16 steps, a parallel-transmit gradient with more coils than
+    ``mrphy_blochsim_rfgr_mc_max_coils()``, fp64 with more than 8 coils) run one
     :func:`blochsim_rfgr` per record segment and stack the results: correct and differentiable, slower.  A pulse
     length that is not a multiple of the 16-step checkpoint segment is split as :func:`blochsim_rfgr` splits it.
     """
@@ -428,7 +502,8 @@ def signal_rfgr(
     samples are the bits a call with that coil alone gives.  A gradient with a pulse length that is not a
     multiple of the 16-step checkpoint segment is split as :func:`blochsim_rfgr_traj` splits it.  Parallel transmit,
     gradients w.r.t. ``loc``/``Δf``/``b1Map``/``rx`` and fp64 above 8 coils compose :func:`blochsim_rfgr_traj` with
-    the product and the sum in torch.  On a spin axis sharded over GPUs the signal is the sum of the ranks' signals
+    the product and the sum in torch (with one transmit coil and map gradients that trajectory is one fused forward
+    and one fused adjoint, not one simulation per record).  On a spin axis sharded over GPUs the signal is the sum of the ranks' signals
     (``dist.all_reduce_pulse_grads`` reduces tensors of this size).
     """
     if isinstance(every, bool) or not isinstance(every, int) or every < 1:

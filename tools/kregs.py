@@ -4,7 +4,8 @@ unit objects `mrphy_amd.build()` leaves under mrphy.py_amd/build/ (no recompilat
     python tools/kregs.py [filter] [--scratch] [--objdir DIR]
     python tools/kregs.py [filter] --diff DIR_A DIR_B
 
-`--scratch` lists only kernels with a private segment (spills); the exit code is then the number found.
+The filter is looked for in the kernel's demangled name and in its unit object's name (`maps`: the kernels of
+tu_fused_maps_bwd.hip).  `--scratch` lists only kernels with a private segment (spills); the exit code is then the number found.
 `--objdir DIR` reads the unit objects of another build instead.
 `--diff` compares two builds kernel by kernel (by unit object and kernel name): the register / LDS / scratch figures
 and the count of every opcode of the disassembly; it names each kernel that differs with the opcodes and counts, and
@@ -105,7 +106,7 @@ if __name__ == '__main__':
     n = 0
     ks = kernels(objdir)
     for obj, name, m in ks:
-        if flt not in name or (only_scratch and not m['private_segment_fixed_size']):
+        if (flt not in name and flt not in obj) or (only_scratch and not m['private_segment_fixed_size']):
             continue
         n += 1
         vg = m['vgpr_count']
