@@ -9,6 +9,10 @@ namespace mrphy {
 constexpr int WAVE = 64;
 constexpr int HIST_STEP = 3 * WAVE;               // history: elements per time step of one 64-spin tile
 constexpr int AB_HIST_STEP = 12 * WAVE;           // beff2ab history: the 3x4 state per step and tile
+// Line-granular K1 / K1h / K3 (k_lines.hpp): a piece = one LINE_BYTES line per spin = LINE_ELEMS<T> elements; three
+// pieces = LINE_ELEMS<T> steps are one period, and a pulse must be whole periods (lines_shape_ok, host_common.hpp).
+constexpr int LINE_BYTES = 128;
+template <typename T> constexpr int LINE_ELEMS = LINE_BYTES / (int)sizeof(T);
 constexpr int SEG = 16;                           // K2 / K2b: steps per checkpoint segment
 // Generic in SEG: K2 (k_fused_fwd.hpp: only the checkpoint stride), the checkpoint / workspace size queries.
 // NOT generic: k_bloch_rfgr_bwd_mc (step = lane >> 2, needs SEG * 4 == WAVE) and the reduction tile of both fused

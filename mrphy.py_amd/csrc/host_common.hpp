@@ -48,16 +48,21 @@ inline int check_common(int dtype, int64_t N, int64_t nM, int64_t nT)
     return 0;
 }
 
-// rows on 128-B lines and whole 32-step periods: what the line-granular kernels need
+// What the line-granular kernels need (k_lines.hpp; the constants are geom.hpp's): rows on whole lines, whole periods
+// of LINE_ELEMS<T> steps, and a tile of WAVE rows within the 32-bit byte offsets of the mover.
+template <typename T>
 inline bool lines_shape_ok(const void* Beff, int64_t nT)
 {
-    return aligned_to(Beff, 128) && nT > 0 && (nT % 32 == 0) && (768 * nT < (int64_t)4294967295);
+    return aligned_to(Beff, LINE_BYTES) && nT > 0 && (nT % LINE_ELEMS<T> == 0) &&
+           ((int64_t)(WAVE * 3 * sizeof(T)) * nT < (int64_t)4294967295);
 }
 
-// ... and for the fp64 line kernels: 16-step periods (a 128-B line = 16 doubles)
-inline bool lines_shape_ok_f64(const void* Beff, int64_t nT)
+// XCD-contiguous tile order (xcd_tile, k_common.hpp): the grid padded to 8 equal shares; returns the share
+inline unsigned xcd_pad(dim3& grid)
 {
-    return aligned_to(Beff, 128) && nT > 0 && (nT % 16 == 0) && (1536 * nT < (int64_t)4294967295);
+    const unsigned per_xcd = (grid.x + 7) / 8;
+    grid.x = per_xcd * 8;
+    return per_xcd;
 }
 
 }  // namespace

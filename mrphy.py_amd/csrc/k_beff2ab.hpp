@@ -48,11 +48,7 @@ __global__ __launch_bounds__(WAVE) void k_beff2ab(AbArgs<T> a)
     __shared__ __attribute__((aligned(16))) T tile[TL::ELEMS];
 
     const int lane = threadIdx.x;
-    const int64_t row0 = (int64_t)blockIdx.x * WAVE;
-    const int64_t r = row0 + lane;
-    const bool valid = r < a.rows;
-    const int64_t rc = valid ? r : a.rows - 1;
-    const int64_t n = rc / a.nM, s = rc % a.nM;
+    const auto [row0, r, valid, rc, n, s] = row_id((int64_t)blockIdx.x, lane, a.rows, a.nM);
     const SpinConst<T, CT> k = load_consts<T, CT>(a.g, a.E1, a.E2, a.E1m1, n, s);
     SpinConst<T, CT> kl = k;
     kl.e1m1 = typename CTr<CT>::reg(0);                                 // the A columns: linear part only
@@ -146,11 +142,7 @@ __global__ __launch_bounds__(WAVE) void k_beff2ab_bwd(AbBwdArgs<T> a)
     __shared__ __attribute__((aligned(16))) T tileB[TL::ELEMS];
 
     const int lane = threadIdx.x;
-    const int64_t row0 = (int64_t)blockIdx.x * WAVE;
-    const int64_t r = row0 + lane;
-    const bool valid = r < a.rows;
-    const int64_t rc = valid ? r : a.rows - 1;
-    const int64_t n = rc / a.nM, s = rc % a.nM;
+    const auto [row0, r, valid, rc, n, s] = row_id((int64_t)blockIdx.x, lane, a.rows, a.nM);
     const SpinConst<T, CT> k = load_consts<T, CT>(a.g, a.E1, a.E2, nullptr, n, s);
 
     T hx[4], hy[4], hz[4];                              // dL/d(state), column j

@@ -2,6 +2,7 @@
 // Fragment: included INSIDE a translation unit's anonymous namespace, after host_common.hpp (HIP runtime,
 // include/mrphy_hip.h, geom.hpp, bloch_math.hpp, k_common.hpp).  Not a standalone header.
 #pragma once
+#include "k_lines.hpp"     // the Beff line mover of the line-granular kernels
 
 // =============================================================================================
 // K3: blochsim backward.  Reads Beff and Mpre chunks (two tiles), sweeps time backwards,
@@ -31,11 +32,7 @@ __global__ __launch_bounds__(WAVE) void k_bloch_bwd(BwdArgs<T> a)
     __shared__ __attribute__((aligned(16))) T tileB[TL::ELEMS];
 
     const int lane = threadIdx.x;
-    const int64_t row0 = (int64_t)blockIdx.x * WAVE;
-    const int64_t r = row0 + lane;
-    const bool valid = r < a.rows;
-    const int64_t rc = valid ? r : a.rows - 1;
-    const int64_t n = rc / a.nM, s = rc % a.nM;
+    const auto [row0, r, valid, rc, n, s] = row_id((int64_t)blockIdx.x, lane, a.rows, a.nM);
     const SpinConst<T, CT> k = load_consts<T, CT>(a.g, a.E1, a.E2, nullptr, n, s);
 
     T hx = a.gMo[rc * 3 + 0], hy = a.gMo[rc * 3 + 1], hz = a.gMo[rc * 3 + 2];
@@ -143,12 +140,11 @@ template <typename T>
 struct HistBatchT {
     T m0[HB_MAX], m1[HB_MAX], m2[HB_MAX];
 };
-using HistBatch = HistBatchT<float>;
 
 template <int NA, typename T>
 __device__ __forceinline__ void hist_fetch(const T* hp, int64_t th, HistBatchT<T>& h)
 {
-    static_assert(NA <= HB_MAX, "batch larger than HistBatch");
+    static_assert(NA <= HB_MAX, "batch larger than HistBatchT");
 #pragma unroll
     for (int j = 0; j < NA; ++j) hist_load<T>(hp, th + j, h.m0[j], h.m1[j], h.m2[j]);
 }
@@ -180,7 +176,7 @@ __device__ __forceinline__ void lines_adj_carry(const SpinConst<T, CT>& k, T b0,
                                                 T& hx, T& hy, T& hz, T& g0,
                                                 T& g1, T& g2)
 {
-    static_assert(NA + 1 <= HB_MAX, "batch larger than HistBatch");
+    static_assert(NA + 1 <= HB_MAX, "batch larger than HistBatchT");
     T Bx[NA + 1], By[NA + 1], Bz[NA + 1];
     Bx[0] = b0; By[0] = b1; Bz[0] = b2;
 #pragma unroll
@@ -203,73 +199,35 @@ template <typename CT, bool RELAX>
 __global__ __launch_bounds__(WAVE, 3) void k_bloch_bwd_lines(BwdArgs<float> a)
 {
     using T = float;
-    constexpr int PF = 32;
-    constexpr int PITCH = PF + 4;
-    __shared__ __attribute__((aligned(16))) T tile[WAVE * PITCH];
+    using LM = LineMover<T>;
+    constexpr int PF = LM::PF;
+    __shared__ __attribute__((aligned(16))) T tile[WAVE * LM::PITCH];
 
     const int lane = threadIdx.x;
     const int64_t tile_id = xcd_tile(a.per_xcd);
     if (tile_id * WAVE >= a.rows) return;
-    const int64_t row0 = tile_id * WAVE;
-    const int64_t r = row0 + lane;
-    const bool valid = r < a.rows;
-    const int64_t rc = valid ? r : a.rows - 1;
-    const int64_t n = rc / a.nM, s = rc % a.nM;
+    const auto [row0, r, valid, rc, n, s] = row_id(tile_id, lane, a.rows, a.nM);
     const SpinConst<T, CT> k = load_consts<T, CT>(a.g, a.E1, a.E2, nullptr, n, s);
     T hx = a.gMo[rc * 3 + 0], hy = a.gMo[rc * 3 + 1], hz = a.gMo[rc * 3 + 2];
     adj_begin<RELAX, T, CT>(k, hx, hy, hz);
 
     const int64_t rowlen = 3 * a.nT;
     const int64_t npieces = rowlen / PF;                   // multiple of 3
-    const int frow = lane >> 3, fcol = (lane & 7) * 4;
-    const T* __restrict__ base = a.Beff + row0 * rowlen;
+    const LM lm(a.Beff, tile, lane, row0, a.rows, a.nT);
     T* __restrict__ obase = a.gBeff ? a.gBeff + row0 * rowlen : nullptr;
-    const int64_t last = a.rows - 1 - row0;
-    // byte offset of load / store i = min(off0 + i * ostride, olim), as in the forward kernel: two
-    // VGPRs instead of eight precomputed offsets (o0 laundered per use, or LICM hoists all eight
-    // back into registers); rows past the end of the last tile are clamped for the loads and
-    // skipped for the stores
-    const unsigned ostride = (unsigned)(8 * rowlen * sizeof(T));
-    const unsigned off0 = (unsigned)(((frow < last ? frow : last) * rowlen + fcol) * sizeof(T));
-    const unsigned olim = (unsigned)(((last < 63 ? last : 63) * rowlen + fcol) * sizeof(T));
-    const int lastrow = (int)(last < 63 ? last : 63);
-#define MRPHY_OFF(i) (min(o0 + (unsigned)(i) * ostride, olim))
-    T* wr = tile + frow * PITCH + fcol;
-    T* my_ = tile + lane * PITCH;
+    T* my_ = tile + lane * LM::PITCH;
     const T* hp = hist_tile_base<T>(a.hist, tile_id, a.nT) + lane;
     const T* rowp = a.Beff + rc * rowlen;                  // this lane's own row, for the tails
-
-    f32x4 st[8];
-#define MRPHY_FETCH(p)                                                                     \
-    { unsigned o0 = off0; asm volatile("" : "+v"(o0));                                     \
-    _Pragma("unroll") for (int i = 0; i < 8; ++i)                                          \
-        st[i] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(                 \
-            reinterpret_cast<const char*>(base + (p) * PF) + MRPHY_OFF(i))); }
-#define MRPHY_STAGE()                                                                      \
-    __syncthreads();                                                                       \
-    _Pragma("unroll") for (int i = 0; i < 8; ++i)                                          \
-        *reinterpret_cast<f32x4*>(wr + i * 8 * PITCH) = st[i];                             \
-    __syncthreads();
-#define MRPHY_STORE(p)                                                                     \
-    if (obase) {                                                                           \
-        __syncthreads();                                                                   \
-        unsigned o0 = off0; asm volatile("" : "+v"(o0));                                   \
-        _Pragma("unroll") for (int i = 0; i < 8; ++i) {                                    \
-            const f32x4 v = *reinterpret_cast<const f32x4*>(wr + i * 8 * PITCH);           \
-            if (frow + 8 * i <= lastrow)                                                   \
-                __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(                   \
-                    reinterpret_cast<char*>(obase + (p) * PF) + MRPHY_OFF(i)));            \
-        }                                                                                  \
-    }
+    typename LM::V st[8];
     // Batches of a 32-step period in processing order (time reversed), steps [first, count]:
     //   piece p+2: [29,3] [25,4] [21,4: carry 21 + 22..24]    piece p+1: [18,3] [14,4] [10,4: carry]
     //   piece p  : [7,3] [4,3] [0,4]
     // H0/H1 alternate: each batch issues the history loads of the NEXT one before it computes.
     // First in a turn the order is: stage, next batch's history, next piece's Beff, compute.
 #define LA(NA_, Q_, H_) lines_adj<RELAX, false, CT, NA_>(k, my_ + (Q_), H_, hx, hy, hz)
-    HistBatch H0, H1;
+    HistBatchT<T> H0, H1;
     if (npieces > 0) {
-        MRPHY_FETCH(npieces - 1)
+        MRPHY_LINES_FETCH(lm, st, npieces - 1)
         hist_fetch<3, float>(hp, (npieces / 3 - 1) * 32 + 29, H0);
     }
     for (int64_t p = npieces - 3; p >= 0; p -= 3) {
@@ -278,9 +236,9 @@ __global__ __launch_bounds__(WAVE, 3) void k_bloch_bwd_lines(BwdArgs<float> a)
         // ---- piece p+2: floats 64..95 of the period.  steps 31..22 (from float 2), then the
         //      straddling step 21 = (tail float 63 | floats 0, 1)
         const T tl63 = rowp[(p + 2) * PF - 1];
-        MRPHY_STAGE()
+        MRPHY_LINES_STAGE(lm, st)
         hist_fetch<4, float>(hp, t0 + 25, H1);
-        MRPHY_FETCH(p + 1)
+        MRPHY_LINES_FETCH(lm, st, p + 1)
         LA(3, 23, H0);
         hist_fetch<4, float>(hp, t0 + 21, H0);
         LA(4, 11, H1);
@@ -288,13 +246,13 @@ __global__ __launch_bounds__(WAVE, 3) void k_bloch_bwd_lines(BwdArgs<float> a)
         lines_adj_carry<RELAX, false, CT, 3>(k, tl63, my_[0], my_[1], my_ + 2, H0, hx, hy, hz, g0, g1, g2);
         my_[0] = g1; my_[1] = g2;
         T cg31 = g0;                                       // -> float 31 of piece p+1
-        MRPHY_STORE(p + 2)
+        MRPHY_LINES_STORE(lm, obase, p + 2)
         // ---- piece p+1: floats 32..63.  steps 20..11 (from float 1), straddling step 10 =
         //      (tail floats 30, 31 | float 0)
         const T tl30 = rowp[(p + 1) * PF - 2], tl31 = rowp[(p + 1) * PF - 1];
-        MRPHY_STAGE()
+        MRPHY_LINES_STAGE(lm, st)
         hist_fetch<4, float>(hp, t0 + 14, H0);
-        MRPHY_FETCH(p)
+        MRPHY_LINES_FETCH(lm, st, p)
         my_[31] = cg31;
         LA(3, 22, H1);
         hist_fetch<4, float>(hp, t0 + 10, H1);
@@ -302,11 +260,11 @@ __global__ __launch_bounds__(WAVE, 3) void k_bloch_bwd_lines(BwdArgs<float> a)
         hist_fetch<3, float>(hp, t0 + 7, H0);
         lines_adj_carry<RELAX, false, CT, 3>(k, tl30, tl31, my_[0], my_ + 1, H1, hx, hy, hz, g0, g1, g2);
         my_[0] = g2;
-        MRPHY_STORE(p + 1)
+        MRPHY_LINES_STORE(lm, obase, p + 1)
         // ---- piece p: floats 0..31.  floats 30, 31 <- carried gradient of step 10; steps 9..0
-        MRPHY_STAGE()
+        MRPHY_LINES_STAGE(lm, st)
         hist_fetch<3, float>(hp, t0 + 4, H1);
-        if (p > 0) { MRPHY_FETCH(p - 1) }
+        if (p > 0) { MRPHY_LINES_FETCH(lm, st, p - 1) }
         my_[30] = g0; my_[31] = g1;
         LA(3, 21, H0);
         hist_fetch<4, float>(hp, t0 + 0, H0);
@@ -314,12 +272,8 @@ __global__ __launch_bounds__(WAVE, 3) void k_bloch_bwd_lines(BwdArgs<float> a)
         if (p > 0) hist_fetch<3, float>(hp, t0 - 32 + 29, H1);    // first batch of the next period
         LA(4, 0, H0);
         H0 = H1;
-        MRPHY_STORE(p)
+        MRPHY_LINES_STORE(lm, obase, p)
     }
-#undef MRPHY_FETCH
-#undef MRPHY_STAGE
-#undef MRPHY_STORE
-#undef MRPHY_OFF
 #undef LA
     adj_end<RELAX, T, CT>(k, hx, hy, hz);
     if (valid && a.gMi) { a.gMi[r * 3] = hx; a.gMi[r * 3 + 1] = hy; a.gMi[r * 3 + 2] = hz; }
@@ -343,66 +297,32 @@ template <typename CT, bool RELAX>
 __global__ __launch_bounds__(WAVE, 2) void k_bloch_bwd_lines_f64(BwdArgs<double> a)
 {
     using T = double;
-    constexpr int PF = 16;
-    constexpr int PITCH = PF + 2;
-    __shared__ __attribute__((aligned(16))) T tile[WAVE * PITCH];
+    using LM = LineMover<T>;
+    constexpr int PF = LM::PF;
+    __shared__ __attribute__((aligned(16))) T tile[WAVE * LM::PITCH];
 
     const int lane = threadIdx.x;
     const int64_t tile_id = xcd_tile(a.per_xcd);
     if (tile_id * WAVE >= a.rows) return;
-    const int64_t row0 = tile_id * WAVE;
-    const int64_t r = row0 + lane;
-    const bool valid = r < a.rows;
-    const int64_t rc = valid ? r : a.rows - 1;
-    const int64_t n = rc / a.nM, s = rc % a.nM;
+    const auto [row0, r, valid, rc, n, s] = row_id(tile_id, lane, a.rows, a.nM);
     const SpinConst<T, CT> k = load_consts<T, CT>(a.g, a.E1, a.E2, nullptr, n, s);
     T hx = a.gMo[rc * 3 + 0], hy = a.gMo[rc * 3 + 1], hz = a.gMo[rc * 3 + 2];
     adj_begin<RELAX, T, CT>(k, hx, hy, hz);
 
     const int64_t rowlen = 3 * a.nT;
     const int64_t npieces = rowlen / PF;                   // multiple of 3
-    const int frow = lane >> 3, fcol = (lane & 7) * 2;
-    const T* __restrict__ base = a.Beff + row0 * rowlen;
+    const LM lm(a.Beff, tile, lane, row0, a.rows, a.nT);
     T* __restrict__ obase = a.gBeff ? a.gBeff + row0 * rowlen : nullptr;
-    const int64_t last = a.rows - 1 - row0;
-    const unsigned ostride = (unsigned)(8 * rowlen * sizeof(T));
-    const unsigned off0 = (unsigned)(((frow < last ? frow : last) * rowlen + fcol) * sizeof(T));
-    const unsigned olim = (unsigned)(((last < 63 ? last : 63) * rowlen + fcol) * sizeof(T));
-    const int lastrow = (int)(last < 63 ? last : 63);
-#define MRPHY_OFF(i) (min(o0 + (unsigned)(i) * ostride, olim))
-    T* wr = tile + frow * PITCH + fcol;
-    T* my_ = tile + lane * PITCH;
+    T* my_ = tile + lane * LM::PITCH;
     const T* hp = hist_tile_base<T>(a.hist, tile_id, a.nT) + lane;
     const T* rowp = a.Beff + rc * rowlen;                  // this lane's own row, for the tails
-
-    f64x2 st[8];
-#define MRPHY_FETCH(p)                                                                     \
-    { unsigned o0 = off0; asm volatile("" : "+v"(o0));                                     \
-    _Pragma("unroll") for (int i = 0; i < 8; ++i)                                          \
-        st[i] = __builtin_nontemporal_load(reinterpret_cast<const f64x2*>(                 \
-            reinterpret_cast<const char*>(base + (p) * PF) + MRPHY_OFF(i))); }
-#define MRPHY_STAGE()                                                                      \
-    __syncthreads();                                                                       \
-    _Pragma("unroll") for (int i = 0; i < 8; ++i)                                          \
-        *reinterpret_cast<f64x2*>(wr + i * 8 * PITCH) = st[i];                             \
-    __syncthreads();
-#define MRPHY_STORE(p)                                                                     \
-    if (obase) {                                                                           \
-        __syncthreads();                                                                   \
-        unsigned o0 = off0; asm volatile("" : "+v"(o0));                                   \
-        _Pragma("unroll") for (int i = 0; i < 8; ++i) {                                    \
-            const f64x2 v = *reinterpret_cast<const f64x2*>(wr + i * 8 * PITCH);           \
-            if (frow + 8 * i <= lastrow)                                                   \
-                __builtin_nontemporal_store(v, reinterpret_cast<f64x2*>(                   \
-                    reinterpret_cast<char*>(obase + (p) * PF) + MRPHY_OFF(i)));            \
-        }                                                                                  \
-    }
+    typename LM::V st[8];
 #define LA(NA_, Q_, H_) lines_adj<RELAX, true, CT, NA_, T>(k, my_ + (Q_), H_, hx, hy, hz)
     // Batches of at most two steps, processing order, steps [first, count]:
     //   piece p+2: [14,2] [12,2] [10,2: carry 10 + 11]   piece p+1: [8,2] [7,1] [5,2: carry 5 + 6]   piece p: [3,2] [1,2] [0,1]
     HistBatchT<T> H0, H1;
     if (npieces > 0) {
-        MRPHY_FETCH(npieces - 1)
+        MRPHY_LINES_FETCH(lm, st, npieces - 1)
         hist_fetch<2, T>(hp, (npieces / 3 - 1) * 16 + 14, H0);
     }
     for (int64_t p = npieces - 3; p >= 0; p -= 3) {
@@ -410,9 +330,9 @@ __global__ __launch_bounds__(WAVE, 2) void k_bloch_bwd_lines_f64(BwdArgs<double>
         T g0, g1, g2;
         // ---- piece p+2
         const T tl14 = rowp[(p + 2) * PF - 2], tl15 = rowp[(p + 2) * PF - 1];
-        MRPHY_STAGE()
+        MRPHY_LINES_STAGE(lm, st)
         hist_fetch<2, T>(hp, t0 + 12, H1);
-        MRPHY_FETCH(p + 1)
+        MRPHY_LINES_FETCH(lm, st, p + 1)
         LA(2, 10, H0);                                     // steps 14, 15
         hist_fetch<2, T>(hp, t0 + 10, H0);
         LA(2, 4, H1);                                      // steps 12, 13
@@ -420,12 +340,12 @@ __global__ __launch_bounds__(WAVE, 2) void k_bloch_bwd_lines_f64(BwdArgs<double>
         lines_adj_carry<RELAX, true, CT, 1, T>(k, tl14, tl15, my_[0], my_ + 1, H0, hx, hy, hz, g0, g1, g2);
         my_[0] = g2;
         const T cg14 = g0, cg15 = g1;
-        MRPHY_STORE(p + 2)
+        MRPHY_LINES_STORE(lm, obase, p + 2)
         // ---- piece p+1
         const T tp15 = rowp[(p + 1) * PF - 1];
-        MRPHY_STAGE()
+        MRPHY_LINES_STAGE(lm, st)
         hist_fetch<1, T>(hp, t0 + 7, H0);
-        MRPHY_FETCH(p)
+        MRPHY_LINES_FETCH(lm, st, p)
         my_[14] = cg14; my_[15] = cg15;
         LA(2, 8, H1);                                      // steps 8, 9
         hist_fetch<2, T>(hp, t0 + 5, H1);
@@ -434,11 +354,11 @@ __global__ __launch_bounds__(WAVE, 2) void k_bloch_bwd_lines_f64(BwdArgs<double>
         lines_adj_carry<RELAX, true, CT, 1, T>(k, tp15, my_[0], my_[1], my_ + 2, H1, hx, hy, hz, g0, g1, g2);
         my_[0] = g1; my_[1] = g2;
         const T cgp15 = g0;
-        MRPHY_STORE(p + 1)
+        MRPHY_LINES_STORE(lm, obase, p + 1)
         // ---- piece p
-        MRPHY_STAGE()
+        MRPHY_LINES_STAGE(lm, st)
         hist_fetch<2, T>(hp, t0 + 1, H1);
-        if (p > 0) { MRPHY_FETCH(p - 1) }
+        if (p > 0) { MRPHY_LINES_FETCH(lm, st, p - 1) }
         my_[15] = cgp15;
         LA(2, 9, H0);                                      // steps 3, 4
         hist_fetch<1, T>(hp, t0 + 0, H0);
@@ -446,12 +366,8 @@ __global__ __launch_bounds__(WAVE, 2) void k_bloch_bwd_lines_f64(BwdArgs<double>
         if (p > 0) hist_fetch<2, T>(hp, t0 - 16 + 14, H1); // first batch of the next period
         LA(1, 0, H0);                                      // step 0
         H0 = H1;
-        MRPHY_STORE(p)
+        MRPHY_LINES_STORE(lm, obase, p)
     }
-#undef MRPHY_FETCH
-#undef MRPHY_STAGE
-#undef MRPHY_STORE
-#undef MRPHY_OFF
 #undef LA
     adj_end<RELAX, T, CT>(k, hx, hy, hz);
     if (valid && a.gMi) { a.gMi[r * 3] = hx; a.gMi[r * 3 + 1] = hy; a.gMi[r * 3 + 2] = hz; }

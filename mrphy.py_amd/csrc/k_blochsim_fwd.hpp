@@ -2,6 +2,7 @@
 // Fragment: included INSIDE a translation unit's anonymous namespace, after host_common.hpp (HIP runtime,
 // include/mrphy_hip.h, geom.hpp, bloch_math.hpp, k_common.hpp).  Not a standalone header.
 #pragma once
+#include "k_lines.hpp"     // the Beff line mover of the line-granular kernels
 
 // =============================================================================================
 // K1: blochsim forward, materialised Beff.
@@ -17,7 +18,6 @@ struct FwdArgs {
     int64_t rows, nM, nT;
     int vec_ok;
     unsigned per_xcd;      // line kernels: > 0 -> block b works on spin tile (b % 8) * per_xcd + b / 8
-    int xcd_rev;           // ... or on (b % 8) * per_xcd + per_xcd - 1 - b / 8: each XCD walks its eighth from the end
 };
 
 template <typename T, typename CT, int TC, bool SAVE>
@@ -29,11 +29,7 @@ __global__ __launch_bounds__(WAVE) void k_bloch_fwd(FwdArgs<T> a)
     __shared__ __attribute__((aligned(16))) T tile[TL::ELEMS];
 
     const int lane = threadIdx.x;
-    const int64_t row0 = (int64_t)blockIdx.x * WAVE;
-    const int64_t r = row0 + lane;
-    const bool valid = r < a.rows;
-    const int64_t rc = valid ? r : a.rows - 1;
-    const int64_t n = rc / a.nM, s = rc % a.nM;
+    const auto [row0, r, valid, rc, n, s] = row_id((int64_t)blockIdx.x, lane, a.rows, a.nM);
     const SpinConst<T, CT> k = load_consts<T, CT>(a.g, a.E1, a.E2, a.E1m1, n, s);
 
     T mx = a.Mi[rc * 3 + 0], my = a.Mi[rc * 3 + 1], mz = a.Mi[rc * 3 + 2];
@@ -90,16 +86,11 @@ __global__ __launch_bounds__(WAVE) void k_bloch_fwd(FwdArgs<T> a)
 // The chunked kernel above fetches 16 steps = 192 B per spin per chunk, i.e. one and a half
 // cache lines: measured with FETCH_SIZE it reads 1.22x the algorithmic bytes, because the shared
 // half line has usually left L2 when the next chunk asks for it.  Here the unit of transfer is
-// ONE 128-B line per spin ("piece" = 32 floats = 10 2/3 steps):
-//   * a piece of the 64-spin tile is 8 wave-loads; load i, lane l fetches 16 B of row 8i + l/8 at
-//     byte 16*(l%8) of that row's line: every wave-load covers 8 rows x one WHOLE line;
-//   * the next piece waits in 8 VGPR quads (32 VGPRs) while the current one is integrated;
-//   * LDS tile 64 x (32+4) floats = 9 KB; lane = spin reads its row with conflict-free reads
-//     (pitch 9 x 16 B, odd);
-//   * a step needs 3 consecutive floats, so steps straddle piece boundaries; 3 pieces = 96 floats =
-//     32 steps is the period: piece 0 holds steps 0-9 + 2 floats of step 10, piece 1 the rest of
-//     step 10, steps 11-20 + 1 float of step 21, piece 2 the rest of step 21 and steps 22-31.  The
-//     straddling floats travel in two carry registers.
+// ONE 128-B line per spin ("piece" = 32 floats = 10 2/3 steps), moved by LineMover (k_lines.hpp: the
+// wave-loads, the VGPR staging, the LDS tile).  A step needs 3 consecutive floats, so steps straddle
+// piece boundaries; 3 pieces = 96 floats = 32 steps is the period: piece 0 holds steps 0-9 + 2 floats
+// of step 10, piece 1 the rest of step 10, steps 11-20 + 1 float of step 21, piece 2 the rest of step
+// 21 and steps 22-31.  The straddling floats travel in two carry registers.
 // =============================================================================================
 // NA steps whose samples start at float `first` of this lane's LDS row, optionally preceded by a
 // straddling step whose leading floats arrive in registers.
@@ -151,83 +142,51 @@ template <typename CT, bool RELAX, int SPLIT, bool SAVE, bool PIN>
 __global__ __launch_bounds__(WAVE, 3) void k_bloch_fwd_lines(FwdArgs<float> a)
 {
     using T = float;
-    constexpr int PF = 32;                 // floats per piece = one 128-B line
-    constexpr int PITCH = PF + 4;          // 9 slots of 16 B
-    __shared__ __attribute__((aligned(16))) T tile[WAVE * PITCH];
+    using LM = LineMover<T>;
+    constexpr int PF = LM::PF;
+    __shared__ __attribute__((aligned(16))) T tile[WAVE * LM::PITCH];
 
     const int lane = threadIdx.x;
-    const int64_t tile_id = xcd_tile(a.per_xcd, a.xcd_rev != 0);
+    const int64_t tile_id = xcd_tile(a.per_xcd);
     if (tile_id * WAVE >= a.rows) return;
-    const int64_t row0 = tile_id * WAVE;
-    const int64_t r = row0 + lane;
-    const bool valid = r < a.rows;
-    const int64_t rc = valid ? r : a.rows - 1;
-    const int64_t n = rc / a.nM, s = rc % a.nM;
+    const auto [row0, r, valid, rc, n, s] = row_id(tile_id, lane, a.rows, a.nM);
     const SpinConst<T, CT> k = load_consts<T, CT>(a.g, a.E1, a.E2, a.E1m1, n, s);
     T mx = a.Mi[rc * 3 + 0], my = a.Mi[rc * 3 + 1], mz = a.Mi[rc * 3 + 2];
 
     const int64_t rowlen = 3 * a.nT;                       // floats; multiple of 96
     const int64_t npieces = rowlen / PF;                   // multiple of 3
-    const int frow = lane >> 3, fcol = (lane & 7) * 4;
-    // wave-uniform base (SGPRs) + 32-bit per-lane offsets: loads use the saddr+voffset form and
-    // need 8 VGPRs of addressing instead of 16 (host guarantees 64*rowlen < 2^31)
-    const T* __restrict__ base = a.Beff + row0 * rowlen;
-    const int64_t last = a.rows - 1 - row0;                // last valid row of this tile
-    // byte offset of load i = min(off0 + i * ostride, olim): rows past the end of the last tile
-    // re-read its last valid row (two VGPRs instead of eight precomputed offsets)
-    const unsigned ostride = (unsigned)(8 * rowlen * sizeof(T));
-    const unsigned off0 = (unsigned)(((frow < last ? frow : last) * rowlen + fcol) * sizeof(T));
-    const unsigned olim = (unsigned)(((last < 63 ? last : 63) * rowlen + fcol) * sizeof(T));
-// (o0 is laundered through an empty asm per piece, or the compiler hoists all eight offsets back
-// into registers for the whole loop)
-#define MRPHY_OFF(i) (min(o0 + (unsigned)(i) * ostride, olim))
-    T* wr = tile + frow * PITCH + fcol;                    // + i*8*PITCH per load
-    const T* my_ = tile + lane * PITCH;
-
-    f32x4 st0[8];
-#define MRPHY_FETCH(S, p)                                                                  \
-    { unsigned o0 = off0; asm volatile("" : "+v"(o0));                                     \
-    _Pragma("unroll") for (int i = 0; i < 8; ++i)                                          \
-        S[i] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(                  \
-            reinterpret_cast<const char*>(base + (p) * PF) + MRPHY_OFF(i))); }
-#define MRPHY_STAGE(S)                                                                     \
-    __syncthreads();                                                                       \
-    _Pragma("unroll") for (int i = 0; i < 8; ++i)                                          \
-        *reinterpret_cast<f32x4*>(wr + i * 8 * PITCH) = S[i];                              \
-    __syncthreads();
-
+    const LM lm(a.Beff, tile, lane, row0, a.rows, a.nT);
+    const T* my_ = tile + lane * LM::PITCH;
+    typename LM::V st0[8];
     T* hp = SAVE ? hist_tile_base<T>(a.hist, tile_id, a.nT) + lane : nullptr;
 #define LS(NA_, Q_, TH_) lines_steps<RELAX, SAVE, PIN, CT, NA_>(k, my_ + (Q_), hp, t0 + (TH_), mx, my, mz)
 #define LC(NA_, B0_, B1_, B2_, Q_, TH_) \
     lines_steps_carry<RELAX, SAVE, PIN, CT, NA_>(k, B0_, B1_, B2_, my_ + (Q_), hp, t0 + (TH_), mx, my, mz)
-    if (npieces > 0) { MRPHY_FETCH(st0, 0) }
+    if (npieces > 0) { MRPHY_LINES_FETCH(lm, st0, 0) }
     T c0, c1;
     for (int64_t p = 0; p < npieces; p += 3) {
         const int64_t t0 = (p / 3) * 32;
         const bool more = p + 3 < npieces;
         // piece 0: steps 0..9 (floats 0..29), carry floats 30, 31
-        MRPHY_STAGE(st0)
-        MRPHY_FETCH(st0, p + 1)
+        MRPHY_LINES_STAGE(lm, st0)
+        MRPHY_LINES_FETCH(lm, st0, p + 1)
         if (SPLIT == 2) { LS(5, 0, 0); LS(5, 15, 5); }
         else            { LS(4, 0, 0); LS(3, 12, 4); LS(3, 21, 7); }
         c0 = my_[30]; c1 = my_[31];
         // piece 1: step 10 = (c0, c1, f0); steps 11..20 from float 1; carry float 31
-        MRPHY_STAGE(st0)
-        MRPHY_FETCH(st0, p + 2)
+        MRPHY_LINES_STAGE(lm, st0)
+        MRPHY_LINES_FETCH(lm, st0, p + 2)
         if (SPLIT == 2) { LC(5, c0, c1, my_[0], 1, 10); LS(5, 16, 16); }
         else            { LC(3, c0, c1, my_[0], 1, 10); LS(4, 10, 14); LS(3, 22, 18); }
         c0 = my_[31];
         // piece 2: step 21 = (c0, f0, f1); steps 22..31 from float 2
-        MRPHY_STAGE(st0)
-        if (more) { MRPHY_FETCH(st0, p + 3) }
+        MRPHY_LINES_STAGE(lm, st0)
+        if (more) { MRPHY_LINES_FETCH(lm, st0, p + 3) }
         if (SPLIT == 2) { LC(5, c0, my_[0], my_[1], 2, 21); LS(5, 17, 27); }
         else            { LC(3, c0, my_[0], my_[1], 2, 21); LS(4, 11, 25); LS(3, 23, 29); }
     }
 #undef LS
 #undef LC
-#undef MRPHY_FETCH
-#undef MRPHY_STAGE
-#undef MRPHY_OFF
     if (valid) { a.Mo[r * 3] = mx; a.Mo[r * 3 + 1] = my; a.Mo[r * 3 + 2] = mz; }
 }
 
@@ -242,80 +201,53 @@ __global__ __launch_bounds__(WAVE, 3) void k_bloch_fwd_lines(FwdArgs<float> a)
 //     piece 1: step 5 = (carry, d0, d1), steps 6-9 (doubles 2-13), doubles 14, 15 carried;
 //     piece 2: step 10 = (carry, carry, d0), steps 11-15 (doubles 1-15).
 // Batches of at most two steps (a Rot<double> is 10 VGPRs): 150-160 VGPRs, three waves per SIMD, no scratch.
-// A wave-load is still 8 rows x one whole line (lane l: row 8i + l/8, 16 B at byte 16 (l % 8)); LDS
-// tile 64 x (16 + 2) doubles = 9 KB, pitch 9 x 16 B (odd: conflict-free row reads).
+// The mover is the same struct at sizeof(T) = 8: LDS tile 64 x (16 + 2) doubles = 9 KB.
 // =============================================================================================
 template <typename CT, bool RELAX, bool SAVE>
 __global__ __launch_bounds__(WAVE, 3) void k_bloch_fwd_lines_f64(FwdArgs<double> a)
 {
     using T = double;
-    constexpr int PF = 16;                 // doubles per piece = one 128-B line
-    constexpr int PITCH = PF + 2;          // 9 slots of 16 B
-    __shared__ __attribute__((aligned(16))) T tile[WAVE * PITCH];
+    using LM = LineMover<T>;
+    constexpr int PF = LM::PF;
+    __shared__ __attribute__((aligned(16))) T tile[WAVE * LM::PITCH];
 
     const int lane = threadIdx.x;
-    const int64_t tile_id = xcd_tile(a.per_xcd, a.xcd_rev != 0);
+    const int64_t tile_id = xcd_tile(a.per_xcd);
     if (tile_id * WAVE >= a.rows) return;
-    const int64_t row0 = tile_id * WAVE;
-    const int64_t r = row0 + lane;
-    const bool valid = r < a.rows;
-    const int64_t rc = valid ? r : a.rows - 1;
-    const int64_t n = rc / a.nM, s = rc % a.nM;
+    const auto [row0, r, valid, rc, n, s] = row_id(tile_id, lane, a.rows, a.nM);
     const SpinConst<T, CT> k = load_consts<T, CT>(a.g, a.E1, a.E2, a.E1m1, n, s);
     T mx = a.Mi[rc * 3 + 0], my = a.Mi[rc * 3 + 1], mz = a.Mi[rc * 3 + 2];
 
     const int64_t rowlen = 3 * a.nT;                       // doubles; multiple of 48
     const int64_t npieces = rowlen / PF;                   // multiple of 3
-    const int frow = lane >> 3, fcol = (lane & 7) * 2;
-    const T* __restrict__ base = a.Beff + row0 * rowlen;
-    const int64_t last = a.rows - 1 - row0;
-    const unsigned ostride = (unsigned)(8 * rowlen * sizeof(T));
-    const unsigned off0 = (unsigned)(((frow < last ? frow : last) * rowlen + fcol) * sizeof(T));
-    const unsigned olim = (unsigned)(((last < 63 ? last : 63) * rowlen + fcol) * sizeof(T));
-#define MRPHY_OFF(i) (min(o0 + (unsigned)(i) * ostride, olim))
-    T* wr = tile + frow * PITCH + fcol;
-    const T* my_ = tile + lane * PITCH;
-
-    f64x2 st0[8];
-#define MRPHY_FETCH(S, p)                                                                  \
-    { unsigned o0 = off0; asm volatile("" : "+v"(o0));                                     \
-    _Pragma("unroll") for (int i = 0; i < 8; ++i)                                          \
-        S[i] = __builtin_nontemporal_load(reinterpret_cast<const f64x2*>(                  \
-            reinterpret_cast<const char*>(base + (p) * PF) + MRPHY_OFF(i))); }
-#define MRPHY_STAGE(S)                                                                     \
-    __syncthreads();                                                                       \
-    _Pragma("unroll") for (int i = 0; i < 8; ++i)                                          \
-        *reinterpret_cast<f64x2*>(wr + i * 8 * PITCH) = S[i];                              \
-    __syncthreads();
-
+    const LM lm(a.Beff, tile, lane, row0, a.rows, a.nT);
+    const T* my_ = tile + lane * LM::PITCH;
+    typename LM::V st0[8];
     T* hp = SAVE ? hist_tile_base<T>(a.hist, tile_id, a.nT) + lane : nullptr;
 #define LS(NA_, Q_, TH_) lines_steps<RELAX, SAVE, true, CT, NA_, T>(k, my_ + (Q_), hp, t0 + (TH_), mx, my, mz)
 #define LC(NA_, B0_, B1_, B2_, Q_, TH_) \
     lines_steps_carry<RELAX, SAVE, true, CT, NA_, T>(k, B0_, B1_, B2_, my_ + (Q_), hp, t0 + (TH_), mx, my, mz)
-    if (npieces > 0) { MRPHY_FETCH(st0, 0) }
+    if (npieces > 0) { MRPHY_LINES_FETCH(lm, st0, 0) }
     T c0, c1;
     for (int64_t p = 0; p < npieces; p += 3) {
         const int64_t t0 = (p / 3) * 16;
         const bool more = p + 3 < npieces;
         // piece 0: steps 0..4 (doubles 0..14), carry double 15
-        MRPHY_STAGE(st0)
-        MRPHY_FETCH(st0, p + 1)
+        MRPHY_LINES_STAGE(lm, st0)
+        MRPHY_LINES_FETCH(lm, st0, p + 1)
         LS(2, 0, 0); LS(2, 6, 2); LS(1, 12, 4);
         c0 = my_[15];
         // piece 1: step 5 = (c0, d0, d1); steps 6..9 from double 2; carry doubles 14, 15
-        MRPHY_STAGE(st0)
-        MRPHY_FETCH(st0, p + 2)
+        MRPHY_LINES_STAGE(lm, st0)
+        MRPHY_LINES_FETCH(lm, st0, p + 2)
         LC(1, c0, my_[0], my_[1], 2, 5); LS(2, 5, 7); LS(1, 11, 9);
         c0 = my_[14]; c1 = my_[15];
         // piece 2: step 10 = (c0, c1, d0); steps 11..15 from double 1
-        MRPHY_STAGE(st0)
-        if (more) { MRPHY_FETCH(st0, p + 3) }
+        MRPHY_LINES_STAGE(lm, st0)
+        if (more) { MRPHY_LINES_FETCH(lm, st0, p + 3) }
         LC(1, c0, c1, my_[0], 1, 10); LS(2, 4, 12); LS(2, 10, 14);
     }
 #undef LS
 #undef LC
-#undef MRPHY_FETCH
-#undef MRPHY_STAGE
-#undef MRPHY_OFF
     if (valid) { a.Mo[r * 3] = mx; a.Mo[r * 3 + 1] = my; a.Mo[r * 3 + 2] = mz; }
 }

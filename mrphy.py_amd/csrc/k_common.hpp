@@ -35,6 +35,22 @@ __device__ __forceinline__ SpinConst<T, CT> load_consts(const Bc& g, const Bc& E
     return k;
 }
 
+// Lane `lane` of the wave that works on 64-spin tile `tile`: its row r of the (N nM) rows, whether that row exists
+// (the last tile may be ragged), the row it reads instead if not (rc), and rc's batch n and spin s.
+struct RowId {
+    int64_t row0, r;
+    bool valid;
+    int64_t rc, n, s;
+};
+__device__ __forceinline__ RowId row_id(int64_t tile, int lane, int64_t rows, int64_t nM)
+{
+    const int64_t row0 = tile * WAVE;
+    const int64_t r = row0 + lane;
+    const bool valid = r < rows;
+    const int64_t rc = valid ? r : rows - 1;
+    return {row0, r, valid, rc, rc / nM, rc % nM};
+}
+
 // ---------------------------------------------------------------------------------------------
 // Chunk tile geometry: 64 rows x (3*TC) elements, LDS pitch padded by one 16-B slot so that
 // "lane = row, same column" ds_read_b128 is conflict-free (slots per row is odd).
@@ -165,11 +181,11 @@ __device__ __forceinline__ void hist_load(const T* hp, int64_t t, T& mx, T& my, 
 
 // Blocks are dealt round-robin to the 8 XCDs; with this map each XCD walks its own contiguous
 // eighth of the spin tiles (see run_rfgr2beff for what that is worth on the write side).
-__device__ __forceinline__ int64_t xcd_tile(unsigned per_xcd, bool reversed = false)
+__device__ __forceinline__ int64_t xcd_tile(unsigned per_xcd)
 {
     if (!per_xcd) return (int64_t)blockIdx.x;
     const unsigned k = blockIdx.x >> 3;
-    return (int64_t)MRPHY_XCD_SLOT(blockIdx.x) * per_xcd + (reversed ? per_xcd - 1 - k : k);
+    return (int64_t)MRPHY_XCD_SLOT(blockIdx.x) * per_xcd + k;
 }
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));

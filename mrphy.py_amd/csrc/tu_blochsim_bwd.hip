@@ -24,27 +24,18 @@ int run_bwd(HistParts hist, const void* Beff, Bc g, Bc E1, Bc E2, const void* gM
         hipLaunchKernelGGL((k_bloch_bwd<T, CT, TC_BWD<T>, true>), grid, dim3(WAVE), 0, st, a);
         return launch_status();
     }
-    if constexpr (sizeof(T) == 4) {
-        if (lines_shape_ok(Beff, nT) && (!gBeff || aligned_to(gBeff, 128))) {
-            a.per_xcd = (grid.x + 7) / 8; grid.x = a.per_xcd * 8;
-            // 3 waves/SIMD.  Same-box A/B at 128^3 x 1024 (ms), round 2: history fetched in-batch 13.28 | one batch
-            // ahead: 2 waves/SIMD 12.83, 3 waves/SIMD 13.04 with 36 B/lane of spills; without forming w, v in the
-            // adjoint step the 3-wave build has 134-136 VGPRs and no spills: 12.6-12.8 (round 3, 64^3 x 2048:
-            // 2 | 3 | 4 waves 3.33 | 3.36 | 3.32 ms: no occupancy effect)
-            if (E1.p) hipLaunchKernelGGL((k_bloch_bwd_lines<CT, true>), grid, dim3(WAVE), 0, st, a);
-            else      hipLaunchKernelGGL((k_bloch_bwd_lines<CT, false>), grid, dim3(WAVE), 0, st, a);
-            return launch_status();
-        }
-    }
-    if constexpr (sizeof(T) == 8) {
-        // fp64: the line-granular adjoint where the shape allows it (round 4; the chunked fp64 adjoint needs
-        // 430-456 VGPRs = one wave per SIMD)
-        if (lines_shape_ok_f64(Beff, nT) && (!gBeff || aligned_to(gBeff, 128))) {
-            a.per_xcd = (grid.x + 7) / 8; grid.x = a.per_xcd * 8;
+    if (lines_shape_ok<T>(Beff, nT) && (!gBeff || aligned_to(gBeff, LINE_BYTES))) {
+        // The line-granular adjoints, XCD-contiguous tile order: fp32 at 3 waves/SIMD, fp64 at 2 (the chunked fp64
+        // adjoint needs 430-456 VGPRs = one).  The A/Bs: docs/LABNOTES.md, "K1 / K3 launchers: how the builds were chosen".
+        a.per_xcd = xcd_pad(grid);
+        if constexpr (sizeof(T) == 8) {
             if (E1.p) hipLaunchKernelGGL((k_bloch_bwd_lines_f64<CT, true>), grid, dim3(WAVE), 0, st, a);
             else      hipLaunchKernelGGL((k_bloch_bwd_lines_f64<CT, false>), grid, dim3(WAVE), 0, st, a);
-            return launch_status();
+        } else {
+            if (E1.p) hipLaunchKernelGGL((k_bloch_bwd_lines<CT, true>), grid, dim3(WAVE), 0, st, a);
+            else      hipLaunchKernelGGL((k_bloch_bwd_lines<CT, false>), grid, dim3(WAVE), 0, st, a);
         }
+        return launch_status();
     }
     hipLaunchKernelGGL((k_bloch_bwd<T, CT, TC_BWD<T>, false>), grid, dim3(WAVE), 0, st, a);
     return launch_status();

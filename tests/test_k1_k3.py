@@ -1079,32 +1079,54 @@ def test_k1_xcd_tile_order_is_the_same_arithmetic(mode, nM):
     assert torch.equal(Mh.detach(), Mo)
 
 
-@pytest.mark.parametrize('relax', [True, False])
-@pytest.mark.parametrize('nM', [64 * 9 + 7, 64 * 8])
-def test_fp64_line_kernels_equal_the_chunked_ones(relax, nM):
-    r"""Round 4: fp64 ``blochsim`` (forward, forward with history, adjoint) runs line-granular kernels when the
-    rows sit on 128-B lines and nT % 16 == 0 (a line = 16 doubles, period 3 lines = 16 steps).  Same step
-    arithmetic as the chunked kernels they replace there: outputs and gradients bit for bit -- ragged last tile,
-    several 16-step periods, carries across all three piece boundaries."""
-    f64 = torch.float64
-    nT = 80                                                   # 5 periods
-    sp, p, kw = _problem(16, nT, dtype=f64, idx=torch.arange(nM))
+# (kind, relax, N, nM): every data type and step, with and without relaxation, at a ragged last tile, full tiles, a
+# last tile of three rows (the mover's off0 / olim clamp for rows past the end, and the skipped stores), one ragged
+# tile in a grid padded to 8 blocks (7 blocks leave at the top); and a batch of two with a tile across the batch
+# boundary, where the row prologue's (n, s) split meets per-spin T1 / T2.
+_LINE_CASES = [(kind, relax, 1, nM) for kind in ('f64', 'precise', 'fast') for relax in (True, False)
+               for nM in (64 * 9 + 7, 64 * 8, 64 + 3, 5)] + [(kind, True, 2, 70) for kind in ('f64', 'precise', 'fast')]
+
+
+@pytest.mark.parametrize('kind,relax,N,nM', _LINE_CASES, ids=lambda v: str(v))
+def test_line_kernels_equal_the_chunked_ones(kind, relax, N, nM):
+    r"""``blochsim`` (forward, forward with history, adjoint) runs line-granular kernels when the rows sit on 128-B
+    lines and nT is whole periods (a line = 16 doubles / 32 floats, period 3 lines = 16 / 32 steps); the same values
+    at an address off the 128-B grid run the chunked kernels.  Same step arithmetic: outputs and gradients bit for
+    bit, in fp64 (round 4) and in fp32 with the precise and the fast step -- several periods, carries across all three
+    piece boundaries.  The line kernels share one Beff mover and all kernels one row prologue (k_lines.hpp,
+    k_common.hpp): the row counts are the mover's and the prologue's edge cases.  A backward in which Beff needs no
+    gradient (the mover stores nothing) gives grad_Mi the same bits."""
+    dtype = torch.float64 if kind == 'f64' else torch.float32
+    nT = 80 if kind == 'f64' else 96                          # 5 / 3 periods
+    sp, p, kw = _problem(16, nT, dtype=dtype, idx=torch.arange(N * nM))
+    beff = beffective.rfgr2beff(p['rf'] * 40, p['gr'] * 3, sp['loc'], Δf=sp['Δf'], γ=sp['γ'])   # some steps beyond pi
+    beff = beff.reshape(N, nM, nT, 3)
+    M0 = sp['M0'].reshape(N, nM, 3)
+    kw = dict(kw, T1=kw['T1'].reshape(N, nM), T2=kw['T2'].reshape(N, nM))
     if not relax:
         kw = dict(γ=kw['γ'], dt=kw['dt'])
-    beff = beffective.rfgr2beff(p['rf'] * 40, p['gr'] * 3, sp['loc'], Δf=sp['Δf'], γ=sp['γ'])   # some steps beyond pi
-    assert beff.data_ptr() % 128 == 0
+    assert beff.data_ptr() % 128 == 0 and beff.is_contiguous()
     res = []
-    for b in (beff, _offset_copy(beff)):
-        b = b.detach().requires_grad_(True)
-        Mi = sp['M0'].clone().requires_grad_(True)
-        with torch.no_grad():
-            Mo_ng = sims.blochsim(Mi, b, **kw)                # no history
-        Mo = sims.blochsim(Mi, b, **kw)                       # with history
-        gM, gB = torch.autograd.grad(Mo, (Mi, b), torch.cos(Mo.detach() * 3.0))
-        res.append((Mo_ng, Mo.detach(), gM, gB))
-    for a_, b_ in zip(*res):
-        assert torch.equal(a_, b_)
-    assert torch.equal(res[0][0], res[0][1])
+    with mrphy_amd.precision('fast' if kind == 'fast' else 'precise'):
+        for b in (beff, _offset_copy(beff)):
+            b = b.detach().requires_grad_(True)
+            Mi = M0.clone().requires_grad_(True)
+            with torch.no_grad():
+                Mo_ng = sims.blochsim(Mi, b, **kw)            # no history
+            Mo = sims.blochsim(Mi, b, **kw)                   # with history
+            gMo = torch.cos(Mo.detach() * 3.0)
+            gM, gB = torch.autograd.grad(Mo, (Mi, b), gMo)
+            Mo2 = sims.blochsim(Mi, b.detach(), **kw)         # Beff needs no gradient: nothing is stored
+            gM2, = torch.autograd.grad(Mo2, (Mi,), gMo)
+            res.append((Mo_ng, Mo.detach(), gM, gB, gM2))
+    names = ('Mo', 'Mo_hist', 'grad_Mi', 'grad_Beff', 'grad_Mi_alone')
+    dist = {n_: float((a_.double() - b_.double()).abs().max()) for n_, a_, b_ in zip(names, *res)}
+    print(f'line vs chunked kernels, max |difference| {kind} relax={relax} N={N} nM={nM}: {dist}')
+    for n_, a_, b_ in zip(names, *res):
+        assert torch.equal(a_, b_), (n_, dist)
+    for r_ in res:
+        assert torch.equal(r_[0], r_[1])                      # with history: the same output
+        assert torch.equal(r_[2], r_[4])                      # ... and grad_Mi whether or not grad_Beff is wanted
 
 
 def test_blochsim_constant_gradients_with_a_gamma_zero_spin():

@@ -1,7 +1,8 @@
 """The VALU-bound kernels for several builds of the library, one child process each, twice (alternating):
     python tools/ab_libs_valu.py LIB_A.so LIB_B.so ...
 fp32 precise: fused forward K2 (64^3 x 2048, 128^3 x 1024), fused forward + adjoint K2 + K2b (64^3 x 2048), 8 transmit coils
-fused forward + adjoint (64^3 x 1024); fp64: K2 and K2 + K2b (64^3 x 1024).  Norms printed to compare bits.
+fused forward + adjoint (64^3 x 1024); fp64: K2 and K2 + K2b (64^3 x 1024); then the materialised route K1, K1h, K3 (fp32 64^3 x 2048, 128^3 x 1024,
+fp64 64^3 x 1024) with the fraction of the 8 TB/s HBM peak.  Norms and integer-view sums printed to compare bits.
     python tools/ab_libs_valu.py --bits LIB_A.so LIB_B.so ...
 no timing: the integer-view sums of the outputs and of grad_Mi, grad_rf, grad_gr of fused.blochsim_rfgr_traj (every 1, 5,
 16; one coil and 2 coils) and fused.signal_rfgr (every 1, 16, with a receive map and with a receive array of 3 coils) at
@@ -114,11 +115,11 @@ for label, dt, n, nT, nC in (('f32 64^3x2048', torch.float32, 64, 2048, 1), ('f3
         del Mo_
     out.append(s + f' |Mo| {float(Mo.double().norm()):.12e}')
     del sp
-# the materialised route in fp32 (HBM-bound): K1 on a resident block, K1 with history + K3   (MRPHY_AB_NO_MAT=1 skips it)
+# the materialised route (HBM-bound), fp32 and fp64 line kernels: K1 on a resident block, K1 with history + K3   (MRPHY_AB_NO_MAT=1 skips it)
 from mrphy_amd import beffective, sims
-for n, nT in (() if os.environ.get('MRPHY_AB_NO_MAT') else ((64, 2048), (128, 1024))):
-    sp = synth.cube_spins(n, dtype=torch.float32, device=dev, seed_M0=4)
-    p = synth.pulse(nT, dtype=torch.float32, device=dev)
+for dt, n, nT in (() if os.environ.get('MRPHY_AB_NO_MAT') else ((torch.float32, 64, 2048), (torch.float32, 128, 1024), (torch.float64, 64, 1024))):
+    sp = synth.cube_spins(n, dtype=dt, device=dev, seed_M0=4)
+    p = synth.pulse(nT, dtype=dt, device=dev)
     kw = dict(T1=sp['T1'], T2=sp['T2'], γ=sp['γ'], dt=p['dt'])
     with torch.no_grad():
         beff = beffective.rfgr2beff(p['rf'], p['gr'], sp['loc'], Δf=sp['Δf'], γ=sp['γ'])
@@ -127,8 +128,8 @@ for n, nT in (() if os.environ.get('MRPHY_AB_NO_MAT') else ((64, 2048), (128, 10
     Mi = sp['M0'].clone().requires_grad_(True)
     t1h, Mo2 = t_of(lambda: sims.blochsim(Mi, beff, **kw), 4, 2)
     t3, g = t_of(lambda: torch.autograd.grad(Mo2, (Mi, beff), torch.ones_like(Mo2), retain_graph=True), 4, 2)
-    ss = n ** 3 * nT
-    out.append(f'f32 {n}^3x{nT}: K1 {t1:.3f} ({12 * ss / t1 / 8e9:.3f}) K1h {t1h:.3f} ({24 * ss / t1h / 8e9:.3f}) K3 {t3:.3f} ({36 * ss / t3 / 8e9:.3f}) '
-               f'|gB| {float(g[1].double().norm()):.12e}')
+    es = n ** 3 * nT * beff.element_size()                  # bytes per component of Beff: K1 moves 3, K1h 6, K3 9 of them
+    out.append(f'{str(dt)[6:].replace("float", "f")} {n}^3x{nT}: K1 {t1:.3f} ({3 * es / t1 / 8e9:.3f}) K1h {t1h:.3f} ({6 * es / t1h / 8e9:.3f}) K3 {t3:.3f} ({9 * es / t3 / 8e9:.3f}) '
+               f'|gB| {float(g[1].double().norm()):.12e} bits(Mo, gMi, gB) {bits(Mo)} {bits(g[0])} {bits(g[1])}')
     del beff, Mo2, g, sp
 print('   '.join(out))
