@@ -73,7 +73,9 @@ extern "C" {
  *      the transverse magnetisation summed over the spins, sample by sample); mrphy_signal_rfgr_max_rx,
  *      mrphy_signal_rfgr_mrx_fwd_workspace, mrphy_signal_rfgr_mrx_fwd, mrphy_signal_rfgr_mrx_bwd (the same for the coils
  *      of a receive array from ONE simulation per launch); mrphy_blochsim_rfgr_maps_bwd (K2b / K2bt of one transmit
- *      coil, which also returns the gradients w.r.t. loc, df and b1). */
+ *      coil, which also returns the gradients w.r.t. loc, df and b1); mrphy_blochsim_rfgr_consts_bwd,
+ *      mrphy_signal_rfgr_consts_bwd (the same adjoints, which also return the gradients w.r.t. the step constants
+ *      g = gamma 2 pi dt, E1, E2, E1m1 per spin). */
 #define MRPHY_ABI_VERSION 5
 
 #define MRPHY_F32      0  /* T = float,  CT = float                                          */
@@ -574,6 +576,33 @@ int mrphy_blochsim_rfgr_maps_bwd(int dtype,
                                  void* work, size_t work_bytes,
                                  int64_t N, int64_t nM, int64_t nT,
                                  void* stream);
+/* mrphy_blochsim_rfgr_maps_bwd with the gradients w.r.t. the step constants besides, in the same sweep:
+ *     grad_consts (N, nM, 4)   [dL/dg, dL/dE1, dL/dE2, dL/dE1m1][n,s],  g = gamma 2 pi dt
+ * per spin, each the sum over the steps that mrphy_blochsim_bwd_consts forms on the two-kernel route (with u = R m the
+ * rotated state of a step and h = dL/dm' the cotangent after it: dL/dE2 += hx ux + hy uy, dL/dE1 += hz uz,
+ * dL/dE1m1 -= hz, dL/dg += dL/db . B), in the order of the map sums; without relaxation the last three are zeros.  The
+ * caller folds them to its operands: dL/dE1 and dL/dE1m1 add for an E1m1 formed as E1 - 1.  grad_consts is optional like
+ * the other outputs; every other output comes out bit for bit as mrphy_blochsim_rfgr_maps_bwd gives it.  Under codes
+ * 3 / 4 E1 and E2 must be non-zero (see the history above).  Same checkpoints, workspace, refusals and empty-problem
+ * rule as mrphy_blochsim_rfgr_maps_bwd. */
+int mrphy_blochsim_rfgr_consts_bwd(int dtype,
+                                   const void* Mck,
+                                   const void* rf, int64_t rf_sn,
+                                   const void* gr, int64_t gr_sn,
+                                   const void* loc,
+                                   const void* df, int64_t df_sn, int64_t df_sm,
+                                   const void* gamma, int64_t gamma_sn, int64_t gamma_sm,
+                                   const void* b1,
+                                   const void* g,  int64_t g_sn,  int64_t g_sm,
+                                   const void* E1, int64_t E1_sn, int64_t E1_sm,
+                                   const void* E2, int64_t E2_sn, int64_t E2_sm,
+                                   const void* E1m1,
+                                   const void* grad_Mo, const void* grad_Mt, int64_t every,
+                                   void* grad_Mi, void* grad_rf, void* grad_gr,
+                                   void* grad_loc, void* grad_Bz, void* grad_b1, void* grad_consts,
+                                   void* work, size_t work_bytes,
+                                   int64_t N, int64_t nM, int64_t nT,
+                                   void* stream);
 int mrphy_blochsim_rfgr_mc_traj_bwd(int dtype,
                                     const void* Mck,
                                     const void* rf, int64_t rf_sn,
@@ -721,6 +750,29 @@ int mrphy_signal_rfgr_mrx_bwd(int dtype,
                               void* work, size_t work_bytes,
                               int64_t N, int64_t nM, int64_t nT,
                               void* stream);
+/* mrphy_signal_rfgr_mrx_bwd with grad_consts (N, nM, 4) besides, as mrphy_blochsim_rfgr_consts_bwd returns it (optional);
+ * 1 <= nRx <= mrphy_signal_rfgr_max_rx(dtype) -- a build for each of the capacities 1, 2, 4, 8 -- and for nRx == 1 rx
+ * may be NULL, the (1, 0) of mrphy_signal_rfgr_bwd.  grad_Mi, grad_rf, grad_gr come out bit for bit as
+ * mrphy_signal_rfgr_bwd (nRx == 1) and mrphy_signal_rfgr_mrx_bwd give them.  No gradient w.r.t. rx or the spin-side
+ * maps.  Everything else, refusals included, as mrphy_signal_rfgr_mrx_bwd. */
+int mrphy_signal_rfgr_consts_bwd(int dtype,
+                                 const void* Mck,
+                                 const void* rf, int64_t rf_sn,
+                                 const void* gr, int64_t gr_sn,
+                                 const void* loc,
+                                 const void* df, int64_t df_sn, int64_t df_sm,
+                                 const void* gamma, int64_t gamma_sn, int64_t gamma_sm,
+                                 const void* b1,
+                                 const void* g,  int64_t g_sn,  int64_t g_sm,
+                                 const void* E1, int64_t E1_sn, int64_t E1_sm,
+                                 const void* E2, int64_t E2_sn, int64_t E2_sm,
+                                 const void* E1m1,
+                                 const void* rx, int64_t nRx,
+                                 const void* grad_Mo, const void* grad_sig, int64_t every,
+                                 void* grad_Mi, void* grad_rf, void* grad_gr, void* grad_consts,
+                                 void* work, size_t work_bytes,
+                                 int64_t N, int64_t nM, int64_t nT,
+                                 void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * the steps either side of the path in SpinArray.applypulse (mobjs.py:427-433,449).

@@ -62,6 +62,7 @@ PROTOTYPES = {
     'mrphy_blochsim_rfgr_traj_fwd': (_int, _FUSED + [_vp, _vp, _i64, _vp, _i64] + [_i64] * 4 + [_vp]),
     'mrphy_blochsim_rfgr_traj_bwd': (_int, _FUSED + [_vp, _i64, _vp, _vp, _vp, _vp, _sz] + [_i64] * 3 + [_vp]),
     'mrphy_blochsim_rfgr_maps_bwd': (_int, _FUSED + [_vp, _vp, _i64] + [_vp] * 6 + [_vp, _sz] + [_i64] * 3 + [_vp]),
+    'mrphy_blochsim_rfgr_consts_bwd': (_int, _FUSED + [_vp, _vp, _i64] + [_vp] * 7 + [_vp, _sz] + [_i64] * 3 + [_vp]),
     'mrphy_blochsim_rfgr_mc_traj_bwd': (_int, _FUSED + [_vp, _i64, _vp, _vp, _vp, _vp, _sz] + [_i64] * 4 + [_vp]),
     'mrphy_signal_rfgr_fwd_workspace': (_sz, [_int] + [_i64] * 4),
     'mrphy_signal_rfgr_fwd': (_int, _FUSED + [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _sz] + [_i64] * 4 + [_vp]),
@@ -71,6 +72,8 @@ PROTOTYPES = {
     'mrphy_signal_rfgr_mrx_fwd': (_int, _FUSED + [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _sz] + [_i64] * 4 + [_vp]),
     'mrphy_signal_rfgr_mrx_bwd': (_int, _FUSED + [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _sz] + [_i64] * 3
                                   + [_vp]),
+    'mrphy_signal_rfgr_consts_bwd': (_int, _FUSED + [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz] + [_i64] * 3
+                                     + [_vp]),
     'mrphy_freeprec_fwd': (_int, [_int, _vp, _vp, _i64] + _BC * 3 + [_vp, _i64, _i64, _vp]),
     'mrphy_freeprec_bwd': (_int, [_int, _vp, _vp, _i64] + _BC * 3 + [_vp, _i64, _i64, _vp]),
     'mrphy_freeprec_bwd_consts': (_int, [_int, _vp, _vp, _vp, _i64] + _BC * 3 + [_vp, _i64, _i64, _vp]),
@@ -108,8 +111,13 @@ UNITS = [(f, m) for f, masks in (
     ('tu_fused_fwd1.hip', (_F32, _C64, _P, _PC64)),
     ('tu_fused_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_fused_maps_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
+    ('tu_fused_consts_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_signal.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_fused_mrx_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
+    ('tu_signal_consts8_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
+    ('tu_signal_consts4_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
+    ('tu_signal_consts2_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
+    ('tu_signal_consts1_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_signal_mrx8.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_signal_mrx4.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_signal_mrx2.hip', (_F32, _F64, _C64, _P, _PC64)),

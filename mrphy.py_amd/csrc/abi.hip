@@ -94,10 +94,11 @@ int rfgr_bwd(bool traj, int dtype, const void* Mck, const PulseOps& in, const vo
 }
 
 // The MAPS builds: grad_Mo (mode 0) or grad_Mt (modes 1, 2), exactly one of them; refuses what rfgr_bwd refuses, and a
-// grad_b1 without a b1 map to differentiate
-int rfgr_maps_bwd(int dtype, const void* Mck, const PulseOps& in, const void* grad_Mo, const void* grad_Mt, int64_t every,
-                  void* grad_Mi, void* grad_rf, void* grad_gr, void* grad_loc, void* grad_Bz, void* grad_b1, void* work,
-                  size_t work_bytes, int64_t N, int64_t nM, int64_t nT, void* stream)
+// grad_b1 without a b1 map to differentiate.  `consts`: the CONSTS builds, which return grad_consts besides (optional as
+// the map outputs are)
+int rfgr_maps_bwd(bool consts, int dtype, const void* Mck, const PulseOps& in, const void* grad_Mo, const void* grad_Mt,
+                  int64_t every, void* grad_Mi, void* grad_rf, void* grad_gr, void* grad_loc, void* grad_Bz, void* grad_b1,
+                  void* grad_consts, void* work, size_t work_bytes, int64_t N, int64_t nM, int64_t nT, void* stream)
 {
     if (int e = check_common(dtype, N, nM, nT)) return e;
     if (nT % SEG != 0 || (grad_Mt && every < 1) || (grad_Mo && grad_Mt) || (grad_b1 && !in.b1)) return MRPHY_EINVAL;
@@ -106,6 +107,9 @@ int rfgr_maps_bwd(int dtype, const void* Mck, const PulseOps& in, const void* gr
     if (int e = check_ops(in, true, false)) return e;
     if (work_bytes < mrphy_blochsim_rfgr_bwd_workspace(dtype, N, nM, nT)) return MRPHY_ENOSPC;
     hipStream_t st = (hipStream_t)stream;
+    if (consts)
+        MRPHY_DISPATCH(dtype, (run_rfgr_consts_bwd<T, CT>(Mck, in, grad_Mo, grad_Mt, every, grad_Mi, grad_rf, grad_gr,
+                                                          grad_loc, grad_Bz, grad_b1, grad_consts, work, N, nM, nT, st)));
     MRPHY_DISPATCH(dtype, (run_rfgr_maps_bwd<T, CT>(Mck, in, grad_Mo, grad_Mt, every, grad_Mi, grad_rf, grad_gr, grad_loc,
                                                     grad_Bz, grad_b1, work, N, nM, nT, st)));
 }
@@ -148,19 +152,35 @@ int signal_fwd(bool mrx, int dtype, const void* Mi, const PulseOps& in, const vo
 #undef MRPHY_SIGNAL_FWD
 }
 
-int signal_bwd(bool mrx, int dtype, const void* Mck, const PulseOps& in, const void* rx, int64_t nRx, const void* grad_Mo,
-               const void* grad_sig, int64_t every, void* grad_Mi, void* grad_rf, void* grad_gr, void* work,
-               size_t work_bytes, int64_t N, int64_t nM, int64_t nT, void* stream)
+// `consts`: the CONSTS builds, which return grad_consts (optional) besides; rx may then be null for nRx == 1, the one-coil
+// entry point's (1, 0), and the smallest capacity 1, 2, 4, 8 that holds nRx runs
+int signal_bwd(bool mrx, bool consts, int dtype, const void* Mck, const PulseOps& in, const void* rx, int64_t nRx,
+               const void* grad_Mo, const void* grad_sig, int64_t every, void* grad_Mi, void* grad_rf, void* grad_gr,
+               void* grad_consts, void* work, size_t work_bytes, int64_t N, int64_t nM, int64_t nT, void* stream)
 {
     if (int e = check_common(dtype, N, nM, nT)) return e;
     // whole checkpoint segments only; at least one of the two cotangents
     if (nT % SEG != 0 || every < 1 || N > 65535 || (!grad_Mo && !grad_sig)) return MRPHY_EINVAL;
     if (nRx < 1 || nRx > sig_max_rx(tsize(dtype))) return MRPHY_EINVAL;
     if (N * nM * nT == 0) return 0;
-    if (!Mck || (mrx && !rx) || !work) return MRPHY_EINVAL;
+    if (!Mck || (mrx && !rx && !(consts && nRx == 1)) || !work) return MRPHY_EINVAL;
     if (int e = check_ops(in, true, false)) return e;
     if (work_bytes < mrphy_blochsim_rfgr_bwd_workspace(dtype, N, nM, nT)) return MRPHY_ENOSPC;
     hipStream_t st = (hipStream_t)stream;
+    if (consts) {
+        // without grad_sig there is nothing of the signal to inject: the CONSTS build of K2b on grad_Mo
+        if (!grad_sig)
+            MRPHY_DISPATCH(dtype, (run_rfgr_consts_bwd<T, CT>(Mck, in, grad_Mo, nullptr, 0, grad_Mi, grad_rf, grad_gr, nullptr,
+                                                              nullptr, nullptr, grad_consts, work, N, nM, nT, st)));
+#define MRPHY_SIGNAL_CONSTS_BWD(R_)                                                                                    \
+    MRPHY_DISPATCH(dtype, (run_signal_consts_bwd<T, CT, R_>(Mck, in, grad_Mo, every, rx, nRx, grad_sig, grad_Mi, grad_rf, \
+                                                            grad_gr, grad_consts, work, N, nM, nT, st)))
+        if (nRx == 1) MRPHY_SIGNAL_CONSTS_BWD(1);
+        if (nRx <= 2) MRPHY_SIGNAL_CONSTS_BWD(2);
+        if (nRx <= 4) MRPHY_SIGNAL_CONSTS_BWD(4);
+        MRPHY_SIGNAL_CONSTS_BWD(8);
+#undef MRPHY_SIGNAL_CONSTS_BWD
+    }
     // a receive array: the capacities 2 .. 8 are a unit of their own, which picks the smallest that holds nRx.  Without
     // grad_sig there is nothing of the signal to inject: K2b on grad_Mo
     if (grad_sig && nRx > 1)
@@ -409,8 +429,17 @@ int mrphy_blochsim_rfgr_maps_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PAR
                                  void* grad_loc, void* grad_Bz, void* grad_b1, void* work, size_t work_bytes, int64_t N,
                                  int64_t nM, int64_t nT, void* stream)
 {
-    return rfgr_maps_bwd(dtype, Mck, MRPHY_PULSE_OPS, grad_Mo, grad_Mt, every, grad_Mi, grad_rf, grad_gr, grad_loc,
-                         grad_Bz, grad_b1, work, work_bytes, N, nM, nT, stream);
+    return rfgr_maps_bwd(false, dtype, Mck, MRPHY_PULSE_OPS, grad_Mo, grad_Mt, every, grad_Mi, grad_rf, grad_gr, grad_loc,
+                         grad_Bz, grad_b1, nullptr, work, work_bytes, N, nM, nT, stream);
+}
+
+int mrphy_blochsim_rfgr_consts_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PARAMS, const void* grad_Mo,
+                                   const void* grad_Mt, int64_t every, void* grad_Mi, void* grad_rf, void* grad_gr,
+                                   void* grad_loc, void* grad_Bz, void* grad_b1, void* grad_consts, void* work,
+                                   size_t work_bytes, int64_t N, int64_t nM, int64_t nT, void* stream)
+{
+    return rfgr_maps_bwd(true, dtype, Mck, MRPHY_PULSE_OPS, grad_Mo, grad_Mt, every, grad_Mi, grad_rf, grad_gr, grad_loc,
+                         grad_Bz, grad_b1, grad_consts, work, work_bytes, N, nM, nT, stream);
 }
 
 int mrphy_blochsim_rfgr_mc_traj_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PARAMS, const void* grad_Mt,
@@ -439,8 +468,8 @@ int mrphy_signal_rfgr_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PARAMS, co
                           const void* grad_sig, int64_t every, void* grad_Mi, void* grad_rf, void* grad_gr, void* work,
                           size_t work_bytes, int64_t N, int64_t nM, int64_t nT, void* stream)
 {
-    return signal_bwd(false, dtype, Mck, MRPHY_PULSE_OPS, rx, 1, grad_Mo, grad_sig, every, grad_Mi, grad_rf, grad_gr,
-                      work, work_bytes, N, nM, nT, stream);
+    return signal_bwd(false, false, dtype, Mck, MRPHY_PULSE_OPS, rx, 1, grad_Mo, grad_sig, every, grad_Mi, grad_rf,
+                      grad_gr, nullptr, work, work_bytes, N, nM, nT, stream);
 }
 
 int mrphy_signal_rfgr_max_rx(int dtype)
@@ -468,8 +497,17 @@ int mrphy_signal_rfgr_mrx_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PARAMS
                               void* grad_gr, void* work, size_t work_bytes, int64_t N, int64_t nM, int64_t nT,
                               void* stream)
 {
-    return signal_bwd(true, dtype, Mck, MRPHY_PULSE_OPS, rx, nRx, grad_Mo, grad_sig, every, grad_Mi, grad_rf, grad_gr,
-                      work, work_bytes, N, nM, nT, stream);
+    return signal_bwd(true, false, dtype, Mck, MRPHY_PULSE_OPS, rx, nRx, grad_Mo, grad_sig, every, grad_Mi, grad_rf,
+                      grad_gr, nullptr, work, work_bytes, N, nM, nT, stream);
+}
+
+int mrphy_signal_rfgr_consts_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PARAMS, const void* rx, int64_t nRx,
+                                 const void* grad_Mo, const void* grad_sig, int64_t every, void* grad_Mi, void* grad_rf,
+                                 void* grad_gr, void* grad_consts, void* work, size_t work_bytes, int64_t N, int64_t nM,
+                                 int64_t nT, void* stream)
+{
+    return signal_bwd(true, true, dtype, Mck, MRPHY_PULSE_OPS, rx, nRx, grad_Mo, grad_sig, every, grad_Mi, grad_rf,
+                      grad_gr, grad_consts, work, work_bytes, N, nM, nT, stream);
 }
 
 int mrphy_beff2ab(int dtype, const void* Beff,

@@ -57,6 +57,20 @@ int run_rfgr_maps_bwd(const void* Mck, PulseOps in, const void* gMo, const void*
                       void* ggr, void* gloc, void* gBz, void* gb1, void* work, int64_t N, int64_t nM, int64_t nT,
                       hipStream_t st);
 
+// the CONSTS builds of K2b / K2bt (tu_fused_consts_bwd.hip): run_rfgr_maps_bwd, which also returns the gradients w.r.t.
+// the step constants per spin, gC (N, nM, 4) = [dL/dg, dL/dE1, dL/dE2, dL/dE1m1]; may be null like the map outputs
+template <typename T, typename CT>
+int run_rfgr_consts_bwd(const void* Mck, PulseOps in, const void* gMo, const void* gMt, int64_t every, void* gMi,
+                        void* grf, void* ggr, void* gloc, void* gBz, void* gb1, void* gC, void* work, int64_t N,
+                        int64_t nM, int64_t nT, hipStream_t st);
+
+// the CONSTS builds of K2bs (tu_signal_consts1 / 2 / 4 / 8_bwd.hip, one unit per coil capacity R >= nRx): the signal
+// adjoint with a non-null gsig, which also returns gC as above; rx may be null at R = 1 only
+template <typename T, typename CT, int R>
+int run_signal_consts_bwd(const void* Mck, PulseOps in, const void* gMo, int64_t every, const void* rx, int64_t nRx,
+                          const void* gsig, void* gMi, void* grf, void* ggr, void* gC, void* work, int64_t N, int64_t nM,
+                          int64_t nT, hipStream_t st);
+
 // K2s / K2bs: the received signal of the fused simulation (one transmit coil) for nRx <= sig_max_rx receive coils in one
 // launch, rx (N, nM, 2, nRx), sig / gsig (N, 2, nRec, nRx).  The forward has one unit per coil capacity R >= nRx
 // (tu_signal.hip: 1, where rx may be null = (1, 0); tu_signal_mrx2 / 4 / 8.hip).  Its adjoint takes a non-null

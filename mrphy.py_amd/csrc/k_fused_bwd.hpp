@@ -11,10 +11,20 @@
 // the partials into the running sums once per segment (segments descending) -- the sequential sum's rounding error then
 // grows with 16 + nT / 16 terms, not nT.  Lanes past nM carry a zero cotangent, so their sums are exact zeros; their
 // stores are guarded by `valid`.  Everything the MAPS = false build computes is computed by the same expressions.
-template <typename T, typename CT, bool RELAX, bool HB1, int INJ, bool MAPS = false>
-__global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdKArgsT<T, INJ, MAPS> a)
+//
+// CONSTS (tu_fused_consts_bwd.hip: modes 0 .. 2; tu_signal_consts*_bwd.hip: the signal modes 3 .. 6, i.e. the capacities
+// 1, 2, 4 and 8 -- every capacity K2bs has): the same sweep also gives the gradients w.r.t. the lane's own step
+// constants, gC = [dL/dg, dL/dE1, dL/dE2, dL/dE1m1] (g = gamma 2 pi dt), by the arithmetic of K3's GC builds
+// (bloch_math.hpp: adj_const_accumulate, adj_const_finish): lane-private sums over time in the two levels of the map
+// sums, no LDS, no workspace, no second pass.  In modes 0 .. 2 the CONSTS build forms the MAPS sums as well, each of
+// gloc, gBz, gb1, gC optional: one launch serves any mix of per-spin gradients, and the map outputs are the MAPS
+// build's bits.  The signal modes have CONSTS without MAPS.
+template <typename T, typename CT, bool RELAX, bool HB1, int INJ, bool MAPS = false, bool CONSTS = false>
+__global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdKArgsT<T, INJ, MAPS, CONSTS> a)
 {
     static_assert(!MAPS || INJ < 3, "the map gradients are built for the plain and the trajectory modes");
+    static_assert(!(MAPS && CONSTS), "the CONSTS build of modes 0 .. 2 forms the map sums itself");
+    constexpr bool MSUM = MAPS || (CONSTS && INJ < 3);      // the sums over time of dL/dB
     __shared__ __attribute__((aligned(16))) T red[5 * SEG * RED_PITCH];
     const int lane = threadIdx.x;
     const int64_t w = blockIdx.x, n = blockIdx.y;
@@ -74,6 +84,8 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdKArgsT<T, INJ, 
         // (aBr, aBi) = sum (g0 rf_re + g1 rf_im, g1 rf_re - g0 rf_im), the transpose of field_xy_acc's product
         // (one unused element each without MAPS, as wr / wi above)
         T aZ = T(0), aL[3] = {T(0), T(0), T(0)}, aBr = T(0), aBi = T(0);
+        // CONSTS: the running sums of the constants' gradients, reset per tile likewise
+        T aC[4] = {T(0), T(0), T(0), T(0)};
 
         auto field = [&](int64_t t, T& Bx, T& By, T& Bz) { field_1coil<HB1>(br, bi, pc, t, sp, Bx, By, Bz); };
 
@@ -128,6 +140,7 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdKArgsT<T, INJ, 
             SegStates<T> h;
             seg_recompute<RELAX>(k, t0, mx, my, mz, field, h);
             T pZ = T(0), pL[3] = {T(0), T(0), T(0)}, pBr = T(0), pBi = T(0);      // MAPS: this segment's partial sums
+            T pC[4] = {T(0), T(0), T(0), T(0)};                                   // CONSTS: likewise
             // 2. adjoint sweep, contributions to LDS
 #pragma unroll
             for (int sb = SEG / 4 - 1; sb >= 0; --sb) {
@@ -165,13 +178,17 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdKArgsT<T, INJ, 
                         }
                     }
                     T g0, g1, g2;
-                    rot_apply_adj<RELAX, T, CT>(k, ra[j], h.M0[st], h.M1[st], h.M2[st], hx, hy, hz, g0, g1, g2);
+                    if constexpr (CONSTS)     // (the carried state as it stands after the injection above goes in)
+                        rot_apply_adj_consts<RELAX, T, CT>(k, ra[j], Bx[j], By[j], Bz[j], h.M0[st], h.M1[st], h.M2[st],
+                                                           hx, hy, hz, g0, g1, g2, pC);
+                    else
+                        rot_apply_adj<RELAX, T, CT>(k, ra[j], h.M0[st], h.M1[st], h.M2[st], hx, hy, hz, g0, g1, g2);
                     red[red_idx(0 * SEG + st, lane)] = sp.lx * g2;
                     red[red_idx(1 * SEG + st, lane)] = sp.ly * g2;
                     red[red_idx(2 * SEG + st, lane)] = sp.lz * g2;
                     red[red_idx(3 * SEG + st, lane)] = HB1 ? br * g0 + bi * g1 : g0;
                     red[red_idx(4 * SEG + st, lane)] = HB1 ? br * g1 - bi * g0 : g1;
-                    if constexpr (MAPS) {
+                    if constexpr (MSUM) {
                         // the step's pulse sample: the wave-uniform scalars `field` read above
                         const int64_t t = t0 + st;
                         pZ += g2;
@@ -184,7 +201,11 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdKArgsT<T, INJ, 
                     }
                 }
             }
-            if constexpr (MAPS) {
+            if constexpr (CONSTS) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) aC[i] += pC[i];
+            }
+            if constexpr (MSUM) {
                 aZ += pZ; aL[0] += pL[0]; aL[1] += pL[1]; aL[2] += pL[2];
                 if constexpr (HB1) { aBr += pBr; aBi += pBi; }
             }
@@ -220,7 +241,14 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdKArgsT<T, INJ, 
         }
         adj_end<RELAX, T, CT>(k, hx, hy, hz);
         if (valid && a.gMi) { a.gMi[row * 3] = hx; a.gMi[row * 3 + 1] = hy; a.gMi[row * 3 + 2] = hz; }
-        if constexpr (MAPS) {
+        if constexpr (CONSTS) {
+            adj_const_finish<T, CT>(k, aC);                 // the precise fp32 mode carried t = E h: E divided out once
+            if (valid && a.gC) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) a.gC[row * 4 + i] = aC[i];
+            }
+        }
+        if constexpr (MSUM) {
             // once per spin; each output optional.  gBz is dL/d(df / gamma): the division by gamma and the folds to
             // the operands' own shapes are the host's
             if (valid && a.gloc) { a.gloc[row * 3] = aL[0]; a.gloc[row * 3 + 1] = aL[1]; a.gloc[row * 3 + 2] = aL[2]; }
@@ -301,6 +329,64 @@ int launch_rfgr_maps_bwd(const void* Mck, const PulseOps& in, const void* gMo, c
     else       { if (in.E1.p) MRPHY_K2BMT(true, false); else MRPHY_K2BMT(false, false); }
 #undef MRPHY_K2BMT
 #undef MRPHY_K2BM
+    e = launch_status();
+    if (e || !(grf || ggr)) return e;
+    return launch_p2<T>(work, ggr, 3, grf, 1, N, nT, a.P, st);
+}
+
+// Host: the launcher of the CONSTS builds of modes 0 .. 2 (tu_fused_consts_bwd.hip): launch_rfgr_maps_bwd with gC
+// (N, nM, 4) besides, optional as the map outputs are.
+template <typename T, typename CT>
+int launch_rfgr_consts_bwd(const void* Mck, const PulseOps& in, const void* gMo, const void* gMt, int64_t every, void* gMi,
+                           void* grf, void* ggr, void* gloc, void* gBz, void* gb1, void* gC, void* work, int64_t N,
+                           int64_t nM, int64_t nT, hipStream_t st)
+{
+    dim3 grid;
+    int e;
+    if (!fused_grid(N * nM * nT, k2b_waves(nM), N, grid, e)) return e;
+    FusedBwdConstsArgs<T> a;
+    static_cast<FusedBwdTrajArgs<T>&>(a) = fused_bwd_args<T>(Mck, in, gMo, gMt, every, gMi, work, N, nM, nT,
+                                                             grid.x);
+    a.gloc = (T*)gloc; a.gBz = (T*)gBz; a.gb1 = (T*)gb1; a.gC = (T*)gC;
+#define MRPHY_K2BC(RX_, HB_, INJ_) \
+    hipLaunchKernelGGL((k_bloch_rfgr_bwd<T, CT, RX_, HB_, INJ_, false, true>), grid, dim3(WAVE), 0, st, a)
+#define MRPHY_K2BCT(RX_, HB_)                                                                   \
+    do {                                                                                        \
+        if (!gMt) MRPHY_K2BC(RX_, HB_, 0);                                                      \
+        else if (every < SEG) MRPHY_K2BC(RX_, HB_, 1);                                          \
+        else MRPHY_K2BC(RX_, HB_, 2);                                                           \
+    } while (0)
+    if (in.b1) { if (in.E1.p) MRPHY_K2BCT(true, true);  else MRPHY_K2BCT(false, true); }
+    else       { if (in.E1.p) MRPHY_K2BCT(true, false); else MRPHY_K2BCT(false, false); }
+#undef MRPHY_K2BCT
+#undef MRPHY_K2BC
+    e = launch_status();
+    if (e || !(grf || ggr)) return e;
+    return launch_p2<T>(work, ggr, 3, grf, 1, N, nT, a.P, st);
+}
+
+// Host: the launcher of the CONSTS builds of the signal mode at the capacity R = 1, 2, 4, 8 (tu_signal_consts*_bwd.hip,
+// one unit each): launch_rfgr_bwd's signal mode with gC (N, nM, 4) besides; 1 <= nRx <= R, a null rx at R = 1 only.
+template <typename T, typename CT, int R>
+int launch_signal_consts_bwd(const void* Mck, const PulseOps& in, const void* gMo, int64_t every, const void* rx,
+                             int64_t nRx, const void* gsig, void* gMi, void* grf, void* ggr, void* gC, void* work,
+                             int64_t N, int64_t nM, int64_t nT, hipStream_t st)
+{
+    constexpr int INJ = R == 1 ? 3 : R == 2 ? 4 : R == 4 ? 5 : 6;
+    static_assert(inj_rx_cap(INJ) == R, "capacities 1, 2, 4, 8");
+    dim3 grid;
+    int e;
+    if (!fused_grid(N * nM * nT, k2b_waves(nM), N, grid, e)) return e;
+    FusedBwdSigConstsArgs<T> a;
+    static_cast<FusedBwdTrajArgs<T>&>(a) = fused_bwd_args<T>(Mck, in, gMo, nullptr, every, gMi, work, N, nM, nT,
+                                                             grid.x);
+    a.rx = (const T*)rx; a.gsig = (const T*)gsig; a.nRx = nRx; a.gC = (T*)gC;
+    a.nRec = sig_records(nT, every);
+#define MRPHY_K2BSC(RX_, HB_) \
+    hipLaunchKernelGGL((k_bloch_rfgr_bwd<T, CT, RX_, HB_, INJ, false, true>), grid, dim3(WAVE), 0, st, a)
+    if (in.b1) { if (in.E1.p) MRPHY_K2BSC(true, true);  else MRPHY_K2BSC(false, true); }
+    else       { if (in.E1.p) MRPHY_K2BSC(true, false); else MRPHY_K2BSC(false, false); }
+#undef MRPHY_K2BSC
     e = launch_status();
     if (e || !(grf || ggr)) return e;
     return launch_p2<T>(work, ggr, 3, grf, 1, N, nT, a.P, st);

@@ -79,8 +79,21 @@ struct FusedBwdMapsArgs : FusedBwdTrajArgs<T> {
     T* gBz;                          // (N, nM): dL/d(df / gamma) = sum over time of dL/dBz
     T* gb1;                          // (N, nM, 2): dL/db1; builds with a b1 map only
 };
-template <typename T, int INJ, bool MAPS>
-using FusedBwdKArgsT = std::conditional_t<MAPS, FusedBwdMapsArgs<T>, FusedBwdArgsT<T, INJ>>;
+// CONSTS builds (k_fused_bwd.hpp; mrphy_blochsim_rfgr_consts_bwd, mrphy_signal_rfgr_consts_bwd): the gradients w.r.t. the
+// lane's step constants besides, one more optional pointer after the arguments of the build they extend -- the MAPS
+// struct in modes 0 .. 2 (whose map sums the CONSTS build forms too), the signal struct in modes 3 .. 6.
+template <typename T>
+struct FusedBwdConstsArgs : FusedBwdMapsArgs<T> {
+    T* gC;                           // (N, nM, 4): [dL/dg, dL/dE1, dL/dE2, dL/dE1m1], g = gamma 2 pi dt
+};
+template <typename T>
+struct FusedBwdSigConstsArgs : FusedBwdSigArgs<T> {
+    T* gC;                           // as above
+};
+template <typename T, int INJ, bool MAPS, bool CONSTS = false>
+using FusedBwdKArgsT =
+    std::conditional_t<CONSTS, std::conditional_t<(INJ >= 3), FusedBwdSigConstsArgs<T>, FusedBwdConstsArgs<T>>,
+                       std::conditional_t<MAPS, FusedBwdMapsArgs<T>, FusedBwdArgsT<T, INJ>>>;
 // the kernarg layout is part of the kernels' machine code: `in` sits where its twelve fields were written out
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winvalid-offsetof"
@@ -96,10 +109,18 @@ constexpr bool fused_bwd_maps_args_layout =
     offsetof(FusedBwdMapsArgs<T>, every) == 240 && offsetof(FusedBwdMapsArgs<T>, nRec) == 248 &&
     offsetof(FusedBwdMapsArgs<T>, gloc) == 256 && offsetof(FusedBwdMapsArgs<T>, gBz) == 264 &&
     offsetof(FusedBwdMapsArgs<T>, gb1) == 272 && sizeof(FusedBwdMapsArgs<T>) == 280;
+template <typename T>
+constexpr bool fused_bwd_consts_args_layout =
+    offsetof(FusedBwdConstsArgs<T>, gloc) == 256 && offsetof(FusedBwdConstsArgs<T>, gb1) == 272 &&
+    offsetof(FusedBwdConstsArgs<T>, gC) == 280 && sizeof(FusedBwdConstsArgs<T>) == 288 &&
+    offsetof(FusedBwdSigConstsArgs<T>, rx) == 256 && offsetof(FusedBwdSigConstsArgs<T>, nRx) == 272 &&
+    offsetof(FusedBwdSigConstsArgs<T>, gC) == 280 && sizeof(FusedBwdSigConstsArgs<T>) == 288;
 #pragma clang diagnostic pop
 static_assert(fused_bwd_args_layout<float> && fused_bwd_args_layout<double>, "K2b's kernel arguments moved");
 static_assert(fused_bwd_maps_args_layout<float> && fused_bwd_maps_args_layout<double>,
               "the MAPS builds' kernel arguments moved");
+static_assert(fused_bwd_consts_args_layout<float> && fused_bwd_consts_args_layout<double>,
+              "the CONSTS builds' kernel arguments moved");
 
 // the arguments of K2b / K2bt (host side, shared by tu_fused_bwd.hip and tu_fused_mc_bwd.hip): a null gMt selects the
 // plain kernel (INJ == 0), which takes the FusedBwdArgs part; otherwise gMt is the cotangent the kernel reads
@@ -120,6 +141,32 @@ __device__ __forceinline__ void adj_inject(const SpinConst<T, CT>& k, T& hx, T& 
 #pragma clang fp contract(off)
     adj_begin<RELAX, T, CT>(k, gx, gy, gz);
     hx += gx; hy += gy; hz += gz;
+}
+
+// One adjoint step of the CONSTS builds: rot_apply_adj's expressions -- the core, then dL/dB = g dL/db, so (gx, gy, gz)
+// and the carried state keep rot_apply_adj's bits -- and the step's terms of the constants' gradients added to acc
+// (adj_const_accumulate, as K3's GC builds call it).  (Bx, By, Bz): the unscaled field of the step; (hx, hy, hz) comes
+// in as the carried state AFTER the step's record injection, which is the `s` the accumulation wants (t = E h in the
+// precise fp32 mode: adj_const_finish divides the E out of the finished sums).
+template <bool RELAX, typename T, typename CT>
+__device__ __forceinline__ void rot_apply_adj_consts(const SpinConst<T, CT>& k, const RotAdj<T>& r, T Bx, T By, T Bz,
+                                                     T mx, T my, T mz, T& hx, T& hy, T& hz, T& gx, T& gy, T& gz,
+                                                     T (&acc)[4])
+{
+#pragma clang fp contract(off)
+    using R = typename CTr<CT>::reg;
+    const T sx = hx, sy = hy, sz = hz;
+    T dbx, dby, dbz;
+    rot_apply_adj_core<RELAX, T, CT>(k, r, mx, my, mz, hx, hy, hz, dbx, dby, dbz);
+    gx = T(R(dbx) * k.g);
+    gy = T(R(dby) * k.g);
+    gz = T(R(dbz) * k.g);
+    adj_const_accumulate<RELAX, T, CT>(r, Bx, By, Bz, mx, my, mz, sx, sy, sz, dbx, dby, dbz, acc);
+    // The sums are read at the end of the segment only, and the compiler sinks each step's terms below the guards of
+    // the following steps' cold large-angle paths, down to there -- with the step's m, b, S, C, s and B alive all the
+    // way: a private segment in fp64.  Pinned as bloch_math.hpp's pin_state pins the forward state: the step's terms are
+    // complete here.  No instruction is emitted.
+    asm volatile("" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]));
 }
 
 // Two global round trips per segment used to sit on the critical path: the checkpoint (used

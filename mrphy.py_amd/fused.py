@@ -15,8 +15,11 @@ and ``grad_rf``/``grad_gr`` come out of a deterministic reduction over spins; pa
 the same sweep also gives the gradients w.r.t. the spin-side maps ``loc``, ``Δf`` and ``b1Map``
 (``mrphy_blochsim_rfgr_maps_bwd``): they are the per-step ``dL/dBeff`` the sweep holds in registers,
 summed over time per spin in a fixed order, so neither ``Beff`` nor ``grad_Beff`` is ever written.
-Cases the fused adjoint does not cover (more coils, map gradients under parallel transmit, pulses
-shorter than 16 steps with a map gradient) compose ``rfgr2beff`` and ``blochsim`` instead -- HIP
+So do the gradients w.r.t. ``T1``, ``T2``, ``γ``, ``dt`` (or the entries of ``consts=``) and ``γ_beff``
+(``mrphy_blochsim_rfgr_consts_bwd``, ``mrphy_signal_rfgr_consts_bwd``): the sweep sums the step constants'
+gradients per spin as K3's ``mrphy_blochsim_bwd_consts`` does, and autograd carries them on to the operands.
+Cases the fused adjoint does not cover (more coils, map or constants' gradients under parallel transmit, pulses
+shorter than 16 steps with a map or constants' gradient) compose ``rfgr2beff`` and ``blochsim`` instead -- HIP
 kernels as well; a pulse length that is not a multiple of 16 is split into a fused part and a tail
 of at most 15 composed steps.
 
@@ -117,6 +120,29 @@ def _fold_map_grads(gloc, gBz, gb1, p, likes):
     return tuple(out)
 
 
+def _fold_const_grads(gC, p, likes, needs):
+    r"""``(grad_γ2πdt, grad_E1, grad_E2, grad_E1_1)`` from the per-spin ``gC`` `(N, *Nd, 4)` of the CONSTS builds: each
+    summed over the axes its constant was broadcast along, in the constant's own shape and dtype and on its device
+    (``likes``: their :func:`_like`, ``None`` for an absent one), ``None`` where ``needs`` does not ask -- as
+    ``sims.BlochSimHIP.backward`` folds the ``gC`` of ``mrphy_blochsim_bwd_consts``."""
+    from . import sims
+    out = []
+    for i, (like, want) in enumerate(zip(likes, needs)):
+        if not want or like is None:
+            out.append(None)
+            continue
+        c = torch.empty(like[0], dtype=like[1], device='meta')
+        out.append(sims._reduce_to_const(gC[..., i], c, p.N, p.Nd).to(like[2]))
+    return tuple(out)
+
+
+def _fold_gamma_beff_grad(gBz, p, like):
+    r"""``grad_γ_beff`` from ``gBz = dL/d(Δf / γ_beff)`` `(N, *Nd)`: ``-gBz·Δf / γ_beff²`` summed to ``γ_beff``'s own
+    shape, as ``RfGr2BeffHIP.backward`` forms it (``beffective.py:161-167``)."""
+    from .beffective import _sum_to
+    return _sum_to(-gBz * p.df_v / (p.gam_v * p.gam_v), like[0]).to(device=like[2], dtype=like[1])
+
+
 def _fold_grads(gMi, g_rf, g_gr, p, rf_shape, gr_shape, rf_dtype, gr_dtype):
     r"""``(grad_Mi, grad_rf, grad_gr)`` in the shapes and dtypes the caller's ``rf`` and ``gr`` had."""
     from .beffective import _fold_pulse_grad
@@ -136,10 +162,17 @@ class BlochSimRfGrHIP(Function):
     ``loc``, ``Δf``, ``b1Map``: the caller's own tensors, handed over only when one of them wants a gradient through
     the fused adjoint (one transmit coil; ``pulse_on_spins`` holds their detached, normalised copies, which is what
     the kernels read).  The backward then runs ``mrphy_blochsim_rfgr_maps_bwd`` in place of the two entry points
-    above -- the same sweep, the same bits for ``grad_Mi``, ``grad_rf``, ``grad_gr``."""
+    above -- the same sweep, the same bits for ``grad_Mi``, ``grad_rf``, ``grad_gr``.  ``γ_beff`` likewise, when it
+    wants a gradient and there is a ``Δf``: its gradient is a fold of the same ``gBz`` as ``Δf``'s.
+
+    ``γ2πdt``, ``E1``, ``E2``, ``E1_1`` that require grad (:func:`_route` forms them with differentiable torch ops when
+    ``T1, T2, γ, dt`` do; the entries of ``consts=`` are the caller's own) get their gradients from the same sweep
+    again: ``mrphy_blochsim_rfgr_consts_bwd`` returns them per spin besides everything the entry points above return,
+    bit for bit, and they are summed here over the axes each constant broadcasts along."""
 
     @staticmethod
-    def forward(ctx, Mi, rf, gr, p, γ2πdt, E1, E2, E1_1, want_ckpt=False, every=None, loc=None, Δf=None, b1Map=None):
+    def forward(ctx, Mi, rf, gr, p, γ2πdt, E1, E2, E1_1, want_ckpt=False, every=None, loc=None, Δf=None, b1Map=None,
+                γ_beff=None):
         lib = _lib.require_library()
         device, dtype = Mi.device, Mi.dtype
         need = bool(want_ckpt)
@@ -158,18 +191,22 @@ class BlochSimRfGrHIP(Function):
         if need:
             ctx.save_for_backward(Mck)
             ctx.keep = (p, code, consts, alive, rf.shape, gr.shape, rf.dtype, gr.dtype, every)
-            ctx.maps_like = tuple(None if x is None else _like(x) for x in (loc, Δf, b1Map))
+            ctx.maps_like = tuple(None if x is None else _like(x) for x in (loc, Δf, b1Map, γ_beff))
+            ctx.const_like = tuple(None if x is None else _like(x) for x in (γ2πdt, E1, E2, E1_1))
         return M
 
     @staticmethod
     def backward(ctx, grad_M):
-        needs = ctx.needs_input_grad[0:3]
-        needs_maps = tuple(ctx.needs_input_grad[10:13])     # loc, Δf, b1Map: all False where they were not handed over
-        if not any(needs) and not any(needs_maps):
-            return (None,) * 13
+        nig = tuple(ctx.needs_input_grad) + (False,) * 4   # (as long as the arguments handed over: loc .. γ_beff may be missing)
+        needs = nig[0:3]
+        needs_c = nig[4:8]                                  # γ2πdt, E1, E2, E1_1
+        needs_maps = nig[10:13]                             # loc, Δf, b1Map: all False where they were not handed over
+        if not any(needs) and not any(needs_maps) and not any(needs_c) and not nig[13]:
+            return (None,) * 14
         lib = _lib.require_library()
         (Mck,) = ctx.saved_tensors
         p, code, consts, _alive, rf_shape, gr_shape, rf_dtype, gr_dtype, every = ctx.keep
+        need_γb = nig[13] and p.df is not None        # without Δf the field does not depend on γ_beff
         traj = every is not None
         # the precise adjoint divides by E once (as the reference's does at every step): refuse E == 0 HERE, where it
         # matters -- the forward succeeds as the reference's does; cached per constants
@@ -180,25 +217,32 @@ class BlochSimRfGrHIP(Function):
         grads, outs, work = _backward_prep(lib, p, code, needs, dtype, device)
         tr = (every,) if traj else ()
         pulse_grads = lambda: _fold_grads(*grads, p, rf_shape, gr_shape, rf_dtype, gr_dtype)  # noqa: E731
-        if any(needs_maps):                     # one transmit coil (_route): the MAPS builds of K2b / K2bt
-            mgrads, mouts = _maps_backward_prep(p, needs_maps, dtype, device)
-            if p.N * p.nM * p.nT == 0:          # nothing depends on the maps either
+        if any(needs_maps) or any(needs_c) or need_γb:
+            # one transmit coil (_route): the MAPS builds of K2b / K2bt, or -- with a constant's gradient wanted -- the
+            # CONSTS builds, which form the map sums too
+            want_maps = (needs_maps[0], needs_maps[1] or need_γb, needs_maps[2])
+            mgrads, mouts = _maps_backward_prep(p, want_maps, dtype, device)
+            gC = torch.empty((p.N,) + p.Nd + (4,), dtype=dtype, device=device) if any(needs_c) else None
+            if p.N * p.nM * p.nT == 0:          # nothing depends on the maps or the constants either
                 _empty_problem_grads(grads, None if traj else gM)
-                for g in mgrads:
+                for g in (*mgrads, gC):
                     if g is not None:
                         g.zero_()
             else:
-                name = 'mrphy_blochsim_rfgr_maps_bwd'
+                name = 'mrphy_blochsim_rfgr_maps_bwd' if gC is None else 'mrphy_blochsim_rfgr_consts_bwd'
                 gMo, gMt, ev = (None, gM.data_ptr(), every) if traj else (gM.data_ptr(), None, 0)
                 with torch.cuda.device(device):
-                    rc = lib.mrphy_blochsim_rfgr_maps_bwd(code, Mck.data_ptr(), *p.k0_args(), *consts, gMo, gMt, ev,
-                                                          *outs, *mouts, work.data_ptr(), work.numel(),
-                                                          p.N, p.nM, p.nT, _host.current_stream(device))
+                    rc = getattr(lib, name)(code, Mck.data_ptr(), *p.k0_args(), *consts, gMo, gMt, ev, *outs, *mouts,
+                                            *(() if gC is None else (gC.data_ptr(),)), work.data_ptr(), work.numel(),
+                                            p.N, p.nM, p.nT, _host.current_stream(device))
                 _lib.check(rc, name)
-            return (*pulse_grads(), *(None,) * 7, *_fold_map_grads(*mgrads, p, ctx.maps_like))
+            g_c = (None,) * 4 if gC is None else _fold_const_grads(gC, p, ctx.const_like, needs_c)
+            g_γb = _fold_gamma_beff_grad(mgrads[1], p, ctx.maps_like[3]) if need_γb else None
+            g_maps = _fold_map_grads(mgrads[0], mgrads[1] if needs_maps[1] else None, mgrads[2], p, ctx.maps_like)
+            return (*pulse_grads(), None, *g_c, None, None, *g_maps, g_γb)
         if p.N * p.nM * p.nT == 0:
             _empty_problem_grads(grads, None if traj else gM)
-            return (*pulse_grads(), *(None,) * 10)
+            return (*pulse_grads(), *(None,) * 11)
         if p.nC == 1:
             name, nc = ('mrphy_blochsim_rfgr_traj_bwd' if traj else 'mrphy_blochsim_rfgr_bwd'), ()
         else:                                   # parallel transmit
@@ -208,7 +252,7 @@ class BlochSimRfGrHIP(Function):
                                     work.data_ptr(), work.numel(), p.N, p.nM, p.nT, *nc,
                                     _host.current_stream(device))
         _lib.check(rc, name)
-        return (*pulse_grads(), *(None,) * 10)
+        return (*pulse_grads(), *(None,) * 11)
 
 
 class SignalRfGrHIP(Function):
@@ -219,7 +263,8 @@ class SignalRfGrHIP(Function):
     ``mrphy_signal_rfgr_max_rx(code)``, ``sig`` is `(N, xy, nRec, nRx)`: every coil from one simulation, forward and
     adjoint (``mrphy_signal_rfgr_mrx_fwd`` / ``_mrx_bwd``), each coil's samples the bits the one-coil call gives.  Both
     outputs may carry a cotangent; an output the loss does not use costs nothing (its cotangent stays ``None``).
-    ``want_ckpt`` as in :class:`BlochSimRfGrHIP`."""
+    ``want_ckpt`` as in :class:`BlochSimRfGrHIP`; so are the gradients of ``γ2πdt``, ``E1``, ``E2``, ``E1_1`` that require
+    grad (``mrphy_signal_rfgr_consts_bwd``, for one coil and for an array, in place of the two adjoints above)."""
 
     @staticmethod
     def forward(ctx, Mi, rf, gr, p, rx, γ2πdt, E1, E2, E1_1, want_ckpt=False, every=1):
@@ -228,7 +273,7 @@ class SignalRfGrHIP(Function):
         need = bool(want_ckpt)
         code, alive, consts, Mck, ckpt = _forward_prep(lib, p, γ2πdt, E1, E2, E1_1, dtype, device, need)
         mrx = (rx.shape[-1],) if rx is not None and rx.ndim == 4 else ()      # the coil count, for the _mrx_ entry points
-        consts = (*consts, None if rx is None else rx.data_ptr(), *mrx)
+        rxa = (None if rx is None else rx.data_ptr(), *mrx)
         Mi_c = Mi.detach().contiguous()
         sig = torch.empty((p.N, 2, -(-p.nT // every), *mrx), dtype=dtype, device=device)
         Mo = torch.empty_like(Mi_c)
@@ -241,40 +286,50 @@ class SignalRfGrHIP(Function):
             sig.zero_()                         # no spin: empty sums (the library writes nothing for an empty problem)
         name = 'mrphy_signal_rfgr_mrx_fwd' if mrx else 'mrphy_signal_rfgr_fwd'
         with torch.cuda.device(device):
-            rc = getattr(lib, name)(code, Mi_c.data_ptr(), *p.k0_args(), *consts, Mo.data_ptr(), *ckpt,
+            rc = getattr(lib, name)(code, Mi_c.data_ptr(), *p.k0_args(), *consts, *rxa, Mo.data_ptr(), *ckpt,
                                     sig.data_ptr(), every, work.data_ptr(), work.numel(),
                                     p.N, p.nM, p.nT, p.nC, _host.current_stream(device))
         _lib.check(rc, name)
         ctx.set_materialize_grads(False)
         if need:
             ctx.save_for_backward(Mck)
-            ctx.keep = (p, code, consts, (*alive, rx), rf.shape, gr.shape, rf.dtype, gr.dtype, every, bool(mrx))
+            ctx.keep = (p, code, consts, rxa, (*alive, rx), rf.shape, gr.shape, rf.dtype, gr.dtype, every, bool(mrx))
+            ctx.const_like = tuple(None if x is None else _like(x) for x in (γ2πdt, E1, E2, E1_1))
         return sig, Mo
 
     @staticmethod
     def backward(ctx, grad_sig, grad_Mo):
         needs = ctx.needs_input_grad[0:3]
-        if not any(needs) or (grad_sig is None and grad_Mo is None):
+        needs_c = tuple(ctx.needs_input_grad[5:9])          # γ2πdt, E1, E2, E1_1
+        if not (any(needs) or any(needs_c)) or (grad_sig is None and grad_Mo is None):
             return (None,) * 11
         lib = _lib.require_library()
         (Mck,) = ctx.saved_tensors
-        p, code, consts, _alive, rf_shape, gr_shape, rf_dtype, gr_dtype, every, mrx = ctx.keep
+        p, code, consts, rxa, _alive, rf_shape, gr_shape, rf_dtype, gr_dtype, every, mrx = ctx.keep
         _host.require_invertible_relaxation(code, _alive[1], _alive[2], 'fused.signal_rfgr')
         device, dtype = Mck.device, Mck.dtype
         gs = None if grad_sig is None else grad_sig.to(dtype).contiguous()
         gM = None if grad_Mo is None else grad_Mo.to(dtype).contiguous()
         grads, outs, work = _backward_prep(lib, p, code, needs, dtype, device)      # one transmit coil: K2b's workspace
+        gC = torch.empty((p.N,) + p.Nd + (4,), dtype=dtype, device=device) if any(needs_c) else None
         ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        done = lambda: (*_fold_grads(*grads, p, rf_shape, gr_shape, rf_dtype, gr_dtype), None, None,  # noqa: E731
+                        *((None,) * 4 if gC is None else _fold_const_grads(gC, p, ctx.const_like, needs_c)), None, None)
         if p.N * p.nM * p.nT == 0:
             _empty_problem_grads(grads, gM)
-            return (*_fold_grads(*grads, p, rf_shape, gr_shape, rf_dtype, gr_dtype), *(None,) * 8)
-        name = 'mrphy_signal_rfgr_mrx_bwd' if mrx else 'mrphy_signal_rfgr_bwd'
+            if gC is not None:
+                gC.zero_()                      # nothing depends on the constants either
+            return done()
+        if gC is not None:                      # the CONSTS builds take one coil and an array alike: rx, nRx
+            name, rxa, gc = 'mrphy_signal_rfgr_consts_bwd', (rxa[0], rxa[1] if mrx else 1), (gC.data_ptr(),)
+        else:
+            name, gc = ('mrphy_signal_rfgr_mrx_bwd' if mrx else 'mrphy_signal_rfgr_bwd'), ()
         with torch.cuda.device(device):
-            rc = getattr(lib, name)(code, Mck.data_ptr(), *p.k0_args(), *consts, ptr(gM), ptr(gs), every,
-                                    *outs, work.data_ptr(), work.numel(),
+            rc = getattr(lib, name)(code, Mck.data_ptr(), *p.k0_args(), *consts, *rxa, ptr(gM), ptr(gs), every,
+                                    *outs, *gc, work.data_ptr(), work.numel(),
                                     p.N, p.nM, p.nT, _host.current_stream(device))
         _lib.check(rc, name)
-        return (*_fold_grads(*grads, p, rf_shape, gr_shape, rf_dtype, gr_dtype), *(None,) * 8)
+        return done()
 
 
 def _route(Mi, rf, gr, loc, every, kw, signal=False, rx=None):
@@ -289,7 +344,13 @@ def _route(Mi, rf, gr, loc, every, kw, signal=False, rx=None):
     block of up to ``mrphy_signal_rfgr_max_rx(code)`` coils -- one forward and one backward launch for all of a
     block's coils; ``sig`` is the blocks' concatenated on the coil axis, ``Mo`` the first block's, and autograd adds the
     blocks' gradients.  The signal kernels take one transmit coil and form no gradient w.r.t. ``rx``: parallel transmit
-    and that gradient are composed."""
+    and that gradient are composed.
+
+    ``consts_grad``: one of ``T1, T2, γ, dt`` -- or an entry of ``consts=`` -- requires grad.  With one transmit coil
+    and whole segments the constants then reach the Function as differentiable tensors (formed as
+    ``slowsims.blochsim`` forms them, with the values :func:`mrphy_amd.sims.relax_constants` gives) and its backward
+    runs the CONSTS builds; every other case is composed, or split as above.  A ``γ_beff`` that requires grad where
+    there is a ``Δf`` counts with the spin-side maps: its gradient is a fold of theirs."""
     from . import beffective, sims
     _host.require_device_tensor(Mi, 'Mi')
     Δf, b1Map, T1, T2 = kw['Δf'], kw['b1Map'], kw['T1'], kw['T2']
@@ -297,9 +358,12 @@ def _route(Mi, rf, gr, loc, every, kw, signal=False, rx=None):
     lib = _lib.require_library()
     grad_on = torch.is_grad_enabled()
     rq = lambda x: grad_on and isinstance(x, Tensor) and x.requires_grad  # noqa: E731
-    maps_grad = any(rq(x) for x in (loc, Δf, b1Map))
+    γb_grad = rq(kw['γ_beff']) and Δf is not None       # (without Δf the field does not depend on γ_beff)
+    maps_grad = any(rq(x) for x in (loc, Δf, b1Map)) or γb_grad
     rx_grad = signal and rq(rx)
     pulse_grad = any(rq(x) for x in (Mi, rf, gr))
+    consts_grad = any(rq(x) for x in (kw['consts'].values() if kw['consts'] is not None
+                                      else (T1, T2, kw['γ'], kw['dt'])))
     p = beffective._PulseOnSpins(rf.detach(), gr.detach(), loc.detach(),
                                  None if Δf is None else Δf.detach(),
                                  None if b1Map is None else b1Map.detach(), kw['γ_beff'].detach())
@@ -311,14 +375,16 @@ def _route(Mi, rf, gr, loc, every, kw, signal=False, rx=None):
     # the map gradients come out of the one-coil adjoint's sweep (the MAPS builds of K2b / K2bt); the signal call keeps
     # its composed route for them, whose trajectory takes this one
     maps_fused = maps_grad and one_coil and not signal
-    if not seg_ok and p.nT > seg and not rx_grad and \
-            (maps_fused or (pulse_grad and not maps_grad and (one_coil or ptx))):
+    # the constants' gradients likewise (the CONSTS builds), in the signal call as well -- but not under parallel transmit
+    consts_fused = consts_grad and one_coil and (not signal or not maps_grad)
+    if not seg_ok and p.nT > seg and not rx_grad and (not consts_grad or consts_fused) and \
+            (maps_fused or ((pulse_grad or consts_fused) and not maps_grad and (one_coil or ptx))):
         return 'split', (p.nT // seg) * seg
     # fp64 with more than 8 transmit coils: the fused forward has no register build for it (it would spill),
     # the composed route does (k_rfgr2beff_steps / _pk + K1) and gives the same bits
     wide_f64 = (p.dtype == torch.float64 and p.nC > 8) or (p.b1 is not None and p.nC > 64)   # (> 64: coil-blocked K0 + K1)
     if (maps_grad and not (maps_fused and seg_ok)) or rx_grad or wide_f64 or (pulse_grad and not fused_adjoint_ok) \
-            or (signal and p.nC != 1):
+            or (signal and p.nC != 1) or (consts_grad and not (consts_fused and seg_ok)):
         return 'composed', None
 
     device, dtype = Mi.device, Mi.dtype
@@ -326,9 +392,15 @@ def _route(Mi, rf, gr, loc, every, kw, signal=False, rx=None):
     assert tuple(Mi.shape[:-1]) == (p.N,) + p.Nd
     if kw['consts'] is not None:
         γ2πdt, E1, E2, E1_1 = (kw['consts'].get(k) for k in ('γ2πdt', 'E1', 'E2', 'E1_1'))
+    elif consts_grad:
+        # differentiable, as slowsims.blochsim forms them: relax_constants' expressions on the same padded operands on
+        # the same device, so the values -- and Mo -- are the bits of the call that does not differentiate them
+        cdev = _host.const_device(device)
+        pad = lambda x: None if x is None else _host.pad_trailing(x.to(cdev), 1 + len(p.Nd) + 2)  # noqa: E731
+        γ2πdt, E1, E2, E1_1 = sims._gamma_dt_constants(pad(T1), pad(T2), pad(kw['γ']), pad(kw['dt']))
     else:
         γ2πdt, E1, E2, E1_1 = sims.relax_constants(T1, T2, kw['γ'], kw['dt'], 1 + len(p.Nd) + 2, device)
-    want = (pulse_grad or maps_fused) and fused_adjoint_ok
+    want = (pulse_grad or maps_fused or consts_fused) and fused_adjoint_ok
     if signal:
         apply = lambda r: SignalRfGrHIP.apply(Mi, rf, gr, p, r, γ2πdt, E1, E2, E1_1, want, every)  # noqa: E731
         if rx is None:
@@ -346,7 +418,8 @@ def _route(Mi, rf, gr, loc, every, kw, signal=False, rx=None):
         outs = [apply(r[..., c:c + cap].contiguous()) for c in range(0, nrx, cap)]
         return 'fused', (outs[0][0] if len(outs) == 1 else torch.cat([o[0] for o in outs], dim=-1), outs[0][1])
     if maps_fused:
-        return 'fused', BlochSimRfGrHIP.apply(Mi, rf, gr, p, γ2πdt, E1, E2, E1_1, want, every, loc, Δf, b1Map)
+        return 'fused', BlochSimRfGrHIP.apply(Mi, rf, gr, p, γ2πdt, E1, E2, E1_1, want, every, loc, Δf, b1Map,
+                                              kw['γ_beff'] if γb_grad else None)
     return 'fused', BlochSimRfGrHIP.apply(Mi, rf, gr, p, γ2πdt, E1, E2, E1_1, want, every)
 
 
@@ -361,14 +434,16 @@ def blochsim_rfgr(
     γ=γ, dt=dt)`` without the intermediate tensor, differentiable w.r.t. ``Mi``, ``rf``, ``gr`` and the spin-side
     maps ``loc``, ``Δf``, ``b1Map`` (with one transmit coil through the fused adjoint, which sums the sweep's
     ``dL/dBeff`` over time per spin; parallel transmit and pulses shorter than 16 steps through ``rfgr2beff`` +
-    ``blochsim``).  ``γ_beff`` is not differentiated here.
+    ``blochsim``), and w.r.t. ``T1``, ``T2``, ``γ``, ``dt`` (or the entries of ``consts``) and ``γ_beff`` the same way:
+with one transmit coil the fused adjoint returns the step constants' gradients per spin from the same sweep
+(``mrphy_blochsim_rfgr_consts_bwd``), otherwise ``rfgr2beff`` + ``slowsims.blochsim`` do.
 
     ``Mi``: `(N, *Nd, xyz)`; the other arguments as in
     :func:`mrphy_amd.beffective.rfgr2beff` and :func:`mrphy_amd.sims.blochsim`.  ``consts``
     (``dict(γ2πdt=, E1=, E1_1=, E2=)``) replaces ``T1, T2, γ, dt`` as in
     :func:`mrphy_amd.sims.blochsim_consts`.
     """
-    from . import beffective, sims
+    from . import beffective, sims, slowsims
     kw = dict(Δf=Δf, b1Map=b1Map, γ_beff=γ_beff, T1=T1, T2=T2, γ=γ, dt=dt, consts=consts)
     route, out = _route(Mi, rf, gr, loc, None, kw)
     if route == 'split':
@@ -382,7 +457,8 @@ def blochsim_rfgr(
         beff = beffective.rfgr2beff(rf, gr, loc, Δf=Δf, b1Map=b1Map, γ=γ_beff, lazy=False)
         if consts is not None:
             return sims.blochsim_consts(Mi, beff, **consts)
-        return sims.blochsim(Mi, beff, T1=T1, T2=T2, γ=γ, dt=dt)
+        # (slowsims.blochsim is sims.blochsim unless T1, T2, γ or dt requires grad: then K3 returns their gradients too)
+        return slowsims.blochsim(Mi, beff, T1=T1, T2=T2, γ=γ, dt=dt)
     return out
 
 
@@ -415,15 +491,16 @@ def blochsim_rfgr_traj(
     ceil(nT / every)``, where ``Mt[..., j, :]`` is M after step ``min((j+1)·every, nT) - 1`` -- so the last record
     is the final state, equal to ``blochsim_rfgr(...)`` bit for bit, and ``every = 1`` gives the reference's
     history ``Mhst`` (``sims.py:83``).  Differentiable w.r.t. ``Mi``, ``rf``, ``gr`` and the spin-side maps ``loc``,
-    ``Δf``, ``b1Map`` (one transmit coil: the fused adjoint, one launch whatever ``every`` is); operands, dtypes,
-    ``consts`` and the precision mode as :func:`blochsim_rfgr`.
+    ``Δf``, ``b1Map`` and the constants ``T1``, ``T2``, ``γ``, ``dt`` (or the entries of ``consts``), ``γ_beff`` (one
+    transmit coil: the fused adjoint, one launch whatever ``every`` is and whichever of them require grad); operands,
+    dtypes, ``consts`` and the precision mode as :func:`blochsim_rfgr`.
 
     Layout: the result is a view ``.movedim(0, -2)`` of time-major storage `(nRec, N, *Nd, 3)` -- each record is
     one contiguous block, which the kernel writes with coalesced per-wave stores.  ``Mt.movedim(-2, 0)`` gives the
     contiguous tensor back; a loss that keeps that layout hands its gradient to the adjoint without a copy.
 
-    The cases the fused adjoint does not cover (gradients w.r.t. ``loc``/``Δf``/``b1Map`` under parallel transmit or
-    with fewer than 16 steps, a parallel-transmit gradient with more coils than
+    The cases the fused adjoint does not cover (gradients w.r.t. ``loc``/``Δf``/``b1Map`` or the constants under parallel
+    transmit or with fewer than 16 steps, a parallel-transmit gradient with more coils than
     ``mrphy_blochsim_rfgr_mc_max_coils()``, fp64 with more than 8 coils) run one
     :func:`blochsim_rfgr` per record segment and stack the results: correct and differentiable, slower.  A pulse
     length that is not a multiple of the 16-step checkpoint segment is split as :func:`blochsim_rfgr` splits it.
@@ -491,7 +568,9 @@ def signal_rfgr(
     ``rx``: `(N, *Nd, xy)` or `(N, *Nd, xy, nRx)`, the layout of ``b1Map``; ``None`` is ``(1, 0)``, the plain sums of
     ``Mx`` and ``My``.  Returns ``sig`` `(N, xy, nRec)` -- `(N, xy, nRec, nRx)` when ``rx`` has a coil axis -- the layout
     of ``rf``; with ``return_Mo=True`` ``(sig, Mo)``, where ``Mo`` equals ``blochsim_rfgr(...)`` bit for bit, so a
-    sequence can carry on from it.  Differentiable w.r.t. ``Mi``, ``rf``, ``gr`` through both outputs; the other
+    sequence can carry on from it.  Differentiable w.r.t. ``Mi``, ``rf``, ``gr`` and the constants ``T1``, ``T2``, ``γ``,
+    ``dt`` (or the entries of ``consts``) through both outputs -- what a fit of T1 / T2 maps to a measured signal
+    differentiates -- inside the signal kernels (``mrphy_signal_rfgr_consts_bwd``, every coil capacity); the other
     arguments, the dtypes, ``consts`` and the precision mode as :func:`blochsim_rfgr_traj`.  The reference has no
     counterpart (it forms ``Mhst`` and drops it, ``sims.py:83,131``): this is an extension.
 
@@ -501,7 +580,8 @@ def signal_rfgr(
     adjoint: up to ``mrphy_signal_rfgr_max_rx`` coils (8) per launch, more in blocks of that many, and every coil's
     samples are the bits a call with that coil alone gives.  A gradient with a pulse length that is not a
     multiple of the 16-step checkpoint segment is split as :func:`blochsim_rfgr_traj` splits it.  Parallel transmit,
-    gradients w.r.t. ``loc``/``Δf``/``b1Map``/``rx`` and fp64 above 8 coils compose :func:`blochsim_rfgr_traj` with
+    gradients w.r.t. ``loc``/``Δf``/``b1Map``/``rx`` (and w.r.t. a ``γ_beff`` that multiplies a ``Δf``: a fold of
+    ``Δf``'s) and fp64 above 8 coils compose :func:`blochsim_rfgr_traj` with
     the product and the sum in torch (with one transmit coil and map gradients that trajectory is one fused forward
     and one fused adjoint, not one simulation per record).  On a spin axis sharded over GPUs the signal is the sum of the ranks' signals
     (``dist.all_reduce_pulse_grads`` reduces tensors of this size).
