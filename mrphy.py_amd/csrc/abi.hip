@@ -1,6 +1,7 @@
 // abi.hip -- the C ABI of libmrphy_hip.so (include/mrphy_hip.h): argument validation and dispatch on the
 // dtype code to the launchers of the tu_*.hip units (internal.hpp).  No kernel is defined here.  The operands of the
-// fused family are packed into one struct at the entry point (MRPHY_PULSE_OPS below) and travel as that struct.
+// fused family are packed into one struct at the entry point (MRPHY_PULSE_OPS below) and travel as that struct; so does
+// everything else an adjoint call of that family carries (MRPHY_ADJOINT_REQ).
 #include "host_common.hpp"
 
 using namespace mrphy_i;
@@ -77,56 +78,51 @@ int rfgr_fwd(bool traj, int dtype, const void* Mi, const PulseOps& in, void* Mo,
     MRPHY_DISPATCH(dtype, (run_rfgr_fwd<T, CT>(Mi, in, Mo, Mck, ck_every, Mt, every, N, nM, nT, nC, st)));
 }
 
-// grad_M: grad_Mo, or (traj) grad_Mt
-int rfgr_bwd(bool traj, int dtype, const void* Mck, const PulseOps& in, const void* grad_M, int64_t every,
-             void* grad_Mi, void* grad_rf, void* grad_gr, void* work, size_t work_bytes, int64_t N, int64_t nM,
-             int64_t nT, void* stream)
+// What an adjoint entry point packs besides MRPHY_PULSE_OPS: the request (geom.hpp: AdjointReq), once -- the part every
+// one of them has, under the same names; the cotangents and per-spin outputs it has itself it sets by name.
+#define MRPHY_ADJOINT_REQ(nC_) \
+    AdjointReq r{};            \
+    r.Mck = Mck; r.gMi = grad_Mi; r.grf = grad_rf; r.ggr = grad_gr; r.work = work; r.N = N; r.nM = nM; r.nT = nT; r.nC = nC_
+
+// The one dispatch of a validated request to its build's launcher (internal.hpp: AdjBuild), one row per build
+int dispatch_adjoint(AdjBuild b, int dtype, const AdjointReq& r, const PulseOps& in, void* stream)
 {
-    if (int e = check_common(dtype, N, nM, nT)) return e;
-    if (nT % SEG != 0 || (traj && every < 1)) return MRPHY_EINVAL;   // whole checkpoint segments only
-    if (N * nM * nT == 0) return 0;
-    if (!Mck || !grad_M || !work) return MRPHY_EINVAL;
-    if (int e = check_ops(in, true, false)) return e;
-    if (work_bytes < mrphy_blochsim_rfgr_bwd_workspace(dtype, N, nM, nT)) return MRPHY_ENOSPC;
     hipStream_t st = (hipStream_t)stream;
-    MRPHY_DISPATCH(dtype, (run_rfgr_bwd<T, CT>(Mck, in, traj ? nullptr : grad_M, traj ? grad_M : nullptr, every,
-                                               nullptr, nullptr, grad_Mi, grad_rf, grad_gr, work, N, nM, nT, st)));
+#define MRPHY_ADJ(B_) \
+    case AdjBuild::B_: MRPHY_DISPATCH(dtype, (run_fused_bwd<AdjBuild::B_, T, CT>(r, in, st)))
+    switch (b) {
+        MRPHY_ADJ(PLAIN);
+        MRPHY_ADJ(MRX);
+        MRPHY_ADJ(MAPS);
+        MRPHY_ADJ(CONSTS);
+        MRPHY_ADJ(SIG_CONSTS1);
+        MRPHY_ADJ(SIG_CONSTS2);
+        MRPHY_ADJ(SIG_CONSTS4);
+        MRPHY_ADJ(SIG_CONSTS8);
+        MRPHY_ADJ(MC);
+    }
+#undef MRPHY_ADJ
+    return MRPHY_EINVAL;
 }
 
-// The MAPS builds: grad_Mo (mode 0) or grad_Mt (modes 1, 2), exactly one of them; refuses what rfgr_bwd refuses, and a
-// grad_b1 without a b1 map to differentiate.  `consts`: the CONSTS builds, which return grad_consts besides (optional as
-// the map outputs are)
-int rfgr_maps_bwd(bool consts, int dtype, const void* Mck, const PulseOps& in, const void* grad_Mo, const void* grad_Mt,
-                  int64_t every, void* grad_Mi, void* grad_rf, void* grad_gr, void* grad_loc, void* grad_Bz, void* grad_b1,
-                  void* grad_consts, void* work, size_t work_bytes, int64_t N, int64_t nM, int64_t nT, void* stream)
+// The adjoints of K2b / K2bt, builds PLAIN, MAPS, CONSTS and MC: grad_Mo (mode 0) or grad_Mt (modes 1, 2), exactly one of
+// them; a grad_b1 needs a b1 map to differentiate.  The plain call is the MAPS call without per-spin outputs.  `traj`:
+// a `_traj_` entry point, whose `every` counts whether or not grad_Mt is given.  The multi-coil build adds its coil
+// count, cannot do without a b1 map and has a workspace of its own.
+int rfgr_bwd(AdjBuild b, bool traj, int dtype, const AdjointReq& r, const PulseOps& in, size_t work_bytes, void* stream)
 {
-    if (int e = check_common(dtype, N, nM, nT)) return e;
-    if (nT % SEG != 0 || (grad_Mt && every < 1) || (grad_Mo && grad_Mt) || (grad_b1 && !in.b1)) return MRPHY_EINVAL;
-    if (N * nM * nT == 0) return 0;
-    if (!Mck || !(grad_Mo || grad_Mt) || !work) return MRPHY_EINVAL;
-    if (int e = check_ops(in, true, false)) return e;
-    if (work_bytes < mrphy_blochsim_rfgr_bwd_workspace(dtype, N, nM, nT)) return MRPHY_ENOSPC;
-    hipStream_t st = (hipStream_t)stream;
-    if (consts)
-        MRPHY_DISPATCH(dtype, (run_rfgr_consts_bwd<T, CT>(Mck, in, grad_Mo, grad_Mt, every, grad_Mi, grad_rf, grad_gr,
-                                                          grad_loc, grad_Bz, grad_b1, grad_consts, work, N, nM, nT, st)));
-    MRPHY_DISPATCH(dtype, (run_rfgr_maps_bwd<T, CT>(Mck, in, grad_Mo, grad_Mt, every, grad_Mi, grad_rf, grad_gr, grad_loc,
-                                                    grad_Bz, grad_b1, work, N, nM, nT, st)));
-}
-
-int rfgr_mc_bwd(bool traj, int dtype, const void* Mck, const PulseOps& in, const void* grad_M, int64_t every,
-                void* grad_Mi, void* grad_rf, void* grad_gr, void* work, size_t work_bytes, int64_t N, int64_t nM,
-                int64_t nT, int64_t nC, void* stream)
-{
-    if (int e = check_common(dtype, N, nM, nT)) return e;
-    if (nT % SEG != 0 || (traj && every < 1) || nC < 1 || nC > K2B_MAXC) return MRPHY_EINVAL;
-    if (N * nM * nT == 0) return 0;
-    if (!Mck || !grad_M || !work) return MRPHY_EINVAL;
-    if (int e = check_ops(in, true, true)) return e;
-    if (work_bytes < mrphy_blochsim_rfgr_mc_bwd_workspace(dtype, N, nM, nT, nC)) return MRPHY_ENOSPC;
-    hipStream_t st = (hipStream_t)stream;
-    MRPHY_DISPATCH(dtype, (run_rfgr_mc_bwd<T, CT>(Mck, in, traj ? nullptr : grad_M, traj ? grad_M : nullptr, every,
-                                                  grad_Mi, grad_rf, grad_gr, work, N, nM, nT, nC, st)));
+    const bool mc = b == AdjBuild::MC;
+    if (int e = check_common(dtype, r.N, r.nM, r.nT)) return e;
+    if (r.nT % SEG != 0 || ((traj || r.gMt) && r.every < 1) || (r.gMo && r.gMt) || (r.gb1 && !in.b1) ||
+        (mc && (r.nC < 1 || r.nC > K2B_MAXC)))
+        return MRPHY_EINVAL;                                         // whole checkpoint segments only
+    if (r.N * r.nM * r.nT == 0) return 0;
+    if (!r.Mck || !(r.gMo || r.gMt) || !r.work) return MRPHY_EINVAL;
+    if (int e = check_ops(in, true, mc)) return e;
+    if (work_bytes < (mc ? mrphy_blochsim_rfgr_mc_bwd_workspace(dtype, r.N, r.nM, r.nT, r.nC)
+                         : mrphy_blochsim_rfgr_bwd_workspace(dtype, r.N, r.nM, r.nT)))
+        return MRPHY_ENOSPC;
+    return dispatch_adjoint(b, dtype, r, in, stream);
 }
 
 // The signal entry points and their `_mrx_` twins (a receive array: rx with a coil axis of nRx, never null) likewise; the
@@ -154,40 +150,22 @@ int signal_fwd(bool mrx, int dtype, const void* Mi, const PulseOps& in, const vo
 
 // `consts`: the CONSTS builds, which return grad_consts (optional) besides; rx may then be null for nRx == 1, the one-coil
 // entry point's (1, 0), and the smallest capacity 1, 2, 4, 8 that holds nRx runs
-int signal_bwd(bool mrx, bool consts, int dtype, const void* Mck, const PulseOps& in, const void* rx, int64_t nRx,
-               const void* grad_Mo, const void* grad_sig, int64_t every, void* grad_Mi, void* grad_rf, void* grad_gr,
-               void* grad_consts, void* work, size_t work_bytes, int64_t N, int64_t nM, int64_t nT, void* stream)
+int signal_bwd(bool mrx, bool consts, int dtype, const AdjointReq& r, const PulseOps& in, size_t work_bytes, void* stream)
 {
-    if (int e = check_common(dtype, N, nM, nT)) return e;
+    if (int e = check_common(dtype, r.N, r.nM, r.nT)) return e;
     // whole checkpoint segments only; at least one of the two cotangents
-    if (nT % SEG != 0 || every < 1 || N > 65535 || (!grad_Mo && !grad_sig)) return MRPHY_EINVAL;
-    if (nRx < 1 || nRx > sig_max_rx(tsize(dtype))) return MRPHY_EINVAL;
-    if (N * nM * nT == 0) return 0;
-    if (!Mck || (mrx && !rx && !(consts && nRx == 1)) || !work) return MRPHY_EINVAL;
+    if (r.nT % SEG != 0 || r.every < 1 || r.N > 65535 || (!r.gMo && !r.gsig)) return MRPHY_EINVAL;
+    if (r.nRx < 1 || r.nRx > sig_max_rx(tsize(dtype))) return MRPHY_EINVAL;
+    if (r.N * r.nM * r.nT == 0) return 0;
+    if (!r.Mck || (mrx && !r.rx && !(consts && r.nRx == 1)) || !r.work) return MRPHY_EINVAL;
     if (int e = check_ops(in, true, false)) return e;
-    if (work_bytes < mrphy_blochsim_rfgr_bwd_workspace(dtype, N, nM, nT)) return MRPHY_ENOSPC;
-    hipStream_t st = (hipStream_t)stream;
-    if (consts) {
-        // without grad_sig there is nothing of the signal to inject: the CONSTS build of K2b on grad_Mo
-        if (!grad_sig)
-            MRPHY_DISPATCH(dtype, (run_rfgr_consts_bwd<T, CT>(Mck, in, grad_Mo, nullptr, 0, grad_Mi, grad_rf, grad_gr, nullptr,
-                                                              nullptr, nullptr, grad_consts, work, N, nM, nT, st)));
-#define MRPHY_SIGNAL_CONSTS_BWD(R_)                                                                                    \
-    MRPHY_DISPATCH(dtype, (run_signal_consts_bwd<T, CT, R_>(Mck, in, grad_Mo, every, rx, nRx, grad_sig, grad_Mi, grad_rf, \
-                                                            grad_gr, grad_consts, work, N, nM, nT, st)))
-        if (nRx == 1) MRPHY_SIGNAL_CONSTS_BWD(1);
-        if (nRx <= 2) MRPHY_SIGNAL_CONSTS_BWD(2);
-        if (nRx <= 4) MRPHY_SIGNAL_CONSTS_BWD(4);
-        MRPHY_SIGNAL_CONSTS_BWD(8);
-#undef MRPHY_SIGNAL_CONSTS_BWD
-    }
-    // a receive array: the capacities 2 .. 8 are a unit of their own, which picks the smallest that holds nRx.  Without
-    // grad_sig there is nothing of the signal to inject: K2b on grad_Mo
-    if (grad_sig && nRx > 1)
-        MRPHY_DISPATCH(dtype, (run_rfgr_mrx_bwd<T, CT>(Mck, in, grad_Mo, every, rx, nRx, grad_sig, grad_Mi, grad_rf,
-                                                       grad_gr, work, N, nM, nT, st)));
-    MRPHY_DISPATCH(dtype, (run_rfgr_bwd<T, CT>(Mck, in, grad_Mo, nullptr, every, rx, grad_sig, grad_Mi, grad_rf, grad_gr,
-                                               work, N, nM, nT, st)));
+    if (work_bytes < mrphy_blochsim_rfgr_bwd_workspace(dtype, r.N, r.nM, r.nT)) return MRPHY_ENOSPC;
+    // without grad_sig there is nothing of the signal to inject: K2b on grad_Mo, its CONSTS build for grad_consts.  A
+    // receive array: the capacities 2 .. 8 are a unit of their own, which picks the smallest that holds nRx
+    const AdjBuild b = !r.gsig ? (consts ? AdjBuild::CONSTS : AdjBuild::PLAIN)
+                       : consts ? sig_consts_build(r.nRx == 1 ? 1 : r.nRx <= 2 ? 2 : r.nRx <= 4 ? 4 : 8)
+                                : (r.nRx > 1 ? AdjBuild::MRX : AdjBuild::PLAIN);
+    return dispatch_adjoint(b, dtype, r, in, stream);
 }
 }  // namespace
 
@@ -389,8 +367,9 @@ int mrphy_blochsim_rfgr_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PARAMS, 
                             void* grad_rf, void* grad_gr, void* work, size_t work_bytes, int64_t N, int64_t nM,
                             int64_t nT, void* stream)
 {
-    return rfgr_bwd(false, dtype, Mck, MRPHY_PULSE_OPS, grad_Mo, 0, grad_Mi, grad_rf, grad_gr, work, work_bytes, N, nM,
-                    nT, stream);
+    MRPHY_ADJOINT_REQ(1);
+    r.gMo = grad_Mo;
+    return rfgr_bwd(AdjBuild::PLAIN, false, dtype, r, MRPHY_PULSE_OPS, work_bytes, stream);
 }
 
 int64_t mrphy_blochsim_rfgr_mc_max_coils(void) { return K2B_MAXC; }
@@ -405,8 +384,9 @@ int mrphy_blochsim_rfgr_mc_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PARAM
                                void* grad_rf, void* grad_gr, void* work, size_t work_bytes, int64_t N, int64_t nM,
                                int64_t nT, int64_t nC, void* stream)
 {
-    return rfgr_mc_bwd(false, dtype, Mck, MRPHY_PULSE_OPS, grad_Mo, 0, grad_Mi, grad_rf, grad_gr, work, work_bytes, N,
-                       nM, nT, nC, stream);
+    MRPHY_ADJOINT_REQ(nC);
+    r.gMo = grad_Mo;
+    return rfgr_bwd(AdjBuild::MC, false, dtype, r, MRPHY_PULSE_OPS, work_bytes, stream);
 }
 
 int mrphy_blochsim_rfgr_traj_fwd(int dtype, const void* Mi, MRPHY_PULSE_OPS_PARAMS, void* Mo, void* Mck,
@@ -420,8 +400,9 @@ int mrphy_blochsim_rfgr_traj_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PAR
                                  void* grad_Mi, void* grad_rf, void* grad_gr, void* work, size_t work_bytes, int64_t N,
                                  int64_t nM, int64_t nT, void* stream)
 {
-    return rfgr_bwd(true, dtype, Mck, MRPHY_PULSE_OPS, grad_Mt, every, grad_Mi, grad_rf, grad_gr, work, work_bytes, N,
-                    nM, nT, stream);
+    MRPHY_ADJOINT_REQ(1);
+    r.gMt = grad_Mt; r.every = every;
+    return rfgr_bwd(AdjBuild::PLAIN, true, dtype, r, MRPHY_PULSE_OPS, work_bytes, stream);
 }
 
 int mrphy_blochsim_rfgr_maps_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PARAMS, const void* grad_Mo,
@@ -429,8 +410,9 @@ int mrphy_blochsim_rfgr_maps_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PAR
                                  void* grad_loc, void* grad_Bz, void* grad_b1, void* work, size_t work_bytes, int64_t N,
                                  int64_t nM, int64_t nT, void* stream)
 {
-    return rfgr_maps_bwd(false, dtype, Mck, MRPHY_PULSE_OPS, grad_Mo, grad_Mt, every, grad_Mi, grad_rf, grad_gr, grad_loc,
-                         grad_Bz, grad_b1, nullptr, work, work_bytes, N, nM, nT, stream);
+    MRPHY_ADJOINT_REQ(1);
+    r.gMo = grad_Mo; r.gMt = grad_Mt; r.every = every; r.gloc = grad_loc; r.gBz = grad_Bz; r.gb1 = grad_b1;
+    return rfgr_bwd(AdjBuild::MAPS, false, dtype, r, MRPHY_PULSE_OPS, work_bytes, stream);
 }
 
 int mrphy_blochsim_rfgr_consts_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PARAMS, const void* grad_Mo,
@@ -438,16 +420,19 @@ int mrphy_blochsim_rfgr_consts_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_P
                                    void* grad_loc, void* grad_Bz, void* grad_b1, void* grad_consts, void* work,
                                    size_t work_bytes, int64_t N, int64_t nM, int64_t nT, void* stream)
 {
-    return rfgr_maps_bwd(true, dtype, Mck, MRPHY_PULSE_OPS, grad_Mo, grad_Mt, every, grad_Mi, grad_rf, grad_gr, grad_loc,
-                         grad_Bz, grad_b1, grad_consts, work, work_bytes, N, nM, nT, stream);
+    MRPHY_ADJOINT_REQ(1);
+    r.gMo = grad_Mo; r.gMt = grad_Mt; r.every = every; r.gloc = grad_loc; r.gBz = grad_Bz; r.gb1 = grad_b1;
+    r.gC = grad_consts;
+    return rfgr_bwd(AdjBuild::CONSTS, false, dtype, r, MRPHY_PULSE_OPS, work_bytes, stream);
 }
 
 int mrphy_blochsim_rfgr_mc_traj_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PARAMS, const void* grad_Mt,
                                     int64_t every, void* grad_Mi, void* grad_rf, void* grad_gr, void* work,
                                     size_t work_bytes, int64_t N, int64_t nM, int64_t nT, int64_t nC, void* stream)
 {
-    return rfgr_mc_bwd(true, dtype, Mck, MRPHY_PULSE_OPS, grad_Mt, every, grad_Mi, grad_rf, grad_gr, work, work_bytes,
-                       N, nM, nT, nC, stream);
+    MRPHY_ADJOINT_REQ(nC);
+    r.gMt = grad_Mt; r.every = every;
+    return rfgr_bwd(AdjBuild::MC, true, dtype, r, MRPHY_PULSE_OPS, work_bytes, stream);
 }
 
 size_t mrphy_signal_rfgr_fwd_workspace(int dtype, int64_t N, int64_t nM, int64_t nT, int64_t every)
@@ -468,8 +453,9 @@ int mrphy_signal_rfgr_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PARAMS, co
                           const void* grad_sig, int64_t every, void* grad_Mi, void* grad_rf, void* grad_gr, void* work,
                           size_t work_bytes, int64_t N, int64_t nM, int64_t nT, void* stream)
 {
-    return signal_bwd(false, false, dtype, Mck, MRPHY_PULSE_OPS, rx, 1, grad_Mo, grad_sig, every, grad_Mi, grad_rf,
-                      grad_gr, nullptr, work, work_bytes, N, nM, nT, stream);
+    MRPHY_ADJOINT_REQ(1);
+    r.gMo = grad_Mo; r.gsig = grad_sig; r.every = every; r.rx = rx; r.nRx = 1;
+    return signal_bwd(false, false, dtype, r, MRPHY_PULSE_OPS, work_bytes, stream);
 }
 
 int mrphy_signal_rfgr_max_rx(int dtype)
@@ -497,8 +483,9 @@ int mrphy_signal_rfgr_mrx_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PARAMS
                               void* grad_gr, void* work, size_t work_bytes, int64_t N, int64_t nM, int64_t nT,
                               void* stream)
 {
-    return signal_bwd(true, false, dtype, Mck, MRPHY_PULSE_OPS, rx, nRx, grad_Mo, grad_sig, every, grad_Mi, grad_rf,
-                      grad_gr, nullptr, work, work_bytes, N, nM, nT, stream);
+    MRPHY_ADJOINT_REQ(1);
+    r.gMo = grad_Mo; r.gsig = grad_sig; r.every = every; r.rx = rx; r.nRx = nRx;
+    return signal_bwd(true, false, dtype, r, MRPHY_PULSE_OPS, work_bytes, stream);
 }
 
 int mrphy_signal_rfgr_consts_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PARAMS, const void* rx, int64_t nRx,
@@ -506,8 +493,9 @@ int mrphy_signal_rfgr_consts_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PAR
                                  void* grad_gr, void* grad_consts, void* work, size_t work_bytes, int64_t N, int64_t nM,
                                  int64_t nT, void* stream)
 {
-    return signal_bwd(true, true, dtype, Mck, MRPHY_PULSE_OPS, rx, nRx, grad_Mo, grad_sig, every, grad_Mi, grad_rf,
-                      grad_gr, grad_consts, work, work_bytes, N, nM, nT, stream);
+    MRPHY_ADJOINT_REQ(1);
+    r.gMo = grad_Mo; r.gsig = grad_sig; r.every = every; r.rx = rx; r.nRx = nRx; r.gC = grad_consts;
+    return signal_bwd(true, true, dtype, r, MRPHY_PULSE_OPS, work_bytes, stream);
 }
 
 int mrphy_beff2ab(int dtype, const void* Beff,

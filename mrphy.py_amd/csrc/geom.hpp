@@ -50,6 +50,21 @@ static_assert(sizeof(PulseOps) == 176 && sizeof(PulseOpsT<float>) == 176 && size
 template <typename T>
 inline PulseOpsT<T> typed(const PulseOps& o) { return __builtin_bit_cast(PulseOpsT<T>, o); }
 
+// Everything an adjoint call of the fused family (K2b, its trajectory, signal, MAPS, CONSTS and multi-coil builds)
+// carries besides PulseOps.  Each adjoint entry point of abi.hip packs it once; the validators, the launchers and the
+// kernel argument structs take it from there on.  A null pointer is "not given" (a cotangent) or "not wanted" (an output).
+struct AdjointReq {
+    const void* Mck;                  // (nT/SEG, N*nM, 3): the forward's checkpoints
+    const void* gMo;                  // cotangents: grad_Mo (N, nM, 3) ...
+    const void* gMt; int64_t every;   // ... or grad_Mt (nRec, N, nM, 3), a record every `every` steps;
+    const void* rx; int64_t nRx;      // the signal's receive map (N, nM, 2, nRx) with
+    const void* gsig;                 // grad_sig (N, 2, nRec, nRx)
+    void *gMi, *grf, *ggr;            // outputs: (N, nM, 3), (N, 2, nT, nC), (N, 3, nT)
+    void *gloc, *gBz, *gb1, *gC;      // per-spin outputs: (N, nM, 3), (N, nM), (N, nM, 2), (N, nM, 4)
+    void* work;
+    int64_t N, nM, nT, nC;
+};
+
 inline int64_t hist_tiles(int64_t N, int64_t nM) { return (N * nM + WAVE - 1) / WAVE; }
 inline int64_t hist_elems(int64_t N, int64_t nM, int64_t nT)
 {

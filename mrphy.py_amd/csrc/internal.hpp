@@ -11,6 +11,7 @@
 namespace mrphy_i {
 using mrphy::Bc;
 using mrphy::PulseOps;
+using mrphy::AdjointReq;
 using mrphy::HistParts;
 
 template <typename T, typename CT>
@@ -45,49 +46,34 @@ template <typename T, typename CT>
 int run_rfgr_fwd1(const void* Mi, PulseOps in, void* Mo, void* Mck, int64_t ck_every, void* Mt, int64_t every,
                   int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st);
 
-template <typename T, typename CT>
-int run_rfgr_bwd(const void* Mck, PulseOps in, const void* gMo, const void* gMt, int64_t every, const void* rx,
-                 const void* gsig, void* gMi, void* grf, void* ggr, void* work, int64_t N, int64_t nM, int64_t nT,
-                 hipStream_t st);
-
-// the MAPS builds of K2b / K2bt (tu_fused_maps_bwd.hip): run_rfgr_bwd's plain and trajectory modes, which also return
-// the gradients w.r.t. the spin-side operands -- gloc (N, nM, 3), gBz (N, nM), gb1 (N, nM, 2), each may be null
-template <typename T, typename CT>
-int run_rfgr_maps_bwd(const void* Mck, PulseOps in, const void* gMo, const void* gMt, int64_t every, void* gMi, void* grf,
-                      void* ggr, void* gloc, void* gBz, void* gb1, void* work, int64_t N, int64_t nM, int64_t nT,
-                      hipStream_t st);
-
-// the CONSTS builds of K2b / K2bt (tu_fused_consts_bwd.hip): run_rfgr_maps_bwd, which also returns the gradients w.r.t.
-// the step constants per spin, gC (N, nM, 4) = [dL/dg, dL/dE1, dL/dE2, dL/dE1m1]; may be null like the map outputs
-template <typename T, typename CT>
-int run_rfgr_consts_bwd(const void* Mck, PulseOps in, const void* gMo, const void* gMt, int64_t every, void* gMi,
-                        void* grf, void* ggr, void* gloc, void* gBz, void* gb1, void* gC, void* work, int64_t N,
-                        int64_t nM, int64_t nT, hipStream_t st);
-
-// the CONSTS builds of K2bs (tu_signal_consts1 / 2 / 4 / 8_bwd.hip, one unit per coil capacity R >= nRx): the signal
-// adjoint with a non-null gsig, which also returns gC as above; rx may be null at R = 1 only
-template <typename T, typename CT, int R>
-int run_signal_consts_bwd(const void* Mck, PulseOps in, const void* gMo, int64_t every, const void* rx, int64_t nRx,
-                          const void* gsig, void* gMi, void* grf, void* ggr, void* gC, void* work, int64_t N, int64_t nM,
-                          int64_t nT, hipStream_t st);
-
 // K2s / K2bs: the received signal of the fused simulation (one transmit coil) for nRx <= sig_max_rx receive coils in one
 // launch, rx (N, nM, 2, nRx), sig / gsig (N, 2, nRec, nRx).  The forward has one unit per coil capacity R >= nRx
 // (tu_signal.hip: 1, where rx may be null = (1, 0); tu_signal_mrx2 / 4 / 8.hip).  Its adjoint takes a non-null
-// gsig (the cotangent of the samples) and the receive map rx, and gMo may then be null: run_rfgr_bwd for one coil,
-// run_rfgr_mrx_bwd (tu_fused_mrx_bwd.hip: the capacities 2 .. 8, the smallest that holds nRx) for more
+// gsig (the cotangent of the samples) and the receive map rx, and gMo may then be null: the builds PLAIN for one coil
+// and MRX for more of run_fused_bwd below
 template <typename T, typename CT, int R>
 int run_signal_fwd(const void* Mi, PulseOps in, const void* rx, int64_t nRx, void* Mo, void* Mck, int64_t ck_every,
                    void* sig, int64_t every, void* work, int64_t N, int64_t nM, int64_t nT, hipStream_t st);
 
-template <typename T, typename CT>
-int run_rfgr_mrx_bwd(const void* Mck, PulseOps in, const void* gMo, int64_t every, const void* rx, int64_t nRx,
-                     const void* gsig, void* gMi, void* grf, void* ggr, void* work, int64_t N, int64_t nM, int64_t nT,
-                     hipStream_t st);
-
-template <typename T, typename CT>
-int run_rfgr_mc_bwd(const void* Mck, PulseOps in, const void* gMo, const void* gMt, int64_t every, void* gMi, void* grf,
-                    void* ggr, void* work, int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st);
+// The adjoints of the fused family: ONE launcher declaration.  A build is the set of kernels one translation unit
+// compiles; each tu_*_bwd unit defines run_fused_bwd for its own build and instantiates it for its dtype codes.  The call
+// travels as the request (geom.hpp: AdjointReq) next to the operands; abi.hip has validated both and chosen the build.
+enum class AdjBuild {
+    PLAIN,      // tu_fused_bwd.hip: K2b, K2bt (a non-null gMt), and K2bs at a capacity of 1 receive coil (a non-null gsig)
+    MRX,        // tu_fused_mrx_bwd.hip: K2bs at the smallest capacity 2, 4, 8 that holds nRx; gsig is not null
+    MAPS,       // tu_fused_maps_bwd.hip: K2b / K2bt that also return gloc, gBz, gb1, each of which may be null
+    CONSTS,     // tu_fused_consts_bwd.hip: the MAPS builds that also return gC = [dL/dg, dL/dE1, dL/dE2, dL/dE1m1] per spin
+    SIG_CONSTS1, SIG_CONSTS2, SIG_CONSTS4, SIG_CONSTS8,     // tu_signal_consts1 / 2 / 4 / 8_bwd.hip, one unit per capacity
+                // R >= nRx: K2bs that also returns gC; gsig is not null, rx may be null at R = 1 only
+    MC,         // tu_fused_mc_bwd.hip: K2b / K2bt for nC <= K2B_MAXC transmit coils with their b1 map
+};
+constexpr AdjBuild sig_consts_build(int R)
+{
+    return R == 1 ? AdjBuild::SIG_CONSTS1 : R == 2 ? AdjBuild::SIG_CONSTS2 : R == 4 ? AdjBuild::SIG_CONSTS4
+                                                                                      : AdjBuild::SIG_CONSTS8;
+}
+template <AdjBuild B, typename T, typename CT>
+int run_fused_bwd(const AdjointReq& r, PulseOps in, hipStream_t st);
 
 template <typename T, typename CT>
 int run_beff2ab(const void* Beff, Bc g, Bc E1, Bc E2, const void* E1m1, void* A, void* B, void* hist,

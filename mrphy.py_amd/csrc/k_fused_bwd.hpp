@@ -260,134 +260,76 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_bwd(FusedBwdKArgsT<T, INJ, 
     }
 }
 
-// Host: the launcher of both units that compile this kernel.  MRX picks the unit's instantiations: false (tu_fused_bwd.hip)
-// the plain and the trajectory modes and the signal mode at capacity 1, true (tu_fused_mrx_bwd.hip) the signal mode at
-// the smallest capacity 2, 4, 8 that holds nRx (abi.hip has refused nRx > sig_max_rx = 8).  gsig (the cotangent of the
-// signal's samples, with the receive map rx) selects the signal mode, which may have no gMo; its records are counted
-// as the trajectory's.  Otherwise a null gMt runs the plain kernel.
-template <typename T, typename CT, bool MRX>
-int launch_rfgr_bwd(const void* Mck, const PulseOps& in, const void* gMo, const void* gMt, int64_t every, const void* rx,
-                    int64_t nRx, const void* gsig, void* gMi, void* grf, void* ggr, void* work, int64_t N, int64_t nM,
-                    int64_t nT, hipStream_t st)
+// Host: what a build's kernels take after the common arguments (fused_bwd_args), from the request.  The signal's records
+// are counted as the trajectory's; a request without gsig leaves nRec to the plain and trajectory modes.
+template <typename T>
+void k2b_extra_args(FusedBwdSigArgs<T>& a, const AdjointReq& r)
 {
-    dim3 grid;
-    int e;
-    if (!fused_grid(N * nM * nT, k2b_waves(nM), N, grid, e)) return e;
-    FusedBwdSigArgs<T> a;
-    static_cast<FusedBwdTrajArgs<T>&>(a) = fused_bwd_args<T>(Mck, in, gMo, gMt, every, gMi, work, N, nM, nT,
-                                                             grid.x);
-    a.rx = (const T*)rx; a.gsig = (const T*)gsig; a.nRx = nRx;
-    if (gsig) a.nRec = sig_records(nT, every);
-#define MRPHY_K2B(RX_, HB_, INJ_)                                                               \
-    hipLaunchKernelGGL((k_bloch_rfgr_bwd<T, CT, RX_, HB_, INJ_>), grid, dim3(WAVE), 0, st, \
-                       (static_cast<const FusedBwdArgsT<T, INJ_>&>(a)))
-#define MRPHY_K2BT(RX_, HB_)                                                                    \
-    do {                                                                                        \
-        if constexpr (MRX) {                                                                    \
-            if (nRx <= 2) MRPHY_K2B(RX_, HB_, 4);                                               \
-            else if (nRx <= 4) MRPHY_K2B(RX_, HB_, 5);                                          \
-            else MRPHY_K2B(RX_, HB_, 6);                                                        \
-        }                                                                                       \
-        else if (gsig) MRPHY_K2B(RX_, HB_, 3);                                                  \
-        else if (!gMt) MRPHY_K2B(RX_, HB_, 0);                                                  \
-        else if (every < SEG) MRPHY_K2B(RX_, HB_, 1);                                           \
-        else MRPHY_K2B(RX_, HB_, 2);                                                            \
-    } while (0)
-    if (in.b1) { if (in.E1.p) MRPHY_K2BT(true, true);  else MRPHY_K2BT(false, true); }
-    else       { if (in.E1.p) MRPHY_K2BT(true, false); else MRPHY_K2BT(false, false); }   // no b1 map: Bxy = rf
-#undef MRPHY_K2BT
+    a.rx = (const T*)r.rx; a.gsig = (const T*)r.gsig; a.nRx = r.nRx;
+    if (r.gsig) a.nRec = sig_records(r.nT, r.every);
+}
+template <typename T>
+void k2b_extra_args(FusedBwdMapsArgs<T>& a, const AdjointReq& r)
+{
+    a.gloc = (T*)r.gloc; a.gBz = (T*)r.gBz; a.gb1 = (T*)r.gb1;
+}
+template <typename T>
+void k2b_extra_args(FusedBwdConstsArgs<T>& a, const AdjointReq& r)
+{
+    k2b_extra_args(static_cast<FusedBwdMapsArgs<T>&>(a), r); a.gC = (T*)r.gC;
+}
+template <typename T>
+void k2b_extra_args(FusedBwdSigConstsArgs<T>& a, const AdjointReq& r)
+{
+    k2b_extra_args(static_cast<FusedBwdSigArgs<T>&>(a), r); a.gC = (T*)r.gC;
+}
+
+// Host: the launcher of every unit that compiles this kernel.  The build B (internal.hpp: AdjBuild) says which kernels the
+// unit instantiates: which of MAPS / CONSTS, and which modes INJ the request chooses among --
+//   PLAIN         0 .. 2 as below, and 3 (the signal at a capacity of 1 receive coil) for a non-null gsig;
+//   MRX           4, 5, 6: the smallest capacity 2, 4, 8 that holds nRx (abi.hip has refused nRx > sig_max_rx = 8);
+//   MAPS, CONSTS  0 without gMt, else 1 for every < SEG and 2 otherwise (abi.hip has refused a gb1 without a b1 map);
+//   SIG_CONSTS<R> the one mode of capacity R; 1 <= nRx <= R, a null rx at R = 1 only.
+// Everything else is the same for all of them: the grid, the workspace and the second pass (fused_bwd_launch), the
+// common arguments, RELAX x HB1 from the operands.
+template <mrphy_i::AdjBuild B, typename T, typename CT>
+int launch_k2b(const AdjointReq& r, const PulseOps& in, hipStream_t st)
+{
+    using mrphy_i::AdjBuild;
+    constexpr int RC = B == AdjBuild::SIG_CONSTS1 ? 1 : B == AdjBuild::SIG_CONSTS2 ? 2 : B == AdjBuild::SIG_CONSTS4 ? 4 :
+                       B == AdjBuild::SIG_CONSTS8 ? 8 : 0;
+    constexpr bool MAPS = B == AdjBuild::MAPS, CONSTS = B == AdjBuild::CONSTS || RC > 0;
+    constexpr bool SIGNAL = B == AdjBuild::PLAIN || B == AdjBuild::MRX || RC > 0;
+    static_assert(SIGNAL || MAPS || CONSTS, "a build of the one-coil kernel");
+    return fused_bwd_launch<T>(r, k2b_waves(r.nM), st, [&](dim3 grid) {
+        // the widest argument struct of the build's kernels; each takes the part it was compiled for
+        FusedBwdKArgsT<T, SIGNAL ? 3 : 0, MAPS, CONSTS> a;
+        static_cast<FusedBwdTrajArgs<T>&>(a) = fused_bwd_args<T>(r, in, grid.x);
+        k2b_extra_args(a, r);
+        auto start = [&](auto inj) {
+            constexpr int INJ = decltype(inj)::value;
+            const FusedBwdKArgsT<T, INJ, MAPS, CONSTS>& ka = a;
+#define MRPHY_K2B(RX_, HB_) \
+    hipLaunchKernelGGL((k_bloch_rfgr_bwd<T, CT, RX_, HB_, INJ, MAPS, CONSTS>), grid, dim3(WAVE), 0, st, ka)
+            if (in.b1) { if (in.E1.p) MRPHY_K2B(true, true);  else MRPHY_K2B(false, true); }
+            else       { if (in.E1.p) MRPHY_K2B(true, false); else MRPHY_K2B(false, false); }   // no b1 map: Bxy = rf
 #undef MRPHY_K2B
-    e = launch_status();
-    if (e || !(grf || ggr)) return e;
-    return launch_p2<T>(work, ggr, 3, grf, 1, N, nT, a.P, st);
-}
-
-// Host: the launcher of the MAPS builds (tu_fused_maps_bwd.hip): modes 0 .. 2 chosen as launch_rfgr_bwd chooses them,
-// the same grid, workspace and second pass; gloc (N, nM, 3), gBz (N, nM), gb1 (N, nM, 2) each optional (abi.hip has
-// refused a gb1 without a b1 map).
-template <typename T, typename CT>
-int launch_rfgr_maps_bwd(const void* Mck, const PulseOps& in, const void* gMo, const void* gMt, int64_t every, void* gMi,
-                         void* grf, void* ggr, void* gloc, void* gBz, void* gb1, void* work, int64_t N, int64_t nM,
-                         int64_t nT, hipStream_t st)
-{
-    dim3 grid;
-    int e;
-    if (!fused_grid(N * nM * nT, k2b_waves(nM), N, grid, e)) return e;
-    FusedBwdMapsArgs<T> a;
-    static_cast<FusedBwdTrajArgs<T>&>(a) = fused_bwd_args<T>(Mck, in, gMo, gMt, every, gMi, work, N, nM, nT,
-                                                             grid.x);
-    a.gloc = (T*)gloc; a.gBz = (T*)gBz; a.gb1 = (T*)gb1;
-#define MRPHY_K2BM(RX_, HB_, INJ_) \
-    hipLaunchKernelGGL((k_bloch_rfgr_bwd<T, CT, RX_, HB_, INJ_, true>), grid, dim3(WAVE), 0, st, a)
-#define MRPHY_K2BMT(RX_, HB_)                                                                   \
-    do {                                                                                        \
-        if (!gMt) MRPHY_K2BM(RX_, HB_, 0);                                                      \
-        else if (every < SEG) MRPHY_K2BM(RX_, HB_, 1);                                          \
-        else MRPHY_K2BM(RX_, HB_, 2);                                                           \
-    } while (0)
-    if (in.b1) { if (in.E1.p) MRPHY_K2BMT(true, true);  else MRPHY_K2BMT(false, true); }
-    else       { if (in.E1.p) MRPHY_K2BMT(true, false); else MRPHY_K2BMT(false, false); }
-#undef MRPHY_K2BMT
-#undef MRPHY_K2BM
-    e = launch_status();
-    if (e || !(grf || ggr)) return e;
-    return launch_p2<T>(work, ggr, 3, grf, 1, N, nT, a.P, st);
-}
-
-// Host: the launcher of the CONSTS builds of modes 0 .. 2 (tu_fused_consts_bwd.hip): launch_rfgr_maps_bwd with gC
-// (N, nM, 4) besides, optional as the map outputs are.
-template <typename T, typename CT>
-int launch_rfgr_consts_bwd(const void* Mck, const PulseOps& in, const void* gMo, const void* gMt, int64_t every, void* gMi,
-                           void* grf, void* ggr, void* gloc, void* gBz, void* gb1, void* gC, void* work, int64_t N,
-                           int64_t nM, int64_t nT, hipStream_t st)
-{
-    dim3 grid;
-    int e;
-    if (!fused_grid(N * nM * nT, k2b_waves(nM), N, grid, e)) return e;
-    FusedBwdConstsArgs<T> a;
-    static_cast<FusedBwdTrajArgs<T>&>(a) = fused_bwd_args<T>(Mck, in, gMo, gMt, every, gMi, work, N, nM, nT,
-                                                             grid.x);
-    a.gloc = (T*)gloc; a.gBz = (T*)gBz; a.gb1 = (T*)gb1; a.gC = (T*)gC;
-#define MRPHY_K2BC(RX_, HB_, INJ_) \
-    hipLaunchKernelGGL((k_bloch_rfgr_bwd<T, CT, RX_, HB_, INJ_, false, true>), grid, dim3(WAVE), 0, st, a)
-#define MRPHY_K2BCT(RX_, HB_)                                                                   \
-    do {                                                                                        \
-        if (!gMt) MRPHY_K2BC(RX_, HB_, 0);                                                      \
-        else if (every < SEG) MRPHY_K2BC(RX_, HB_, 1);                                          \
-        else MRPHY_K2BC(RX_, HB_, 2);                                                           \
-    } while (0)
-    if (in.b1) { if (in.E1.p) MRPHY_K2BCT(true, true);  else MRPHY_K2BCT(false, true); }
-    else       { if (in.E1.p) MRPHY_K2BCT(true, false); else MRPHY_K2BCT(false, false); }
-#undef MRPHY_K2BCT
-#undef MRPHY_K2BC
-    e = launch_status();
-    if (e || !(grf || ggr)) return e;
-    return launch_p2<T>(work, ggr, 3, grf, 1, N, nT, a.P, st);
-}
-
-// Host: the launcher of the CONSTS builds of the signal mode at the capacity R = 1, 2, 4, 8 (tu_signal_consts*_bwd.hip,
-// one unit each): launch_rfgr_bwd's signal mode with gC (N, nM, 4) besides; 1 <= nRx <= R, a null rx at R = 1 only.
-template <typename T, typename CT, int R>
-int launch_signal_consts_bwd(const void* Mck, const PulseOps& in, const void* gMo, int64_t every, const void* rx,
-                             int64_t nRx, const void* gsig, void* gMi, void* grf, void* ggr, void* gC, void* work,
-                             int64_t N, int64_t nM, int64_t nT, hipStream_t st)
-{
-    constexpr int INJ = R == 1 ? 3 : R == 2 ? 4 : R == 4 ? 5 : 6;
-    static_assert(inj_rx_cap(INJ) == R, "capacities 1, 2, 4, 8");
-    dim3 grid;
-    int e;
-    if (!fused_grid(N * nM * nT, k2b_waves(nM), N, grid, e)) return e;
-    FusedBwdSigConstsArgs<T> a;
-    static_cast<FusedBwdTrajArgs<T>&>(a) = fused_bwd_args<T>(Mck, in, gMo, nullptr, every, gMi, work, N, nM, nT,
-                                                             grid.x);
-    a.rx = (const T*)rx; a.gsig = (const T*)gsig; a.nRx = nRx; a.gC = (T*)gC;
-    a.nRec = sig_records(nT, every);
-#define MRPHY_K2BSC(RX_, HB_) \
-    hipLaunchKernelGGL((k_bloch_rfgr_bwd<T, CT, RX_, HB_, INJ, false, true>), grid, dim3(WAVE), 0, st, a)
-    if (in.b1) { if (in.E1.p) MRPHY_K2BSC(true, true);  else MRPHY_K2BSC(false, true); }
-    else       { if (in.E1.p) MRPHY_K2BSC(true, false); else MRPHY_K2BSC(false, false); }
-#undef MRPHY_K2BSC
-    e = launch_status();
-    if (e || !(grf || ggr)) return e;
-    return launch_p2<T>(work, ggr, 3, grf, 1, N, nT, a.P, st);
+        };
+        using std::integral_constant;
+        if constexpr (RC > 0) {
+            constexpr int INJ = RC == 1 ? 3 : RC == 2 ? 4 : RC == 4 ? 5 : 6;
+            static_assert(inj_rx_cap(INJ) == RC, "capacities 1, 2, 4, 8");
+            start(integral_constant<int, INJ>{});
+        } else if constexpr (B == AdjBuild::MRX) {
+            if (r.nRx <= 2) start(integral_constant<int, 4>{});
+            else if (r.nRx <= 4) start(integral_constant<int, 5>{});
+            else start(integral_constant<int, 6>{});
+        } else {
+            if constexpr (B == AdjBuild::PLAIN)
+                if (r.gsig) return start(integral_constant<int, 3>{});
+            if (!r.gMt) start(integral_constant<int, 0>{});
+            else if (r.every < SEG) start(integral_constant<int, 1>{});
+            else start(integral_constant<int, 2>{});
+        }
+    });
 }

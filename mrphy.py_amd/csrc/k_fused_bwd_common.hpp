@@ -122,17 +122,31 @@ static_assert(fused_bwd_maps_args_layout<float> && fused_bwd_maps_args_layout<do
 static_assert(fused_bwd_consts_args_layout<float> && fused_bwd_consts_args_layout<double>,
               "the CONSTS builds' kernel arguments moved");
 
-// the arguments of K2b / K2bt (host side, shared by tu_fused_bwd.hip and tu_fused_mc_bwd.hip): a null gMt selects the
-// plain kernel (INJ == 0), which takes the FusedBwdArgs part; otherwise gMt is the cotangent the kernel reads
+// Host: the arguments every fused adjoint takes, from the request: a null gMt selects the plain kernel (INJ == 0), which
+// takes the FusedBwdArgs part; otherwise gMt is the cotangent the kernel reads.  P: the grid's persistent waves
 template <typename T>
-FusedBwdTrajArgs<T> fused_bwd_args(const void* Mck, const PulseOps& in, const void* gMo, const void* gMt,
-                                   int64_t every, void* gMi, void* work, int64_t N, int64_t nM, int64_t nT, int64_t P)
+FusedBwdTrajArgs<T> fused_bwd_args(const AdjointReq& r, const PulseOps& in, int64_t P)
 {
     FusedBwdTrajArgs<T> a;
-    a.Mck = (const T*)Mck; a.in = typed<T>(in); a.gMo = (const T*)(gMt ? gMt : gMo); a.gMi = (T*)gMi;
-    a.work = (T*)work; a.N = N; a.nM = nM; a.nT = nT; a.P = P;
-    a.every = every; a.nRec = gMt ? (nT + every - 1) / every : 0;
+    a.Mck = (const T*)r.Mck; a.in = typed<T>(in); a.gMo = (const T*)(r.gMt ? r.gMt : r.gMo); a.gMi = (T*)r.gMi;
+    a.work = (T*)r.work; a.N = r.N; a.nM = r.nM; a.nT = r.nT; a.P = P;
+    a.every = r.every; a.nRec = r.gMt ? (r.nT + r.every - 1) / r.every : 0;
     return a;
+}
+
+// Host: the frame of every fused adjoint launch.  `waves` persistent one-wave blocks per batch entry; `kernel(grid)`
+// starts the caller's choice among its builds on that grid; then, if a pulse gradient is wanted, the second pass
+// sums the workspace rows of the grid's waves into ggr and the nC coils of grf.
+template <typename T, typename K>
+int fused_bwd_launch(const AdjointReq& r, int64_t waves, hipStream_t st, K&& kernel)
+{
+    dim3 grid;
+    int e;
+    if (!fused_grid(r.N * r.nM * r.nT, waves, r.N, grid, e)) return e;
+    kernel(grid);
+    e = launch_status();
+    if (e || !(r.grf || r.ggr)) return e;
+    return launch_p2<T>(r.work, r.ggr, 3, r.grf, r.nC, r.N, r.nT, grid.x, st);
 }
 
 template <bool RELAX, typename T, typename CT>

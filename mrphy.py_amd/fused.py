@@ -32,7 +32,7 @@ magnetisation summed over the spins at the trajectory's record steps (K2s, and t
 per-spin records in memory; the coils of a receive array share one simulation per launch.
 """
 from math import pi as π, prod  # noqa: F401
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 from torch import Tensor
@@ -60,51 +60,15 @@ def _forward_prep(lib, p, γ2πdt, E1, E2, E1_1, dtype, device, need):
     return code, (g, e1, e2, e1m1), consts, Mck, ckpt
 
 
-def _backward_prep(lib, p, code, needs, dtype, device):
-    r"""The gradient-output side the two adjoints share: ``(gMi, g_rf, g_gr)`` -- ``None`` where ``needs`` says so --
-    their pointers, and the workspace of the adjoint for ``p.nC`` coils."""
-    need_Mi, need_rf, need_gr = needs
-    gMi = torch.empty((p.N,) + p.Nd + (3,), dtype=dtype, device=device) if need_Mi else None
-    g_rf = torch.empty((p.N, 2, p.nT, p.nC), dtype=dtype, device=device) if need_rf else None
-    g_gr = torch.empty((p.N, 3, p.nT), dtype=dtype, device=device) if need_gr else None
-    if p.nC == 1:
-        nbytes = int(lib.mrphy_blochsim_rfgr_bwd_workspace(code, p.N, p.nM, p.nT))
-    else:                                       # parallel transmit: per-coil sums in the kernel
-        nbytes = int(lib.mrphy_blochsim_rfgr_mc_bwd_workspace(code, p.N, p.nM, p.nT, p.nC))
-    work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
-    grads = (gMi, g_rf, g_gr)
-    return grads, tuple(None if x is None else x.data_ptr() for x in grads), work
-
-
-def _empty_problem_grads(grads, gMo):
-    r"""No spin or no step (``N·nM·nT == 0``): the library's adjoints are no-ops then (``include/mrphy_hip.h``: an empty
-    problem is a success that writes nothing), so the gradients are written here -- ``Mo`` is ``Mi`` (``gMo``: its
-    cotangent, or ``None``) and nothing depends on the pulse."""
-    gMi, g_rf, g_gr = grads
-    if gMi is not None:
-        gMi.zero_() if gMo is None else gMi.copy_(gMo.reshape(gMi.shape))
-    for g in (g_rf, g_gr):
-        if g is not None:
-            g.zero_()
-
-
-def _like(x):
-    r"""What the backward needs of an operand to shape its gradient: ``(shape, dtype, device)``."""
-    return tuple(x.shape), x.dtype, x.device
-
-
-def _maps_backward_prep(p, needs, dtype, device):
-    r"""The per-spin outputs of ``mrphy_blochsim_rfgr_maps_bwd`` that ``needs`` (loc, Δf, b1Map) asks for:
-    ``(gloc (N, *Nd, 3), gBz (N, *Nd), gb1 (N, *Nd, 2))`` -- ``None`` where not wanted -- and their pointers."""
-    full = (p.N,) + p.Nd
-    outs = tuple(torch.empty(full + tail, dtype=dtype, device=device) if want else None
-                 for want, tail in zip(needs, ((3,), (), (2,))))
-    return outs, tuple(None if x is None else x.data_ptr() for x in outs)
+def _likes(**given):
+    r"""What the backward needs of the operands given (not ``None``) to shape their gradients: ``{name: (shape, dtype,
+    device)}``."""
+    return {k: (tuple(x.shape), x.dtype, x.device) for k, x in given.items() if x is not None}
 
 
 def _fold_map_grads(gloc, gBz, gb1, p, likes):
     r"""``(grad_loc, grad_Δf, grad_b1Map)`` in the shapes, dtypes and on the devices the caller's operands had
-    (``likes``: their :func:`_like`, ``None`` for an absent one): ``grad_Δf = gBz / γ_beff`` summed over the axes
+    (``likes``: their entries of :func:`_likes`, ``None`` for an absent one): ``grad_Δf = gBz / γ_beff`` summed over the axes
     ``Δf`` was broadcast along (``beffective.py:161-165``); ``grad_b1Map`` likewise, with the trailing coil axis of
     length 1 if the map had one."""
     from .beffective import _sum_to
@@ -123,7 +87,7 @@ def _fold_map_grads(gloc, gBz, gb1, p, likes):
 def _fold_const_grads(gC, p, likes, needs):
     r"""``(grad_γ2πdt, grad_E1, grad_E2, grad_E1_1)`` from the per-spin ``gC`` `(N, *Nd, 4)` of the CONSTS builds: each
     summed over the axes its constant was broadcast along, in the constant's own shape and dtype and on its device
-    (``likes``: their :func:`_like`, ``None`` for an absent one), ``None`` where ``needs`` does not ask -- as
+    (``likes``: their entries of :func:`_likes`, ``None`` for an absent one), ``None`` where ``needs`` does not ask -- as
     ``sims.BlochSimHIP.backward`` folds the ``gC`` of ``mrphy_blochsim_bwd_consts``."""
     from . import sims
     out = []
@@ -143,12 +107,91 @@ def _fold_gamma_beff_grad(gBz, p, like):
     return _sum_to(-gBz * p.df_v / (p.gam_v * p.gam_v), like[0]).to(device=like[2], dtype=like[1])
 
 
-def _fold_grads(gMi, g_rf, g_gr, p, rf_shape, gr_shape, rf_dtype, gr_dtype):
-    r"""``(grad_Mi, grad_rf, grad_gr)`` in the shapes and dtypes the caller's ``rf`` and ``gr`` had."""
+class _Saved(NamedTuple):
+    r"""What a forward keeps for its backward besides the checkpoints."""
+    p: object                 # the pulse on the spins (beffective._PulseOnSpins)
+    code: int                 # the dtype code
+    consts: tuple             # the constants' arguments g .. E1m1, pointing into ...
+    alive: tuple              # ... these (g, E1, E2, E1m1; the signal: and rx)
+    every: Optional[int]      # None: the plain call
+    rx: tuple                 # the signal: (rx's pointer or None,), and the coil count for an array; else ()
+    likes: dict               # _likes of the operands whose gradients the backward shapes, by argument name
+
+
+_CONSTS = ('γ2πdt', 'E1', 'E2', 'E1_1')
+_MAPS = ('loc', 'Δf', 'b1Map')
+# The adjoint entry points: what each takes between the operands and ``work, work_bytes, N, nM, nT[, nC], stream``, by
+# the names of :func:`_fused_adjoint`'s values.
+_PULSE_OUT = ('gMi', 'grf', 'ggr')
+_ADJOINT_ARGS = {
+    'mrphy_blochsim_rfgr_bwd': ('gMo', *_PULSE_OUT),
+    'mrphy_blochsim_rfgr_traj_bwd': ('gMt', 'every', *_PULSE_OUT),
+    'mrphy_blochsim_rfgr_mc_bwd': ('gMo', *_PULSE_OUT),
+    'mrphy_blochsim_rfgr_mc_traj_bwd': ('gMt', 'every', *_PULSE_OUT),
+    'mrphy_blochsim_rfgr_maps_bwd': ('gMo', 'gMt', 'every', *_PULSE_OUT, 'gloc', 'gBz', 'gb1'),
+    'mrphy_blochsim_rfgr_consts_bwd': ('gMo', 'gMt', 'every', *_PULSE_OUT, 'gloc', 'gBz', 'gb1', 'gC'),
+    'mrphy_signal_rfgr_bwd': ('rx', 'gMo', 'gsig', 'every', *_PULSE_OUT),
+    'mrphy_signal_rfgr_mrx_bwd': ('rx', 'nRx', 'gMo', 'gsig', 'every', *_PULSE_OUT),
+    'mrphy_signal_rfgr_consts_bwd': ('rx', 'nRx', 'gMo', 'gsig', 'every', *_PULSE_OUT, 'gC'),
+}
+
+
+def _fused_adjoint(s, Mck, signal, want, gMo=None, gMt=None, gsig=None):
+    r"""The one adjoint call of both Functions: ``s`` the forward's :class:`_Saved`, ``want`` the gradients wanted by
+    argument name, ``gMo``, ``gMt``, ``gsig`` the cotangents received (contiguous, of the kernels' dtype).  Returns the
+    raw gradients ``{name: tensor, or None where not wanted}``: per spin ``gMi``, ``gloc``, ``gBz`` (for ``Δf``),
+    ``gb1``, ``gC``; per pulse ``grf`` `(N, 2, nT, nC)`, ``ggr`` `(N, 3, nT)`."""
+    lib = _lib.require_library()
+    p, device, full = s.p, Mck.device, (s.p.N,) + s.p.Nd
+    outs = dict(gMi=(want['Mi'], full + (3,)), grf=(want['rf'], (p.N, 2, p.nT, p.nC)), ggr=(want['gr'], (p.N, 3, p.nT)),
+                gloc=(want.get('loc'), full + (3,)), gBz=(want.get('Δf'), full), gb1=(want.get('b1Map'), full + (2,)),
+                gC=(any(want[k] for k in _CONSTS), full + (4,)))
+    out = {k: torch.empty(shape, dtype=Mck.dtype, device=device) if w else None for k, (w, shape) in outs.items()}
+    if p.N * p.nM * p.nT == 0:
+        # No spin or no step: the library's adjoints are no-ops then (``include/mrphy_hip.h``: an empty problem is a
+        # success that writes nothing), so the gradients are written here -- ``Mo`` is ``Mi`` and nothing depends on
+        # the pulse, the maps or the constants.
+        for k, g in out.items():
+            if g is not None:
+                g.copy_(gMo.reshape(g.shape)) if k == 'gMi' and gMo is not None else g.zero_()
+        return out
+    mc, mrx = p.nC != 1, len(s.rx) > 1
+    # the CONSTS builds form the map sums too, and the signal's take one coil and an array alike (rx, nRx); a map
+    # gradient is wanted under one transmit coil only (_route)
+    if signal:
+        name = 'mrphy_signal_rfgr_' + ('consts_bwd' if out['gC'] is not None else 'mrx_bwd' if mrx else 'bwd')
+    elif out['gC'] is not None:
+        name = 'mrphy_blochsim_rfgr_consts_bwd'
+    elif any(out[k] is not None for k in ('gloc', 'gBz', 'gb1')):
+        name = 'mrphy_blochsim_rfgr_maps_bwd'
+    else:
+        name = 'mrphy_blochsim_rfgr_' + ('mc_' if mc else '') + ('traj_bwd' if gMt is not None else 'bwd')
+    nbytes = int(lib.mrphy_blochsim_rfgr_mc_bwd_workspace(s.code, p.N, p.nM, p.nT, p.nC) if mc    # per-coil sums
+                 else lib.mrphy_blochsim_rfgr_bwd_workspace(s.code, p.N, p.nM, p.nT))
+    work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+    vals = dict(out, gMo=gMo, gMt=gMt, gsig=gsig, every=s.every or 0, rx=s.rx[0] if s.rx else None,
+                nRx=s.rx[1] if mrx else 1)
+    ptr = lambda x: x.data_ptr() if isinstance(x, Tensor) else x  # noqa: E731
+    with torch.cuda.device(device):
+        rc = getattr(lib, name)(s.code, Mck.data_ptr(), *p.k0_args(), *s.consts,
+                                *(ptr(vals[k]) for k in _ADJOINT_ARGS[name]), work.data_ptr(), work.numel(),
+                                p.N, p.nM, p.nT, *((p.nC,) if mc else ()), _host.current_stream(device))
+    _lib.check(rc, name)
+    return out
+
+
+def _fold_pulse_and_const_grads(raw, s, want):
+    r"""``{argument name: gradient}`` of ``Mi``, ``rf``, ``gr`` and the step constants from the raw gradients, in the
+    shapes and dtypes the caller's operands had: what both backwards return."""
     from .beffective import _fold_pulse_grad
-    return (gMi,
-            None if g_rf is None else _fold_pulse_grad(g_rf, rf_shape, rf_dtype, p.b1 is None),
-            None if g_gr is None else _fold_pulse_grad(g_gr, gr_shape, gr_dtype, False))
+    g = dict(Mi=raw['gMi'])
+    for k, raw_k, no_b1 in (('rf', 'grf', s.p.b1 is None), ('gr', 'ggr', False)):
+        if raw[raw_k] is not None:
+            g[k] = _fold_pulse_grad(raw[raw_k], s.likes[k][0], s.likes[k][1], no_b1)
+    if raw['gC'] is not None:
+        g.update(zip(_CONSTS, _fold_const_grads(raw['gC'], s.p, [s.likes.get(k) for k in _CONSTS],
+                                                [want[k] for k in _CONSTS])))
+    return g
 
 
 class BlochSimRfGrHIP(Function):
@@ -170,13 +213,14 @@ class BlochSimRfGrHIP(Function):
     again: ``mrphy_blochsim_rfgr_consts_bwd`` returns them per spin besides everything the entry points above return,
     bit for bit, and they are summed here over the axes each constant broadcasts along."""
 
+    ARGS = ('Mi', 'rf', 'gr', 'p', 'γ2πdt', 'E1', 'E2', 'E1_1', 'want_ckpt', 'every', 'loc', 'Δf', 'b1Map', 'γ_beff')
+
     @staticmethod
     def forward(ctx, Mi, rf, gr, p, γ2πdt, E1, E2, E1_1, want_ckpt=False, every=None, loc=None, Δf=None, b1Map=None,
                 γ_beff=None):
         lib = _lib.require_library()
         device, dtype = Mi.device, Mi.dtype
-        need = bool(want_ckpt)
-        code, alive, consts, Mck, ckpt = _forward_prep(lib, p, γ2πdt, E1, E2, E1_1, dtype, device, need)
+        code, alive, consts, Mck, ckpt = _forward_prep(lib, p, γ2πdt, E1, E2, E1_1, dtype, device, bool(want_ckpt))
         Mi_c = Mi.detach().contiguous()
         traj = every is not None
         M = (torch.empty((-(-p.nT // every), p.N) + p.Nd + (3,), dtype=dtype, device=device) if traj
@@ -188,71 +232,34 @@ class BlochSimRfGrHIP(Function):
             rc = getattr(lib, name)(code, Mi_c.data_ptr(), *p.k0_args(), *consts, *outs,
                                     p.N, p.nM, p.nT, p.nC, _host.current_stream(device))
         _lib.check(rc, name)
-        if need:
+        if Mck is not None:                     # the checkpoints: a backward is wanted
             ctx.save_for_backward(Mck)
-            ctx.keep = (p, code, consts, alive, rf.shape, gr.shape, rf.dtype, gr.dtype, every)
-            ctx.maps_like = tuple(None if x is None else _like(x) for x in (loc, Δf, b1Map, γ_beff))
-            ctx.const_like = tuple(None if x is None else _like(x) for x in (γ2πdt, E1, E2, E1_1))
+            ctx.saved = _Saved(p, code, consts, alive, every, (), _likes(
+                rf=rf, gr=gr, loc=loc, Δf=Δf, b1Map=b1Map, γ_beff=γ_beff, γ2πdt=γ2πdt, E1=E1, E2=E2, E1_1=E1_1))
         return M
 
     @staticmethod
     def backward(ctx, grad_M):
-        nig = tuple(ctx.needs_input_grad) + (False,) * 4   # (as long as the arguments handed over: loc .. γ_beff may be missing)
-        needs = nig[0:3]
-        needs_c = nig[4:8]                                  # γ2πdt, E1, E2, E1_1
-        needs_maps = nig[10:13]                             # loc, Δf, b1Map: all False where they were not handed over
-        if not any(needs) and not any(needs_maps) and not any(needs_c) and not nig[13]:
-            return (None,) * 14
-        lib = _lib.require_library()
+        ARGS = BlochSimRfGrHIP.ARGS                   # (loc .. γ_beff: False where they were not handed over)
+        want = dict(zip(ARGS, (*ctx.needs_input_grad, *(False,) * len(ARGS))))
+        if not any(want.values()):
+            return tuple(None for _ in ARGS)
+        s = ctx.saved
         (Mck,) = ctx.saved_tensors
-        p, code, consts, _alive, rf_shape, gr_shape, rf_dtype, gr_dtype, every = ctx.keep
-        need_γb = nig[13] and p.df is not None        # without Δf the field does not depend on γ_beff
-        traj = every is not None
+        need_γb = want['γ_beff'] and s.p.df is not None        # without Δf the field does not depend on γ_beff
+        traj = s.every is not None
         # the precise adjoint divides by E once (as the reference's does at every step): refuse E == 0 HERE, where it
         # matters -- the forward succeeds as the reference's does; cached per constants
-        _host.require_invertible_relaxation(code, _alive[1], _alive[2],
+        _host.require_invertible_relaxation(s.code, s.alive[1], s.alive[2],
                                             'fused.blochsim_rfgr_traj' if traj else 'fused.blochsim_rfgr')
-        device, dtype = Mck.device, Mck.dtype
-        gM = grad_M.to(dtype).contiguous()      # the trajectory's: time-major, as the forward returned it -- free if so
-        grads, outs, work = _backward_prep(lib, p, code, needs, dtype, device)
-        tr = (every,) if traj else ()
-        pulse_grads = lambda: _fold_grads(*grads, p, rf_shape, gr_shape, rf_dtype, gr_dtype)  # noqa: E731
-        if any(needs_maps) or any(needs_c) or need_γb:
-            # one transmit coil (_route): the MAPS builds of K2b / K2bt, or -- with a constant's gradient wanted -- the
-            # CONSTS builds, which form the map sums too
-            want_maps = (needs_maps[0], needs_maps[1] or need_γb, needs_maps[2])
-            mgrads, mouts = _maps_backward_prep(p, want_maps, dtype, device)
-            gC = torch.empty((p.N,) + p.Nd + (4,), dtype=dtype, device=device) if any(needs_c) else None
-            if p.N * p.nM * p.nT == 0:          # nothing depends on the maps or the constants either
-                _empty_problem_grads(grads, None if traj else gM)
-                for g in (*mgrads, gC):
-                    if g is not None:
-                        g.zero_()
-            else:
-                name = 'mrphy_blochsim_rfgr_maps_bwd' if gC is None else 'mrphy_blochsim_rfgr_consts_bwd'
-                gMo, gMt, ev = (None, gM.data_ptr(), every) if traj else (gM.data_ptr(), None, 0)
-                with torch.cuda.device(device):
-                    rc = getattr(lib, name)(code, Mck.data_ptr(), *p.k0_args(), *consts, gMo, gMt, ev, *outs, *mouts,
-                                            *(() if gC is None else (gC.data_ptr(),)), work.data_ptr(), work.numel(),
-                                            p.N, p.nM, p.nT, _host.current_stream(device))
-                _lib.check(rc, name)
-            g_c = (None,) * 4 if gC is None else _fold_const_grads(gC, p, ctx.const_like, needs_c)
-            g_γb = _fold_gamma_beff_grad(mgrads[1], p, ctx.maps_like[3]) if need_γb else None
-            g_maps = _fold_map_grads(mgrads[0], mgrads[1] if needs_maps[1] else None, mgrads[2], p, ctx.maps_like)
-            return (*pulse_grads(), None, *g_c, None, None, *g_maps, g_γb)
-        if p.N * p.nM * p.nT == 0:
-            _empty_problem_grads(grads, None if traj else gM)
-            return (*pulse_grads(), *(None,) * 11)
-        if p.nC == 1:
-            name, nc = ('mrphy_blochsim_rfgr_traj_bwd' if traj else 'mrphy_blochsim_rfgr_bwd'), ()
-        else:                                   # parallel transmit
-            name, nc = ('mrphy_blochsim_rfgr_mc_traj_bwd' if traj else 'mrphy_blochsim_rfgr_mc_bwd'), (p.nC,)
-        with torch.cuda.device(device):
-            rc = getattr(lib, name)(code, Mck.data_ptr(), *p.k0_args(), *consts, gM.data_ptr(), *tr, *outs,
-                                    work.data_ptr(), work.numel(), p.N, p.nM, p.nT, *nc,
-                                    _host.current_stream(device))
-        _lib.check(rc, name)
-        return (*pulse_grads(), *(None,) * 11)
+        gM = grad_M.to(Mck.dtype).contiguous()  # the trajectory's: time-major, as the forward returned it -- free if so
+        raw = _fused_adjoint(s, Mck, False, {**want, 'Δf': want['Δf'] or need_γb}, **{'gMt' if traj else 'gMo': gM})
+        g = _fold_pulse_and_const_grads(raw, s, want)
+        g.update(zip(_MAPS, _fold_map_grads(raw['gloc'], raw['gBz'] if want['Δf'] else None, raw['gb1'], s.p,
+                                            [s.likes.get(k) for k in _MAPS])))
+        if need_γb:
+            g['γ_beff'] = _fold_gamma_beff_grad(raw['gBz'], s.p, s.likes['γ_beff'])
+        return tuple(g.get(k) for k in ARGS)
 
 
 class SignalRfGrHIP(Function):
@@ -266,12 +273,13 @@ class SignalRfGrHIP(Function):
     ``want_ckpt`` as in :class:`BlochSimRfGrHIP`; so are the gradients of ``γ2πdt``, ``E1``, ``E2``, ``E1_1`` that require
     grad (``mrphy_signal_rfgr_consts_bwd``, for one coil and for an array, in place of the two adjoints above)."""
 
+    ARGS = ('Mi', 'rf', 'gr', 'p', 'rx', 'γ2πdt', 'E1', 'E2', 'E1_1', 'want_ckpt', 'every')
+
     @staticmethod
     def forward(ctx, Mi, rf, gr, p, rx, γ2πdt, E1, E2, E1_1, want_ckpt=False, every=1):
         lib = _lib.require_library()
         device, dtype = Mi.device, Mi.dtype
-        need = bool(want_ckpt)
-        code, alive, consts, Mck, ckpt = _forward_prep(lib, p, γ2πdt, E1, E2, E1_1, dtype, device, need)
+        code, alive, consts, Mck, ckpt = _forward_prep(lib, p, γ2πdt, E1, E2, E1_1, dtype, device, bool(want_ckpt))
         mrx = (rx.shape[-1],) if rx is not None and rx.ndim == 4 else ()      # the coil count, for the _mrx_ entry points
         rxa = (None if rx is None else rx.data_ptr(), *mrx)
         Mi_c = Mi.detach().contiguous()
@@ -291,50 +299,54 @@ class SignalRfGrHIP(Function):
                                     p.N, p.nM, p.nT, p.nC, _host.current_stream(device))
         _lib.check(rc, name)
         ctx.set_materialize_grads(False)
-        if need:
+        if Mck is not None:                     # the checkpoints: a backward is wanted
             ctx.save_for_backward(Mck)
-            ctx.keep = (p, code, consts, rxa, (*alive, rx), rf.shape, gr.shape, rf.dtype, gr.dtype, every, bool(mrx))
-            ctx.const_like = tuple(None if x is None else _like(x) for x in (γ2πdt, E1, E2, E1_1))
+            ctx.saved = _Saved(p, code, consts, (*alive, rx), every, rxa,
+                               _likes(rf=rf, gr=gr, γ2πdt=γ2πdt, E1=E1, E2=E2, E1_1=E1_1))
         return sig, Mo
 
     @staticmethod
     def backward(ctx, grad_sig, grad_Mo):
-        needs = ctx.needs_input_grad[0:3]
-        needs_c = tuple(ctx.needs_input_grad[5:9])          # γ2πdt, E1, E2, E1_1
-        if not (any(needs) or any(needs_c)) or (grad_sig is None and grad_Mo is None):
-            return (None,) * 11
-        lib = _lib.require_library()
+        want = dict(zip(SignalRfGrHIP.ARGS, ctx.needs_input_grad))
+        if not any(want.values()) or (grad_sig is None and grad_Mo is None):
+            return tuple(None for _ in SignalRfGrHIP.ARGS)
+        s = ctx.saved
         (Mck,) = ctx.saved_tensors
-        p, code, consts, rxa, _alive, rf_shape, gr_shape, rf_dtype, gr_dtype, every, mrx = ctx.keep
-        _host.require_invertible_relaxation(code, _alive[1], _alive[2], 'fused.signal_rfgr')
-        device, dtype = Mck.device, Mck.dtype
-        gs = None if grad_sig is None else grad_sig.to(dtype).contiguous()
-        gM = None if grad_Mo is None else grad_Mo.to(dtype).contiguous()
-        grads, outs, work = _backward_prep(lib, p, code, needs, dtype, device)      # one transmit coil: K2b's workspace
-        gC = torch.empty((p.N,) + p.Nd + (4,), dtype=dtype, device=device) if any(needs_c) else None
-        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
-        done = lambda: (*_fold_grads(*grads, p, rf_shape, gr_shape, rf_dtype, gr_dtype), None, None,  # noqa: E731
-                        *((None,) * 4 if gC is None else _fold_const_grads(gC, p, ctx.const_like, needs_c)), None, None)
-        if p.N * p.nM * p.nT == 0:
-            _empty_problem_grads(grads, gM)
-            if gC is not None:
-                gC.zero_()                      # nothing depends on the constants either
-            return done()
-        if gC is not None:                      # the CONSTS builds take one coil and an array alike: rx, nRx
-            name, rxa, gc = 'mrphy_signal_rfgr_consts_bwd', (rxa[0], rxa[1] if mrx else 1), (gC.data_ptr(),)
-        else:
-            name, gc = ('mrphy_signal_rfgr_mrx_bwd' if mrx else 'mrphy_signal_rfgr_bwd'), ()
-        with torch.cuda.device(device):
-            rc = getattr(lib, name)(code, Mck.data_ptr(), *p.k0_args(), *consts, *rxa, ptr(gM), ptr(gs), every,
-                                    *outs, *gc, work.data_ptr(), work.numel(),
-                                    p.N, p.nM, p.nT, _host.current_stream(device))
-        _lib.check(rc, name)
-        return done()
+        _host.require_invertible_relaxation(s.code, s.alive[1], s.alive[2], 'fused.signal_rfgr')
+        cot = {k: None if x is None else x.to(Mck.dtype).contiguous() for k, x in (('gsig', grad_sig), ('gMo', grad_Mo))}
+        raw = _fused_adjoint(s, Mck, True, want, **cot)
+        g = _fold_pulse_and_const_grads(raw, s, want)
+        return tuple(g.get(k) for k in SignalRfGrHIP.ARGS)
+
+
+def _decide_route(*, nT, seg, nC, one_coil, has_b1, f64, signal, ptx_max, pulse_grad, maps_grad, consts_grad, rx_grad,
+                  γb_grad=False):
+    r"""The decision of :func:`_route`, which explains it, as a function of plain facts (``ptx_max``: the coil limit of
+    the parallel-transmit adjoint; ``maps_grad`` includes ``γb_grad``): ``('split', n1)``, ``('composed', None)`` or
+    ``('fused', want_ckpt, maps_fused, γb_grad)`` -- run the Function, with checkpoints, handing it the maps and ``γ_beff``."""
+    seg_ok = nT % seg == 0
+    ptx = 1 < nC <= ptx_max and has_b1 and not signal
+    fused_adjoint_ok = seg_ok and (one_coil or ptx)
+    # the map gradients come out of the one-coil adjoint's sweep (the MAPS builds of K2b / K2bt); the signal call keeps
+    # its composed route for them, whose trajectory takes this one
+    maps_fused = maps_grad and one_coil and not signal
+    # the constants' gradients likewise (the CONSTS builds), in the signal call as well -- but not under parallel transmit
+    consts_fused = consts_grad and one_coil and (not signal or not maps_grad)
+    if not seg_ok and nT > seg and not rx_grad and (not consts_grad or consts_fused) and \
+            (maps_fused or ((pulse_grad or consts_fused) and not maps_grad and (one_coil or ptx))):
+        return 'split', (nT // seg) * seg
+    # fp64 with more than 8 transmit coils: the fused forward has no register build for it (it would spill),
+    # the composed route does (k_rfgr2beff_steps / _pk + K1) and gives the same bits
+    wide_f64 = (f64 and nC > 8) or (has_b1 and nC > 64)   # (> 64: coil-blocked K0 + K1)
+    if (maps_grad and not (maps_fused and seg_ok)) or rx_grad or wide_f64 or (pulse_grad and not fused_adjoint_ok) \
+            or (signal and nC != 1) or (consts_grad and not (consts_fused and seg_ok)):
+        return 'composed', None
+    return 'fused', (pulse_grad or maps_fused or consts_fused) and fused_adjoint_ok, maps_fused, γb_grad
 
 
 def _route(Mi, rf, gr, loc, every, kw, signal=False, rx=None):
     r"""The routing :func:`blochsim_rfgr` (``every = None``), :func:`blochsim_rfgr_traj` and (``signal``, with its
-    receive map ``rx``) :func:`signal_rfgr` share.  Returns
+    receive map ``rx``) :func:`signal_rfgr` share; the decision itself is :func:`_decide_route`'s.  Returns
     ``('split', n1)``: a gradient through the fused adjoint, but a length that is not a whole number of
     checkpoint segments -- the caller runs the first ``n1`` steps fused and composes the tail (autograd adds the two
     parts' gradients w.r.t. the maps); ``('composed', None)``: a case the fused kernels do not cover (gradients w.r.t.
@@ -367,31 +379,20 @@ def _route(Mi, rf, gr, loc, every, kw, signal=False, rx=None):
     p = beffective._PulseOnSpins(rf.detach(), gr.detach(), loc.detach(),
                                  None if Δf is None else Δf.detach(),
                                  None if b1Map is None else b1Map.detach(), kw['γ_beff'].detach())
-    seg = int(lib.mrphy_blochsim_rfgr_ck_every())
-    seg_ok = p.nT % seg == 0
-    one_coil = p.nC == 1 and (rf.ndim == 3 or b1Map is not None or rf.shape[-1] == 1)
-    ptx = 1 < p.nC <= int(lib.mrphy_blochsim_rfgr_mc_max_coils()) and p.b1 is not None and not signal
-    fused_adjoint_ok = seg_ok and (one_coil or ptx)
-    # the map gradients come out of the one-coil adjoint's sweep (the MAPS builds of K2b / K2bt); the signal call keeps
-    # its composed route for them, whose trajectory takes this one
-    maps_fused = maps_grad and one_coil and not signal
-    # the constants' gradients likewise (the CONSTS builds), in the signal call as well -- but not under parallel transmit
-    consts_fused = consts_grad and one_coil and (not signal or not maps_grad)
-    if not seg_ok and p.nT > seg and not rx_grad and (not consts_grad or consts_fused) and \
-            (maps_fused or ((pulse_grad or consts_fused) and not maps_grad and (one_coil or ptx))):
-        return 'split', (p.nT // seg) * seg
-    # fp64 with more than 8 transmit coils: the fused forward has no register build for it (it would spill),
-    # the composed route does (k_rfgr2beff_steps / _pk + K1) and gives the same bits
-    wide_f64 = (p.dtype == torch.float64 and p.nC > 8) or (p.b1 is not None and p.nC > 64)   # (> 64: coil-blocked K0 + K1)
-    if (maps_grad and not (maps_fused and seg_ok)) or rx_grad or wide_f64 or (pulse_grad and not fused_adjoint_ok) \
-            or (signal and p.nC != 1) or (consts_grad and not (consts_fused and seg_ok)):
-        return 'composed', None
+    decision = _decide_route(
+        nT=p.nT, seg=int(lib.mrphy_blochsim_rfgr_ck_every()), nC=p.nC,
+        one_coil=p.nC == 1 and (rf.ndim == 3 or b1Map is not None or rf.shape[-1] == 1), has_b1=p.b1 is not None,
+        f64=p.dtype == torch.float64, signal=signal, ptx_max=int(lib.mrphy_blochsim_rfgr_mc_max_coils()),
+        pulse_grad=pulse_grad, maps_grad=maps_grad, consts_grad=consts_grad, rx_grad=rx_grad, γb_grad=γb_grad)
+    if decision[0] != 'fused':
+        return decision
+    _, want, maps_fused, _ = decision
 
     device, dtype = Mi.device, Mi.dtype
     assert p.device == device and p.dtype == dtype, "Mi and loc must share device and dtype"
     assert tuple(Mi.shape[:-1]) == (p.N,) + p.Nd
     if kw['consts'] is not None:
-        γ2πdt, E1, E2, E1_1 = (kw['consts'].get(k) for k in ('γ2πdt', 'E1', 'E2', 'E1_1'))
+        γ2πdt, E1, E2, E1_1 = (kw['consts'].get(k) for k in _CONSTS)
     elif consts_grad:
         # differentiable, as slowsims.blochsim forms them: relax_constants' expressions on the same padded operands on
         # the same device, so the values -- and Mo -- are the bits of the call that does not differentiate them
@@ -400,7 +401,6 @@ def _route(Mi, rf, gr, loc, every, kw, signal=False, rx=None):
         γ2πdt, E1, E2, E1_1 = sims._gamma_dt_constants(pad(T1), pad(T2), pad(kw['γ']), pad(kw['dt']))
     else:
         γ2πdt, E1, E2, E1_1 = sims.relax_constants(T1, T2, kw['γ'], kw['dt'], 1 + len(p.Nd) + 2, device)
-    want = (pulse_grad or maps_fused or consts_fused) and fused_adjoint_ok
     if signal:
         apply = lambda r: SignalRfGrHIP.apply(Mi, rf, gr, p, r, γ2πdt, E1, E2, E1_1, want, every)  # noqa: E731
         if rx is None:
@@ -417,10 +417,8 @@ def _route(Mi, rf, gr, loc, every, kw, signal=False, rx=None):
         cap = int(lib.mrphy_signal_rfgr_max_rx(_lib.F64 if dtype == torch.float64 else _lib.F32))
         outs = [apply(r[..., c:c + cap].contiguous()) for c in range(0, nrx, cap)]
         return 'fused', (outs[0][0] if len(outs) == 1 else torch.cat([o[0] for o in outs], dim=-1), outs[0][1])
-    if maps_fused:
-        return 'fused', BlochSimRfGrHIP.apply(Mi, rf, gr, p, γ2πdt, E1, E2, E1_1, want, every, loc, Δf, b1Map,
-                                              kw['γ_beff'] if γb_grad else None)
-    return 'fused', BlochSimRfGrHIP.apply(Mi, rf, gr, p, γ2πdt, E1, E2, E1_1, want, every)
+    maps = (loc, Δf, b1Map, kw['γ_beff'] if γb_grad else None) if maps_fused else ()
+    return 'fused', BlochSimRfGrHIP.apply(Mi, rf, gr, p, γ2πdt, E1, E2, E1_1, want, every, *maps)
 
 
 @_host.half_via_float
