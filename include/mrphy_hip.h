@@ -75,7 +75,8 @@ extern "C" {
  *      of a receive array from ONE simulation per launch); mrphy_blochsim_rfgr_maps_bwd (K2b / K2bt of one transmit
  *      coil, which also returns the gradients w.r.t. loc, df and b1); mrphy_blochsim_rfgr_consts_bwd,
  *      mrphy_signal_rfgr_consts_bwd (the same adjoints, which also return the gradients w.r.t. the step constants
- *      g = gamma 2 pi dt, E1, E2, E1m1 per spin). */
+ *      g = gamma 2 pi dt, E1, E2, E1m1 per spin); mrphy_ab_rfgr_fwd, mrphy_ab_rfgr_bwd (Hargreaves' A, B of a pulse
+ *      from rf and gr without Beff in memory, and the adjoint w.r.t. the pulse). */
 #define MRPHY_ABI_VERSION 5
 
 #define MRPHY_F32      0  /* T = float,  CT = float                                          */
@@ -855,6 +856,60 @@ int mrphy_beff2ab_bwd_consts(int dtype, const void* hist, const void* Beff,
                              const void* E2, int64_t E2_sn, int64_t E2_sm,
                              const void* grad_A, const void* grad_B, void* grad_Beff,
                              void* grad_consts, int64_t N, int64_t nM, int64_t nT, void* stream);
+/* ---------------------------------------------------------------------------------------------
+ * K2ab  fused rf,gr -> A, B: mrphy.beffective.beff2ab (beffective.py:40-104) of mrphy.beffective.rfgr2beff
+ * (beffective.py:107-168) without Beff (N,nM,nT,3) in HBM.  Operands and constants as mrphy_blochsim_rfgr_fwd, ONE
+ * transmit coil (rf (N|1, 2, nT, 1), b1 (N, nM, 2) or NULL); E1 == E2 == E1m1 == NULL is "no relaxation": A is then a
+ * pure rotation and B an exact zero.  A (N,nM,3,3), B (N,nM,3) as mrphy_beff2ab lays them out, and with the same
+ * constants they are mrphy_beff2ab(mrphy_rfgr2beff(.)) bit for bit: one field and one rotation per step, applied to
+ * the three A columns with a zero offset and to the B column with E1m1.  nT == 0 writes A = I, B = 0.
+ * ABck (nCk, 4, N*nM, 3), nCk = ceil(nT/ck_every), may be NULL; otherwise plane j of checkpoint c receives column j
+ * (j == 3: B) before step c*ck_every (ck_every a positive multiple of 8): plane j < 3 is the Mck that
+ * mrphy_blochsim_rfgr_fwd writes for Mi = e_j with a zero E1m1, bit for bit.
+ *
+ * K2abb  its adjoint w.r.t. the pulse: grad_A (N,nM,3,3), grad_B (N,nM,3) (either may be NULL = zero) -> grad_rf
+ * (N,2,nT), grad_gr (N,3,nT) (either may be NULL), per batch entry as mrphy_blochsim_rfgr_bwd returns them.  ABck must
+ * be the checkpoints of mrphy_ab_rfgr_fwd with ck_every = mrphy_blochsim_rfgr_ck_every(), nT a multiple of it; `work`
+ * holds mrphy_blochsim_rfgr_bwd_workspace() bytes.  Per segment the four columns are recomputed and swept one after
+ * another (they share the step's rotation; S and C are formed once), their dL/dBeff summed in a fixed order, then
+ * reduced over the spins as K2b reduces: deterministic, no Beff, no history, no grad_Beff in memory.  Under codes
+ * 3 / 4 E1 and E2 must be non-zero, as for the other adjoints.
+ * Both refuse with MRPHY_EINVAL, before anything is launched: an unknown dtype, a NULL required pointer, N > 65535;
+ * the adjoint also nT not a multiple of the segment and a workspace shorter than the query's.  An empty problem
+ * (N*nM == 0; the adjoint: N*nM*nT == 0) is a success that writes nothing.
+ * ------------------------------------------------------------------------------------------- */
+int mrphy_ab_rfgr_fwd(int dtype,
+                      const void* rf, int64_t rf_sn,
+                      const void* gr, int64_t gr_sn,
+                      const void* loc,
+                      const void* df, int64_t df_sn, int64_t df_sm,
+                      const void* gamma, int64_t gamma_sn, int64_t gamma_sm,
+                      const void* b1,
+                      const void* g,  int64_t g_sn,  int64_t g_sm,
+                      const void* E1, int64_t E1_sn, int64_t E1_sm,
+                      const void* E2, int64_t E2_sn, int64_t E2_sm,
+                      const void* E1m1,
+                      void* A, void* B, void* ABck, int64_t ck_every,
+                      int64_t N, int64_t nM, int64_t nT,
+                      void* stream);
+int mrphy_ab_rfgr_bwd(int dtype,
+                      const void* ABck,
+                      const void* rf, int64_t rf_sn,
+                      const void* gr, int64_t gr_sn,
+                      const void* loc,
+                      const void* df, int64_t df_sn, int64_t df_sm,
+                      const void* gamma, int64_t gamma_sn, int64_t gamma_sm,
+                      const void* b1,
+                      const void* g,  int64_t g_sn,  int64_t g_sm,
+                      const void* E1, int64_t E1_sn, int64_t E1_sm,
+                      const void* E2, int64_t E2_sn, int64_t E2_sm,
+                      const void* E1m1,
+                      const void* grad_A, const void* grad_B,
+                      void* grad_rf, void* grad_gr,
+                      void* work, size_t work_bytes,
+                      int64_t N, int64_t nM, int64_t nT,
+                      void* stream);
+
 int mrphy_blochsim_ab(int dtype, const void* M, const void* A, const void* B, void* Mo,
                       int64_t rows, void* stream);
 int mrphy_blochsim_ab_bwd(int dtype, const void* M, const void* A, const void* gMo, void* gM,

@@ -498,6 +498,36 @@ int mrphy_signal_rfgr_consts_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PAR
     return signal_bwd(true, true, dtype, r, MRPHY_PULSE_OPS, work_bytes, stream);
 }
 
+// K2ab / K2abb.  Order of the checks as in the rest of the fused family: dtype and sizes, the mode arguments, the empty
+// problem, null pointers, the workspace.  The forward runs at nT == 0 (A = I, B = 0), without a pulse then.
+int mrphy_ab_rfgr_fwd(int dtype, MRPHY_PULSE_OPS_PARAMS, void* A, void* B, void* ABck, int64_t ck_every, int64_t N,
+                      int64_t nM, int64_t nT, void* stream)
+{
+    if (int e = check_common(dtype, N, nM, nT)) return e;
+    if (N > 65535 || (ABck && (ck_every < 8 || ck_every % 8 != 0))) return MRPHY_EINVAL;
+    if (N * nM == 0) return 0;
+    if (!A || !B) return MRPHY_EINVAL;
+    const PulseOps in = MRPHY_PULSE_OPS;
+    if (int e = check_ops(in, nT > 0, false)) return e;
+    hipStream_t st = (hipStream_t)stream;
+    MRPHY_DISPATCH(dtype, (run_ab_rfgr_fwd<T, CT>(in, A, B, ABck, ck_every, N, nM, nT, st)));
+}
+
+int mrphy_ab_rfgr_bwd(int dtype, const void* ABck, MRPHY_PULSE_OPS_PARAMS, const void* grad_A, const void* grad_B,
+                      void* grad_rf, void* grad_gr, void* work, size_t work_bytes, int64_t N, int64_t nM, int64_t nT,
+                      void* stream)
+{
+    if (int e = check_common(dtype, N, nM, nT)) return e;
+    if (N > 65535 || nT % SEG != 0) return MRPHY_EINVAL;               // whole checkpoint segments only
+    if (N * nM * nT == 0) return 0;
+    if (!ABck || !work) return MRPHY_EINVAL;
+    const PulseOps in = MRPHY_PULSE_OPS;
+    if (int e = check_ops(in, true, false)) return e;
+    if (work_bytes < mrphy_blochsim_rfgr_bwd_workspace(dtype, N, nM, nT)) return MRPHY_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    MRPHY_DISPATCH(dtype, (run_ab_rfgr_bwd<T, CT>(ABck, in, grad_A, grad_B, grad_rf, grad_gr, work, N, nM, nT, st)));
+}
+
 int mrphy_beff2ab(int dtype, const void* Beff,
                   const void* g, int64_t g_sn, int64_t g_sm,
                   const void* E1, int64_t E1_sn, int64_t E1_sm,

@@ -75,6 +75,16 @@ constexpr AdjBuild sig_consts_build(int R)
 template <AdjBuild B, typename T, typename CT>
 int run_fused_bwd(const AdjointReq& r, PulseOps in, hipStream_t st);
 
+// K2ab / K2abb (tu_ab_rfgr_fwd.hip, tu_ab_rfgr_bwd.hip): Hargreaves' A, B of the fused family's operands, one transmit
+// coil, and the adjoint w.r.t. the pulse.  ABck (nCk, 4, N*nM, 3): the four columns' checkpoints, null for none
+template <typename T, typename CT>
+int run_ab_rfgr_fwd(PulseOps in, void* A, void* B, void* ABck, int64_t ck_every, int64_t N, int64_t nM, int64_t nT,
+                    hipStream_t st);
+
+template <typename T, typename CT>
+int run_ab_rfgr_bwd(const void* ABck, PulseOps in, const void* gA, const void* gB, void* grf, void* ggr, void* work,
+                    int64_t N, int64_t nM, int64_t nT, hipStream_t st);
+
 template <typename T, typename CT>
 int run_beff2ab(const void* Beff, Bc g, Bc E1, Bc E2, const void* E1m1, void* A, void* B, void* hist,
                 int64_t N, int64_t nM, int64_t nT, hipStream_t st);

@@ -30,6 +30,11 @@ trajectory kernels K2t / K2bt.
 :func:`signal_rfgr` is the same simulation again, returning what a receive coil measures: the transverse
 magnetisation summed over the spins at the trajectory's record steps (K2s, and the signal mode of K2b), without the
 per-spin records in memory; the coils of a receive array share one simulation per launch.
+
+:func:`ab_rfgr` is Hargreaves' propagator of the whole pulse per spin, ``M_after = A @ M_before + B``
+(``beffective.beff2ab`` of ``beffective.rfgr2beff``), from the same operands: the four columns of ``[I | 0]`` share
+each step's field and rotation (K2ab), and the gradients w.r.t. ``rf`` and ``gr`` come from a fused adjoint over the
+four columns' checkpoints (K2abb) -- again without ``Beff``, a history or ``grad_Beff`` in memory.
 """
 from math import pi as π, prod  # noqa: F401
 from typing import NamedTuple, Optional
@@ -41,7 +46,7 @@ from torch.autograd import Function
 from . import _lib, _host
 from ._consts import γH, dt0
 
-__all__ = ['blochsim_rfgr', 'blochsim_rfgr_traj', 'signal_rfgr']
+__all__ = ['blochsim_rfgr', 'blochsim_rfgr_traj', 'signal_rfgr', 'ab_rfgr']
 
 
 def _forward_prep(lib, p, γ2πdt, E1, E2, E1_1, dtype, device, need):
@@ -317,6 +322,88 @@ class SignalRfGrHIP(Function):
         raw = _fused_adjoint(s, Mck, True, want, **cot)
         g = _fold_pulse_and_const_grads(raw, s, want)
         return tuple(g.get(k) for k in SignalRfGrHIP.ARGS)
+
+
+class AbRfGrHIP(Function):
+    r"""``A, B = AbRfGrHIP.apply(rf, gr, pulse_on_spins, γ2πdt, E1, E2, E1_1, want_ckpt)``
+
+    Hargreaves' ``A`` `(N, *Nd, xyz, 3)`, ``B`` `(N, *Nd, xyz)` of the pulse on the spins (``mrphy_ab_rfgr_fwd``), one
+    transmit coil; ``E1 = E2 = E1_1 = None`` is no relaxation.  Differentiable w.r.t. ``rf`` and ``gr``
+    (``mrphy_ab_rfgr_bwd``); either output may go without a cotangent.  ``want_ckpt`` as in :class:`BlochSimRfGrHIP`:
+    decided by the caller (:func:`_decide_ab_route`), and the pulse length is then a whole number of segments."""
+
+    ARGS = ('rf', 'gr', 'p', 'γ2πdt', 'E1', 'E2', 'E1_1', 'want_ckpt')
+
+    @staticmethod
+    def forward(ctx, rf, gr, p, γ2πdt, E1, E2, E1_1, want_ckpt=False):
+        lib = _lib.require_library()
+        device, dtype = p.device, p.dtype
+        code, alive, consts, _, _ = _forward_prep(lib, p, γ2πdt, E1, E2, E1_1, dtype, device, False)
+        ck = int(lib.mrphy_blochsim_rfgr_ck_every())
+        # the four columns' checkpoints, one set per started segment: (ceil(nT / ck), 4, N nM, 3)
+        ABck = torch.empty((-(-p.nT // ck), 4, p.N * p.nM, 3), dtype=dtype, device=device) if want_ckpt else None
+        A = torch.empty((p.N,) + p.Nd + (3, 3), dtype=dtype, device=device)
+        B = torch.empty((p.N,) + p.Nd + (3,), dtype=dtype, device=device)
+        with torch.cuda.device(device):
+            rc = lib.mrphy_ab_rfgr_fwd(code, *p.k0_args(), *consts, A.data_ptr(), B.data_ptr(),
+                                       ABck.data_ptr() if want_ckpt else None, ck if want_ckpt else 0,
+                                       p.N, p.nM, p.nT, _host.current_stream(device))
+        _lib.check(rc, 'mrphy_ab_rfgr_fwd')
+        ctx.set_materialize_grads(False)
+        if want_ckpt:
+            ctx.save_for_backward(ABck)
+            ctx.saved = _Saved(p, code, consts, alive, None, (), _likes(rf=rf, gr=gr))
+        return A, B
+
+    @staticmethod
+    def backward(ctx, grad_A, grad_B):
+        from .beffective import _fold_pulse_grad
+        ARGS = AbRfGrHIP.ARGS
+        want = dict(zip(ARGS, ctx.needs_input_grad))
+        if not (want['rf'] or want['gr']) or (grad_A is None and grad_B is None):
+            return tuple(None for _ in ARGS)
+        lib = _lib.require_library()
+        s = ctx.saved
+        (ABck,) = ctx.saved_tensors
+        p, device, dtype = s.p, ABck.device, ABck.dtype
+        _host.require_invertible_relaxation(s.code, s.alive[1], s.alive[2], 'fused.ab_rfgr')
+        gA, gB = (None if x is None else x.to(dtype).contiguous() for x in (grad_A, grad_B))
+        raw = dict(rf=torch.empty((p.N, 2, p.nT, 1), dtype=dtype, device=device) if want['rf'] else None,
+                   gr=torch.empty((p.N, 3, p.nT), dtype=dtype, device=device) if want['gr'] else None)
+        if p.N * p.nM * p.nT == 0:
+            # no spin or no step: the library's adjoint writes nothing then, and A = I, B = 0 whatever the pulse is
+            for g in raw.values():
+                if g is not None:
+                    g.zero_()
+        else:
+            nbytes = int(lib.mrphy_blochsim_rfgr_bwd_workspace(s.code, p.N, p.nM, p.nT))
+            work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+            ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+            with torch.cuda.device(device):
+                rc = lib.mrphy_ab_rfgr_bwd(s.code, ABck.data_ptr(), *p.k0_args(), *s.consts, ptr(gA), ptr(gB),
+                                           ptr(raw['rf']), ptr(raw['gr']), work.data_ptr(), work.numel(),
+                                           p.N, p.nM, p.nT, _host.current_stream(device))
+            _lib.check(rc, 'mrphy_ab_rfgr_bwd')
+        g = {k: _fold_pulse_grad(x, s.likes[k][0], s.likes[k][1], k == 'rf' and p.b1 is None)
+             for k, x in raw.items() if x is not None}
+        return tuple(g.get(k) for k in ARGS)
+
+
+def _decide_ab_route(*, nT, seg, one_coil, pulse_grad, maps_grad, consts_grad):
+    r"""The route of :func:`ab_rfgr` as a function of plain facts (``maps_grad``: a gradient w.r.t. ``loc``, ``Δf``,
+    ``b1Map`` or a ``γ_beff`` that multiplies a ``Δf``): ``('fused', want_ckpt)`` -- one transmit coil and either no
+    gradient or a pulse gradient over whole checkpoint segments; ``('split', n1)`` -- one coil, a pulse gradient, more
+    than one segment's steps and a ragged last one: the first ``n1`` steps fused, the tail composed;
+    ``('composed', None)`` -- everything else: ``rfgr2beff`` + ``beff2ab``, whose autograd serves every operand."""
+    if not one_coil or maps_grad or consts_grad:
+        return 'composed', None
+    if not pulse_grad:
+        return 'fused', False
+    if nT % seg == 0:
+        return 'fused', True
+    if nT > seg:
+        return 'split', (nT // seg) * seg
+    return 'composed', None
 
 
 def _decide_route(*, nT, seg, nC, one_coil, has_b1, f64, signal, ptx_max, pulse_grad, maps_grad, consts_grad, rx_grad,
@@ -604,3 +691,81 @@ def signal_rfgr(
     else:
         sig, Mo = _signal_composed(Mi, rf, gr, loc, every, rx, kw)
     return (sig, Mo) if return_Mo else sig
+
+
+def _ab_composed(rf, gr, loc, kw, cs, consts_grad):
+    r"""``A, B`` as ``rfgr2beff`` followed by ``beff2ab``'s kernels on the step constants ``cs = (γ2πdt, E1, E2, E1_1)``
+    (``E1 = None``: no relaxation, i.e. factors of one and a zero offset): differentiable w.r.t. every operand, at the
+    price of ``Beff`` and, with gradients, the columns' history in memory -- the route of the cases the fused kernels do
+    not cover, and the tests' yardstick."""
+    from . import beffective
+    beff = beffective.rfgr2beff(rf, gr, loc, Δf=kw['Δf'], b1Map=kw['b1Map'], γ=kw['γ_beff'], lazy=False)
+    γ2πdt, E1, E2, E1_1 = cs
+    if E1 is None:
+        E1 = E2 = torch.ones((), dtype=beff.dtype, device=beff.device)
+        E1_1 = torch.zeros((), dtype=beff.dtype, device=beff.device)
+    return beffective._Beff2AB.apply(beff, γ2πdt, E1, E2, E1_1,
+                                     torch.is_grad_enabled() and (beff.requires_grad or consts_grad))
+
+
+@_host.half_via_float
+def ab_rfgr(
+    rf: Tensor, gr: Tensor, loc: Tensor, *,
+    Δf: Optional[Tensor] = None, b1Map: Optional[Tensor] = None, γ_beff: Tensor = γH,
+    T1: Optional[Tensor] = None, T2: Optional[Tensor] = None,
+    γ: Tensor = γH, dt: Tensor = dt0, consts: Optional[dict] = None
+):
+    r"""Hargreaves' propagator of the whole pulse per spin, ``M_after = A @ M_before + B``
+    (`doi:10.1002/mrm.1170 <https://doi.org/10.1002/mrm.1170>`_), from ``rf`` and ``gr``: what
+    ``beffective.beff2ab(beffective.rfgr2beff(rf, gr, loc, Δf=Δf, b1Map=b1Map, γ=γ_beff), ...)`` gives -- bit for bit
+    with the same step constants -- without the intermediate ``Beff``.  It is what a loss on the elements of the
+    rotation ``A`` needs (refocusing and inversion pulses), and what a steady state ``(I - A)^-1 B`` is composed from.
+
+    Operands exactly as :func:`blochsim_rfgr` without ``Mi`` (shapes, broadcasting, dtypes, ``consts`` and the
+    precision mode); ``T1 = T2 = None`` is no relaxation: ``A`` is then a pure rotation and ``B`` an exact zero.
+    Returns ``A`` `(N, *Nd, xyz, 3)` and ``B`` `(N, *Nd, xyz)` in the dtype of ``loc``, as ``beffective.beff2ab`` lays
+    them out; :func:`mrphy_amd.slowsims.blochsim_ab` consumes them unchanged.
+
+    With one transmit coil (with or without ``b1Map``) one kernel carries the four columns of ``[I | 0]`` through the
+    pulse: one field and one rotation per step for all four (K2ab).  Gradients w.r.t. ``rf`` and ``gr`` come from a
+    fused adjoint (K2abb) over checkpoints of the four columns every 16 steps -- a quarter of ``Beff``'s bytes, where
+    ``beff2ab``'s own adjoint keeps ``Beff`` and four times as much history -- deterministically: the same inputs give
+    the same bits.  A pulse length that is not a multiple of 16 is split: the whole segments fused, the tail of at most
+    15 steps through ``rfgr2beff`` + ``beff2ab``, joined as ``A = A_tail @ A_head``, ``B = A_tail @ B_head + B_tail``.
+    Parallel transmit, gradients w.r.t. ``loc``, ``Δf``, ``b1Map``, ``γ_beff`` or the constants, and a pulse gradient
+    with fewer than 16 steps compose ``rfgr2beff`` + ``beff2ab`` (HIP kernels as well), whose autograd serves every
+    operand.
+    """
+    from . import beffective, sims
+    _host.require_device_tensor(loc, 'loc')
+    assert (T1 is None) == (T2 is None)
+    kw = dict(Δf=Δf, b1Map=b1Map, γ_beff=γ_beff, T1=T1, T2=T2, γ=γ, dt=dt, consts=consts)
+    lib = _lib.require_library()
+    grad_on = torch.is_grad_enabled()
+    rq = lambda x: grad_on and isinstance(x, Tensor) and x.requires_grad  # noqa: E731
+    maps_grad = any(rq(x) for x in (loc, Δf, b1Map)) or (rq(γ_beff) and Δf is not None)
+    consts_grad = any(rq(x) for x in (consts.values() if consts is not None else (T1, T2, γ, dt)))
+    p = beffective._PulseOnSpins(rf.detach(), gr.detach(), loc.detach(), None if Δf is None else Δf.detach(),
+                                 None if b1Map is None else b1Map.detach(), γ_beff.detach())
+    route, out = _decide_ab_route(
+        nT=p.nT, seg=int(lib.mrphy_blochsim_rfgr_ck_every()),
+        one_coil=p.nC == 1 and (rf.ndim == 3 or b1Map is not None or rf.shape[-1] == 1),
+        pulse_grad=any(rq(x) for x in (rf, gr)), maps_grad=maps_grad, consts_grad=consts_grad)
+    if route == 'split':
+        # whole segments fused, the tail of <= 15 steps composed; the step map of the tail acts on the head's
+        A1, B1 = ab_rfgr(rf[:, :, :out], gr[:, :, :out], loc, **kw)
+        A2, B2 = ab_rfgr(rf[:, :, out:], gr[:, :, out:], loc, **kw)
+        return A2 @ A1, (A2 @ B1[..., None])[..., 0] + B2
+    device, ndim = p.device, 1 + len(p.Nd) + 2
+    if consts is not None:
+        cs = tuple(consts.get(k) for k in _CONSTS)
+    elif consts_grad:
+        # differentiable, as slowsims.blochsim forms them (see _route)
+        cdev = _host.const_device(device)
+        pad = lambda x: None if x is None else _host.pad_trailing(x.to(cdev), ndim)  # noqa: E731
+        cs = sims._gamma_dt_constants(pad(T1), pad(T2), pad(γ), pad(dt))
+    else:
+        cs = sims.relax_constants(T1, T2, γ, dt, ndim, device)
+    if route == 'composed':
+        return _ab_composed(rf, gr, loc, kw, cs, consts_grad)
+    return AbRfGrHIP.apply(rf, gr, p, *cs, out)
