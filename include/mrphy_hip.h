@@ -76,7 +76,8 @@ extern "C" {
  *      coil, which also returns the gradients w.r.t. loc, df and b1); mrphy_blochsim_rfgr_consts_bwd,
  *      mrphy_signal_rfgr_consts_bwd (the same adjoints, which also return the gradients w.r.t. the step constants
  *      g = gamma 2 pi dt, E1, E2, E1m1 per spin); mrphy_ab_rfgr_fwd, mrphy_ab_rfgr_bwd (Hargreaves' A, B of a pulse
- *      from rf and gr without Beff in memory, and the adjoint w.r.t. the pulse). */
+ *      from rf and gr without Beff in memory, and the adjoint w.r.t. the pulse); mrphy_ab_steadystate_fwd,
+ *      mrphy_ab_steadystate_bwd (the steady state of a periodic pulse from A, B and a rest period, and its adjoint). */
 #define MRPHY_ABI_VERSION 5
 
 #define MRPHY_F32      0  /* T = float,  CT = float                                          */
@@ -909,6 +910,48 @@ int mrphy_ab_rfgr_bwd(int dtype,
                       void* work, size_t work_bytes,
                       int64_t N, int64_t nM, int64_t nT,
                       void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Kss  the steady state of a sequence that repeats every period: a rest of duration `rest` -- free precession exactly
+ * as mrphy_freeprec_fwd defines it, M- = F M + f with F = diag(E2r, E2r, E1r) Rz(-2 pi df rest), E1r = exp(-rest/T1),
+ * E2r = exp(-rest/T2), f = (0, 0, -expm1(-rest/T1)) -- then the pulse M_after = A M_before + B (Hargreaves' A, B of
+ * mrphy_ab_rfgr_fwd or mrphy_beff2ab, or any product of them).  The state right after the pulse solves
+ *     (I - A F) Mss = A f + B,
+ * one thread per spin.  A (N,nM,3,3), B (N,nM,3) as mrphy_beff2ab lays them out; Mss (N,nM,3); rest (N|1,) with
+ * element stride rest_sn (0 broadcasts), as `dur` of mrphy_freeprec_fwd; T1, T2, df broadcastable per-spin constants of
+ * the DATA type (MRPHY_F32 or MRPHY_F64, the codes mrphy_freeprec_* accept).  rest == NULL is "no rest period":
+ * F = I, f = 0, Mss = (I - A)^-1 B, and T1, T2, df must then be NULL too; with a rest, T1 and T2 are both given or
+ * neither (no relaxation in the rest), df == NULL is no precession.
+ * Whatever the data type, all arithmetic in the kernel is fp64 (the rest constants, the products, the solve) and the
+ * outputs are rounded once: Mss carries the rounding of A amplified by the condition number of I - A F, about
+ * 1 / (1 - E1r), and the kernel adds nothing to it.  The solve is the cofactor form with one division by the
+ * determinant.  A singular system -- no relaxation in the pulse nor in the rest: det == 0 -- yields non-finite
+ * output; nothing is synchronised with the host to detect it.
+ *
+ * Kssb  its adjoint, for the cotangent grad_Mss (N,nM,3); Mss is recomputed from A, B and the constants:
+ *     lambda = (I - A F)^-T grad_Mss,   M- = F Mss + f,   mu = A^T lambda
+ *     grad_B (N,nM,3) = lambda,   grad_A (N,nM,3,3) = lambda M-^T,
+ *     grad_consts (N,nM,4) = [dL/d rest, dL/d T1, dL/d T2, dL/d df]  (0 where the operand is NULL): the per-spin
+ *     formulas of mrphy_freeprec_bwd_consts at Mi := Mss, grad_Mo := mu; the caller sums each column over the axes its
+ *     operand broadcasts along.
+ * Each of grad_A, grad_B, grad_consts may be NULL, not all three.
+ * Both refuse before anything is launched: MRPHY_EINVAL for an unknown dtype, a negative size, a NULL required
+ * pointer or a breach of the operand rules above; MRPHY_EALIGN for a pointer not aligned to its element size.  An
+ * empty problem (N*nM == 0) is a success that writes nothing, whatever the pointers are.
+ * ------------------------------------------------------------------------------------------- */
+int mrphy_ab_steadystate_fwd(int dtype, const void* A, const void* B,
+                             const void* rest, int64_t rest_sn,
+                             const void* T1, int64_t T1_sn, int64_t T1_sm,
+                             const void* T2, int64_t T2_sn, int64_t T2_sm,
+                             const void* df, int64_t df_sn, int64_t df_sm,
+                             void* Mss, int64_t N, int64_t nM, void* stream);
+int mrphy_ab_steadystate_bwd(int dtype, const void* A, const void* B, const void* grad_Mss,
+                             const void* rest, int64_t rest_sn,
+                             const void* T1, int64_t T1_sn, int64_t T1_sm,
+                             const void* T2, int64_t T2_sn, int64_t T2_sm,
+                             const void* df, int64_t df_sn, int64_t df_sm,
+                             void* grad_A, void* grad_B, void* grad_consts,
+                             int64_t N, int64_t nM, void* stream);
 
 int mrphy_blochsim_ab(int dtype, const void* M, const void* A, const void* B, void* Mo,
                       int64_t rows, void* stream);

@@ -93,6 +93,8 @@ PROTOTYPES = {
     'mrphy_beff2ab_bwd_consts': (_int, [_int, _vp, _vp] + _BC * 3 + [_vp, _vp, _vp, _vp] + [_i64] * 3 + [_vp]),
     'mrphy_ab_rfgr_fwd': (_int, [_int] + _PULSE_OPS + [_vp, _vp, _vp, _i64] + [_i64] * 3 + [_vp]),
     'mrphy_ab_rfgr_bwd': (_int, _FUSED + [_vp, _vp, _vp, _vp, _vp, _sz] + [_i64] * 3 + [_vp]),
+    'mrphy_ab_steadystate_fwd': (_int, [_int, _vp, _vp, _vp, _i64] + _BC * 3 + [_vp, _i64, _i64, _vp]),
+    'mrphy_ab_steadystate_bwd': (_int, [_int, _vp, _vp, _vp, _vp, _i64] + _BC * 3 + [_vp, _vp, _vp, _i64, _i64, _vp]),
     'mrphy_blochsim_ab': (_int, [_int, _vp, _vp, _vp, _vp, _i64, _vp]),
     'mrphy_blochsim_ab_bwd': (_int, [_int, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
@@ -131,6 +133,7 @@ UNITS = [(f, m) for f, masks in (
     ('tu_rfgr2beff_fwd.hip', (_F32, _F64)),
     ('tu_rfgr2beff_bwd.hip', (_F32, _F64)),
     ('tu_aux.hip', (None,)),
+    ('tu_ab_steady.hip', (None,)),
     ('abi.hip', (None,)),
 ) for m in masks]
 

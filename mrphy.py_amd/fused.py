@@ -35,6 +35,11 @@ per-spin records in memory; the coils of a receive array share one simulation pe
 (``beffective.beff2ab`` of ``beffective.rfgr2beff``), from the same operands: the four columns of ``[I | 0]`` share
 each step's field and rotation (K2ab), and the gradients w.r.t. ``rf`` and ``gr`` come from a fused adjoint over the
 four columns' checkpoints (K2abb) -- again without ``Beff``, a history or ``grad_Beff`` in memory.
+
+:func:`ab_steadystate` solves ``(I - A F) Mss = A f + B`` per spin for the magnetisation of a sequence that repeats the
+pulse ``A, B`` after a rest ``F, f`` (``sims.freeprec``), with an adjoint w.r.t. ``A``, ``B`` and the rest's operands
+(Kss / Kssb); :func:`steadystate_rfgr` is that on top of :func:`ab_rfgr`: ``Mss(rf, gr)`` and its gradient in closed
+form instead of hundreds of simulated periods.
 """
 from math import pi as π, prod  # noqa: F401
 from typing import NamedTuple, Optional
@@ -46,7 +51,7 @@ from torch.autograd import Function
 from . import _lib, _host
 from ._consts import γH, dt0
 
-__all__ = ['blochsim_rfgr', 'blochsim_rfgr_traj', 'signal_rfgr', 'ab_rfgr']
+__all__ = ['blochsim_rfgr', 'blochsim_rfgr_traj', 'signal_rfgr', 'ab_rfgr', 'ab_steadystate', 'steadystate_rfgr']
 
 
 def _forward_prep(lib, p, γ2πdt, E1, E2, E1_1, dtype, device, need):
@@ -769,3 +774,143 @@ def ab_rfgr(
     if route == 'composed':
         return _ab_composed(rf, gr, loc, kw, cs, consts_grad)
     return AbRfGrHIP.apply(rf, gr, p, *cs, out)
+
+
+class AbSteadyStateHIP(Function):
+    r"""``Mss = AbSteadyStateHIP.apply(A, B, rest, T1, T2, Δf)`` -- see :func:`ab_steadystate`.  The backward
+    (``mrphy_ab_steadystate_bwd``) recomputes ``Mss`` from the inputs: nothing else is saved."""
+
+    @staticmethod
+    def _operands(A, rest, T1, T2, Δf):
+        r"""``(N, Nd, nM, code, keep, args)``: the arguments ``rest .. df_sm`` of the two entry points and the tensors
+        that keep their pointers alive."""
+        device, dtype = A.device, A.dtype
+        N, Nd = A.shape[0], tuple(A.shape[1:-2])
+        nul = _host.NULL_BC
+        d = None
+        if rest is not None:
+            d = rest.detach().to(device=device, dtype=dtype).reshape(-1).contiguous()
+            assert d.numel() in (1, N), "rest must be () or (N ⊻ 1,)"
+        mk = lambda c: None if c is None else _host.Bcast(c.detach(), N, Nd, dtype, device)  # noqa: E731
+        t1, t2, df = mk(T1), mk(T2), mk(Δf)
+        args = (None if d is None else d.data_ptr(), 1 if (d is not None and d.numel() == N and N > 1) else 0,
+                *(t1.args if t1 else nul), *(t2.args if t2 else nul), *(df.args if df else nul))
+        return N, Nd, prod(Nd), _lib.F64 if dtype == torch.float64 else _lib.F32, (d, t1, t2, df), args
+
+    @staticmethod
+    def forward(ctx, A, B, rest, T1, T2, Δf):
+        lib = _lib.require_library()
+        device = A.device
+        a, b = A.detach().contiguous(), B.detach().contiguous()
+        N, Nd, nM, code, keep, args = AbSteadyStateHIP._operands(a, rest, T1, T2, Δf)
+        Mss = torch.empty_like(b)
+        with torch.cuda.device(device):
+            rc = lib.mrphy_ab_steadystate_fwd(code, a.data_ptr(), b.data_ptr(), *args, Mss.data_ptr(), N, nM,
+                                              _host.current_stream(device))
+        _lib.check(rc, 'mrphy_ab_steadystate_fwd')
+        del keep
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(a, b)
+        ctx.consts = (rest, T1, T2, Δf)
+        return Mss
+
+    @staticmethod
+    def backward(ctx, grad_Mss):
+        from . import sims
+        need = ctx.needs_input_grad
+        consts = ctx.consts
+        need_c = [w and c is not None for w, c in zip(need[2:6], consts)]
+        if grad_Mss is None or not (need[0] or need[1] or any(need_c)):
+            return (None,) * 6
+        lib = _lib.require_library()
+        a, b = ctx.saved_tensors
+        device, dtype = a.device, a.dtype
+        N, Nd, nM, code, keep, args = AbSteadyStateHIP._operands(a, *consts)
+        g = grad_Mss.detach().to(dtype).contiguous()
+        gA = torch.empty_like(a) if need[0] else None
+        gB = torch.empty_like(b) if need[1] else None
+        gC = torch.empty((N,) + Nd + (4,), dtype=dtype, device=device) if any(need_c) else None
+        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        with torch.cuda.device(device):
+            rc = lib.mrphy_ab_steadystate_bwd(code, a.data_ptr(), b.data_ptr(), g.data_ptr(), *args, ptr(gA), ptr(gB),
+                                              ptr(gC), N, nM, _host.current_stream(device))
+        _lib.check(rc, 'mrphy_ab_steadystate_bwd')
+        del keep
+        gcs = tuple(sims._reduce_to_const(gC[..., i], c, N, Nd).to(c.device) if want else None
+                    for i, (c, want) in enumerate(zip(consts, need_c)))
+        return (gA, gB) + gcs
+
+
+@_host.half_via_float
+def ab_steadystate(
+    A: Tensor, B: Tensor, *,
+    rest: Optional[Tensor] = None, T1: Optional[Tensor] = None, T2: Optional[Tensor] = None,
+    Δf: Optional[Tensor] = None
+) -> Tensor:
+    r"""The steady state of a sequence that repeats every period -- a rest of duration ``rest``
+    (``sims.freeprec(M, rest, T1=T1, T2=T2, Δf=Δf)``: ``M⁻ = F M + f``), then the pulse ``M = A M⁻ + B`` -- from
+    Hargreaves' ``A, B`` (:func:`ab_rfgr`, ``beffective.beff2ab``, or a product of several): the solution of
+
+        ``(I - A F) Mss = A f + B``,
+
+    one thread per spin (``mrphy_ab_steadystate_fwd``).  ``Mss`` is the state right AFTER the pulse;
+    ``sims.freeprec(Mss, rest, ...)`` is the one before it.
+
+    Usage:
+        ``Mss = ab_steadystate(A, B, *, rest, T1, T2, Δf)``
+    Inputs:
+        - ``A``: `(N, *Nd, xyz, 3)`, ``B``: `(N, *Nd, xyz)`, as :func:`ab_rfgr` returns them.
+    Optionals (shapes and broadcasting exactly as ``sims.freeprec``):
+        - ``rest``: `()` ⊻ `(N ⊻ 1,)`, "Sec"; ``None`` = no rest period: ``Mss = (I - A)^-1 B`` of whatever period the
+          caller composed (several pulses: ``A2 @ A1``, ``A2 @ B1 + B2``).  ``T1, T2, Δf`` must then be ``None`` too.
+        - ``T1``, ``T2``: `()` ⊻ `(N ⊻ 1, *Nd ⊻ 1,)`, "Sec"; both ``None`` = no relaxation during the rest.
+        - ``Δf``: `(N ⊻ 1, *Nd ⊻ 1,)`, "Hz"; ``None`` = no precession during the rest.
+    Outputs:
+        - ``Mss``: `(N, *Nd, xyz)`.
+
+    Differentiable w.r.t. ``A``, ``B`` and whichever of ``rest, T1, T2, Δf`` require grad
+    (``mrphy_ab_steadystate_bwd``: one transposed 3×3 solve per spin, ``Mss`` recomputed).  The kernels compute in
+    fp64 whatever the data type and round the outputs once; in fp32 ``Mss`` still inherits the rounding of ``A``
+    amplified by the condition number of ``I - A F``, about ``1 / (1 - exp(-rest/T1))``.  A singular system (no
+    relaxation in the pulse nor in the rest) gives non-finite values: nothing synchronises with the host to detect it.
+    """
+    _host.require_device_tensor(A, 'A')
+    _host.require_device_tensor(B, 'B')
+    assert A.dtype == B.dtype and A.device == B.device, "A and B must share dtype and device"
+    assert A.shape[-2:] == (3, 3) and tuple(B.shape) == tuple(A.shape[:-1]), \
+        f"A {tuple(A.shape)} must be (N, *Nd, 3, 3) and B {tuple(B.shape)} (N, *Nd, 3)"
+    assert (T1 is None) == (T2 is None)  # both or neither
+    assert rest is not None or (T1 is None and Δf is None), "T1, T2, Δf describe the rest period: give `rest`"
+    return AbSteadyStateHIP.apply(A, B, rest, T1, T2, Δf)
+
+
+@_host.half_via_float
+def steadystate_rfgr(
+    rf: Tensor, gr: Tensor, loc: Tensor, *,
+    rest: Optional[Tensor] = None, T1: Optional[Tensor] = None, T2: Optional[Tensor] = None,
+    Δf: Optional[Tensor] = None, b1Map: Optional[Tensor] = None, γ_beff: Tensor = γH,
+    γ: Tensor = γH, dt: Tensor = dt0, consts: Optional[dict] = None, Δf_rest: Optional[Tensor] = None
+) -> Tensor:
+    r"""The steady-state magnetisation of a pulse repeated every ``rest + nT·dt`` (bSSFP, SPGR / FLASH, any train of
+    identical excitations), from ``rf`` and ``gr``:
+
+        ``ab_steadystate(*ab_rfgr(rf, gr, loc, ...), rest=rest, T1=T1, T2=T2, Δf=Δf if Δf_rest is None else Δf_rest)``
+
+    -- the closed form of what hundreds of repetitions of ``blochsim_rfgr`` + ``sims.freeprec`` converge to.
+
+    Operands of the pulse exactly as :func:`ab_rfgr`; ``rest`` `()` ⊻ `(N ⊻ 1,)` "Sec", ``T1`` and ``T2`` are required
+    (a steady state needs relaxation).  ``Δf_rest`` `(N ⊻ 1, *Nd ⊻ 1,)` "Hz" lets the rest period precess differently
+    from the pulse: an RF phase increment or an unbalanced gradient moment per period, expressed in Hz; by default the
+    rest precesses with ``Δf``.  Returns ``Mss`` `(N, *Nd, xyz)`: the state right AFTER the pulse;
+    ``sims.freeprec(Mss, rest, T1=T1, T2=T2, Δf=...)`` is the one before it.
+
+    Every route of :func:`ab_rfgr` (fused, split, composed) serves it, so gradients reach every operand ``ab_rfgr``
+    serves, and ``rest, T1, T2, Δf`` / ``Δf_rest`` through the rest period as well.  fp32: the solve itself runs in
+    fp64, but ``Mss`` inherits the rounding of the fp32 ``A`` amplified by the conditioning of ``I - A F``, about
+    ``1 / (1 - exp(-rest/T1))``: relative errors of a few 1e-6 at a factor of 50, 3e-5 at 170 -- for any fp32 route,
+    the reference's operations included.
+    """
+    assert rest is not None and T1 is not None and T2 is not None, \
+        "steadystate_rfgr: a steady state needs relaxation -- `rest`, `T1` and `T2` are required"
+    A, B = ab_rfgr(rf, gr, loc, Δf=Δf, b1Map=b1Map, γ_beff=γ_beff, T1=T1, T2=T2, γ=γ, dt=dt, consts=consts)
+    return ab_steadystate(A, B, rest=rest, T1=T1, T2=T2, Δf=Δf if Δf_rest is None else Δf_rest)
