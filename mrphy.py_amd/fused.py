@@ -394,6 +394,27 @@ class AbRfGrHIP(Function):
         return tuple(g.get(k) for k in ARGS)
 
 
+class _JoinAb(Function):
+    r"""``A, B = _JoinAb.apply(A1, B1, A2, B2)``: the propagator of a head ``(A1, B1)`` followed by a tail ``(A2, B2)``,
+    ``A = A2 @ A1``, ``B = A2 @ B1 + B2`` -- the join of :func:`ab_rfgr`'s split route.  Its backward forms the four
+    3x3 products on CONTIGUOUS copies of the cotangents: left to autograd, the batched products take a cotangent in
+    whatever strides the caller's loss gave it, and a permuted one rounds differently from a contiguous one of the same
+    values (one ulp in fp64) -- the gradients then depended on the spelling of the cotangent."""
+
+    @staticmethod
+    def forward(ctx, A1, B1, A2, B2):
+        ctx.save_for_backward(A1, B1, A2)
+        return A2 @ A1, (A2 @ B1[..., None])[..., 0] + B2
+
+    @staticmethod
+    def backward(ctx, grad_A, grad_B):
+        A1, B1, A2 = ctx.saved_tensors
+        gA, gB = grad_A.contiguous(), grad_B.contiguous()
+        A2t = A2.transpose(-1, -2)
+        return (A2t @ gA, (A2t @ gB[..., None])[..., 0],
+                gA @ A1.transpose(-1, -2) + gB[..., None] * B1[..., None, :], gB)
+
+
 def _decide_ab_route(*, nT, seg, one_coil, pulse_grad, maps_grad, consts_grad):
     r"""The route of :func:`ab_rfgr` as a function of plain facts (``maps_grad``: a gradient w.r.t. ``loc``, ``Δf``,
     ``b1Map`` or a ``γ_beff`` that multiplies a ``Δf``): ``('fused', want_ckpt)`` -- one transmit coil and either no
@@ -736,7 +757,8 @@ def ab_rfgr(
     fused adjoint (K2abb) over checkpoints of the four columns every 16 steps -- a quarter of ``Beff``'s bytes, where
     ``beff2ab``'s own adjoint keeps ``Beff`` and four times as much history -- deterministically: the same inputs give
     the same bits.  A pulse length that is not a multiple of 16 is split: the whole segments fused, the tail of at most
-    15 steps through ``rfgr2beff`` + ``beff2ab``, joined as ``A = A_tail @ A_head``, ``B = A_tail @ B_head + B_tail``.
+    15 steps through ``rfgr2beff`` + ``beff2ab``, joined as ``A = A_tail @ A_head``, ``B = A_tail @ B_head + B_tail``
+    (:class:`_JoinAb`: its adjoint works on contiguous cotangents, so the bits do not depend on the strides of the loss's).
     Parallel transmit, gradients w.r.t. ``loc``, ``Δf``, ``b1Map``, ``γ_beff`` or the constants, and a pulse gradient
     with fewer than 16 steps compose ``rfgr2beff`` + ``beff2ab`` (HIP kernels as well), whose autograd serves every
     operand.
@@ -760,7 +782,7 @@ def ab_rfgr(
         # whole segments fused, the tail of <= 15 steps composed; the step map of the tail acts on the head's
         A1, B1 = ab_rfgr(rf[:, :, :out], gr[:, :, :out], loc, **kw)
         A2, B2 = ab_rfgr(rf[:, :, out:], gr[:, :, out:], loc, **kw)
-        return A2 @ A1, (A2 @ B1[..., None])[..., 0] + B2
+        return _JoinAb.apply(A1, B1, A2, B2)
     device, ndim = p.device, 1 + len(p.Nd) + 2
     if consts is not None:
         cs = tuple(consts.get(k) for k in _CONSTS)

@@ -2,7 +2,14 @@ r"""``fused.ab_rfgr`` without a GPU: the two entry points ``mrphy_ab_rfgr_fwd`` 
 alike and refuse bad arguments before any launch; the routing decision ``fused._decide_ab_route`` row by row; and the
 fixtures ``tests/golden/ab_rfgr_f32.npz`` / ``_f64.npz`` (the live reference's ``rfgr2beff`` -> ``beff2ab`` with its own
 autograd, ``tests/golden/make_golden_ab_rfgr.py``) against the CPU oracle's composition, which the GPU tests use as
-their yardstick beside the fixture."""
+their yardstick beside the fixture.
+
+Two yardsticks for ``A, B`` and their pulse gradients live here.  ``oracle_ab`` / ``oracle_ab_beff2ab``: ``O.rfgr2beff`` ->
+``O.beff2ab`` and autograd, what ``test_ab_rfgr.py`` uses -- right wherever no spin sits at zero field.
+``oracle_ab_columns``: the same ``A, B`` column by column through the EXPLICIT simulator ``O.blochsim``, whose adjoint
+holds the analytic zero-field limit -- what ``test_ab_operands.py`` uses, because its cases have dead time and spins at
+the iso-centre, where autograd through ``F.normalize`` returns an exact 0 for gradients that are O(1)
+(``test_columns_hold_the_zero_field_limit_that_beff2ab_misses``: finite differences decide)."""
 import ctypes
 import os
 import re
@@ -188,3 +195,179 @@ def test_oracle_composition_matches_the_reference_fixture(tag):
     if tag == 'f32':
         # the generator's condition: the reference's own fp32 run is the function to a tenth of the gate
         assert max(float(G[f'distance_f32_vs_f64.{k}']) for k in ('A', 'B', 'grad_rf', 'grad_gr')) <= 1e-6
+
+
+# ---------------------------------------------------------------------------------------------
+# the column yardstick: A, B from the explicit adjoint, which holds the analytic zero-field limit
+# ---------------------------------------------------------------------------------------------
+def _wide(x, dtype=torch.float64):
+    return None if x is None else x.detach().to(dtype)
+
+
+def oracle_ab_columns(v, rf=None, gr=None, dtype=torch.float64):
+    r"""``A, B`` of the operand dict ``v`` (keys as ``cases.fused_operand_variants``: ``rf, gr, loc, Δf, b1Map, γ_beff, T1,
+    T2, γ, dt``, each in any form the simulators take) in fp64 from ``O.rfgr2beff`` and the EXPLICIT simulator:
+    ``B = O.blochsim(0, beff, ...)`` and ``A[..., :, j] = O.blochsim(e_j, beff, ...) - B``, the four columns as four
+    batch entries of one call.  Differentiable w.r.t. ``rf`` and ``gr`` when they are handed over as fp64 leaves.
+
+    This is the yardstick of the GPU tests of ``fused.ab_rfgr`` / ``steadystate_rfgr`` (``test_ab_operands.py``), not
+    ``O.beff2ab``: ``beff2ab`` is differentiated by autograd through ``F.normalize`` and returns an exact 0 for the field
+    gradient of every step at which a spin sits at zero field, where the true value is the limit ``-γ2πdt (m x h̃)`` of
+    ``O.explicit_backward`` (``test_columns_hold_the_zero_field_limit_that_beff2ab_misses``: finite differences side
+    with the columns).  Their VALUES are the same function (``test_column_yardstick_is_beff2ab``: 1e-12).  ``dtype``: the
+    same chain in another precision (fp32: what an all-fp32 evaluation of this very chain loses, the measure of the fp32
+    margins of ``test_ab_operands.py``)."""
+    P = {k: _wide(v.get(k), dtype) for k in ('loc', 'Δf', 'b1Map', 'γ_beff', 'T1', 'T2', 'γ', 'dt')}
+    rf, gr = (_wide(v['rf'], dtype) if rf is None else rf), (_wide(v['gr'], dtype) if gr is None else gr)
+    beff = O.rfgr2beff(rf, gr, P['loc'], Δf=P['Δf'], b1Map=P['b1Map'], γ=P['γ_beff'])
+    lead = tuple(beff.shape[:-2])
+    Mi = torch.zeros((4,) + lead + (3,), dtype=dtype)
+    for j in range(3):
+        Mi[j, ..., j] = 1
+    # the columns as batch entries: whatever runs over the batch is repeated, whatever broadcasts over it stays
+    rep = lambda x: x if x is None or x.ndim == 0 or x.shape[0] == 1 else torch.cat([x] * 4, 0)  # noqa: E731
+    Mo = O.blochsim(Mi.reshape((4 * lead[0],) + lead[1:] + (3,)), torch.cat([beff] * 4, 0), T1=rep(P['T1']),
+                    T2=rep(P['T2']), γ=rep(P['γ']), dt=rep(P['dt']))
+    Mo = Mo.reshape((4,) + lead + (3,))
+    return torch.stack([Mo[j] - Mo[3] for j in range(3)], dim=-1), Mo[3]
+
+
+def oracle_ab_beff2ab(v, rf=None, gr=None):
+    r"""The same ``A, B`` by ``O.rfgr2beff`` -> ``O.beff2ab`` (autograd): the yardstick of ``test_ab_rfgr.py``, right
+    wherever no spin sits at zero field."""
+    P = {k: _wide(v.get(k)) for k in ('loc', 'Δf', 'b1Map', 'γ_beff', 'T1', 'T2', 'γ', 'dt')}
+    rf, gr = (_wide(v['rf']) if rf is None else rf), (_wide(v['gr']) if gr is None else gr)
+    beff = O.rfgr2beff(rf, gr, P['loc'], Δf=P['Δf'], b1Map=P['b1Map'], γ=P['γ_beff'])
+    k = beff.ndim - 2
+    dt = O._rpad(P['dt'], k)
+    one = torch.ones((), dtype=torch.float64)
+    E1, E2 = (one, one) if P['T1'] is None else (torch.exp(-dt / O._rpad(P['T1'], k)), torch.exp(-dt / O._rpad(P['T2'], k)))
+    return O.beff2ab(beff, E1=E1, E2=E2, γ=P['γ'], dt=P['dt'])
+
+
+def ab_weights(v):
+    r"""The cotangents of the operand tests, formed from the case's own ``w``: ``wB = w`` and ``wA = w[..., None] * (0.9,
+    -0.6, 0.4)`` in the FORM of ``w`` -- a ``w`` that starts one element into its buffer gives a ``wA`` that does, a
+    non-contiguous ``w`` a non-contiguous ``wA``."""
+    w = v['w']
+    wA = (w[..., None] * torch.tensor([0.9, -0.6, 0.4], dtype=w.dtype)).contiguous()
+    if w.storage_offset():
+        buf = torch.zeros(wA.numel() + w.storage_offset() + 3, dtype=w.dtype)
+        buf[w.storage_offset():w.storage_offset() + wA.numel()].view(wA.shape).copy_(wA)
+        wA = buf[w.storage_offset():w.storage_offset() + wA.numel()].view(wA.shape)
+    elif not w.is_contiguous():
+        wA = wA.movedim(-1, 0).contiguous().movedim(0, -1)
+    return wA, w
+
+
+def oracle_ab_grads(v, ab=oracle_ab_columns, wA=None, wB=None):
+    r"""``A, B, grad_rf, grad_gr`` of ``(A wA).sum() + (B wB).sum()`` in fp64 through ``ab``; the gradients in the shapes of
+    ``rf`` and ``gr`` as given."""
+    if wA is None:
+        wA, wB = ab_weights(v)
+    rf, gr = _wide(v['rf']).clone().requires_grad_(True), _wide(v['gr']).clone().requires_grad_(True)
+    A, B = ab(v, rf, gr)
+    ((A * _wide(wA)).sum() + (B * _wide(wB)).sum()).backward()
+    return dict(A=A.detach(), B=B.detach(), grad_rf=rf.grad, grad_gr=gr.grad)
+
+
+def oracle_steadystate_columns(v, rest, T1, T2, df, dtype=torch.float64):
+    r"""``Mss, grad_rf, grad_gr`` of ``(Mss w).sum()``: ``test_steadystate_host.torch_steadystate`` on the column
+    yardstick's ``A, B`` of ``v`` (whose ``T1, T2`` the caller has set to those of the rest period), all in ``dtype``.
+    ``T1, T2, df``: broadcastable against the spins ``(N, *Nd)`` from the left, as the simulators take them."""
+    from test_steadystate_host import torch_steadystate
+    rf, gr = _wide(v['rf'], dtype).clone().requires_grad_(True), _wide(v['gr'], dtype).clone().requires_grad_(True)
+    A, B = oracle_ab_columns(v, rf, gr, dtype)
+    k = B.ndim - 1
+    pad = lambda x: None if x is None else O._rpad(_wide(x, dtype), k) if x.ndim else _wide(x, dtype)  # noqa: E731
+    Mss = torch_steadystate(A, B, _wide(rest, dtype), pad(T1), pad(T2), pad(df))
+    (Mss * _wide(v['w'], dtype)).sum().backward()
+    return dict(Mss=Mss.detach(), grad_rf=rf.grad, grad_gr=gr.grad)
+
+
+def zero_field_masks(v):
+    r"""``(live_rf, live_gr)``, boolean `(N, nT)`, read from the case: the pulse samples at which autograd through
+    ``F.normalize`` still gives the right ``grad_rf`` / ``grad_gr`` -- no spin of the batch entry sits at zero field there,
+    except spins whose own factor on that gradient is an exact zero anyway (``b1Map = 0`` for ``rf``; ``loc = 0`` for
+    ``gr``: the iso-centre spins on the pure-``gr`` samples of ``ZERO_RF_ONLY``)."""
+    beff = O.rfgr2beff(_wide(v['rf']), _wide(v['gr']), _wide(v['loc']), Δf=_wide(v['Δf']), b1Map=_wide(v['b1Map']),
+                       γ=_wide(v['γ_beff']))
+    dead = (beff == 0).all(dim=-1)                                               # (N, nM, nT)
+    loc0 = (_wide(v['loc']) == 0).all(dim=-1)[..., None]
+    b10 = torch.zeros_like(loc0) if v['b1Map'] is None else (_wide(v['b1Map']).reshape(loc0.shape[:2] + (-1,)) == 0).all(-1)[..., None]
+    return ~(dead & ~b10).any(dim=1), ~(dead & ~loc0).any(dim=1)
+
+
+ZERO_FIELD_CASES = [(nC, nT) for nC in (0, 1) for nT in (48, 53)]
+FD_SAMPLES = ((0, 2), (1, 15), (0, 17), (1, 46)) + ((1, 20), (1, 29))   # four inside ZERO_STEPS, two inside ZERO_SEGMENT
+
+
+def _zero_case(nC, nT):
+    import cases
+    v, zero = cases.zero_field_case(torch.float64, nC, nT)
+    gen = torch.Generator().manual_seed(4000 + 10 * nC + nT)
+    N, nM = v['loc'].shape[:2]
+    wA = torch.rand((N, nM, 3, 3), generator=gen, dtype=torch.float64) * 2 - 1
+    wB = torch.rand((N, nM, 3), generator=gen, dtype=torch.float64) * 2 - 1
+    return cases, v, zero, wA, wB
+
+
+@pytest.mark.parametrize('nC,nT', ZERO_FIELD_CASES)
+def test_column_yardstick_is_beff2ab(nC, nT):
+    r"""On the zero-field case: ``A, B`` of the two yardsticks to 1e-12, and the gradients of a seeded ``(A wA).sum() + (B
+    wB).sum()`` to 1e-9 on every pulse sample the case leaves live (:func:`zero_field_masks`)."""
+    cases, v, zero, wA, wB = _zero_case(nC, nT)
+    col, b2a = oracle_ab_grads(v, oracle_ab_columns, wA, wB), oracle_ab_grads(v, oracle_ab_beff2ab, wA, wB)
+    for k in ('A', 'B'):
+        assert float((col[k] - b2a[k]).abs().max()) <= 1e-12, k
+    live_rf, live_gr = zero_field_masks(v)
+    # the masks are the case's: dead time takes both out, the pure-gr samples only grad_rf -- and not even that in batch
+    # entry 1 with a map, whose one iso-centre spin has b1Map = 0
+    rf_only = torch.zeros_like(zero)
+    rf_only[:1 if nC else 2, list(cases.ZERO_RF_ONLY)] = True
+    assert torch.equal(live_gr, ~zero) and torch.equal(live_rf, ~zero & ~rf_only)
+    assert int(live_rf.sum()) >= 40 and int(live_gr.sum()) > int(live_rf.sum())
+    for k, live in (('grad_rf', live_rf), ('grad_gr', live_gr)):
+        a, b = col[k].movedim(2, 1)[live], b2a[k].movedim(2, 1)[live]
+        assert float(a.abs().max()) > 0.1
+        assert float((a - b).abs().max()) <= 1e-9, k
+
+
+@pytest.mark.parametrize('nC,nT', ZERO_FIELD_CASES)
+def test_columns_hold_the_zero_field_limit_that_beff2ab_misses(nC, nT):
+    r"""Central finite differences in fp64 (h = 1e-4 G, G/cm: the loss is smooth in ``γ2πdt b``, 0.1 rad per Gauss, so the
+    truncation error is O(1e-11) and the rounding error O(1e-10)) on the five components of six dead pulse samples: within
+    1e-6 relative of the column yardstick; ``O.beff2ab``'s autograd holds an exact zero there -- a distance of 1.
+
+    Dry run (nC = 0 / 1; nT = 48, 53): over the dead samples the columns' ``grad_rf`` reaches 1.4, 3.2 / 1.1, 2.0 and
+    ``grad_gr`` 7.9, 9.3 / 2.2, 9.8 in max abs where ``beff2ab`` gives 0; over the whole gradients the two yardsticks are
+    0.43 .. 0.78 apart in relative L2.  A kernel held to ``beff2ab`` there would have to return zeros, more than 4e4 fp32
+    gates (1e9 fp64 gates) away from the truth."""
+    cases, v, zero, wA, wB = _zero_case(nC, nT)
+    col, b2a = oracle_ab_grads(v, oracle_ab_columns, wA, wB), oracle_ab_grads(v, oracle_ab_beff2ab, wA, wB)
+    h = 1e-4
+
+    def loss(rf, gr):
+        with torch.no_grad():
+            A, B = oracle_ab_columns(v, rf, gr)
+            return float((A * wA).sum() + (B * wB).sum())
+
+    for n, t_ in FD_SAMPLES:
+        assert bool(zero[n, t_]) and (t_ in cases.ZERO_STEPS or (n == 1 and t_ in cases.ZERO_SEGMENT))
+        fd = []
+        for name, ncomp in (('rf', 2), ('gr', 3)):
+            for c in range(ncomp):
+                x = {k: _wide(v[k]).clone() for k in ('rf', 'gr')}
+                x[name][n, c, t_] = h
+                up = loss(x['rf'], x['gr'])
+                x[name][n, c, t_] = -h
+                fd.append((up - loss(x['rf'], x['gr'])) / (2 * h))
+        fd = torch.tensor(fd, dtype=torch.float64)
+        want = torch.cat((col['grad_rf'][n, :, t_], col['grad_gr'][n, :, t_]))
+        auto = torch.cat((b2a['grad_rf'][n, :, t_], b2a['grad_gr'][n, :, t_]))
+        assert float(fd.norm()) > 0.1, (n, t_)
+        assert float((fd - want).norm() / fd.norm()) <= 1e-6, (n, t_, fd, want)
+        assert float(auto.abs().max()) == 0.0 and float((fd - auto).norm() / fd.norm()) > 0.5, (n, t_, auto)
+    dead = zero
+    assert float(b2a['grad_rf'].movedim(2, 1)[dead].abs().max()) == 0.0 == float(b2a['grad_gr'].movedim(2, 1)[dead].abs().max())
+    assert float(col['grad_rf'].movedim(2, 1)[dead].abs().max()) > 0.1 < float(col['grad_gr'].movedim(2, 1)[dead].abs().max())

@@ -1,5 +1,7 @@
 r"""``mrphy_blochsim_rfgr_consts_bwd`` and ``mrphy_signal_rfgr_consts_bwd`` on the host: what the ABI answers before any launch
-(the pointers are fake and never dereferenced), the bindings, the build's unit list.  No GPU needed."""
+(the pointers are fake and never dereferenced), the bindings, the build's unit list; and the two forms of the CPU oracle
+as yardsticks of the fused adjoints on every operand form and at zero field (``oracle_fused``,
+``test_slow_oracle_at_zero_field``), which ``test_fused_grads_operands.py`` rests on.  No GPU needed."""
 import os
 
 import pytest
@@ -118,3 +120,104 @@ def test_consts_entry_points_reject_bad_arguments_on_the_host(dtype):
     assert _sig(dtype, gMo=None, work_bytes=need - 1) == ENOSPC
     assert _sig(dtype, gsig=None, gC=None, work_bytes=need - 1) == ENOSPC
     assert _sig(dtype, Mck=None, work_bytes=need - 1) == EINVAL
+
+
+# ---------------------------------------------------------------------------------------------
+# the two oracle forms as yardsticks of the fused adjoints on the operand zoo and at zero field
+# ---------------------------------------------------------------------------------------------
+FIELD_LEAVES = ('M0', 'rf', 'gr', 'loc', 'Δf', 'b1Map')            # the explicit oracle differentiates these
+CONST_LEAVES = ('T1', 'T2', 'γ', 'dt', 'γ_beff')                   # only the slow (autograd) form differentiates these
+
+
+def oracle_fused(v, sim, needs, ends=None, cot=None):
+    r"""The fp64 CPU oracle of the fused simulators on an operand dict ``v`` (``cases.fused_operand_variants`` /
+    ``zero_field_case``), every operand in the form it is given in and those named in ``needs`` as leaves of that form:
+    ``{'out': trajectory (N, *Nd, nRec, 3), <name>: gradient}`` of ``<cot, out>`` (``cot`` defaults to ``w`` on the one
+    record ``ends = [nT]``).
+
+    ``sim = 'explicit'``: ``O.rfgr2beff`` + ``O.blochsim``, whose adjoint holds the analytic zero-field limit -- the
+    yardstick for ``Mi, rf, gr, loc, Δf, b1Map``.  ``sim = 'slow'``: ``O.blochsim_slow`` and autograd, the only form that
+    differentiates ``T1, T2, γ, dt`` -- take nothing but those from it where a step has zero field
+    (``test_slow_oracle_at_zero_field``).  It relaxes its input in place when a segment's first step has no field
+    anywhere, so every segment gets a fresh non-leaf copy; and it forms ``exp(-dt / T1)`` before any padding, so a batch
+    ``dt`` is padded to ``(N, 1, ...)`` here."""
+    import torch
+    import bloch_oracle as O
+    wide = lambda x: None if x is None else x.detach().double()  # noqa: E731
+    Q = {k: wide(v.get(k)) for k in FIELD_LEAVES + CONST_LEAVES}
+    for k in needs:
+        if Q[k] is not None:
+            Q[k] = Q[k].clone().requires_grad_(True)
+    beff = O.rfgr2beff(Q['rf'], Q['gr'], Q['loc'], Δf=Q['Δf'], b1Map=Q['b1Map'], γ=Q['γ_beff'])
+    nT, k = beff.shape[-2], beff.ndim - 2
+    ends = [nT] if ends is None else list(ends)
+    dt = Q['dt'] if Q['dt'].ndim == 0 else Q['dt'].reshape(tuple(Q['dt'].shape) + (k - Q['dt'].ndim) * (1,))
+    step = O.blochsim if sim == 'explicit' else O.blochsim_slow
+    recs, M, t0 = [], Q['M0'], 0
+    for e in ends:
+        M = step(M.clone(), beff[..., t0:e, :], T1=Q['T1'], T2=Q['T2'], γ=Q['γ'], dt=dt)
+        recs.append(M)
+        t0 = e
+    out = torch.stack(recs, dim=-2)
+    cot = wide(v['w']).unsqueeze(-2) if cot is None else wide(cot)
+    (out * cot).sum().backward()
+    res = {k: Q[k].grad for k in needs if Q[k] is not None}
+    res['out'] = out.detach()
+    return res
+
+
+def zero_field_maps_case(dtype, nC, nT):
+    r"""``cases.zero_field_case`` with ``Δf`` an exact-zero `(N, nM)` map: a leaf beside which the field is still zero."""
+    import torch
+    import cases
+    v, zero = cases.zero_field_case(dtype, nC, nT)
+    v['Δf'] = torch.zeros(v['loc'].shape[:2], dtype=dtype)
+    return v, zero
+
+
+@pytest.mark.parametrize('nC', [0, 1])
+@pytest.mark.parametrize('nT', [48, 53])
+def test_slow_oracle_at_zero_field(nC, nT):
+    r"""What the GPU tests of the fused adjoints at zero field rest on (``test_fused_grads_operands.py``), pinned so that a
+    change of the oracle cannot move their yardstick unseen:
+
+    * ``O.blochsim_slow``'s gradients w.r.t. ``T1, T2, γ, dt`` on the exact-zero case are those of the same case with every
+      zero field component replaced by 1e-9 G, to 1e-6 relative (measured: <= 8.6e-9, the size of the perturbation: nothing
+      of the constants' gradients hangs on the branch autograd takes at ``|B| = 0``; a wrong branch would be O(1));
+    * its gradients w.r.t. ``loc``, ``Δf`` (and ``b1Map``) are NOT the explicit adjoint's there: relative L2 (nC = 0 / 1)
+      0.014 / 0.024 at nT = 48 and 0.099 / 0.082 at 53 (``loc``), 0.42 .. 0.46 (``Δf``), 0.035 and 0.013 (``b1Map``, nT =
+      48 and 53) -- more than 1e3 times the fp32 gate 1e-5,
+      so a kernel that returned the autograd zeros on those steps would miss the explicit yardstick by that much;
+    * it raises on a leaf ``Mi`` when the first step has zero field everywhere (in-place relaxation of its input)."""
+    import torch
+    import bloch_oracle as O
+    from util import rel_l2
+    v, zero = zero_field_maps_case(torch.float64, nC, nT)
+    assert bool(zero[:, 0].all())
+    consts = ('T1', 'T2', 'γ', 'dt')
+    slow = oracle_fused(v, 'slow', consts + ('loc', 'Δf', 'b1Map'))
+    expl = oracle_fused(v, 'explicit', ('loc', 'Δf', 'b1Map'))
+    assert float((slow['out'] - expl['out']).abs().max()) <= 1e-12
+
+    # (a) the constants' gradients do not hang on the zero-field branch
+    wide = lambda x: None if x is None else x.detach().double()  # noqa: E731
+    Q = {k: wide(v[k]).clone().requires_grad_(k in consts) for k in consts}
+    beff = O.rfgr2beff(wide(v['rf']), wide(v['gr']), wide(v['loc']), Δf=wide(v['Δf']), b1Map=wide(v['b1Map']),
+                       γ=wide(v['γ_beff']))
+    assert int((beff == 0).sum()) > 3 * 2 * len(zero[0].nonzero())
+    beff = torch.where(beff == 0, torch.full_like(beff, 1e-9), beff)
+    Mo = O.blochsim_slow(wide(v['M0']).clone(), beff, **Q)
+    (Mo * wide(v['w'])).sum().backward()
+    for k in consts:
+        assert float(slow[k].abs().max()) > 0
+        assert rel_l2(slow[k], Q[k].grad) <= 1e-6, (k, rel_l2(slow[k], Q[k].grad))
+
+    # (b) its field gradients are wrong there
+    seen = {k: rel_l2(slow[k], expl[k]) for k in ('loc', 'Δf') + (('b1Map',) if nC else ())}
+    assert all(d > 1e3 * 1e-5 for d in seen.values()), seen
+
+    # (c) the in-place relaxation
+    Mi = wide(v['M0']).clone().requires_grad_(True)
+    with pytest.raises(RuntimeError, match='in-place'):
+        O.blochsim_slow(Mi, beff * 0, T1=wide(v['T1']), T2=wide(v['T2']), γ=wide(v['γ']), dt=wide(v['dt']))
+    O.blochsim_slow(Mi + 0, beff * 0, T1=wide(v['T1']), T2=wide(v['T2']), γ=wide(v['γ']), dt=wide(v['dt']))
