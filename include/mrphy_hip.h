@@ -417,7 +417,8 @@ int mrphy_freeprec_bwd_consts(int dtype, const void* Mi, const void* grad_Mo,
  * only): lo[j] = index of the left neighbour in the ZERO-PREPENDED source (mobjs.py:204-207; 0 means
  * the prepended sample), w[j] = t_new[j] - t[lo[j]], dx[j] = t[lo[j]+1] - t[lo[j]], fp64.
  * dir > 0: out = interp(y).  dir <= 0: the adjoint, `y` = grad wrt the resampled pulse (nch x nTn),
- * `out` = grad wrt the source (nch x nTo).
+ * `out` = grad wrt the source (nch x nTo).  An empty result (nTn == 0: dt_new longer than the whole
+ * pulse) has a zero adjoint: `out` is zeroed, `y` and the grid may then be NULL (here and in _select).
  * ------------------------------------------------------------------------------------------- */
 int mrphy_pulse_interp_linear(int dtype, int dir, const void* y, void* out,
                               const void* lo, const void* w, const void* dx,

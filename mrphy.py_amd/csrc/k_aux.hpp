@@ -234,8 +234,9 @@ __global__ __launch_bounds__(256) void k_uphirot(const T* U, const T* Phi, const
 // Adjoints of the two helpers (the reference gets them from autograd over plain torch ops,
 // beffective.py:35-36, utils.py:351-357).
 //   beff2uphi: n = |b|, d = max(n, eps), U = b/d, Phi = -n g
-//     n > eps : gb = gU/n - b (b.gU)/n^3 - gPhi g b/n        (F.normalize + norm backward)
-//     n <= eps: gb = gU/eps - gPhi g b/n   (clamp_min cuts the U branch from the norm; the Phi
+//     n >= eps: gb = gU/n - b (b.gU)/n^3 - gPhi g b/n        (F.normalize + norm backward; the tie
+//                                            n == eps goes here: clamp_min's backward passes `>=`)
+//     n < eps : gb = gU/eps - gPhi g b/n   (clamp_min cuts the U branch from the norm; the Phi
 //                                            branch stays; at n = 0 torch's norm backward gives 0)
 //     gg (per spin, optional) = -gPhi n
 template <typename T, typename CT>
@@ -250,7 +251,7 @@ __global__ __launch_bounds__(256) void k_beff2uphi_bwd(const T* b, Bc g, const T
     const T nrm = sqrt_(x * x + y * y + z * z);
     const CT gam = bc_load<CT>(g, r / nM, r % nM);
     T ox, oy, oz;
-    if (nrm > T(1e-12)) {
+    if (nrm >= T(1e-12)) {
         const T rn = T(1) / nrm;
         const T bu = (x * ux + y * uy + z * uz) * rn * rn;          // (b.gU)/n^2
         const T kp = T(CT(gp) * gam);
@@ -259,7 +260,7 @@ __global__ __launch_bounds__(256) void k_beff2uphi_bwd(const T* b, Bc g, const T
         oz = (uz - z * bu - kp * z) * rn;
     } else {
         ox = ux * T(1e12); oy = uy * T(1e12); oz = uz * T(1e12);
-        if (nrm > T(0)) {                   // 0 < n <= eps: the clamp cuts the U branch only; torch's
+        if (nrm > T(0)) {                   // 0 < n < eps: the clamp cuts the U branch only; torch's
             const T kp = T(CT(gp) * gam) / nrm;          // norm backward still passes -gPhi g b/n
             ox -= kp * x; oy -= kp * y; oz -= kp * z;
         }

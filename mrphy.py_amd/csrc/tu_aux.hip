@@ -77,7 +77,9 @@ int mrphy_pulse_interp_linear(int dtype, int dir, const void* y, void* out, cons
     if ((dtype != MRPHY_F32 && dtype != MRPHY_F64) || nch < 0 || nTo < 0 || nTn < 0)
         return MRPHY_EINVAL;
     if (nch == 0 || (dir > 0 && nTn == 0) || (dir <= 0 && nTo == 0)) return 0;
-    if (!y || !out || (nTn > 0 && (!lo || !w || !dx))) return MRPHY_EINVAL;
+    // the adjoint of an empty result (nTn == 0: a dwell time longer than the pulse) is a zero gradient: the kernel
+    // finds no contribution and reads neither the (null) cotangent nor the (null) grid
+    if (!out || (nTn > 0 && (!y || !lo || !w || !dx)) || (dir > 0 && !y)) return MRPHY_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     if (dir > 0) {
         const dim3 grid((unsigned)((nTn + 255) / 256), (unsigned)nch);
@@ -112,7 +114,8 @@ int mrphy_pulse_interp_select(int dtype, int dir, const void* y, void* out, cons
         return MRPHY_EINVAL;
     if (nch == 0 || (dir > 0 && nTn == 0) || (dir <= 0 && nTo == 0)) return 0;
     if (nch > 65535) return MRPHY_EINVAL;
-    if (!y || !out || (nTn > 0 && !sel)) return MRPHY_EINVAL;
+    // nTn == 0 in the adjoint direction: a zero gradient, from a null cotangent and a null index (as for 'linear')
+    if (!out || (nTn > 0 && (!y || !sel)) || (dir > 0 && !y)) return MRPHY_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const int64_t npts = dir > 0 ? nTn : nTo;
     const dim3 grid((unsigned)((npts + 255) / 256), (unsigned)nch);

@@ -64,6 +64,19 @@ def _as_index(m: Union[Tensor, MaskIndex]) -> MaskIndex:
     return m if isinstance(m, MaskIndex) else MaskIndex(m)
 
 
+def _require_word_payload(x: Tensor, name: str):
+    r"""The gather moves raw 4- and 8-byte words (``k_mask_extract``): any dtype of that element size on the device
+    -- float32 / float64, int32 / int64, complex64 -- and nothing else."""
+    if not isinstance(x, Tensor):
+        raise TypeError(f"mrphy_amd: `{name}` must be a torch.Tensor")
+    if x.element_size() not in (4, 8):
+        raise RuntimeError(f"mrphy_amd: `{name}` has dtype {x.dtype} with element size {x.element_size()} bytes; "
+                           "the mask kernels move elements of 4 or 8 bytes")
+    if x.device.type != 'cuda':
+        raise RuntimeError(f"mrphy_amd: `{name}` is on {x.device}; this package only runs HIP kernels on a "
+                           "ROCm device tensor ('cuda:N'). There is no CPU fallback.")
+
+
 def _launch_extract(v: Tensor, ix: MaskIndex, out_: Tensor, N: int, K: int):
     lib = _lib.require_library()
     with torch.cuda.device(v.device):
@@ -127,14 +140,15 @@ def extract(v: Tensor, mask: Union[Tensor, MaskIndex], *, out_: Optional[Tensor]
     r"""``SpinArray.extract`` (``mobjs.py:532-553``): keep the voxels of the mask, compactly.
 
     Inputs:
-        - ``v``: `(N, *Nd, ...)`;
+        - ``v``: `(N, *Nd, ...)`, any dtype of 4 or 8 bytes per element (elements move as raw words; a 2-byte
+          dtype raises ``RuntimeError``);
         - ``mask``: `(1, *Nd)` bool, or the :class:`MaskIndex` made from it (reuse it).
     Optionals:
         - ``out_``: `(N, nM, ...)`, in-place holder, must be contiguous.
     Outputs:
         - ``out_``: `(N, nM, ...)`.
     """
-    _host.require_device_tensor(v, 'v')
+    _require_word_payload(v, 'v')
     ix = _as_index(mask)
     nd = len(ix.Nd)
     assert tuple(v.shape[1:1 + nd]) == ix.Nd, \

@@ -73,9 +73,17 @@ def uϕrot(U: Tensor, Φ: Tensor, Vi: Tensor) -> Tensor:
 
     Differentiable w.r.t. ``U``, ``Φ`` and ``Vi`` (explicit adjoint kernel), like the reference's
     plain torch expression.
+
+    ``U`` and ``Φ`` broadcast over the leading shape of ``Vi`` as in the reference (``U.expand_as(Vi)``,
+    ``utils.py:351-357``): a ``U`` `(1, *Nd, xyz)` turns every batch entry of ``Vi`` `(N, *Nd, xyz, (nV))`, and its
+    gradient is summed over the batch.  A leading shape that does not broadcast to ``Vi``'s raises ``RuntimeError``.
     """
     _host.require_device_tensor(U, 'U')
     _host.require_device_tensor(Vi, 'Vi')
     has_nv = Vi.ndim == U.ndim + 1
-    assert has_nv or Vi.shape == U.shape
+    assert has_nv or Vi.ndim == U.ndim
+    lead = tuple(Vi.shape[:U.ndim - 1])
+    if tuple(U.shape[:-1]) != lead:     # a stride-0 view: _UPhiRot materialises it, autograd sums its gradient back
+        U = U.expand(lead + (3,))
+    assert Vi.shape[U.ndim - 1] == 3 and U.shape[-1] == 3
     return _UPhiRot.apply(U, Φ, Vi)

@@ -350,3 +350,134 @@ def zero_field_case(dtype, nC: int, nT: int = 48, seed: int = 31):
              T1=0.5 + u(N, nM), T2=0.02 + 0.1 * u(N, nM), γ=tensor(γH_val), dt=tensor([dt0_val]),
              w=u(N, nM, 3) * 2 - 1)
     return {k: (None if x is None else x.to(dtype)) for k, x in d.items()}, zero
+
+
+# ---------------------------------------------------------------------------------------------
+# The elementwise helpers (csrc/k_aux.hpp, the 1-step kernel): leading shapes that cross a 256-thread block, the
+# spellings of one per-spin constant, special rows of beff2uϕ (tests/test_helpers_operands.py, test_helpers_host.py)
+# ---------------------------------------------------------------------------------------------
+HELPER_BLOCK = 256                    # every helper kernel: row = blockIdx.x * 256 + threadIdx.x
+HELPER_CUBE = (5, 4, 7)
+
+
+def helper_rows():
+    r"""The leading shapes ``(N, *Nd)`` every helper test runs at, the smallest that cross a 256-thread block: one row
+    short of a block, a block, one row more; 513 rows in three batch entries of 171, where blocks straddle batch entries
+    and per-batch operands differ; a cube of two batch entries (280 rows)."""
+    return ((1, 255), (1, 256), (1, 257), (3, 171), (2,) + HELPER_CUBE)
+
+
+def helper_constant_forms(N: int, Nd: tuple, dtype, fn=None, seed: int = 41):
+    r"""``{name: tensor}``: the spellings of ONE per-spin constant over spins ``(N, *Nd)``, as in
+    :func:`fused_operand_variants` -- 0-dim, all-singleton, per batch entry, per spin of one entry, per spin, a stride-0
+    ``.expand``, the transpose of its stored transpose, one element into a larger buffer, fp64 whatever ``dtype``; on
+    a cube (``len(Nd) == 3``) also one value per plane, one per in-plane position, and one map for the whole batch.
+    The stored numbers are ``fn(u)`` of uniform ``u`` in [0, 1) (fp64, the same ``u`` for the same ``seed`` whatever
+    ``fn``: two constants that must share a form, E1 and E1 - 1, are two calls), cast to ``dtype``.  CPU tensors; a
+    view keeps its strides and offset on the device through ``tests/gpu_common.py: place``."""
+    gen = torch.Generator(device='cpu').manual_seed(seed + 1000 * N + len(Nd))
+    fn = fn or (lambda u: u)
+    raw = lambda *s: fn(torch.rand(s, generator=gen, dtype=torch.float64))      # noqa: E731
+    mk = lambda *s: raw(*s).to(dtype)                                            # noqa: E731
+    Nd = tuple(Nd)
+    one = (1,) * len(Nd)
+    nM = 1
+    for d in Nd:
+        nM *= d
+    v = {'scalar': mk().reshape(()), 'one_one': mk(1, *one), 'per_batch': mk(N, *one), 'per_spin_of_one': mk(1, *Nd),
+         'per_spin': mk(N, *Nd), 'expanded': mk(N, *one).expand(N, *Nd), 'after': _after(mk(N, *Nd)),
+         'f64': raw(N, *Nd)}
+    if len(Nd) == 1:
+        v['transposed'] = mk(nM, N).t()
+    else:
+        assert len(Nd) == 3
+        v['planes'] = mk(N, Nd[0], 1, 1)
+        v['in_plane'] = mk(1, 1, Nd[1], Nd[2])
+        v['planes_expanded'] = mk(N, Nd[0], 1, 1).expand(N, *Nd)      # no flat view exists: the host layer copies it
+    return v
+
+
+def helper_dense(c, N: int, Nd: tuple):
+    r"""A constant form over ``(N, *Nd)``, fp64, contiguous: the numbers it holds, for the oracle."""
+    Nd = tuple(Nd)
+    x = c.double()
+    x = x.reshape(tuple(x.shape) + (1 + len(Nd) - x.ndim) * (1,))
+    return x.expand((N,) + Nd).contiguous()
+
+
+BEFF_EPS = 1e-12                      # F.normalize's eps (reference beffective.py:35)
+HELPER_SPECIAL = ('zero', 'below', 'tie', 'above', 'plain')
+
+
+def beff_special_row(kind: str, dtype):
+    r"""One field vector of each kind around the clamp of ``beff2uϕ``: exact zero; |b| = 3e-13 (inside the clamp, not
+    zero); |b| = 1e-12 EXACTLY as ``dtype`` holds it, along x so that ``sqrt(x*x + 0 + 0)`` returns it whether or not the
+    sum is contracted; |b| = 2e-12 (just outside); an ordinary vector."""
+    row = {'zero': [0., 0., 0.], 'below': [1.8e-13, 0., -2.4e-13], 'tie': [BEFF_EPS, 0., 0.],
+           'above': [0., -1.2e-12, 1.6e-12], 'plain': [3., -4., 12.]}[kind]
+    return tensor(row, dtype=torch.float64).to(dtype)
+
+
+def helper_special_positions(rows: int):
+    r"""Flat row numbers that get a special row: the first, the last of block 0, the first of block 1, the last."""
+    return tuple(sorted({p for p in (0, HELPER_BLOCK - 1, HELPER_BLOCK, rows - 1) if 0 <= p < rows}))
+
+
+def plant_special_rows(b, shift: int = 0):
+    r"""``b`` `(N, *Nd, xyz)` with :func:`beff_special_row` s written (in place, through a flat view of a contiguous
+    ``b``) at :func:`helper_special_positions`, the kinds rotated by ``shift``; returns ``{flat row: kind}``."""
+    flat = b.view(-1, 3)
+    out = {}
+    for i, p in enumerate(helper_special_positions(flat.shape[0])):
+        kind = HELPER_SPECIAL[(i + shift) % len(HELPER_SPECIAL)]
+        flat[p] = beff_special_row(kind, b.dtype)
+        out[p] = kind
+    return out
+
+
+def beff2uphi_grad_closed(b, g, gU, gΦ, dtype):
+    r"""Closed form of the adjoint of ``beff2uϕ`` in fp64, per row: ``b, gU`` `(rows, 3)`, ``g, gΦ`` `(rows,)`, the very
+    numbers a ``dtype`` run reads (cast up by the caller).  With ``n = |b|`` and ``eps`` = 1e-12 AS ``dtype`` HOLDS IT --
+    ``F.normalize`` clamps in the data type, and so does the kernel --
+
+        n >= eps:  gb = gU/n - b (b·gU)/n³ - gΦ g b/n      (the tie included: ``clamp_min``'s backward passes ``>=``)
+        0 < n < eps:  gb = gU/eps - gΦ g b/n               (the clamp cuts the U branch off the norm)
+        n == 0:    gb = gU/eps                             (torch's norm backward is 0 at 0)
+
+    and ``gg = -gΦ n`` per row.  ``n`` is compared as ``dtype`` computes it.  Pinned against torch's autograd through
+    ``oracle/bloch_oracle.py: beff2uphi`` in ``tests/test_helpers_host.py``."""
+    f64 = torch.float64
+    eps_t = tensor(BEFF_EPS, dtype=dtype)
+    bt = b.to(dtype)
+    n_t = torch.sqrt(bt[:, 0] * bt[:, 0] + bt[:, 1] * bt[:, 1] + bt[:, 2] * bt[:, 2])
+    b, g, gU, gΦ = b.to(f64), g.to(f64), gU.to(f64), gΦ.to(f64)
+    n = b.norm(dim=-1)
+    eps = float(eps_t.double())
+    free = (n_t >= eps_t)
+    safe = torch.where(n > 0, n, torch.ones_like(n))
+    phi_term = torch.where((n > 0)[:, None], -(gΦ * g / safe)[:, None] * b, torch.zeros_like(b))
+    g_free = gU / safe[:, None] - b * ((b * gU).sum(-1) / safe ** 3)[:, None] + phi_term
+    g_clamped = gU / eps + phi_term
+    return torch.where(free[:, None], g_free, g_clamped), -gΦ * n
+
+
+def helper_mask(Nd: tuple):
+    r"""A closed-form `(1, *Nd)` bool mask of any rank, about 3/5 of the voxels, first and last voxel included."""
+    n = 1
+    for d in Nd:
+        n *= d
+    k = torch.arange(n, dtype=torch.int64)
+    m = ((k * k + 3 * k) % 5) != 3
+    m[0] = m[-1] = True
+    return m.reshape((1,) + tuple(Nd))
+
+
+# nT, dt -> dt_new, new samples (counted on the CPU; tests/test_helpers_host.py asserts them), what the grid stresses
+INTERP_GRIDS = (
+    (257, 4e-6, 1.5e-6, 685),      # both sides cross 256; up to 3 outputs per source interval
+    (300, 4e-6, 1.3e-5, 92),       # 208 source samples feed no interval's upper end
+    (600, 4e-6, 8e-6, 299),        # every w == dx: weights exactly 1 and exactly 0
+    (513, 2e-6, 7e-6, 146),
+    (1, 4e-6, 1e-6, 4),
+    (3, 4e-6, 2e-5, 0),            # a dwell time longer than the pulse: an empty result
+)

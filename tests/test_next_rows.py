@@ -323,7 +323,10 @@ def test_interpT_select_kinds_vs_scipy(kind, tag):
     from mrphy_amd import interp
     dt_ = DT[tag]
     g = torch.Generator().manual_seed(31)
-    for nT, dt_o, dt_n, nC in ((96, 8e-6, 4e-6, None), (130, 4e-6, 1.3e-5, 3), (64, 4e-6, 4e-6 * 0.37, None)):
+    # (the last three: both sides past one 256-thread block, 208 source samples that no output selects from above,
+    # and a dwell time longer than the pulse -- an empty result, whose adjoint is a zero gradient)
+    for nT, dt_o, dt_n, nC in ((96, 8e-6, 4e-6, None), (130, 4e-6, 1.3e-5, 3), (64, 4e-6, 4e-6 * 0.37, None),
+                               (257, 4e-6, 1.5e-6, 3), (300, 4e-6, 1.3e-5, None), (3, 4e-6, 2e-5, 3)):
         rf = torch.randn((2, 2, nT) + ((nC,) if nC else ()), generator=g, dtype=torch.float64).to(dt_)
         gr = torch.randn((2, 3, nT), generator=g, dtype=torch.float64).to(dt_)
         dt, dtn = torch.tensor([dt_o], dtype=torch.float64), torch.tensor([dt_n], dtype=torch.float64)
@@ -332,6 +335,8 @@ def test_interpT_select_kinds_vs_scipy(kind, tag):
 
         def ref(x):                                    # mobjs.py:203-215
             x0 = np.concatenate([np.zeros_like(x[:, :, :1]), x], axis=2)
+            if len(t_n) == 0:                          # nothing to evaluate: the empty pulse, time on axis 2
+                return np.zeros(x.shape[:2] + (0,) + x.shape[3:], dtype=x.dtype)
             return interpolate.interp1d(t_o, x0, axis=2, kind=kind, copy=False, assume_sorted=True)(t_n)
         rf_h, gr_h = _leaf(rf, DEV), _leaf(gr, DEV)
         rf_n, gr_n, dt_out = interp.interpT(rf_h, gr_h, dev(dt), dev(dtn), kind=kind)
