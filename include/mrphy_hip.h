@@ -76,7 +76,9 @@ extern "C" {
  *      coil, which also returns the gradients w.r.t. loc, df and b1); mrphy_blochsim_rfgr_consts_bwd,
  *      mrphy_signal_rfgr_consts_bwd (the same adjoints, which also return the gradients w.r.t. the step constants
  *      g = gamma 2 pi dt, E1, E2, E1m1 per spin); mrphy_ab_rfgr_fwd, mrphy_ab_rfgr_bwd (Hargreaves' A, B of a pulse
- *      from rf and gr without Beff in memory, and the adjoint w.r.t. the pulse); mrphy_ab_steadystate_fwd,
+ *      from rf and gr without Beff in memory, and the adjoint w.r.t. the pulse); mrphy_ab_rfgr_maps_bwd,
+ *      mrphy_ab_rfgr_consts_bwd (that adjoint, which also returns the gradients w.r.t. loc, df and b1 -- and w.r.t. the
+ *      step constants -- per spin); mrphy_ab_steadystate_fwd,
  *      mrphy_ab_steadystate_bwd (the steady state of a periodic pulse from A, B and a rest period, and its adjoint). */
 #define MRPHY_ABI_VERSION 5
 
@@ -911,6 +913,52 @@ int mrphy_ab_rfgr_bwd(int dtype,
                       void* work, size_t work_bytes,
                       int64_t N, int64_t nM, int64_t nT,
                       void* stream);
+/* K2abb's MAPS and CONSTS builds: mrphy_ab_rfgr_bwd -- the same arguments, the same sweep, the same bits for grad_rf and
+ * grad_gr -- which also returns, per spin, the gradients w.r.t. the spin-side operands, as
+ * mrphy_blochsim_rfgr_maps_bwd / _consts_bwd return them for K2b: grad_loc (N,nM,3), grad_Bz (N,nM) = dL/d(df / gamma)
+ * (the division by gamma is the caller's), grad_b1 (N,nM,2), and from the CONSTS build grad_consts (N,nM,4) =
+ * [dL/dg, dL/dE1, dL/dE2, dL/dE1m1] of the step constants (g = gamma 2 pi dt; dL/dE1m1 comes from the B column alone, the
+ * only one the offset acts on; without relaxation the last three are exact zeros).  Each of the per-spin outputs may
+ * be NULL (not wanted); they are sums over time in a fixed order: the same inputs give the same bits.  No workspace
+ * beyond mrphy_blochsim_rfgr_bwd_workspace().
+ * Both refuse with MRPHY_EINVAL, before anything is launched, what mrphy_ab_rfgr_bwd refuses, and a grad_b1 without a
+ * b1 map.  An empty problem (N*nM*nT == 0) is a success that writes nothing. */
+int mrphy_ab_rfgr_maps_bwd(int dtype,
+                           const void* ABck,
+                           const void* rf, int64_t rf_sn,
+                           const void* gr, int64_t gr_sn,
+                           const void* loc,
+                           const void* df, int64_t df_sn, int64_t df_sm,
+                           const void* gamma, int64_t gamma_sn, int64_t gamma_sm,
+                           const void* b1,
+                           const void* g,  int64_t g_sn,  int64_t g_sm,
+                           const void* E1, int64_t E1_sn, int64_t E1_sm,
+                           const void* E2, int64_t E2_sn, int64_t E2_sm,
+                           const void* E1m1,
+                           const void* grad_A, const void* grad_B,
+                           void* grad_rf, void* grad_gr,
+                           void* grad_loc, void* grad_Bz, void* grad_b1,
+                           void* work, size_t work_bytes,
+                           int64_t N, int64_t nM, int64_t nT,
+                           void* stream);
+int mrphy_ab_rfgr_consts_bwd(int dtype,
+                             const void* ABck,
+                             const void* rf, int64_t rf_sn,
+                             const void* gr, int64_t gr_sn,
+                             const void* loc,
+                             const void* df, int64_t df_sn, int64_t df_sm,
+                             const void* gamma, int64_t gamma_sn, int64_t gamma_sm,
+                             const void* b1,
+                             const void* g,  int64_t g_sn,  int64_t g_sm,
+                             const void* E1, int64_t E1_sn, int64_t E1_sm,
+                             const void* E2, int64_t E2_sn, int64_t E2_sm,
+                             const void* E1m1,
+                             const void* grad_A, const void* grad_B,
+                             void* grad_rf, void* grad_gr,
+                             void* grad_loc, void* grad_Bz, void* grad_b1, void* grad_consts,
+                             void* work, size_t work_bytes,
+                             int64_t N, int64_t nM, int64_t nT,
+                             void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Kss  the steady state of a sequence that repeats every period: a rest of duration `rest` -- free precession exactly

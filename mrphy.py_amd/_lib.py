@@ -93,6 +93,8 @@ PROTOTYPES = {
     'mrphy_beff2ab_bwd_consts': (_int, [_int, _vp, _vp] + _BC * 3 + [_vp, _vp, _vp, _vp] + [_i64] * 3 + [_vp]),
     'mrphy_ab_rfgr_fwd': (_int, [_int] + _PULSE_OPS + [_vp, _vp, _vp, _i64] + [_i64] * 3 + [_vp]),
     'mrphy_ab_rfgr_bwd': (_int, _FUSED + [_vp, _vp, _vp, _vp, _vp, _sz] + [_i64] * 3 + [_vp]),
+    'mrphy_ab_rfgr_maps_bwd': (_int, _FUSED + [_vp] * 7 + [_vp, _sz] + [_i64] * 3 + [_vp]),
+    'mrphy_ab_rfgr_consts_bwd': (_int, _FUSED + [_vp] * 8 + [_vp, _sz] + [_i64] * 3 + [_vp]),
     'mrphy_ab_steadystate_fwd': (_int, [_int, _vp, _vp, _vp, _i64] + _BC * 3 + [_vp, _i64, _i64, _vp]),
     'mrphy_ab_steadystate_bwd': (_int, [_int, _vp, _vp, _vp, _vp, _i64] + _BC * 3 + [_vp, _vp, _vp, _i64, _i64, _vp]),
     'mrphy_blochsim_ab': (_int, [_int, _vp, _vp, _vp, _vp, _i64, _vp]),
@@ -117,6 +119,8 @@ UNITS = [(f, m) for f, masks in (
     ('tu_fused_maps_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_fused_consts_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_ab_rfgr_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
+    ('tu_ab_rfgr_maps_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
+    ('tu_ab_rfgr_consts_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_signal.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_ab_rfgr_fwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_fused_mrx_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),

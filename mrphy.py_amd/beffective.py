@@ -487,7 +487,7 @@ class _Beff2AB(Function):
         if need_hist:
             ctx.save_for_backward(b, hist, g.t, e1.t, e2.t)
             ctx.meta = (code, (g.sn, g.sm), (e1.sn, e1.sm), (e2.sn, e2.sm), N, nM, nT, beff.dtype,
-                        tuple((tuple(c.shape), c.dtype) for c in (γ2πdt, E1, E2, E1_1)), tuple(Nd))
+                        tuple((tuple(c.shape), c.dtype, c.device) for c in (γ2πdt, E1, E2, E1_1)), tuple(Nd))
         return A, B
 
     @staticmethod
@@ -513,8 +513,9 @@ class _Beff2AB(Function):
                                                   _host.current_stream(b.device))
                 _lib.check(rc, 'mrphy_beff2ab_bwd_consts')
                 full = gC.reshape((N,) + tuple(Nd) + (4,))
-                gcs = tuple(_reduce_to_const(full[..., i], torch.empty(shp, dtype=dt_, device='meta'), N, Nd)
-                            if want else None for i, ((shp, dt_), want) in enumerate(zip(cshapes, need[1:5])))
+                # (on the constant's own device: under constants_on('cpu') differentiable constants live on the host)
+                gcs = tuple(_reduce_to_const(full[..., i], torch.empty(shp, dtype=dt_, device='meta'), N, Nd).to(dev_)
+                            if want else None for i, ((shp, dt_, dev_), want) in enumerate(zip(cshapes, need[1:5])))
             else:
                 rc = lib.mrphy_beff2ab_bwd(code, hist.data_ptr(), b.data_ptr(), gt.data_ptr(), *gs,
                                            e1t.data_ptr(), *e1s, e2t.data_ptr(), *e2s, ptr(gA), ptr(gB),

@@ -528,6 +528,36 @@ int mrphy_ab_rfgr_bwd(int dtype, const void* ABck, MRPHY_PULSE_OPS_PARAMS, const
     MRPHY_DISPATCH(dtype, (run_ab_rfgr_bwd<T, CT>(ABck, in, grad_A, grad_B, grad_rf, grad_gr, work, N, nM, nT, st)));
 }
 
+// The MAPS and CONSTS builds of K2abb: mrphy_ab_rfgr_bwd's checks in its order, and a grad_b1 needs a b1 map to
+// differentiate (a mode argument, as in mrphy_blochsim_rfgr_maps_bwd: refused on an empty problem too)
+#define MRPHY_AB_SPIN_BWD(CONSTS_, GC_)                                                                              \
+    if (int e = check_common(dtype, N, nM, nT)) return e;                                                            \
+    if (N > 65535 || nT % SEG != 0 || (grad_b1 && !b1)) return MRPHY_EINVAL;                                         \
+    if (N * nM * nT == 0) return 0;                                                                                  \
+    if (!ABck || !work) return MRPHY_EINVAL;                                                                         \
+    const PulseOps in = MRPHY_PULSE_OPS;                                                                             \
+    if (int e = check_ops(in, true, false)) return e;                                                                \
+    if (work_bytes < mrphy_blochsim_rfgr_bwd_workspace(dtype, N, nM, nT)) return MRPHY_EINVAL;                       \
+    hipStream_t st = (hipStream_t)stream;                                                                            \
+    MRPHY_DISPATCH(dtype, (run_ab_rfgr_spin_bwd<CONSTS_, T, CT>(ABck, in, grad_A, grad_B, grad_rf, grad_gr, grad_loc, \
+                                                                grad_Bz, grad_b1, GC_, work, N, nM, nT, st)))
+
+int mrphy_ab_rfgr_maps_bwd(int dtype, const void* ABck, MRPHY_PULSE_OPS_PARAMS, const void* grad_A, const void* grad_B,
+                           void* grad_rf, void* grad_gr, void* grad_loc, void* grad_Bz, void* grad_b1, void* work,
+                           size_t work_bytes, int64_t N, int64_t nM, int64_t nT, void* stream)
+{
+    MRPHY_AB_SPIN_BWD(false, nullptr);
+}
+
+int mrphy_ab_rfgr_consts_bwd(int dtype, const void* ABck, MRPHY_PULSE_OPS_PARAMS, const void* grad_A,
+                             const void* grad_B, void* grad_rf, void* grad_gr, void* grad_loc, void* grad_Bz,
+                             void* grad_b1, void* grad_consts, void* work, size_t work_bytes, int64_t N, int64_t nM,
+                             int64_t nT, void* stream)
+{
+    MRPHY_AB_SPIN_BWD(true, grad_consts);
+}
+#undef MRPHY_AB_SPIN_BWD
+
 int mrphy_beff2ab(int dtype, const void* Beff,
                   const void* g, int64_t g_sn, int64_t g_sm,
                   const void* E1, int64_t E1_sn, int64_t E1_sm,

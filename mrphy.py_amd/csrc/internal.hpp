@@ -85,6 +85,12 @@ template <typename T, typename CT>
 int run_ab_rfgr_bwd(const void* ABck, PulseOps in, const void* gA, const void* gB, void* grf, void* ggr, void* work,
                     int64_t N, int64_t nM, int64_t nT, hipStream_t st);
 
+// the MAPS (CONSTS == false: tu_ab_rfgr_maps_bwd.hip) and CONSTS (tu_ab_rfgr_consts_bwd.hip) builds of K2abb: the same
+// adjoint, which also returns gloc, gBz, gb1 -- and gC = [dL/dg, dL/dE1, dL/dE2, dL/dE1m1] -- per spin, each may be null
+template <bool CONSTS, typename T, typename CT>
+int run_ab_rfgr_spin_bwd(const void* ABck, PulseOps in, const void* gA, const void* gB, void* grf, void* ggr, void* gloc,
+                         void* gBz, void* gb1, void* gC, void* work, int64_t N, int64_t nM, int64_t nT, hipStream_t st);
+
 template <typename T, typename CT>
 int run_beff2ab(const void* Beff, Bc g, Bc E1, Bc E2, const void* E1m1, void* A, void* B, void* hist,
                 int64_t N, int64_t nM, int64_t nT, hipStream_t st);

@@ -139,6 +139,19 @@ int launch_k2ab(const PulseOps& in, void* A, void* B, void* ABck, int64_t ck_eve
 // The relaxation offset is an additive constant: it enters the recompute of the B column only and not the adjoint.
 // No adj_end: nothing is returned per spin.  Without relaxation the B column is skipped (its states are exact zeros,
 // and every dL/dB it would form is linear in them).
+//
+// MAPS (tu_ab_rfgr_maps_bwd.hip): the gradients w.r.t. the lane's own loc, df / gamma and b1 besides, as K2b's MAPS
+// builds form them (k_fused_bwd.hpp) -- step 4 holds the column-summed (g0, g1, g2) = dL/dB of the segment's 16 steps,
+// and sums them over TIME there: partials per segment (steps ascending), added to lane-private running sums once per
+// segment (segments descending), reset per tile, stored per spin under `valid`.  No LDS beyond the reduction tile, no
+// workspace, no second pass, a fixed order of summation; the sweep is untouched.
+// CONSTS (tu_ab_rfgr_consts_bwd.hip): the gradients w.r.t. the lane's own step constants besides, gC = [dL/dg, dL/dE1,
+// dL/dE2, dL/dE1m1], by K2b's CONSTS arithmetic (rot_apply_adj_consts): dL/dg, dL/dE1, dL/dE2 summed over every stepped
+// column, dL/dE1m1 over the B column alone -- the A columns run without the offset.  The segment's partials are carried
+// through the column loop; in the precise fp32 mode all four columns carry t = E h (adj_begin on each), and one
+// adj_const_finish per tile divides the E out.  Without relaxation gC[1..3] are exact zeros, as K2b's.  The CONSTS
+// build forms the MAPS sums as well (the MAPS build's bits); each of gloc, gBz, gb1, gC may be null.
+// Everything the plain build computes is computed by the same expressions in all three.
 // =============================================================================================
 template <typename T>
 struct AbFusedBwdArgs {
@@ -149,6 +162,19 @@ struct AbFusedBwdArgs {
     T* work;                         // (P, N, 5, nT)
     int64_t N, nM, nT, P;
 };
+template <typename T>
+struct AbFusedBwdMapsArgs : AbFusedBwdArgs<T> {
+    T* gloc;                         // (N, nM, 3): dL/dloc
+    T* gBz;                          // (N, nM): dL/d(df / gamma)
+    T* gb1;                          // (N, nM, 2): dL/db1; builds with a b1 map only
+};
+template <typename T>
+struct AbFusedBwdConstsArgs : AbFusedBwdMapsArgs<T> {
+    T* gC;                           // (N, nM, 4): [dL/dg, dL/dE1, dL/dE2, dL/dE1m1], g = gamma 2 pi dt
+};
+template <typename T, bool MAPS, bool CONSTS>
+using AbFusedBwdKArgsT = std::conditional_t<CONSTS, AbFusedBwdConstsArgs<T>,
+                                            std::conditional_t<MAPS, AbFusedBwdMapsArgs<T>, AbFusedBwdArgs<T>>>;
 
 // seg_recompute (k_fused_bwd_common.hpp) with the rotations' S, C either formed and kept in h (GIVEN == false) or taken
 // from h (GIVEN == true): Rot is scale_b's b and those S, C, which is what rot_prepare leaves in it
@@ -181,9 +207,14 @@ __device__ __forceinline__ void ab_seg_recompute(const SpinConst<T, CT>& k, int6
     }
 }
 
-template <typename T, typename CT, bool RELAX, bool HB1>
-__global__ __launch_bounds__(WAVE) void k_ab_rfgr_bwd(AbFusedBwdArgs<T> a)
+// (the fp32 MAPS / CONSTS builds are bound to two waves per SIMD, K2b's occupancy: a build that outgrows 256 VGPRs then
+// spills, which tools/kregs.py --scratch and the suite's scratch test name, instead of halving the occupancy unseen)
+template <typename T, typename CT, bool RELAX, bool HB1, bool MAPS = false, bool CONSTS = false>
+__global__ __launch_bounds__(WAVE, ((MAPS || CONSTS) && sizeof(T) == 4 ? 2 : 1))
+void k_ab_rfgr_bwd(AbFusedBwdKArgsT<T, MAPS, CONSTS> a)
 {
+    static_assert(!(MAPS && CONSTS), "the CONSTS build forms the map sums itself");
+    constexpr bool MSUM = MAPS || CONSTS;                   // the sums over time of dL/dB
     constexpr int NCOL = AB_COLS<RELAX>;
     using R = typename CTr<CT>::reg;
     __shared__ __attribute__((aligned(16))) T red[5 * SEG * RED_PITCH];
@@ -217,6 +248,9 @@ __global__ __launch_bounds__(WAVE) void k_ab_rfgr_bwd(AbFusedBwdArgs<T> a)
         hz[3] = a.gB ? a.gB[row * 3 + 2] * vmask : T(0);
 #pragma unroll
         for (int j = 0; j < 4; ++j) adj_begin<RELAX, T, CT>(k, hx[j], hy[j], hz[j]);
+        // MAPS / CONSTS: the running sums over time, reset per tile (unused, and compiled away, in the plain build)
+        T aZ = T(0), aL[3] = {T(0), T(0), T(0)}, aBr = T(0), aBi = T(0);
+        T aC[4] = {T(0), T(0), T(0), T(0)};
 
         // The checkpoints are visited segments descending, columns ascending; each is requested one column ahead of
         // its use (the first column of a segment during the last column of the segment before).
@@ -233,6 +267,7 @@ __global__ __launch_bounds__(WAVE) void k_ab_rfgr_bwd(AbFusedBwdArgs<T> a)
             T old0 = T(0), old1 = T(0);
             if (!first) { old0 = *dst0; old1 = *dst1; }
             SegStates<T> h;
+            T pC[4] = {T(0), T(0), T(0), T(0)};             // CONSTS: this segment's partial sums, over its columns
 #pragma unroll 1
             for (int j = 0; j < NCOL; ++j) {
                 T mx = cx, my = cy, mz = cz;
@@ -266,8 +301,20 @@ __global__ __launch_bounds__(WAVE) void k_ab_rfgr_bwd(AbFusedBwdArgs<T> a)
                     for (int q = 3; q >= 0; --q) {
                         const int st = sb * 4 + q;
                         T g0, g1, g2;
-                        rot_apply_adj<RELAX, T, CT>(kc, ra[q], h.M0[st], h.M1[st], h.M2[st], hx[0], hy[0], hz[0],
-                                                    g0, g1, g2);
+                        if constexpr (CONSTS) {
+                            // dL/dg wants the step's unscaled field: assembled again here (the same expressions, the
+                            // same bits) from operands pinned per step, or the batch's Bx, By, Bz stay alive through
+                            // its four steps -- twelve registers at the sweep's peak, which the fp32 builds do not have
+                            // at two waves per SIMD.  The offset's gradient comes from the B column only (wave-uniform).
+                            asm volatile("" : "+v"(spc.lx), "+v"(spc.ly), "+v"(spc.lz), "+v"(spc.delta), "+v"(brc),
+                                              "+v"(bic));
+                            T fx, fy, fz;
+                            field(t0 + st, fx, fy, fz);
+                            rot_apply_adj_consts<RELAX, T, CT>(kc, ra[q], fx, fy, fz, h.M0[st], h.M1[st], h.M2[st],
+                                                               hx[0], hy[0], hz[0], g0, g1, g2, pC, j == 3);
+                        } else
+                            rot_apply_adj<RELAX, T, CT>(kc, ra[q], h.M0[st], h.M1[st], h.M2[st], hx[0], hy[0], hz[0],
+                                                        g0, g1, g2);
                         T* q0 = red + red_idx(0 * SEG + st, lane);
                         T* q1 = red + red_idx(1 * SEG + st, lane);
                         T* q2 = red + red_idx(2 * SEG + st, lane);
@@ -282,15 +329,39 @@ __global__ __launch_bounds__(WAVE) void k_ab_rfgr_bwd(AbFusedBwdArgs<T> a)
                 hx[NCOL - 1] = tx; hy[NCOL - 1] = ty; hz[NCOL - 1] = tz;
             }
             // 4. the five contributions of each step from the columns' sum, as K2b forms them from one column's
+            T pZ = T(0), pL[3] = {T(0), T(0), T(0)}, pBr = T(0), pBi = T(0);      // MAPS: this segment's partial sums
 #pragma unroll
             for (int st = 0; st < SEG; ++st) {
                 const T g0 = red[red_idx(0 * SEG + st, lane)], g1 = red[red_idx(1 * SEG + st, lane)],
                         g2 = red[red_idx(2 * SEG + st, lane)];
+                if constexpr (MSUM) {
+                    // the step's pulse sample: wave-uniform scalars, as the sweep's `field` read them
+                    const int64_t t = t0 + st;
+                    pZ += g2;
+                    pL[0] += g2 * pc.gx[t]; pL[1] += g2 * pc.gy[t]; pL[2] += g2 * pc.gz[t];
+                    if constexpr (HB1) {
+                        const T rr = pc.rfr[t], ri = pc.rfi[t];
+                        pBr += g0 * rr + g1 * ri;
+                        pBi += g1 * rr - g0 * ri;
+                    }
+                }
                 red[red_idx(0 * SEG + st, lane)] = sp.lx * g2;
                 red[red_idx(1 * SEG + st, lane)] = sp.ly * g2;
                 red[red_idx(2 * SEG + st, lane)] = sp.lz * g2;
                 red[red_idx(3 * SEG + st, lane)] = HB1 ? br * g0 + bi * g1 : g0;
                 red[red_idx(4 * SEG + st, lane)] = HB1 ? br * g1 - bi * g0 : g1;
+                // (the pulse samples a batch of steps at a time, as the sweep takes them: requested all at once, the 80
+                // scalars of a segment do not fit the scalar registers in fp64)
+                if constexpr (MSUM)
+                    if (st % 4 == 3) __builtin_amdgcn_sched_barrier(0);
+            }
+            if constexpr (CONSTS) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) aC[i] += pC[i];
+            }
+            if constexpr (MSUM) {
+                aZ += pZ; aL[0] += pL[0]; aL[1] += pL[1]; aL[2] += pL[2];
+                if constexpr (HB1) { aBr += pBr; aBi += pBi; }
             }
             __syncthreads();
             // 80 row sums, K2b's: lanes 0..63 take rows 0..63, then lane (r, j) chain j of row 64 + r; ONE explicit wait
@@ -317,22 +388,43 @@ __global__ __launch_bounds__(WAVE) void k_ab_rfgr_bwd(AbFusedBwdArgs<T> a)
             }
             __syncthreads();
         }
+        if constexpr (CONSTS) {
+            adj_const_finish<T, CT>(k, aC);                 // the precise fp32 mode carried t = E h: E divided out once
+            if (valid && a.gC) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) a.gC[row * 4 + i] = aC[i];
+            }
+        }
+        if constexpr (MSUM) {
+            // once per spin; each output optional.  gBz is dL/d(df / gamma): the division by gamma and the folds to
+            // the operands' own shapes are the host's
+            if (valid && a.gloc) { a.gloc[row * 3] = aL[0]; a.gloc[row * 3 + 1] = aL[1]; a.gloc[row * 3 + 2] = aL[2]; }
+            if (valid && a.gBz) a.gBz[row] = aZ;
+            if constexpr (HB1)
+                if (valid && a.gb1) { a.gb1[row * 2] = aBr; a.gb1[row * 2 + 1] = aBi; }
+        }
         first = false;
     }
 }
 
+// the per-spin outputs of the MAPS and CONSTS builds, each may be null; the plain build takes none
+struct AbSpinGrads { void *gloc = nullptr, *gBz = nullptr, *gb1 = nullptr, *gC = nullptr; };
+
 // Host: K2abb on k2b_waves persistent waves per batch entry, then the second pass into grad_gr / grad_rf
-template <typename T, typename CT>
+template <typename T, typename CT, bool MAPS = false, bool CONSTS = false>
 int launch_k2abb(const void* ABck, const PulseOps& in, const void* gA, const void* gB, void* grf, void* ggr, void* work,
-                 int64_t N, int64_t nM, int64_t nT, hipStream_t st)
+                 int64_t N, int64_t nM, int64_t nT, hipStream_t st, const AbSpinGrads& sg = {})
 {
     dim3 grid;
     int e;
     if (!fused_grid(N * nM * nT, k2b_waves(nM), N, grid, e)) return e;
-    AbFusedBwdArgs<T> a;
+    AbFusedBwdKArgsT<T, MAPS, CONSTS> a;
     a.ABck = (const T*)ABck; a.in = typed<T>(in); a.gA = (const T*)gA; a.gB = (const T*)gB; a.work = (T*)work;
     a.N = N; a.nM = nM; a.nT = nT; a.P = grid.x;
-#define MRPHY_K2ABB(RX_, HB_) hipLaunchKernelGGL((k_ab_rfgr_bwd<T, CT, RX_, HB_>), grid, dim3(WAVE), 0, st, a)
+    if constexpr (MAPS || CONSTS) { a.gloc = (T*)sg.gloc; a.gBz = (T*)sg.gBz; a.gb1 = (T*)sg.gb1; }
+    if constexpr (CONSTS) a.gC = (T*)sg.gC;
+#define MRPHY_K2ABB(RX_, HB_) \
+    hipLaunchKernelGGL((k_ab_rfgr_bwd<T, CT, RX_, HB_, MAPS, CONSTS>), grid, dim3(WAVE), 0, st, a)
     if (in.b1) { if (in.E1.p) MRPHY_K2ABB(true, true);  else MRPHY_K2ABB(false, true); }
     else       { if (in.E1.p) MRPHY_K2ABB(true, false); else MRPHY_K2ABB(false, false); }
 #undef MRPHY_K2ABB

@@ -161,11 +161,12 @@ __device__ __forceinline__ void adj_inject(const SpinConst<T, CT>& k, T& hx, T& 
 // and the carried state keep rot_apply_adj's bits -- and the step's terms of the constants' gradients added to acc
 // (adj_const_accumulate, as K3's GC builds call it).  (Bx, By, Bz): the unscaled field of the step; (hx, hy, hz) comes
 // in as the carried state AFTER the step's record injection, which is the `s` the accumulation wants (t = E h in the
-// precise fp32 mode: adj_const_finish divides the E out of the finished sums).
+// precise fp32 mode: adj_const_finish divides the E out of the finished sums).  `offset`: the step has the relaxation
+// offset, whose gradient is then summed -- false for K2abb's A columns (k_ab_rfgr.hpp), which run without it.
 template <bool RELAX, typename T, typename CT>
 __device__ __forceinline__ void rot_apply_adj_consts(const SpinConst<T, CT>& k, const RotAdj<T>& r, T Bx, T By, T Bz,
                                                      T mx, T my, T mz, T& hx, T& hy, T& hz, T& gx, T& gy, T& gz,
-                                                     T (&acc)[4])
+                                                     T (&acc)[4], bool offset = true)
 {
 #pragma clang fp contract(off)
     using R = typename CTr<CT>::reg;
@@ -175,7 +176,7 @@ __device__ __forceinline__ void rot_apply_adj_consts(const SpinConst<T, CT>& k, 
     gx = T(R(dbx) * k.g);
     gy = T(R(dby) * k.g);
     gz = T(R(dbz) * k.g);
-    adj_const_accumulate<RELAX, T, CT>(r, Bx, By, Bz, mx, my, mz, sx, sy, sz, dbx, dby, dbz, acc);
+    adj_const_accumulate<RELAX, T, CT>(r, Bx, By, Bz, mx, my, mz, sx, sy, sz, dbx, dby, dbz, acc, offset);
     // The sums are read at the end of the segment only, and the compiler sinks each step's terms below the guards of
     // the following steps' cold large-angle paths, down to there -- with the step's m, b, S, C, s and B alive all the
     // way: a private segment in fp64.  Pinned as bloch_math.hpp's pin_state pins the forward state: the step's terms are

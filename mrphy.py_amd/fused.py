@@ -34,7 +34,9 @@ per-spin records in memory; the coils of a receive array share one simulation pe
 :func:`ab_rfgr` is Hargreaves' propagator of the whole pulse per spin, ``M_after = A @ M_before + B``
 (``beffective.beff2ab`` of ``beffective.rfgr2beff``), from the same operands: the four columns of ``[I | 0]`` share
 each step's field and rotation (K2ab), and the gradients w.r.t. ``rf`` and ``gr`` come from a fused adjoint over the
-four columns' checkpoints (K2abb) -- again without ``Beff``, a history or ``grad_Beff`` in memory.
+four columns' checkpoints (K2abb) -- again without ``Beff``, a history or ``grad_Beff`` in memory.  The same sweep gives
+the gradients w.r.t. ``loc``, ``Δf``, ``b1Map`` and ``γ_beff`` (``mrphy_ab_rfgr_maps_bwd``) and w.r.t. ``T1``, ``T2``, ``γ``,
+``dt`` or the entries of ``consts=`` (``mrphy_ab_rfgr_consts_bwd``), as K2b's MAPS and CONSTS builds do for ``blochsim_rfgr``.
 
 :func:`ab_steadystate` solves ``(I - A F) Mss = A f + B`` per spin for the magnetisation of a sequence that repeats the
 pulse ``A, B`` after a rest ``F, f`` (``sims.freeprec``), with an adjoint w.r.t. ``A``, ``B`` and the rest's operands
@@ -335,12 +337,18 @@ class AbRfGrHIP(Function):
     Hargreaves' ``A`` `(N, *Nd, xyz, 3)`, ``B`` `(N, *Nd, xyz)` of the pulse on the spins (``mrphy_ab_rfgr_fwd``), one
     transmit coil; ``E1 = E2 = E1_1 = None`` is no relaxation.  Differentiable w.r.t. ``rf`` and ``gr``
     (``mrphy_ab_rfgr_bwd``); either output may go without a cotangent.  ``want_ckpt`` as in :class:`BlochSimRfGrHIP`:
-    decided by the caller (:func:`_decide_ab_route`), and the pulse length is then a whole number of segments."""
+    decided by the caller (:func:`_decide_ab_route`), and the pulse length is then a whole number of segments.
 
-    ARGS = ('rf', 'gr', 'p', 'γ2πdt', 'E1', 'E2', 'E1_1', 'want_ckpt')
+    ``loc``, ``Δf``, ``b1Map``, ``γ_beff``: the caller's own tensors, handed over only when one of them wants a gradient,
+    as to :class:`BlochSimRfGrHIP`; ``γ2πdt``, ``E1``, ``E2``, ``E1_1`` that require grad likewise.  The backward makes ONE
+    call, to the cheapest entry point that serves what is wanted: ``mrphy_ab_rfgr_bwd``, ``mrphy_ab_rfgr_maps_bwd`` (the
+    maps) or ``mrphy_ab_rfgr_consts_bwd`` (the constants, with or without maps) -- the same sweep, the same bits for
+    ``grad_rf`` and ``grad_gr`` -- and folds the per-spin gradients to the operands' own shapes."""
+
+    ARGS = ('rf', 'gr', 'p', 'γ2πdt', 'E1', 'E2', 'E1_1', 'want_ckpt', 'loc', 'Δf', 'b1Map', 'γ_beff')
 
     @staticmethod
-    def forward(ctx, rf, gr, p, γ2πdt, E1, E2, E1_1, want_ckpt=False):
+    def forward(ctx, rf, gr, p, γ2πdt, E1, E2, E1_1, want_ckpt=False, loc=None, Δf=None, b1Map=None, γ_beff=None):
         lib = _lib.require_library()
         device, dtype = p.device, p.dtype
         code, alive, consts, _, _ = _forward_prep(lib, p, γ2πdt, E1, E2, E1_1, dtype, device, False)
@@ -357,15 +365,16 @@ class AbRfGrHIP(Function):
         ctx.set_materialize_grads(False)
         if want_ckpt:
             ctx.save_for_backward(ABck)
-            ctx.saved = _Saved(p, code, consts, alive, None, (), _likes(rf=rf, gr=gr))
+            ctx.saved = _Saved(p, code, consts, alive, None, (), _likes(
+                rf=rf, gr=gr, loc=loc, Δf=Δf, b1Map=b1Map, γ_beff=γ_beff, γ2πdt=γ2πdt, E1=E1, E2=E2, E1_1=E1_1))
         return A, B
 
     @staticmethod
     def backward(ctx, grad_A, grad_B):
         from .beffective import _fold_pulse_grad
-        ARGS = AbRfGrHIP.ARGS
-        want = dict(zip(ARGS, ctx.needs_input_grad))
-        if not (want['rf'] or want['gr']) or (grad_A is None and grad_B is None):
+        ARGS = AbRfGrHIP.ARGS                         # (loc .. γ_beff: False where they were not handed over)
+        want = dict(zip(ARGS, (*ctx.needs_input_grad, *(False,) * len(ARGS))))
+        if not any(want.values()) or (grad_A is None and grad_B is None):
             return tuple(None for _ in ARGS)
         lib = _lib.require_library()
         s = ctx.saved
@@ -373,24 +382,39 @@ class AbRfGrHIP(Function):
         p, device, dtype = s.p, ABck.device, ABck.dtype
         _host.require_invertible_relaxation(s.code, s.alive[1], s.alive[2], 'fused.ab_rfgr')
         gA, gB = (None if x is None else x.to(dtype).contiguous() for x in (grad_A, grad_B))
-        raw = dict(rf=torch.empty((p.N, 2, p.nT, 1), dtype=dtype, device=device) if want['rf'] else None,
-                   gr=torch.empty((p.N, 3, p.nT), dtype=dtype, device=device) if want['gr'] else None)
+        need_γb = want['γ_beff'] and p.df is not None          # without Δf the field does not depend on γ_beff
+        full = (p.N,) + p.Nd
+        outs = dict(grf=(want['rf'], (p.N, 2, p.nT, 1)), ggr=(want['gr'], (p.N, 3, p.nT)),
+                    gloc=(want['loc'], full + (3,)), gBz=(want['Δf'] or need_γb, full), gb1=(want['b1Map'], full + (2,)),
+                    gC=(any(want[k] for k in _CONSTS), full + (4,)))
+        raw = {k: torch.empty(shape, dtype=dtype, device=device) if w else None for k, (w, shape) in outs.items()}
         if p.N * p.nM * p.nT == 0:
-            # no spin or no step: the library's adjoint writes nothing then, and A = I, B = 0 whatever the pulse is
+            # no spin or no step: the library's adjoints write nothing then, and A = I, B = 0 whatever the operands are
             for g in raw.values():
                 if g is not None:
                     g.zero_()
         else:
+            # the cheapest build that serves what is wanted; the CONSTS build forms the map sums too
+            spin = (('gloc', 'gBz', 'gb1', 'gC') if raw['gC'] is not None else
+                    ('gloc', 'gBz', 'gb1') if any(raw[k] is not None for k in ('gloc', 'gBz', 'gb1')) else ())
+            name = 'mrphy_ab_rfgr_' + {0: '', 3: 'maps_', 4: 'consts_'}[len(spin)] + 'bwd'
             nbytes = int(lib.mrphy_blochsim_rfgr_bwd_workspace(s.code, p.N, p.nM, p.nT))
             work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
             ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
             with torch.cuda.device(device):
-                rc = lib.mrphy_ab_rfgr_bwd(s.code, ABck.data_ptr(), *p.k0_args(), *s.consts, ptr(gA), ptr(gB),
-                                           ptr(raw['rf']), ptr(raw['gr']), work.data_ptr(), work.numel(),
-                                           p.N, p.nM, p.nT, _host.current_stream(device))
-            _lib.check(rc, 'mrphy_ab_rfgr_bwd')
-        g = {k: _fold_pulse_grad(x, s.likes[k][0], s.likes[k][1], k == 'rf' and p.b1 is None)
-             for k, x in raw.items() if x is not None}
+                rc = getattr(lib, name)(s.code, ABck.data_ptr(), *p.k0_args(), *s.consts, ptr(gA), ptr(gB),
+                                        ptr(raw['grf']), ptr(raw['ggr']), *(ptr(raw[k]) for k in spin),
+                                        work.data_ptr(), work.numel(), p.N, p.nM, p.nT, _host.current_stream(device))
+            _lib.check(rc, name)
+        g = {k: _fold_pulse_grad(raw[r], s.likes[k][0], s.likes[k][1], k == 'rf' and p.b1 is None)
+             for k, r in (('rf', 'grf'), ('gr', 'ggr')) if raw[r] is not None}
+        if raw['gC'] is not None:
+            g.update(zip(_CONSTS, _fold_const_grads(raw['gC'], p, [s.likes.get(k) for k in _CONSTS],
+                                                    [want[k] for k in _CONSTS])))
+        g.update(zip(_MAPS, _fold_map_grads(raw['gloc'], raw['gBz'] if want['Δf'] else None, raw['gb1'], p,
+                                            [s.likes.get(k) for k in _MAPS])))
+        if need_γb:
+            g['γ_beff'] = _fold_gamma_beff_grad(raw['gBz'], p, s.likes['γ_beff'])
         return tuple(g.get(k) for k in ARGS)
 
 
@@ -415,15 +439,24 @@ class _JoinAb(Function):
                 gA @ A1.transpose(-1, -2) + gB[..., None] * B1[..., None, :], gB)
 
 
-def _decide_ab_route(*, nT, seg, one_coil, pulse_grad, maps_grad, consts_grad):
+def _ab_spin_fused(dtype, consts_grad):
+    r"""Whether K2abb's MAPS / CONSTS builds serve :func:`ab_rfgr`'s map and constants' gradients in ``dtype``: every
+    build of the library does."""
+    return True
+
+
+def _decide_ab_route(*, nT, seg, one_coil, pulse_grad, maps_grad, consts_grad, spin_fused=False):
     r"""The route of :func:`ab_rfgr` as a function of plain facts (``maps_grad``: a gradient w.r.t. ``loc``, ``Δf``,
-    ``b1Map`` or a ``γ_beff`` that multiplies a ``Δf``): ``('fused', want_ckpt)`` -- one transmit coil and either no
-    gradient or a pulse gradient over whole checkpoint segments; ``('split', n1)`` -- one coil, a pulse gradient, more
-    than one segment's steps and a ragged last one: the first ``n1`` steps fused, the tail composed;
-    ``('composed', None)`` -- everything else: ``rfgr2beff`` + ``beff2ab``, whose autograd serves every operand."""
-    if not one_coil or maps_grad or consts_grad:
+    ``b1Map`` or a ``γ_beff`` that multiplies a ``Δf``; ``spin_fused``: the fused adjoint's MAPS / CONSTS builds serve
+    the map and constants' gradients that are wanted -- :func:`ab_rfgr` says so, the default is the adjoint w.r.t. the
+    pulse alone): ``('fused', want_ckpt)`` -- one transmit coil and either no gradient or gradients the fused adjoint
+    serves over whole checkpoint segments; ``('split', n1)`` -- one coil, such gradients, more than one segment's steps
+    and a ragged last one: the first ``n1`` steps fused, the tail composed; ``('composed', None)`` -- everything else:
+    ``rfgr2beff`` + ``beff2ab``, whose autograd serves every operand."""
+    spin_grad = maps_grad or consts_grad
+    if not one_coil or (spin_grad and not spin_fused):
         return 'composed', None
-    if not pulse_grad:
+    if not (pulse_grad or spin_grad):
         return 'fused', False
     if nT % seg == 0:
         return 'fused', True
@@ -759,9 +792,11 @@ def ab_rfgr(
     the same bits.  A pulse length that is not a multiple of 16 is split: the whole segments fused, the tail of at most
     15 steps through ``rfgr2beff`` + ``beff2ab``, joined as ``A = A_tail @ A_head``, ``B = A_tail @ B_head + B_tail``
     (:class:`_JoinAb`: its adjoint works on contiguous cotangents, so the bits do not depend on the strides of the loss's).
-    Parallel transmit, gradients w.r.t. ``loc``, ``Δf``, ``b1Map``, ``γ_beff`` or the constants, and a pulse gradient
-    with fewer than 16 steps compose ``rfgr2beff`` + ``beff2ab`` (HIP kernels as well), whose autograd serves every
-    operand.
+    Gradients w.r.t. ``loc``, ``Δf``, ``b1Map``, ``γ_beff`` and w.r.t. ``T1``, ``T2``, ``γ``, ``dt`` (or the entries of
+    ``consts=``) come out of the same adjoint sweep, summed over time per spin in a fixed order (K2abb's MAPS and CONSTS
+    builds: one forward, one adjoint call, still no ``Beff``); on the split route autograd adds the two parts'.  ``A, B``
+    are the bits of the call that does not differentiate them.  Parallel transmit and any gradient of a pulse with
+    fewer than 16 steps compose ``rfgr2beff`` + ``beff2ab`` (HIP kernels as well), whose autograd serves every operand.
     """
     from . import beffective, sims
     _host.require_device_tensor(loc, 'loc')
@@ -770,14 +805,16 @@ def ab_rfgr(
     lib = _lib.require_library()
     grad_on = torch.is_grad_enabled()
     rq = lambda x: grad_on and isinstance(x, Tensor) and x.requires_grad  # noqa: E731
-    maps_grad = any(rq(x) for x in (loc, Δf, b1Map)) or (rq(γ_beff) and Δf is not None)
+    γb_grad = rq(γ_beff) and Δf is not None         # (without Δf the field does not depend on γ_beff)
+    maps_grad = any(rq(x) for x in (loc, Δf, b1Map)) or γb_grad
     consts_grad = any(rq(x) for x in (consts.values() if consts is not None else (T1, T2, γ, dt)))
     p = beffective._PulseOnSpins(rf.detach(), gr.detach(), loc.detach(), None if Δf is None else Δf.detach(),
                                  None if b1Map is None else b1Map.detach(), γ_beff.detach())
     route, out = _decide_ab_route(
         nT=p.nT, seg=int(lib.mrphy_blochsim_rfgr_ck_every()),
         one_coil=p.nC == 1 and (rf.ndim == 3 or b1Map is not None or rf.shape[-1] == 1),
-        pulse_grad=any(rq(x) for x in (rf, gr)), maps_grad=maps_grad, consts_grad=consts_grad)
+        pulse_grad=any(rq(x) for x in (rf, gr)), maps_grad=maps_grad, consts_grad=consts_grad,
+        spin_fused=_ab_spin_fused(p.dtype, consts_grad))
     if route == 'split':
         # whole segments fused, the tail of <= 15 steps composed; the step map of the tail acts on the head's
         A1, B1 = ab_rfgr(rf[:, :, :out], gr[:, :, :out], loc, **kw)
@@ -795,7 +832,8 @@ def ab_rfgr(
         cs = sims.relax_constants(T1, T2, γ, dt, ndim, device)
     if route == 'composed':
         return _ab_composed(rf, gr, loc, kw, cs, consts_grad)
-    return AbRfGrHIP.apply(rf, gr, p, *cs, out)
+    maps = (loc, Δf, b1Map, γ_beff if γb_grad else None) if maps_grad else ()
+    return AbRfGrHIP.apply(rf, gr, p, *cs, out, *maps)
 
 
 class AbSteadyStateHIP(Function):
@@ -927,7 +965,9 @@ def steadystate_rfgr(
     ``sims.freeprec(Mss, rest, T1=T1, T2=T2, Δf=...)`` is the one before it.
 
     Every route of :func:`ab_rfgr` (fused, split, composed) serves it, so gradients reach every operand ``ab_rfgr``
-    serves, and ``rest, T1, T2, Δf`` / ``Δf_rest`` through the rest period as well.  fp32: the solve itself runs in
+    serves -- with one transmit coil ``T1, T2, Δf, b1Map, loc`` as well as ``rf, gr`` through the fused adjoint, without
+    ``Beff`` in memory -- and ``rest, T1, T2, Δf`` / ``Δf_rest`` through the rest period as well: ``T1`` and ``T2``, shared
+    by the pulse and the rest, receive the sum of both paths.  fp32: the solve itself runs in
     fp64, but ``Mss`` inherits the rounding of the fp32 ``A`` amplified by the conditioning of ``I - A F``, about
     ``1 / (1 - exp(-rest/T1))``: relative errors of a few 1e-6 at a factor of 50, 3e-5 at 170 -- for any fp32 route,
     the reference's operations included.

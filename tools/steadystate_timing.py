@@ -1,6 +1,6 @@
 r"""What ``fused.steadystate_rfgr`` costs next to the same composition with the rest period and the solve in plain torch.
 
-    python tools/steadystate_timing.py [--n 64] [--nT 1024] [--reps 10] [--out profiles/steadystate_timing.json]
+    python tools/steadystate_timing.py [--n 64] [--nT 1024] [--reps 10] [--wrt pulse|maps|consts|all] [--out FILE.json]
 
 Shape: n^3 spins x nT steps, fp32, one transmit coil with a ``b1Map`` and per-spin ``T1 / T2`` (the problem of
 ``tools/ab_rfgr_timing.py``), a rest of 5 ms, in ``precision('precise')`` and ``('fast')``, the forward alone
@@ -18,6 +18,12 @@ HIP events around each call (the loss and its backward included), three warm-up 
 alternate the contenders in one process; reported per contender: median, min, max and the quartiles of the rounds, and
 the relative L2 distance of (a)'s ``Mss`` and gradients from (b)'s.  Nothing is asserted: the file records what comes
 out.  Needs the GPU; there is no other path.
+
+``--wrt maps | consts | all`` (default ``pulse``: everything above, the output keys unchanged): forward + backward of
+``(Mss w).sum()`` with ``loc, Δf, b1Map`` and / or ``T1, T2`` requiring grad as well, Kss / Kssb on the ``A, B`` of the three
+contenders of ``tools/ab_rfgr_timing.py --wrt`` -- ``ab_rfgr``, the batch-4 emulation through ``blochsim_rfgr``, and
+``rfgr2beff`` + ``beff2ab`` --, ``T1, T2, Δf`` shared by the pulse and the rest; default output
+``profiles/steadystate_spin_grads_timing.json``.
 """
 import argparse
 import json
@@ -33,7 +39,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import mrphy_amd  # noqa: E402
 from mrphy_amd import fused  # noqa: E402
-from ab_rfgr_timing import problem, rel_l2  # noqa: E402
+from ab_rfgr_timing import WRT, main_wrt, problem, rel_l2  # noqa: E402
 
 REST = 5e-3
 
@@ -115,11 +121,24 @@ def main():
     ap.add_argument('--n', type=int, default=64)
     ap.add_argument('--nT', type=int, default=1024)
     ap.add_argument('--reps', type=int, default=10)
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'steadystate_timing.json'))
+    ap.add_argument('--wrt', choices=sorted(WRT), default='pulse')
+    ap.add_argument('--out', default=None)
     args = ap.parse_args()
+    args.out = args.out or os.path.join(ROOT, 'profiles', 'steadystate_timing.json' if args.wrt == 'pulse'
+                                        else 'steadystate_spin_grads_timing.json')
     assert torch.cuda.is_available(), 'tools/steadystate_timing.py measures on the GPU'
     assert args.reps >= 10, 'the median of at least ten rounds'
     dev = torch.device('cuda:0')
+    if args.wrt != 'pulse':
+        rest = torch.tensor(REST, dtype=torch.float32, device=dev)
+        res = main_wrt(args, dev, lambda A, B, L, w: (fused.ab_steadystate(
+            A, B, rest=rest, T1=L['T1'], T2=L['T2'], Δf=L['Δf']) * w).sum())
+        res['rest_s'] = REST
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as f:
+            json.dump(res, f, indent=1)
+        print('wrote', args.out)
+        return
     sp, p, b1, _, w = problem(args.n, args.nT, dev)
     rf, gr = p['rf'], p['gr']
     res = {'device': torch.cuda.get_device_name(0), 'n': args.n, 'nT': args.nT, 'dtype': 'float32', 'reps': args.reps,
