@@ -79,7 +79,9 @@ extern "C" {
  *      from rf and gr without Beff in memory, and the adjoint w.r.t. the pulse); mrphy_ab_rfgr_maps_bwd,
  *      mrphy_ab_rfgr_consts_bwd (that adjoint, which also returns the gradients w.r.t. loc, df and b1 -- and w.r.t. the
  *      step constants -- per spin); mrphy_ab_steadystate_fwd,
- *      mrphy_ab_steadystate_bwd (the steady state of a periodic pulse from A, B and a rest period, and its adjoint). */
+ *      mrphy_ab_steadystate_bwd (the steady state of a periodic pulse from A, B and a rest period, and its adjoint);
+ *      mrphy_ab_rfgr_mc_max_coils, mrphy_ab_rfgr_mc_bwd_workspace, mrphy_ab_rfgr_mc_fwd, mrphy_ab_rfgr_mc_bwd (A, B and
+ *      the adjoint w.r.t. the pulse under parallel transmit, 2 .. 8 coils with their b1 map). */
 #define MRPHY_ABI_VERSION 5
 
 #define MRPHY_F32      0  /* T = float,  CT = float                                          */
@@ -959,6 +961,52 @@ int mrphy_ab_rfgr_consts_bwd(int dtype,
                              void* work, size_t work_bytes,
                              int64_t N, int64_t nM, int64_t nT,
                              void* stream);
+/* K2ab-mc / K2abb-mc: mrphy_ab_rfgr_fwd / mrphy_ab_rfgr_bwd under parallel transmit -- rf (N|1, 2, nT, nC), b1 (N, nM, 2,
+ * nC) required, 1 <= nC <= mrphy_ab_rfgr_mc_max_coils(dtype) (8 for the fp32 codes, 4 for MRPHY_F64, whose
+ * capacity-8 adjoint would not fit the register file; 0 for an unknown code).  The field is the coil sum mrphy_rfgr2beff and mrphy_blochsim_rfgr_fwd form (one ascending FMA chain), so A, B
+ * are mrphy_beff2ab(mrphy_rfgr2beff(.)) bit for bit and B is mrphy_blochsim_rfgr_fwd(Mi = 0)'s.  ABck as above.  The adjoint
+ * returns grad_rf (N, 2, nT, nC) and grad_gr (N, 3, nT) (either may be NULL) from grad_A, grad_B (either may be NULL,
+ * not both): K2abb's sweep over the four columns, then the per-coil reduction over the spins of
+ * mrphy_blochsim_rfgr_mc_bwd -- deterministic.  `work` holds mrphy_ab_rfgr_mc_bwd_workspace() bytes, which IS
+ * mrphy_blochsim_rfgr_mc_bwd_workspace(): the same rows [gr_x, gr_y, gr_z, (re, im) x nC] per persistent wave.
+ * Both refuse, before anything is launched, with MRPHY_EINVAL what the one-coil entry points refuse, a coil count
+ * outside 1 .. max_coils and a NULL b1; the adjoint also nT not a whole number of segments and both cotangents NULL, and
+ * with MRPHY_ENOSPC a workspace shorter than the query's.  An empty problem (N*nM == 0; the adjoint: N*nM*nT == 0) is a
+ * success that writes nothing; the forward at nT == 0 writes A = I, B = 0.  The gradients w.r.t. the spin-side operands
+ * and the step constants have no parallel-transmit build. */
+int mrphy_ab_rfgr_mc_max_coils(int dtype);
+size_t mrphy_ab_rfgr_mc_bwd_workspace(int dtype, int64_t N, int64_t nM, int64_t nT, int64_t nC);
+int mrphy_ab_rfgr_mc_fwd(int dtype,
+                         const void* rf, int64_t rf_sn,
+                         const void* gr, int64_t gr_sn,
+                         const void* loc,
+                         const void* df, int64_t df_sn, int64_t df_sm,
+                         const void* gamma, int64_t gamma_sn, int64_t gamma_sm,
+                         const void* b1,
+                         const void* g,  int64_t g_sn,  int64_t g_sm,
+                         const void* E1, int64_t E1_sn, int64_t E1_sm,
+                         const void* E2, int64_t E2_sn, int64_t E2_sm,
+                         const void* E1m1,
+                         void* A, void* B, void* ABck, int64_t ck_every,
+                         int64_t N, int64_t nM, int64_t nT, int64_t nC,
+                         void* stream);
+int mrphy_ab_rfgr_mc_bwd(int dtype,
+                         const void* ABck,
+                         const void* rf, int64_t rf_sn,
+                         const void* gr, int64_t gr_sn,
+                         const void* loc,
+                         const void* df, int64_t df_sn, int64_t df_sm,
+                         const void* gamma, int64_t gamma_sn, int64_t gamma_sm,
+                         const void* b1,
+                         const void* g,  int64_t g_sn,  int64_t g_sm,
+                         const void* E1, int64_t E1_sn, int64_t E1_sm,
+                         const void* E2, int64_t E2_sn, int64_t E2_sm,
+                         const void* E1m1,
+                         const void* grad_A, const void* grad_B,
+                         void* grad_rf, void* grad_gr,
+                         void* work, size_t work_bytes,
+                         int64_t N, int64_t nM, int64_t nT, int64_t nC,
+                         void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Kss  the steady state of a sequence that repeats every period: a rest of duration `rest` -- free precession exactly

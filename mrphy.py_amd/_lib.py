@@ -95,6 +95,10 @@ PROTOTYPES = {
     'mrphy_ab_rfgr_bwd': (_int, _FUSED + [_vp, _vp, _vp, _vp, _vp, _sz] + [_i64] * 3 + [_vp]),
     'mrphy_ab_rfgr_maps_bwd': (_int, _FUSED + [_vp] * 7 + [_vp, _sz] + [_i64] * 3 + [_vp]),
     'mrphy_ab_rfgr_consts_bwd': (_int, _FUSED + [_vp] * 8 + [_vp, _sz] + [_i64] * 3 + [_vp]),
+    'mrphy_ab_rfgr_mc_max_coils': (_int, [_int]),
+    'mrphy_ab_rfgr_mc_bwd_workspace': (_sz, [_int] + [_i64] * 4),
+    'mrphy_ab_rfgr_mc_fwd': (_int, [_int] + _PULSE_OPS + [_vp, _vp, _vp, _i64] + [_i64] * 4 + [_vp]),
+    'mrphy_ab_rfgr_mc_bwd': (_int, _FUSED + [_vp, _vp, _vp, _vp, _vp, _sz] + [_i64] * 4 + [_vp]),
     'mrphy_ab_steadystate_fwd': (_int, [_int, _vp, _vp, _vp, _i64] + _BC * 3 + [_vp, _i64, _i64, _vp]),
     'mrphy_ab_steadystate_bwd': (_int, [_int, _vp, _vp, _vp, _vp, _i64] + _BC * 3 + [_vp, _vp, _vp, _i64, _i64, _vp]),
     'mrphy_blochsim_ab': (_int, [_int, _vp, _vp, _vp, _vp, _i64, _vp]),
@@ -118,6 +122,10 @@ UNITS = [(f, m) for f, masks in (
     ('tu_fused_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_fused_maps_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_fused_consts_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
+    ('tu_ab_rfgr_mc8_bwd.hip', (_F32, _C64, _P, _PC64)),          # fp64 stops at 4 coils (geom.hpp: AB_MC_MAXC_F64)
+    ('tu_ab_rfgr_mc4_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
+    ('tu_ab_rfgr_mc2_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
+    ('tu_ab_rfgr_mc_fwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_ab_rfgr_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_ab_rfgr_maps_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_ab_rfgr_consts_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),

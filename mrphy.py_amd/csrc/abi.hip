@@ -167,6 +167,19 @@ int signal_bwd(bool mrx, bool consts, int dtype, const AdjointReq& r, const Puls
                                 : (r.nRx > 1 ? AdjBuild::MRX : AdjBuild::PLAIN);
     return dispatch_adjoint(b, dtype, r, in, stream);
 }
+
+// K2abb-mc: the unit of the smallest coil capacity 2, 4, 8 that holds nC (the caller has checked nC against the data
+// type's largest)
+template <typename T, typename CT>
+int ab_rfgr_mc_bwd(const void* ABck, const PulseOps& in, const void* gA, const void* gB, void* grf, void* ggr, void* work,
+                   int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st)
+{
+    if (nC <= 2) return run_ab_rfgr_mc_bwd<2, T, CT>(ABck, in, gA, gB, grf, ggr, work, N, nM, nT, nC, st);
+    if (nC <= 4) return run_ab_rfgr_mc_bwd<4, T, CT>(ABck, in, gA, gB, grf, ggr, work, N, nM, nT, nC, st);
+    if constexpr (ab_mc_max_coils(sizeof(T)) >= 8)
+        return run_ab_rfgr_mc_bwd<8, T, CT>(ABck, in, gA, gB, grf, ggr, work, N, nM, nT, nC, st);
+    return MRPHY_EINVAL;
+}
 }  // namespace
 
 // =============================================================================================
@@ -557,6 +570,49 @@ int mrphy_ab_rfgr_consts_bwd(int dtype, const void* ABck, MRPHY_PULSE_OPS_PARAMS
     MRPHY_AB_SPIN_BWD(true, grad_consts);
 }
 #undef MRPHY_AB_SPIN_BWD
+
+// K2ab-mc / K2abb-mc: the one-coil entry points' checks in their order; the coil count is a mode argument (refused on
+// an empty problem too), the b1 map a required pointer, and a short workspace is MRPHY_ENOSPC
+int mrphy_ab_rfgr_mc_max_coils(int dtype)
+{
+    if (check_common(dtype, 0, 0, 0)) return 0;
+    return ab_mc_max_coils(tsize(dtype));
+}
+
+size_t mrphy_ab_rfgr_mc_bwd_workspace(int dtype, int64_t N, int64_t nM, int64_t nT, int64_t nC)
+{
+    return mrphy_blochsim_rfgr_mc_bwd_workspace(dtype, N, nM, nT, nC);
+}
+
+int mrphy_ab_rfgr_mc_fwd(int dtype, MRPHY_PULSE_OPS_PARAMS, void* A, void* B, void* ABck, int64_t ck_every, int64_t N,
+                         int64_t nM, int64_t nT, int64_t nC, void* stream)
+{
+    if (int e = check_common(dtype, N, nM, nT)) return e;
+    if (N > 65535 || (ABck && (ck_every < 8 || ck_every % 8 != 0)) || nC < 1 || nC > mrphy_ab_rfgr_mc_max_coils(dtype))
+        return MRPHY_EINVAL;
+    if (N * nM == 0) return 0;
+    if (!A || !B) return MRPHY_EINVAL;
+    const PulseOps in = MRPHY_PULSE_OPS;
+    if (int e = check_ops(in, nT > 0, true)) return e;
+    hipStream_t st = (hipStream_t)stream;
+    MRPHY_DISPATCH(dtype, (run_ab_rfgr_mc_fwd<T, CT>(in, A, B, ABck, ck_every, N, nM, nT, nC, st)));
+}
+
+int mrphy_ab_rfgr_mc_bwd(int dtype, const void* ABck, MRPHY_PULSE_OPS_PARAMS, const void* grad_A, const void* grad_B,
+                         void* grad_rf, void* grad_gr, void* work, size_t work_bytes, int64_t N, int64_t nM, int64_t nT,
+                         int64_t nC, void* stream)
+{
+    if (int e = check_common(dtype, N, nM, nT)) return e;
+    if (N > 65535 || nT % SEG != 0 || nC < 1 || nC > mrphy_ab_rfgr_mc_max_coils(dtype))
+        return MRPHY_EINVAL;                                            // whole checkpoint segments only
+    if (N * nM * nT == 0) return 0;
+    if (!ABck || !work || (!grad_A && !grad_B)) return MRPHY_EINVAL;
+    const PulseOps in = MRPHY_PULSE_OPS;
+    if (int e = check_ops(in, true, true)) return e;
+    if (work_bytes < mrphy_ab_rfgr_mc_bwd_workspace(dtype, N, nM, nT, nC)) return MRPHY_ENOSPC;
+    hipStream_t st = (hipStream_t)stream;
+    MRPHY_DISPATCH(dtype, (ab_rfgr_mc_bwd<T, CT>(ABck, in, grad_A, grad_B, grad_rf, grad_gr, work, N, nM, nT, nC, st)));
+}
 
 int mrphy_beff2ab(int dtype, const void* Beff,
                   const void* g, int64_t g_sn, int64_t g_sm,

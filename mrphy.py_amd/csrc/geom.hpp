@@ -22,6 +22,12 @@ constexpr int64_t SIG_MAX_WAVES = 256 * 16;       // K2s (signal forward): 8 / 1
 constexpr int SIG_MAX_RX_F32 = 8, SIG_MAX_RX_F64 = 8;   // receive coils per launch of the signal kernels
 constexpr int K2B_MAXC = 8;                       // fused adjoint: largest coil capacity
 constexpr int64_t K2B_MC_MAX_WAVES = 256 * 8;     // 18 KB of LDS per wave -> 8 per CU = 2 per SIMD
+// K2ab-mc / K2abb-mc (k_ab_rfgr_mc.hpp): the largest coil capacity built (2, 4, 8) per data type, forward and adjoint
+// alike; never above K2B_MAXC, whose workspace rows and persistent waves the adjoint shares
+// (fp64 stops at 4: K2abb is at 443-464 VGPRs there, the capacity-8 adjoint would need a private segment)
+constexpr int AB_MC_MAXC_F32 = 8, AB_MC_MAXC_F64 = 4;
+constexpr int ab_mc_max_coils(size_t tsize) { return tsize == 8 ? AB_MC_MAXC_F64 : AB_MC_MAXC_F32; }
+static_assert(AB_MC_MAXC_F32 <= K2B_MAXC && AB_MC_MAXC_F64 <= K2B_MAXC, "K2abb-mc takes K2b-mc's workspace");
 constexpr int BWD_MAXC = 32;                      // K0 adjoint: largest coil capacity of the one-pass kernels
 
 // broadcastable per-spin constant (see mrphy_hip.h): element (n, s) at p[n * sn + s * sm]

@@ -91,6 +91,16 @@ template <bool CONSTS, typename T, typename CT>
 int run_ab_rfgr_spin_bwd(const void* ABck, PulseOps in, const void* gA, const void* gB, void* grf, void* ggr, void* gloc,
                          void* gBz, void* gb1, void* gC, void* work, int64_t N, int64_t nM, int64_t nT, hipStream_t st);
 
+// K2ab-mc / K2abb-mc (tu_ab_rfgr_mc_fwd.hip; tu_ab_rfgr_mc2 / 4 / 8_bwd.hip, one unit per coil capacity MC >= nC): the same
+// under parallel transmit, rf (N|1, 2, nT, nC), b1 (N, nM, 2, nC) not null, 1 <= nC <= ab_mc_max_coils (geom.hpp)
+template <typename T, typename CT>
+int run_ab_rfgr_mc_fwd(PulseOps in, void* A, void* B, void* ABck, int64_t ck_every, int64_t N, int64_t nM, int64_t nT,
+                       int64_t nC, hipStream_t st);
+
+template <int MC, typename T, typename CT>
+int run_ab_rfgr_mc_bwd(const void* ABck, PulseOps in, const void* gA, const void* gB, void* grf, void* ggr, void* work,
+                       int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st);
+
 template <typename T, typename CT>
 int run_beff2ab(const void* Beff, Bc g, Bc E1, Bc E2, const void* E1m1, void* A, void* B, void* hist,
                 int64_t N, int64_t nM, int64_t nT, hipStream_t st);

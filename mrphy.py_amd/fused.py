@@ -37,6 +37,9 @@ each step's field and rotation (K2ab), and the gradients w.r.t. ``rf`` and ``gr`
 four columns' checkpoints (K2abb) -- again without ``Beff``, a history or ``grad_Beff`` in memory.  The same sweep gives
 the gradients w.r.t. ``loc``, ``Δf``, ``b1Map`` and ``γ_beff`` (``mrphy_ab_rfgr_maps_bwd``) and w.r.t. ``T1``, ``T2``, ``γ``,
 ``dt`` or the entries of ``consts=`` (``mrphy_ab_rfgr_consts_bwd``), as K2b's MAPS and CONSTS builds do for ``blochsim_rfgr``.
+Parallel transmit (``rf`` `(N,xy,nT,nCoils)` with a ``b1Map``, up to ``mrphy_ab_rfgr_mc_max_coils`` coils: 8 in fp32, 4
+in fp64) has kernels of its own for ``A, B`` and the pulse gradient (K2ab-mc / K2abb-mc, ``mrphy_ab_rfgr_mc_fwd`` /
+``_mc_bwd``); more coils, and map or constants' gradients under parallel transmit, compose ``rfgr2beff`` + ``beff2ab``.
 
 :func:`ab_steadystate` solves ``(I - A F) Mss = A f + B`` per spin for the magnetisation of a sequence that repeats the
 pulse ``A, B`` after a rest ``F, f`` (``sims.freeprec``), with an adjoint w.r.t. ``A``, ``B`` and the rest's operands
@@ -336,8 +339,11 @@ class AbRfGrHIP(Function):
 
     Hargreaves' ``A`` `(N, *Nd, xyz, 3)`, ``B`` `(N, *Nd, xyz)` of the pulse on the spins (``mrphy_ab_rfgr_fwd``), one
     transmit coil; ``E1 = E2 = E1_1 = None`` is no relaxation.  Differentiable w.r.t. ``rf`` and ``gr``
-    (``mrphy_ab_rfgr_bwd``); either output may go without a cotangent.  ``want_ckpt`` as in :class:`BlochSimRfGrHIP`:
-    decided by the caller (:func:`_decide_ab_route`), and the pulse length is then a whole number of segments.
+    (``mrphy_ab_rfgr_bwd``); either output may go without a cotangent.  Several transmit coils (``pulse_on_spins.nC > 1``,
+    which the caller has checked against ``mrphy_ab_rfgr_mc_max_coils``) run ``mrphy_ab_rfgr_mc_fwd`` / ``_mc_bwd`` instead:
+    the same checkpoints, ``grad_rf`` `(N, 2, nT, nC)` folded to ``rf``'s own shape, the pulse gradient only.
+    ``want_ckpt`` as in :class:`BlochSimRfGrHIP`: decided by the caller (:func:`_decide_ab_route`), and the pulse length
+    is then a whole number of segments.
 
     ``loc``, ``Δf``, ``b1Map``, ``γ_beff``: the caller's own tensors, handed over only when one of them wants a gradient,
     as to :class:`BlochSimRfGrHIP`; ``γ2πdt``, ``E1``, ``E2``, ``E1_1`` that require grad likewise.  The backward makes ONE
@@ -357,11 +363,13 @@ class AbRfGrHIP(Function):
         ABck = torch.empty((-(-p.nT // ck), 4, p.N * p.nM, 3), dtype=dtype, device=device) if want_ckpt else None
         A = torch.empty((p.N,) + p.Nd + (3, 3), dtype=dtype, device=device)
         B = torch.empty((p.N,) + p.Nd + (3,), dtype=dtype, device=device)
+        mc = p.nC != 1                          # parallel transmit: the `_mc_` entry points, which take the coil count
+        name = 'mrphy_ab_rfgr_mc_fwd' if mc else 'mrphy_ab_rfgr_fwd'
         with torch.cuda.device(device):
-            rc = lib.mrphy_ab_rfgr_fwd(code, *p.k0_args(), *consts, A.data_ptr(), B.data_ptr(),
-                                       ABck.data_ptr() if want_ckpt else None, ck if want_ckpt else 0,
-                                       p.N, p.nM, p.nT, _host.current_stream(device))
-        _lib.check(rc, 'mrphy_ab_rfgr_fwd')
+            rc = getattr(lib, name)(code, *p.k0_args(), *consts, A.data_ptr(), B.data_ptr(),
+                                    ABck.data_ptr() if want_ckpt else None, ck if want_ckpt else 0,
+                                    p.N, p.nM, p.nT, *((p.nC,) if mc else ()), _host.current_stream(device))
+        _lib.check(rc, name)
         ctx.set_materialize_grads(False)
         if want_ckpt:
             ctx.save_for_backward(ABck)
@@ -384,7 +392,7 @@ class AbRfGrHIP(Function):
         gA, gB = (None if x is None else x.to(dtype).contiguous() for x in (grad_A, grad_B))
         need_γb = want['γ_beff'] and p.df is not None          # without Δf the field does not depend on γ_beff
         full = (p.N,) + p.Nd
-        outs = dict(grf=(want['rf'], (p.N, 2, p.nT, 1)), ggr=(want['gr'], (p.N, 3, p.nT)),
+        outs = dict(grf=(want['rf'], (p.N, 2, p.nT, p.nC)), ggr=(want['gr'], (p.N, 3, p.nT)),
                     gloc=(want['loc'], full + (3,)), gBz=(want['Δf'] or need_γb, full), gb1=(want['b1Map'], full + (2,)),
                     gC=(any(want[k] for k in _CONSTS), full + (4,)))
         raw = {k: torch.empty(shape, dtype=dtype, device=device) if w else None for k, (w, shape) in outs.items()}
@@ -397,14 +405,19 @@ class AbRfGrHIP(Function):
             # the cheapest build that serves what is wanted; the CONSTS build forms the map sums too
             spin = (('gloc', 'gBz', 'gb1', 'gC') if raw['gC'] is not None else
                     ('gloc', 'gBz', 'gb1') if any(raw[k] is not None for k in ('gloc', 'gBz', 'gb1')) else ())
-            name = 'mrphy_ab_rfgr_' + {0: '', 3: 'maps_', 4: 'consts_'}[len(spin)] + 'bwd'
-            nbytes = int(lib.mrphy_blochsim_rfgr_bwd_workspace(s.code, p.N, p.nM, p.nT))
+            # parallel transmit: the pulse gradient alone (_decide_ab_route), per-coil sums in the workspace
+            mc = p.nC != 1
+            assert not (mc and spin), "fused.ab_rfgr: no map or constants' gradient under parallel transmit"
+            name = 'mrphy_ab_rfgr_' + ('mc_' if mc else {0: '', 3: 'maps_', 4: 'consts_'}[len(spin)]) + 'bwd'
+            nbytes = int(lib.mrphy_ab_rfgr_mc_bwd_workspace(s.code, p.N, p.nM, p.nT, p.nC) if mc
+                         else lib.mrphy_blochsim_rfgr_bwd_workspace(s.code, p.N, p.nM, p.nT))
             work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
             ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
             with torch.cuda.device(device):
                 rc = getattr(lib, name)(s.code, ABck.data_ptr(), *p.k0_args(), *s.consts, ptr(gA), ptr(gB),
                                         ptr(raw['grf']), ptr(raw['ggr']), *(ptr(raw[k]) for k in spin),
-                                        work.data_ptr(), work.numel(), p.N, p.nM, p.nT, _host.current_stream(device))
+                                        work.data_ptr(), work.numel(), p.N, p.nM, p.nT, *((p.nC,) if mc else ()),
+                                        _host.current_stream(device))
             _lib.check(rc, name)
         g = {k: _fold_pulse_grad(raw[r], s.likes[k][0], s.likes[k][1], k == 'rf' and p.b1 is None)
              for k, r in (('rf', 'grf'), ('gr', 'ggr')) if raw[r] is not None}
@@ -445,16 +458,19 @@ def _ab_spin_fused(dtype, consts_grad):
     return True
 
 
-def _decide_ab_route(*, nT, seg, one_coil, pulse_grad, maps_grad, consts_grad, spin_fused=False):
+def _decide_ab_route(*, nT, seg, one_coil, pulse_grad, maps_grad, consts_grad, spin_fused=False, ptx_fused=False):
     r"""The route of :func:`ab_rfgr` as a function of plain facts (``maps_grad``: a gradient w.r.t. ``loc``, ``Δf``,
     ``b1Map`` or a ``γ_beff`` that multiplies a ``Δf``; ``spin_fused``: the fused adjoint's MAPS / CONSTS builds serve
     the map and constants' gradients that are wanted -- :func:`ab_rfgr` says so, the default is the adjoint w.r.t. the
-    pulse alone): ``('fused', want_ckpt)`` -- one transmit coil and either no gradient or gradients the fused adjoint
-    serves over whole checkpoint segments; ``('split', n1)`` -- one coil, such gradients, more than one segment's steps
-    and a ragged last one: the first ``n1`` steps fused, the tail composed; ``('composed', None)`` -- everything else:
-    ``rfgr2beff`` + ``beff2ab``, whose autograd serves every operand."""
+    pulse alone; ``ptx_fused``: several transmit coils with their ``b1Map``, no more than the parallel-transmit kernels
+    K2ab-mc / K2abb-mc take -- the default keeps parallel transmit composed): ``('fused', want_ckpt)`` -- one transmit
+    coil and either no gradient or gradients the fused adjoint serves over whole checkpoint segments, or such coils and
+    at most a pulse gradient; ``('split', n1)`` -- such gradients, more than one segment's steps and a ragged last one:
+    the first ``n1`` steps fused, the tail composed; ``('composed', None)`` -- everything else (a map or constants'
+    gradient under parallel transmit among it): ``rfgr2beff`` + ``beff2ab``, whose autograd serves every operand."""
     spin_grad = maps_grad or consts_grad
-    if not one_coil or (spin_grad and not spin_fused):
+    ptx = ptx_fused and not one_coil and not spin_grad
+    if not (one_coil or ptx) or (spin_grad and not spin_fused):
         return 'composed', None
     if not (pulse_grad or spin_grad):
         return 'fused', False
@@ -795,8 +811,16 @@ def ab_rfgr(
     Gradients w.r.t. ``loc``, ``Δf``, ``b1Map``, ``γ_beff`` and w.r.t. ``T1``, ``T2``, ``γ``, ``dt`` (or the entries of
     ``consts=``) come out of the same adjoint sweep, summed over time per spin in a fixed order (K2abb's MAPS and CONSTS
     builds: one forward, one adjoint call, still no ``Beff``); on the split route autograd adds the two parts'.  ``A, B``
-    are the bits of the call that does not differentiate them.  Parallel transmit and any gradient of a pulse with
-    fewer than 16 steps compose ``rfgr2beff`` + ``beff2ab`` (HIP kernels as well), whose autograd serves every operand.
+    are the bits of the call that does not differentiate them.
+
+    Parallel transmit -- ``rf`` `(N ⊻ 1, xy, nT, nCoils)` with a ``b1Map`` `(N ⊻ 1, *Nd ⊻ 1, xy, nCoils)`, 2 coils up to
+    ``mrphy_ab_rfgr_mc_max_coils`` (8 in fp32, 4 in fp64) -- runs the same two kernels with the coil sum in the field
+    (K2ab-mc) and a per-coil reduction over the spins (K2abb-mc): ``A, B`` still bit for bit ``beff2ab(rfgr2beff(.))``,
+    ``grad_rf`` in the shape of ``rf`` and ``grad_gr`` deterministic, the same split of a ragged length, no ``Beff`` in
+    memory.  What stays composed (``rfgr2beff`` + ``beff2ab``, HIP kernels as well, whose autograd serves every operand):
+    more coils than that capacity; multi-coil ``rf`` without a ``b1Map`` (the coils add); gradients w.r.t. ``loc``, ``Δf``,
+    ``b1Map``, ``γ_beff`` or ``T1``, ``T2``, ``γ``, ``dt`` under parallel transmit; any gradient of a pulse with fewer than 16
+    steps.
     """
     from . import beffective, sims
     _host.require_device_tensor(loc, 'loc')
@@ -814,7 +838,9 @@ def ab_rfgr(
         nT=p.nT, seg=int(lib.mrphy_blochsim_rfgr_ck_every()),
         one_coil=p.nC == 1 and (rf.ndim == 3 or b1Map is not None or rf.shape[-1] == 1),
         pulse_grad=any(rq(x) for x in (rf, gr)), maps_grad=maps_grad, consts_grad=consts_grad,
-        spin_fused=_ab_spin_fused(p.dtype, consts_grad))
+        spin_fused=_ab_spin_fused(p.dtype, consts_grad),
+        ptx_fused=b1Map is not None and 2 <= p.nC <= int(lib.mrphy_ab_rfgr_mc_max_coils(
+            _lib.F64 if p.dtype == torch.float64 else _lib.F32)))
     if route == 'split':
         # whole segments fused, the tail of <= 15 steps composed; the step map of the tail acts on the head's
         A1, B1 = ab_rfgr(rf[:, :, :out], gr[:, :, :out], loc, **kw)
@@ -966,7 +992,9 @@ def steadystate_rfgr(
 
     Every route of :func:`ab_rfgr` (fused, split, composed) serves it, so gradients reach every operand ``ab_rfgr``
     serves -- with one transmit coil ``T1, T2, Δf, b1Map, loc`` as well as ``rf, gr`` through the fused adjoint, without
-    ``Beff`` in memory -- and ``rest, T1, T2, Δf`` / ``Δf_rest`` through the rest period as well: ``T1`` and ``T2``, shared
+    ``Beff`` in memory; under parallel transmit (2 coils up to ``ab_rfgr``'s capacity, with their ``b1Map``) ``rf`` and ``gr``
+    through its parallel-transmit adjoint, the spin-side operands through the composed route -- and ``rest, T1, T2, Δf`` /
+    ``Δf_rest`` through the rest period as well: ``T1`` and ``T2``, shared
     by the pulse and the rest, receive the sum of both paths.  fp32: the solve itself runs in
     fp64, but ``Mss`` inherits the rounding of the fp32 ``A`` amplified by the conditioning of ``I - A F``, about
     ``1 / (1 - exp(-rest/T1))``: relative errors of a few 1e-6 at a factor of 50, 3e-5 at 170 -- for any fp32 route,

@@ -1,6 +1,7 @@
 r"""What ``fused.ab_rfgr`` costs next to the two ways the same ``A, B`` were available before it.
 
-    python tools/ab_rfgr_timing.py [--n 64] [--nT 1024] [--reps 10] [--wrt pulse|maps|consts|all] [--out FILE.json]
+    python tools/ab_rfgr_timing.py [--n 64] [--nT 1024] [--reps 10] [--wrt pulse|maps|consts|all] [--coils 1]
+                                   [--out FILE.json]
 
 Shape: n^3 spins x nT steps, fp32, one transmit coil with a ``b1Map`` and per-spin ``T1 / T2`` (the synthetic cube and
 pulse of ``mrphy_amd.synth``), in ``precision('precise')`` and ``('fast')``, the forward alone (``torch.no_grad``) and
@@ -24,6 +25,11 @@ in (a); K2b's in (b), whose constants are then formed from ``T1, T2`` by differe
 builds).  The default output is then ``profiles/ab_rfgr_spin_grads_timing.json``, which also says whether (a)'s median lies
 below (c)'s by more than the rounds' min - max spread (the larger of the two): the condition for (a) to replace (c).
 These runs form the step constants with torch's own ``exp`` on the device (``constants_on('native')``), all three alike.
+
+``--coils N`` (default 1: everything above) is the default run under parallel transmit: ``rf`` `(1, xy, nT, N)` with a
+``b1Map`` `(1, nM, xy, N)`, gradients w.r.t. the pulse.  (a) is then K2ab-mc / K2abb-mc up to the coil capacity, (b) K2 / K2b's
+parallel-transmit builds at batch 4, (c) the composed route ``ab_rfgr`` took under parallel transmit before (a) had
+those kernels.  The default output is ``profiles/ab_rfgr_ptx_timing.json``, one entry ``coils<N>`` per coil count measured.
 """
 import argparse
 import json
@@ -39,12 +45,18 @@ import mrphy_amd  # noqa: E402
 from mrphy_amd import beffective, fused, sims, synth  # noqa: E402
 
 
-def problem(n, nT, dev):
+def problem(n, nT, dev, coils=1):
     sp = synth.cube_spins(n, dtype=torch.float32, device=dev)
     p = synth.pulse(nT, dtype=torch.float32, device=dev)
     nM = n ** 3
     gen = torch.Generator().manual_seed(5)
     b1 = (torch.rand((1, nM, 2), generator=gen, dtype=torch.float64) * 0.4 + 0.8).float().to(dev)
+    if coils > 1:
+        # parallel transmit: every coil plays the synthetic waveform at a weight of its own (they add up to about one
+        # coil's), through a map of its own
+        wc = ((torch.rand(coils, generator=gen, dtype=torch.float64) * 0.5 + 0.75) / coils).float().to(dev)
+        p = dict(p, rf=(p['rf'][..., None] * wc).contiguous())
+        b1 = (torch.rand((1, nM, 2, coils), generator=gen, dtype=torch.float64) * 0.4 + 0.8).float().to(dev)
     idx = lambda m: torch.arange(m, dtype=torch.float64)  # noqa: E731
     wA = torch.sin(idx(nM * 9) * 0.61 + 1).reshape(1, nM, 3, 3).float().to(dev)
     wB = torch.sin(idx(nM * 3) * 0.37 + 0.3).reshape(1, nM, 3).float().to(dev)
@@ -229,10 +241,13 @@ def main():
     ap.add_argument('--nT', type=int, default=1024)
     ap.add_argument('--reps', type=int, default=10)
     ap.add_argument('--wrt', choices=sorted(WRT), default='pulse')
+    ap.add_argument('--coils', type=int, default=1)
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
-    args.out = args.out or os.path.join(ROOT, 'profiles', 'ab_rfgr_timing.json' if args.wrt == 'pulse'
-                                        else 'ab_rfgr_spin_grads_timing.json')
+    assert args.coils >= 1 and (args.coils == 1 or args.wrt == 'pulse'), \
+        'parallel transmit: gradients w.r.t. the pulse only (the others compose in (a) as well)'
+    args.out = args.out or os.path.join(ROOT, 'profiles', 'ab_rfgr_ptx_timing.json' if args.coils > 1 else
+                                        'ab_rfgr_timing.json' if args.wrt == 'pulse' else 'ab_rfgr_spin_grads_timing.json')
     assert torch.cuda.is_available(), 'tools/ab_rfgr_timing.py measures on the GPU'
     assert args.reps >= 10, 'the median of at least ten rounds'
     dev = torch.device('cuda:0')
@@ -243,10 +258,12 @@ def main():
             json.dump(res, f, indent=1)
         print('wrote', args.out)
         return
-    sp, p, b1, wA, wB = problem(args.n, args.nT, dev)
+    sp, p, b1, wA, wB = problem(args.n, args.nT, dev, args.coils)
     rf, gr = p['rf'], p['gr']
     res = {'device': torch.cuda.get_device_name(0), 'n': args.n, 'nT': args.nT, 'dtype': 'float32', 'reps': args.reps,
            'beff_bytes': 12 * args.n ** 3 * args.nT, 'modes': {}}
+    if args.coils > 1:
+        res['coils'] = args.coils
     for mode in ('precise', 'fast'):
         with mrphy_amd.precision(mode):
             runs, last = contenders(sp, p, b1, wA, wB)
@@ -284,6 +301,13 @@ def main():
                 print(mode, 'fwd+bwd' if grad else 'fwd', {k: round(v['median_ms'], 3) for k, v in what.items()
                                                            if isinstance(v, dict)}, flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    if args.coils > 1:
+        # one file for every coil count measured: {'coils4': ..., 'coils8': ...}
+        try:
+            with open(args.out) as f:
+                res = dict(json.load(f), **{f'coils{args.coils}': res})
+        except (OSError, ValueError):
+            res = {f'coils{args.coils}': res}
     with open(args.out, 'w') as f:
         json.dump(res, f, indent=1)
     print('wrote', args.out)
