@@ -81,7 +81,8 @@ extern "C" {
  *      step constants -- per spin); mrphy_ab_steadystate_fwd,
  *      mrphy_ab_steadystate_bwd (the steady state of a periodic pulse from A, B and a rest period, and its adjoint);
  *      mrphy_ab_rfgr_mc_max_coils, mrphy_ab_rfgr_mc_bwd_workspace, mrphy_ab_rfgr_mc_fwd, mrphy_ab_rfgr_mc_bwd (A, B and
- *      the adjoint w.r.t. the pulse under parallel transmit, 2 .. 8 coils with their b1 map). */
+ *      the adjoint w.r.t. the pulse under parallel transmit, 2 .. 8 coils with their b1 map); mrphy_ab_train_fwd,
+ *      mrphy_ab_train_bwd (the transient of a pulse repeated K times with an RF phase per repetition, and its adjoint). */
 #define MRPHY_ABI_VERSION 5
 
 #define MRPHY_F32      0  /* T = float,  CT = float                                          */
@@ -1049,6 +1050,52 @@ int mrphy_ab_steadystate_bwd(int dtype, const void* A, const void* B, const void
                              const void* df, int64_t df_sn, int64_t df_sm,
                              void* grad_A, void* grad_B, void* grad_consts,
                              int64_t N, int64_t nM, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Ktr  the transient of the same sequence over its first K repetitions, the RF phase phi_k (rad) changing from one
+ * to the next.  Per spin, from M_0 = Mi, for k = 0 .. K-1:
+ *     M-      = F M_k + f                           the rest, F and f exactly as Kss forms them (above)
+ *     M_{k+1} = Rz(phi_k) [ A Rz(-phi_k) M- + B ]   the pulse played with its rf multiplied by e^{i phi_k}
+ * with Rz(phi) = [[c,-s,0],[s,c,0],[0,0,1]].  Record k is M_{k+1}, the state right after pulse k (as Mss of Kss), and
+ * the records are stored TIME-MAJOR: Mt (K,N,nM,3).  A, B, rest, T1, T2, df and their rules as in Kss.  Mi (N|1,nM|1,3)
+ * of the data type with ELEMENT strides Mi_sn, Mi_sm (0 broadcasts; xyz contiguous), NULL = (0,0,1).  cs (N|1,K,2):
+ * cos phi_k, sin phi_k, ALWAYS fp64, contiguous over (K,2) with element stride cs_sn between batch entries
+ * (0 broadcasts); NULL = all phases zero.  One thread per spin, blockIdx.y = the batch entry: N <= 65535.  Whatever the
+ * data type, all arithmetic is fp64, the state carried from one repetition to the next stays fp64, and each record is
+ * rounded once on its store.
+ *
+ * Ktrb  its adjoint, for the cotangents grad_Mt (K,N,nM,3) of the records.  It walks k downwards and reads M_{k+1} and
+ * M_k from Mt, the forward's own output (M_0 = Mi): nothing else is saved, nothing is recomputed forward.  From h = 0:
+ *     lambda = h + grad_Mt[k],   u = Rz(-phi_k) lambda,   p = Rz(-phi_k) M-,   M- = F M_k + f
+ *     grad_B (N,nM,3) += u,   grad_A (N,nM,3,3) += u p^T,   gM- = Rz(phi_k) A^T u
+ *     grad_phase (K,N,nM)[k] = (lambda_y M_x - lambda_x M_y) at M_{k+1} - (gM-_y M-_x - gM-_x M-_y)   PER SPIN: the
+ *         caller sums over the spins that share a phase
+ *     grad_consts (N,nM,4) = [dL/d rest, dL/d T1, dL/d T2, dL/d df] += the per-spin formulas of
+ *         mrphy_freeprec_bwd_consts at Mi := M_k, grad_Mo := gM-  (0 where the operand is NULL)
+ *     h = F^T gM-                                      and at the end grad_Mi (N,nM,3) = h.
+ * Every sum is private to its thread and runs in a fixed order: no workspace, no atomics, the same bits every run.
+ * Each of grad_A, grad_B, grad_consts, grad_Mi, grad_phase may be NULL, not all five.
+ * Both refuse before anything is launched: MRPHY_EINVAL for an unknown dtype, a negative size, N > 65535, a NULL
+ * required pointer (A, B, Mt, grad_Mt) or a breach of the operand rules of Kss; MRPHY_EALIGN for a pointer not aligned to
+ * its element size (cs: 8).  An empty problem (N*nM*K == 0) is a success that writes nothing, whatever the pointers are.
+ * ------------------------------------------------------------------------------------------- */
+int mrphy_ab_train_fwd(int dtype, const void* A, const void* B,
+                       const void* rest, int64_t rest_sn,
+                       const void* T1, int64_t T1_sn, int64_t T1_sm,
+                       const void* T2, int64_t T2_sn, int64_t T2_sm,
+                       const void* df, int64_t df_sn, int64_t df_sm,
+                       const void* Mi, int64_t Mi_sn, int64_t Mi_sm,
+                       const void* cs, int64_t cs_sn,
+                       void* Mt, int64_t N, int64_t nM, int64_t K, void* stream);
+int mrphy_ab_train_bwd(int dtype, const void* A, const void* B, const void* grad_Mt,
+                       const void* rest, int64_t rest_sn,
+                       const void* T1, int64_t T1_sn, int64_t T1_sm,
+                       const void* T2, int64_t T2_sn, int64_t T2_sm,
+                       const void* df, int64_t df_sn, int64_t df_sm,
+                       const void* Mi, int64_t Mi_sn, int64_t Mi_sm,
+                       const void* cs, int64_t cs_sn, const void* Mt,
+                       void* grad_A, void* grad_B, void* grad_consts, void* grad_Mi, void* grad_phase,
+                       int64_t N, int64_t nM, int64_t K, void* stream);
 
 int mrphy_blochsim_ab(int dtype, const void* M, const void* A, const void* B, void* Mo,
                       int64_t rows, void* stream);

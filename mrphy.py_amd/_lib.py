@@ -101,6 +101,9 @@ PROTOTYPES = {
     'mrphy_ab_rfgr_mc_bwd': (_int, _FUSED + [_vp, _vp, _vp, _vp, _vp, _sz] + [_i64] * 4 + [_vp]),
     'mrphy_ab_steadystate_fwd': (_int, [_int, _vp, _vp, _vp, _i64] + _BC * 3 + [_vp, _i64, _i64, _vp]),
     'mrphy_ab_steadystate_bwd': (_int, [_int, _vp, _vp, _vp, _vp, _i64] + _BC * 3 + [_vp, _vp, _vp, _i64, _i64, _vp]),
+    'mrphy_ab_train_fwd': (_int, [_int, _vp, _vp, _vp, _i64] + _BC * 3 + _BC + [_vp, _i64, _vp] + [_i64] * 3 + [_vp]),
+    'mrphy_ab_train_bwd': (_int, [_int, _vp, _vp, _vp, _vp, _i64] + _BC * 3 + _BC + [_vp, _i64, _vp] + [_vp] * 5
+                           + [_i64] * 3 + [_vp]),
     'mrphy_blochsim_ab': (_int, [_int, _vp, _vp, _vp, _vp, _i64, _vp]),
     'mrphy_blochsim_ab_bwd': (_int, [_int, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
@@ -146,6 +149,7 @@ UNITS = [(f, m) for f, masks in (
     ('tu_rfgr2beff_bwd.hip', (_F32, _F64)),
     ('tu_aux.hip', (None,)),
     ('tu_ab_steady.hip', (None,)),
+    ('tu_ab_train.hip', (None,)),
     ('abi.hip', (None,)),
 ) for m in masks]
 

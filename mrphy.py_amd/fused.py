@@ -45,6 +45,11 @@ in fp64) has kernels of its own for ``A, B`` and the pulse gradient (K2ab-mc / K
 pulse ``A, B`` after a rest ``F, f`` (``sims.freeprec``), with an adjoint w.r.t. ``A``, ``B`` and the rest's operands
 (Kss / Kssb); :func:`steadystate_rfgr` is that on top of :func:`ab_rfgr`: ``Mss(rf, gr)`` and its gradient in closed
 form instead of hundreds of simulated periods.
+
+:func:`ab_train` is the transient of the same sequence: the state right after each of the first ``K`` repetitions, the
+RF phase changing from one to the next (RF spoiling, phase-cycled bSSFP, a catalysed or inversion-prepared train), one
+thread per spin with the recursion carried in fp64 and the records as the only saved state (Ktr / Ktrb);
+:func:`train_rfgr` is that on top of :func:`ab_rfgr`.
 """
 from math import pi as π, prod  # noqa: F401
 from typing import NamedTuple, Optional
@@ -56,7 +61,8 @@ from torch.autograd import Function
 from . import _lib, _host
 from ._consts import γH, dt0
 
-__all__ = ['blochsim_rfgr', 'blochsim_rfgr_traj', 'signal_rfgr', 'ab_rfgr', 'ab_steadystate', 'steadystate_rfgr']
+__all__ = ['blochsim_rfgr', 'blochsim_rfgr_traj', 'signal_rfgr', 'ab_rfgr', 'ab_steadystate', 'steadystate_rfgr',
+           'ab_train', 'train_rfgr']
 
 
 def _forward_prep(lib, p, γ2πdt, E1, E2, E1_1, dtype, device, need):
@@ -1004,3 +1010,197 @@ def steadystate_rfgr(
         "steadystate_rfgr: a steady state needs relaxation -- `rest`, `T1` and `T2` are required"
     A, B = ab_rfgr(rf, gr, loc, Δf=Δf, b1Map=b1Map, γ_beff=γ_beff, T1=T1, T2=T2, γ=γ, dt=dt, consts=consts)
     return ab_steadystate(A, B, rest=rest, T1=T1, T2=T2, Δf=Δf if Δf_rest is None else Δf_rest)
+
+
+class AbTrainHIP(Function):
+    r"""``Mt = AbTrainHIP.apply(A, B, Mi, phase, rest, T1, T2, Δf, K)`` -- see :func:`ab_train`; ``Mt`` is time-major
+    `(K, N, *Nd, xyz)`.  The backward (``mrphy_ab_train_bwd``) reads the states from ``Mt`` itself: besides the inputs,
+    the output is all that is saved."""
+
+    @staticmethod
+    def _state_operands(a, Mi, phase):
+        r"""``(mi, cs)``: ``Mi`` `(N ⊻ 1, nM ⊻ 1, 3)` in the data type and the fp64 table ``(cos φ, sin φ)``
+        `(N ⊻ 1, K, 2)`, formed here once per call with torch ops; ``None`` for an absent operand."""
+        device, dtype = a.device, a.dtype
+        Nd = tuple(a.shape[1:-2])
+        mi = cs = None
+        if Mi is not None:
+            mi = Mi.detach().to(device=device, dtype=dtype)
+            if all(d == 1 for d in mi.shape[1:-1]):
+                mi = mi.reshape(mi.shape[0], 1, 3).contiguous()
+            else:
+                mi = mi.expand((mi.shape[0],) + Nd + (3,)).reshape(mi.shape[0], prod(Nd), 3).contiguous()
+        if phase is not None:
+            φ = phase.detach().to(device=device, dtype=torch.float64)
+            cs = torch.stack((torch.cos(φ), torch.sin(φ)), dim=-1).contiguous()
+        return mi, cs
+
+    @staticmethod
+    def _state_args(mi, cs, N):
+        r"""The arguments ``Mi .. cs_sn`` of the two entry points: pointers and element strides, 0 where it broadcasts."""
+        over_n = lambda x: x.stride(0) if (x.shape[0] == N and N > 1) else 0  # noqa: E731
+        return ((None, 0, 0) if mi is None else (mi.data_ptr(), over_n(mi), 3 if mi.shape[1] > 1 else 0)) + \
+               ((None, 0) if cs is None else (cs.data_ptr(), over_n(cs)))
+
+    @staticmethod
+    def forward(ctx, A, B, Mi, phase, rest, T1, T2, Δf, K):
+        lib = _lib.require_library()
+        device = A.device
+        a, b = A.detach().contiguous(), B.detach().contiguous()
+        N, Nd, nM, code, keep, args = AbSteadyStateHIP._operands(a, rest, T1, T2, Δf)
+        mi, cs = AbTrainHIP._state_operands(a, Mi, phase)
+        sargs = AbTrainHIP._state_args(mi, cs, N)
+        Mt = torch.empty((K,) + tuple(b.shape), dtype=b.dtype, device=device)
+        with torch.cuda.device(device):
+            rc = lib.mrphy_ab_train_fwd(code, a.data_ptr(), b.data_ptr(), *args, *sargs, Mt.data_ptr(), N, nM, K,
+                                        _host.current_stream(device))
+        _lib.check(rc, 'mrphy_ab_train_fwd')
+        del keep
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(a, b, Mt, mi, cs)
+        ctx.consts = (rest, T1, T2, Δf)
+        ctx.state = (Mi, phase, K)
+        return Mt
+
+    @staticmethod
+    def backward(ctx, grad_Mt):
+        from . import sims
+        need = ctx.needs_input_grad
+        consts = ctx.consts
+        Mi, phase, K = ctx.state
+        need_c = [w and c is not None for w, c in zip(need[4:8], consts)]
+        need_mi, need_φ = need[2] and Mi is not None, need[3] and phase is not None
+        if grad_Mt is None or not (need[0] or need[1] or need_mi or need_φ or any(need_c)):
+            return (None,) * 9
+        lib = _lib.require_library()
+        a, b, Mt, mi, cs = ctx.saved_tensors
+        device, dtype = a.device, a.dtype
+        N, Nd, nM, code, keep, args = AbSteadyStateHIP._operands(a, *consts)
+        sargs = AbTrainHIP._state_args(mi, cs, N)
+        g = grad_Mt.detach().to(dtype).contiguous()
+        # an empty problem launches nothing: its gradients are the zeros of a sum without terms
+        new = torch.zeros if N * nM * K == 0 else torch.empty
+        gA = new(a.shape, dtype=dtype, device=device) if need[0] else None
+        gB = new(b.shape, dtype=dtype, device=device) if need[1] else None
+        gC = new((N,) + Nd + (4,), dtype=dtype, device=device) if any(need_c) else None
+        gMi = new(b.shape, dtype=dtype, device=device) if need_mi else None
+        gφ = new((K, N, nM), dtype=dtype, device=device) if need_φ else None
+        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        with torch.cuda.device(device):
+            rc = lib.mrphy_ab_train_bwd(code, a.data_ptr(), b.data_ptr(), g.data_ptr(), *args, *sargs, Mt.data_ptr(),
+                                        ptr(gA), ptr(gB), ptr(gC), ptr(gMi), ptr(gφ), N, nM, K,
+                                        _host.current_stream(device))
+        _lib.check(rc, 'mrphy_ab_train_bwd')
+        del keep
+        gcs = tuple(sims._reduce_to_const(gC[..., i], c, N, Nd).to(c.device) if want else None
+                    for i, (c, want) in enumerate(zip(consts, need_c)))
+        if need_mi:
+            gMi = gMi.sum_to_size(tuple(Mi.shape)).to(device=Mi.device, dtype=Mi.dtype)
+        if need_φ:
+            # per spin from the kernel; the sum over the spins that share a phase, accumulated in fp64
+            gφ = torch.sum(gφ, dim=-1, dtype=torch.float64).T.sum_to_size(tuple(phase.shape))
+            gφ = gφ.to(device=phase.device, dtype=phase.dtype)
+        return (gA, gB, gMi, gφ) + gcs + (None,)
+
+
+def _train_length(n, phase, N):
+    r"""``K`` of :func:`ab_train` from ``n`` and ``phase``, checked as ``every`` of :func:`blochsim_rfgr_traj`."""
+    if n is not None and (isinstance(n, bool) or not isinstance(n, int) or n < 0):
+        raise ValueError(f"mrphy_amd: `n` must be an int >= 0, got {n!r}")
+    if phase is None:
+        if n is None:
+            raise ValueError("mrphy_amd: the number of repetitions is unknown: give `n`, `phase` (N ⊻ 1, K) or both")
+        return n
+    if phase.ndim != 2 or phase.shape[0] not in (1, N):
+        raise ValueError(f"mrphy_amd: `phase` {tuple(phase.shape)} must be (N ⊻ 1, K) with N = {N}")
+    if n is not None and n != phase.shape[1]:
+        raise ValueError(f"mrphy_amd: `n` = {n} disagrees with `phase` {tuple(phase.shape)}: K = {phase.shape[1]}")
+    return int(phase.shape[1])
+
+
+@_host.half_via_float
+def ab_train(
+    A: Tensor, B: Tensor, *, n: Optional[int] = None, Mi: Optional[Tensor] = None, phase: Optional[Tensor] = None,
+    rest: Optional[Tensor] = None, T1: Optional[Tensor] = None, T2: Optional[Tensor] = None,
+    Δf: Optional[Tensor] = None
+) -> Tensor:
+    r"""The transient of a sequence that repeats a pulse ``K`` times -- what :func:`ab_steadystate` is the limit of, and
+    what exists where no one-period steady state does (RF spoiling).  Per spin, from ``M_0 = Mi``, for ``k = 0 … K-1``:
+
+        ``M⁻ = F M_k + f``  -- the rest, ``sims.freeprec(M_k, rest, T1=T1, T2=T2, Δf=Δf)``, exactly as in
+        :func:`ab_steadystate`;
+
+        ``M_{k+1} = Rz(φ_k) [A Rz(-φ_k) M⁻ + B]``  -- the pulse ``A, B`` (:func:`ab_rfgr`, ``beffective.beff2ab``) played
+        with its ``rf`` multiplied by ``exp(iφ_k)``; ``Rz(φ) = [[c, -s, 0], [s, c, 0], [0, 0, 1]]``.
+
+    Record ``k`` is ``M_{k+1}``, the state right AFTER pulse ``k`` (as ``Mss`` of :func:`ab_steadystate`).
+
+    Usage:
+        ``Mt = ab_train(A, B, *, n, Mi, phase, rest, T1, T2, Δf)``
+    Inputs:
+        - ``A``: `(N, *Nd, xyz, 3)`, ``B``: `(N, *Nd, xyz)`, as :func:`ab_rfgr` returns them.
+    Optionals:
+        - ``n``: int, the number of repetitions ``K``; at least one of ``n`` and ``phase`` is given, and they agree.
+        - ``Mi``: `(N ⊻ 1, *Nd ⊻ 1, xyz)`; ``None`` = ``(0, 0, 1)``.
+        - ``phase``: `(N ⊻ 1, K)`, "rad"; ``None`` = all zeros.
+        - ``rest``, ``T1``, ``T2``, ``Δf``: shapes, broadcasting and absences exactly as :func:`ab_steadystate`
+          (``rest=None``: no rest period, ``T1, T2, Δf`` must then be ``None``; ``T1, T2`` both or neither).
+    Outputs:
+        - ``Mt``: `(N, *Nd, K, xyz)`.
+
+    Layout: the result is a view ``.movedim(0, -2)`` of time-major storage `(K, N, *Nd, 3)`, as
+    :func:`blochsim_rfgr_traj` returns its trajectory: each record is one contiguous block.  ``Mt.movedim(-2, 0)`` gives
+    the contiguous tensor back; a loss that keeps that layout hands its gradient to the adjoint without a copy.
+
+    One kernel, one thread per spin (``mrphy_ab_train_fwd``): all arithmetic in fp64 whatever the data type, the state
+    carried in fp64 from one repetition to the next, each record rounded once on its store; ``cos φ, sin φ`` are formed
+    once per call in fp64.  Differentiable w.r.t. ``A``, ``B``, ``Mi``, ``phase``, ``rest``, ``T1``, ``T2`` and ``Δf``
+    (``mrphy_ab_train_bwd``: one sweep down the repetitions that reads the states from ``Mt`` itself -- nothing per
+    repetition is kept besides the output --, deterministic).  In fp32 errors of ``A`` are amplified as in
+    :func:`ab_steadystate`, by about ``1 / (1 - contraction)``.
+
+    Out of scope: a flip angle or ``rest`` per repetition (the pulse is then not one ``A, B``); thinning the records
+    (``every``); the sum over the spins inside the kernel (a signal variant); demodulating the records by ``-φ_k`` (one
+    elementwise torch op on ``Mt``).
+    """
+    assert A.shape[-2:] == (3, 3) and tuple(B.shape) == tuple(A.shape[:-1]), \
+        f"A {tuple(A.shape)} must be (N, *Nd, 3, 3) and B {tuple(B.shape)} (N, *Nd, 3)"
+    N, Nd = A.shape[0], tuple(A.shape[1:-2])
+    K = _train_length(n, phase, N)
+    _host.require_device_tensor(A, 'A')
+    _host.require_device_tensor(B, 'B')
+    assert A.dtype == B.dtype and A.device == B.device, "A and B must share dtype and device"
+    assert (T1 is None) == (T2 is None)  # both or neither
+    assert rest is not None or (T1 is None and Δf is None), "T1, T2, Δf describe the rest period: give `rest`"
+    if Mi is not None:
+        assert Mi.ndim == 2 + len(Nd) and Mi.shape[-1] == 3 and Mi.shape[0] in (1, N) and \
+            all(m in (1, d) for m, d in zip(Mi.shape[1:-1], Nd)), \
+            f"Mi {tuple(Mi.shape)} must be (N ⊻ 1, *Nd ⊻ 1, 3) for spins {(N,) + Nd}"
+    return AbTrainHIP.apply(A, B, Mi, phase, rest, T1, T2, Δf, K).movedim(0, -2)
+
+
+@_host.half_via_float
+def train_rfgr(
+    rf: Tensor, gr: Tensor, loc: Tensor, *,
+    n: Optional[int] = None, Mi: Optional[Tensor] = None, phase: Optional[Tensor] = None,
+    rest: Optional[Tensor] = None, T1: Optional[Tensor] = None, T2: Optional[Tensor] = None,
+    Δf: Optional[Tensor] = None, b1Map: Optional[Tensor] = None, γ_beff: Tensor = γH,
+    γ: Tensor = γH, dt: Tensor = dt0, consts: Optional[dict] = None, Δf_rest: Optional[Tensor] = None
+) -> Tensor:
+    r"""The magnetisation right after each of the first ``K`` repetitions of a pulse, the RF phase ``phase[:, k]``
+    changing from one to the next (RF-spoiled gradient echo, phase-cycled bSSFP, the approach to a steady state), from
+    ``rf`` and ``gr``:
+
+        ``ab_train(*ab_rfgr(rf, gr, loc, ...), n=n, Mi=Mi, phase=phase, rest=rest, T1=T1, T2=T2,
+        Δf=Δf if Δf_rest is None else Δf_rest)``
+
+    built as :func:`steadystate_rfgr` is on :func:`ab_steadystate`.  Operands of the pulse exactly as :func:`ab_rfgr`,
+    those of the train as :func:`ab_train`; ``Δf_rest`` as in :func:`steadystate_rfgr`.  Relaxation is not required: a
+    transient exists without it.  Returns ``Mt`` `(N, *Nd, K, xyz)`, a ``.movedim(0, -2)`` view of time-major storage.
+
+    Every route of :func:`ab_rfgr` (fused, split, composed; parallel transmit) serves it, so gradients reach every
+    operand ``ab_rfgr`` serves, and ``Mi, phase, rest, T1, T2, Δf`` / ``Δf_rest`` through the train: ``T1`` and ``T2``,
+    shared by the pulse and the rest, receive the sum of both paths.  Out of scope as in :func:`ab_train`.
+    """
+    A, B = ab_rfgr(rf, gr, loc, Δf=Δf, b1Map=b1Map, γ_beff=γ_beff, T1=T1, T2=T2, γ=γ, dt=dt, consts=consts)
+    return ab_train(A, B, n=n, Mi=Mi, phase=phase, rest=rest, T1=T1, T2=T2, Δf=Δf if Δf_rest is None else Δf_rest)
