@@ -82,7 +82,10 @@ extern "C" {
  *      mrphy_ab_steadystate_bwd (the steady state of a periodic pulse from A, B and a rest period, and its adjoint);
  *      mrphy_ab_rfgr_mc_max_coils, mrphy_ab_rfgr_mc_bwd_workspace, mrphy_ab_rfgr_mc_fwd, mrphy_ab_rfgr_mc_bwd (A, B and
  *      the adjoint w.r.t. the pulse under parallel transmit, 2 .. 8 coils with their b1 map); mrphy_ab_train_fwd,
- *      mrphy_ab_train_bwd (the transient of a pulse repeated K times with an RF phase per repetition, and its adjoint). */
+ *      mrphy_ab_train_bwd (the transient of a pulse repeated K times with an RF phase per repetition, and its adjoint);
+ *      mrphy_train_signal_ck_every, mrphy_train_signal_max_rx, mrphy_train_signal_workspace, mrphy_train_signal_fwd,
+ *      mrphy_train_signal_bwd (the received signal of that transient: the transverse magnetisation of its records summed
+ *      over the spins, for up to 8 receive coils per launch, and its adjoint). */
 #define MRPHY_ABI_VERSION 5
 
 #define MRPHY_F32      0  /* T = float,  CT = float                                          */
@@ -1096,6 +1099,64 @@ int mrphy_ab_train_bwd(int dtype, const void* A, const void* B, const void* grad
                        const void* cs, int64_t cs_sn, const void* Mt,
                        void* grad_A, void* grad_B, void* grad_consts, void* grad_Mi, void* grad_phase,
                        int64_t N, int64_t nM, int64_t K, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Ktrs  the signal of Ktr's train: the same recursion, operands and rules (A, B, rest, T1, T2, df, Mi, cs as
+ * mrphy_ab_train_fwd takes them), the same fp64 arithmetic and therefore the same bits of the state, but instead of the
+ * records what nRx receive coils see of them, summed over the spins of each batch entry:
+ *     sig[n,0,k,c] = sum_s rx_re Mx - rx_im My,   sig[n,1,k,c] = sum_s rx_re My + rx_im Mx      at record k = M_{k+1}
+ * with rx (N,nM,2,nRx) of the data type, contiguous (the product of mrphy_signal_rfgr_fwd, no conjugate); rx NULL means
+ * weight (1,0) and needs nRx == 1.  1 <= nRx <= mrphy_train_signal_max_rx(dtype) (8 for both data types; 0 for another
+ * code): builds at the capacities 1, 2, 4, 8, pad coils of weight zero; a caller with more coils runs blocks of that
+ * many.  sig (N,2,K,nRx) of the data type.  Mlast (N,nM,3) of the data type, or NULL: the last record, the bits of
+ * Mt[K-1] of mrphy_ab_train_fwd.  ck: NULL, or fp64 (ceil(K/S),N*nM,3) with S = mrphy_train_signal_ck_every(): the state
+ * BEFORE repetitions 0, S, 2S, ... for the adjoint; with NULL nothing per spin is written besides Mlast.
+ * One wave per 64 spins of one batch entry, persistent over the tiles w, w+P, ... with P = min(ceil(nM/64), 2048): per
+ * repetition each lane's 2 nRx products (fp64) go into an LDS tile, a full tile is summed over the lanes in a fixed order
+ * and added into the wave's OWN row of work (P,N,2 nRx,K) fp64; a second pass sums the P rows in fixed order and rounds
+ * once into sig.  No atomics: the same inputs give the same bits, and coil c's samples are the bits of the one-coil
+ * call.  work_bytes >= mrphy_train_signal_workspace(dtype,N,nM,K,rows) = P*N*rows*K*8 with rows = 2 nRx (the adjoint:
+ * rows = 1, and only when grad_phase is wanted).
+ *
+ * Ktrsb  its adjoint, for the cotangents grad_sig -- REPACKED by the caller as an fp64 table (N,K,nRx,2), NULL = none --
+ * and grad_Mlast (N,nM,3) of the data type, NULL = none; not both NULL.  Ktrb's sweep (mrphy_ab_train_bwd) from
+ * h = grad_Mlast, with the cotangent of record k formed per spin as
+ *     (sum_c rx_re g0 + rx_im g1,  sum_c rx_re g1 - rx_im g0,  0),   g = grad_sig[n,k,c,:],  in ascending c,
+ * and M_k, M_{k+1} recomputed per segment of S repetitions from ck (required) instead of read from records.  grad_A,
+ * grad_B, grad_Mi per spin as Ktrb writes them; grad_consts (N,nM,4) per spin with Ktrb's formulas but ALWAYS fp64 (the
+ * caller sums it over the spins that share an operand -- every spin for rest -- and rounds once); grad_rx (N,nM,2,nRx):
+ *     d/d rx_re = sum_k g0 Mx + g1 My,   d/d rx_im = sum_k g1 Mx - g0 My      at M_{k+1};
+ * grad_phase (N,K) is SUMMED OVER THE SPINS of each batch entry inside the kernel (the forward's reduction with one row
+ * per repetition, work (P,N,K) fp64, the same second pass).  Each output may be NULL, not all six.
+ * Both refuse before anything is launched: what mrphy_ab_train_fwd refuses, with the same codes; MRPHY_EINVAL for a
+ * coil count outside 1 .. the limit, a NULL rx with nRx != 1, a NULL sig, ck (adjoint) or a NULL work that is needed;
+ * MRPHY_EALIGN for a pointer not aligned to its element size (ck, work, grad_sig, grad_consts, cs: 8); MRPHY_ENOSPC for a workspace
+ * shorter than the query's.  An empty problem (N*nM*K == 0) is a success that writes nothing.
+ * ------------------------------------------------------------------------------------------- */
+int64_t mrphy_train_signal_ck_every(void);
+int mrphy_train_signal_max_rx(int dtype);
+size_t mrphy_train_signal_workspace(int dtype, int64_t N, int64_t nM, int64_t K, int64_t rows);
+int mrphy_train_signal_fwd(int dtype, const void* A, const void* B,
+                           const void* rest, int64_t rest_sn,
+                           const void* T1, int64_t T1_sn, int64_t T1_sm,
+                           const void* T2, int64_t T2_sn, int64_t T2_sm,
+                           const void* df, int64_t df_sn, int64_t df_sm,
+                           const void* Mi, int64_t Mi_sn, int64_t Mi_sm,
+                           const void* cs, int64_t cs_sn,
+                           const void* rx, int64_t nRx,
+                           void* sig, void* Mlast, void* ck, void* work, size_t work_bytes,
+                           int64_t N, int64_t nM, int64_t K, void* stream);
+int mrphy_train_signal_bwd(int dtype, const void* A, const void* B, const void* grad_sig, const void* grad_Mlast,
+                           const void* rest, int64_t rest_sn,
+                           const void* T1, int64_t T1_sn, int64_t T1_sm,
+                           const void* T2, int64_t T2_sn, int64_t T2_sm,
+                           const void* df, int64_t df_sn, int64_t df_sm,
+                           const void* Mi, int64_t Mi_sn, int64_t Mi_sm,
+                           const void* cs, int64_t cs_sn,
+                           const void* rx, int64_t nRx, const void* ck,
+                           void* grad_A, void* grad_B, void* grad_consts, void* grad_Mi, void* grad_phase,
+                           void* grad_rx, void* work, size_t work_bytes,
+                           int64_t N, int64_t nM, int64_t K, void* stream);
 
 int mrphy_blochsim_ab(int dtype, const void* M, const void* A, const void* B, void* Mo,
                       int64_t rows, void* stream);

@@ -104,6 +104,13 @@ PROTOTYPES = {
     'mrphy_ab_train_fwd': (_int, [_int, _vp, _vp, _vp, _i64] + _BC * 3 + _BC + [_vp, _i64, _vp] + [_i64] * 3 + [_vp]),
     'mrphy_ab_train_bwd': (_int, [_int, _vp, _vp, _vp, _vp, _i64] + _BC * 3 + _BC + [_vp, _i64, _vp] + [_vp] * 5
                            + [_i64] * 3 + [_vp]),
+    'mrphy_train_signal_ck_every': (_i64, []),
+    'mrphy_train_signal_max_rx': (_int, [_int]),
+    'mrphy_train_signal_workspace': (_sz, [_int] + [_i64] * 4),
+    'mrphy_train_signal_fwd': (_int, [_int, _vp, _vp, _vp, _i64] + _BC * 3 + _BC + [_vp, _i64] + [_vp, _i64]
+                               + [_vp, _vp, _vp, _vp, _sz] + [_i64] * 3 + [_vp]),
+    'mrphy_train_signal_bwd': (_int, [_int, _vp, _vp, _vp, _vp, _vp, _i64] + _BC * 3 + _BC + [_vp, _i64] + [_vp, _i64]
+                               + [_vp] + [_vp] * 6 + [_vp, _sz] + [_i64] * 3 + [_vp]),
     'mrphy_blochsim_ab': (_int, [_int, _vp, _vp, _vp, _vp, _i64, _vp]),
     'mrphy_blochsim_ab_bwd': (_int, [_int, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
@@ -150,6 +157,7 @@ UNITS = [(f, m) for f, masks in (
     ('tu_aux.hip', (None,)),
     ('tu_ab_steady.hip', (None,)),
     ('tu_ab_train.hip', (None,)),
+    ('tu_train_signal.hip', (None,)),
     ('abi.hip', (None,)),
 ) for m in masks]
 

@@ -119,6 +119,26 @@ inline int64_t sig_records(int64_t nT, int64_t every) { return nT / every + (nT 
 // kernels are built at (1, 2, 4, 8), forward and adjoint alike (DESIGN.md section 3 has the register readings)
 constexpr int sig_max_rx(size_t tsize) { return tsize == 8 ? SIG_MAX_RX_F64 : SIG_MAX_RX_F32; }
 
+// Ktrs / Ktrsb (k_train_signal.hpp): the signal of a K-repetition train.  One wave per block, persistent over the
+// 64-spin tiles w, w + P, ... with P = trs_waves(nM) partial rows whatever nM: 17 KB of LDS per wave -> 9 per CU fit,
+// 8 are asked for.  TRS_SEG repetitions per checkpoint segment of the adjoint; TRS_ROWS rows of the forward's tile.
+constexpr int TRS_SEG = 8;
+constexpr int TRS_ROWS = 32;
+constexpr int64_t TRS_MAX_WAVES = 256 * 8;
+constexpr int TRS_MAX_RX_F32 = 8, TRS_MAX_RX_F64 = 8;   // receive coils per launch (capacities 1, 2, 4, 8)
+constexpr int trs_max_rx(size_t tsize) { return tsize == 8 ? TRS_MAX_RX_F64 : TRS_MAX_RX_F32; }
+inline int64_t trs_waves(int64_t nM)
+{
+    const int64_t tiles = (nM + WAVE - 1) / WAVE;
+    return tiles < TRS_MAX_WAVES ? tiles : TRS_MAX_WAVES;
+}
+inline int64_t trs_segments(int64_t K) { return (K + TRS_SEG - 1) / TRS_SEG; }
+// workspace of one launch: P partial rows of (N, rows, K) fp64 sums -- rows = 2 nRx (forward), 1 (the adjoint's phase)
+inline size_t trs_workspace(int64_t N, int64_t nM, int64_t K, int64_t rows)
+{
+    return (size_t)(trs_waves(nM) * N * rows * K) * sizeof(double);
+}
+
 inline int64_t k2b_mc_waves(int64_t nM)
 {
     const int64_t tiles = (nM + WAVE - 1) / WAVE;

@@ -4,25 +4,6 @@
 
 namespace {
 #include "k_ab_train.hpp"
-
-// What both entry points check alike, in the order of tu_ab_steady.hip's steady_check: dtype and sizes, the empty
-// problem (0), null pointers and the operand rules, alignment.  `empty` is set for a problem without records.
-int train_check(int dtype, const void* A, const void* B, const void* rest, const void* T1, const void* T2,
-                const void* df, const void* Mi, const void* cs, int64_t N, int64_t nM, int64_t K, bool& empty)
-{
-    empty = false;
-    if ((dtype != MRPHY_F32 && dtype != MRPHY_F64) || N < 0 || nM < 0 || K < 0) return MRPHY_EINVAL;
-    if (N * nM * K == 0) { empty = true; return 0; }
-    if (N > 65535 || (nM + 255) / 256 > (int64_t)0x7fffffff) return MRPHY_EINVAL;   // blockIdx.y = n, as K0 / K2
-    if (!A || !B) return MRPHY_EINVAL;
-    if (!rest && (T1 || T2 || df)) return MRPHY_EINVAL;               // no rest period: nothing to relax or precess in
-    if ((T1 == nullptr) != (T2 == nullptr)) return MRPHY_EINVAL;      // both or neither
-    const size_t ts = tsize(dtype);
-    if (!aligned_to(A, ts) || !aligned_to(B, ts) || !aligned_to(rest, ts) || !aligned_to(T1, ts) ||
-        !aligned_to(T2, ts) || !aligned_to(df, ts) || !aligned_to(Mi, ts) || !aligned_to(cs, sizeof(double)))
-        return MRPHY_EALIGN;
-    return 0;
-}
 }  // namespace
 
 extern "C" {

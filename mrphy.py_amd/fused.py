@@ -50,6 +50,11 @@ form instead of hundreds of simulated periods.
 RF phase changing from one to the next (RF spoiling, phase-cycled bSSFP, a catalysed or inversion-prepared train), one
 thread per spin with the recursion carried in fp64 and the records as the only saved state (Ktr / Ktrb);
 :func:`train_rfgr` is that on top of :func:`ab_rfgr`.
+
+:func:`train_signal` is that transient as a receiver sees it: per repetition the transverse magnetisation summed over
+the spins, for one receive coil or an array, formed inside the kernel without the per-spin records in memory, with an
+adjoint that recomputes the states per segment from fp64 checkpoints (Ktrs / Ktrsb); :func:`train_signal_rfgr` is
+that on top of :func:`ab_rfgr`.
 """
 from math import pi as π, prod  # noqa: F401
 from typing import NamedTuple, Optional
@@ -62,7 +67,7 @@ from . import _lib, _host
 from ._consts import γH, dt0
 
 __all__ = ['blochsim_rfgr', 'blochsim_rfgr_traj', 'signal_rfgr', 'ab_rfgr', 'ab_steadystate', 'steadystate_rfgr',
-           'ab_train', 'train_rfgr']
+           'ab_train', 'train_rfgr', 'train_signal', 'train_signal_rfgr']
 
 
 def _forward_prep(lib, p, γ2πdt, E1, E2, E1_1, dtype, device, need):
@@ -1160,8 +1165,8 @@ def ab_train(
     :func:`ab_steadystate`, by about ``1 / (1 - contraction)``.
 
     Out of scope: a flip angle or ``rest`` per repetition (the pulse is then not one ``A, B``); thinning the records
-    (``every``); the sum over the spins inside the kernel (a signal variant); demodulating the records by ``-φ_k`` (one
-    elementwise torch op on ``Mt``).
+    (``every``); demodulating the records by ``-φ_k`` (one elementwise torch op on ``Mt``).  The sum over the spins inside
+    the kernel is :func:`train_signal`.
     """
     assert A.shape[-2:] == (3, 3) and tuple(B.shape) == tuple(A.shape[:-1]), \
         f"A {tuple(A.shape)} must be (N, *Nd, 3, 3) and B {tuple(B.shape)} (N, *Nd, 3)"
@@ -1204,3 +1209,226 @@ def train_rfgr(
     """
     A, B = ab_rfgr(rf, gr, loc, Δf=Δf, b1Map=b1Map, γ_beff=γ_beff, T1=T1, T2=T2, γ=γ, dt=dt, consts=consts)
     return ab_train(A, B, n=n, Mi=Mi, phase=phase, rest=rest, T1=T1, T2=T2, Δf=Δf if Δf_rest is None else Δf_rest)
+
+
+class TrainSignalHIP(Function):
+    r"""``sig, Mlast = TrainSignalHIP.apply(A, B, Mi, phase, rest, T1, T2, Δf, rx, K, want_ckpt)`` -- see
+    :func:`train_signal`.  ``rx`` `(N ⊻ 1, *Nd, xy)` or `(N ⊻ 1, *Nd, xy, nRx)` with ``nRx`` up to
+    ``mrphy_train_signal_max_rx``, or ``None``; ``sig`` `(N, xy, K)` / `(N, xy, K, nRx)`, ``Mlast`` `(N, *Nd, xyz)`.
+    Both outputs may carry a cotangent.  With ``want_ckpt`` the forward (``mrphy_train_signal_fwd``) leaves the fp64
+    state every ``mrphy_train_signal_ck_every()`` repetitions, all the adjoint (``mrphy_train_signal_bwd``) reads
+    besides the inputs; without it nothing per spin is written but ``Mlast``."""
+
+    ARGS = ('A', 'B', 'Mi', 'phase', 'rest', 'T1', 'T2', 'Δf', 'rx', 'K', 'want_ckpt')
+
+    @staticmethod
+    def _rx_operand(a, rx):
+        r"""``(r, nRx)``: ``rx`` as `(N, nM, 2, nRx)` contiguous in the data type; ``(None, 1)`` for ``None``."""
+        if rx is None:
+            return None, 1
+        N, Nd = a.shape[0], tuple(a.shape[1:-2])
+        r = rx.detach().to(device=a.device, dtype=a.dtype)
+        nRx = r.shape[-1] if r.ndim == len(Nd) + 3 else 1
+        r = r.expand((N,) + Nd + tuple(r.shape[1 + len(Nd):])).reshape(N, prod(Nd), 2, nRx).contiguous()
+        return r, nRx
+
+    @staticmethod
+    def forward(ctx, A, B, Mi, phase, rest, T1, T2, Δf, rx, K, want_ckpt):
+        lib = _lib.require_library()
+        device, dtype = A.device, A.dtype
+        a, b = A.detach().contiguous(), B.detach().contiguous()
+        N, Nd, nM, code, keep, args = AbSteadyStateHIP._operands(a, rest, T1, T2, Δf)
+        mi, cs = AbTrainHIP._state_operands(a, Mi, phase)
+        sargs = AbTrainHIP._state_args(mi, cs, N)
+        r, nRx = TrainSignalHIP._rx_operand(a, rx)
+        coils = () if rx is None or rx.ndim == b.ndim else (nRx,)
+        empty = N * nM * K == 0
+        sig = (torch.zeros if empty else torch.empty)((N, 2, K, *coils), dtype=dtype, device=device)
+        Mlast = torch.empty_like(b)
+        if K == 0:                              # no repetition: the state is still Mi
+            Mlast.copy_(torch.tensor((0., 0., 1.), dtype=dtype, device=device) if mi is None else
+                        mi.reshape((mi.shape[0],) + (Nd if mi.shape[1] > 1 else (1,) * len(Nd)) + (3,)))
+        S = int(lib.mrphy_train_signal_ck_every())
+        ck = torch.empty((-(-K // S), N * nM, 3), dtype=torch.float64, device=device) if want_ckpt else None
+        nbytes = int(lib.mrphy_train_signal_workspace(code, N, nM, K, 2 * nRx))
+        work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        with torch.cuda.device(device):
+            rc = lib.mrphy_train_signal_fwd(code, a.data_ptr(), b.data_ptr(), *args, *sargs, ptr(r), nRx,
+                                            sig.data_ptr(), Mlast.data_ptr(), ptr(ck), work.data_ptr(), work.numel(),
+                                            N, nM, K, _host.current_stream(device))
+        _lib.check(rc, 'mrphy_train_signal_fwd')
+        del keep
+        ctx.set_materialize_grads(False)
+        if want_ckpt:
+            ctx.save_for_backward(a, b, mi, cs, r, ck)
+            ctx.consts = (rest, T1, T2, Δf)
+            ctx.state = (Mi, phase, rx, K, nRx)
+        return sig, Mlast
+
+    @staticmethod
+    def backward(ctx, grad_sig, grad_Mlast):
+        from . import sims
+        need = ctx.needs_input_grad
+        none = (None,) * len(TrainSignalHIP.ARGS)
+        if not any(need) or (grad_sig is None and grad_Mlast is None):
+            return none
+        consts = ctx.consts
+        Mi, phase, rx, K, nRx = ctx.state
+        need_c = [w and c is not None for w, c in zip(need[4:8], consts)]
+        need_mi, need_φ, need_rx = need[2] and Mi is not None, need[3] and phase is not None, need[8] and rx is not None
+        if not (need[0] or need[1] or need_mi or need_φ or need_rx or any(need_c)):
+            return none
+        lib = _lib.require_library()
+        a, b, mi, cs, r, ck = ctx.saved_tensors
+        device, dtype = a.device, a.dtype
+        N, Nd, nM, code, keep, args = AbSteadyStateHIP._operands(a, *consts)
+        sargs = AbTrainHIP._state_args(mi, cs, N)
+        # the cotangent of the signal as the wave-uniform table (N, K, nRx, 2) in fp64
+        gs = None if grad_sig is None else \
+            grad_sig.detach().to(torch.float64).reshape(N, 2, K, nRx).permute(0, 2, 3, 1).contiguous()
+        gl = None if grad_Mlast is None else grad_Mlast.detach().to(dtype).contiguous()
+        # an empty problem launches nothing: its gradients are the zeros of a sum without terms
+        new = torch.zeros if N * nM * K == 0 else torch.empty
+        gA = new(a.shape, dtype=dtype, device=device) if need[0] else None
+        gB = new(b.shape, dtype=dtype, device=device) if need[1] else None
+        # per spin in fp64 whatever the data type: summed over the spins that share the operand, then rounded once
+        gC = new((N,) + Nd + (4,), dtype=torch.float64, device=device) if any(need_c) else None
+        gMi = new(b.shape, dtype=dtype, device=device) if need_mi else None
+        gφ = new((N, K), dtype=dtype, device=device) if need_φ else None
+        grx = new((N, nM, 2, nRx), dtype=dtype, device=device) if need_rx else None
+        nbytes = int(lib.mrphy_train_signal_workspace(code, N, nM, K, 1)) if need_φ else 0
+        work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        with torch.cuda.device(device):
+            rc = lib.mrphy_train_signal_bwd(code, a.data_ptr(), b.data_ptr(), ptr(gs), ptr(gl), *args, *sargs, ptr(r),
+                                            nRx, ck.data_ptr(), ptr(gA), ptr(gB), ptr(gC), ptr(gMi), ptr(gφ), ptr(grx),
+                                            work.data_ptr(), work.numel(), N, nM, K, _host.current_stream(device))
+        _lib.check(rc, 'mrphy_train_signal_bwd')
+        del keep
+        gcs = tuple(sims._reduce_to_const(gC[..., i], c, N, Nd).to(c.device) if want else None
+                    for i, (c, want) in enumerate(zip(consts, need_c)))
+        if need_mi:
+            if K == 0 and gl is not None:       # no repetition: Mlast is Mi
+                gMi = gl
+            if tuple(Mi.shape) != tuple(gMi.shape):     # a shared Mi: the sum over those who share it, in fp64
+                gMi = gMi.to(torch.float64).sum_to_size(tuple(Mi.shape))
+            gMi = gMi.to(device=Mi.device, dtype=Mi.dtype)
+        if need_φ:                              # summed over the spins by the kernel; here over the entries that share a phase
+            gφ = gφ.to(torch.float64).sum_to_size(tuple(phase.shape)).to(device=phase.device, dtype=phase.dtype)
+        if need_rx:
+            grx = grx.reshape((N,) + Nd + tuple(rx.shape[1 + len(Nd):]))
+            if rx.shape[0] != N:                        # a map shared by the batch
+                grx = grx.to(torch.float64).sum_to_size(tuple(rx.shape))
+            grx = grx.to(device=rx.device, dtype=rx.dtype)
+        return (gA, gB, gMi, gφ) + gcs + (grx, None, None)
+
+
+def _train_signal_max_rx(dtype) -> int:
+    return int(_lib.require_library().mrphy_train_signal_max_rx(_lib.F64 if dtype == torch.float64 else _lib.F32))
+
+
+@_host.half_via_float
+def train_signal(
+    A: Tensor, B: Tensor, *, n: Optional[int] = None, Mi: Optional[Tensor] = None, phase: Optional[Tensor] = None,
+    rest: Optional[Tensor] = None, T1: Optional[Tensor] = None, T2: Optional[Tensor] = None,
+    Δf: Optional[Tensor] = None, rx: Optional[Tensor] = None, demod: bool = False, return_last: bool = False
+):
+    r"""The signal a receive coil measures after each of the ``K`` repetitions of :func:`ab_train`: the transverse
+    magnetisation of record ``k`` (``M_{k+1}``, right after pulse ``k``) summed over the spins ``*Nd``, weighted by the
+    receive map ``rx`` as :func:`signal_rfgr` weights it (a complex product, no conjugate):
+
+        ``sig[n, 0, k] = Σ_s rx_re·Mx − rx_im·My``,  ``sig[n, 1, k] = Σ_s rx_re·My + rx_im·Mx``.
+
+    The recursion, the operands ``A, B, n, Mi, phase, rest, T1, T2, Δf``, their shapes, broadcasting and absences are
+    exactly :func:`ab_train`'s.
+
+    Usage:
+        ``sig = train_signal(A, B, *, n, Mi, phase, rest, T1, T2, Δf, rx, demod)``
+        ``sig, Mlast = train_signal(..., return_last=True)``
+    Optionals besides :func:`ab_train`'s:
+        - ``rx``: `(N ⊻ 1, *Nd, xy)` or `(N ⊻ 1, *Nd, xy, nRx)`, the layout of ``b1Map``; ``None`` = ``(1, 0)``, the plain
+          sums of ``Mx`` and ``My``.
+        - ``demod``: multiply sample ``k`` by ``exp(-iφ_k)``, so that the receiver follows the RF phase (``φ_k`` is
+          shared by the spins, so this commutes with the sum: torch ops on the small result, through autograd).
+        - ``return_last``: also return ``Mlast`` `(N, *Nd, xyz)`, the last record -- :func:`ab_train`'s bit for bit --,
+          so that a sequence can carry on from it as ``Mi`` of the next call: segments with different pulses (a
+          variable flip angle) chain this way.  For ``K = 0`` it is ``Mi`` expanded, or ``(0, 0, 1)``.
+    Outputs:
+        - ``sig``: `(N, xy, K)`, or `(N, xy, K, nRx)` when ``rx`` has a coil axis.
+
+    The sum is formed inside the kernel (Ktrs, ``mrphy_train_signal_fwd``): the recursion is Ktr's, in fp64 whatever
+    the data type; per repetition the lane's products go through an LDS tile into fp64 partial sums per wave, a second
+    pass adds those in a fixed order and rounds once.  No float atomics, the same inputs give the same bits, and nothing
+    of size ``K × spins`` is written: with a gradient wanted, the fp64 state every ``mrphy_train_signal_ck_every()``
+    repetitions.  Up to ``mrphy_train_signal_max_rx`` coils (8) share one simulation per launch, more run in blocks of
+    that many; every coil's samples are the bits a call with that coil alone gives.
+
+    Differentiable w.r.t. ``A, B, Mi, phase, rest, T1, T2, Δf`` and ``rx`` through both outputs
+    (Ktrsb, ``mrphy_train_signal_bwd``: Ktrb's sweep on states recomputed per segment from the checkpoints; the
+    gradient of the phase is summed over the spins inside the kernel; deterministic).  With the gradient w.r.t. ``rx``
+    a proton density, a coil sensitivity and an echo time stay in torch on per-spin tensors: the signal at an echo time
+    ``TE`` after the pulse is this one with ``rx · exp(-TE/T2) · exp(-i2πΔf·TE)`` for ``rx``.
+
+    Out of scope as :func:`ab_train`: a flip angle or ``rest`` per repetition within one call, thinning the records.
+    """
+    assert A.shape[-2:] == (3, 3) and tuple(B.shape) == tuple(A.shape[:-1]), \
+        f"A {tuple(A.shape)} must be (N, *Nd, 3, 3) and B {tuple(B.shape)} (N, *Nd, 3)"
+    N, Nd = A.shape[0], tuple(A.shape[1:-2])
+    K = _train_length(n, phase, N)
+    if rx is not None:
+        if rx.ndim not in (B.ndim, B.ndim + 1) or rx.shape[0] not in (1, N) or \
+                tuple(rx.shape[1:B.ndim]) != Nd + (2,) or (rx.ndim == B.ndim + 1 and rx.shape[-1] < 1):
+            raise ValueError(f"mrphy_amd: `rx` {tuple(rx.shape)} must be (N ⊻ 1, *Nd, xy) or (N ⊻ 1, *Nd, xy, nRx) "
+                             f"for spins {(N,) + Nd}")
+    _host.require_device_tensor(A, 'A')
+    _host.require_device_tensor(B, 'B')
+    assert A.dtype == B.dtype and A.device == B.device, "A and B must share dtype and device"
+    assert (T1 is None) == (T2 is None)  # both or neither
+    assert rest is not None or (T1 is None and Δf is None), "T1, T2, Δf describe the rest period: give `rest`"
+    if Mi is not None:
+        assert Mi.ndim == 2 + len(Nd) and Mi.shape[-1] == 3 and Mi.shape[0] in (1, N) and \
+            all(m in (1, d) for m, d in zip(Mi.shape[1:-1], Nd)), \
+            f"Mi {tuple(Mi.shape)} must be (N ⊻ 1, *Nd ⊻ 1, 3) for spins {(N,) + Nd}"
+    operands = (A, B, Mi, phase, rest, T1, T2, Δf, rx)
+    want = torch.is_grad_enabled() and any(isinstance(x, Tensor) and x.requires_grad for x in operands)
+    cap = _train_signal_max_rx(A.dtype)
+    if rx is not None and rx.ndim == B.ndim + 1 and rx.shape[-1] > cap:
+        # blocks of `cap` coils, one simulation each; a coil's sums do not depend on the other coils
+        parts = [TrainSignalHIP.apply(A, B, Mi, phase, rest, T1, T2, Δf, rx[..., c:c + cap], K, want)
+                 for c in range(0, rx.shape[-1], cap)]
+        sig, Mlast = torch.cat([p[0] for p in parts], dim=-1), parts[0][1]
+    else:
+        sig, Mlast = TrainSignalHIP.apply(A, B, Mi, phase, rest, T1, T2, Δf, rx, K, want)
+    if demod and phase is not None:
+        φ = phase.to(device=sig.device, dtype=torch.float64).reshape(phase.shape + (1,) * (sig.ndim - 3))
+        c, s = torch.cos(φ), torch.sin(φ)
+        s0, s1 = sig[:, 0].to(torch.float64), sig[:, 1].to(torch.float64)
+        sig = torch.stack((s0 * c + s1 * s, s1 * c - s0 * s), dim=1).to(sig.dtype)
+    return (sig, Mlast) if return_last else sig
+
+
+@_host.half_via_float
+def train_signal_rfgr(
+    rf: Tensor, gr: Tensor, loc: Tensor, *,
+    n: Optional[int] = None, Mi: Optional[Tensor] = None, phase: Optional[Tensor] = None,
+    rest: Optional[Tensor] = None, T1: Optional[Tensor] = None, T2: Optional[Tensor] = None,
+    Δf: Optional[Tensor] = None, rx: Optional[Tensor] = None, demod: bool = False, return_last: bool = False,
+    b1Map: Optional[Tensor] = None, γ_beff: Tensor = γH,
+    γ: Tensor = γH, dt: Tensor = dt0, consts: Optional[dict] = None, Δf_rest: Optional[Tensor] = None
+):
+    r"""The signal of the first ``K`` repetitions of a pulse (SPGR with RF spoiling, phase-cycled bSSFP, an
+    inversion-prepared train), from ``rf`` and ``gr``:
+
+        ``train_signal(*ab_rfgr(rf, gr, loc, ...), n=n, Mi=Mi, phase=phase, rest=rest, T1=T1, T2=T2,
+        Δf=Δf if Δf_rest is None else Δf_rest, rx=rx, demod=demod, return_last=return_last)``
+
+    built as :func:`train_rfgr` is on :func:`ab_train`.  Operands of the pulse exactly as :func:`ab_rfgr`, those of the
+    train and of the receiver as :func:`train_signal`; ``Δf_rest`` as in :func:`steadystate_rfgr`.  Every route of
+    :func:`ab_rfgr` (fused, split, composed; parallel transmit) serves it, so gradients reach every operand ``ab_rfgr``
+    serves, and ``Mi, phase, rest, T1, T2, Δf`` / ``Δf_rest``, ``rx`` through the train: ``T1`` and ``T2``, shared by the
+    pulse and the rest, receive the sum of both paths.
+    """
+    A, B = ab_rfgr(rf, gr, loc, Δf=Δf, b1Map=b1Map, γ_beff=γ_beff, T1=T1, T2=T2, γ=γ, dt=dt, consts=consts)
+    return train_signal(A, B, n=n, Mi=Mi, phase=phase, rest=rest, T1=T1, T2=T2,
+                        Δf=Δf if Δf_rest is None else Δf_rest, rx=rx, demod=demod, return_last=return_last)
