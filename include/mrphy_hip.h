@@ -85,7 +85,9 @@ extern "C" {
  *      mrphy_ab_train_bwd (the transient of a pulse repeated K times with an RF phase per repetition, and its adjoint);
  *      mrphy_train_signal_ck_every, mrphy_train_signal_max_rx, mrphy_train_signal_workspace, mrphy_train_signal_fwd,
  *      mrphy_train_signal_bwd (the received signal of that transient: the transverse magnetisation of its records summed
- *      over the spins, for up to 8 receive coils per launch, and its adjoint). */
+ *      over the spins, for up to 8 receive coils per launch, and its adjoint); mrphy_ab_sequence_bwd_workspace,
+ *      mrphy_ab_sequence_fwd, mrphy_ab_sequence_bwd (that transient with a pulse of a bank and a rest duration per
+ *      repetition, and its adjoint). */
 #define MRPHY_ABI_VERSION 5
 
 #define MRPHY_F32      0  /* T = float,  CT = float                                          */
@@ -1157,6 +1159,52 @@ int mrphy_train_signal_bwd(int dtype, const void* A, const void* B, const void* 
                            void* grad_A, void* grad_B, void* grad_consts, void* grad_Mi, void* grad_phase,
                            void* grad_rx, void* work, size_t work_bytes,
                            int64_t N, int64_t nM, int64_t K, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Ksq  Ktr's transient with a schedule: repetition k plays entry pulse_k of a bank of P >= 1 pulses after a rest of
+ * its own duration rest_k.  Per spin, from M_0 = Mi, for k = 0 .. K-1:
+ *     M-      = F_k M_k + f_k                                   F, f of Kss at the duration rest_k (0 is legal: no rest)
+ *     M_{k+1} = Rz(phi_k) [ A_p Rz(-phi_k) M- + B_p ],  p = pulse_k
+ * A (P,N,nM,3,3), B (P,N,nM,3) of the data type, contiguous, the bank axis leading.  pulse (K,): int32 on the device,
+ * one schedule for all batch entries, NULL = all zeros (P == 1 only); 0 <= pulse_k < P is a PRECONDITION (the library
+ * cannot read device memory on the host).  rs (N|1,K): the rest durations, ALWAYS fp64 -- the caller's operand rounded
+ * to the data type and widened, the number Ktr sees --, contiguous over K with element stride rs_sn between batch
+ * entries (0 broadcasts); NULL = no rest period (T1, T2, df must then be NULL).  T1 .. cs_sn, Mt (K,N,nM,3), the grid
+ * and the arithmetic as mrphy_ab_train_fwd: the repetition is Ktr's, bit for bit; A_p, B_p are reloaded when pulse_k
+ * changes and the rest's constants re-formed when the bits of rest_k change, both uniform over the block.
+ *
+ * Ksqb  its adjoint: Ktrb's sweep with the same two refreshes.  grad_A (P,N,nM,3,3), grad_B (P,N,nM,3): the whole bank,
+ * exact zeros for an entry the schedule never plays; accumulated per run of equal pulse_k in registers and added into
+ * the lane's own slots of work (P,12,N*nM) fp64 when pulse_k changes (no atomics, fixed order), rounded once by a second
+ * pass.  work is needed when grad_A or grad_B is: work_bytes >= mrphy_ab_sequence_bwd_workspace(dtype,P,N,nM) =
+ * P*12*N*nM*8; it is passed in uninitialised and cleared on the caller's stream.  grad_consts (N,nM,3) = [dL/d T1,
+ * dL/d T2, dL/d df] summed over k with rest_k inside the sum; grad_rest (K,N,nM): Ktrb's dL/d rest per repetition and
+ * PER SPIN (the caller sums over the spins, and over k for one duration); grad_Mi, grad_phase as Ktrb.  Each of the six
+ * may be NULL, not all.
+ * Both refuse before anything is launched, in the order of mrphy_ab_train_*: MRPHY_EINVAL for what those refuse (rs in
+ * the place of rest), P < 1 or P > 65535, pulse == NULL with P > 1, a NULL work that is needed; MRPHY_EALIGN for a
+ * misaligned pointer (rs, cs, work: 8; pulse: 4); MRPHY_ENOSPC for a workspace shorter than the query's.  An empty
+ * problem (N*nM*K == 0) is a success that writes nothing.
+ * ------------------------------------------------------------------------------------------- */
+size_t mrphy_ab_sequence_bwd_workspace(int dtype, int64_t P, int64_t N, int64_t nM);
+int mrphy_ab_sequence_fwd(int dtype, const void* A, const void* B, int64_t P, const void* pulse,
+                          const void* rs, int64_t rs_sn,
+                          const void* T1, int64_t T1_sn, int64_t T1_sm,
+                          const void* T2, int64_t T2_sn, int64_t T2_sm,
+                          const void* df, int64_t df_sn, int64_t df_sm,
+                          const void* Mi, int64_t Mi_sn, int64_t Mi_sm,
+                          const void* cs, int64_t cs_sn,
+                          void* Mt, int64_t N, int64_t nM, int64_t K, void* stream);
+int mrphy_ab_sequence_bwd(int dtype, const void* A, const void* B, int64_t P, const void* pulse, const void* grad_Mt,
+                          const void* rs, int64_t rs_sn,
+                          const void* T1, int64_t T1_sn, int64_t T1_sm,
+                          const void* T2, int64_t T2_sn, int64_t T2_sm,
+                          const void* df, int64_t df_sn, int64_t df_sm,
+                          const void* Mi, int64_t Mi_sn, int64_t Mi_sm,
+                          const void* cs, int64_t cs_sn, const void* Mt,
+                          void* grad_A, void* grad_B, void* grad_consts, void* grad_rest, void* grad_Mi,
+                          void* grad_phase, void* work, size_t work_bytes,
+                          int64_t N, int64_t nM, int64_t K, void* stream);
 
 int mrphy_blochsim_ab(int dtype, const void* M, const void* A, const void* B, void* Mo,
                       int64_t rows, void* stream);

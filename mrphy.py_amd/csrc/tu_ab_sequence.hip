@@ -1,0 +1,114 @@
+// tu_ab_sequence.hip -- a train with a pulse of a bank and a rest per repetition, from Hargreaves' A, B: the entry
+// points of the C ABI together with their kernels (k_ab_sequence.hpp on k_ab_train.hpp, train_rep of
+// k_train_signal.hpp).  Two data types, no constant type, as tu_ab_train.hip.
+#include "host_common.hpp"
+
+namespace {
+#include "k_ab_train.hpp"
+#include "k_train_signal.hpp"
+#include "k_ab_sequence.hpp"
+
+inline size_t seq_workspace(int64_t P, int64_t N, int64_t nM) { return (size_t)P * 12 * (size_t)(N * nM) * sizeof(double); }
+
+// What both entry points check alike, in train_check's order: dtype and sizes (P among them), the empty problem (0),
+// null pointers and the operand rules; `align` is what train_check found of misaligned pointers, to be returned after
+// the caller's own null checks.
+int seq_check(int dtype, const void* A, const void* B, int64_t P, const void* pulse, const void* rs, const void* T1,
+              const void* T2, const void* df, const void* Mi, const void* cs, int64_t N, int64_t nM, int64_t K,
+              bool& empty, int& align)
+{
+    align = 0;
+    const int e = train_check(dtype, A, B, rs, T1, T2, df, Mi, cs, N, nM, K, empty);
+    if (e == MRPHY_EINVAL || P < 1 || P > 65535) return MRPHY_EINVAL;           // blockIdx.y = p in the second pass
+    if (empty) return 0;
+    if (!pulse && P > 1) return MRPHY_EINVAL;
+    align = (e || !aligned_to(rs, sizeof(double)) || !aligned_to(pulse, sizeof(int32_t))) ? MRPHY_EALIGN : 0;
+    return 0;
+}
+
+void seq_fill(SeqArgs& q, const void* A, const void* B, int64_t P, const void* pulse, const void* rs, int64_t rs_sn,
+              Bc T1, Bc T2, Bc df, const void* Mi, int64_t Mi_sn, int64_t Mi_sm, const void* cs, int64_t cs_sn,
+              int64_t N, int64_t nM, int64_t K)
+{
+    q.A = A; q.B = B; q.P = P; q.pulse = reinterpret_cast<const int32_t*>(pulse);
+    q.rs = reinterpret_cast<const double*>(rs); q.rs_sn = rs_sn;
+    q.T1 = T1; q.T2 = T2; q.df = df;
+    q.Mi = Mi; q.Mi_sn = Mi_sn; q.Mi_sm = Mi_sm; q.cs = reinterpret_cast<const double*>(cs); q.cs_sn = cs_sn;
+    q.rows = N * nM; q.nM = nM; q.K = K;
+}
+}  // namespace
+
+extern "C" {
+
+size_t mrphy_ab_sequence_bwd_workspace(int dtype, int64_t P, int64_t N, int64_t nM)
+{
+    if ((dtype != MRPHY_F32 && dtype != MRPHY_F64) || P <= 0 || N <= 0 || nM <= 0) return 0;
+    return seq_workspace(P, N, nM);
+}
+
+int mrphy_ab_sequence_fwd(int dtype, const void* A, const void* B, int64_t P, const void* pulse, const void* rs,
+                          int64_t rs_sn, const void* T1, int64_t T1_sn, int64_t T1_sm, const void* T2, int64_t T2_sn,
+                          int64_t T2_sm, const void* df, int64_t df_sn, int64_t df_sm, const void* Mi, int64_t Mi_sn,
+                          int64_t Mi_sm, const void* cs, int64_t cs_sn, void* Mt, int64_t N, int64_t nM, int64_t K,
+                          void* stream)
+{
+    bool empty; int align;
+    if (int e = seq_check(dtype, A, B, P, pulse, rs, T1, T2, df, Mi, cs, N, nM, K, empty, align)) return e;
+    if (empty) return 0;
+    if (!Mt) return MRPHY_EINVAL;
+    if (align || !aligned_to(Mt, tsize(dtype))) return MRPHY_EALIGN;
+    SeqArgs q{};
+    seq_fill(q, A, B, P, pulse, rs, rs_sn, Bc{T1, T1_sn, T1_sm}, Bc{T2, T2_sn, T2_sm}, Bc{df, df_sn, df_sm}, Mi, Mi_sn,
+             Mi_sm, cs, cs_sn, N, nM, K);
+    q.Mt = Mt;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)((nM + 255) / 256), (unsigned)N);
+    if (dtype == MRPHY_F32) hipLaunchKernelGGL((k_ab_sequence_fwd<float>), grid, dim3(256), 0, st, q);
+    else                    hipLaunchKernelGGL((k_ab_sequence_fwd<double>), grid, dim3(256), 0, st, q);
+    return launch_status();
+}
+
+int mrphy_ab_sequence_bwd(int dtype, const void* A, const void* B, int64_t P, const void* pulse, const void* grad_Mt,
+                          const void* rs, int64_t rs_sn, const void* T1, int64_t T1_sn, int64_t T1_sm, const void* T2,
+                          int64_t T2_sn, int64_t T2_sm, const void* df, int64_t df_sn, int64_t df_sm, const void* Mi,
+                          int64_t Mi_sn, int64_t Mi_sm, const void* cs, int64_t cs_sn, const void* Mt, void* grad_A,
+                          void* grad_B, void* grad_consts, void* grad_rest, void* grad_Mi, void* grad_phase, void* work,
+                          size_t work_bytes, int64_t N, int64_t nM, int64_t K, void* stream)
+{
+    bool empty; int align;
+    if (int e = seq_check(dtype, A, B, P, pulse, rs, T1, T2, df, Mi, cs, N, nM, K, empty, align)) return e;
+    if (empty) return 0;
+    if (!grad_Mt || !Mt || (!grad_A && !grad_B && !grad_consts && !grad_rest && !grad_Mi && !grad_phase))
+        return MRPHY_EINVAL;
+    const bool bank = grad_A || grad_B;
+    const size_t need = bank ? seq_workspace(P, N, nM) : 0;
+    if (need && !work) return MRPHY_EINVAL;
+    const size_t ts = tsize(dtype);
+    if (align || !aligned_to(grad_Mt, ts) || !aligned_to(Mt, ts) || !aligned_to(grad_A, ts) || !aligned_to(grad_B, ts) ||
+        !aligned_to(grad_consts, ts) || !aligned_to(grad_rest, ts) || !aligned_to(grad_Mi, ts) ||
+        !aligned_to(grad_phase, ts) || !aligned_to(work, sizeof(double)))
+        return MRPHY_EALIGN;
+    if (work_bytes < need) return MRPHY_ENOSPC;
+    SeqArgs q{};
+    seq_fill(q, A, B, P, pulse, rs, rs_sn, Bc{T1, T1_sn, T1_sm}, Bc{T2, T2_sn, T2_sm}, Bc{df, df_sn, df_sm}, Mi, Mi_sn,
+             Mi_sm, cs, cs_sn, N, nM, K);
+    q.g = grad_Mt; q.Mt = const_cast<void*>(Mt);
+    q.gC = grad_consts; q.grest = grad_rest; q.gMi = grad_Mi; q.gphi = grad_phase;
+    q.work = bank ? reinterpret_cast<double*>(work) : nullptr;
+    hipStream_t st = (hipStream_t)stream;
+    if (bank)
+        if (hipError_t e = hipMemsetAsync(work, 0, need, st)) return (int)e;
+    const dim3 grid((unsigned)((nM + 255) / 256), (unsigned)N);
+    if (dtype == MRPHY_F32) hipLaunchKernelGGL((k_ab_sequence_bwd<float>), grid, dim3(256), 0, st, q);
+    else                    hipLaunchKernelGGL((k_ab_sequence_bwd<double>), grid, dim3(256), 0, st, q);
+    if (int e = launch_status()) return e;
+    if (!bank) return 0;
+    const dim3 grid2((unsigned)((q.rows + 255) / 256), (unsigned)P);
+    if (dtype == MRPHY_F32)
+        hipLaunchKernelGGL((k_ab_sequence_p2<float>), grid2, dim3(256), 0, st, q.work, (float*)grad_A, (float*)grad_B, q.rows);
+    else
+        hipLaunchKernelGGL((k_ab_sequence_p2<double>), grid2, dim3(256), 0, st, q.work, (double*)grad_A, (double*)grad_B, q.rows);
+    return launch_status();
+}
+
+}  // extern "C"

@@ -55,6 +55,10 @@ thread per spin with the recursion carried in fp64 and the records as the only s
 the spins, for one receive coil or an array, formed inside the kernel without the per-spin records in memory, with an
 adjoint that recomputes the states per segment from fp64 checkpoints (Ktrs / Ktrsb); :func:`train_signal_rfgr` is
 that on top of :func:`ab_rfgr`.
+
+:func:`ab_sequence` is the transient of a sequence whose repetitions differ: each plays one pulse of a bank ``A, B``
+after a rest of its own duration, by a host-side schedule (MR fingerprinting, prepared or variable-flip-angle trains),
+still one launch each way (Ksq / Ksqb); :func:`sequence_rfgr` is that on top of one :func:`ab_rfgr` call for the bank.
 """
 from math import pi as π, prod  # noqa: F401
 from typing import NamedTuple, Optional
@@ -67,7 +71,7 @@ from . import _lib, _host
 from ._consts import γH, dt0
 
 __all__ = ['blochsim_rfgr', 'blochsim_rfgr_traj', 'signal_rfgr', 'ab_rfgr', 'ab_steadystate', 'steadystate_rfgr',
-           'ab_train', 'train_rfgr', 'train_signal', 'train_signal_rfgr']
+           'ab_train', 'train_rfgr', 'train_signal', 'train_signal_rfgr', 'ab_sequence', 'sequence_rfgr']
 
 
 def _forward_prep(lib, p, γ2πdt, E1, E2, E1_1, dtype, device, need):
@@ -1164,9 +1168,9 @@ def ab_train(
     repetition is kept besides the output --, deterministic).  In fp32 errors of ``A`` are amplified as in
     :func:`ab_steadystate`, by about ``1 / (1 - contraction)``.
 
-    Out of scope: a flip angle or ``rest`` per repetition (the pulse is then not one ``A, B``); thinning the records
-    (``every``); demodulating the records by ``-φ_k`` (one elementwise torch op on ``Mt``).  The sum over the spins inside
-    the kernel is :func:`train_signal`.
+    Out of scope: thinning the records (``every``); demodulating the records by ``-φ_k`` (one elementwise torch op on
+    ``Mt``).  A flip angle or ``rest`` per repetition (the pulse is then not one ``A, B``) is :func:`ab_sequence`; the
+    sum over the spins inside the kernel is :func:`train_signal`.
     """
     assert A.shape[-2:] == (3, 3) and tuple(B.shape) == tuple(A.shape[:-1]), \
         f"A {tuple(A.shape)} must be (N, *Nd, 3, 3) and B {tuple(B.shape)} (N, *Nd, 3)"
@@ -1209,6 +1213,249 @@ def train_rfgr(
     """
     A, B = ab_rfgr(rf, gr, loc, Δf=Δf, b1Map=b1Map, γ_beff=γ_beff, T1=T1, T2=T2, γ=γ, dt=dt, consts=consts)
     return ab_train(A, B, n=n, Mi=Mi, phase=phase, rest=rest, T1=T1, T2=T2, Δf=Δf if Δf_rest is None else Δf_rest)
+
+
+class AbSequenceHIP(Function):
+    r"""``Mt = AbSequenceHIP.apply(A, B, Mi, phase, rest, T1, T2, Δf, K, sched)`` -- see :func:`ab_sequence`; ``A, B``
+    carry the bank axis in front, ``sched`` is the checked schedule (an int32 CPU tensor `(K,)`, or ``None`` for all
+    zeros), ``Mt`` is time-major `(K, N, *Nd, xyz)`.  The backward (``mrphy_ab_sequence_bwd``) reads the states from
+    ``Mt`` itself, as :class:`AbTrainHIP`; its only scratch is the fp64 workspace of the bank's gradients."""
+
+    @staticmethod
+    def _rest_table(a, rest, N, K):
+        r"""``rs`` `(N ⊻ 1, K)` fp64 on the device: ``rest`` rounded to the data type (what ``ab_train`` hands its
+        kernel) and widened, a duration that does not change written out over ``K``; ``None`` without a rest."""
+        if rest is None:
+            return None
+        d = rest.detach().to(device=a.device, dtype=a.dtype).double()
+        d = d.reshape(-1, 1) if d.ndim < 2 else d
+        return d.expand(d.shape[0], K).contiguous()
+
+    @staticmethod
+    def _args(a, rs, T1, T2, Δf, mi, cs, sched_dev):
+        r"""``(N, Nd, nM, code, keep, head, tail)``: ``P, pulse`` and ``rs .. cs_sn`` of the two entry points."""
+        N, Nd, nM, code, keep, args = AbSteadyStateHIP._operands(a[0], None, T1, T2, Δf)
+        head = (a.shape[0], None if sched_dev is None else sched_dev.data_ptr())
+        tail = (None if rs is None else rs.data_ptr(), rs.stride(0) if (rs is not None and rs.shape[0] == N and N > 1) else 0,
+                *args[2:], *AbTrainHIP._state_args(mi, cs, N))
+        return N, Nd, nM, code, keep, head, tail
+
+    @staticmethod
+    def forward(ctx, A, B, Mi, phase, rest, T1, T2, Δf, K, sched):
+        lib = _lib.require_library()
+        device = A.device
+        a, b = A.detach().contiguous(), B.detach().contiguous()
+        sched_dev = None if sched is None else sched.to(device)
+        rs = AbSequenceHIP._rest_table(a, rest, a.shape[1], K)
+        mi, cs = AbTrainHIP._state_operands(a[0], Mi, phase)
+        N, Nd, nM, code, keep, head, tail = AbSequenceHIP._args(a, rs, T1, T2, Δf, mi, cs, sched_dev)
+        Mt = torch.empty((K,) + tuple(b.shape[1:]), dtype=b.dtype, device=device)
+        with torch.cuda.device(device):
+            rc = lib.mrphy_ab_sequence_fwd(code, a.data_ptr(), b.data_ptr(), *head, *tail, Mt.data_ptr(), N, nM, K,
+                                           _host.current_stream(device))
+        _lib.check(rc, 'mrphy_ab_sequence_fwd')
+        del keep
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(a, b, Mt, mi, cs, rs, sched_dev)
+        ctx.consts = (T1, T2, Δf)
+        ctx.state = (Mi, phase, rest, K)
+        return Mt
+
+    @staticmethod
+    def backward(ctx, grad_Mt):
+        from . import sims
+        need = ctx.needs_input_grad
+        consts = ctx.consts
+        Mi, phase, rest, K = ctx.state
+        need_c = [w and c is not None for w, c in zip(need[5:8], consts)]
+        need_mi, need_φ, need_r = need[2] and Mi is not None, need[3] and phase is not None, need[4] and rest is not None
+        if grad_Mt is None or not (need[0] or need[1] or need_mi or need_φ or need_r or any(need_c)):
+            return (None,) * 10
+        lib = _lib.require_library()
+        a, b, Mt, mi, cs, rs, sched_dev = ctx.saved_tensors
+        device, dtype = a.device, a.dtype
+        N, Nd, nM, code, keep, head, tail = AbSequenceHIP._args(a, rs, *consts, mi, cs, sched_dev)
+        g = grad_Mt.detach().to(dtype).contiguous()
+        # an empty problem launches nothing: its gradients are the zeros of a sum without terms
+        new = torch.zeros if N * nM * K == 0 else torch.empty
+        gA = new(a.shape, dtype=dtype, device=device) if need[0] else None
+        gB = new(b.shape, dtype=dtype, device=device) if need[1] else None
+        gC = new((N,) + Nd + (3,), dtype=dtype, device=device) if any(need_c) else None
+        gr_ = new((K, N, nM), dtype=dtype, device=device) if need_r else None
+        gMi = new(b.shape[1:], dtype=dtype, device=device) if need_mi else None
+        gφ = new((K, N, nM), dtype=dtype, device=device) if need_φ else None
+        nbytes = int(lib.mrphy_ab_sequence_bwd_workspace(code, a.shape[0], N, nM)) if (need[0] or need[1]) else 0
+        work = torch.empty(nbytes // 8, dtype=torch.float64, device=device) if nbytes else None
+        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        with torch.cuda.device(device):
+            rc = lib.mrphy_ab_sequence_bwd(code, a.data_ptr(), b.data_ptr(), *head, g.data_ptr(), *tail, Mt.data_ptr(),
+                                           ptr(gA), ptr(gB), ptr(gC), ptr(gr_), ptr(gMi), ptr(gφ), ptr(work), nbytes,
+                                           N, nM, K, _host.current_stream(device))
+        _lib.check(rc, 'mrphy_ab_sequence_bwd')
+        del keep, work
+        gcs = tuple(sims._reduce_to_const(gC[..., i], c, N, Nd).to(c.device) if want else None
+                    for i, (c, want) in enumerate(zip(consts, need_c)))
+        if need_mi:
+            gMi = gMi.sum_to_size(tuple(Mi.shape)).to(device=Mi.device, dtype=Mi.dtype)
+        # per spin from the kernel; the sums over the spins that share a phase or a duration, accumulated in fp64
+        over_spins = lambda x: torch.sum(x, dim=-1, dtype=torch.float64).T  # noqa: E731  (N, K)
+        if need_φ:
+            gφ = over_spins(gφ).sum_to_size(tuple(phase.shape)).to(device=phase.device, dtype=phase.dtype)
+        if need_r:
+            gr_ = over_spins(gr_)
+            gr_ = gr_.sum_to_size(tuple(rest.shape)) if rest.ndim == 2 else gr_.sum(1).sum_to_size(tuple(rest.shape) or (1,))
+            gr_ = gr_.reshape(rest.shape).to(device=rest.device, dtype=rest.dtype)
+        return (gA, gB, gMi, gφ, gr_) + gcs + (None, None)
+
+
+def _sequence_schedule(pulse, P):
+    r"""``pulse`` of :func:`ab_sequence` checked on the host: an int32 CPU tensor `(K,)`, or ``None`` (all zeros)."""
+    if pulse is None:
+        if P != 1:
+            raise ValueError(f"mrphy_amd: `pulse` is required with a bank of P = {P} pulses: which one does repetition 0 play?")
+        return None
+    if isinstance(pulse, Tensor):
+        if pulse.device.type != 'cpu':
+            raise ValueError(f"mrphy_amd: `pulse` is a host-side schedule: a CPU tensor, got one on {pulse.device}")
+        if pulse.ndim != 1:
+            raise ValueError(f"mrphy_amd: `pulse` {tuple(pulse.shape)} must be (K,)")
+        if pulse.dtype.is_floating_point or pulse.dtype.is_complex or pulse.dtype == torch.bool:
+            raise ValueError(f"mrphy_amd: `pulse` must hold integers: repetition 0"
+                             f"{f' is {pulse[0].item()!r}' if pulse.numel() else ''} of dtype {pulse.dtype}")
+        sched = pulse.detach().to(torch.int64)
+    else:
+        import numbers
+        entries = list(pulse)
+        for k, x in enumerate(entries):
+            if isinstance(x, bool) or not isinstance(x, numbers.Integral):
+                raise ValueError(f"mrphy_amd: `pulse` must hold integers: repetition {k} is {x!r}")
+        sched = torch.tensor([int(x) for x in entries], dtype=torch.int64)
+    bad = ((sched < 0) | (sched >= P)).nonzero()
+    if bad.numel():
+        k = int(bad[0])
+        raise ValueError(f"mrphy_amd: repetition {k} plays `pulse` = {int(sched[k])}, outside the bank [0, {P})")
+    return sched.to(torch.int32).contiguous()
+
+
+def _sequence_length(n, sched, phase, N):
+    r"""``K`` of :func:`ab_sequence` from ``n``, ``pulse`` and ``phase``, in the style of :func:`_train_length`."""
+    if n is not None and (isinstance(n, bool) or not isinstance(n, int) or n < 0):
+        raise ValueError(f"mrphy_amd: `n` must be an int >= 0, got {n!r}")
+    if phase is not None and (phase.ndim != 2 or phase.shape[0] not in (1, N)):
+        raise ValueError(f"mrphy_amd: `phase` {tuple(phase.shape)} must be (N ⊻ 1, K) with N = {N}")
+    given = [(f"`{name}`{what}", k) for name, what, k in (
+        ('n', '' if n is None else f' = {n}', n),
+        ('pulse', '' if sched is None else f' ({sched.numel()},)', None if sched is None else int(sched.numel())),
+        ('phase', '' if phase is None else f' {tuple(phase.shape)}', None if phase is None else int(phase.shape[1])))
+        if k is not None]
+    if not given:
+        raise ValueError("mrphy_amd: the number of repetitions is unknown: give `n`, `pulse` (K,), `phase` (N ⊻ 1, K) "
+                         "or several")
+    for what, k in given[1:]:
+        if k != given[0][1]:
+            raise ValueError(f"mrphy_amd: {given[0][0]} disagrees with {what}: K = {given[0][1]} or {k}?")
+    return given[0][1]
+
+
+@_host.half_via_float
+def ab_sequence(
+    A: Tensor, B: Tensor, *, pulse=None, n: Optional[int] = None, Mi: Optional[Tensor] = None,
+    phase: Optional[Tensor] = None, rest: Optional[Tensor] = None, T1: Optional[Tensor] = None,
+    T2: Optional[Tensor] = None, Δf: Optional[Tensor] = None
+) -> Tensor:
+    r"""The transient of a sequence whose repetitions differ: repetition ``k`` plays pulse ``pulse[k]`` of a bank after
+    a rest of its own duration -- MR fingerprinting, an inversion- or T2-prepared train, variable flip angles, dummy or
+    catalysing pulses before a train.  Per spin, from ``M_0 = Mi``, for ``k = 0 … K-1``:
+
+        ``M⁻ = F_k M_k + f_k``  -- ``sims.freeprec(M_k, rest_k, T1=T1, T2=T2, Δf=Δf)``, exactly as in :func:`ab_train`;
+
+        ``M_{k+1} = Rz(φ_k) [A_p Rz(-φ_k) M⁻ + B_p]``, ``p = pulse[k]``.
+
+    Record ``k`` is ``M_{k+1}``.  With ``P = 1`` and one ``rest`` it is :func:`ab_train`, bit for bit.
+
+    Usage:
+        ``Mt = ab_sequence(A, B, *, pulse, n, Mi, phase, rest, T1, T2, Δf)``
+    Inputs:
+        - ``A``: `(P, N, *Nd, xyz, 3)`, ``B``: `(P, N, *Nd, xyz)`: a bank of ``P ≥ 1`` pulses, the bank axis in front --
+          :func:`ab_rfgr`'s output for a batch of ``P·N`` entries is one by ``.unflatten(0, (P, N))``, a view.
+    Optionals:
+        - ``pulse``: a sequence of ints or an integer CPU tensor `(K,)`, each in ``[0, P)``: a host-side schedule, one for
+          all batch entries, checked before anything else and copied to the device once per call.  ``None`` = all
+          zeros, with ``P == 1`` only.
+        - ``n``: int; ``K`` comes from ``n``, ``pulse`` and ``phase``: at least one is given, and all given agree.
+        - ``Mi``: `(N ⊻ 1, *Nd ⊻ 1, xyz)`; ``None`` = ``(0, 0, 1)``.  ``phase``: `(N ⊻ 1, K)`, "rad"; ``None`` = zeros.
+        - ``rest``: `()` ⊻ `(N ⊻ 1,)`, "Sec", the same before every pulse as in :func:`ab_train`; or `(N ⊻ 1, K)`, one
+          duration per repetition.  A 1-d tensor always has the first meaning, also when ``N == K``.  ``rest_k = 0`` is
+          legal: no rest before pulse ``k``.  ``None``: no rest period at all.
+        - ``T1``, ``T2``, ``Δf``: shapes, broadcasting and absences exactly as :func:`ab_train`.
+    Outputs:
+        - ``Mt``: `(N, *Nd, K, xyz)`, the ``.movedim(0, -2)`` view of time-major storage, as :func:`ab_train` returns.
+
+    One kernel whatever the schedule (Ksq, ``mrphy_ab_sequence_fwd``): :func:`ab_train`'s repetition in fp64, the lane
+    reloading ``A_p, B_p`` when ``pulse[k]`` changes and re-forming the rest's constants when ``rest_k`` changes; a run of
+    equal repetitions costs what :func:`ab_train` costs.  Differentiable w.r.t. ``A``, ``B`` (the whole bank: an entry the
+    schedule never plays gets an exactly-zero gradient), ``Mi``, ``phase``, ``rest`` (in the form given), ``T1``, ``T2``
+    and ``Δf`` (Ksqb, ``mrphy_ab_sequence_bwd``: one sweep down the repetitions on the records themselves; the bank's
+    gradients go through an fp64 workspace of ``P·12`` numbers per spin, nothing of size ``K × spins`` is kept besides
+    the output), deterministic.
+
+    Out of scope: the received signal of such a sequence summed inside the kernel (a :func:`train_signal` with a
+    schedule); a steady state of a multi-pulse period; a schedule per batch entry; thinning the records; reading out at
+    an echo time after the pulse (``sims.freeprec`` on the records, an elementwise operation); a CPU path.
+    """
+    assert A.ndim >= 4 and A.shape[-2:] == (3, 3) and tuple(B.shape) == tuple(A.shape[:-1]), \
+        f"A {tuple(A.shape)} must be (P, N, *Nd, 3, 3) and B {tuple(B.shape)} (P, N, *Nd, 3)"
+    P, N, Nd = A.shape[0], A.shape[1], tuple(A.shape[2:-2])
+    sched = _sequence_schedule(pulse, P)
+    K = _sequence_length(n, sched, phase, N)
+    if rest is not None and (rest.ndim > 2 or (rest.ndim == 1 and rest.shape[0] not in (1, N)) or
+                             (rest.ndim == 2 and (rest.shape[0] not in (1, N) or rest.shape[1] != K))):
+        raise ValueError(f"mrphy_amd: `rest` {tuple(rest.shape)} must be (), (N ⊻ 1,) or (N ⊻ 1, K) with N = {N}, K = {K}")
+    _host.require_device_tensor(A, 'A')
+    _host.require_device_tensor(B, 'B')
+    assert A.dtype == B.dtype and A.device == B.device, "A and B must share dtype and device"
+    assert (T1 is None) == (T2 is None)  # both or neither
+    assert rest is not None or (T1 is None and Δf is None), "T1, T2, Δf describe the rest period: give `rest`"
+    if Mi is not None:
+        assert Mi.ndim == 2 + len(Nd) and Mi.shape[-1] == 3 and Mi.shape[0] in (1, N) and \
+            all(m in (1, d) for m, d in zip(Mi.shape[1:-1], Nd)), \
+            f"Mi {tuple(Mi.shape)} must be (N ⊻ 1, *Nd ⊻ 1, 3) for spins {(N,) + Nd}"
+    return AbSequenceHIP.apply(A, B, Mi, phase, rest, T1, T2, Δf, K, sched).movedim(0, -2)
+
+
+@_host.half_via_float
+def sequence_rfgr(
+    rf: Tensor, gr: Tensor, loc: Tensor, *,
+    pulse=None, n: Optional[int] = None, Mi: Optional[Tensor] = None, phase: Optional[Tensor] = None,
+    rest: Optional[Tensor] = None, T1: Optional[Tensor] = None, T2: Optional[Tensor] = None,
+    Δf: Optional[Tensor] = None, b1Map: Optional[Tensor] = None, γ_beff: Tensor = γH,
+    γ: Tensor = γH, dt: Tensor = dt0, consts: Optional[dict] = None, Δf_rest: Optional[Tensor] = None
+) -> Tensor:
+    r"""The magnetisation right after each repetition of a sequence that plays a bank of pulses by a schedule, from
+    ``rf`` `(P, N, xy, nT[, nCoils])` and ``gr`` `(P ⊻ 1, N, xyz, nT)`: ONE :func:`ab_rfgr` call on the batch ``P·N``
+    (``rf.flatten(0, 1)``, the spin-side operands ``loc, Δf, b1Map, T1, T2, γ, dt, γ_beff`` / ``consts`` repeated over
+    ``P``), its ``A, B`` viewed as the bank, then :func:`ab_sequence` -- built as :func:`train_rfgr` is on
+    :func:`ab_train`.  Operands of the pulses as :func:`ab_rfgr`, those of the train as :func:`ab_sequence`; ``Δf_rest``
+    as in :func:`steadystate_rfgr`.  Returns ``Mt`` `(N, *Nd, K, xyz)`.
+
+    Every route of :func:`ab_rfgr` (fused, split, composed; parallel transmit) serves it, so gradients reach ``rf``, ``gr``
+    and every operand ``ab_rfgr`` differentiates -- a flip-angle schedule ``rf = s[:, None, None, None] * rf0`` gets
+    ``∂/∂s`` by autograd -- and ``Mi, phase, rest, T1, T2, Δf`` / ``Δf_rest`` through the train: ``T1`` and ``T2`` receive the
+    sum of the pulses' and the rests' paths.  :func:`ab_rfgr`'s limit on the batch is inherited: ``P·N ≤ 65535``.  Out of
+    scope as in :func:`ab_sequence`.
+    """
+    assert rf.ndim in (4, 5) and gr.ndim == 4 and gr.shape[0] in (1, rf.shape[0]) and gr.shape[1] == rf.shape[1], \
+        f"rf {tuple(rf.shape)} must be (P, N, xy, nT[, nCoils]) and gr {tuple(gr.shape)} (P ⊻ 1, N, xyz, nT)"
+    P, N = rf.shape[0], rf.shape[1]
+    sched = _sequence_schedule(pulse, P)          # before any work on the device
+    over = lambda x: x.expand((P,) + tuple(x.shape)).flatten(0, 1)  # noqa: E731
+    # a spin-side operand: repeated over the bank where it has the batch axis, left to broadcast where it has not
+    side = lambda x: over(x) if (isinstance(x, Tensor) and x.ndim >= 1 and x.shape[0] == N and N > 1) else x  # noqa: E731
+    A, B = ab_rfgr(rf.flatten(0, 1), over(gr[0]) if gr.shape[0] == 1 else gr.flatten(0, 1), over(loc), Δf=side(Δf),
+                   b1Map=side(b1Map), γ_beff=side(γ_beff), T1=side(T1), T2=side(T2), γ=side(γ), dt=side(dt),
+                   consts=None if consts is None else {k: side(v) for k, v in consts.items()})
+    return ab_sequence(A.unflatten(0, (P, N)), B.unflatten(0, (P, N)), pulse=sched, n=n, Mi=Mi, phase=phase, rest=rest,
+                       T1=T1, T2=T2, Δf=Δf if Δf_rest is None else Δf_rest)
 
 
 class TrainSignalHIP(Function):
