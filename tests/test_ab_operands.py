@@ -1,4 +1,4 @@
-r"""``fused.ab_rfgr`` (K2ab / K2abb, its split and composed routes) and ``fused.steadystate_rfgr`` / ``ab_steadystate`` on every
+r"""``fused.ab_rfgr`` (K2ab / K2abb, under parallel transmit K2ab-mc / K2abb-mc, its split and composed routes) and ``fused.steadystate_rfgr`` / ``ab_steadystate`` on every
 operand form the host code accepts -- ``cases.fused_operand_variants``: broadcast shapes, 0-dim and stride-0 operands, a
 general ``*Nd`` grid, permuted views, buffers off the 16-byte grid, ``γ_beff != γ``, a batch ``dt``, non-contiguous and
 unaligned cotangents --, on steps of exactly zero field (``cases.zero_field_case``), with spins whose ``γ`` is 0, and at
@@ -32,6 +32,8 @@ import pytest
 from gpu_common import *  # noqa: F401,F403
 from mrphy_amd import _host
 from mrphy_amd.fused import _forward_prep
+from test_ab_ptx import BWD_MC, COUNTED, FWD_MC, _cap
+from test_ab_rfgr import _counted
 from test_ab_rfgr_host import ab_weights, oracle_ab_grads, oracle_steadystate_columns
 from test_fused_operands import VARIANTS, _batch_problem, _same_bits
 from test_steadystate import _gate as _ss_gate, _kernel_problem, _run as _ss_run
@@ -134,12 +136,40 @@ def _relaxed_only(v, n, s, nT):
     return torch.diag(torch.tensor([a2, a2, a1], dtype=torch.float64)), torch.tensor([0.0, 0.0, b], dtype=torch.float64)
 
 
-def _invariants(tag, mode, kind, nC, nT, name=None):
-    r"""Invariants (1)-(4) of the module docstring for one case; returns the fused results."""
+def _expected_route(tag, nC, nT):
+    r"""The route of ``ab_rfgr`` with a pulse gradient for ``nC > 1`` coils with their map, written out from
+    ``fused._decide_ab_route``'s rules and ``ab_rfgr``'s docstring (segments of 16 steps; the capacity of K2ab-mc /
+    K2abb-mc is 8 coils in fp32 and 4 in fp64): 'composed' above the capacity, 'fused' on whole segments, 'split' for a
+    ragged length of more than one segment."""
+    table = {(True, True): 'fused', (True, False): 'split', (False, True): 'composed', (False, False): 'composed'}
+    return table[(2 <= nC <= _cap(tag), nT % 16 == 0)] if nT > 16 else 'composed'
+
+
+def _assert_route(n, route, key):
+    r"""The calls ``n`` of one ``ab_rfgr`` forward + backward under parallel transmit are those of ``route``; the
+    one-coil entry points are never called."""
+    n = {k: c for k, c in n.items() if c}
+    assert not n.get('mrphy_ab_rfgr_fwd') and not n.get('mrphy_ab_rfgr_bwd'), (key, n)
+    if route == 'fused':
+        assert n == {FWD_MC: 1, BWD_MC: 1}, (key, n)
+    elif route == 'split':
+        assert n.get(FWD_MC) == 1 and n.get(BWD_MC) == 1 and n.get('mrphy_beff2ab_save') == 1, (key, n)
+    else:
+        assert not n.get(FWD_MC) and not n.get(BWD_MC) and n.get('mrphy_beff2ab_save') == 1, (key, n)
+
+
+def _invariants(tag, mode, kind, nC, nT, name=None, calls=None):
+    r"""Invariants (1)-(4) of the module docstring for one case; returns the fused results.  ``calls``: the counter of
+    ``test_ab_rfgr._counted`` over ``test_ab_ptx.COUNTED``; under parallel transmit the first run's route is asserted
+    by its call counts (:func:`_expected_route`)."""
     v, dense, zero = _case(tag, kind, nC, nT, name)
     key = f'c{nC}.nT{nT}.{name or kind}'
     lead = tuple(v['loc'].shape[:-1])
+    if calls is not None:
+        calls.clear()
     fu = _run('fused', v)
+    if calls is not None and nC > 1:
+        _assert_route(dict(calls), _expected_route(tag, nC, nT), key)
     assert fu['A'].shape == lead + (3, 3) and fu['B'].shape == lead + (3,), (key, fu['A'].shape, fu['B'].shape)
     assert fu['grad_rf'].shape == v['rf'].shape and fu['grad_gr'].shape == v['gr'].shape, key
     for k in NAMES:
@@ -159,7 +189,8 @@ def _invariants(tag, mode, kind, nC, nT, name=None):
     with torch.no_grad():
         Mo = fused.blochsim_rfgr(torch.zeros(lead + (3,), dtype=DT[tag], device=DEV), place(v['rf']), place(v['gr']),
                                  place(v['loc']), **kw)
-    # the forward alone is one K2ab over all nT steps (the composed kernels under parallel transmit), whatever nT is; with
+    # the forward alone is one K2ab over all nT steps (K2ab-mc under parallel transmit up to its capacity, the composed
+    # kernels above it), whatever nT is; with
     # a pulse gradient a ragged length is split and joined by two 3x3 products: the same numbers, other roundings
     f0 = _run('fused', v, grads=False)
     _same_bits(f0['B'], Mo, f'{key}: B vs blochsim_rfgr(Mi = 0)')
@@ -204,16 +235,20 @@ def _invariants(tag, mode, kind, nC, nT, name=None):
 # (a) spellings
 # =============================================================================================
 SPELLINGS = ([(nC, n, 48) for nC in (0, 1) for n in VARIANTS] + [(nC, n, 53) for nC in (0, 1) for n in cases.FUSED_NT53] +
-             [(4, 'cube', 48), (4, 'compact_mixed', 48)])
+             [(4, n, 48) for n in VARIANTS] + [(4, n, 53) for n in cases.FUSED_NT53] +
+             [(nC, n, 48) for nC in (2, 8) for n in ('compact_mixed', 'views', 'offset')])
 
 
 @pytest.mark.usefixtures('host_constants')
 @pytest.mark.parametrize('tag,mode', MODES)
 @pytest.mark.parametrize('nC,name,nT', SPELLINGS, ids=[f'c{c}-{n}-{t_}' for c, n, t_ in SPELLINGS])
-def test_operand_spellings(tag, mode, nC, name, nT):
+def test_operand_spellings(tag, mode, nC, name, nT, monkeypatch):
     r"""One problem, many spellings (module docstring).  nT = 48: K2ab and three checkpoint segments through K2abb; nT = 53:
     the split route, 48 fused steps joined with 5 composed ones (``A2 @ A1``, ``A2 @ B1 + B2`` on the operands' own
-    ``*Nd``); nC = 4: composed, and still right."""
+    ``*Nd``).  nC = 2, 4, 8 with their map: the parallel-transmit kernels K2ab-mc / K2abb-mc on the same zoo -- 4 coils on
+    all eight variants and on the split, 2 and 8 coils on 'compact_mixed' (a batch-shared ``b1Map`` under a batch-1
+    pulse), 'views' and 'offset'; 8 coils are the fp32 adjoint build that reads the map from LDS, and in fp64, above
+    that type's capacity of 4, the composed route.  The route each of them took is asserted by call counts."""
     given = _case(tag, 'zoo', nC, nT, name)[0]
     wA, wB = ab_weights(given)
     if name == 'views':        # the forms under test arrive as such
@@ -223,8 +258,9 @@ def test_operand_spellings(tag, mode, nC, name, nT):
                    for x in (given['loc'], given['rf'], given['gr'], wA, wB))
     if name == 'expanded':
         assert all(0 in place(given[k]).stride() for k in ('loc', 'Δf', 'γ_beff', 'T1', 'T2', 'γ'))
+    calls = _counted(monkeypatch, COUNTED)
     with mrphy_amd.precision(mode):
-        _invariants(tag, mode, 'zoo', nC, nT, name)
+        _invariants(tag, mode, 'zoo', nC, nT, name, calls=calls)
 
 
 # =============================================================================================

@@ -86,15 +86,21 @@ def _yardstick(P, K, use=OPS):
     return out
 
 
-def _run(P, K, use=OPS, over=None, pulse='own', n=False):
-    r"""The same through ``fused.ab_sequence`` on the device; ``over``: device tensors that replace operands (operand
-    forms); ``pulse``: what is passed as the schedule instead of the problem's own tuple."""
-    L = {k: dev(P[k]).clone().requires_grad_(True) for k in ('A', 'B') + tuple(use)}
+def _run(P, K, use=OPS, over=None, pulse='own', n=False, leaves=None, loss=None):
+    r"""The same through ``fused.ab_sequence`` on the device; ``over``: tensors that replace operands (operand forms);
+    ``pulse``: what is passed as the schedule instead of the problem's own tuple; ``leaves``: the names of the operands
+    that require grad (all of them by default; the others' gradients come back ``None``); ``loss``: a callable that is
+    handed ``Mt`` and runs the backward pass itself, instead of ``(Mt w).sum()``."""
+    wanted = lambda k: leaves is None or k in leaves  # noqa: E731
+    L = {k: dev(P[k]).clone().requires_grad_(wanted(k)) for k in ('A', 'B') + tuple(use)}
     for k, x in (over or {}).items():
-        L[k] = x.requires_grad_(True)
+        L[k] = x.requires_grad_(wanted(k))
     Mt = fused.ab_sequence(L['A'], L['B'], pulse=list(P['pulse']) if isinstance(pulse, str) else pulse,
                            **({'n': K} if n else {}), **{KW[k]: L[k] for k in use})
-    (Mt.movedim(-2, 0) * dev(P['w']).reshape((K,) + Mt.shape[:-2] + (3,))).sum().backward()
+    if loss is not None:
+        loss(Mt)
+    elif Mt.requires_grad:
+        (Mt.movedim(-2, 0) * dev(P['w']).reshape((K,) + Mt.shape[:-2] + (3,))).sum().backward()
     out = {'grad_' + k: x.grad for k, x in L.items()}
     out['Mt'] = Mt.detach()
     return out

@@ -276,6 +276,19 @@ def test_rest_of_a_wrong_shape_is_refused(shape):
         fused.ab_sequence(A, B, pulse=[0, 1, 2, 0], rest=torch.full(shape, 5e-3))
 
 
+@pytest.mark.parametrize('shape', [(2, 1), (1, 1)])
+def test_a_rest_table_of_one_column_is_refused_unless_K_is_1(shape):
+    r"""N = 2, K = 4: a 2-d ``rest`` is a table `(N ⊻ 1, K)`, so `(N, 1)` and `(1, 1)` -- durations that do not change,
+    written with a column axis -- are a ``ValueError``; the spellings of a constant rest are `()`, `(1,)` and `(N,)`.
+    At ``K = 1`` the same two shapes ARE the table and pass the check (the call then goes on to ask for device
+    tensors)."""
+    A, B = _cpu_bank()
+    with pytest.raises(ValueError, match='`rest`'):
+        fused.ab_sequence(A, B, pulse=[0, 1, 2, 0], rest=torch.full(shape, 5e-3))
+    with pytest.raises(RuntimeError, match='no CPU fallback'):
+        fused.ab_sequence(A, B, pulse=[1], rest=torch.full(shape, 5e-3))
+
+
 # ---------------------------------------------------------------------------------------------
 # the fixture from the reference against the yardstick on the oracle's A, B
 # ---------------------------------------------------------------------------------------------

@@ -71,15 +71,21 @@ def _yardstick(P, use=CONSTS):
     return out
 
 
-def _run(P, use=CONSTS, over=None):
+def _run(P, use=CONSTS, over=None, leaves=None, loss=None):
     r"""``Mss`` and the gradients of ``(Mss w).sum()`` w.r.t. ``A, B`` and the operands ``use`` through
-    ``fused.ab_steadystate`` on the device; ``over``: device tensors that replace operands (operand forms)."""
-    L = {k: dev(P[k]).clone().requires_grad_(True) for k in ('A', 'B') + tuple(use)}
+    ``fused.ab_steadystate`` on the device; ``over``: tensors that replace operands (operand forms); ``leaves``: the
+    names of the operands that require grad (all of them by default; the others' gradients come back ``None``);
+    ``loss``: a callable that is handed ``Mss`` and runs the backward pass itself, instead of ``(Mss w).sum()``."""
+    wanted = lambda k: leaves is None or k in leaves  # noqa: E731
+    L = {k: dev(P[k]).clone().requires_grad_(wanted(k)) for k in ('A', 'B') + tuple(use)}
     for k, x in (over or {}).items():
-        L[k] = x.requires_grad_(True)
+        L[k] = x.requires_grad_(wanted(k))
     kw = {('Δf' if k == 'df' else k): L[k] for k in use}
     Mss = fused.ab_steadystate(L['A'], L['B'], **kw)
-    (Mss * dev(P['w']).reshape(Mss.shape)).sum().backward()
+    if loss is not None:
+        loss(Mss)
+    elif Mss.requires_grad:
+        (Mss * dev(P['w']).reshape(Mss.shape)).sum().backward()
     out = {'grad_' + k: x.grad for k, x in L.items()}
     out['Mss'] = Mss.detach()
     return out

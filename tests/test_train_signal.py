@@ -92,17 +92,24 @@ def _cached_yardstick(N, nM, K, tag, nRx):
     return _yardstick(P, K, _rx(N, nM, nRx, tag))
 
 
-def _run(P, K, rx, use=OPS, over=None, w=None, v=None, n=True, **kw):
-    r"""The same through ``fused.train_signal`` on the device; ``over``: device tensors that replace operands."""
+def _run(P, K, rx, use=OPS, over=None, w=None, v=None, n=True, leaves=None, loss=None, **kw):
+    r"""The same through ``fused.train_signal`` on the device; ``over``: tensors that replace operands; ``leaves``: the
+    names of the operands that require grad (all of them by default; the others' gradients come back ``None``);
+    ``loss``: a callable that is handed ``sig, Mlast`` and runs the backward pass itself, instead of
+    ``(sig w).sum() + (Mlast v).sum()``."""
     w, v = _loss_weights(P, K, rx, w, v)
-    L = {k: dev(P[k]).clone().requires_grad_(True) for k in ('A', 'B') + tuple(use)}
+    wanted = lambda k: leaves is None or k in leaves  # noqa: E731
+    L = {k: dev(P[k]).clone().requires_grad_(wanted(k)) for k in ('A', 'B') + tuple(use)}
     if rx is not None:
-        L['rx'] = dev(rx).clone().requires_grad_(True)
+        L['rx'] = dev(rx).clone().requires_grad_(wanted('rx'))
     for k, x in (over or {}).items():
-        L[k] = x.requires_grad_(True)
+        L[k] = x.requires_grad_(wanted(k))
     sig, Mlast = fused.train_signal(L['A'], L['B'], **({'n': K} if n else {}), **{KW[k]: L[k] for k in use},
                                     rx=L.get('rx'), return_last=True, **kw)
-    ((sig * dev(w)).sum() + (Mlast * dev(v)).sum()).backward()
+    if loss is not None:
+        loss(sig, Mlast)
+    elif sig.requires_grad:
+        ((sig * dev(w)).sum() + (Mlast * dev(v)).sum()).backward()
     out = {'grad_' + k: x.grad for k, x in L.items()}
     out['sig'], out['Mlast'] = sig.detach(), Mlast.detach()
     return out
