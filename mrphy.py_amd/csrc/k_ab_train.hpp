@@ -214,3 +214,14 @@ inline int train_check(int dtype, const void* A, const void* B, const void* rest
         return MRPHY_EALIGN;
     return 0;
 }
+
+// the operands A .. cs and the sizes, as every entry point of Ktr / Ktrb and Ktrs / Ktrsb passes them on
+inline void train_fill(TrainArgs& q, const void* A, const void* B, const void* rest, int64_t rest_sn, Bc T1, Bc T2, Bc df,
+                       const void* Mi, int64_t Mi_sn, int64_t Mi_sm, const void* cs, int64_t cs_sn, int64_t N,
+                       int64_t nM, int64_t K)
+{
+    q.A = A; q.B = B; q.rest = rest; q.rest_sn = rest_sn;
+    q.T1 = T1; q.T2 = T2; q.df = df;
+    q.Mi = Mi; q.Mi_sn = Mi_sn; q.Mi_sm = Mi_sm; q.cs = reinterpret_cast<const double*>(cs); q.cs_sn = cs_sn;
+    q.rows = N * nM; q.nM = nM; q.K = K;
+}

@@ -19,10 +19,9 @@ int mrphy_ab_train_fwd(int dtype, const void* A, const void* B, const void* rest
     if (!Mt) return MRPHY_EINVAL;
     if (!aligned_to(Mt, tsize(dtype))) return MRPHY_EALIGN;
     TrainArgs q{};
-    q.A = A; q.B = B; q.rest = rest; q.rest_sn = rest_sn;
-    q.T1 = Bc{T1, T1_sn, T1_sm}; q.T2 = Bc{T2, T2_sn, T2_sm}; q.df = Bc{df, df_sn, df_sm};
-    q.Mi = Mi; q.Mi_sn = Mi_sn; q.Mi_sm = Mi_sm; q.cs = reinterpret_cast<const double*>(cs); q.cs_sn = cs_sn;
-    q.Mt = Mt; q.rows = N * nM; q.nM = nM; q.K = K;
+    train_fill(q, A, B, rest, rest_sn, Bc{T1, T1_sn, T1_sm}, Bc{T2, T2_sn, T2_sm}, Bc{df, df_sn, df_sm}, Mi, Mi_sn, Mi_sm,
+               cs, cs_sn, N, nM, K);
+    q.Mt = Mt;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)((nM + 255) / 256), (unsigned)N);
     if (dtype == MRPHY_F32) hipLaunchKernelGGL((k_ab_train_fwd<float>), grid, dim3(256), 0, st, q);
@@ -46,12 +45,10 @@ int mrphy_ab_train_bwd(int dtype, const void* A, const void* B, const void* grad
         !aligned_to(grad_consts, ts) || !aligned_to(grad_Mi, ts) || !aligned_to(grad_phase, ts))
         return MRPHY_EALIGN;
     TrainArgs q{};
-    q.A = A; q.B = B; q.g = grad_Mt; q.rest = rest; q.rest_sn = rest_sn;
-    q.T1 = Bc{T1, T1_sn, T1_sm}; q.T2 = Bc{T2, T2_sn, T2_sm}; q.df = Bc{df, df_sn, df_sm};
-    q.Mi = Mi; q.Mi_sn = Mi_sn; q.Mi_sm = Mi_sm; q.cs = reinterpret_cast<const double*>(cs); q.cs_sn = cs_sn;
-    q.Mt = const_cast<void*>(Mt);
+    train_fill(q, A, B, rest, rest_sn, Bc{T1, T1_sn, T1_sm}, Bc{T2, T2_sn, T2_sm}, Bc{df, df_sn, df_sm}, Mi, Mi_sn, Mi_sm,
+               cs, cs_sn, N, nM, K);
+    q.g = grad_Mt; q.Mt = const_cast<void*>(Mt);
     q.gA = grad_A; q.gB = grad_B; q.gC = grad_consts; q.gMi = grad_Mi; q.gphi = grad_phase;
-    q.rows = N * nM; q.nM = nM; q.K = K;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)((nM + 255) / 256), (unsigned)N);
     if (dtype == MRPHY_F32) hipLaunchKernelGGL((k_ab_train_bwd<float>), grid, dim3(256), 0, st, q);

@@ -75,11 +75,8 @@ int mrphy_train_signal_fwd(int dtype, const void* A, const void* B, const void* 
     const size_t ts = tsize(dtype);
     if (!aligned_to(sig, ts) || !aligned_to(Mlast, ts) || !aligned_to(ck, sizeof(double))) return MRPHY_EALIGN;
     TrainSigArgs a{};
-    TrainArgs& q = a.t;
-    q.A = A; q.B = B; q.rest = rest; q.rest_sn = rest_sn;
-    q.T1 = Bc{T1, T1_sn, T1_sm}; q.T2 = Bc{T2, T2_sn, T2_sm}; q.df = Bc{df, df_sn, df_sm};
-    q.Mi = Mi; q.Mi_sn = Mi_sn; q.Mi_sm = Mi_sm; q.cs = reinterpret_cast<const double*>(cs); q.cs_sn = cs_sn;
-    q.rows = N * nM; q.nM = nM; q.K = K;
+    train_fill(a.t, A, B, rest, rest_sn, Bc{T1, T1_sn, T1_sm}, Bc{T2, T2_sn, T2_sm}, Bc{df, df_sn, df_sm}, Mi, Mi_sn, Mi_sm,
+               cs, cs_sn, N, nM, K);
     a.rx = rx; a.nRx = nRx; a.Mlast = Mlast; a.ck = reinterpret_cast<double*>(ck);
     a.work = reinterpret_cast<double*>(work); a.N = N; a.P = trs_waves(nM);
     hipStream_t st = (hipStream_t)stream;
@@ -111,12 +108,9 @@ int mrphy_train_signal_bwd(int dtype, const void* A, const void* B, const void* 
         !aligned_to(grad_Mi, ts) || !aligned_to(grad_phase, ts) || !aligned_to(grad_rx, ts))
         return MRPHY_EALIGN;
     TrainSigArgs a{};
-    TrainArgs& q = a.t;
-    q.A = A; q.B = B; q.rest = rest; q.rest_sn = rest_sn;
-    q.T1 = Bc{T1, T1_sn, T1_sm}; q.T2 = Bc{T2, T2_sn, T2_sm}; q.df = Bc{df, df_sn, df_sm};
-    q.Mi = Mi; q.Mi_sn = Mi_sn; q.Mi_sm = Mi_sm; q.cs = reinterpret_cast<const double*>(cs); q.cs_sn = cs_sn;
-    q.gA = grad_A; q.gB = grad_B; q.gC = grad_consts; q.gMi = grad_Mi;
-    q.rows = N * nM; q.nM = nM; q.K = K;
+    train_fill(a.t, A, B, rest, rest_sn, Bc{T1, T1_sn, T1_sm}, Bc{T2, T2_sn, T2_sm}, Bc{df, df_sn, df_sm}, Mi, Mi_sn, Mi_sm,
+               cs, cs_sn, N, nM, K);
+    a.t.gA = grad_A; a.t.gB = grad_B; a.t.gC = grad_consts; a.t.gMi = grad_Mi;
     a.rx = rx; a.nRx = nRx; a.ck = const_cast<double*>(reinterpret_cast<const double*>(ck));
     a.work = grad_phase ? reinterpret_cast<double*>(work) : nullptr;
     a.gs = reinterpret_cast<const double*>(grad_sig); a.gMl = grad_Mlast; a.grx = grad_rx;

@@ -69,9 +69,15 @@ from torch.autograd import Function
 
 from . import _lib, _host
 from ._consts import γH, dt0
+from .beffective import _code
 
 __all__ = ['blochsim_rfgr', 'blochsim_rfgr_traj', 'signal_rfgr', 'ab_rfgr', 'ab_steadystate', 'steadystate_rfgr',
            'ab_train', 'train_rfgr', 'train_signal', 'train_signal_rfgr', 'ab_sequence', 'sequence_rfgr']
+
+
+def _ptr(x):
+    r"""What ctypes gets for ``x``: a tensor's address; ``None`` and plain numbers as they are."""
+    return x.data_ptr() if isinstance(x, Tensor) else x
 
 
 def _forward_prep(lib, p, γ2πdt, E1, E2, E1_1, dtype, device, need):
@@ -153,6 +159,7 @@ _MAPS = ('loc', 'Δf', 'b1Map')
 # The adjoint entry points: what each takes between the operands and ``work, work_bytes, N, nM, nT[, nC], stream``, by
 # the names of :func:`_fused_adjoint`'s values.
 _PULSE_OUT = ('gMi', 'grf', 'ggr')
+_AB_OUT = ('gA', 'gB', 'grf', 'ggr')
 _ADJOINT_ARGS = {
     'mrphy_blochsim_rfgr_bwd': ('gMo', *_PULSE_OUT),
     'mrphy_blochsim_rfgr_traj_bwd': ('gMt', 'every', *_PULSE_OUT),
@@ -163,56 +170,73 @@ _ADJOINT_ARGS = {
     'mrphy_signal_rfgr_bwd': ('rx', 'gMo', 'gsig', 'every', *_PULSE_OUT),
     'mrphy_signal_rfgr_mrx_bwd': ('rx', 'nRx', 'gMo', 'gsig', 'every', *_PULSE_OUT),
     'mrphy_signal_rfgr_consts_bwd': ('rx', 'nRx', 'gMo', 'gsig', 'every', *_PULSE_OUT, 'gC'),
+    'mrphy_ab_rfgr_bwd': _AB_OUT,
+    'mrphy_ab_rfgr_mc_bwd': _AB_OUT,
+    'mrphy_ab_rfgr_maps_bwd': (*_AB_OUT, 'gloc', 'gBz', 'gb1'),
+    'mrphy_ab_rfgr_consts_bwd': (*_AB_OUT, 'gloc', 'gBz', 'gb1', 'gC'),
 }
 
 
-def _fused_adjoint(s, Mck, signal, want, gMo=None, gMt=None, gsig=None):
-    r"""The one adjoint call of both Functions: ``s`` the forward's :class:`_Saved`, ``want`` the gradients wanted by
-    argument name, ``gMo``, ``gMt``, ``gsig`` the cotangents received (contiguous, of the kernels' dtype).  Returns the
-    raw gradients ``{name: tensor, or None where not wanted}``: per spin ``gMi``, ``gloc``, ``gBz`` (for ``Δf``),
-    ``gb1``, ``gC``; per pulse ``grf`` `(N, 2, nT, nC)`, ``ggr`` `(N, 3, nT)`."""
+def _need_γb(want, p):
+    r"""Whether ``γ_beff`` gets a gradient: it is wanted and there is a ``Δf`` (without one the field does not depend on
+    ``γ_beff``).  It is a fold of ``gBz``, which the adjoint then forms whether ``Δf`` wants its own or not."""
+    return bool(want.get('γ_beff')) and p.df is not None
+
+
+def _adjoint_name(family, spin, mc, mrx, traj):
+    r"""The cheapest entry point of ``family`` ('blochsim', 'signal', 'ab') that serves a request: ``spin`` is ``'consts_'``
+    (the CONSTS builds form the map sums too), ``'maps_'`` or ``''``; ``mc``: parallel transmit, where a map or constants'
+    gradient is never wanted (:func:`_decide_route`, :func:`_decide_ab_route`); the signal's builds take one receive coil
+    and an array alike, ``mrx`` says which the plain one is asked for."""
+    if family == 'signal':
+        return 'mrphy_signal_rfgr_' + ('consts_' if spin == 'consts_' else 'mrx_' if mrx else '') + 'bwd'
+    if family == 'ab':
+        assert not (mc and spin), "fused.ab_rfgr: no map or constants' gradient under parallel transmit"
+        return 'mrphy_ab_rfgr_' + ('mc_' if mc else spin) + 'bwd'
+    return 'mrphy_blochsim_rfgr_' + (spin or ('mc_' if mc else '') + ('traj_' if traj else '')) + 'bwd'
+
+
+def _fused_adjoint(s, Mck, family, want, gMo=None, gMt=None, gsig=None, gA=None, gB=None):
+    r"""The one adjoint call of the three Functions: ``s`` the forward's :class:`_Saved`, ``Mck`` its checkpoints,
+    ``family`` 'blochsim', 'signal' or 'ab', ``want`` the gradients wanted by argument name, ``gMo``, ``gMt``, ``gsig``
+    (``ab``: ``gA``, ``gB``) the cotangents received (contiguous, of the kernels' dtype).  Returns the raw gradients
+    ``{name: tensor, or None where not wanted}``: per spin ``gMi`` (not ``ab``: it has no ``Mi``), ``gloc``, ``gBz`` (for
+    ``Δf`` and ``γ_beff``), ``gb1``, ``gC``; per pulse ``grf`` `(N, 2, nT, nC)`, ``ggr`` `(N, 3, nT)`."""
     lib = _lib.require_library()
     p, device, full = s.p, Mck.device, (s.p.N,) + s.p.Nd
-    outs = dict(gMi=(want['Mi'], full + (3,)), grf=(want['rf'], (p.N, 2, p.nT, p.nC)), ggr=(want['gr'], (p.N, 3, p.nT)),
-                gloc=(want.get('loc'), full + (3,)), gBz=(want.get('Δf'), full), gb1=(want.get('b1Map'), full + (2,)),
-                gC=(any(want[k] for k in _CONSTS), full + (4,)))
+    outs = dict(gMi=(want.get('Mi'), full + (3,)), grf=(want['rf'], (p.N, 2, p.nT, p.nC)), ggr=(want['gr'], (p.N, 3, p.nT)),
+                gloc=(want.get('loc'), full + (3,)), gBz=(want.get('Δf') or _need_γb(want, p), full),
+                gb1=(want.get('b1Map'), full + (2,)), gC=(any(want[k] for k in _CONSTS), full + (4,)))
     out = {k: torch.empty(shape, dtype=Mck.dtype, device=device) if w else None for k, (w, shape) in outs.items()}
     if p.N * p.nM * p.nT == 0:
         # No spin or no step: the library's adjoints are no-ops then (``include/mrphy_hip.h``: an empty problem is a
-        # success that writes nothing), so the gradients are written here -- ``Mo`` is ``Mi`` and nothing depends on
-        # the pulse, the maps or the constants.
+        # success that writes nothing), so the gradients are written here -- ``Mo`` is ``Mi`` (``A = I, B = 0``) and
+        # nothing depends on the pulse, the maps or the constants.
         for k, g in out.items():
             if g is not None:
                 g.copy_(gMo.reshape(g.shape)) if k == 'gMi' and gMo is not None else g.zero_()
         return out
     mc, mrx = p.nC != 1, len(s.rx) > 1
-    # the CONSTS builds form the map sums too, and the signal's take one coil and an array alike (rx, nRx); a map
-    # gradient is wanted under one transmit coil only (_route)
-    if signal:
-        name = 'mrphy_signal_rfgr_' + ('consts_bwd' if out['gC'] is not None else 'mrx_bwd' if mrx else 'bwd')
-    elif out['gC'] is not None:
-        name = 'mrphy_blochsim_rfgr_consts_bwd'
-    elif any(out[k] is not None for k in ('gloc', 'gBz', 'gb1')):
-        name = 'mrphy_blochsim_rfgr_maps_bwd'
-    else:
-        name = 'mrphy_blochsim_rfgr_' + ('mc_' if mc else '') + ('traj_bwd' if gMt is not None else 'bwd')
-    nbytes = int(lib.mrphy_blochsim_rfgr_mc_bwd_workspace(s.code, p.N, p.nM, p.nT, p.nC) if mc    # per-coil sums
+    name = _adjoint_name(family, 'consts_' if out['gC'] is not None else
+                         'maps_' if any(out[k] is not None for k in ('gloc', 'gBz', 'gb1')) else '', mc, mrx, gMt is not None)
+    nbytes = int((lib.mrphy_ab_rfgr_mc_bwd_workspace if family == 'ab' else lib.mrphy_blochsim_rfgr_mc_bwd_workspace)(
+                     s.code, p.N, p.nM, p.nT, p.nC) if mc    # per-coil sums
                  else lib.mrphy_blochsim_rfgr_bwd_workspace(s.code, p.N, p.nM, p.nT))
     work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
-    vals = dict(out, gMo=gMo, gMt=gMt, gsig=gsig, every=s.every or 0, rx=s.rx[0] if s.rx else None,
+    vals = dict(out, gMo=gMo, gMt=gMt, gsig=gsig, gA=gA, gB=gB, every=s.every or 0, rx=s.rx[0] if s.rx else None,
                 nRx=s.rx[1] if mrx else 1)
-    ptr = lambda x: x.data_ptr() if isinstance(x, Tensor) else x  # noqa: E731
     with torch.cuda.device(device):
         rc = getattr(lib, name)(s.code, Mck.data_ptr(), *p.k0_args(), *s.consts,
-                                *(ptr(vals[k]) for k in _ADJOINT_ARGS[name]), work.data_ptr(), work.numel(),
+                                *(_ptr(vals[k]) for k in _ADJOINT_ARGS[name]), work.data_ptr(), work.numel(),
                                 p.N, p.nM, p.nT, *((p.nC,) if mc else ()), _host.current_stream(device))
     _lib.check(rc, name)
     return out
 
 
-def _fold_pulse_and_const_grads(raw, s, want):
-    r"""``{argument name: gradient}`` of ``Mi``, ``rf``, ``gr`` and the step constants from the raw gradients, in the
-    shapes and dtypes the caller's operands had: what both backwards return."""
+def _fold_grads(raw, s, want):
+    r"""``{argument name: gradient}`` from the raw gradients of :func:`_fused_adjoint`, in the shapes and dtypes the
+    caller's operands had: ``Mi``, ``rf``, ``gr``, the step constants, the spin-side maps and ``γ_beff`` -- what the three
+    backwards return."""
     from .beffective import _fold_pulse_grad
     g = dict(Mi=raw['gMi'])
     for k, raw_k, no_b1 in (('rf', 'grf', s.p.b1 is None), ('gr', 'ggr', False)):
@@ -221,6 +245,10 @@ def _fold_pulse_and_const_grads(raw, s, want):
     if raw['gC'] is not None:
         g.update(zip(_CONSTS, _fold_const_grads(raw['gC'], s.p, [s.likes.get(k) for k in _CONSTS],
                                                 [want[k] for k in _CONSTS])))
+    g.update(zip(_MAPS, _fold_map_grads(raw['gloc'], raw['gBz'] if want.get('Δf') else None, raw['gb1'], s.p,
+                                        [s.likes.get(k) for k in _MAPS])))
+    if _need_γb(want, s.p):
+        g['γ_beff'] = _fold_gamma_beff_grad(raw['gBz'], s.p, s.likes['γ_beff'])
     return g
 
 
@@ -276,19 +304,13 @@ class BlochSimRfGrHIP(Function):
             return tuple(None for _ in ARGS)
         s = ctx.saved
         (Mck,) = ctx.saved_tensors
-        need_γb = want['γ_beff'] and s.p.df is not None        # without Δf the field does not depend on γ_beff
         traj = s.every is not None
         # the precise adjoint divides by E once (as the reference's does at every step): refuse E == 0 HERE, where it
         # matters -- the forward succeeds as the reference's does; cached per constants
         _host.require_invertible_relaxation(s.code, s.alive[1], s.alive[2],
                                             'fused.blochsim_rfgr_traj' if traj else 'fused.blochsim_rfgr')
         gM = grad_M.to(Mck.dtype).contiguous()  # the trajectory's: time-major, as the forward returned it -- free if so
-        raw = _fused_adjoint(s, Mck, False, {**want, 'Δf': want['Δf'] or need_γb}, **{'gMt' if traj else 'gMo': gM})
-        g = _fold_pulse_and_const_grads(raw, s, want)
-        g.update(zip(_MAPS, _fold_map_grads(raw['gloc'], raw['gBz'] if want['Δf'] else None, raw['gb1'], s.p,
-                                            [s.likes.get(k) for k in _MAPS])))
-        if need_γb:
-            g['γ_beff'] = _fold_gamma_beff_grad(raw['gBz'], s.p, s.likes['γ_beff'])
+        g = _fold_grads(_fused_adjoint(s, Mck, 'blochsim', want, **{'gMt' if traj else 'gMo': gM}), s, want)
         return tuple(g.get(k) for k in ARGS)
 
 
@@ -344,8 +366,7 @@ class SignalRfGrHIP(Function):
         (Mck,) = ctx.saved_tensors
         _host.require_invertible_relaxation(s.code, s.alive[1], s.alive[2], 'fused.signal_rfgr')
         cot = {k: None if x is None else x.to(Mck.dtype).contiguous() for k, x in (('gsig', grad_sig), ('gMo', grad_Mo))}
-        raw = _fused_adjoint(s, Mck, True, want, **cot)
-        g = _fold_pulse_and_const_grads(raw, s, want)
+        g = _fold_grads(_fused_adjoint(s, Mck, 'signal', want, **cot), s, want)
         return tuple(g.get(k) for k in SignalRfGrHIP.ARGS)
 
 
@@ -394,55 +415,15 @@ class AbRfGrHIP(Function):
 
     @staticmethod
     def backward(ctx, grad_A, grad_B):
-        from .beffective import _fold_pulse_grad
         ARGS = AbRfGrHIP.ARGS                         # (loc .. γ_beff: False where they were not handed over)
         want = dict(zip(ARGS, (*ctx.needs_input_grad, *(False,) * len(ARGS))))
         if not any(want.values()) or (grad_A is None and grad_B is None):
             return tuple(None for _ in ARGS)
-        lib = _lib.require_library()
         s = ctx.saved
         (ABck,) = ctx.saved_tensors
-        p, device, dtype = s.p, ABck.device, ABck.dtype
         _host.require_invertible_relaxation(s.code, s.alive[1], s.alive[2], 'fused.ab_rfgr')
-        gA, gB = (None if x is None else x.to(dtype).contiguous() for x in (grad_A, grad_B))
-        need_γb = want['γ_beff'] and p.df is not None          # without Δf the field does not depend on γ_beff
-        full = (p.N,) + p.Nd
-        outs = dict(grf=(want['rf'], (p.N, 2, p.nT, p.nC)), ggr=(want['gr'], (p.N, 3, p.nT)),
-                    gloc=(want['loc'], full + (3,)), gBz=(want['Δf'] or need_γb, full), gb1=(want['b1Map'], full + (2,)),
-                    gC=(any(want[k] for k in _CONSTS), full + (4,)))
-        raw = {k: torch.empty(shape, dtype=dtype, device=device) if w else None for k, (w, shape) in outs.items()}
-        if p.N * p.nM * p.nT == 0:
-            # no spin or no step: the library's adjoints write nothing then, and A = I, B = 0 whatever the operands are
-            for g in raw.values():
-                if g is not None:
-                    g.zero_()
-        else:
-            # the cheapest build that serves what is wanted; the CONSTS build forms the map sums too
-            spin = (('gloc', 'gBz', 'gb1', 'gC') if raw['gC'] is not None else
-                    ('gloc', 'gBz', 'gb1') if any(raw[k] is not None for k in ('gloc', 'gBz', 'gb1')) else ())
-            # parallel transmit: the pulse gradient alone (_decide_ab_route), per-coil sums in the workspace
-            mc = p.nC != 1
-            assert not (mc and spin), "fused.ab_rfgr: no map or constants' gradient under parallel transmit"
-            name = 'mrphy_ab_rfgr_' + ('mc_' if mc else {0: '', 3: 'maps_', 4: 'consts_'}[len(spin)]) + 'bwd'
-            nbytes = int(lib.mrphy_ab_rfgr_mc_bwd_workspace(s.code, p.N, p.nM, p.nT, p.nC) if mc
-                         else lib.mrphy_blochsim_rfgr_bwd_workspace(s.code, p.N, p.nM, p.nT))
-            work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
-            ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
-            with torch.cuda.device(device):
-                rc = getattr(lib, name)(s.code, ABck.data_ptr(), *p.k0_args(), *s.consts, ptr(gA), ptr(gB),
-                                        ptr(raw['grf']), ptr(raw['ggr']), *(ptr(raw[k]) for k in spin),
-                                        work.data_ptr(), work.numel(), p.N, p.nM, p.nT, *((p.nC,) if mc else ()),
-                                        _host.current_stream(device))
-            _lib.check(rc, name)
-        g = {k: _fold_pulse_grad(raw[r], s.likes[k][0], s.likes[k][1], k == 'rf' and p.b1 is None)
-             for k, r in (('rf', 'grf'), ('gr', 'ggr')) if raw[r] is not None}
-        if raw['gC'] is not None:
-            g.update(zip(_CONSTS, _fold_const_grads(raw['gC'], p, [s.likes.get(k) for k in _CONSTS],
-                                                    [want[k] for k in _CONSTS])))
-        g.update(zip(_MAPS, _fold_map_grads(raw['gloc'], raw['gBz'] if want['Δf'] else None, raw['gb1'], p,
-                                            [s.likes.get(k) for k in _MAPS])))
-        if need_γb:
-            g['γ_beff'] = _fold_gamma_beff_grad(raw['gBz'], p, s.likes['γ_beff'])
+        cot = {k: None if x is None else x.to(ABck.dtype).contiguous() for k, x in (('gA', grad_A), ('gB', grad_B))}
+        g = _fold_grads(_fused_adjoint(s, ABck, 'ab', want, **cot), s, want)
         return tuple(g.get(k) for k in ARGS)
 
 
@@ -469,7 +450,8 @@ class _JoinAb(Function):
 
 def _ab_spin_fused(dtype, consts_grad):
     r"""Whether K2abb's MAPS / CONSTS builds serve :func:`ab_rfgr`'s map and constants' gradients in ``dtype``: every
-    build of the library does."""
+    build of the library does.  Kept as the seam through which ``tests/test_ab_spin_grads.py`` switches them off to
+    obtain the composed route."""
     return True
 
 
@@ -521,6 +503,49 @@ def _decide_route(*, nT, seg, nC, one_coil, has_b1, f64, signal, ptx_max, pulse_
     return 'fused', (pulse_grad or maps_fused or consts_fused) and fused_adjoint_ok, maps_fused, γb_grad
 
 
+def _requires_grad(x) -> bool:
+    return torch.is_grad_enabled() and isinstance(x, Tensor) and x.requires_grad
+
+
+class _PulseFacts(NamedTuple):
+    r"""What :func:`_route` and :func:`ab_rfgr` know of a call before they decide its route."""
+    p: object                 # the pulse on the spins, of the detached operands (beffective._PulseOnSpins)
+    one_coil: bool            # one transmit coil: rf without a coil axis, or one whose coils a b1Map does not weight
+    pulse_grad: bool          # Mi, rf or gr requires grad
+    maps_grad: bool           # loc, Δf or b1Map does, or γb_grad
+    γb_grad: bool             # γ_beff does and there is a Δf (without one the field does not depend on γ_beff)
+    consts_grad: bool         # T1, T2, γ or dt does -- or an entry of consts=
+
+
+def _pulse_facts(rf, gr, loc, kw, Mi=None):
+    from . import beffective
+    Δf, b1Map = kw['Δf'], kw['b1Map']
+    γb_grad = _requires_grad(kw['γ_beff']) and Δf is not None
+    maps_grad = any(_requires_grad(x) for x in (loc, Δf, b1Map)) or γb_grad
+    pulse_grad = any(_requires_grad(x) for x in (Mi, rf, gr))
+    consts_grad = any(_requires_grad(x) for x in (kw['consts'].values() if kw['consts'] is not None
+                                                  else (kw['T1'], kw['T2'], kw['γ'], kw['dt'])))
+    p = beffective._PulseOnSpins(rf.detach(), gr.detach(), loc.detach(), None if Δf is None else Δf.detach(),
+                                 None if b1Map is None else b1Map.detach(), kw['γ_beff'].detach())
+    one_coil = p.nC == 1 and (rf.ndim == 3 or b1Map is not None or rf.shape[-1] == 1)
+    return _PulseFacts(p, one_coil, pulse_grad, maps_grad, γb_grad, consts_grad)
+
+
+def _step_constants(kw, consts_grad, ndim, device):
+    r"""``(γ2πdt, E1, E2, E1_1)`` of a call: the entries of ``consts=``; or, when one of ``T1, T2, γ, dt`` requires grad,
+    differentiable tensors formed as ``slowsims.blochsim`` forms them -- ``relax_constants``' expressions on the same
+    padded operands on the same device, so the values, and the result, are the bits of the call that does not
+    differentiate them; or :func:`mrphy_amd.sims.relax_constants` itself."""
+    from . import sims
+    if kw['consts'] is not None:
+        return tuple(kw['consts'].get(k) for k in _CONSTS)
+    if consts_grad:
+        cdev = _host.const_device(device)
+        pad = lambda x: None if x is None else _host.pad_trailing(x.to(cdev), ndim)  # noqa: E731
+        return sims._gamma_dt_constants(pad(kw['T1']), pad(kw['T2']), pad(kw['γ']), pad(kw['dt']))
+    return sims.relax_constants(kw['T1'], kw['T2'], kw['γ'], kw['dt'], ndim, device)
+
+
 def _route(Mi, rf, gr, loc, every, kw, signal=False, rx=None):
     r"""The routing :func:`blochsim_rfgr` (``every = None``), :func:`blochsim_rfgr_traj` and (``signal``, with its
     receive map ``rx``) :func:`signal_rfgr` share; the decision itself is :func:`_decide_route`'s.  Returns
@@ -540,27 +565,16 @@ def _route(Mi, rf, gr, loc, every, kw, signal=False, rx=None):
     ``slowsims.blochsim`` forms them, with the values :func:`mrphy_amd.sims.relax_constants` gives) and its backward
     runs the CONSTS builds; every other case is composed, or split as above.  A ``γ_beff`` that requires grad where
     there is a ``Δf`` counts with the spin-side maps: its gradient is a fold of theirs."""
-    from . import beffective, sims
     _host.require_device_tensor(Mi, 'Mi')
-    Δf, b1Map, T1, T2 = kw['Δf'], kw['b1Map'], kw['T1'], kw['T2']
-    assert (T1 is None) == (T2 is None)
+    assert (kw['T1'] is None) == (kw['T2'] is None)
     lib = _lib.require_library()
-    grad_on = torch.is_grad_enabled()
-    rq = lambda x: grad_on and isinstance(x, Tensor) and x.requires_grad  # noqa: E731
-    γb_grad = rq(kw['γ_beff']) and Δf is not None       # (without Δf the field does not depend on γ_beff)
-    maps_grad = any(rq(x) for x in (loc, Δf, b1Map)) or γb_grad
-    rx_grad = signal and rq(rx)
-    pulse_grad = any(rq(x) for x in (Mi, rf, gr))
-    consts_grad = any(rq(x) for x in (kw['consts'].values() if kw['consts'] is not None
-                                      else (T1, T2, kw['γ'], kw['dt'])))
-    p = beffective._PulseOnSpins(rf.detach(), gr.detach(), loc.detach(),
-                                 None if Δf is None else Δf.detach(),
-                                 None if b1Map is None else b1Map.detach(), kw['γ_beff'].detach())
+    f = _pulse_facts(rf, gr, loc, kw, Mi)
+    p, Δf, b1Map = f.p, kw['Δf'], kw['b1Map']
     decision = _decide_route(
-        nT=p.nT, seg=int(lib.mrphy_blochsim_rfgr_ck_every()), nC=p.nC,
-        one_coil=p.nC == 1 and (rf.ndim == 3 or b1Map is not None or rf.shape[-1] == 1), has_b1=p.b1 is not None,
+        nT=p.nT, seg=int(lib.mrphy_blochsim_rfgr_ck_every()), nC=p.nC, one_coil=f.one_coil, has_b1=p.b1 is not None,
         f64=p.dtype == torch.float64, signal=signal, ptx_max=int(lib.mrphy_blochsim_rfgr_mc_max_coils()),
-        pulse_grad=pulse_grad, maps_grad=maps_grad, consts_grad=consts_grad, rx_grad=rx_grad, γb_grad=γb_grad)
+        pulse_grad=f.pulse_grad, maps_grad=f.maps_grad, consts_grad=f.consts_grad,
+        rx_grad=signal and _requires_grad(rx), γb_grad=f.γb_grad)
     if decision[0] != 'fused':
         return decision
     _, want, maps_fused, _ = decision
@@ -568,16 +582,7 @@ def _route(Mi, rf, gr, loc, every, kw, signal=False, rx=None):
     device, dtype = Mi.device, Mi.dtype
     assert p.device == device and p.dtype == dtype, "Mi and loc must share device and dtype"
     assert tuple(Mi.shape[:-1]) == (p.N,) + p.Nd
-    if kw['consts'] is not None:
-        γ2πdt, E1, E2, E1_1 = (kw['consts'].get(k) for k in _CONSTS)
-    elif consts_grad:
-        # differentiable, as slowsims.blochsim forms them: relax_constants' expressions on the same padded operands on
-        # the same device, so the values -- and Mo -- are the bits of the call that does not differentiate them
-        cdev = _host.const_device(device)
-        pad = lambda x: None if x is None else _host.pad_trailing(x.to(cdev), 1 + len(p.Nd) + 2)  # noqa: E731
-        γ2πdt, E1, E2, E1_1 = sims._gamma_dt_constants(pad(T1), pad(T2), pad(kw['γ']), pad(kw['dt']))
-    else:
-        γ2πdt, E1, E2, E1_1 = sims.relax_constants(T1, T2, kw['γ'], kw['dt'], 1 + len(p.Nd) + 2, device)
+    γ2πdt, E1, E2, E1_1 = _step_constants(kw, f.consts_grad, 1 + len(p.Nd) + 2, device)
     if signal:
         apply = lambda r: SignalRfGrHIP.apply(Mi, rf, gr, p, r, γ2πdt, E1, E2, E1_1, want, every)  # noqa: E731
         if rx is None:
@@ -591,10 +596,10 @@ def _route(Mi, rf, gr, loc, every, kw, signal=False, rx=None):
             sig, Mo = apply(r[..., 0].contiguous())
             return 'fused', (sig.unsqueeze(-1) if rx.ndim == Mi.ndim + 1 else sig, Mo)
         # (the capacity depends on the data type alone, not on the constants' precision)
-        cap = int(lib.mrphy_signal_rfgr_max_rx(_lib.F64 if dtype == torch.float64 else _lib.F32))
+        cap = int(lib.mrphy_signal_rfgr_max_rx(_code(dtype)))
         outs = [apply(r[..., c:c + cap].contiguous()) for c in range(0, nrx, cap)]
         return 'fused', (outs[0][0] if len(outs) == 1 else torch.cat([o[0] for o in outs], dim=-1), outs[0][1])
-    maps = (loc, Δf, b1Map, kw['γ_beff'] if γb_grad else None) if maps_fused else ()
+    maps = (loc, Δf, b1Map, kw['γ_beff'] if f.γb_grad else None) if maps_fused else ()
     return 'fused', BlochSimRfGrHIP.apply(Mi, rf, gr, p, γ2πdt, E1, E2, E1_1, want, every, *maps)
 
 
@@ -837,44 +842,125 @@ def ab_rfgr(
     ``b1Map``, ``γ_beff`` or ``T1``, ``T2``, ``γ``, ``dt`` under parallel transmit; any gradient of a pulse with fewer than 16
     steps.
     """
-    from . import beffective, sims
     _host.require_device_tensor(loc, 'loc')
     assert (T1 is None) == (T2 is None)
     kw = dict(Δf=Δf, b1Map=b1Map, γ_beff=γ_beff, T1=T1, T2=T2, γ=γ, dt=dt, consts=consts)
     lib = _lib.require_library()
-    grad_on = torch.is_grad_enabled()
-    rq = lambda x: grad_on and isinstance(x, Tensor) and x.requires_grad  # noqa: E731
-    γb_grad = rq(γ_beff) and Δf is not None         # (without Δf the field does not depend on γ_beff)
-    maps_grad = any(rq(x) for x in (loc, Δf, b1Map)) or γb_grad
-    consts_grad = any(rq(x) for x in (consts.values() if consts is not None else (T1, T2, γ, dt)))
-    p = beffective._PulseOnSpins(rf.detach(), gr.detach(), loc.detach(), None if Δf is None else Δf.detach(),
-                                 None if b1Map is None else b1Map.detach(), γ_beff.detach())
+    f = _pulse_facts(rf, gr, loc, kw)
+    p = f.p
     route, out = _decide_ab_route(
-        nT=p.nT, seg=int(lib.mrphy_blochsim_rfgr_ck_every()),
-        one_coil=p.nC == 1 and (rf.ndim == 3 or b1Map is not None or rf.shape[-1] == 1),
-        pulse_grad=any(rq(x) for x in (rf, gr)), maps_grad=maps_grad, consts_grad=consts_grad,
-        spin_fused=_ab_spin_fused(p.dtype, consts_grad),
-        ptx_fused=b1Map is not None and 2 <= p.nC <= int(lib.mrphy_ab_rfgr_mc_max_coils(
-            _lib.F64 if p.dtype == torch.float64 else _lib.F32)))
+        nT=p.nT, seg=int(lib.mrphy_blochsim_rfgr_ck_every()), one_coil=f.one_coil, pulse_grad=f.pulse_grad,
+        maps_grad=f.maps_grad, consts_grad=f.consts_grad, spin_fused=_ab_spin_fused(p.dtype, f.consts_grad),
+        ptx_fused=b1Map is not None and 2 <= p.nC <= int(lib.mrphy_ab_rfgr_mc_max_coils(_code(p.dtype))))
     if route == 'split':
         # whole segments fused, the tail of <= 15 steps composed; the step map of the tail acts on the head's
         A1, B1 = ab_rfgr(rf[:, :, :out], gr[:, :, :out], loc, **kw)
         A2, B2 = ab_rfgr(rf[:, :, out:], gr[:, :, out:], loc, **kw)
         return _JoinAb.apply(A1, B1, A2, B2)
-    device, ndim = p.device, 1 + len(p.Nd) + 2
-    if consts is not None:
-        cs = tuple(consts.get(k) for k in _CONSTS)
-    elif consts_grad:
-        # differentiable, as slowsims.blochsim forms them (see _route)
-        cdev = _host.const_device(device)
-        pad = lambda x: None if x is None else _host.pad_trailing(x.to(cdev), ndim)  # noqa: E731
-        cs = sims._gamma_dt_constants(pad(T1), pad(T2), pad(γ), pad(dt))
-    else:
-        cs = sims.relax_constants(T1, T2, γ, dt, ndim, device)
+    cs = _step_constants(kw, f.consts_grad, 1 + len(p.Nd) + 2, p.device)
     if route == 'composed':
-        return _ab_composed(rf, gr, loc, kw, cs, consts_grad)
-    maps = (loc, Δf, b1Map, γ_beff if γb_grad else None) if maps_grad else ()
+        return _ab_composed(rf, gr, loc, kw, cs, f.consts_grad)
+    maps = (loc, Δf, b1Map, γ_beff if f.γb_grad else None) if f.maps_grad else ()
     return AbRfGrHIP.apply(rf, gr, p, *cs, out, *maps)
+
+
+def _rest_operands(A, rest, T1, T2, Δf):
+    r"""``(N, Nd, nM, code, keep, args)``: the arguments ``rest .. df_sm`` of the entry points that take Hargreaves'
+    ``A`` `(N, *Nd, 3, 3)` and a rest period, and the tensors that keep their pointers alive."""
+    device, dtype = A.device, A.dtype
+    N, Nd = A.shape[0], tuple(A.shape[1:-2])
+    nul = _host.NULL_BC
+    d = None
+    if rest is not None:
+        d = rest.detach().to(device=device, dtype=dtype).reshape(-1).contiguous()
+        assert d.numel() in (1, N), "rest must be () or (N ⊻ 1,)"
+    mk = lambda c: None if c is None else _host.Bcast(c.detach(), N, Nd, dtype, device)  # noqa: E731
+    t1, t2, df = mk(T1), mk(T2), mk(Δf)
+    args = (None if d is None else d.data_ptr(), 1 if (d is not None and d.numel() == N and N > 1) else 0,
+            *(t1.args if t1 else nul), *(t2.args if t2 else nul), *(df.args if df else nul))
+    return N, Nd, prod(Nd), _code(dtype), (d, t1, t2, df), args
+
+
+def _state_operands(a, Mi, phase):
+    r"""``(mi, cs)`` of the train family: ``Mi`` `(N ⊻ 1, nM ⊻ 1, 3)` in the data type and the fp64 table
+    ``(cos φ, sin φ)`` `(N ⊻ 1, K, 2)`, formed here once per call with torch ops; ``None`` for an absent operand."""
+    device, dtype = a.device, a.dtype
+    Nd = tuple(a.shape[1:-2])
+    mi = cs = None
+    if Mi is not None:
+        mi = Mi.detach().to(device=device, dtype=dtype)
+        if all(d == 1 for d in mi.shape[1:-1]):
+            mi = mi.reshape(mi.shape[0], 1, 3).contiguous()
+        else:
+            mi = mi.expand((mi.shape[0],) + Nd + (3,)).reshape(mi.shape[0], prod(Nd), 3).contiguous()
+    if phase is not None:
+        φ = phase.detach().to(device=device, dtype=torch.float64)
+        cs = torch.stack((torch.cos(φ), torch.sin(φ)), dim=-1).contiguous()
+    return mi, cs
+
+
+def _state_args(mi, cs, N):
+    r"""The arguments ``Mi .. cs_sn`` of the train family's entry points: pointers and element strides, 0 where it
+    broadcasts."""
+    over_n = lambda x: x.stride(0) if (x.shape[0] == N and N > 1) else 0  # noqa: E731
+    return ((None, 0, 0) if mi is None else (mi.data_ptr(), over_n(mi), 3 if mi.shape[1] > 1 else 0)) + \
+           ((None, 0) if cs is None else (cs.data_ptr(), over_n(cs)))
+
+
+def _train_spins(A, B, bank=False):
+    r"""``(N, Nd)`` of ``A, B`` as the train family takes them, ``bank``: with the bank axis in front; their shapes
+    checked against each other."""
+    lead = 'P, N' if bank else 'N'
+    assert (not bank or A.ndim >= 4) and A.shape[-2:] == (3, 3) and tuple(B.shape) == tuple(A.shape[:-1]), \
+        f"A {tuple(A.shape)} must be ({lead}, *Nd, 3, 3) and B {tuple(B.shape)} ({lead}, *Nd, 3)"
+    return A.shape[int(bank)], tuple(A.shape[1 + int(bank):-2])
+
+
+def _check_train_operands(A, B, N, Nd, Mi, rest, T1, T2, Δf):
+    r"""What :func:`ab_train`, :func:`train_signal` and :func:`ab_sequence` require of their operands alike, once the
+    number of repetitions is known."""
+    _host.require_device_tensor(A, 'A')
+    _host.require_device_tensor(B, 'B')
+    assert A.dtype == B.dtype and A.device == B.device, "A and B must share dtype and device"
+    assert (T1 is None) == (T2 is None)  # both or neither
+    assert rest is not None or (T1 is None and Δf is None), "T1, T2, Δf describe the rest period: give `rest`"
+    if Mi is not None:
+        assert Mi.ndim == 2 + len(Nd) and Mi.shape[-1] == 3 and Mi.shape[0] in (1, N) and \
+            all(m in (1, d) for m, d in zip(Mi.shape[1:-1], Nd)), \
+            f"Mi {tuple(Mi.shape)} must be (N ⊻ 1, *Nd ⊻ 1, 3) for spins {(N,) + Nd}"
+
+
+def _new_grads(empty, dtype, device, **shapes):
+    r"""``{name: tensor}`` for the raw gradients of an ``A, B``-level adjoint: ``shapes[name]`` is the shape, or a false
+    value for a gradient that is not wanted (``None``).  An ``empty`` problem launches nothing: its gradients are the
+    zeros of a sum without terms."""
+    new = torch.zeros if empty else torch.empty
+    return {k: new(tuple(sh), dtype=dtype, device=device) if sh else None for k, sh in shapes.items()}
+
+
+def _fold_rest_consts(gC, consts, need_c, N, Nd):
+    r"""The gradients of the rest's operands ``consts`` (``rest, T1, T2, Δf``, or the last three) from the per-spin
+    ``gC`` `(N, *Nd, len(consts))`: each summed over the axes its operand broadcasts along, ``None`` where ``need_c`` does
+    not ask."""
+    from . import sims
+    return tuple(sims._reduce_to_const(gC[..., i], c, N, Nd).to(c.device) if want else None
+                 for i, (c, want) in enumerate(zip(consts, need_c)))
+
+
+def _fold_to_operand(g, x, acc=None):
+    r"""``g`` summed over the axes ``x`` broadcasts along -- accumulated in ``acc``, by default in ``g``'s own dtype --, in
+    ``x``'s shape and dtype and on its device."""
+    if tuple(g.shape) != tuple(x.shape):
+        g = (g if acc is None else g.to(acc)).sum_to_size(tuple(x.shape))
+    return g.to(device=x.device, dtype=x.dtype)
+
+
+def _fold_per_repetition(g, x):
+    r"""The gradient of ``phase`` or ``rest`` from the kernel's per-spin ``g`` `(K, N, nM)`: summed in fp64 over the
+    spins, then over what ``x`` shares -- ``x`` `(N ⊻ 1, K)`, or a duration `()` ⊻ `(N ⊻ 1,)` that the repetitions share too."""
+    g = torch.sum(g, dim=-1, dtype=torch.float64).T      # (N, K)
+    g = g.sum_to_size(tuple(x.shape)) if x.ndim == 2 else g.sum(1).sum_to_size(tuple(x.shape) or (1,))
+    return g.reshape(x.shape).to(device=x.device, dtype=x.dtype)
 
 
 class AbSteadyStateHIP(Function):
@@ -882,28 +968,11 @@ class AbSteadyStateHIP(Function):
     (``mrphy_ab_steadystate_bwd``) recomputes ``Mss`` from the inputs: nothing else is saved."""
 
     @staticmethod
-    def _operands(A, rest, T1, T2, Δf):
-        r"""``(N, Nd, nM, code, keep, args)``: the arguments ``rest .. df_sm`` of the two entry points and the tensors
-        that keep their pointers alive."""
-        device, dtype = A.device, A.dtype
-        N, Nd = A.shape[0], tuple(A.shape[1:-2])
-        nul = _host.NULL_BC
-        d = None
-        if rest is not None:
-            d = rest.detach().to(device=device, dtype=dtype).reshape(-1).contiguous()
-            assert d.numel() in (1, N), "rest must be () or (N ⊻ 1,)"
-        mk = lambda c: None if c is None else _host.Bcast(c.detach(), N, Nd, dtype, device)  # noqa: E731
-        t1, t2, df = mk(T1), mk(T2), mk(Δf)
-        args = (None if d is None else d.data_ptr(), 1 if (d is not None and d.numel() == N and N > 1) else 0,
-                *(t1.args if t1 else nul), *(t2.args if t2 else nul), *(df.args if df else nul))
-        return N, Nd, prod(Nd), _lib.F64 if dtype == torch.float64 else _lib.F32, (d, t1, t2, df), args
-
-    @staticmethod
     def forward(ctx, A, B, rest, T1, T2, Δf):
         lib = _lib.require_library()
         device = A.device
         a, b = A.detach().contiguous(), B.detach().contiguous()
-        N, Nd, nM, code, keep, args = AbSteadyStateHIP._operands(a, rest, T1, T2, Δf)
+        N, Nd, nM, code, keep, args = _rest_operands(a, rest, T1, T2, Δf)
         Mss = torch.empty_like(b)
         with torch.cuda.device(device):
             rc = lib.mrphy_ab_steadystate_fwd(code, a.data_ptr(), b.data_ptr(), *args, Mss.data_ptr(), N, nM,
@@ -917,7 +986,6 @@ class AbSteadyStateHIP(Function):
 
     @staticmethod
     def backward(ctx, grad_Mss):
-        from . import sims
         need = ctx.needs_input_grad
         consts = ctx.consts
         need_c = [w and c is not None for w, c in zip(need[2:6], consts)]
@@ -926,20 +994,16 @@ class AbSteadyStateHIP(Function):
         lib = _lib.require_library()
         a, b = ctx.saved_tensors
         device, dtype = a.device, a.dtype
-        N, Nd, nM, code, keep, args = AbSteadyStateHIP._operands(a, *consts)
+        N, Nd, nM, code, keep, args = _rest_operands(a, *consts)
         g = grad_Mss.detach().to(dtype).contiguous()
-        gA = torch.empty_like(a) if need[0] else None
-        gB = torch.empty_like(b) if need[1] else None
-        gC = torch.empty((N,) + Nd + (4,), dtype=dtype, device=device) if any(need_c) else None
-        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        o = _new_grads(False, dtype, device, gA=need[0] and a.shape, gB=need[1] and b.shape,
+                       gC=any(need_c) and (N,) + Nd + (4,))
         with torch.cuda.device(device):
-            rc = lib.mrphy_ab_steadystate_bwd(code, a.data_ptr(), b.data_ptr(), g.data_ptr(), *args, ptr(gA), ptr(gB),
-                                              ptr(gC), N, nM, _host.current_stream(device))
+            rc = lib.mrphy_ab_steadystate_bwd(code, a.data_ptr(), b.data_ptr(), g.data_ptr(), *args, _ptr(o['gA']),
+                                              _ptr(o['gB']), _ptr(o['gC']), N, nM, _host.current_stream(device))
         _lib.check(rc, 'mrphy_ab_steadystate_bwd')
         del keep
-        gcs = tuple(sims._reduce_to_const(gC[..., i], c, N, Nd).to(c.device) if want else None
-                    for i, (c, want) in enumerate(zip(consts, need_c)))
-        return (gA, gB) + gcs
+        return (o['gA'], o['gB']) + _fold_rest_consts(o['gC'], consts, need_c, N, Nd)
 
 
 @_host.half_via_float
@@ -1027,38 +1091,13 @@ class AbTrainHIP(Function):
     the output is all that is saved."""
 
     @staticmethod
-    def _state_operands(a, Mi, phase):
-        r"""``(mi, cs)``: ``Mi`` `(N ⊻ 1, nM ⊻ 1, 3)` in the data type and the fp64 table ``(cos φ, sin φ)``
-        `(N ⊻ 1, K, 2)`, formed here once per call with torch ops; ``None`` for an absent operand."""
-        device, dtype = a.device, a.dtype
-        Nd = tuple(a.shape[1:-2])
-        mi = cs = None
-        if Mi is not None:
-            mi = Mi.detach().to(device=device, dtype=dtype)
-            if all(d == 1 for d in mi.shape[1:-1]):
-                mi = mi.reshape(mi.shape[0], 1, 3).contiguous()
-            else:
-                mi = mi.expand((mi.shape[0],) + Nd + (3,)).reshape(mi.shape[0], prod(Nd), 3).contiguous()
-        if phase is not None:
-            φ = phase.detach().to(device=device, dtype=torch.float64)
-            cs = torch.stack((torch.cos(φ), torch.sin(φ)), dim=-1).contiguous()
-        return mi, cs
-
-    @staticmethod
-    def _state_args(mi, cs, N):
-        r"""The arguments ``Mi .. cs_sn`` of the two entry points: pointers and element strides, 0 where it broadcasts."""
-        over_n = lambda x: x.stride(0) if (x.shape[0] == N and N > 1) else 0  # noqa: E731
-        return ((None, 0, 0) if mi is None else (mi.data_ptr(), over_n(mi), 3 if mi.shape[1] > 1 else 0)) + \
-               ((None, 0) if cs is None else (cs.data_ptr(), over_n(cs)))
-
-    @staticmethod
     def forward(ctx, A, B, Mi, phase, rest, T1, T2, Δf, K):
         lib = _lib.require_library()
         device = A.device
         a, b = A.detach().contiguous(), B.detach().contiguous()
-        N, Nd, nM, code, keep, args = AbSteadyStateHIP._operands(a, rest, T1, T2, Δf)
-        mi, cs = AbTrainHIP._state_operands(a, Mi, phase)
-        sargs = AbTrainHIP._state_args(mi, cs, N)
+        N, Nd, nM, code, keep, args = _rest_operands(a, rest, T1, T2, Δf)
+        mi, cs = _state_operands(a, Mi, phase)
+        sargs = _state_args(mi, cs, N)
         Mt = torch.empty((K,) + tuple(b.shape), dtype=b.dtype, device=device)
         with torch.cuda.device(device):
             rc = lib.mrphy_ab_train_fwd(code, a.data_ptr(), b.data_ptr(), *args, *sargs, Mt.data_ptr(), N, nM, K,
@@ -1073,7 +1112,6 @@ class AbTrainHIP(Function):
 
     @staticmethod
     def backward(ctx, grad_Mt):
-        from . import sims
         need = ctx.needs_input_grad
         consts = ctx.consts
         Mi, phase, K = ctx.state
@@ -1084,32 +1122,21 @@ class AbTrainHIP(Function):
         lib = _lib.require_library()
         a, b, Mt, mi, cs = ctx.saved_tensors
         device, dtype = a.device, a.dtype
-        N, Nd, nM, code, keep, args = AbSteadyStateHIP._operands(a, *consts)
-        sargs = AbTrainHIP._state_args(mi, cs, N)
+        N, Nd, nM, code, keep, args = _rest_operands(a, *consts)
+        sargs = _state_args(mi, cs, N)
         g = grad_Mt.detach().to(dtype).contiguous()
-        # an empty problem launches nothing: its gradients are the zeros of a sum without terms
-        new = torch.zeros if N * nM * K == 0 else torch.empty
-        gA = new(a.shape, dtype=dtype, device=device) if need[0] else None
-        gB = new(b.shape, dtype=dtype, device=device) if need[1] else None
-        gC = new((N,) + Nd + (4,), dtype=dtype, device=device) if any(need_c) else None
-        gMi = new(b.shape, dtype=dtype, device=device) if need_mi else None
-        gφ = new((K, N, nM), dtype=dtype, device=device) if need_φ else None
-        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        o = _new_grads(N * nM * K == 0, dtype, device, gA=need[0] and a.shape, gB=need[1] and b.shape,
+                       gC=any(need_c) and (N,) + Nd + (4,), gMi=need_mi and b.shape, gφ=need_φ and (K, N, nM))
         with torch.cuda.device(device):
             rc = lib.mrphy_ab_train_bwd(code, a.data_ptr(), b.data_ptr(), g.data_ptr(), *args, *sargs, Mt.data_ptr(),
-                                        ptr(gA), ptr(gB), ptr(gC), ptr(gMi), ptr(gφ), N, nM, K,
+                                        *(_ptr(o[k]) for k in ('gA', 'gB', 'gC', 'gMi', 'gφ')), N, nM, K,
                                         _host.current_stream(device))
         _lib.check(rc, 'mrphy_ab_train_bwd')
         del keep
-        gcs = tuple(sims._reduce_to_const(gC[..., i], c, N, Nd).to(c.device) if want else None
-                    for i, (c, want) in enumerate(zip(consts, need_c)))
-        if need_mi:
-            gMi = gMi.sum_to_size(tuple(Mi.shape)).to(device=Mi.device, dtype=Mi.dtype)
-        if need_φ:
-            # per spin from the kernel; the sum over the spins that share a phase, accumulated in fp64
-            gφ = torch.sum(gφ, dim=-1, dtype=torch.float64).T.sum_to_size(tuple(phase.shape))
-            gφ = gφ.to(device=phase.device, dtype=phase.dtype)
-        return (gA, gB, gMi, gφ) + gcs + (None,)
+        # grad_Mi is summed over those who share Mi in the data type; grad_phase over the spins in fp64
+        return (o['gA'], o['gB'], _fold_to_operand(o['gMi'], Mi) if need_mi else None,
+                _fold_per_repetition(o['gφ'], phase) if need_φ else None) + \
+            _fold_rest_consts(o['gC'], consts, need_c, N, Nd) + (None,)
 
 
 def _train_length(n, phase, N):
@@ -1172,19 +1199,9 @@ def ab_train(
     ``Mt``).  A flip angle or ``rest`` per repetition (the pulse is then not one ``A, B``) is :func:`ab_sequence`; the
     sum over the spins inside the kernel is :func:`train_signal`.
     """
-    assert A.shape[-2:] == (3, 3) and tuple(B.shape) == tuple(A.shape[:-1]), \
-        f"A {tuple(A.shape)} must be (N, *Nd, 3, 3) and B {tuple(B.shape)} (N, *Nd, 3)"
-    N, Nd = A.shape[0], tuple(A.shape[1:-2])
+    N, Nd = _train_spins(A, B)
     K = _train_length(n, phase, N)
-    _host.require_device_tensor(A, 'A')
-    _host.require_device_tensor(B, 'B')
-    assert A.dtype == B.dtype and A.device == B.device, "A and B must share dtype and device"
-    assert (T1 is None) == (T2 is None)  # both or neither
-    assert rest is not None or (T1 is None and Δf is None), "T1, T2, Δf describe the rest period: give `rest`"
-    if Mi is not None:
-        assert Mi.ndim == 2 + len(Nd) and Mi.shape[-1] == 3 and Mi.shape[0] in (1, N) and \
-            all(m in (1, d) for m, d in zip(Mi.shape[1:-1], Nd)), \
-            f"Mi {tuple(Mi.shape)} must be (N ⊻ 1, *Nd ⊻ 1, 3) for spins {(N,) + Nd}"
+    _check_train_operands(A, B, N, Nd, Mi, rest, T1, T2, Δf)
     return AbTrainHIP.apply(A, B, Mi, phase, rest, T1, T2, Δf, K).movedim(0, -2)
 
 
@@ -1234,10 +1251,10 @@ class AbSequenceHIP(Function):
     @staticmethod
     def _args(a, rs, T1, T2, Δf, mi, cs, sched_dev):
         r"""``(N, Nd, nM, code, keep, head, tail)``: ``P, pulse`` and ``rs .. cs_sn`` of the two entry points."""
-        N, Nd, nM, code, keep, args = AbSteadyStateHIP._operands(a[0], None, T1, T2, Δf)
+        N, Nd, nM, code, keep, args = _rest_operands(a[0], None, T1, T2, Δf)
         head = (a.shape[0], None if sched_dev is None else sched_dev.data_ptr())
         tail = (None if rs is None else rs.data_ptr(), rs.stride(0) if (rs is not None and rs.shape[0] == N and N > 1) else 0,
-                *args[2:], *AbTrainHIP._state_args(mi, cs, N))
+                *args[2:], *_state_args(mi, cs, N))
         return N, Nd, nM, code, keep, head, tail
 
     @staticmethod
@@ -1247,7 +1264,7 @@ class AbSequenceHIP(Function):
         a, b = A.detach().contiguous(), B.detach().contiguous()
         sched_dev = None if sched is None else sched.to(device)
         rs = AbSequenceHIP._rest_table(a, rest, a.shape[1], K)
-        mi, cs = AbTrainHIP._state_operands(a[0], Mi, phase)
+        mi, cs = _state_operands(a[0], Mi, phase)
         N, Nd, nM, code, keep, head, tail = AbSequenceHIP._args(a, rs, T1, T2, Δf, mi, cs, sched_dev)
         Mt = torch.empty((K,) + tuple(b.shape[1:]), dtype=b.dtype, device=device)
         with torch.cuda.device(device):
@@ -1263,7 +1280,6 @@ class AbSequenceHIP(Function):
 
     @staticmethod
     def backward(ctx, grad_Mt):
-        from . import sims
         need = ctx.needs_input_grad
         consts = ctx.consts
         Mi, phase, rest, K = ctx.state
@@ -1276,36 +1292,22 @@ class AbSequenceHIP(Function):
         device, dtype = a.device, a.dtype
         N, Nd, nM, code, keep, head, tail = AbSequenceHIP._args(a, rs, *consts, mi, cs, sched_dev)
         g = grad_Mt.detach().to(dtype).contiguous()
-        # an empty problem launches nothing: its gradients are the zeros of a sum without terms
-        new = torch.zeros if N * nM * K == 0 else torch.empty
-        gA = new(a.shape, dtype=dtype, device=device) if need[0] else None
-        gB = new(b.shape, dtype=dtype, device=device) if need[1] else None
-        gC = new((N,) + Nd + (3,), dtype=dtype, device=device) if any(need_c) else None
-        gr_ = new((K, N, nM), dtype=dtype, device=device) if need_r else None
-        gMi = new(b.shape[1:], dtype=dtype, device=device) if need_mi else None
-        gφ = new((K, N, nM), dtype=dtype, device=device) if need_φ else None
+        o = _new_grads(N * nM * K == 0, dtype, device, gA=need[0] and a.shape, gB=need[1] and b.shape,
+                       gC=any(need_c) and (N,) + Nd + (3,), gr=need_r and (K, N, nM), gMi=need_mi and b.shape[1:],
+                       gφ=need_φ and (K, N, nM))
         nbytes = int(lib.mrphy_ab_sequence_bwd_workspace(code, a.shape[0], N, nM)) if (need[0] or need[1]) else 0
         work = torch.empty(nbytes // 8, dtype=torch.float64, device=device) if nbytes else None
-        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
         with torch.cuda.device(device):
             rc = lib.mrphy_ab_sequence_bwd(code, a.data_ptr(), b.data_ptr(), *head, g.data_ptr(), *tail, Mt.data_ptr(),
-                                           ptr(gA), ptr(gB), ptr(gC), ptr(gr_), ptr(gMi), ptr(gφ), ptr(work), nbytes,
+                                           *(_ptr(o[k]) for k in ('gA', 'gB', 'gC', 'gr', 'gMi', 'gφ')), _ptr(work), nbytes,
                                            N, nM, K, _host.current_stream(device))
         _lib.check(rc, 'mrphy_ab_sequence_bwd')
         del keep, work
-        gcs = tuple(sims._reduce_to_const(gC[..., i], c, N, Nd).to(c.device) if want else None
-                    for i, (c, want) in enumerate(zip(consts, need_c)))
-        if need_mi:
-            gMi = gMi.sum_to_size(tuple(Mi.shape)).to(device=Mi.device, dtype=Mi.dtype)
-        # per spin from the kernel; the sums over the spins that share a phase or a duration, accumulated in fp64
-        over_spins = lambda x: torch.sum(x, dim=-1, dtype=torch.float64).T  # noqa: E731  (N, K)
-        if need_φ:
-            gφ = over_spins(gφ).sum_to_size(tuple(phase.shape)).to(device=phase.device, dtype=phase.dtype)
-        if need_r:
-            gr_ = over_spins(gr_)
-            gr_ = gr_.sum_to_size(tuple(rest.shape)) if rest.ndim == 2 else gr_.sum(1).sum_to_size(tuple(rest.shape) or (1,))
-            gr_ = gr_.reshape(rest.shape).to(device=rest.device, dtype=rest.dtype)
-        return (gA, gB, gMi, gφ, gr_) + gcs + (None, None)
+        # grad_Mi is summed over those who share Mi in the data type; grad_phase and grad_rest over the spins in fp64
+        return (o['gA'], o['gB'], _fold_to_operand(o['gMi'], Mi) if need_mi else None,
+                _fold_per_repetition(o['gφ'], phase) if need_φ else None,
+                _fold_per_repetition(o['gr'], rest) if need_r else None) + \
+            _fold_rest_consts(o['gC'], consts, need_c, N, Nd) + (None, None)
 
 
 def _sequence_schedule(pulse, P):
@@ -1403,23 +1405,14 @@ def ab_sequence(
     schedule); a steady state of a multi-pulse period; a schedule per batch entry; thinning the records; reading out at
     an echo time after the pulse (``sims.freeprec`` on the records, an elementwise operation); a CPU path.
     """
-    assert A.ndim >= 4 and A.shape[-2:] == (3, 3) and tuple(B.shape) == tuple(A.shape[:-1]), \
-        f"A {tuple(A.shape)} must be (P, N, *Nd, 3, 3) and B {tuple(B.shape)} (P, N, *Nd, 3)"
-    P, N, Nd = A.shape[0], A.shape[1], tuple(A.shape[2:-2])
+    N, Nd = _train_spins(A, B, bank=True)
+    P = A.shape[0]
     sched = _sequence_schedule(pulse, P)
     K = _sequence_length(n, sched, phase, N)
     if rest is not None and (rest.ndim > 2 or (rest.ndim == 1 and rest.shape[0] not in (1, N)) or
                              (rest.ndim == 2 and (rest.shape[0] not in (1, N) or rest.shape[1] != K))):
         raise ValueError(f"mrphy_amd: `rest` {tuple(rest.shape)} must be (), (N ⊻ 1,) or (N ⊻ 1, K) with N = {N}, K = {K}")
-    _host.require_device_tensor(A, 'A')
-    _host.require_device_tensor(B, 'B')
-    assert A.dtype == B.dtype and A.device == B.device, "A and B must share dtype and device"
-    assert (T1 is None) == (T2 is None)  # both or neither
-    assert rest is not None or (T1 is None and Δf is None), "T1, T2, Δf describe the rest period: give `rest`"
-    if Mi is not None:
-        assert Mi.ndim == 2 + len(Nd) and Mi.shape[-1] == 3 and Mi.shape[0] in (1, N) and \
-            all(m in (1, d) for m, d in zip(Mi.shape[1:-1], Nd)), \
-            f"Mi {tuple(Mi.shape)} must be (N ⊻ 1, *Nd ⊻ 1, 3) for spins {(N,) + Nd}"
+    _check_train_operands(A, B, N, Nd, Mi, rest, T1, T2, Δf)
     return AbSequenceHIP.apply(A, B, Mi, phase, rest, T1, T2, Δf, K, sched).movedim(0, -2)
 
 
@@ -1484,9 +1477,9 @@ class TrainSignalHIP(Function):
         lib = _lib.require_library()
         device, dtype = A.device, A.dtype
         a, b = A.detach().contiguous(), B.detach().contiguous()
-        N, Nd, nM, code, keep, args = AbSteadyStateHIP._operands(a, rest, T1, T2, Δf)
-        mi, cs = AbTrainHIP._state_operands(a, Mi, phase)
-        sargs = AbTrainHIP._state_args(mi, cs, N)
+        N, Nd, nM, code, keep, args = _rest_operands(a, rest, T1, T2, Δf)
+        mi, cs = _state_operands(a, Mi, phase)
+        sargs = _state_args(mi, cs, N)
         r, nRx = TrainSignalHIP._rx_operand(a, rx)
         coils = () if rx is None or rx.ndim == b.ndim else (nRx,)
         empty = N * nM * K == 0
@@ -1499,10 +1492,9 @@ class TrainSignalHIP(Function):
         ck = torch.empty((-(-K // S), N * nM, 3), dtype=torch.float64, device=device) if want_ckpt else None
         nbytes = int(lib.mrphy_train_signal_workspace(code, N, nM, K, 2 * nRx))
         work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
-        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
         with torch.cuda.device(device):
-            rc = lib.mrphy_train_signal_fwd(code, a.data_ptr(), b.data_ptr(), *args, *sargs, ptr(r), nRx,
-                                            sig.data_ptr(), Mlast.data_ptr(), ptr(ck), work.data_ptr(), work.numel(),
+            rc = lib.mrphy_train_signal_fwd(code, a.data_ptr(), b.data_ptr(), *args, *sargs, _ptr(r), nRx,
+                                            sig.data_ptr(), Mlast.data_ptr(), _ptr(ck), work.data_ptr(), work.numel(),
                                             N, nM, K, _host.current_stream(device))
         _lib.check(rc, 'mrphy_train_signal_fwd')
         del keep
@@ -1515,7 +1507,6 @@ class TrainSignalHIP(Function):
 
     @staticmethod
     def backward(ctx, grad_sig, grad_Mlast):
-        from . import sims
         need = ctx.needs_input_grad
         none = (None,) * len(TrainSignalHIP.ARGS)
         if not any(need) or (grad_sig is None and grad_Mlast is None):
@@ -1529,50 +1520,40 @@ class TrainSignalHIP(Function):
         lib = _lib.require_library()
         a, b, mi, cs, r, ck = ctx.saved_tensors
         device, dtype = a.device, a.dtype
-        N, Nd, nM, code, keep, args = AbSteadyStateHIP._operands(a, *consts)
-        sargs = AbTrainHIP._state_args(mi, cs, N)
+        N, Nd, nM, code, keep, args = _rest_operands(a, *consts)
+        sargs = _state_args(mi, cs, N)
         # the cotangent of the signal as the wave-uniform table (N, K, nRx, 2) in fp64
         gs = None if grad_sig is None else \
             grad_sig.detach().to(torch.float64).reshape(N, 2, K, nRx).permute(0, 2, 3, 1).contiguous()
         gl = None if grad_Mlast is None else grad_Mlast.detach().to(dtype).contiguous()
-        # an empty problem launches nothing: its gradients are the zeros of a sum without terms
-        new = torch.zeros if N * nM * K == 0 else torch.empty
-        gA = new(a.shape, dtype=dtype, device=device) if need[0] else None
-        gB = new(b.shape, dtype=dtype, device=device) if need[1] else None
+        empty = N * nM * K == 0
+        o = _new_grads(empty, dtype, device, gA=need[0] and a.shape, gB=need[1] and b.shape, gMi=need_mi and b.shape,
+                       gφ=need_φ and (N, K), grx=need_rx and (N, nM, 2, nRx))
         # per spin in fp64 whatever the data type: summed over the spins that share the operand, then rounded once
-        gC = new((N,) + Nd + (4,), dtype=torch.float64, device=device) if any(need_c) else None
-        gMi = new(b.shape, dtype=dtype, device=device) if need_mi else None
-        gφ = new((N, K), dtype=dtype, device=device) if need_φ else None
-        grx = new((N, nM, 2, nRx), dtype=dtype, device=device) if need_rx else None
+        o.update(_new_grads(empty, torch.float64, device, gC=any(need_c) and (N,) + Nd + (4,)))
         nbytes = int(lib.mrphy_train_signal_workspace(code, N, nM, K, 1)) if need_φ else 0
         work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
-        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
         with torch.cuda.device(device):
-            rc = lib.mrphy_train_signal_bwd(code, a.data_ptr(), b.data_ptr(), ptr(gs), ptr(gl), *args, *sargs, ptr(r),
-                                            nRx, ck.data_ptr(), ptr(gA), ptr(gB), ptr(gC), ptr(gMi), ptr(gφ), ptr(grx),
+            rc = lib.mrphy_train_signal_bwd(code, a.data_ptr(), b.data_ptr(), _ptr(gs), _ptr(gl), *args, *sargs, _ptr(r),
+                                            nRx, ck.data_ptr(), *(_ptr(o[k]) for k in ('gA', 'gB', 'gC', 'gMi', 'gφ', 'grx')),
                                             work.data_ptr(), work.numel(), N, nM, K, _host.current_stream(device))
         _lib.check(rc, 'mrphy_train_signal_bwd')
         del keep
-        gcs = tuple(sims._reduce_to_const(gC[..., i], c, N, Nd).to(c.device) if want else None
-                    for i, (c, want) in enumerate(zip(consts, need_c)))
-        if need_mi:
-            if K == 0 and gl is not None:       # no repetition: Mlast is Mi
-                gMi = gl
-            if tuple(Mi.shape) != tuple(gMi.shape):     # a shared Mi: the sum over those who share it, in fp64
-                gMi = gMi.to(torch.float64).sum_to_size(tuple(Mi.shape))
-            gMi = gMi.to(device=Mi.device, dtype=Mi.dtype)
-        if need_φ:                              # summed over the spins by the kernel; here over the entries that share a phase
-            gφ = gφ.to(torch.float64).sum_to_size(tuple(phase.shape)).to(device=phase.device, dtype=phase.dtype)
+        # an operand shared by spins or batch entries gets the sum over those who share it, accumulated in fp64; grad_phase
+        # is summed over the spins by the kernel
+        f64 = torch.float64
+        gMi = gφ = grx = None
+        if need_mi:                             # no repetition: Mlast is Mi
+            gMi = _fold_to_operand(gl if (K == 0 and gl is not None) else o['gMi'], Mi, f64)
+        if need_φ:
+            gφ = _fold_to_operand(o['gφ'], phase, f64)
         if need_rx:
-            grx = grx.reshape((N,) + Nd + tuple(rx.shape[1 + len(Nd):]))
-            if rx.shape[0] != N:                        # a map shared by the batch
-                grx = grx.to(torch.float64).sum_to_size(tuple(rx.shape))
-            grx = grx.to(device=rx.device, dtype=rx.dtype)
-        return (gA, gB, gMi, gφ) + gcs + (grx, None, None)
+            grx = _fold_to_operand(o['grx'].reshape((N,) + Nd + tuple(rx.shape[1 + len(Nd):])), rx, f64)
+        return (o['gA'], o['gB'], gMi, gφ) + _fold_rest_consts(o['gC'], consts, need_c, N, Nd) + (grx, None, None)
 
 
 def _train_signal_max_rx(dtype) -> int:
-    return int(_lib.require_library().mrphy_train_signal_max_rx(_lib.F64 if dtype == torch.float64 else _lib.F32))
+    return int(_lib.require_library().mrphy_train_signal_max_rx(_code(dtype)))
 
 
 @_host.half_via_float
@@ -1619,24 +1600,14 @@ def train_signal(
 
     Out of scope as :func:`ab_train`: a flip angle or ``rest`` per repetition within one call, thinning the records.
     """
-    assert A.shape[-2:] == (3, 3) and tuple(B.shape) == tuple(A.shape[:-1]), \
-        f"A {tuple(A.shape)} must be (N, *Nd, 3, 3) and B {tuple(B.shape)} (N, *Nd, 3)"
-    N, Nd = A.shape[0], tuple(A.shape[1:-2])
+    N, Nd = _train_spins(A, B)
     K = _train_length(n, phase, N)
     if rx is not None:
         if rx.ndim not in (B.ndim, B.ndim + 1) or rx.shape[0] not in (1, N) or \
                 tuple(rx.shape[1:B.ndim]) != Nd + (2,) or (rx.ndim == B.ndim + 1 and rx.shape[-1] < 1):
             raise ValueError(f"mrphy_amd: `rx` {tuple(rx.shape)} must be (N ⊻ 1, *Nd, xy) or (N ⊻ 1, *Nd, xy, nRx) "
                              f"for spins {(N,) + Nd}")
-    _host.require_device_tensor(A, 'A')
-    _host.require_device_tensor(B, 'B')
-    assert A.dtype == B.dtype and A.device == B.device, "A and B must share dtype and device"
-    assert (T1 is None) == (T2 is None)  # both or neither
-    assert rest is not None or (T1 is None and Δf is None), "T1, T2, Δf describe the rest period: give `rest`"
-    if Mi is not None:
-        assert Mi.ndim == 2 + len(Nd) and Mi.shape[-1] == 3 and Mi.shape[0] in (1, N) and \
-            all(m in (1, d) for m, d in zip(Mi.shape[1:-1], Nd)), \
-            f"Mi {tuple(Mi.shape)} must be (N ⊻ 1, *Nd ⊻ 1, 3) for spins {(N,) + Nd}"
+    _check_train_operands(A, B, N, Nd, Mi, rest, T1, T2, Δf)
     operands = (A, B, Mi, phase, rest, T1, T2, Δf, rx)
     want = torch.is_grad_enabled() and any(isinstance(x, Tensor) and x.requires_grad for x in operands)
     cap = _train_signal_max_rx(A.dtype)

@@ -161,6 +161,25 @@ def test_fused_adjoints_pin_their_segment_length():
     assert 'constexpr int SEG = 16;' in geom and 'NOT generic' in geom
 
 
+def test_fused_adjoint_table_agrees_with_the_prototypes():
+    r"""``fused._ADJOINT_ARGS`` names what ``fused._fused_adjoint`` hands each adjoint entry point between the operands and
+    the workspace.  Every entry point of the table, ``ab_rfgr``'s among them, must take exactly the call
+    ``_fused_adjoint`` makes -- the dtype code, the checkpoints, ``k0_args()``, the constants' arguments (together
+    ``_lib._FUSED``), the table's entries (``every`` and ``nRx`` integers, everything else a pointer), ``work,
+    work_bytes, N, nM, nT``, ``nC`` for the parallel-transmit ones, ``stream``: a wrong entry would shift every pointer
+    after it, on the device."""
+    from mrphy_amd.fused import _ADJOINT_ARGS
+    vp, i64, sz = ctypes.c_void_p, ctypes.c_int64, ctypes.c_size_t
+    adjoints = {n for n in _lib.PROTOTYPES if re.fullmatch(r'mrphy_(blochsim|signal|ab)_rfgr_\w*bwd', n)}
+    assert set(_ADJOINT_ARGS) == adjoints
+    for name, between in _ADJOINT_ARGS.items():
+        mc = '_mc_' in name
+        call = _lib._FUSED + [i64 if k in ('every', 'nRx') else vp for k in between] + [vp, sz] + [i64] * (3 + mc) + [vp]
+        argtypes = _lib.PROTOTYPES[name][1]
+        assert len(call) == len(argtypes), name
+        assert call == argtypes, name
+
+
 def test_signatures_match_the_reference():
     import inspect
     sig = inspect.signature(mrphy_amd.sims.blochsim)
