@@ -87,7 +87,8 @@ extern "C" {
  *      mrphy_train_signal_bwd (the received signal of that transient: the transverse magnetisation of its records summed
  *      over the spins, for up to 8 receive coils per launch, and its adjoint); mrphy_ab_sequence_bwd_workspace,
  *      mrphy_ab_sequence_fwd, mrphy_ab_sequence_bwd (that transient with a pulse of a bank and a rest duration per
- *      repetition, and its adjoint). */
+ *      repetition, and its adjoint); mrphy_sequence_signal_workspace, mrphy_sequence_signal_bank_workspace,
+ *      mrphy_sequence_signal_fwd, mrphy_sequence_signal_bwd (the received signal of that sequence, and its adjoint). */
 #define MRPHY_ABI_VERSION 5
 
 #define MRPHY_F32      0  /* T = float,  CT = float                                          */
@@ -1205,6 +1206,57 @@ int mrphy_ab_sequence_bwd(int dtype, const void* A, const void* B, int64_t P, co
                           void* grad_A, void* grad_B, void* grad_consts, void* grad_rest, void* grad_Mi,
                           void* grad_phase, void* work, size_t work_bytes,
                           int64_t N, int64_t nM, int64_t K, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Ksqs  the received signal of Ksq's sequence: the transverse magnetisation of its records summed over the spins per
+ * repetition, for nRx receive coils, inside the kernel -- Ktrs's frame around Ksq's repetition.  A .. cs_sn exactly as
+ * mrphy_ab_sequence_fwd (the bank, the int32 schedule, the fp64 rs), rx .. work_bytes exactly as
+ * mrphy_train_signal_fwd: rx (N,nM,2,nRx) or NULL with nRx == 1, 1 <= nRx <= mrphy_train_signal_max_rx(dtype),
+ * sig (N,2,K,nRx), Mlast (N,nM,3) or NULL, ck (ceil(K/S),N*nM,3) fp64 with S = mrphy_train_signal_ck_every() or NULL
+ * (no adjoint wanted), work_bytes >= mrphy_sequence_signal_workspace(dtype,N,nM,K,2*nRx) = Pw*N*2*nRx*K*8 with
+ * Pw = min(ceil(nM/64), 2048) persistent waves.  The state has Ksq's bits, a coil's samples those of a call with that
+ * coil alone; without a schedule (P == 1, one duration) sig and Mlast are mrphy_train_signal_fwd's, bit for bit.
+ *
+ * Ksqsb  its adjoint: Ktrsb's sweep per segment of S repetitions, the segment's states recomputed from ck into LDS,
+ * with Ksqb's refreshes.  grad_sig (N,K,nRx,2) fp64 and grad_Mlast (N,nM,3): either may be NULL, not both.
+ * grad_A (P,N,nM,3,3), grad_B (P,N,nM,3): the whole bank through bank (P,12,N*nM) fp64, needed when either is wanted:
+ * bank_bytes >= mrphy_sequence_signal_bank_workspace(dtype,P,N,nM) = P*12*N*nM*8, passed in uninitialised and cleared
+ * on the caller's stream.  grad_consts (N,nM,3) FP64 = [dL/d T1, dL/d T2, dL/d df] per spin with rest_k inside the sum;
+ * grad_phase (N,K) and grad_rest (N,K), both FP64: dL/d phi_k and dL/d rest_k summed over the spins inside the kernel
+ * (the caller folds them over what shares the operand and rounds once); they need work_bytes >=
+ * mrphy_sequence_signal_workspace(dtype,N,nM,K,nQ), nQ = how many of the two are wanted.  grad_Mi (N,nM,3),
+ * grad_rx (N,nM,2,nRx) of the data type.  Each of the seven may be NULL, not all.
+ * Both refuse before anything is launched: MRPHY_EINVAL for what mrphy_ab_sequence_* and mrphy_train_signal_* refuse
+ * (the coil count, rx == NULL with nRx != 1, a NULL output, ck, work or bank that is needed); MRPHY_EALIGN for a
+ * misaligned pointer (rs, cs, ck, work, bank, grad_sig, grad_consts, grad_phase, grad_rest: 8; pulse: 4);
+ * MRPHY_ENOSPC for a workspace shorter than its query's.  0 <= pulse_k < P is a PRECONDITION as for Ksq.  An empty
+ * problem (N*nM*K == 0) is a success that writes nothing, whatever the pointers.
+ * ------------------------------------------------------------------------------------------- */
+size_t mrphy_sequence_signal_workspace(int dtype, int64_t N, int64_t nM, int64_t K, int64_t rows);
+size_t mrphy_sequence_signal_bank_workspace(int dtype, int64_t P, int64_t N, int64_t nM);
+int mrphy_sequence_signal_fwd(int dtype, const void* A, const void* B, int64_t P, const void* pulse,
+                              const void* rs, int64_t rs_sn,
+                              const void* T1, int64_t T1_sn, int64_t T1_sm,
+                              const void* T2, int64_t T2_sn, int64_t T2_sm,
+                              const void* df, int64_t df_sn, int64_t df_sm,
+                              const void* Mi, int64_t Mi_sn, int64_t Mi_sm,
+                              const void* cs, int64_t cs_sn,
+                              const void* rx, int64_t nRx, void* sig, void* Mlast, void* ck,
+                              void* work, size_t work_bytes,
+                              int64_t N, int64_t nM, int64_t K, void* stream);
+int mrphy_sequence_signal_bwd(int dtype, const void* A, const void* B, int64_t P, const void* pulse,
+                              const void* grad_sig, const void* grad_Mlast,
+                              const void* rs, int64_t rs_sn,
+                              const void* T1, int64_t T1_sn, int64_t T1_sm,
+                              const void* T2, int64_t T2_sn, int64_t T2_sm,
+                              const void* df, int64_t df_sn, int64_t df_sm,
+                              const void* Mi, int64_t Mi_sn, int64_t Mi_sm,
+                              const void* cs, int64_t cs_sn,
+                              const void* rx, int64_t nRx, const void* ck,
+                              void* grad_A, void* grad_B, void* grad_consts, void* grad_rest, void* grad_Mi,
+                              void* grad_phase, void* grad_rx, void* work, size_t work_bytes,
+                              void* bank, size_t bank_bytes,
+                              int64_t N, int64_t nM, int64_t K, void* stream);
 
 int mrphy_blochsim_ab(int dtype, const void* M, const void* A, const void* B, void* Mo,
                       int64_t rows, void* stream);

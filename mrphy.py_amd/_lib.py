@@ -116,6 +116,12 @@ PROTOTYPES = {
                               + [_i64] * 3 + [_vp]),
     'mrphy_ab_sequence_bwd': (_int, [_int, _vp, _vp, _i64, _vp, _vp, _vp, _i64] + _BC * 3 + _BC + [_vp, _i64, _vp]
                               + [_vp] * 6 + [_vp, _sz] + [_i64] * 3 + [_vp]),
+    'mrphy_sequence_signal_workspace': (_sz, [_int] + [_i64] * 4),
+    'mrphy_sequence_signal_bank_workspace': (_sz, [_int] + [_i64] * 3),
+    'mrphy_sequence_signal_fwd': (_int, [_int, _vp, _vp, _i64, _vp, _vp, _i64] + _BC * 3 + _BC + [_vp, _i64] + [_vp, _i64]
+                                  + [_vp, _vp, _vp, _vp, _sz] + [_i64] * 3 + [_vp]),
+    'mrphy_sequence_signal_bwd': (_int, [_int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64] + _BC * 3 + _BC + [_vp, _i64]
+                                  + [_vp, _i64] + [_vp] + [_vp] * 7 + [_vp, _sz] + [_vp, _sz] + [_i64] * 3 + [_vp]),
     'mrphy_blochsim_ab': (_int, [_int, _vp, _vp, _vp, _vp, _i64, _vp]),
     'mrphy_blochsim_ab_bwd': (_int, [_int, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
@@ -164,6 +170,7 @@ UNITS = [(f, m) for f, masks in (
     ('tu_ab_train.hip', (None,)),
     ('tu_train_signal.hip', (None,)),
     ('tu_ab_sequence.hip', (None,)),
+    ('tu_sequence_signal.hip', (None,)),
     ('abi.hip', (None,)),
 ) for m in masks]
 

@@ -72,7 +72,8 @@ from ._consts import γH, dt0
 from .beffective import _code
 
 __all__ = ['blochsim_rfgr', 'blochsim_rfgr_traj', 'signal_rfgr', 'ab_rfgr', 'ab_steadystate', 'steadystate_rfgr',
-           'ab_train', 'train_rfgr', 'train_signal', 'train_signal_rfgr', 'ab_sequence', 'sequence_rfgr']
+           'ab_train', 'train_rfgr', 'train_signal', 'train_signal_rfgr', 'ab_sequence', 'sequence_rfgr',
+           'sequence_signal', 'sequence_signal_rfgr']
 
 
 def _ptr(x):
@@ -1401,9 +1402,9 @@ def ab_sequence(
     gradients go through an fp64 workspace of ``P·12`` numbers per spin, nothing of size ``K × spins`` is kept besides
     the output), deterministic.
 
-    Out of scope: the received signal of such a sequence summed inside the kernel (a :func:`train_signal` with a
-    schedule); a steady state of a multi-pulse period; a schedule per batch entry; thinning the records; reading out at
-    an echo time after the pulse (``sims.freeprec`` on the records, an elementwise operation); a CPU path.
+    Out of scope: a steady state of a multi-pulse period; a schedule per batch entry; thinning the records; reading out
+    at an echo time after the pulse (``sims.freeprec`` on the records, an elementwise operation); a CPU path.  The
+    received signal of such a sequence summed inside the kernel is :func:`sequence_signal`.
     """
     N, Nd = _train_spins(A, B, bank=True)
     P = A.shape[0]
@@ -1435,7 +1436,7 @@ def sequence_rfgr(
     and every operand ``ab_rfgr`` differentiates -- a flip-angle schedule ``rf = s[:, None, None, None] * rf0`` gets
     ``∂/∂s`` by autograd -- and ``Mi, phase, rest, T1, T2, Δf`` / ``Δf_rest`` through the train: ``T1`` and ``T2`` receive the
     sum of the pulses' and the rests' paths.  :func:`ab_rfgr`'s limit on the batch is inherited: ``P·N ≤ 65535``.  Out of
-    scope as in :func:`ab_sequence`.
+    scope as in :func:`ab_sequence`; the signal of the sequence is :func:`sequence_signal_rfgr`.
     """
     assert rf.ndim in (4, 5) and gr.ndim == 4 and gr.shape[0] in (1, rf.shape[0]) and gr.shape[1] == rf.shape[1], \
         f"rf {tuple(rf.shape)} must be (P, N, xy, nT[, nCoils]) and gr {tuple(gr.shape)} (P ⊻ 1, N, xyz, nT)"
@@ -1598,7 +1599,8 @@ def train_signal(
     a proton density, a coil sensitivity and an echo time stay in torch on per-spin tensors: the signal at an echo time
     ``TE`` after the pulse is this one with ``rx · exp(-TE/T2) · exp(-i2πΔf·TE)`` for ``rx``.
 
-    Out of scope as :func:`ab_train`: a flip angle or ``rest`` per repetition within one call, thinning the records.
+    Out of scope as :func:`ab_train`: thinning the records.  A flip angle or ``rest`` per repetition within one call is
+    :func:`sequence_signal`.
     """
     N, Nd = _train_spins(A, B)
     K = _train_length(n, phase, N)
@@ -1650,3 +1652,216 @@ def train_signal_rfgr(
     A, B = ab_rfgr(rf, gr, loc, Δf=Δf, b1Map=b1Map, γ_beff=γ_beff, T1=T1, T2=T2, γ=γ, dt=dt, consts=consts)
     return train_signal(A, B, n=n, Mi=Mi, phase=phase, rest=rest, T1=T1, T2=T2,
                         Δf=Δf if Δf_rest is None else Δf_rest, rx=rx, demod=demod, return_last=return_last)
+
+
+def _fold_repetition_sums(g, x):
+    r"""The gradient of ``rest`` from the kernel's sums over the spins ``g`` `(N, K)` fp64: folded in fp64 over what ``x``
+    shares -- ``x`` `(N ⊻ 1, K)`, or a duration `()` ⊻ `(N ⊻ 1,)` that the repetitions share too -- and rounded once."""
+    g = g.sum_to_size(tuple(x.shape)) if x.ndim == 2 else g.sum(1).sum_to_size(tuple(x.shape) or (1,))
+    return g.reshape(x.shape).to(device=x.device, dtype=x.dtype)
+
+
+class SequenceSignalHIP(Function):
+    r"""``sig, Mlast = SequenceSignalHIP.apply(A, B, Mi, phase, rest, T1, T2, Δf, rx, K, sched, want_ckpt)`` -- see
+    :func:`sequence_signal`.  ``A, B`` carry the bank axis in front and ``sched`` is the checked schedule as for
+    :class:`AbSequenceHIP`; ``rx``, ``sig``, ``Mlast`` and ``want_ckpt`` as for :class:`TrainSignalHIP`.  The forward
+    (``mrphy_sequence_signal_fwd``) leaves the fp64 state every ``mrphy_train_signal_ck_every()`` repetitions when a
+    gradient is wanted, all the adjoint (``mrphy_sequence_signal_bwd``) reads besides the inputs; the adjoint's scratch
+    is the fp64 workspace of the bank's gradients and the per-wave sums of ``grad_phase`` and ``grad_rest``."""
+
+    ARGS = ('A', 'B', 'Mi', 'phase', 'rest', 'T1', 'T2', 'Δf', 'rx', 'K', 'sched', 'want_ckpt')
+
+    @staticmethod
+    def forward(ctx, A, B, Mi, phase, rest, T1, T2, Δf, rx, K, sched, want_ckpt):
+        lib = _lib.require_library()
+        device, dtype = A.device, A.dtype
+        a, b = A.detach().contiguous(), B.detach().contiguous()
+        sched_dev = None if sched is None else sched.to(device)
+        rs = AbSequenceHIP._rest_table(a, rest, a.shape[1], K)
+        mi, cs = _state_operands(a[0], Mi, phase)
+        N, Nd, nM, code, keep, head, tail = AbSequenceHIP._args(a, rs, T1, T2, Δf, mi, cs, sched_dev)
+        r, nRx = TrainSignalHIP._rx_operand(a[0], rx)
+        coils = () if rx is None or rx.ndim == b.ndim - 1 else (nRx,)
+        empty = N * nM * K == 0
+        sig = (torch.zeros if empty else torch.empty)((N, 2, K, *coils), dtype=dtype, device=device)
+        Mlast = torch.empty_like(b[0])
+        if K == 0:                              # no repetition: the state is still Mi
+            Mlast.copy_(torch.tensor((0., 0., 1.), dtype=dtype, device=device) if mi is None else
+                        mi.reshape((mi.shape[0],) + (Nd if mi.shape[1] > 1 else (1,) * len(Nd)) + (3,)))
+        S = int(lib.mrphy_train_signal_ck_every())
+        ck = torch.empty((-(-K // S), N * nM, 3), dtype=torch.float64, device=device) if want_ckpt else None
+        nbytes = int(lib.mrphy_sequence_signal_workspace(code, N, nM, K, 2 * nRx))
+        work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+        with torch.cuda.device(device):
+            rc = lib.mrphy_sequence_signal_fwd(code, a.data_ptr(), b.data_ptr(), *head, *tail, _ptr(r), nRx,
+                                               sig.data_ptr(), Mlast.data_ptr(), _ptr(ck), work.data_ptr(), work.numel(),
+                                               N, nM, K, _host.current_stream(device))
+        _lib.check(rc, 'mrphy_sequence_signal_fwd')
+        del keep
+        ctx.set_materialize_grads(False)
+        if want_ckpt:
+            ctx.save_for_backward(a, b, mi, cs, rs, sched_dev, r, ck)
+            ctx.consts = (T1, T2, Δf)
+            ctx.state = (Mi, phase, rest, rx, K, nRx)
+        return sig, Mlast
+
+    @staticmethod
+    def backward(ctx, grad_sig, grad_Mlast):
+        need = ctx.needs_input_grad
+        none = (None,) * len(SequenceSignalHIP.ARGS)
+        if not any(need) or (grad_sig is None and grad_Mlast is None):
+            return none
+        consts = ctx.consts
+        Mi, phase, rest, rx, K, nRx = ctx.state
+        need_c = [w and c is not None for w, c in zip(need[5:8], consts)]
+        need_mi, need_φ, need_r = need[2] and Mi is not None, need[3] and phase is not None, need[4] and rest is not None
+        need_rx = need[8] and rx is not None
+        if not (need[0] or need[1] or need_mi or need_φ or need_r or need_rx or any(need_c)):
+            return none
+        lib = _lib.require_library()
+        a, b, mi, cs, rs, sched_dev, r, ck = ctx.saved_tensors
+        device, dtype = a.device, a.dtype
+        N, Nd, nM, code, keep, head, tail = AbSequenceHIP._args(a, rs, *consts, mi, cs, sched_dev)
+        # the cotangent of the signal as the wave-uniform table (N, K, nRx, 2) in fp64
+        gs = None if grad_sig is None else \
+            grad_sig.detach().to(torch.float64).reshape(N, 2, K, nRx).permute(0, 2, 3, 1).contiguous()
+        gl = None if grad_Mlast is None else grad_Mlast.detach().to(dtype).contiguous()
+        empty = N * nM * K == 0
+        f64 = torch.float64
+        o = _new_grads(empty, dtype, device, gA=need[0] and a.shape, gB=need[1] and b.shape,
+                       gMi=need_mi and b.shape[1:], grx=need_rx and (N, nM, 2, nRx))
+        # in fp64 whatever the data type: per spin (gC) or summed over the spins by the kernel (gφ, gr), folded over
+        # those who share the operand, then rounded once
+        o.update(_new_grads(empty, f64, device, gC=any(need_c) and (N,) + Nd + (3,), gφ=need_φ and (N, K),
+                            gr=need_r and (N, K)))
+        nQ = int(bool(need_φ)) + int(bool(need_r))
+        nbytes = int(lib.mrphy_sequence_signal_workspace(code, N, nM, K, nQ)) if nQ else 0
+        work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+        nbank = int(lib.mrphy_sequence_signal_bank_workspace(code, a.shape[0], N, nM)) if (need[0] or need[1]) else 0
+        bank = torch.empty(nbank // 8, dtype=f64, device=device) if nbank else None
+        with torch.cuda.device(device):
+            rc = lib.mrphy_sequence_signal_bwd(code, a.data_ptr(), b.data_ptr(), *head, _ptr(gs), _ptr(gl), *tail, _ptr(r),
+                                               nRx, ck.data_ptr(),
+                                               *(_ptr(o[k]) for k in ('gA', 'gB', 'gC', 'gr', 'gMi', 'gφ', 'grx')),
+                                               work.data_ptr(), work.numel(), _ptr(bank), nbank, N, nM, K,
+                                               _host.current_stream(device))
+        _lib.check(rc, 'mrphy_sequence_signal_bwd')
+        del keep, work, bank
+        gMi = gφ = gr = grx = None
+        if need_mi:                             # no repetition: Mlast is Mi
+            gMi = _fold_to_operand(gl if (K == 0 and gl is not None) else o['gMi'], Mi, f64)
+        if need_φ:
+            gφ = _fold_to_operand(o['gφ'], phase, f64)
+        if need_r:
+            gr = _fold_repetition_sums(o['gr'], rest)
+        if need_rx:
+            grx = _fold_to_operand(o['grx'].reshape((N,) + Nd + tuple(rx.shape[1 + len(Nd):])), rx, f64)
+        return (o['gA'], o['gB'], gMi, gφ, gr) + _fold_rest_consts(o['gC'], consts, need_c, N, Nd) + (grx, None, None, None)
+
+
+@_host.half_via_float
+def sequence_signal(
+    A: Tensor, B: Tensor, *, pulse=None, n: Optional[int] = None, Mi: Optional[Tensor] = None,
+    phase: Optional[Tensor] = None, rest: Optional[Tensor] = None, T1: Optional[Tensor] = None,
+    T2: Optional[Tensor] = None, Δf: Optional[Tensor] = None, rx: Optional[Tensor] = None, demod: bool = False,
+    return_last: bool = False
+):
+    r"""The signal a receive coil measures after each of the ``K`` repetitions of :func:`ab_sequence` -- what one fits
+    to a measured MR-fingerprinting, inversion- or T2-prepared or variable-flip-angle train: the transverse
+    magnetisation of record ``k`` summed over the spins ``*Nd``, weighted by the receive map ``rx`` exactly as
+    :func:`train_signal` weights it,
+
+        ``sig[n, 0, k] = Σ_s rx_re·Mx − rx_im·My``,  ``sig[n, 1, k] = Σ_s rx_re·My + rx_im·Mx``.
+
+    Usage:
+        ``sig = sequence_signal(A, B, *, pulse, n, Mi, phase, rest, T1, T2, Δf, rx, demod)``
+        ``sig, Mlast = sequence_signal(..., return_last=True)``
+
+    The sequence-side operands ``A`` `(P, N, *Nd, xyz, 3)`, ``B`` `(P, N, *Nd, xyz)`, ``pulse``, ``n``, ``Mi``, ``phase``,
+    ``rest`` (`()`, `(N ⊻ 1,)` or `(N ⊻ 1, K)`), ``T1``, ``T2``, ``Δf`` -- shapes, broadcasting, absences, the host-side
+    check of the schedule and its errors -- are exactly :func:`ab_sequence`'s.  The receiver-side operands ``rx``
+    (`(N ⊻ 1, *Nd, xy)` or `(N ⊻ 1, *Nd, xy, nRx)`, ``None`` = ``(1, 0)``), ``demod``, ``return_last``, the output
+    ``sig`` `(N, xy, K[, nRx])`, ``Mlast`` `(N, *Nd, xyz)`, the blocks of ``mrphy_train_signal_max_rx`` coils above that
+    many, and the cases ``K = 0`` and no spins are exactly :func:`train_signal`'s.
+
+    The sum is formed inside the kernel (Ksqs, ``mrphy_sequence_signal_fwd``): :func:`train_signal`'s frame around
+    :func:`ab_sequence`'s repetition.  The state has :func:`ab_sequence`'s bits -- ``Mlast`` is its last record --, a
+    coil's samples are those of a call with that coil alone, and with ``P = 1`` and one ``rest`` both outputs are
+    :func:`train_signal`'s, bit for bit.  No float atomics, the same inputs give the same bits, and nothing of size
+    ``K × spins`` is written: with a gradient wanted, the fp64 state every ``mrphy_train_signal_ck_every()`` repetitions.
+
+    Differentiable through both outputs w.r.t. ``A``, ``B`` (the whole bank: an entry the schedule never plays gets an
+    exactly-zero gradient), ``Mi``, ``phase``, ``rest`` (in the form given), ``T1``, ``T2``, ``Δf`` and ``rx`` (Ksqsb,
+    ``mrphy_sequence_signal_bwd``: :func:`train_signal`'s sweep per segment on states recomputed from the checkpoints,
+    with :func:`ab_sequence`'s refreshes; the bank's gradients go through an fp64 workspace of ``P·12`` numbers per
+    spin; the gradients of ``phase`` and ``rest`` are summed over the spins inside the kernel per repetition and folded
+    over what shares the operand in fp64; deterministic).
+
+    Out of scope: a schedule per batch entry; thinning the samples; a steady state of a multi-pulse period; a readout
+    at an echo time inside the kernel (``rx · exp(-TE/T2) · exp(-i2πΔf·TE)`` for ``rx``, in torch, as
+    :func:`train_signal` documents); a gradient of ``rest`` per spin; a CPU path.
+    """
+    N, Nd = _train_spins(A, B, bank=True)
+    P = A.shape[0]
+    sched = _sequence_schedule(pulse, P)
+    K = _sequence_length(n, sched, phase, N)
+    if rest is not None and (rest.ndim > 2 or (rest.ndim == 1 and rest.shape[0] not in (1, N)) or
+                             (rest.ndim == 2 and (rest.shape[0] not in (1, N) or rest.shape[1] != K))):
+        raise ValueError(f"mrphy_amd: `rest` {tuple(rest.shape)} must be (), (N ⊻ 1,) or (N ⊻ 1, K) with N = {N}, K = {K}")
+    nb = B.ndim - 1                                   # dimensions of one entry's B: (N, *Nd, xyz)
+    if rx is not None:
+        if rx.ndim not in (nb, nb + 1) or rx.shape[0] not in (1, N) or \
+                tuple(rx.shape[1:nb]) != Nd + (2,) or (rx.ndim == nb + 1 and rx.shape[-1] < 1):
+            raise ValueError(f"mrphy_amd: `rx` {tuple(rx.shape)} must be (N ⊻ 1, *Nd, xy) or (N ⊻ 1, *Nd, xy, nRx) "
+                             f"for spins {(N,) + Nd}")
+    _check_train_operands(A, B, N, Nd, Mi, rest, T1, T2, Δf)
+    operands = (A, B, Mi, phase, rest, T1, T2, Δf, rx)
+    want = torch.is_grad_enabled() and any(isinstance(x, Tensor) and x.requires_grad for x in operands)
+    cap = _train_signal_max_rx(A.dtype)
+    if rx is not None and rx.ndim == nb + 1 and rx.shape[-1] > cap:
+        # blocks of `cap` coils, one simulation each; a coil's sums do not depend on the other coils
+        parts = [SequenceSignalHIP.apply(A, B, Mi, phase, rest, T1, T2, Δf, rx[..., c:c + cap], K, sched, want)
+                 for c in range(0, rx.shape[-1], cap)]
+        sig, Mlast = torch.cat([p[0] for p in parts], dim=-1), parts[0][1]
+    else:
+        sig, Mlast = SequenceSignalHIP.apply(A, B, Mi, phase, rest, T1, T2, Δf, rx, K, sched, want)
+    if demod and phase is not None:
+        φ = phase.to(device=sig.device, dtype=torch.float64).reshape(phase.shape + (1,) * (sig.ndim - 3))
+        c, s = torch.cos(φ), torch.sin(φ)
+        s0, s1 = sig[:, 0].to(torch.float64), sig[:, 1].to(torch.float64)
+        sig = torch.stack((s0 * c + s1 * s, s1 * c - s0 * s), dim=1).to(sig.dtype)
+    return (sig, Mlast) if return_last else sig
+
+
+@_host.half_via_float
+def sequence_signal_rfgr(
+    rf: Tensor, gr: Tensor, loc: Tensor, *,
+    pulse=None, n: Optional[int] = None, Mi: Optional[Tensor] = None, phase: Optional[Tensor] = None,
+    rest: Optional[Tensor] = None, T1: Optional[Tensor] = None, T2: Optional[Tensor] = None,
+    Δf: Optional[Tensor] = None, rx: Optional[Tensor] = None, demod: bool = False, return_last: bool = False,
+    b1Map: Optional[Tensor] = None, γ_beff: Tensor = γH,
+    γ: Tensor = γH, dt: Tensor = dt0, consts: Optional[dict] = None, Δf_rest: Optional[Tensor] = None
+):
+    r"""The signal of a sequence that plays a bank of pulses by a schedule, from ``rf`` `(P, N, xy, nT[, nCoils])` and
+    ``gr`` `(P ⊻ 1, N, xyz, nT)`: ONE :func:`ab_rfgr` call on the batch ``P·N`` exactly as :func:`sequence_rfgr` makes
+    it, its ``A, B`` viewed as the bank, then :func:`sequence_signal`.  Operands of the pulses as :func:`ab_rfgr`, those
+    of the sequence and of the receiver as :func:`sequence_signal`; ``Δf_rest`` as in :func:`steadystate_rfgr`.
+
+    Every route of :func:`ab_rfgr` (fused, split, composed; parallel transmit) serves it, so gradients reach ``rf``,
+    ``gr`` and every operand ``ab_rfgr`` differentiates -- a flip-angle schedule ``rf = s[:, None, None, None] * rf0``
+    gets ``∂/∂s`` by autograd -- and ``Mi, phase, rest, T1, T2, Δf`` / ``Δf_rest``, ``rx`` through the sequence.
+    :func:`ab_rfgr`'s limit on the batch is inherited: ``P·N ≤ 65535``.  Out of scope as in :func:`sequence_signal`.
+    """
+    assert rf.ndim in (4, 5) and gr.ndim == 4 and gr.shape[0] in (1, rf.shape[0]) and gr.shape[1] == rf.shape[1], \
+        f"rf {tuple(rf.shape)} must be (P, N, xy, nT[, nCoils]) and gr {tuple(gr.shape)} (P ⊻ 1, N, xyz, nT)"
+    P, N = rf.shape[0], rf.shape[1]
+    sched = _sequence_schedule(pulse, P)          # before any work on the device
+    over = lambda x: x.expand((P,) + tuple(x.shape)).flatten(0, 1)  # noqa: E731
+    # a spin-side operand: repeated over the bank where it has the batch axis, left to broadcast where it has not
+    side = lambda x: over(x) if (isinstance(x, Tensor) and x.ndim >= 1 and x.shape[0] == N and N > 1) else x  # noqa: E731
+    A, B = ab_rfgr(rf.flatten(0, 1), over(gr[0]) if gr.shape[0] == 1 else gr.flatten(0, 1), over(loc), Δf=side(Δf),
+                   b1Map=side(b1Map), γ_beff=side(γ_beff), T1=side(T1), T2=side(T2), γ=side(γ), dt=side(dt),
+                   consts=None if consts is None else {k: side(v) for k, v in consts.items()})
+    return sequence_signal(A.unflatten(0, (P, N)), B.unflatten(0, (P, N)), pulse=sched, n=n, Mi=Mi, phase=phase,
+                           rest=rest, T1=T1, T2=T2, Δf=Δf if Δf_rest is None else Δf_rest, rx=rx, demod=demod,
+                           return_last=return_last)
