@@ -88,7 +88,9 @@ extern "C" {
  *      over the spins, for up to 8 receive coils per launch, and its adjoint); mrphy_ab_sequence_bwd_workspace,
  *      mrphy_ab_sequence_fwd, mrphy_ab_sequence_bwd (that transient with a pulse of a bank and a rest duration per
  *      repetition, and its adjoint); mrphy_sequence_signal_workspace, mrphy_sequence_signal_bank_workspace,
- *      mrphy_sequence_signal_fwd, mrphy_sequence_signal_bwd (the received signal of that sequence, and its adjoint). */
+ *      mrphy_sequence_signal_fwd, mrphy_sequence_signal_bwd (the received signal of that sequence, and its adjoint);
+ *      mrphy_sequence_steadystate_fwd, mrphy_sequence_steadystate_bwd (the steady state of that sequence played as one
+ *      period, and its adjoint). */
 #define MRPHY_ABI_VERSION 5
 
 #define MRPHY_F32      0  /* T = float,  CT = float                                          */
@@ -1257,6 +1259,50 @@ int mrphy_sequence_signal_bwd(int dtype, const void* A, const void* B, int64_t P
                               void* grad_phase, void* grad_rx, void* work, size_t work_bytes,
                               void* bank, size_t bank_bytes,
                               int64_t N, int64_t nM, int64_t K, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Ksqp  the steady state of Ksq's K repetitions played as one period, over and over: per spin the K affine maps compose
+ * to Phi(M) = Abar M + bbar, and Mss = (I - Abar)^-1 bbar is the state right after the LAST repetition of the period
+ * (= the state before the rest of repetition 0; Kss's convention, record K-1 of Ksq started at Mss).  A .. df_sm and
+ * cs, cs_sn exactly as mrphy_ab_sequence_fwd (the bank, the int32 schedule, the fp64 rs and cs); there is no Mi.  One
+ * thread per spin carries four fp64 columns through Ksq's repetition (the affine column from 0 and the columns of I
+ * through the linear part, nothing obtained as a difference), then solves in Kss's cofactor form, fp64, one division;
+ * Mss (N,nM,3) is rounded once into the data type.  A singular period gives non-finite values, as Kss.  Two optional
+ * outputs for the adjoint, both NULL when none is wanted: per (12,N*nM) fp64 = Abar row-major then bbar, slot-major;
+ * ck (ceil(K/S),N*nM,3) fp64 with S = mrphy_train_signal_ck_every() = the state before repetitions 0, S, 2S, ... of the
+ * period started at the unrounded Mss (a second walk of one column in the same launch).
+ *
+ * Ksqpl + Ksqsb  its adjoint for the cotangent grad_Mss (N,nM,3): a small kernel forms lambda = (I - Abar)^-T grad_Mss
+ * from per into lam (N,nM,3) of the data type, scratch passed by the caller; then Ksqsb's sweep (the launcher of
+ * mrphy_sequence_signal_bwd) runs from ck with no signal cotangent and lambda as the cotangent of the last state.  The
+ * outputs are handed over exactly as mrphy_sequence_signal_bwd hands them over: grad_A (P,N,nM,3,3), grad_B (P,N,nM,3)
+ * through bank (exact zeros for an entry never played), grad_consts (N,nM,3) FP64, grad_rest (N,K) and grad_phase (N,K)
+ * FP64 summed over the spins inside the kernel; each may be NULL, not all.  work and bank are sized by
+ * mrphy_sequence_signal_workspace(dtype,N,nM,K,nQ) and mrphy_sequence_signal_bank_workspace(dtype,P,N,nM).  No atomics;
+ * the same inputs give the same bits.
+ * Both refuse before anything is launched what mrphy_ab_sequence_* and mrphy_sequence_signal_* refuse, with the same
+ * codes in the same order (MRPHY_EALIGN: rs, cs, per, ck, work, bank, grad_consts, grad_rest, grad_phase: 8; pulse: 4);
+ * K < 1 with spins present is MRPHY_EINVAL: a period needs a repetition.  N*nM == 0 is a success that writes nothing.
+ * ------------------------------------------------------------------------------------------- */
+int mrphy_sequence_steadystate_fwd(int dtype, const void* A, const void* B, int64_t P, const void* pulse,
+                                   const void* rs, int64_t rs_sn,
+                                   const void* T1, int64_t T1_sn, int64_t T1_sm,
+                                   const void* T2, int64_t T2_sn, int64_t T2_sm,
+                                   const void* df, int64_t df_sn, int64_t df_sm,
+                                   const void* cs, int64_t cs_sn,
+                                   void* Mss, void* per, void* ck,
+                                   int64_t N, int64_t nM, int64_t K, void* stream);
+int mrphy_sequence_steadystate_bwd(int dtype, const void* A, const void* B, int64_t P, const void* pulse,
+                                   const void* grad_Mss,
+                                   const void* rs, int64_t rs_sn,
+                                   const void* T1, int64_t T1_sn, int64_t T1_sm,
+                                   const void* T2, int64_t T2_sn, int64_t T2_sm,
+                                   const void* df, int64_t df_sn, int64_t df_sm,
+                                   const void* cs, int64_t cs_sn,
+                                   const void* per, const void* ck, void* lam,
+                                   void* grad_A, void* grad_B, void* grad_consts, void* grad_rest, void* grad_phase,
+                                   void* work, size_t work_bytes, void* bank, size_t bank_bytes,
+                                   int64_t N, int64_t nM, int64_t K, void* stream);
 
 int mrphy_blochsim_ab(int dtype, const void* M, const void* A, const void* B, void* Mo,
                       int64_t rows, void* stream);

@@ -122,6 +122,10 @@ PROTOTYPES = {
                                   + [_vp, _vp, _vp, _vp, _sz] + [_i64] * 3 + [_vp]),
     'mrphy_sequence_signal_bwd': (_int, [_int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64] + _BC * 3 + _BC + [_vp, _i64]
                                   + [_vp, _i64] + [_vp] + [_vp] * 7 + [_vp, _sz] + [_vp, _sz] + [_i64] * 3 + [_vp]),
+    'mrphy_sequence_steadystate_fwd': (_int, [_int, _vp, _vp, _i64, _vp, _vp, _i64] + _BC * 3 + [_vp, _i64]
+                                       + [_vp, _vp, _vp] + [_i64] * 3 + [_vp]),
+    'mrphy_sequence_steadystate_bwd': (_int, [_int, _vp, _vp, _i64, _vp, _vp, _vp, _i64] + _BC * 3 + [_vp, _i64]
+                                       + [_vp, _vp, _vp] + [_vp] * 5 + [_vp, _sz] + [_vp, _sz] + [_i64] * 3 + [_vp]),
     'mrphy_blochsim_ab': (_int, [_int, _vp, _vp, _vp, _vp, _i64, _vp]),
     'mrphy_blochsim_ab_bwd': (_int, [_int, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
@@ -171,6 +175,7 @@ UNITS = [(f, m) for f, masks in (
     ('tu_train_signal.hip', (None,)),
     ('tu_ab_sequence.hip', (None,)),
     ('tu_sequence_signal.hip', (None,)),
+    ('tu_sequence_steady.hip', (None,)),
     ('abi.hip', (None,)),
 ) for m in masks]
 

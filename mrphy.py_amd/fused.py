@@ -73,7 +73,7 @@ from .beffective import _code
 
 __all__ = ['blochsim_rfgr', 'blochsim_rfgr_traj', 'signal_rfgr', 'ab_rfgr', 'ab_steadystate', 'steadystate_rfgr',
            'ab_train', 'train_rfgr', 'train_signal', 'train_signal_rfgr', 'ab_sequence', 'sequence_rfgr',
-           'sequence_signal', 'sequence_signal_rfgr']
+           'sequence_signal', 'sequence_signal_rfgr', 'sequence_steadystate', 'sequence_steadystate_rfgr']
 
 
 def _ptr(x):
@@ -1402,9 +1402,10 @@ def ab_sequence(
     gradients go through an fp64 workspace of ``P·12`` numbers per spin, nothing of size ``K × spins`` is kept besides
     the output), deterministic.
 
-    Out of scope: a steady state of a multi-pulse period; a schedule per batch entry; thinning the records; reading out
-    at an echo time after the pulse (``sims.freeprec`` on the records, an elementwise operation); a CPU path.  The
-    received signal of such a sequence summed inside the kernel is :func:`sequence_signal`.
+    Out of scope: a schedule per batch entry; thinning the records; reading out at an echo time after the pulse
+    (``sims.freeprec`` on the records, an elementwise operation); a CPU path.  The received signal of such a sequence
+    summed inside the kernel is :func:`sequence_signal`; the steady state of the ``K`` repetitions played as one period
+    is :func:`sequence_steadystate`.
     """
     N, Nd = _train_spins(A, B, bank=True)
     P = A.shape[0]
@@ -1415,6 +1416,23 @@ def ab_sequence(
         raise ValueError(f"mrphy_amd: `rest` {tuple(rest.shape)} must be (), (N ⊻ 1,) or (N ⊻ 1, K) with N = {N}, K = {K}")
     _check_train_operands(A, B, N, Nd, Mi, rest, T1, T2, Δf)
     return AbSequenceHIP.apply(A, B, Mi, phase, rest, T1, T2, Δf, K, sched).movedim(0, -2)
+
+
+def _sequence_bank(rf, gr, loc, pulse, *, Δf, b1Map, γ_beff, T1, T2, γ, dt, consts):
+    r"""``(A, B, sched)`` of :func:`sequence_rfgr` and its siblings: the schedule checked on the host before any work on
+    the device, then ONE :func:`ab_rfgr` call on the batch ``P·N`` whose ``A, B`` are viewed as the bank
+    `(P, N, *Nd, …)`."""
+    assert rf.ndim in (4, 5) and gr.ndim == 4 and gr.shape[0] in (1, rf.shape[0]) and gr.shape[1] == rf.shape[1], \
+        f"rf {tuple(rf.shape)} must be (P, N, xy, nT[, nCoils]) and gr {tuple(gr.shape)} (P ⊻ 1, N, xyz, nT)"
+    P, N = rf.shape[0], rf.shape[1]
+    sched = _sequence_schedule(pulse, P)          # before any work on the device
+    over = lambda x: x.expand((P,) + tuple(x.shape)).flatten(0, 1)  # noqa: E731
+    # a spin-side operand: repeated over the bank where it has the batch axis, left to broadcast where it has not
+    side = lambda x: over(x) if (isinstance(x, Tensor) and x.ndim >= 1 and x.shape[0] == N and N > 1) else x  # noqa: E731
+    A, B = ab_rfgr(rf.flatten(0, 1), over(gr[0]) if gr.shape[0] == 1 else gr.flatten(0, 1), over(loc), Δf=side(Δf),
+                   b1Map=side(b1Map), γ_beff=side(γ_beff), T1=side(T1), T2=side(T2), γ=side(γ), dt=side(dt),
+                   consts=None if consts is None else {k: side(v) for k, v in consts.items()})
+    return A.unflatten(0, (P, N)), B.unflatten(0, (P, N)), sched
 
 
 @_host.half_via_float
@@ -1438,18 +1456,10 @@ def sequence_rfgr(
     sum of the pulses' and the rests' paths.  :func:`ab_rfgr`'s limit on the batch is inherited: ``P·N ≤ 65535``.  Out of
     scope as in :func:`ab_sequence`; the signal of the sequence is :func:`sequence_signal_rfgr`.
     """
-    assert rf.ndim in (4, 5) and gr.ndim == 4 and gr.shape[0] in (1, rf.shape[0]) and gr.shape[1] == rf.shape[1], \
-        f"rf {tuple(rf.shape)} must be (P, N, xy, nT[, nCoils]) and gr {tuple(gr.shape)} (P ⊻ 1, N, xyz, nT)"
-    P, N = rf.shape[0], rf.shape[1]
-    sched = _sequence_schedule(pulse, P)          # before any work on the device
-    over = lambda x: x.expand((P,) + tuple(x.shape)).flatten(0, 1)  # noqa: E731
-    # a spin-side operand: repeated over the bank where it has the batch axis, left to broadcast where it has not
-    side = lambda x: over(x) if (isinstance(x, Tensor) and x.ndim >= 1 and x.shape[0] == N and N > 1) else x  # noqa: E731
-    A, B = ab_rfgr(rf.flatten(0, 1), over(gr[0]) if gr.shape[0] == 1 else gr.flatten(0, 1), over(loc), Δf=side(Δf),
-                   b1Map=side(b1Map), γ_beff=side(γ_beff), T1=side(T1), T2=side(T2), γ=side(γ), dt=side(dt),
-                   consts=None if consts is None else {k: side(v) for k, v in consts.items()})
-    return ab_sequence(A.unflatten(0, (P, N)), B.unflatten(0, (P, N)), pulse=sched, n=n, Mi=Mi, phase=phase, rest=rest,
-                       T1=T1, T2=T2, Δf=Δf if Δf_rest is None else Δf_rest)
+    A, B, sched = _sequence_bank(rf, gr, loc, pulse, Δf=Δf, b1Map=b1Map, γ_beff=γ_beff, T1=T1, T2=T2, γ=γ, dt=dt,
+                                 consts=consts)
+    return ab_sequence(A, B, pulse=sched, n=n, Mi=Mi, phase=phase, rest=rest, T1=T1, T2=T2,
+                       Δf=Δf if Δf_rest is None else Δf_rest)
 
 
 class TrainSignalHIP(Function):
@@ -1797,9 +1807,10 @@ def sequence_signal(
     spin; the gradients of ``phase`` and ``rest`` are summed over the spins inside the kernel per repetition and folded
     over what shares the operand in fp64; deterministic).
 
-    Out of scope: a schedule per batch entry; thinning the samples; a steady state of a multi-pulse period; a readout
-    at an echo time inside the kernel (``rx · exp(-TE/T2) · exp(-i2πΔf·TE)`` for ``rx``, in torch, as
-    :func:`train_signal` documents); a gradient of ``rest`` per spin; a CPU path.
+    Out of scope: a schedule per batch entry; thinning the samples; a readout at an echo time inside the kernel
+    (``rx · exp(-TE/T2) · exp(-i2πΔf·TE)`` for ``rx``, in torch, as :func:`train_signal` documents); a gradient of
+    ``rest`` per spin; a CPU path.  The signal of the steady period is this function with
+    ``Mi=sequence_steadystate(...)``.
     """
     N, Nd = _train_spins(A, B, bank=True)
     P = A.shape[0]
@@ -1852,16 +1863,194 @@ def sequence_signal_rfgr(
     gets ``∂/∂s`` by autograd -- and ``Mi, phase, rest, T1, T2, Δf`` / ``Δf_rest``, ``rx`` through the sequence.
     :func:`ab_rfgr`'s limit on the batch is inherited: ``P·N ≤ 65535``.  Out of scope as in :func:`sequence_signal`.
     """
-    assert rf.ndim in (4, 5) and gr.ndim == 4 and gr.shape[0] in (1, rf.shape[0]) and gr.shape[1] == rf.shape[1], \
-        f"rf {tuple(rf.shape)} must be (P, N, xy, nT[, nCoils]) and gr {tuple(gr.shape)} (P ⊻ 1, N, xyz, nT)"
-    P, N = rf.shape[0], rf.shape[1]
-    sched = _sequence_schedule(pulse, P)          # before any work on the device
-    over = lambda x: x.expand((P,) + tuple(x.shape)).flatten(0, 1)  # noqa: E731
-    # a spin-side operand: repeated over the bank where it has the batch axis, left to broadcast where it has not
-    side = lambda x: over(x) if (isinstance(x, Tensor) and x.ndim >= 1 and x.shape[0] == N and N > 1) else x  # noqa: E731
-    A, B = ab_rfgr(rf.flatten(0, 1), over(gr[0]) if gr.shape[0] == 1 else gr.flatten(0, 1), over(loc), Δf=side(Δf),
-                   b1Map=side(b1Map), γ_beff=side(γ_beff), T1=side(T1), T2=side(T2), γ=side(γ), dt=side(dt),
-                   consts=None if consts is None else {k: side(v) for k, v in consts.items()})
-    return sequence_signal(A.unflatten(0, (P, N)), B.unflatten(0, (P, N)), pulse=sched, n=n, Mi=Mi, phase=phase,
-                           rest=rest, T1=T1, T2=T2, Δf=Δf if Δf_rest is None else Δf_rest, rx=rx, demod=demod,
-                           return_last=return_last)
+    A, B, sched = _sequence_bank(rf, gr, loc, pulse, Δf=Δf, b1Map=b1Map, γ_beff=γ_beff, T1=T1, T2=T2, γ=γ, dt=dt,
+                                 consts=consts)
+    return sequence_signal(A, B, pulse=sched, n=n, Mi=Mi, phase=phase, rest=rest, T1=T1, T2=T2,
+                           Δf=Δf if Δf_rest is None else Δf_rest, rx=rx, demod=demod, return_last=return_last)
+
+
+def _period_length(n, sched, phase, N):
+    r"""``K`` of :func:`sequence_steadystate`: :func:`_sequence_length`, and a period needs a repetition."""
+    K = _sequence_length(n, sched, phase, N)
+    if K == 0:
+        raise ValueError("mrphy_amd: a period needs a repetition: K = 0")
+    return K
+
+
+class SequenceSteadyStateHIP(Function):
+    r"""``Mss = SequenceSteadyStateHIP.apply(A, B, phase, rest, T1, T2, Δf, K, sched, want)`` -- see
+    :func:`sequence_steadystate`.  ``A, B`` carry the bank axis in front and ``sched`` is the checked schedule as for
+    :class:`AbSequenceHIP`.  With ``want`` the forward (``mrphy_sequence_steadystate_fwd``) also leaves the composed
+    period ``per`` `(12, N·nM)` and the fp64 states ``ck`` every ``mrphy_train_signal_ck_every()`` repetitions of the
+    period started at ``Mss``, all the adjoint (``mrphy_sequence_steadystate_bwd``) reads besides the inputs; the
+    adjoint's scratch is ``λ``, the fp64 workspace of the bank's gradients and the per-wave sums of ``grad_phase`` and
+    ``grad_rest``, as :class:`SequenceSignalHIP`'s."""
+
+    ARGS = ('A', 'B', 'phase', 'rest', 'T1', 'T2', 'Δf', 'K', 'sched', 'want')
+
+    @staticmethod
+    def _operands(a, rs, T1, T2, Δf, cs, sched_dev):
+        r"""``AbSequenceHIP._args`` without ``Mi``: there is none."""
+        N, Nd, nM, code, keep, head, tail = AbSequenceHIP._args(a, rs, T1, T2, Δf, None, cs, sched_dev)
+        return N, Nd, nM, code, keep, head, tail[:11] + tail[14:]
+
+    @staticmethod
+    def forward(ctx, A, B, phase, rest, T1, T2, Δf, K, sched, want):
+        lib = _lib.require_library()
+        device = A.device
+        a, b = A.detach().contiguous(), B.detach().contiguous()
+        sched_dev = None if sched is None else sched.to(device)
+        rs = AbSequenceHIP._rest_table(a, rest, a.shape[1], K)
+        _, cs = _state_operands(a[0], None, phase)
+        N, Nd, nM, code, keep, head, ops = SequenceSteadyStateHIP._operands(a, rs, T1, T2, Δf, cs, sched_dev)
+        Mss = torch.empty_like(b[0])
+        per = ck = None
+        if want:
+            S = int(lib.mrphy_train_signal_ck_every())
+            per = torch.empty((12, N * nM), dtype=torch.float64, device=device)
+            ck = torch.empty((-(-K // S), N * nM, 3), dtype=torch.float64, device=device)
+        with torch.cuda.device(device):
+            rc = lib.mrphy_sequence_steadystate_fwd(code, a.data_ptr(), b.data_ptr(), *head, *ops, Mss.data_ptr(),
+                                                    _ptr(per), _ptr(ck), N, nM, K, _host.current_stream(device))
+        _lib.check(rc, 'mrphy_sequence_steadystate_fwd')
+        del keep
+        ctx.set_materialize_grads(False)
+        if want:
+            ctx.save_for_backward(a, b, cs, rs, sched_dev, per, ck)
+            ctx.consts = (T1, T2, Δf)
+            ctx.state = (phase, rest, K)
+        return Mss
+
+    @staticmethod
+    def backward(ctx, grad_Mss):
+        need = ctx.needs_input_grad
+        none = (None,) * len(SequenceSteadyStateHIP.ARGS)
+        if not any(need) or grad_Mss is None:
+            return none
+        consts = ctx.consts
+        phase, rest, K = ctx.state
+        need_c = [w and c is not None for w, c in zip(need[4:7], consts)]
+        need_φ, need_r = need[2] and phase is not None, need[3] and rest is not None
+        if not (need[0] or need[1] or need_φ or need_r or any(need_c)):
+            return none
+        lib = _lib.require_library()
+        a, b, cs, rs, sched_dev, per, ck = ctx.saved_tensors
+        device, dtype = a.device, a.dtype
+        N, Nd, nM, code, keep, head, ops = SequenceSteadyStateHIP._operands(a, rs, *consts, cs, sched_dev)
+        g = grad_Mss.detach().to(dtype).contiguous()
+        lam = torch.empty_like(g)
+        empty = N * nM == 0
+        f64 = torch.float64
+        o = _new_grads(empty, dtype, device, gA=need[0] and a.shape, gB=need[1] and b.shape)
+        # in fp64 whatever the data type, folded over those who share the operand, then rounded once: as
+        # SequenceSignalHIP.backward
+        o.update(_new_grads(empty, f64, device, gC=any(need_c) and (N,) + Nd + (3,), gφ=need_φ and (N, K),
+                            gr=need_r and (N, K)))
+        nQ = int(bool(need_φ)) + int(bool(need_r))
+        nbytes = int(lib.mrphy_sequence_signal_workspace(code, N, nM, K, nQ)) if nQ else 0
+        work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+        nbank = int(lib.mrphy_sequence_signal_bank_workspace(code, a.shape[0], N, nM)) if (need[0] or need[1]) else 0
+        bank = torch.empty(nbank // 8, dtype=f64, device=device) if nbank else None
+        with torch.cuda.device(device):
+            rc = lib.mrphy_sequence_steadystate_bwd(code, a.data_ptr(), b.data_ptr(), *head, g.data_ptr(), *ops,
+                                                    per.data_ptr(), ck.data_ptr(), lam.data_ptr(),
+                                                    *(_ptr(o[k]) for k in ('gA', 'gB', 'gC', 'gr', 'gφ')),
+                                                    work.data_ptr(), work.numel(), _ptr(bank), nbank, N, nM, K,
+                                                    _host.current_stream(device))
+        _lib.check(rc, 'mrphy_sequence_steadystate_bwd')
+        del keep, work, bank, lam
+        gφ = _fold_to_operand(o['gφ'], phase, f64) if need_φ else None
+        gr = _fold_repetition_sums(o['gr'], rest) if need_r else None
+        return (o['gA'], o['gB'], gφ, gr) + _fold_rest_consts(o['gC'], consts, need_c, N, Nd) + (None, None, None)
+
+
+@_host.half_via_float
+def sequence_steadystate(
+    A: Tensor, B: Tensor, *, pulse=None, n: Optional[int] = None, phase: Optional[Tensor] = None,
+    rest: Optional[Tensor] = None, T1: Optional[Tensor] = None, T2: Optional[Tensor] = None,
+    Δf: Optional[Tensor] = None
+) -> Tensor:
+    r"""The steady state of a sequence whose PERIOD is the ``K`` repetitions of :func:`ab_sequence` -- RF-spoiled SPGR,
+    phase-cycled bSSFP, interleaved flip angles or TRs (AFI, VFA pairs), a fingerprinting train played back to back, a
+    prepared train with a recovery delay.  Per spin, repetition ``k`` is :func:`ab_sequence`'s affine map
+
+        ``M⁻ = F_k M + f_k``,  ``M' = Rz(φ_k) [A_p Rz(-φ_k) M⁻ + B_p]``, ``p = pulse[k]``;
+
+    the ``K`` of them compose to ``Φ(M) = Ā M + b̄``, and
+
+        ``Mss = (I - Ā)⁻¹ b̄``.
+
+    ``Mss`` is the state right AFTER the last repetition of the period, which is also the state before the rest of
+    repetition 0: the convention of :func:`ab_steadystate`'s ``Mss`` and record ``K-1`` of :func:`ab_sequence`.
+    ``ab_sequence(A, B, ..., Mi=Mss)`` gives the states after each repetition of the steady period and
+    ``sequence_signal(A, B, ..., Mi=Mss)`` its signal, with gradients flowing through ``Mi`` into this function.
+
+    Usage:
+        ``Mss = sequence_steadystate(A, B, *, pulse, n, phase, rest, T1, T2, Δf)``
+
+    The operands ``A`` `(P, N, *Nd, xyz, 3)`, ``B`` `(P, N, *Nd, xyz)`, ``pulse``, ``n``, ``phase``, ``rest`` (`()`,
+    `(N ⊻ 1,)` or `(N ⊻ 1, K)`), ``T1``, ``T2``, ``Δf`` -- shapes, broadcasting, absences, the host-side check of the
+    schedule and its errors -- are exactly :func:`ab_sequence`'s.  There is no ``Mi``: a steady state has forgotten it.
+    ``K = 0`` is a ``ValueError``: a period needs a repetition.  Returns ``Mss`` `(N, *Nd, xyz)`.
+
+    The caller supplies one WHOLE period.  RF spoiling with the quadratic 117° increment,
+    ``φ_k = 117° · k (k + 1) / 2``: ``φ(k + 80) - φ(k) ≡ 0 (mod 360°)`` for every ``k`` and 40 is not a period, so the
+    period is 80 repetitions -- ``phase`` `(N ⊻ 1, 80)` -- and there is no one-pulse steady state.
+
+    One kernel (Ksqp, ``mrphy_sequence_steadystate_fwd``): one thread per spin carries four fp64 columns through
+    :func:`ab_sequence`'s repetition -- the affine column and the three columns of ``I`` through the linear part; nothing
+    is obtained as a difference -- and solves in :func:`ab_steadystate`'s cofactor form, all in fp64, rounded once.
+    Nothing of size ``K × spins`` is written.  Differentiable w.r.t. ``A``, ``B`` (the whole bank: an entry the schedule
+    never plays gets an exactly-zero gradient), ``phase``, ``rest`` (in the form given), ``T1``, ``T2`` and ``Δf``
+    (``mrphy_sequence_steadystate_bwd``: ``λ = (I - Ā)⁻ᵀ g`` per spin, then :func:`sequence_signal`'s sweep over the
+    period started at ``Mss``, from fp64 checkpoints the forward left when a gradient was wanted; deterministic).
+
+    The kernels compute in fp64 whatever the data type and round the outputs once; in fp32 ``Mss`` still inherits the
+    rounding of ``A``, ``B`` amplified by the condition number of ``I - Ā``, about ``1 / (1 - exp(-Σ_k rest_k / T1))``
+    for pulses that do not relax much.  A singular system (no relaxation in the pulses nor in the rests) gives non-finite
+    values: nothing synchronises with the host to detect it.
+
+    Out of scope: a schedule per batch entry; returning ``Ā, b̄``; a signal summed inside the same launch (that is
+    :func:`sequence_signal` with ``Mi=Mss``); a CPU path.
+    """
+    N, Nd = _train_spins(A, B, bank=True)
+    P = A.shape[0]
+    sched = _sequence_schedule(pulse, P)
+    K = _period_length(n, sched, phase, N)
+    if rest is not None and (rest.ndim > 2 or (rest.ndim == 1 and rest.shape[0] not in (1, N)) or
+                             (rest.ndim == 2 and (rest.shape[0] not in (1, N) or rest.shape[1] != K))):
+        raise ValueError(f"mrphy_amd: `rest` {tuple(rest.shape)} must be (), (N ⊻ 1,) or (N ⊻ 1, K) with N = {N}, K = {K}")
+    _check_train_operands(A, B, N, Nd, None, rest, T1, T2, Δf)
+    operands = (A, B, phase, rest, T1, T2, Δf)
+    want = torch.is_grad_enabled() and any(isinstance(x, Tensor) and x.requires_grad for x in operands)
+    return SequenceSteadyStateHIP.apply(A, B, phase, rest, T1, T2, Δf, K, sched, want)
+
+
+@_host.half_via_float
+def sequence_steadystate_rfgr(
+    rf: Tensor, gr: Tensor, loc: Tensor, *,
+    pulse=None, n: Optional[int] = None, phase: Optional[Tensor] = None,
+    rest: Optional[Tensor] = None, T1: Optional[Tensor] = None, T2: Optional[Tensor] = None,
+    Δf: Optional[Tensor] = None, b1Map: Optional[Tensor] = None, γ_beff: Tensor = γH,
+    γ: Tensor = γH, dt: Tensor = dt0, consts: Optional[dict] = None, Δf_rest: Optional[Tensor] = None
+) -> Tensor:
+    r"""The steady state of a period that plays a bank of pulses by a schedule, from ``rf`` `(P, N, xy, nT[, nCoils])`
+    and ``gr`` `(P ⊻ 1, N, xyz, nT)`: ONE :func:`ab_rfgr` call on the batch ``P·N`` exactly as :func:`sequence_rfgr`
+    makes it, its ``A, B`` viewed as the bank, then :func:`sequence_steadystate`.  Operands of the pulses as
+    :func:`ab_rfgr`, those of the period as :func:`sequence_steadystate`; ``rest``, ``T1`` and ``T2`` are required and
+    ``Δf_rest`` is as in :func:`steadystate_rfgr`.  Returns ``Mss`` `(N, *Nd, xyz)`, the state right after the last
+    repetition of the period.
+
+    Every route of :func:`ab_rfgr` (fused, split, composed; parallel transmit) serves it, so gradients reach ``rf``,
+    ``gr`` and every operand ``ab_rfgr`` differentiates, and ``phase, rest, T1, T2, Δf`` / ``Δf_rest`` through the period:
+    ``T1`` and ``T2`` receive the sum of the pulses' and the rests' paths.  :func:`ab_rfgr`'s limit on the batch is
+    inherited: ``P·N ≤ 65535``.  The fp32 note and what is out of scope as in :func:`sequence_steadystate`.
+    """
+    assert rest is not None and T1 is not None and T2 is not None, \
+        "sequence_steadystate_rfgr: a steady state needs relaxation -- `rest`, `T1` and `T2` are required"
+    if rf.ndim in (4, 5):                         # the schedule and the length before any work on the device
+        _period_length(n, _sequence_schedule(pulse, rf.shape[0]), phase, rf.shape[1])
+    A, B, sched = _sequence_bank(rf, gr, loc, pulse, Δf=Δf, b1Map=b1Map, γ_beff=γ_beff, T1=T1, T2=T2, γ=γ, dt=dt,
+                                 consts=consts)
+    return sequence_steadystate(A, B, pulse=sched, n=n, phase=phase, rest=rest, T1=T1, T2=T2,
+                                Δf=Δf if Δf_rest is None else Δf_rest)
