@@ -26,6 +26,15 @@ _BC = [_vp, _i64, _i64]            # broadcastable per-spin constant: ptr, strid
 # the operands of the fused family, rf .. E1m1 of mrphy_hip.h: rf, rf_sn, gr, gr_sn, loc, df, gamma, b1, g, E1, E2, E1m1
 _PULSE_OPS = [_vp, _i64, _vp, _i64, _vp] + _BC + _BC + [_vp] + _BC * 3 + [_vp]
 _FUSED = [_int, _vp] + _PULSE_OPS  # how the fused entry points begin: dtype, Mi (the adjoints: Mck), the operands
+# the train and the sequence family (ab_train .. sequence_steadystate), group by group as mrphy_hip.h declares them
+_AB = [_int, _vp, _vp]             # dtype, A, B
+_SEQ_HEAD = [_i64, _vp]            # P, pulse
+_REST = [_vp, _i64] + _BC * 3      # rest (the sequences: rs), its stride over n, T1, T2, df
+_PHASE = [_vp, _i64]               # cs, cs_sn
+_STATE = _BC + _PHASE              # Mi, Mi_sn, Mi_sm, cs, cs_sn
+_RX = [_vp, _i64]                  # rx, nRx
+_WORK = [_vp, _sz]                 # a workspace and its size in bytes
+_SIZES = [_i64] * 3 + [_vp]        # N, nM, K, stream
 
 # name -> (restype, argtypes); MUST list every function declared in include/mrphy_hip.h
 PROTOTYPES = {
@@ -101,31 +110,25 @@ PROTOTYPES = {
     'mrphy_ab_rfgr_mc_bwd': (_int, _FUSED + [_vp, _vp, _vp, _vp, _vp, _sz] + [_i64] * 4 + [_vp]),
     'mrphy_ab_steadystate_fwd': (_int, [_int, _vp, _vp, _vp, _i64] + _BC * 3 + [_vp, _i64, _i64, _vp]),
     'mrphy_ab_steadystate_bwd': (_int, [_int, _vp, _vp, _vp, _vp, _i64] + _BC * 3 + [_vp, _vp, _vp, _i64, _i64, _vp]),
-    'mrphy_ab_train_fwd': (_int, [_int, _vp, _vp, _vp, _i64] + _BC * 3 + _BC + [_vp, _i64, _vp] + [_i64] * 3 + [_vp]),
-    'mrphy_ab_train_bwd': (_int, [_int, _vp, _vp, _vp, _vp, _i64] + _BC * 3 + _BC + [_vp, _i64, _vp] + [_vp] * 5
-                           + [_i64] * 3 + [_vp]),
+    'mrphy_ab_train_fwd': (_int, _AB + _REST + _STATE + [_vp] + _SIZES),                           # ..., Mt
+    'mrphy_ab_train_bwd': (_int, _AB + [_vp] + _REST + _STATE + [_vp] + [_vp] * 5 + _SIZES),       # grad_Mt ..., Mt, 5 grads
     'mrphy_train_signal_ck_every': (_i64, []),
     'mrphy_train_signal_max_rx': (_int, [_int]),
     'mrphy_train_signal_workspace': (_sz, [_int] + [_i64] * 4),
-    'mrphy_train_signal_fwd': (_int, [_int, _vp, _vp, _vp, _i64] + _BC * 3 + _BC + [_vp, _i64] + [_vp, _i64]
-                               + [_vp, _vp, _vp, _vp, _sz] + [_i64] * 3 + [_vp]),
-    'mrphy_train_signal_bwd': (_int, [_int, _vp, _vp, _vp, _vp, _vp, _i64] + _BC * 3 + _BC + [_vp, _i64] + [_vp, _i64]
-                               + [_vp] + [_vp] * 6 + [_vp, _sz] + [_i64] * 3 + [_vp]),
+    'mrphy_train_signal_fwd': (_int, _AB + _REST + _STATE + _RX + [_vp] * 3 + _WORK + _SIZES),     # ..., sig, Mlast, ck
+    'mrphy_train_signal_bwd': (_int, _AB + [_vp] * 2 + _REST + _STATE + _RX + [_vp] + [_vp] * 6    # grad_sig, grad_Mlast
+                               + _WORK + _SIZES),                                                  # ..., ck, 6 grads
     'mrphy_ab_sequence_bwd_workspace': (_sz, [_int] + [_i64] * 3),
-    'mrphy_ab_sequence_fwd': (_int, [_int, _vp, _vp, _i64, _vp, _vp, _i64] + _BC * 3 + _BC + [_vp, _i64, _vp]
-                              + [_i64] * 3 + [_vp]),
-    'mrphy_ab_sequence_bwd': (_int, [_int, _vp, _vp, _i64, _vp, _vp, _vp, _i64] + _BC * 3 + _BC + [_vp, _i64, _vp]
-                              + [_vp] * 6 + [_vp, _sz] + [_i64] * 3 + [_vp]),
+    'mrphy_ab_sequence_fwd': (_int, _AB + _SEQ_HEAD + _REST + _STATE + [_vp] + _SIZES),
+    'mrphy_ab_sequence_bwd': (_int, _AB + _SEQ_HEAD + [_vp] + _REST + _STATE + [_vp] + [_vp] * 6 + _WORK + _SIZES),
     'mrphy_sequence_signal_workspace': (_sz, [_int] + [_i64] * 4),
     'mrphy_sequence_signal_bank_workspace': (_sz, [_int] + [_i64] * 3),
-    'mrphy_sequence_signal_fwd': (_int, [_int, _vp, _vp, _i64, _vp, _vp, _i64] + _BC * 3 + _BC + [_vp, _i64] + [_vp, _i64]
-                                  + [_vp, _vp, _vp, _vp, _sz] + [_i64] * 3 + [_vp]),
-    'mrphy_sequence_signal_bwd': (_int, [_int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64] + _BC * 3 + _BC + [_vp, _i64]
-                                  + [_vp, _i64] + [_vp] + [_vp] * 7 + [_vp, _sz] + [_vp, _sz] + [_i64] * 3 + [_vp]),
-    'mrphy_sequence_steadystate_fwd': (_int, [_int, _vp, _vp, _i64, _vp, _vp, _i64] + _BC * 3 + [_vp, _i64]
-                                       + [_vp, _vp, _vp] + [_i64] * 3 + [_vp]),
-    'mrphy_sequence_steadystate_bwd': (_int, [_int, _vp, _vp, _i64, _vp, _vp, _vp, _i64] + _BC * 3 + [_vp, _i64]
-                                       + [_vp, _vp, _vp] + [_vp] * 5 + [_vp, _sz] + [_vp, _sz] + [_i64] * 3 + [_vp]),
+    'mrphy_sequence_signal_fwd': (_int, _AB + _SEQ_HEAD + _REST + _STATE + _RX + [_vp] * 3 + _WORK + _SIZES),
+    'mrphy_sequence_signal_bwd': (_int, _AB + _SEQ_HEAD + [_vp] * 2 + _REST + _STATE + _RX + [_vp] + [_vp] * 7
+                                  + _WORK + _WORK + _SIZES),                                       # ..., work, bank
+    'mrphy_sequence_steadystate_fwd': (_int, _AB + _SEQ_HEAD + _REST + _PHASE + [_vp] * 3 + _SIZES),   # ..., Mss, per, ck
+    'mrphy_sequence_steadystate_bwd': (_int, _AB + _SEQ_HEAD + [_vp] + _REST + _PHASE + [_vp] * 3 + [_vp] * 5   # per, ck, lam
+                                       + _WORK + _WORK + _SIZES),
     'mrphy_blochsim_ab': (_int, [_int, _vp, _vp, _vp, _vp, _i64, _vp]),
     'mrphy_blochsim_ab_bwd': (_int, [_int, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
 }

@@ -260,3 +260,51 @@ __global__ __launch_bounds__(256) void k_ab_sequence_p2(const double* work, T* g
         for (int i = 0; i < 3; ++i) o[i] = T(w[(9 + i) * rows]);
     }
 }
+
+// Host: what the entry points of Ksq / Ksqb, Ksqs / Ksqsb (tu_sequence_signal.hip) and Ksqp (tu_sequence_steady.hip)
+// check alike, in train_check's order: dtype and sizes (P among them), the empty problem (0), null pointers and the
+// operand rules; `align` is what train_check found of misaligned pointers, to be returned after the caller's own null
+// checks.  `period`: the steady state's rules -- Mi is null, only a problem without spins is empty, and a period needs a
+// repetition.
+inline int seq_check(int dtype, const void* A, const void* B, int64_t P, const void* pulse, const void* rs,
+                     const void* T1, const void* T2, const void* df, const void* Mi, const void* cs, int64_t N,
+                     int64_t nM, int64_t K, bool period, bool& empty, int& align)
+{
+    align = 0;
+    const int e = train_check(dtype, A, B, rs, T1, T2, df, Mi, cs, N, nM, K, empty);
+    if (e == MRPHY_EINVAL || P < 1 || P > 65535) return MRPHY_EINVAL;           // blockIdx.y = p in the bank's second pass
+    if (period) empty = N * nM == 0;
+    if (empty) return 0;
+    if (period && K < 1) return MRPHY_EINVAL;                                   // a period needs a repetition
+    if (!pulse && P > 1) return MRPHY_EINVAL;
+    align = (e || !aligned_to(rs, sizeof(double)) || !aligned_to(pulse, sizeof(int32_t))) ? MRPHY_EALIGN : 0;
+    return 0;
+}
+
+// the operands A .. cs and the sizes, as every entry point of the sequence family passes them on
+inline void seq_fill(SeqArgs& q, const void* A, const void* B, int64_t P, const void* pulse, const void* rs,
+                     int64_t rs_sn, Bc T1, Bc T2, Bc df, const void* Mi, int64_t Mi_sn, int64_t Mi_sm, const void* cs,
+                     int64_t cs_sn, int64_t N, int64_t nM, int64_t K)
+{
+    q.A = A; q.B = B; q.P = P; q.pulse = reinterpret_cast<const int32_t*>(pulse);
+    q.rs = reinterpret_cast<const double*>(rs); q.rs_sn = rs_sn;
+    q.T1 = T1; q.T2 = T2; q.df = df;
+    q.Mi = Mi; q.Mi_sn = Mi_sn; q.Mi_sm = Mi_sm; q.cs = reinterpret_cast<const double*>(cs); q.cs_sn = cs_sn;
+    q.rows = N * nM; q.nM = nM; q.K = K;
+}
+
+// the fp64 workspace (P, 12, rows) of the bank's gradients
+inline size_t seq_bank_bytes(int64_t P, int64_t N, int64_t nM) { return (size_t)P * 12 * (size_t)(N * nM) * sizeof(double); }
+
+// the bank's second pass: the workspace rounded once into grad_A, grad_B (either may be null).  A template (W is double)
+// only so that a unit which never calls it -- tu_sequence_steady.hip -- does not instantiate the two kernels.
+template <typename W>
+int seq_launch_bank_p2(int dtype, const W* work, void* grad_A, void* grad_B, int64_t rows, int64_t P, hipStream_t st)
+{
+    const dim3 grid((unsigned)((rows + 255) / 256), (unsigned)P);
+    if (dtype == MRPHY_F32)
+        hipLaunchKernelGGL((k_ab_sequence_p2<float>), grid, dim3(256), 0, st, work, (float*)grad_A, (float*)grad_B, rows);
+    else
+        hipLaunchKernelGGL((k_ab_sequence_p2<double>), grid, dim3(256), 0, st, work, (double*)grad_A, (double*)grad_B, rows);
+    return launch_status();
+}

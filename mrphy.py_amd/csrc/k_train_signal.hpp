@@ -353,3 +353,40 @@ __global__ __launch_bounds__(TP2_K * TP2_G) void k_train_signal_p2(const double*
     if (nRx > 0) out[((n * 2 + (qn & 1)) * K + k) * nRx + (qn >> 1)] = T(sum);
     else         out[n * K + k] = T(sum);
 }
+
+// Host: what the entry points of Ktrs / Ktrsb and of Ksqs / Ksqsb (tu_sequence_signal.hip) share.
+// the coil capacity a launch with nRx coils runs at
+inline int trs_capacity(int64_t nRx) { return nRx <= 1 ? 1 : (nRx <= 2 ? 2 : (nRx <= 4 ? 4 : 8)); }
+
+// f(std::integral_constant<int, R>) for the capacity R = cap of a launch: the kernels take it as a template argument
+template <typename F>
+void trs_at_capacity(int cap, F f)
+{
+    switch (cap) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    default: f(std::integral_constant<int, 8>{}); break;
+    }
+}
+
+// what they check after train_check / seq_check: the coil count, the receive map and the workspace of the sums
+inline int trs_signal_check(int dtype, const void* rx, int64_t nRx, const void* work, size_t work_bytes, size_t need)
+{
+    if (nRx < 1 || nRx > trs_max_rx(tsize(dtype)) || (!rx && nRx != 1)) return MRPHY_EINVAL;
+    if (!aligned_to(rx, tsize(dtype)) || !aligned_to(work, sizeof(double))) return MRPHY_EALIGN;
+    if (need && (!work || work_bytes < need)) return work ? MRPHY_ENOSPC : MRPHY_EINVAL;
+    return 0;
+}
+
+// the sums of quantity qn of the workspace (Pw, N, nQ, K) into out: sig (N, 2, K, nRx) for nRx > 0 (all nQ = 2 nRx
+// quantities in one launch), else one quantity into out (N, K)
+template <typename T>
+int trs_launch_p2(const double* work, T* out, int64_t N, int64_t nQ, int64_t qn, int64_t K, int64_t Pw, int64_t nRx,
+                  hipStream_t st)
+{
+    const unsigned gy = nRx > 0 ? (unsigned)nQ : 1u;
+    hipLaunchKernelGGL((k_train_signal_p2<T>), dim3((unsigned)((K + TP2_K - 1) / TP2_K), gy, (unsigned)N),
+                       dim3(TP2_K * TP2_G), 0, st, work + qn * K, out, N, nQ, K, Pw, nRx);
+    return launch_status();
+}

@@ -7,35 +7,6 @@ namespace {
 #include "k_ab_train.hpp"
 #include "k_train_signal.hpp"
 #include "k_ab_sequence.hpp"
-
-inline size_t seq_workspace(int64_t P, int64_t N, int64_t nM) { return (size_t)P * 12 * (size_t)(N * nM) * sizeof(double); }
-
-// What both entry points check alike, in train_check's order: dtype and sizes (P among them), the empty problem (0),
-// null pointers and the operand rules; `align` is what train_check found of misaligned pointers, to be returned after
-// the caller's own null checks.
-int seq_check(int dtype, const void* A, const void* B, int64_t P, const void* pulse, const void* rs, const void* T1,
-              const void* T2, const void* df, const void* Mi, const void* cs, int64_t N, int64_t nM, int64_t K,
-              bool& empty, int& align)
-{
-    align = 0;
-    const int e = train_check(dtype, A, B, rs, T1, T2, df, Mi, cs, N, nM, K, empty);
-    if (e == MRPHY_EINVAL || P < 1 || P > 65535) return MRPHY_EINVAL;           // blockIdx.y = p in the second pass
-    if (empty) return 0;
-    if (!pulse && P > 1) return MRPHY_EINVAL;
-    align = (e || !aligned_to(rs, sizeof(double)) || !aligned_to(pulse, sizeof(int32_t))) ? MRPHY_EALIGN : 0;
-    return 0;
-}
-
-void seq_fill(SeqArgs& q, const void* A, const void* B, int64_t P, const void* pulse, const void* rs, int64_t rs_sn,
-              Bc T1, Bc T2, Bc df, const void* Mi, int64_t Mi_sn, int64_t Mi_sm, const void* cs, int64_t cs_sn,
-              int64_t N, int64_t nM, int64_t K)
-{
-    q.A = A; q.B = B; q.P = P; q.pulse = reinterpret_cast<const int32_t*>(pulse);
-    q.rs = reinterpret_cast<const double*>(rs); q.rs_sn = rs_sn;
-    q.T1 = T1; q.T2 = T2; q.df = df;
-    q.Mi = Mi; q.Mi_sn = Mi_sn; q.Mi_sm = Mi_sm; q.cs = reinterpret_cast<const double*>(cs); q.cs_sn = cs_sn;
-    q.rows = N * nM; q.nM = nM; q.K = K;
-}
 }  // namespace
 
 extern "C" {
@@ -43,7 +14,7 @@ extern "C" {
 size_t mrphy_ab_sequence_bwd_workspace(int dtype, int64_t P, int64_t N, int64_t nM)
 {
     if ((dtype != MRPHY_F32 && dtype != MRPHY_F64) || P <= 0 || N <= 0 || nM <= 0) return 0;
-    return seq_workspace(P, N, nM);
+    return seq_bank_bytes(P, N, nM);
 }
 
 int mrphy_ab_sequence_fwd(int dtype, const void* A, const void* B, int64_t P, const void* pulse, const void* rs,
@@ -53,7 +24,7 @@ int mrphy_ab_sequence_fwd(int dtype, const void* A, const void* B, int64_t P, co
                           void* stream)
 {
     bool empty; int align;
-    if (int e = seq_check(dtype, A, B, P, pulse, rs, T1, T2, df, Mi, cs, N, nM, K, empty, align)) return e;
+    if (int e = seq_check(dtype, A, B, P, pulse, rs, T1, T2, df, Mi, cs, N, nM, K, false, empty, align)) return e;
     if (empty) return 0;
     if (!Mt) return MRPHY_EINVAL;
     if (align || !aligned_to(Mt, tsize(dtype))) return MRPHY_EALIGN;
@@ -76,12 +47,12 @@ int mrphy_ab_sequence_bwd(int dtype, const void* A, const void* B, int64_t P, co
                           size_t work_bytes, int64_t N, int64_t nM, int64_t K, void* stream)
 {
     bool empty; int align;
-    if (int e = seq_check(dtype, A, B, P, pulse, rs, T1, T2, df, Mi, cs, N, nM, K, empty, align)) return e;
+    if (int e = seq_check(dtype, A, B, P, pulse, rs, T1, T2, df, Mi, cs, N, nM, K, false, empty, align)) return e;
     if (empty) return 0;
     if (!grad_Mt || !Mt || (!grad_A && !grad_B && !grad_consts && !grad_rest && !grad_Mi && !grad_phase))
         return MRPHY_EINVAL;
     const bool bank = grad_A || grad_B;
-    const size_t need = bank ? seq_workspace(P, N, nM) : 0;
+    const size_t need = bank ? seq_bank_bytes(P, N, nM) : 0;
     if (need && !work) return MRPHY_EINVAL;
     const size_t ts = tsize(dtype);
     if (align || !aligned_to(grad_Mt, ts) || !aligned_to(Mt, ts) || !aligned_to(grad_A, ts) || !aligned_to(grad_B, ts) ||
@@ -103,12 +74,7 @@ int mrphy_ab_sequence_bwd(int dtype, const void* A, const void* B, int64_t P, co
     else                    hipLaunchKernelGGL((k_ab_sequence_bwd<double>), grid, dim3(256), 0, st, q);
     if (int e = launch_status()) return e;
     if (!bank) return 0;
-    const dim3 grid2((unsigned)((q.rows + 255) / 256), (unsigned)P);
-    if (dtype == MRPHY_F32)
-        hipLaunchKernelGGL((k_ab_sequence_p2<float>), grid2, dim3(256), 0, st, q.work, (float*)grad_A, (float*)grad_B, q.rows);
-    else
-        hipLaunchKernelGGL((k_ab_sequence_p2<double>), grid2, dim3(256), 0, st, q.work, (double*)grad_A, (double*)grad_B, q.rows);
-    return launch_status();
+    return seq_launch_bank_p2(dtype, q.work, grad_A, grad_B, q.rows, P, st);
 }
 
 }  // extern "C"

@@ -11,73 +11,15 @@ namespace {
 #include "k_ab_sequence.hpp"
 #include "k_sequence_signal.hpp"
 
-inline int sqs_capacity(int64_t nRx) { return nRx <= 1 ? 1 : (nRx <= 2 ? 2 : (nRx <= 4 ? 4 : 8)); }
-inline size_t sqs_bank(int64_t P, int64_t N, int64_t nM) { return (size_t)P * 12 * (size_t)(N * nM) * sizeof(double); }
-
-// What both entry points check alike, as tu_ab_sequence.hip's seq_check: dtype and sizes (P among them), the empty
-// problem (0), null pointers and the operand rules; `align` is what was found of misaligned pointers, to be returned
-// after the caller's own null checks.
-int sqs_check(int dtype, const void* A, const void* B, int64_t P, const void* pulse, const void* rs, const void* T1,
-              const void* T2, const void* df, const void* Mi, const void* cs, int64_t N, int64_t nM, int64_t K,
-              bool& empty, int& align)
-{
-    align = 0;
-    const int e = train_check(dtype, A, B, rs, T1, T2, df, Mi, cs, N, nM, K, empty);
-    if (e == MRPHY_EINVAL || P < 1 || P > 65535) return MRPHY_EINVAL;           // blockIdx.y = p in the bank's second pass
-    if (empty) return 0;
-    if (!pulse && P > 1) return MRPHY_EINVAL;
-    align = (e || !aligned_to(rs, sizeof(double)) || !aligned_to(pulse, sizeof(int32_t))) ? MRPHY_EALIGN : 0;
-    return 0;
-}
-
-// the coil count, the receive map and the workspace of the sums, as tu_train_signal.hip's signal_check
-int sqs_signal_check(int dtype, const void* rx, int64_t nRx, const void* work, size_t work_bytes, size_t need)
-{
-    if (nRx < 1 || nRx > trs_max_rx(tsize(dtype)) || (!rx && nRx != 1)) return MRPHY_EINVAL;
-    if (!aligned_to(rx, tsize(dtype)) || !aligned_to(work, sizeof(double))) return MRPHY_EALIGN;
-    if (need && (!work || work_bytes < need)) return work ? MRPHY_ENOSPC : MRPHY_EINVAL;
-    return 0;
-}
-
-void sqs_fill(SeqArgs& q, const void* A, const void* B, int64_t P, const void* pulse, const void* rs, int64_t rs_sn,
-              Bc T1, Bc T2, Bc df, const void* Mi, int64_t Mi_sn, int64_t Mi_sm, const void* cs, int64_t cs_sn,
-              int64_t N, int64_t nM, int64_t K)
-{
-    q.A = A; q.B = B; q.P = P; q.pulse = reinterpret_cast<const int32_t*>(pulse);
-    q.rs = reinterpret_cast<const double*>(rs); q.rs_sn = rs_sn;
-    q.T1 = T1; q.T2 = T2; q.df = df;
-    q.Mi = Mi; q.Mi_sn = Mi_sn; q.Mi_sm = Mi_sm; q.cs = reinterpret_cast<const double*>(cs); q.cs_sn = cs_sn;
-    q.rows = N * nM; q.nM = nM; q.K = K;
-}
-
-// the sums of quantity qn of the workspace (Pw, N, nQ, K) into out: sig (N, 2, K, nRx) for nRx > 0 (all nQ = 2 nRx
-// quantities in one launch), else one quantity into out (N, K)
-template <typename T>
-int launch_p2(const double* work, T* out, int64_t N, int64_t nQ, int64_t qn, int64_t K, int64_t Pw, int64_t nRx,
-              hipStream_t st)
-{
-    const unsigned gy = nRx > 0 ? (unsigned)nQ : 1u;
-    hipLaunchKernelGGL((k_train_signal_p2<T>), dim3((unsigned)((K + TP2_K - 1) / TP2_K), gy, (unsigned)N),
-                       dim3(TP2_K * TP2_G), 0, st, work + qn * K, out, N, nQ, K, Pw, nRx);
-    return launch_status();
-}
-
 template <typename T, bool BWD>
 void launch_main(const SeqSigArgs& a, int cap, hipStream_t st)
 {
     const dim3 grid((unsigned)a.Pw, (unsigned)a.N);
-#define MRPHY_KSQS(R_)                                                                                       \
-    do {                                                                                                     \
-        if constexpr (BWD) hipLaunchKernelGGL((k_sequence_signal_bwd<T, R_>), grid, dim3(WAVE), 0, st, a);   \
-        else     hipLaunchKernelGGL((k_sequence_signal_fwd<T, R_>), grid, dim3(WAVE), 0, st, a);             \
-    } while (0)
-    switch (cap) {
-    case 1: MRPHY_KSQS(1); break;
-    case 2: MRPHY_KSQS(2); break;
-    case 4: MRPHY_KSQS(4); break;
-    default: MRPHY_KSQS(8); break;
-    }
-#undef MRPHY_KSQS
+    trs_at_capacity(cap, [&](auto r) {
+        constexpr int R = decltype(r)::value;
+        if constexpr (BWD) hipLaunchKernelGGL((k_sequence_signal_bwd<T, R>), grid, dim3(WAVE), 0, st, a);
+        else               hipLaunchKernelGGL((k_sequence_signal_fwd<T, R>), grid, dim3(WAVE), 0, st, a);
+    });
 }
 }  // namespace
 
@@ -85,14 +27,13 @@ extern "C" {
 
 size_t mrphy_sequence_signal_workspace(int dtype, int64_t N, int64_t nM, int64_t K, int64_t rows)
 {
-    if ((dtype != MRPHY_F32 && dtype != MRPHY_F64) || N <= 0 || nM <= 0 || K <= 0 || rows <= 0) return 0;
-    return trs_workspace(N, nM, K, rows);
+    return mrphy_train_signal_workspace(dtype, N, nM, K, rows);
 }
 
 size_t mrphy_sequence_signal_bank_workspace(int dtype, int64_t P, int64_t N, int64_t nM)
 {
     if ((dtype != MRPHY_F32 && dtype != MRPHY_F64) || P <= 0 || N <= 0 || nM <= 0) return 0;
-    return sqs_bank(P, N, nM);
+    return seq_bank_bytes(P, N, nM);
 }
 
 int mrphy_sequence_signal_fwd(int dtype, const void* A, const void* B, int64_t P, const void* pulse, const void* rs,
@@ -103,24 +44,24 @@ int mrphy_sequence_signal_fwd(int dtype, const void* A, const void* B, int64_t P
                               size_t work_bytes, int64_t N, int64_t nM, int64_t K, void* stream)
 {
     bool empty; int align;
-    if (int e = sqs_check(dtype, A, B, P, pulse, rs, T1, T2, df, Mi, cs, N, nM, K, empty, align)) return e;
+    if (int e = seq_check(dtype, A, B, P, pulse, rs, T1, T2, df, Mi, cs, N, nM, K, false, empty, align)) return e;
     if (empty) return 0;
     if (!sig) return MRPHY_EINVAL;
-    if (int e = sqs_signal_check(dtype, rx, nRx, work, work_bytes, trs_workspace(N, nM, K, 2 * (nRx > 0 ? nRx : 1))))
+    if (int e = trs_signal_check(dtype, rx, nRx, work, work_bytes, trs_workspace(N, nM, K, 2 * (nRx > 0 ? nRx : 1))))
         return e;
     const size_t ts = tsize(dtype);
     if (align || !aligned_to(sig, ts) || !aligned_to(Mlast, ts) || !aligned_to(ck, sizeof(double))) return MRPHY_EALIGN;
     SeqSigArgs a{};
-    sqs_fill(a.s, A, B, P, pulse, rs, rs_sn, Bc{T1, T1_sn, T1_sm}, Bc{T2, T2_sn, T2_sm}, Bc{df, df_sn, df_sm}, Mi, Mi_sn,
+    seq_fill(a.s, A, B, P, pulse, rs, rs_sn, Bc{T1, T1_sn, T1_sm}, Bc{T2, T2_sn, T2_sm}, Bc{df, df_sn, df_sm}, Mi, Mi_sn,
              Mi_sm, cs, cs_sn, N, nM, K);
     a.rx = rx; a.nRx = nRx; a.Mlast = Mlast; a.ck = reinterpret_cast<double*>(ck);
     a.sums = reinterpret_cast<double*>(work); a.qphi = a.qrest = -1; a.N = N; a.Pw = trs_waves(nM);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MRPHY_F32) launch_main<float, false>(a, sqs_capacity(nRx), st);
-    else                    launch_main<double, false>(a, sqs_capacity(nRx), st);
+    if (dtype == MRPHY_F32) launch_main<float, false>(a, trs_capacity(nRx), st);
+    else                    launch_main<double, false>(a, trs_capacity(nRx), st);
     if (int e = launch_status()) return e;
-    return dtype == MRPHY_F32 ? launch_p2<float>(a.sums, (float*)sig, N, 2 * nRx, 0, K, a.Pw, nRx, st)
-                              : launch_p2<double>(a.sums, (double*)sig, N, 2 * nRx, 0, K, a.Pw, nRx, st);
+    return dtype == MRPHY_F32 ? trs_launch_p2<float>(a.sums, (float*)sig, N, 2 * nRx, 0, K, a.Pw, nRx, st)
+                              : trs_launch_p2<double>(a.sums, (double*)sig, N, 2 * nRx, 0, K, a.Pw, nRx, st);
 }
 
 int mrphy_sequence_signal_bwd(int dtype, const void* A, const void* B, int64_t P, const void* pulse,
@@ -133,15 +74,15 @@ int mrphy_sequence_signal_bwd(int dtype, const void* A, const void* B, int64_t P
                               void* bank, size_t bank_bytes, int64_t N, int64_t nM, int64_t K, void* stream)
 {
     bool empty; int align;
-    if (int e = sqs_check(dtype, A, B, P, pulse, rs, T1, T2, df, Mi, cs, N, nM, K, empty, align)) return e;
+    if (int e = seq_check(dtype, A, B, P, pulse, rs, T1, T2, df, Mi, cs, N, nM, K, false, empty, align)) return e;
     if (empty) return 0;
     if ((!grad_sig && !grad_Mlast) || !ck ||
         (!grad_A && !grad_B && !grad_consts && !grad_rest && !grad_Mi && !grad_phase && !grad_rx))
         return MRPHY_EINVAL;
     const int nQ = (grad_phase ? 1 : 0) + (grad_rest ? 1 : 0);
-    if (int e = sqs_signal_check(dtype, rx, nRx, work, work_bytes, nQ ? trs_workspace(N, nM, K, nQ) : 0)) return e;
+    if (int e = trs_signal_check(dtype, rx, nRx, work, work_bytes, nQ ? trs_workspace(N, nM, K, nQ) : 0)) return e;
     const bool wantbank = grad_A || grad_B;
-    const size_t need = wantbank ? sqs_bank(P, N, nM) : 0;
+    const size_t need = wantbank ? seq_bank_bytes(P, N, nM) : 0;
     if (need && !bank) return MRPHY_EINVAL;
     const size_t ts = tsize(dtype);
     if (align || !aligned_to(grad_sig, sizeof(double)) || !aligned_to(grad_Mlast, ts) || !aligned_to(ck, sizeof(double)) ||
@@ -151,7 +92,7 @@ int mrphy_sequence_signal_bwd(int dtype, const void* A, const void* B, int64_t P
         return MRPHY_EALIGN;
     if (bank_bytes < need) return MRPHY_ENOSPC;
     SeqSigArgs a{};
-    sqs_fill(a.s, A, B, P, pulse, rs, rs_sn, Bc{T1, T1_sn, T1_sm}, Bc{T2, T2_sn, T2_sm}, Bc{df, df_sn, df_sm}, Mi, Mi_sn,
+    seq_fill(a.s, A, B, P, pulse, rs, rs_sn, Bc{T1, T1_sn, T1_sm}, Bc{T2, T2_sn, T2_sm}, Bc{df, df_sn, df_sm}, Mi, Mi_sn,
              Mi_sm, cs, cs_sn, N, nM, K);
     a.s.gC = grad_consts; a.s.gMi = grad_Mi;
     a.s.work = wantbank ? reinterpret_cast<double*>(bank) : nullptr;
@@ -163,21 +104,16 @@ int mrphy_sequence_signal_bwd(int dtype, const void* A, const void* B, int64_t P
     hipStream_t st = (hipStream_t)stream;
     if (wantbank)
         if (hipError_t e = hipMemsetAsync(bank, 0, need, st)) return (int)e;
-    if (dtype == MRPHY_F32) launch_main<float, true>(a, sqs_capacity(nRx), st);
-    else                    launch_main<double, true>(a, sqs_capacity(nRx), st);
+    if (dtype == MRPHY_F32) launch_main<float, true>(a, trs_capacity(nRx), st);
+    else                    launch_main<double, true>(a, trs_capacity(nRx), st);
     if (int e = launch_status()) return e;
     // the sums over the spins stay fp64 whatever the data type: the caller folds them further before rounding
     if (grad_phase)
-        if (int e = launch_p2<double>(a.sums, (double*)grad_phase, N, nQ, a.qphi, K, a.Pw, 0, st)) return e;
+        if (int e = trs_launch_p2<double>(a.sums, (double*)grad_phase, N, nQ, a.qphi, K, a.Pw, 0, st)) return e;
     if (grad_rest)
-        if (int e = launch_p2<double>(a.sums, (double*)grad_rest, N, nQ, a.qrest, K, a.Pw, 0, st)) return e;
+        if (int e = trs_launch_p2<double>(a.sums, (double*)grad_rest, N, nQ, a.qrest, K, a.Pw, 0, st)) return e;
     if (!wantbank) return 0;
-    const dim3 grid2((unsigned)((a.s.rows + 255) / 256), (unsigned)P);
-    if (dtype == MRPHY_F32)
-        hipLaunchKernelGGL((k_ab_sequence_p2<float>), grid2, dim3(256), 0, st, a.s.work, (float*)grad_A, (float*)grad_B, a.s.rows);
-    else
-        hipLaunchKernelGGL((k_ab_sequence_p2<double>), grid2, dim3(256), 0, st, a.s.work, (double*)grad_A, (double*)grad_B, a.s.rows);
-    return launch_status();
+    return seq_launch_bank_p2(dtype, a.s.work, grad_A, grad_B, a.s.rows, P, st);
 }
 
 }  // extern "C"

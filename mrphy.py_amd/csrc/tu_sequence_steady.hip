@@ -10,33 +10,6 @@ namespace {
 #include "k_train_signal.hpp"
 #include "k_ab_sequence.hpp"
 #include "k_sequence_steady.hpp"
-
-// What both entry points check alike, as tu_sequence_signal.hip's sqs_check (there is no Mi): dtype and sizes (P among
-// them), the problem without spins (0), a period without a repetition, null pointers and the operand rules; `align` is
-// what was found of misaligned pointers, to be returned after the caller's own null checks.
-int sqp_check(int dtype, const void* A, const void* B, int64_t P, const void* pulse, const void* rs, const void* T1,
-              const void* T2, const void* df, const void* cs, int64_t N, int64_t nM, int64_t K, bool& empty, int& align)
-{
-    align = 0;
-    const int e = train_check(dtype, A, B, rs, T1, T2, df, nullptr, cs, N, nM, K, empty);
-    if (e == MRPHY_EINVAL || P < 1 || P > 65535) return MRPHY_EINVAL;
-    empty = N * nM == 0;
-    if (empty) return 0;
-    if (K < 1) return MRPHY_EINVAL;                                             // a period needs a repetition
-    if (!pulse && P > 1) return MRPHY_EINVAL;
-    align = (e || !aligned_to(rs, sizeof(double)) || !aligned_to(pulse, sizeof(int32_t))) ? MRPHY_EALIGN : 0;
-    return 0;
-}
-
-void sqp_fill(SeqArgs& q, const void* A, const void* B, int64_t P, const void* pulse, const void* rs, int64_t rs_sn,
-              Bc T1, Bc T2, Bc df, const void* cs, int64_t cs_sn, int64_t N, int64_t nM, int64_t K)
-{
-    q.A = A; q.B = B; q.P = P; q.pulse = reinterpret_cast<const int32_t*>(pulse);
-    q.rs = reinterpret_cast<const double*>(rs); q.rs_sn = rs_sn;
-    q.T1 = T1; q.T2 = T2; q.df = df;
-    q.cs = reinterpret_cast<const double*>(cs); q.cs_sn = cs_sn;
-    q.rows = N * nM; q.nM = nM; q.K = K;
-}
 }  // namespace
 
 extern "C" {
@@ -48,14 +21,14 @@ int mrphy_sequence_steadystate_fwd(int dtype, const void* A, const void* B, int6
                                    int64_t N, int64_t nM, int64_t K, void* stream)
 {
     bool empty; int align;
-    if (int e = sqp_check(dtype, A, B, P, pulse, rs, T1, T2, df, cs, N, nM, K, empty, align)) return e;
+    if (int e = seq_check(dtype, A, B, P, pulse, rs, T1, T2, df, nullptr, cs, N, nM, K, true, empty, align)) return e;
     if (empty) return 0;
     if (!Mss) return MRPHY_EINVAL;
     if (align || !aligned_to(Mss, tsize(dtype)) || !aligned_to(per, sizeof(double)) || !aligned_to(ck, sizeof(double)))
         return MRPHY_EALIGN;
     SeqSteadyArgs a{};
-    sqp_fill(a.s, A, B, P, pulse, rs, rs_sn, Bc{T1, T1_sn, T1_sm}, Bc{T2, T2_sn, T2_sm}, Bc{df, df_sn, df_sm}, cs, cs_sn,
-             N, nM, K);
+    seq_fill(a.s, A, B, P, pulse, rs, rs_sn, Bc{T1, T1_sn, T1_sm}, Bc{T2, T2_sn, T2_sm}, Bc{df, df_sn, df_sm}, nullptr, 0,
+             0, cs, cs_sn, N, nM, K);
     a.Mss = Mss; a.per = reinterpret_cast<double*>(per); a.ck = reinterpret_cast<double*>(ck);
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)((nM + 255) / 256), (unsigned)N);
@@ -73,7 +46,7 @@ int mrphy_sequence_steadystate_bwd(int dtype, const void* A, const void* B, int6
                                    size_t bank_bytes, int64_t N, int64_t nM, int64_t K, void* stream)
 {
     bool empty; int align;
-    if (int e = sqp_check(dtype, A, B, P, pulse, rs, T1, T2, df, cs, N, nM, K, empty, align)) return e;
+    if (int e = seq_check(dtype, A, B, P, pulse, rs, T1, T2, df, nullptr, cs, N, nM, K, true, empty, align)) return e;
     if (empty) return 0;
     if (!grad_Mss || !per || !ck || !lam || (!grad_A && !grad_B && !grad_consts && !grad_rest && !grad_phase))
         return MRPHY_EINVAL;

@@ -7,42 +7,15 @@ namespace {
 #include "k_ab_train.hpp"
 #include "k_train_signal.hpp"
 
-// the coil capacity a launch with nRx coils runs at
-inline int trs_capacity(int64_t nRx) { return nRx <= 1 ? 1 : (nRx <= 2 ? 2 : (nRx <= 4 ? 4 : 8)); }
-
-// what both entry points check after train_check: the coil count, the receive map and the workspace
-int signal_check(int dtype, const void* rx, int64_t nRx, const void* work, size_t work_bytes, size_t need)
-{
-    if (nRx < 1 || nRx > trs_max_rx(tsize(dtype)) || (!rx && nRx != 1)) return MRPHY_EINVAL;
-    if (!aligned_to(rx, tsize(dtype)) || !aligned_to(work, sizeof(double))) return MRPHY_EALIGN;
-    if (need && (!work || work_bytes < need)) return work ? MRPHY_ENOSPC : MRPHY_EINVAL;
-    return 0;
-}
-
-template <typename T>
-int launch_p2(const double* work, void* out, int64_t N, int64_t nQ, int64_t K, int64_t P, int64_t nRx, hipStream_t st)
-{
-    hipLaunchKernelGGL((k_train_signal_p2<T>), dim3((unsigned)((K + TP2_K - 1) / TP2_K), (unsigned)nQ, (unsigned)N),
-                       dim3(TP2_K * TP2_G), 0, st, work, (T*)out, N, nQ, K, P, nRx);
-    return launch_status();
-}
-
 template <typename T, bool BWD>
 void launch_main(const TrainSigArgs& a, int cap, hipStream_t st)
 {
     const dim3 grid((unsigned)a.P, (unsigned)a.N);
-#define MRPHY_KTRS(R_)                                                                                     \
-    do {                                                                                                   \
-        if constexpr (BWD) hipLaunchKernelGGL((k_train_signal_bwd<T, R_>), grid, dim3(WAVE), 0, st, a);    \
-        else     hipLaunchKernelGGL((k_train_signal_fwd<T, R_>), grid, dim3(WAVE), 0, st, a);              \
-    } while (0)
-    switch (cap) {
-    case 1: MRPHY_KTRS(1); break;
-    case 2: MRPHY_KTRS(2); break;
-    case 4: MRPHY_KTRS(4); break;
-    default: MRPHY_KTRS(8); break;
-    }
-#undef MRPHY_KTRS
+    trs_at_capacity(cap, [&](auto r) {
+        constexpr int R = decltype(r)::value;
+        if constexpr (BWD) hipLaunchKernelGGL((k_train_signal_bwd<T, R>), grid, dim3(WAVE), 0, st, a);
+        else               hipLaunchKernelGGL((k_train_signal_fwd<T, R>), grid, dim3(WAVE), 0, st, a);
+    });
 }
 }  // namespace
 
@@ -71,7 +44,8 @@ int mrphy_train_signal_fwd(int dtype, const void* A, const void* B, const void* 
     if (int e = train_check(dtype, A, B, rest, T1, T2, df, Mi, cs, N, nM, K, empty)) return e;
     if (empty) return 0;
     if (!sig) return MRPHY_EINVAL;
-    if (int e = signal_check(dtype, rx, nRx, work, work_bytes, trs_workspace(N, nM, K, 2 * (nRx > 0 ? nRx : 1)))) return e;
+    if (int e = trs_signal_check(dtype, rx, nRx, work, work_bytes, trs_workspace(N, nM, K, 2 * (nRx > 0 ? nRx : 1))))
+        return e;
     const size_t ts = tsize(dtype);
     if (!aligned_to(sig, ts) || !aligned_to(Mlast, ts) || !aligned_to(ck, sizeof(double))) return MRPHY_EALIGN;
     TrainSigArgs a{};
@@ -83,8 +57,8 @@ int mrphy_train_signal_fwd(int dtype, const void* A, const void* B, const void* 
     if (dtype == MRPHY_F32) launch_main<float, false>(a, trs_capacity(nRx), st);
     else                    launch_main<double, false>(a, trs_capacity(nRx), st);
     if (int e = launch_status()) return e;
-    return dtype == MRPHY_F32 ? launch_p2<float>(a.work, sig, N, 2 * nRx, K, a.P, nRx, st)
-                              : launch_p2<double>(a.work, sig, N, 2 * nRx, K, a.P, nRx, st);
+    return dtype == MRPHY_F32 ? trs_launch_p2<float>(a.work, (float*)sig, N, 2 * nRx, 0, K, a.P, nRx, st)
+                              : trs_launch_p2<double>(a.work, (double*)sig, N, 2 * nRx, 0, K, a.P, nRx, st);
 }
 
 int mrphy_train_signal_bwd(int dtype, const void* A, const void* B, const void* grad_sig, const void* grad_Mlast,
@@ -101,7 +75,8 @@ int mrphy_train_signal_bwd(int dtype, const void* A, const void* B, const void* 
     if ((!grad_sig && !grad_Mlast) || !ck ||
         (!grad_A && !grad_B && !grad_consts && !grad_Mi && !grad_phase && !grad_rx))
         return MRPHY_EINVAL;
-    if (int e = signal_check(dtype, rx, nRx, work, work_bytes, grad_phase ? trs_workspace(N, nM, K, 1) : 0)) return e;
+    if (int e = trs_signal_check(dtype, rx, nRx, work, work_bytes, grad_phase ? trs_workspace(N, nM, K, 1) : 0))
+        return e;
     const size_t ts = tsize(dtype);
     if (!aligned_to(grad_sig, sizeof(double)) || !aligned_to(grad_Mlast, ts) || !aligned_to(ck, sizeof(double)) ||
         !aligned_to(grad_A, ts) || !aligned_to(grad_B, ts) || !aligned_to(grad_consts, sizeof(double)) ||
@@ -120,8 +95,8 @@ int mrphy_train_signal_bwd(int dtype, const void* A, const void* B, const void* 
     else                    launch_main<double, true>(a, trs_capacity(nRx), st);
     if (int e = launch_status()) return e;
     if (!grad_phase) return 0;
-    return dtype == MRPHY_F32 ? launch_p2<float>(a.work, grad_phase, N, 1, K, a.P, 0, st)
-                              : launch_p2<double>(a.work, grad_phase, N, 1, K, a.P, 0, st);
+    return dtype == MRPHY_F32 ? trs_launch_p2<float>(a.work, (float*)grad_phase, N, 1, 0, K, a.P, 0, st)
+                              : trs_launch_p2<double>(a.work, (double*)grad_phase, N, 1, 0, K, a.P, 0, st);
 }
 
 }  // extern "C"

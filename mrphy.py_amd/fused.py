@@ -870,16 +870,20 @@ def _rest_operands(A, rest, T1, T2, Δf):
     ``A`` `(N, *Nd, 3, 3)` and a rest period, and the tensors that keep their pointers alive."""
     device, dtype = A.device, A.dtype
     N, Nd = A.shape[0], tuple(A.shape[1:-2])
-    nul = _host.NULL_BC
     d = None
     if rest is not None:
         d = rest.detach().to(device=device, dtype=dtype).reshape(-1).contiguous()
         assert d.numel() in (1, N), "rest must be () or (N ⊻ 1,)"
-    mk = lambda c: None if c is None else _host.Bcast(c.detach(), N, Nd, dtype, device)  # noqa: E731
-    t1, t2, df = mk(T1), mk(T2), mk(Δf)
-    args = (None if d is None else d.data_ptr(), 1 if (d is not None and d.numel() == N and N > 1) else 0,
-            *(t1.args if t1 else nul), *(t2.args if t2 else nul), *(df.args if df else nul))
-    return N, Nd, prod(Nd), _code(dtype), (d, t1, t2, df), args
+    consts, cargs = _const_operands(A, T1, T2, Δf)
+    args = (None if d is None else d.data_ptr(), 1 if (d is not None and d.numel() == N and N > 1) else 0, *cargs)
+    return N, Nd, prod(Nd), _code(dtype), (d,) + consts, args
+
+
+def _const_operands(A, T1, T2, Δf):
+    r"""``(keep, args)``: the arguments ``T1 .. df_sm`` of the same entry points, null where an operand is absent."""
+    N, Nd = A.shape[0], tuple(A.shape[1:-2])
+    keep = tuple(None if c is None else _host.Bcast(c.detach(), N, Nd, A.dtype, A.device) for c in (T1, T2, Δf))
+    return keep, tuple(x for c in keep for x in (c.args if c else _host.NULL_BC))
 
 
 def _state_operands(a, Mi, phase):
@@ -900,12 +904,69 @@ def _state_operands(a, Mi, phase):
     return mi, cs
 
 
+def _over_n(x, N):
+    r"""The element stride of ``x`` `(N ⊻ 1, …)` over the batch: 0 where it broadcasts."""
+    return x.stride(0) if (x.shape[0] == N and N > 1) else 0
+
+
+def _phase_args(cs, N):
+    r"""The arguments ``cs, cs_sn`` of the train and the sequence family's entry points."""
+    return (None, 0) if cs is None else (cs.data_ptr(), _over_n(cs, N))
+
+
 def _state_args(mi, cs, N):
-    r"""The arguments ``Mi .. cs_sn`` of the train family's entry points: pointers and element strides, 0 where it
-    broadcasts."""
-    over_n = lambda x: x.stride(0) if (x.shape[0] == N and N > 1) else 0  # noqa: E731
-    return ((None, 0, 0) if mi is None else (mi.data_ptr(), over_n(mi), 3 if mi.shape[1] > 1 else 0)) + \
-           ((None, 0) if cs is None else (cs.data_ptr(), over_n(cs)))
+    r"""The arguments ``Mi .. cs_sn`` of the same entry points: pointers and element strides, 0 where it broadcasts."""
+    return ((None, 0, 0) if mi is None else (mi.data_ptr(), _over_n(mi, N), 3 if mi.shape[1] > 1 else 0)) + \
+        _phase_args(cs, N)
+
+
+def _rest_table(a, rest, K):
+    r"""``rs`` `(N ⊻ 1, K)` fp64 on the device, as the sequence family takes ``rest``: rounded to the data type (what
+    ``ab_train`` hands its kernel) and widened, a duration that does not change written out over ``K``; ``None`` without
+    a rest."""
+    if rest is None:
+        return None
+    d = rest.detach().to(device=a.device, dtype=a.dtype).double()
+    d = d.reshape(-1, 1) if d.ndim < 2 else d
+    return d.expand(d.shape[0], K).contiguous()
+
+
+def _sequence_args(a, rs, T1, T2, Δf, mi, cs, sched_dev, with_mi=True):
+    r"""``(N, Nd, nM, code, keep, head, tail)`` of the sequence family's entry points for the bank ``a``
+    `(P, N, *Nd, 3, 3)`: ``head`` is ``P, pulse`` and ``tail`` is ``rs .. cs_sn`` -- the rest table, the constants, the
+    state --, ``with_mi=False``: without ``Mi, Mi_sn, Mi_sm`` (a steady state has none)."""
+    N, Nd = a.shape[1], tuple(a.shape[2:-2])
+    keep, consts = _const_operands(a[0], T1, T2, Δf)
+    head = (a.shape[0], None if sched_dev is None else sched_dev.data_ptr())
+    table = (None, 0) if rs is None else (rs.data_ptr(), _over_n(rs, N))
+    state = _state_args(mi, cs, N) if with_mi else _phase_args(cs, N)
+    return N, Nd, prod(Nd), _code(a.dtype), keep, head, table + consts + state
+
+
+def _rx_operand(a, rx):
+    r"""``(r, nRx)``: ``rx`` as `(N, nM, 2, nRx)` contiguous in the data type of ``a`` `(N, *Nd, 3, 3)``; ``(None, 1)``
+    for ``None``."""
+    if rx is None:
+        return None, 1
+    N, Nd = a.shape[0], tuple(a.shape[1:-2])
+    r = rx.detach().to(device=a.device, dtype=a.dtype)
+    nRx = r.shape[-1] if r.ndim == len(Nd) + 3 else 1
+    r = r.expand((N,) + Nd + tuple(r.shape[1 + len(Nd):])).reshape(N, prod(Nd), 2, nRx).contiguous()
+    return r, nRx
+
+
+def _launch(name, device, *args):
+    r"""Entry point ``name`` of the library on ``device`` and its current stream: ``args`` (a tensor passes as its
+    address) followed by the stream; a non-zero return code raises."""
+    lib = _lib.require_library()
+    with torch.cuda.device(device):
+        rc = getattr(lib, name)(*(_ptr(x) for x in args), _host.current_stream(device))
+    _lib.check(rc, name)
+
+
+def _grad_wanted(*operands) -> bool:
+    r"""Whether a backward may follow: grad mode is on and an operand requires grad."""
+    return torch.is_grad_enabled() and any(isinstance(x, Tensor) and x.requires_grad for x in operands)
 
 
 def _train_spins(A, B, bank=False):
@@ -1093,17 +1154,12 @@ class AbTrainHIP(Function):
 
     @staticmethod
     def forward(ctx, A, B, Mi, phase, rest, T1, T2, Δf, K):
-        lib = _lib.require_library()
         device = A.device
         a, b = A.detach().contiguous(), B.detach().contiguous()
         N, Nd, nM, code, keep, args = _rest_operands(a, rest, T1, T2, Δf)
         mi, cs = _state_operands(a, Mi, phase)
-        sargs = _state_args(mi, cs, N)
         Mt = torch.empty((K,) + tuple(b.shape), dtype=b.dtype, device=device)
-        with torch.cuda.device(device):
-            rc = lib.mrphy_ab_train_fwd(code, a.data_ptr(), b.data_ptr(), *args, *sargs, Mt.data_ptr(), N, nM, K,
-                                        _host.current_stream(device))
-        _lib.check(rc, 'mrphy_ab_train_fwd')
+        _launch('mrphy_ab_train_fwd', device, code, a, b, *args, *_state_args(mi, cs, N), Mt, N, nM, K)
         del keep
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(a, b, Mt, mi, cs)
@@ -1120,19 +1176,14 @@ class AbTrainHIP(Function):
         need_mi, need_φ = need[2] and Mi is not None, need[3] and phase is not None
         if grad_Mt is None or not (need[0] or need[1] or need_mi or need_φ or any(need_c)):
             return (None,) * 9
-        lib = _lib.require_library()
         a, b, Mt, mi, cs = ctx.saved_tensors
         device, dtype = a.device, a.dtype
         N, Nd, nM, code, keep, args = _rest_operands(a, *consts)
-        sargs = _state_args(mi, cs, N)
         g = grad_Mt.detach().to(dtype).contiguous()
         o = _new_grads(N * nM * K == 0, dtype, device, gA=need[0] and a.shape, gB=need[1] and b.shape,
                        gC=any(need_c) and (N,) + Nd + (4,), gMi=need_mi and b.shape, gφ=need_φ and (K, N, nM))
-        with torch.cuda.device(device):
-            rc = lib.mrphy_ab_train_bwd(code, a.data_ptr(), b.data_ptr(), g.data_ptr(), *args, *sargs, Mt.data_ptr(),
-                                        *(_ptr(o[k]) for k in ('gA', 'gB', 'gC', 'gMi', 'gφ')), N, nM, K,
-                                        _host.current_stream(device))
-        _lib.check(rc, 'mrphy_ab_train_bwd')
+        _launch('mrphy_ab_train_bwd', device, code, a, b, g, *args, *_state_args(mi, cs, N), Mt,
+                *(o[k] for k in ('gA', 'gB', 'gC', 'gMi', 'gφ')), N, nM, K)
         del keep
         # grad_Mi is summed over those who share Mi in the data type; grad_phase over the spins in fp64
         return (o['gA'], o['gB'], _fold_to_operand(o['gMi'], Mi) if need_mi else None,
@@ -1240,38 +1291,15 @@ class AbSequenceHIP(Function):
     ``Mt`` itself, as :class:`AbTrainHIP`; its only scratch is the fp64 workspace of the bank's gradients."""
 
     @staticmethod
-    def _rest_table(a, rest, N, K):
-        r"""``rs`` `(N ⊻ 1, K)` fp64 on the device: ``rest`` rounded to the data type (what ``ab_train`` hands its
-        kernel) and widened, a duration that does not change written out over ``K``; ``None`` without a rest."""
-        if rest is None:
-            return None
-        d = rest.detach().to(device=a.device, dtype=a.dtype).double()
-        d = d.reshape(-1, 1) if d.ndim < 2 else d
-        return d.expand(d.shape[0], K).contiguous()
-
-    @staticmethod
-    def _args(a, rs, T1, T2, Δf, mi, cs, sched_dev):
-        r"""``(N, Nd, nM, code, keep, head, tail)``: ``P, pulse`` and ``rs .. cs_sn`` of the two entry points."""
-        N, Nd, nM, code, keep, args = _rest_operands(a[0], None, T1, T2, Δf)
-        head = (a.shape[0], None if sched_dev is None else sched_dev.data_ptr())
-        tail = (None if rs is None else rs.data_ptr(), rs.stride(0) if (rs is not None and rs.shape[0] == N and N > 1) else 0,
-                *args[2:], *_state_args(mi, cs, N))
-        return N, Nd, nM, code, keep, head, tail
-
-    @staticmethod
     def forward(ctx, A, B, Mi, phase, rest, T1, T2, Δf, K, sched):
-        lib = _lib.require_library()
         device = A.device
         a, b = A.detach().contiguous(), B.detach().contiguous()
         sched_dev = None if sched is None else sched.to(device)
-        rs = AbSequenceHIP._rest_table(a, rest, a.shape[1], K)
+        rs = _rest_table(a, rest, K)
         mi, cs = _state_operands(a[0], Mi, phase)
-        N, Nd, nM, code, keep, head, tail = AbSequenceHIP._args(a, rs, T1, T2, Δf, mi, cs, sched_dev)
+        N, Nd, nM, code, keep, head, tail = _sequence_args(a, rs, T1, T2, Δf, mi, cs, sched_dev)
         Mt = torch.empty((K,) + tuple(b.shape[1:]), dtype=b.dtype, device=device)
-        with torch.cuda.device(device):
-            rc = lib.mrphy_ab_sequence_fwd(code, a.data_ptr(), b.data_ptr(), *head, *tail, Mt.data_ptr(), N, nM, K,
-                                           _host.current_stream(device))
-        _lib.check(rc, 'mrphy_ab_sequence_fwd')
+        _launch('mrphy_ab_sequence_fwd', device, code, a, b, *head, *tail, Mt, N, nM, K)
         del keep
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(a, b, Mt, mi, cs, rs, sched_dev)
@@ -1291,18 +1319,15 @@ class AbSequenceHIP(Function):
         lib = _lib.require_library()
         a, b, Mt, mi, cs, rs, sched_dev = ctx.saved_tensors
         device, dtype = a.device, a.dtype
-        N, Nd, nM, code, keep, head, tail = AbSequenceHIP._args(a, rs, *consts, mi, cs, sched_dev)
+        N, Nd, nM, code, keep, head, tail = _sequence_args(a, rs, *consts, mi, cs, sched_dev)
         g = grad_Mt.detach().to(dtype).contiguous()
         o = _new_grads(N * nM * K == 0, dtype, device, gA=need[0] and a.shape, gB=need[1] and b.shape,
                        gC=any(need_c) and (N,) + Nd + (3,), gr=need_r and (K, N, nM), gMi=need_mi and b.shape[1:],
                        gφ=need_φ and (K, N, nM))
         nbytes = int(lib.mrphy_ab_sequence_bwd_workspace(code, a.shape[0], N, nM)) if (need[0] or need[1]) else 0
         work = torch.empty(nbytes // 8, dtype=torch.float64, device=device) if nbytes else None
-        with torch.cuda.device(device):
-            rc = lib.mrphy_ab_sequence_bwd(code, a.data_ptr(), b.data_ptr(), *head, g.data_ptr(), *tail, Mt.data_ptr(),
-                                           *(_ptr(o[k]) for k in ('gA', 'gB', 'gC', 'gr', 'gMi', 'gφ')), _ptr(work), nbytes,
-                                           N, nM, K, _host.current_stream(device))
-        _lib.check(rc, 'mrphy_ab_sequence_bwd')
+        _launch('mrphy_ab_sequence_bwd', device, code, a, b, *head, g, *tail, Mt,
+                *(o[k] for k in ('gA', 'gB', 'gC', 'gr', 'gMi', 'gφ')), work, nbytes, N, nM, K)
         del keep, work
         # grad_Mi is summed over those who share Mi in the data type; grad_phase and grad_rest over the spins in fp64
         return (o['gA'], o['gB'], _fold_to_operand(o['gMi'], Mi) if need_mi else None,
@@ -1360,6 +1385,39 @@ def _sequence_length(n, sched, phase, N):
     return given[0][1]
 
 
+def _period_length(n, sched, phase, N):
+    r"""``K`` of :func:`sequence_steadystate`: :func:`_sequence_length`, and a period needs a repetition."""
+    K = _sequence_length(n, sched, phase, N)
+    if K == 0:
+        raise ValueError("mrphy_amd: a period needs a repetition: K = 0")
+    return K
+
+
+def _check_rx(rx, N, Nd, nb):
+    r"""``rx`` of :func:`train_signal` and :func:`sequence_signal` against the spins; ``nb``: the dimensions of one
+    entry's ``B`` `(N, *Nd, xyz)`."""
+    if rx is not None:
+        if rx.ndim not in (nb, nb + 1) or rx.shape[0] not in (1, N) or \
+                tuple(rx.shape[1:nb]) != Nd + (2,) or (rx.ndim == nb + 1 and rx.shape[-1] < 1):
+            raise ValueError(f"mrphy_amd: `rx` {tuple(rx.shape)} must be (N ⊻ 1, *Nd, xy) or (N ⊻ 1, *Nd, xy, nRx) "
+                             f"for spins {(N,) + Nd}")
+
+
+def _sequence_operands(A, B, pulse, n, phase, rest, T1, T2, Δf, Mi, period=False, rx=None):
+    r"""``(N, Nd, sched, K)`` of :func:`ab_sequence`, :func:`sequence_signal` and :func:`sequence_steadystate`
+    (``period``: ``K = 0`` is refused), every operand checked in the order the three document: the bank's shapes, the
+    schedule, the length, ``rest``, ``rx`` where there is one, then what :func:`_check_train_operands` requires."""
+    N, Nd = _train_spins(A, B, bank=True)
+    sched = _sequence_schedule(pulse, A.shape[0])
+    K = (_period_length if period else _sequence_length)(n, sched, phase, N)
+    if rest is not None and (rest.ndim > 2 or (rest.ndim == 1 and rest.shape[0] not in (1, N)) or
+                             (rest.ndim == 2 and (rest.shape[0] not in (1, N) or rest.shape[1] != K))):
+        raise ValueError(f"mrphy_amd: `rest` {tuple(rest.shape)} must be (), (N ⊻ 1,) or (N ⊻ 1, K) with N = {N}, K = {K}")
+    _check_rx(rx, N, Nd, B.ndim - 1)
+    _check_train_operands(A, B, N, Nd, Mi, rest, T1, T2, Δf)
+    return N, Nd, sched, K
+
+
 @_host.half_via_float
 def ab_sequence(
     A: Tensor, B: Tensor, *, pulse=None, n: Optional[int] = None, Mi: Optional[Tensor] = None,
@@ -1407,14 +1465,7 @@ def ab_sequence(
     summed inside the kernel is :func:`sequence_signal`; the steady state of the ``K`` repetitions played as one period
     is :func:`sequence_steadystate`.
     """
-    N, Nd = _train_spins(A, B, bank=True)
-    P = A.shape[0]
-    sched = _sequence_schedule(pulse, P)
-    K = _sequence_length(n, sched, phase, N)
-    if rest is not None and (rest.ndim > 2 or (rest.ndim == 1 and rest.shape[0] not in (1, N)) or
-                             (rest.ndim == 2 and (rest.shape[0] not in (1, N) or rest.shape[1] != K))):
-        raise ValueError(f"mrphy_amd: `rest` {tuple(rest.shape)} must be (), (N ⊻ 1,) or (N ⊻ 1, K) with N = {N}, K = {K}")
-    _check_train_operands(A, B, N, Nd, Mi, rest, T1, T2, Δf)
+    *_, sched, K = _sequence_operands(A, B, pulse, n, phase, rest, T1, T2, Δf, Mi)
     return AbSequenceHIP.apply(A, B, Mi, phase, rest, T1, T2, Δf, K, sched).movedim(0, -2)
 
 
@@ -1462,6 +1513,51 @@ def sequence_rfgr(
                        Δf=Δf if Δf_rest is None else Δf_rest)
 
 
+def _signal_buffers(query, code, b, mi, rx, nRx, K, want_ckpt):
+    r"""``(sig, Mlast, ck, work)`` of a signal forward for the spins of ``b`` `(N, *Nd, 3)`: the samples (zeros for an
+    empty problem, which launches nothing), the last state (``Mi`` for ``K = 0``), the fp64 checkpoints if wanted and
+    the workspace of the sums as the query ``query`` of the library sizes it."""
+    lib = _lib.require_library()
+    device, dtype = b.device, b.dtype
+    N, Nd = b.shape[0], tuple(b.shape[1:-1])
+    nM = prod(Nd)
+    coils = () if rx is None or rx.ndim == b.ndim else (nRx,)
+    sig = (torch.zeros if N * nM * K == 0 else torch.empty)((N, 2, K, *coils), dtype=dtype, device=device)
+    Mlast = torch.empty_like(b)
+    if K == 0:                              # no repetition: the state is still Mi
+        Mlast.copy_(torch.tensor((0., 0., 1.), dtype=dtype, device=device) if mi is None else
+                    mi.reshape((mi.shape[0],) + (Nd if mi.shape[1] > 1 else (1,) * len(Nd)) + (3,)))
+    S = int(lib.mrphy_train_signal_ck_every())
+    ck = torch.empty((-(-K // S), N * nM, 3), dtype=torch.float64, device=device) if want_ckpt else None
+    nbytes = int(query(code, N, nM, K, 2 * nRx))
+    work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+    return sig, Mlast, ck, work
+
+
+def _signal_cotangents(grad_sig, grad_Mlast, N, K, nRx, dtype):
+    r"""``(gs, gl)`` as the signal adjoints read them: the cotangent of the signal as the wave-uniform table
+    `(N, K, nRx, 2)` in fp64, that of ``Mlast`` contiguous in the data type; ``None`` for an absent one."""
+    gs = None if grad_sig is None else \
+        grad_sig.detach().to(torch.float64).reshape(N, 2, K, nRx).permute(0, 2, 3, 1).contiguous()
+    gl = None if grad_Mlast is None else grad_Mlast.detach().to(dtype).contiguous()
+    return gs, gl
+
+
+def _fold_signal_grads(o, gl, K, N, Nd, Mi, phase, rx):
+    r"""``(gMi, gφ, grx)`` of a signal adjoint from its raw gradients ``o``: an operand shared by spins or batch entries
+    gets the sum over those who share it, accumulated in fp64 (``grad_phase`` is summed over the spins by the kernel);
+    ``None`` where ``o`` holds none.  Without a repetition ``Mlast`` is ``Mi``."""
+    f64 = torch.float64
+    gMi = gφ = grx = None
+    if o['gMi'] is not None:
+        gMi = _fold_to_operand(gl if (K == 0 and gl is not None) else o['gMi'], Mi, f64)
+    if o['gφ'] is not None:
+        gφ = _fold_to_operand(o['gφ'], phase, f64)
+    if o['grx'] is not None:
+        grx = _fold_to_operand(o['grx'].reshape((N,) + Nd + tuple(rx.shape[1 + len(Nd):])), rx, f64)
+    return gMi, gφ, grx
+
+
 class TrainSignalHIP(Function):
     r"""``sig, Mlast = TrainSignalHIP.apply(A, B, Mi, phase, rest, T1, T2, Δf, rx, K, want_ckpt)`` -- see
     :func:`train_signal`.  ``rx`` `(N ⊻ 1, *Nd, xy)` or `(N ⊻ 1, *Nd, xy, nRx)` with ``nRx`` up to
@@ -1473,41 +1569,15 @@ class TrainSignalHIP(Function):
     ARGS = ('A', 'B', 'Mi', 'phase', 'rest', 'T1', 'T2', 'Δf', 'rx', 'K', 'want_ckpt')
 
     @staticmethod
-    def _rx_operand(a, rx):
-        r"""``(r, nRx)``: ``rx`` as `(N, nM, 2, nRx)` contiguous in the data type; ``(None, 1)`` for ``None``."""
-        if rx is None:
-            return None, 1
-        N, Nd = a.shape[0], tuple(a.shape[1:-2])
-        r = rx.detach().to(device=a.device, dtype=a.dtype)
-        nRx = r.shape[-1] if r.ndim == len(Nd) + 3 else 1
-        r = r.expand((N,) + Nd + tuple(r.shape[1 + len(Nd):])).reshape(N, prod(Nd), 2, nRx).contiguous()
-        return r, nRx
-
-    @staticmethod
     def forward(ctx, A, B, Mi, phase, rest, T1, T2, Δf, rx, K, want_ckpt):
         lib = _lib.require_library()
-        device, dtype = A.device, A.dtype
         a, b = A.detach().contiguous(), B.detach().contiguous()
         N, Nd, nM, code, keep, args = _rest_operands(a, rest, T1, T2, Δf)
         mi, cs = _state_operands(a, Mi, phase)
-        sargs = _state_args(mi, cs, N)
-        r, nRx = TrainSignalHIP._rx_operand(a, rx)
-        coils = () if rx is None or rx.ndim == b.ndim else (nRx,)
-        empty = N * nM * K == 0
-        sig = (torch.zeros if empty else torch.empty)((N, 2, K, *coils), dtype=dtype, device=device)
-        Mlast = torch.empty_like(b)
-        if K == 0:                              # no repetition: the state is still Mi
-            Mlast.copy_(torch.tensor((0., 0., 1.), dtype=dtype, device=device) if mi is None else
-                        mi.reshape((mi.shape[0],) + (Nd if mi.shape[1] > 1 else (1,) * len(Nd)) + (3,)))
-        S = int(lib.mrphy_train_signal_ck_every())
-        ck = torch.empty((-(-K // S), N * nM, 3), dtype=torch.float64, device=device) if want_ckpt else None
-        nbytes = int(lib.mrphy_train_signal_workspace(code, N, nM, K, 2 * nRx))
-        work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
-        with torch.cuda.device(device):
-            rc = lib.mrphy_train_signal_fwd(code, a.data_ptr(), b.data_ptr(), *args, *sargs, _ptr(r), nRx,
-                                            sig.data_ptr(), Mlast.data_ptr(), _ptr(ck), work.data_ptr(), work.numel(),
-                                            N, nM, K, _host.current_stream(device))
-        _lib.check(rc, 'mrphy_train_signal_fwd')
+        r, nRx = _rx_operand(a, rx)
+        sig, Mlast, ck, work = _signal_buffers(lib.mrphy_train_signal_workspace, code, b, mi, rx, nRx, K, want_ckpt)
+        _launch('mrphy_train_signal_fwd', a.device, code, a, b, *args, *_state_args(mi, cs, N), r, nRx, sig, Mlast, ck,
+                work, work.numel(), N, nM, K)
         del keep
         ctx.set_materialize_grads(False)
         if want_ckpt:
@@ -1532,11 +1602,7 @@ class TrainSignalHIP(Function):
         a, b, mi, cs, r, ck = ctx.saved_tensors
         device, dtype = a.device, a.dtype
         N, Nd, nM, code, keep, args = _rest_operands(a, *consts)
-        sargs = _state_args(mi, cs, N)
-        # the cotangent of the signal as the wave-uniform table (N, K, nRx, 2) in fp64
-        gs = None if grad_sig is None else \
-            grad_sig.detach().to(torch.float64).reshape(N, 2, K, nRx).permute(0, 2, 3, 1).contiguous()
-        gl = None if grad_Mlast is None else grad_Mlast.detach().to(dtype).contiguous()
+        gs, gl = _signal_cotangents(grad_sig, grad_Mlast, N, K, nRx, dtype)
         empty = N * nM * K == 0
         o = _new_grads(empty, dtype, device, gA=need[0] and a.shape, gB=need[1] and b.shape, gMi=need_mi and b.shape,
                        gφ=need_φ and (N, K), grx=need_rx and (N, nM, 2, nRx))
@@ -1544,27 +1610,37 @@ class TrainSignalHIP(Function):
         o.update(_new_grads(empty, torch.float64, device, gC=any(need_c) and (N,) + Nd + (4,)))
         nbytes = int(lib.mrphy_train_signal_workspace(code, N, nM, K, 1)) if need_φ else 0
         work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
-        with torch.cuda.device(device):
-            rc = lib.mrphy_train_signal_bwd(code, a.data_ptr(), b.data_ptr(), _ptr(gs), _ptr(gl), *args, *sargs, _ptr(r),
-                                            nRx, ck.data_ptr(), *(_ptr(o[k]) for k in ('gA', 'gB', 'gC', 'gMi', 'gφ', 'grx')),
-                                            work.data_ptr(), work.numel(), N, nM, K, _host.current_stream(device))
-        _lib.check(rc, 'mrphy_train_signal_bwd')
+        _launch('mrphy_train_signal_bwd', device, code, a, b, gs, gl, *args, *_state_args(mi, cs, N), r, nRx, ck,
+                *(o[k] for k in ('gA', 'gB', 'gC', 'gMi', 'gφ', 'grx')), work, work.numel(), N, nM, K)
         del keep
-        # an operand shared by spins or batch entries gets the sum over those who share it, accumulated in fp64; grad_phase
-        # is summed over the spins by the kernel
-        f64 = torch.float64
-        gMi = gφ = grx = None
-        if need_mi:                             # no repetition: Mlast is Mi
-            gMi = _fold_to_operand(gl if (K == 0 and gl is not None) else o['gMi'], Mi, f64)
-        if need_φ:
-            gφ = _fold_to_operand(o['gφ'], phase, f64)
-        if need_rx:
-            grx = _fold_to_operand(o['grx'].reshape((N,) + Nd + tuple(rx.shape[1 + len(Nd):])), rx, f64)
+        gMi, gφ, grx = _fold_signal_grads(o, gl, K, N, Nd, Mi, phase, rx)
         return (o['gA'], o['gB'], gMi, gφ) + _fold_rest_consts(o['gC'], consts, need_c, N, Nd) + (grx, None, None)
 
 
 def _train_signal_max_rx(dtype) -> int:
     return int(_lib.require_library().mrphy_train_signal_max_rx(_code(dtype)))
+
+
+def _signal_by_coil_blocks(Fn, head, rx, tail, nb):
+    r"""``sig, Mlast`` of ``Fn.apply(*head, rx, *tail)`` for any number of coils: above the capacity of a launch, blocks
+    of that many coils, one simulation each -- a coil's sums do not depend on the other coils -- with the samples
+    joined along the coil axis and ``Mlast`` of the first block.  ``nb``: the dimensions of one entry's ``B``."""
+    cap = _train_signal_max_rx(head[0].dtype)
+    if rx is None or rx.ndim != nb + 1 or rx.shape[-1] <= cap:
+        return Fn.apply(*head, rx, *tail)
+    parts = [Fn.apply(*head, rx[..., c:c + cap], *tail) for c in range(0, rx.shape[-1], cap)]
+    return torch.cat([p[0] for p in parts], dim=-1), parts[0][1]
+
+
+def _demodulate(sig, phase):
+    r"""``sig`` `(N, xy, K[, nRx])` with sample ``k`` multiplied by ``exp(-iφ_k)``, formed in fp64 and rounded once;
+    ``sig`` itself without a ``phase``."""
+    if phase is None:
+        return sig
+    φ = phase.to(device=sig.device, dtype=torch.float64).reshape(phase.shape + (1,) * (sig.ndim - 3))
+    c, s = torch.cos(φ), torch.sin(φ)
+    s0, s1 = sig[:, 0].to(torch.float64), sig[:, 1].to(torch.float64)
+    return torch.stack((s0 * c + s1 * s, s1 * c - s0 * s), dim=1).to(sig.dtype)
 
 
 @_host.half_via_float
@@ -1614,27 +1690,12 @@ def train_signal(
     """
     N, Nd = _train_spins(A, B)
     K = _train_length(n, phase, N)
-    if rx is not None:
-        if rx.ndim not in (B.ndim, B.ndim + 1) or rx.shape[0] not in (1, N) or \
-                tuple(rx.shape[1:B.ndim]) != Nd + (2,) or (rx.ndim == B.ndim + 1 and rx.shape[-1] < 1):
-            raise ValueError(f"mrphy_amd: `rx` {tuple(rx.shape)} must be (N ⊻ 1, *Nd, xy) or (N ⊻ 1, *Nd, xy, nRx) "
-                             f"for spins {(N,) + Nd}")
+    _check_rx(rx, N, Nd, B.ndim)
     _check_train_operands(A, B, N, Nd, Mi, rest, T1, T2, Δf)
-    operands = (A, B, Mi, phase, rest, T1, T2, Δf, rx)
-    want = torch.is_grad_enabled() and any(isinstance(x, Tensor) and x.requires_grad for x in operands)
-    cap = _train_signal_max_rx(A.dtype)
-    if rx is not None and rx.ndim == B.ndim + 1 and rx.shape[-1] > cap:
-        # blocks of `cap` coils, one simulation each; a coil's sums do not depend on the other coils
-        parts = [TrainSignalHIP.apply(A, B, Mi, phase, rest, T1, T2, Δf, rx[..., c:c + cap], K, want)
-                 for c in range(0, rx.shape[-1], cap)]
-        sig, Mlast = torch.cat([p[0] for p in parts], dim=-1), parts[0][1]
-    else:
-        sig, Mlast = TrainSignalHIP.apply(A, B, Mi, phase, rest, T1, T2, Δf, rx, K, want)
-    if demod and phase is not None:
-        φ = phase.to(device=sig.device, dtype=torch.float64).reshape(phase.shape + (1,) * (sig.ndim - 3))
-        c, s = torch.cos(φ), torch.sin(φ)
-        s0, s1 = sig[:, 0].to(torch.float64), sig[:, 1].to(torch.float64)
-        sig = torch.stack((s0 * c + s1 * s, s1 * c - s0 * s), dim=1).to(sig.dtype)
+    head = (A, B, Mi, phase, rest, T1, T2, Δf)
+    sig, Mlast = _signal_by_coil_blocks(TrainSignalHIP, head, rx, (K, _grad_wanted(*head, rx)), B.ndim)
+    if demod:
+        sig = _demodulate(sig, phase)
     return (sig, Mlast) if return_last else sig
 
 
@@ -1671,6 +1732,31 @@ def _fold_repetition_sums(g, x):
     return g.reshape(x.shape).to(device=x.device, dtype=x.dtype)
 
 
+def _sweep_scratch(code, a, N, Nd, nM, K, empty, need_c, need_φ, need_r, need_bank):
+    r"""``(o, work, bank, nbank)``: what a launch of Ksqsb's sweep (``mrphy_sequence_signal_bwd``, and
+    ``mrphy_sequence_steadystate_bwd`` which hands over to it) needs besides its outputs in the data type.  ``o`` holds
+    ``gC`` per spin and ``gφ``, ``gr`` summed over the spins by the kernel, in fp64 whatever the data type (``None`` where
+    not needed); ``work`` is the workspace of those sums, ``bank`` the fp64 workspace of ``nbank`` bytes of the gradients
+    of the bank ``a`` (``None``, 0 without ``need_bank``)."""
+    lib = _lib.require_library()
+    device, f64 = a.device, torch.float64
+    o = _new_grads(empty, f64, device, gC=any(need_c) and (N,) + Nd + (3,), gφ=need_φ and (N, K), gr=need_r and (N, K))
+    nQ = int(bool(need_φ)) + int(bool(need_r))
+    nbytes = int(lib.mrphy_sequence_signal_workspace(code, N, nM, K, nQ)) if nQ else 0
+    work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+    nbank = int(lib.mrphy_sequence_signal_bank_workspace(code, a.shape[0], N, nM)) if need_bank else 0
+    bank = torch.empty(nbank // 8, dtype=f64, device=device) if nbank else None
+    return o, work, bank, nbank
+
+
+def _fold_sweep_grads(o, rest, consts, need_c, N, Nd):
+    r"""``(gr, (gT1, gT2, gΔf))`` from :func:`_sweep_scratch`'s ``gr`` and ``gC``: each folded in fp64 over those who
+    share the operand, then rounded once; ``None`` where ``o`` holds none.  (``gφ`` folds as any sum does:
+    :func:`_fold_to_operand`.)"""
+    gr = None if o['gr'] is None else _fold_repetition_sums(o['gr'], rest)
+    return gr, _fold_rest_consts(o['gC'], consts, need_c, N, Nd)
+
+
 class SequenceSignalHIP(Function):
     r"""``sig, Mlast = SequenceSignalHIP.apply(A, B, Mi, phase, rest, T1, T2, Δf, rx, K, sched, want_ckpt)`` -- see
     :func:`sequence_signal`.  ``A, B`` carry the bank axis in front and ``sched`` is the checked schedule as for
@@ -1684,29 +1770,16 @@ class SequenceSignalHIP(Function):
     @staticmethod
     def forward(ctx, A, B, Mi, phase, rest, T1, T2, Δf, rx, K, sched, want_ckpt):
         lib = _lib.require_library()
-        device, dtype = A.device, A.dtype
+        device = A.device
         a, b = A.detach().contiguous(), B.detach().contiguous()
         sched_dev = None if sched is None else sched.to(device)
-        rs = AbSequenceHIP._rest_table(a, rest, a.shape[1], K)
+        rs = _rest_table(a, rest, K)
         mi, cs = _state_operands(a[0], Mi, phase)
-        N, Nd, nM, code, keep, head, tail = AbSequenceHIP._args(a, rs, T1, T2, Δf, mi, cs, sched_dev)
-        r, nRx = TrainSignalHIP._rx_operand(a[0], rx)
-        coils = () if rx is None or rx.ndim == b.ndim - 1 else (nRx,)
-        empty = N * nM * K == 0
-        sig = (torch.zeros if empty else torch.empty)((N, 2, K, *coils), dtype=dtype, device=device)
-        Mlast = torch.empty_like(b[0])
-        if K == 0:                              # no repetition: the state is still Mi
-            Mlast.copy_(torch.tensor((0., 0., 1.), dtype=dtype, device=device) if mi is None else
-                        mi.reshape((mi.shape[0],) + (Nd if mi.shape[1] > 1 else (1,) * len(Nd)) + (3,)))
-        S = int(lib.mrphy_train_signal_ck_every())
-        ck = torch.empty((-(-K // S), N * nM, 3), dtype=torch.float64, device=device) if want_ckpt else None
-        nbytes = int(lib.mrphy_sequence_signal_workspace(code, N, nM, K, 2 * nRx))
-        work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
-        with torch.cuda.device(device):
-            rc = lib.mrphy_sequence_signal_fwd(code, a.data_ptr(), b.data_ptr(), *head, *tail, _ptr(r), nRx,
-                                               sig.data_ptr(), Mlast.data_ptr(), _ptr(ck), work.data_ptr(), work.numel(),
-                                               N, nM, K, _host.current_stream(device))
-        _lib.check(rc, 'mrphy_sequence_signal_fwd')
+        N, Nd, nM, code, keep, head, tail = _sequence_args(a, rs, T1, T2, Δf, mi, cs, sched_dev)
+        r, nRx = _rx_operand(a[0], rx)
+        sig, Mlast, ck, work = _signal_buffers(lib.mrphy_sequence_signal_workspace, code, b[0], mi, rx, nRx, K, want_ckpt)
+        _launch('mrphy_sequence_signal_fwd', device, code, a, b, *head, *tail, r, nRx, sig, Mlast, ck, work, work.numel(),
+                N, nM, K)
         del keep
         ctx.set_materialize_grads(False)
         if want_ckpt:
@@ -1728,45 +1801,21 @@ class SequenceSignalHIP(Function):
         need_rx = need[8] and rx is not None
         if not (need[0] or need[1] or need_mi or need_φ or need_r or need_rx or any(need_c)):
             return none
-        lib = _lib.require_library()
         a, b, mi, cs, rs, sched_dev, r, ck = ctx.saved_tensors
         device, dtype = a.device, a.dtype
-        N, Nd, nM, code, keep, head, tail = AbSequenceHIP._args(a, rs, *consts, mi, cs, sched_dev)
-        # the cotangent of the signal as the wave-uniform table (N, K, nRx, 2) in fp64
-        gs = None if grad_sig is None else \
-            grad_sig.detach().to(torch.float64).reshape(N, 2, K, nRx).permute(0, 2, 3, 1).contiguous()
-        gl = None if grad_Mlast is None else grad_Mlast.detach().to(dtype).contiguous()
+        N, Nd, nM, code, keep, head, tail = _sequence_args(a, rs, *consts, mi, cs, sched_dev)
+        gs, gl = _signal_cotangents(grad_sig, grad_Mlast, N, K, nRx, dtype)
         empty = N * nM * K == 0
-        f64 = torch.float64
         o = _new_grads(empty, dtype, device, gA=need[0] and a.shape, gB=need[1] and b.shape,
                        gMi=need_mi and b.shape[1:], grx=need_rx and (N, nM, 2, nRx))
-        # in fp64 whatever the data type: per spin (gC) or summed over the spins by the kernel (gφ, gr), folded over
-        # those who share the operand, then rounded once
-        o.update(_new_grads(empty, f64, device, gC=any(need_c) and (N,) + Nd + (3,), gφ=need_φ and (N, K),
-                            gr=need_r and (N, K)))
-        nQ = int(bool(need_φ)) + int(bool(need_r))
-        nbytes = int(lib.mrphy_sequence_signal_workspace(code, N, nM, K, nQ)) if nQ else 0
-        work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
-        nbank = int(lib.mrphy_sequence_signal_bank_workspace(code, a.shape[0], N, nM)) if (need[0] or need[1]) else 0
-        bank = torch.empty(nbank // 8, dtype=f64, device=device) if nbank else None
-        with torch.cuda.device(device):
-            rc = lib.mrphy_sequence_signal_bwd(code, a.data_ptr(), b.data_ptr(), *head, _ptr(gs), _ptr(gl), *tail, _ptr(r),
-                                               nRx, ck.data_ptr(),
-                                               *(_ptr(o[k]) for k in ('gA', 'gB', 'gC', 'gr', 'gMi', 'gφ', 'grx')),
-                                               work.data_ptr(), work.numel(), _ptr(bank), nbank, N, nM, K,
-                                               _host.current_stream(device))
-        _lib.check(rc, 'mrphy_sequence_signal_bwd')
+        o64, work, bank, nbank = _sweep_scratch(code, a, N, Nd, nM, K, empty, need_c, need_φ, need_r, need[0] or need[1])
+        o.update(o64)
+        _launch('mrphy_sequence_signal_bwd', device, code, a, b, *head, gs, gl, *tail, r, nRx, ck,
+                *(o[k] for k in ('gA', 'gB', 'gC', 'gr', 'gMi', 'gφ', 'grx')), work, work.numel(), bank, nbank, N, nM, K)
         del keep, work, bank
-        gMi = gφ = gr = grx = None
-        if need_mi:                             # no repetition: Mlast is Mi
-            gMi = _fold_to_operand(gl if (K == 0 and gl is not None) else o['gMi'], Mi, f64)
-        if need_φ:
-            gφ = _fold_to_operand(o['gφ'], phase, f64)
-        if need_r:
-            gr = _fold_repetition_sums(o['gr'], rest)
-        if need_rx:
-            grx = _fold_to_operand(o['grx'].reshape((N,) + Nd + tuple(rx.shape[1 + len(Nd):])), rx, f64)
-        return (o['gA'], o['gB'], gMi, gφ, gr) + _fold_rest_consts(o['gC'], consts, need_c, N, Nd) + (grx, None, None, None)
+        gMi, gφ, grx = _fold_signal_grads(o, gl, K, N, Nd, Mi, phase, rx)
+        gr, gconsts = _fold_sweep_grads(o, rest, consts, need_c, N, Nd)
+        return (o['gA'], o['gB'], gMi, gφ, gr) + gconsts + (grx, None, None, None)
 
 
 @_host.half_via_float
@@ -1812,35 +1861,11 @@ def sequence_signal(
     ``rest`` per spin; a CPU path.  The signal of the steady period is this function with
     ``Mi=sequence_steadystate(...)``.
     """
-    N, Nd = _train_spins(A, B, bank=True)
-    P = A.shape[0]
-    sched = _sequence_schedule(pulse, P)
-    K = _sequence_length(n, sched, phase, N)
-    if rest is not None and (rest.ndim > 2 or (rest.ndim == 1 and rest.shape[0] not in (1, N)) or
-                             (rest.ndim == 2 and (rest.shape[0] not in (1, N) or rest.shape[1] != K))):
-        raise ValueError(f"mrphy_amd: `rest` {tuple(rest.shape)} must be (), (N ⊻ 1,) or (N ⊻ 1, K) with N = {N}, K = {K}")
-    nb = B.ndim - 1                                   # dimensions of one entry's B: (N, *Nd, xyz)
-    if rx is not None:
-        if rx.ndim not in (nb, nb + 1) or rx.shape[0] not in (1, N) or \
-                tuple(rx.shape[1:nb]) != Nd + (2,) or (rx.ndim == nb + 1 and rx.shape[-1] < 1):
-            raise ValueError(f"mrphy_amd: `rx` {tuple(rx.shape)} must be (N ⊻ 1, *Nd, xy) or (N ⊻ 1, *Nd, xy, nRx) "
-                             f"for spins {(N,) + Nd}")
-    _check_train_operands(A, B, N, Nd, Mi, rest, T1, T2, Δf)
-    operands = (A, B, Mi, phase, rest, T1, T2, Δf, rx)
-    want = torch.is_grad_enabled() and any(isinstance(x, Tensor) and x.requires_grad for x in operands)
-    cap = _train_signal_max_rx(A.dtype)
-    if rx is not None and rx.ndim == nb + 1 and rx.shape[-1] > cap:
-        # blocks of `cap` coils, one simulation each; a coil's sums do not depend on the other coils
-        parts = [SequenceSignalHIP.apply(A, B, Mi, phase, rest, T1, T2, Δf, rx[..., c:c + cap], K, sched, want)
-                 for c in range(0, rx.shape[-1], cap)]
-        sig, Mlast = torch.cat([p[0] for p in parts], dim=-1), parts[0][1]
-    else:
-        sig, Mlast = SequenceSignalHIP.apply(A, B, Mi, phase, rest, T1, T2, Δf, rx, K, sched, want)
-    if demod and phase is not None:
-        φ = phase.to(device=sig.device, dtype=torch.float64).reshape(phase.shape + (1,) * (sig.ndim - 3))
-        c, s = torch.cos(φ), torch.sin(φ)
-        s0, s1 = sig[:, 0].to(torch.float64), sig[:, 1].to(torch.float64)
-        sig = torch.stack((s0 * c + s1 * s, s1 * c - s0 * s), dim=1).to(sig.dtype)
+    *_, sched, K = _sequence_operands(A, B, pulse, n, phase, rest, T1, T2, Δf, Mi, rx=rx)
+    head = (A, B, Mi, phase, rest, T1, T2, Δf)
+    sig, Mlast = _signal_by_coil_blocks(SequenceSignalHIP, head, rx, (K, sched, _grad_wanted(*head, rx)), B.ndim - 1)
+    if demod:
+        sig = _demodulate(sig, phase)
     return (sig, Mlast) if return_last else sig
 
 
@@ -1869,14 +1894,6 @@ def sequence_signal_rfgr(
                            Δf=Δf if Δf_rest is None else Δf_rest, rx=rx, demod=demod, return_last=return_last)
 
 
-def _period_length(n, sched, phase, N):
-    r"""``K`` of :func:`sequence_steadystate`: :func:`_sequence_length`, and a period needs a repetition."""
-    K = _sequence_length(n, sched, phase, N)
-    if K == 0:
-        raise ValueError("mrphy_amd: a period needs a repetition: K = 0")
-    return K
-
-
 class SequenceSteadyStateHIP(Function):
     r"""``Mss = SequenceSteadyStateHIP.apply(A, B, phase, rest, T1, T2, Δf, K, sched, want)`` -- see
     :func:`sequence_steadystate`.  ``A, B`` carry the bank axis in front and ``sched`` is the checked schedule as for
@@ -1889,30 +1906,21 @@ class SequenceSteadyStateHIP(Function):
     ARGS = ('A', 'B', 'phase', 'rest', 'T1', 'T2', 'Δf', 'K', 'sched', 'want')
 
     @staticmethod
-    def _operands(a, rs, T1, T2, Δf, cs, sched_dev):
-        r"""``AbSequenceHIP._args`` without ``Mi``: there is none."""
-        N, Nd, nM, code, keep, head, tail = AbSequenceHIP._args(a, rs, T1, T2, Δf, None, cs, sched_dev)
-        return N, Nd, nM, code, keep, head, tail[:11] + tail[14:]
-
-    @staticmethod
     def forward(ctx, A, B, phase, rest, T1, T2, Δf, K, sched, want):
         lib = _lib.require_library()
         device = A.device
         a, b = A.detach().contiguous(), B.detach().contiguous()
         sched_dev = None if sched is None else sched.to(device)
-        rs = AbSequenceHIP._rest_table(a, rest, a.shape[1], K)
+        rs = _rest_table(a, rest, K)
         _, cs = _state_operands(a[0], None, phase)
-        N, Nd, nM, code, keep, head, ops = SequenceSteadyStateHIP._operands(a, rs, T1, T2, Δf, cs, sched_dev)
+        N, Nd, nM, code, keep, head, ops = _sequence_args(a, rs, T1, T2, Δf, None, cs, sched_dev, with_mi=False)
         Mss = torch.empty_like(b[0])
         per = ck = None
         if want:
             S = int(lib.mrphy_train_signal_ck_every())
             per = torch.empty((12, N * nM), dtype=torch.float64, device=device)
             ck = torch.empty((-(-K // S), N * nM, 3), dtype=torch.float64, device=device)
-        with torch.cuda.device(device):
-            rc = lib.mrphy_sequence_steadystate_fwd(code, a.data_ptr(), b.data_ptr(), *head, *ops, Mss.data_ptr(),
-                                                    _ptr(per), _ptr(ck), N, nM, K, _host.current_stream(device))
-        _lib.check(rc, 'mrphy_sequence_steadystate_fwd')
+        _launch('mrphy_sequence_steadystate_fwd', device, code, a, b, *head, *ops, Mss, per, ck, N, nM, K)
         del keep
         ctx.set_materialize_grads(False)
         if want:
@@ -1933,35 +1941,21 @@ class SequenceSteadyStateHIP(Function):
         need_φ, need_r = need[2] and phase is not None, need[3] and rest is not None
         if not (need[0] or need[1] or need_φ or need_r or any(need_c)):
             return none
-        lib = _lib.require_library()
         a, b, cs, rs, sched_dev, per, ck = ctx.saved_tensors
         device, dtype = a.device, a.dtype
-        N, Nd, nM, code, keep, head, ops = SequenceSteadyStateHIP._operands(a, rs, *consts, cs, sched_dev)
+        N, Nd, nM, code, keep, head, ops = _sequence_args(a, rs, *consts, None, cs, sched_dev, with_mi=False)
         g = grad_Mss.detach().to(dtype).contiguous()
         lam = torch.empty_like(g)
         empty = N * nM == 0
-        f64 = torch.float64
         o = _new_grads(empty, dtype, device, gA=need[0] and a.shape, gB=need[1] and b.shape)
-        # in fp64 whatever the data type, folded over those who share the operand, then rounded once: as
-        # SequenceSignalHIP.backward
-        o.update(_new_grads(empty, f64, device, gC=any(need_c) and (N,) + Nd + (3,), gφ=need_φ and (N, K),
-                            gr=need_r and (N, K)))
-        nQ = int(bool(need_φ)) + int(bool(need_r))
-        nbytes = int(lib.mrphy_sequence_signal_workspace(code, N, nM, K, nQ)) if nQ else 0
-        work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
-        nbank = int(lib.mrphy_sequence_signal_bank_workspace(code, a.shape[0], N, nM)) if (need[0] or need[1]) else 0
-        bank = torch.empty(nbank // 8, dtype=f64, device=device) if nbank else None
-        with torch.cuda.device(device):
-            rc = lib.mrphy_sequence_steadystate_bwd(code, a.data_ptr(), b.data_ptr(), *head, g.data_ptr(), *ops,
-                                                    per.data_ptr(), ck.data_ptr(), lam.data_ptr(),
-                                                    *(_ptr(o[k]) for k in ('gA', 'gB', 'gC', 'gr', 'gφ')),
-                                                    work.data_ptr(), work.numel(), _ptr(bank), nbank, N, nM, K,
-                                                    _host.current_stream(device))
-        _lib.check(rc, 'mrphy_sequence_steadystate_bwd')
+        o64, work, bank, nbank = _sweep_scratch(code, a, N, Nd, nM, K, empty, need_c, need_φ, need_r, need[0] or need[1])
+        o.update(o64)
+        _launch('mrphy_sequence_steadystate_bwd', device, code, a, b, *head, g, *ops, per, ck, lam,
+                *(o[k] for k in ('gA', 'gB', 'gC', 'gr', 'gφ')), work, work.numel(), bank, nbank, N, nM, K)
         del keep, work, bank, lam
-        gφ = _fold_to_operand(o['gφ'], phase, f64) if need_φ else None
-        gr = _fold_repetition_sums(o['gr'], rest) if need_r else None
-        return (o['gA'], o['gB'], gφ, gr) + _fold_rest_consts(o['gC'], consts, need_c, N, Nd) + (None, None, None)
+        gφ = _fold_to_operand(o['gφ'], phase, torch.float64) if need_φ else None
+        gr, gconsts = _fold_sweep_grads(o, rest, consts, need_c, N, Nd)
+        return (o['gA'], o['gB'], gφ, gr) + gconsts + (None, None, None)
 
 
 @_host.half_via_float
@@ -2013,16 +2007,8 @@ def sequence_steadystate(
     Out of scope: a schedule per batch entry; returning ``Ā, b̄``; a signal summed inside the same launch (that is
     :func:`sequence_signal` with ``Mi=Mss``); a CPU path.
     """
-    N, Nd = _train_spins(A, B, bank=True)
-    P = A.shape[0]
-    sched = _sequence_schedule(pulse, P)
-    K = _period_length(n, sched, phase, N)
-    if rest is not None and (rest.ndim > 2 or (rest.ndim == 1 and rest.shape[0] not in (1, N)) or
-                             (rest.ndim == 2 and (rest.shape[0] not in (1, N) or rest.shape[1] != K))):
-        raise ValueError(f"mrphy_amd: `rest` {tuple(rest.shape)} must be (), (N ⊻ 1,) or (N ⊻ 1, K) with N = {N}, K = {K}")
-    _check_train_operands(A, B, N, Nd, None, rest, T1, T2, Δf)
-    operands = (A, B, phase, rest, T1, T2, Δf)
-    want = torch.is_grad_enabled() and any(isinstance(x, Tensor) and x.requires_grad for x in operands)
+    *_, sched, K = _sequence_operands(A, B, pulse, n, phase, rest, T1, T2, Δf, None, period=True)
+    want = _grad_wanted(A, B, phase, rest, T1, T2, Δf)
     return SequenceSteadyStateHIP.apply(A, B, phase, rest, T1, T2, Δf, K, sched, want)
 
 

@@ -180,6 +180,72 @@ def test_fused_adjoint_table_agrees_with_the_prototypes():
         assert call == argtypes, name
 
 
+class _RecordingCtx:
+    r"""What a ``Function``'s ``forward`` / ``backward`` ask of their ``ctx``, without autograd."""
+
+    def __init__(self, n_inputs):
+        self.needs_input_grad = (True,) * n_inputs
+
+    def set_materialize_grads(self, flag):
+        pass
+
+    def save_for_backward(self, *tensors):
+        self.saved_tensors = tensors
+
+
+@pytest.mark.parametrize('bare', (False, True), ids=('every_operand', 'no_optional_operand'))
+def test_train_family_arguments_agree_with_the_prototypes(monkeypatch, bare):
+    r"""The ten entry points of the train and the sequence family get their arguments from ``fused``'s operand helpers
+    (``_rest_operands``, ``_state_args``, ``_sequence_args`` with and without ``Mi``, ``_rx_operand``, ``_signal_buffers``,
+    ``_sweep_scratch``), joined by each ``Function``.  Their forwards and backwards run here on tiny CPU tensors with the
+    launch replaced by a recorder: every call must hand over exactly ``len(argtypes)`` arguments (the stream included),
+    ``None`` or an address where the prototype has a pointer and an ``int`` where it has an integer.  With every optional
+    operand absent its null pointers must still sit in pointer positions: a group dropped or kept by a wrong index --
+    the steady state takes ``_sequence_args``' tuple without ``Mi`` -- shifts a ``None`` onto an integer."""
+    from mrphy_amd import fused
+    mrphy_amd.build()
+    seen = []
+
+    def record(name, device, *args):
+        argtypes = _lib.PROTOTYPES[name][1]
+        assert argtypes[-1] is ctypes.c_void_p, name                                   # the stream, appended by _launch
+        assert len(args) + 1 == len(argtypes), (name, len(args) + 1, len(argtypes))
+        for i, (x, t) in enumerate(zip(args, argtypes)):
+            x = fused._ptr(x)
+            if t is ctypes.c_void_p:
+                assert x is None or type(x) is int, (name, i, x)
+            else:
+                assert type(x) is int, (name, i, x)
+        seen.append(name)
+
+    monkeypatch.setattr(fused, '_launch', record)
+    f = torch.float32
+    N, nM, K, P, nRx = 2, 3, 2, 2, 3
+    A, B = torch.rand(P, N, nM, 3, 3, dtype=f), torch.rand(P, N, nM, 3, dtype=f)
+    opt = lambda x: None if bare else x  # noqa: E731
+    Mi, phase, rx = opt(torch.rand(N, nM, 3, dtype=f)), opt(torch.rand(N, K, dtype=f)), opt(torch.rand(N, nM, 2, nRx, dtype=f))
+    rest, table = opt(torch.tensor(3e-3, dtype=f)), opt(torch.full((1, K), 3e-3, dtype=f))
+    T1, T2, df = opt(torch.rand(N, nM, dtype=f) + 1), opt(torch.rand(N, nM, dtype=f) + .1), opt(torch.rand(N, nM, dtype=f))
+    sched = torch.tensor([0, 1], dtype=torch.int32)
+    coils = () if bare else (nRx,)
+    gMt, gsig, gM = torch.ones(K, N, nM, 3, dtype=f), torch.ones(N, 2, K, *coils, dtype=f), torch.ones(N, nM, 3, dtype=f)
+    runs = (
+        (fused.AbTrainHIP, (A[0], B[0], Mi, phase, rest, T1, T2, df, K), (gMt,)),
+        (fused.TrainSignalHIP, (A[0], B[0], Mi, phase, rest, T1, T2, df, rx, K, True), (gsig, gM)),
+        (fused.AbSequenceHIP, (A, B, Mi, phase, table, T1, T2, df, K, sched), (gMt,)),
+        (fused.SequenceSignalHIP, (A, B, Mi, phase, table, T1, T2, df, rx, K, sched, True), (gsig, gM)),
+        (fused.SequenceSteadyStateHIP, (A, B, phase, table, T1, T2, df, K, sched, True), (gM,)),
+    )
+    for Fn, inputs, cotangents in runs:
+        ctx = _RecordingCtx(len(inputs))
+        Fn.forward(ctx, *inputs)
+        grads = Fn.backward(ctx, *cotangents)
+        assert len(grads) == len(inputs), Fn.__name__
+    family = [f'mrphy_{name}_{way}' for name in ('ab_train', 'train_signal', 'ab_sequence', 'sequence_signal',
+                                                  'sequence_steadystate') for way in ('fwd', 'bwd')]
+    assert seen == family
+
+
 def test_signatures_match_the_reference():
     import inspect
     sig = inspect.signature(mrphy_amd.sims.blochsim)
