@@ -90,7 +90,8 @@ extern "C" {
  *      repetition, and its adjoint); mrphy_sequence_signal_workspace, mrphy_sequence_signal_bank_workspace,
  *      mrphy_sequence_signal_fwd, mrphy_sequence_signal_bwd (the received signal of that sequence, and its adjoint);
  *      mrphy_sequence_steadystate_fwd, mrphy_sequence_steadystate_bwd (the steady state of that sequence played as one
- *      period, and its adjoint). */
+ *      period, and its adjoint); mrphy_blochsim_rfgr_moving_fwd, mrphy_blochsim_rfgr_moving_bwd (K2 / K2b for spins that
+ *      move at constant velocity). */
 #define MRPHY_ABI_VERSION 5
 
 #define MRPHY_F32      0  /* T = float,  CT = float                                          */
@@ -1303,6 +1304,55 @@ int mrphy_sequence_steadystate_bwd(int dtype, const void* A, const void* B, int6
                                    void* grad_A, void* grad_B, void* grad_consts, void* grad_rest, void* grad_phase,
                                    void* work, size_t work_bytes, void* bank, size_t bank_bytes,
                                    int64_t N, int64_t nM, int64_t K, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * K2v / K2vb  K2 / K2b for spins that move at constant velocity (ONE transmit coil: nC == 1, b1 (N, nM, 2) or NULL).
+ * A spin that is at loc when step 0 begins sees, during step t of this call, the gradient at its midpoint position
+ *     pos_t = loc + vdt * (step0 + t + 1/2),      Bz_t = gr_t . pos_t + df / gamma,
+ * vdt (N, nM, 3) = velocity * dt in cm per step, of the data type (formed and rounded once by the caller), step0 >= 0
+ * the number of steps played before this call (a pulse chained over several calls gives the single call's bits).
+ * Bxy is K2's: a b1 map is sampled at loc.  pos_t is one FMA per component in closed form, never a running sum, so the
+ * forward, the adjoint's recompute and a chained call see the same bits; step0 + nT must stay below 2^23 in the
+ * float types for step0 + t + 1/2 to be exact (the caller's check).  With vdt == 0 both are mrphy_blochsim_rfgr_fwd /
+ * _bwd bit for bit.  Every other argument, the checkpoints, the workspace (mrphy_blochsim_rfgr_bwd_workspace), the
+ * order of the checks and the return codes are those calls'; in addition a NULL vdt (with spins present), step0 < 0 and
+ * nC != 1 are MRPHY_EINVAL before anything is launched.  grad_gr's rows are the sums over spins of pos_t * dL/dBz_t.
+ * No atomics; the same inputs give the same bits.
+ * ------------------------------------------------------------------------------------------- */
+int mrphy_blochsim_rfgr_moving_fwd(int dtype,
+                                   const void* Mi,
+                                   const void* rf, int64_t rf_sn,
+                                   const void* gr, int64_t gr_sn,
+                                   const void* loc,
+                                   const void* df, int64_t df_sn, int64_t df_sm,
+                                   const void* gamma, int64_t gamma_sn, int64_t gamma_sm,
+                                   const void* b1,
+                                   const void* g,  int64_t g_sn,  int64_t g_sm,
+                                   const void* E1, int64_t E1_sn, int64_t E1_sm,
+                                   const void* E2, int64_t E2_sn, int64_t E2_sm,
+                                   const void* E1m1,
+                                   const void* vdt, int64_t step0,
+                                   void* Mo, void* Mck, int64_t ck_every,
+                                   int64_t N, int64_t nM, int64_t nT, int64_t nC,
+                                   void* stream);
+int mrphy_blochsim_rfgr_moving_bwd(int dtype,
+                                   const void* Mck,
+                                   const void* rf, int64_t rf_sn,
+                                   const void* gr, int64_t gr_sn,
+                                   const void* loc,
+                                   const void* df, int64_t df_sn, int64_t df_sm,
+                                   const void* gamma, int64_t gamma_sn, int64_t gamma_sm,
+                                   const void* b1,
+                                   const void* g,  int64_t g_sn,  int64_t g_sm,
+                                   const void* E1, int64_t E1_sn, int64_t E1_sm,
+                                   const void* E2, int64_t E2_sn, int64_t E2_sm,
+                                   const void* E1m1,
+                                   const void* vdt, int64_t step0,
+                                   const void* grad_Mo,
+                                   void* grad_Mi, void* grad_rf, void* grad_gr,
+                                   void* work, size_t work_bytes,
+                                   int64_t N, int64_t nM, int64_t nT,
+                                   void* stream);
 
 int mrphy_blochsim_ab(int dtype, const void* M, const void* A, const void* B, void* Mo,
                       int64_t rows, void* stream);

@@ -129,6 +129,8 @@ PROTOTYPES = {
     'mrphy_sequence_steadystate_fwd': (_int, _AB + _SEQ_HEAD + _REST + _PHASE + [_vp] * 3 + _SIZES),   # ..., Mss, per, ck
     'mrphy_sequence_steadystate_bwd': (_int, _AB + _SEQ_HEAD + [_vp] + _REST + _PHASE + [_vp] * 3 + [_vp] * 5   # per, ck, lam
                                        + _WORK + _WORK + _SIZES),
+    'mrphy_blochsim_rfgr_moving_fwd': (_int, _FUSED + [_vp, _i64] + [_vp, _vp, _i64] + [_i64] * 4 + [_vp]),   # vdt, step0
+    'mrphy_blochsim_rfgr_moving_bwd': (_int, _FUSED + [_vp, _i64] + [_vp, _vp, _vp, _vp, _vp, _sz] + [_i64] * 3 + [_vp]),
     'mrphy_blochsim_ab': (_int, [_int, _vp, _vp, _vp, _vp, _i64, _vp]),
     'mrphy_blochsim_ab_bwd': (_int, [_int, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
@@ -149,6 +151,8 @@ UNITS = [(f, m) for f, masks in (
     ('tu_fused_fwd1.hip', (_F32, _C64, _P, _PC64)),
     ('tu_fused_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_fused_maps_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
+    ('tu_fused_moving_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
+    ('tu_fused_moving_fwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_fused_consts_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_ab_rfgr_mc8_bwd.hip', (_F32, _C64, _P, _PC64)),          # fp64 stops at 4 coils (geom.hpp: AB_MC_MAXC_F64)
     ('tu_ab_rfgr_mc4_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
@@ -210,7 +214,9 @@ def unit_object(objdir: str, src: str, mask) -> str:
 # 15 % (64^3 x 2048: 0.81 -> 0.69 ms; tools/ab_libs_valu.py, profiles/r04_sched_ilp_ab.txt, r04_k2_ilp_ab.json).
 # The multi-coil and fp64 builds lose with it (registers), K2b is indifferent: they keep the default.
 _ILP = ('-mllvm', '-amdgpu-sched-strategy=max-ilp')
-UNIT_FLAGS = {'tu_fused_fwd1.hip': _ILP}
+# K2v's float builds take the schedule of the K2 builds they are measured against; its fp64 build keeps the default
+UNIT_FLAGS = {'tu_fused_fwd1.hip': _ILP,
+              **{('tu_fused_moving_fwd.hip', m): _ILP for m in (_F32, _C64, _P, _PC64)}}
 
 
 def unit_command(src: str, mask, obj: str, extra=()) -> list:

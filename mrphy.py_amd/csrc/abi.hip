@@ -60,6 +60,12 @@ int check_ops(const PulseOps& in, bool need_pulse, bool need_b1)
     return 0;
 }
 
+// K2v / K2vb form step0 + t + 1/2 in the data type: exact below 2^23 steps in the float types (k_fused_moving.hpp: step_mid)
+inline bool moving_steps_ok(size_t ts, int64_t step0, int64_t nT)
+{
+    return ts == 8 || (step0 < ((int64_t)1 << 23) && nT < ((int64_t)1 << 23) - step0);
+}
+
 // Each plain entry point and its `_traj_` twin share one validation and dispatch.  `traj` tells them apart; what
 // differs is written out where it differs.  The launchers take a null Mt / grad_Mt for the plain kernels.  Order of
 // the checks, everywhere: dtype and sizes, the mode arguments, the empty problem (0), null pointers, the workspace.
@@ -383,6 +389,42 @@ int mrphy_blochsim_rfgr_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PARAMS, 
     MRPHY_ADJOINT_REQ(1);
     r.gMo = grad_Mo;
     return rfgr_bwd(AdjBuild::PLAIN, false, dtype, r, MRPHY_PULSE_OPS, work_bytes, stream);
+}
+
+// K2v / K2vb: the checks of mrphy_blochsim_rfgr_fwd / _bwd in their order; step0, the coil count and (the float types)
+// the range in which step0 + t + 1/2 is exact are mode arguments, refused on an empty problem too; vdt is a required
+// pointer
+int mrphy_blochsim_rfgr_moving_fwd(int dtype, const void* Mi, MRPHY_PULSE_OPS_PARAMS, const void* vdt, int64_t step0,
+                                   void* Mo, void* Mck, int64_t ck_every, int64_t N, int64_t nM, int64_t nT, int64_t nC,
+                                   void* stream)
+{
+    if (int e = check_common(dtype, N, nM, nT)) return e;
+    if (step0 < 0 || nC != 1 || (Mck && (ck_every < 8 || ck_every % 8 != 0)) || !moving_steps_ok(tsize(dtype), step0, nT))
+        return MRPHY_EINVAL;
+    if (N * nM == 0) return 0;                            // runs at nT == 0: Mo = Mi
+    if (!Mi || !Mo || !vdt) return MRPHY_EINVAL;
+    const PulseOps in = MRPHY_PULSE_OPS;
+    if (int e = check_ops(in, nT > 0, false)) return e;
+    hipStream_t st = (hipStream_t)stream;
+    MRPHY_DISPATCH(dtype, (run_rfgr_moving_fwd<T, CT>(Mi, in, vdt, step0, Mo, Mck, ck_every, N, nM, nT, st)));
+}
+
+int mrphy_blochsim_rfgr_moving_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PARAMS, const void* vdt, int64_t step0,
+                                   const void* grad_Mo, void* grad_Mi, void* grad_rf, void* grad_gr, void* work,
+                                   size_t work_bytes, int64_t N, int64_t nM, int64_t nT, void* stream)
+{
+    MRPHY_ADJOINT_REQ(1);
+    r.gMo = grad_Mo;
+    if (int e = check_common(dtype, N, nM, nT)) return e;
+    if (step0 < 0 || nT % SEG != 0 || !moving_steps_ok(tsize(dtype), step0, nT))
+        return MRPHY_EINVAL;                                         // whole checkpoint segments only
+    if (N * nM * nT == 0) return 0;
+    if (!Mck || !grad_Mo || !work || !vdt) return MRPHY_EINVAL;
+    const PulseOps in = MRPHY_PULSE_OPS;
+    if (int e = check_ops(in, true, false)) return e;
+    if (work_bytes < mrphy_blochsim_rfgr_bwd_workspace(dtype, N, nM, nT)) return MRPHY_ENOSPC;
+    hipStream_t st = (hipStream_t)stream;
+    MRPHY_DISPATCH(dtype, (run_rfgr_moving_bwd<T, CT>(r, in, vdt, step0, st)));
 }
 
 int64_t mrphy_blochsim_rfgr_mc_max_coils(void) { return K2B_MAXC; }

@@ -101,6 +101,16 @@ template <int MC, typename T, typename CT>
 int run_ab_rfgr_mc_bwd(const void* ABck, PulseOps in, const void* gA, const void* gB, void* grf, void* ggr, void* work,
                        int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st);
 
+// K2v / K2vb (tu_fused_moving_fwd.hip, tu_fused_moving_bwd.hip): K2 / K2b for spins at constant velocity, one transmit
+// coil.  vdt (N, nM, 3): the displacement per step; step0: the steps played before this call.  The request is K2b's
+// plain one (gMo; gMi, grf, ggr; the workspace of mrphy_blochsim_rfgr_bwd_workspace)
+template <typename T, typename CT>
+int run_rfgr_moving_fwd(const void* Mi, PulseOps in, const void* vdt, int64_t step0, void* Mo, void* Mck,
+                        int64_t ck_every, int64_t N, int64_t nM, int64_t nT, hipStream_t st);
+
+template <typename T, typename CT>
+int run_rfgr_moving_bwd(const AdjointReq& r, PulseOps in, const void* vdt, int64_t step0, hipStream_t st);
+
 template <typename T, typename CT>
 int run_beff2ab(const void* Beff, Bc g, Bc E1, Bc E2, const void* E1m1, void* A, void* B, void* hist,
                 int64_t N, int64_t nM, int64_t nT, hipStream_t st);

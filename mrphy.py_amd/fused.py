@@ -27,6 +27,11 @@ of at most 15 composed steps.
 ``Mhst`` the reference forms inside ``BlochSim.forward`` and drops, ``sims.py:83,131``), differentiable through the
 trajectory kernels K2t / K2bt.
 
+:func:`blochsim_rfgr_moving` is the same simulation for spins that move at constant velocity during the pulse (flow:
+velocity-selective preparation, flow-compensated excitation, blood crossing a slice): each step's gradient field is
+taken at the spin's midpoint position of that step, formed in registers (K2v), and the fused adjoint w.r.t. ``Mi``,
+``rf``, ``gr`` re-forms it in its recompute and sweep (K2vb) -- no time-dependent ``Beff`` in memory.
+
 :func:`signal_rfgr` is the same simulation again, returning what a receive coil measures: the transverse
 magnetisation summed over the spins at the trajectory's record steps (K2s, and the signal mode of K2b), without the
 per-spin records in memory; the coils of a receive array share one simulation per launch.
@@ -71,8 +76,8 @@ from . import _lib, _host
 from ._consts import γH, dt0
 from .beffective import _code
 
-__all__ = ['blochsim_rfgr', 'blochsim_rfgr_traj', 'signal_rfgr', 'ab_rfgr', 'ab_steadystate', 'steadystate_rfgr',
-           'ab_train', 'train_rfgr', 'train_signal', 'train_signal_rfgr', 'ab_sequence', 'sequence_rfgr',
+__all__ = ['blochsim_rfgr', 'blochsim_rfgr_moving', 'blochsim_rfgr_traj', 'signal_rfgr', 'ab_rfgr', 'ab_steadystate',
+           'steadystate_rfgr', 'ab_train', 'train_rfgr', 'train_signal', 'train_signal_rfgr', 'ab_sequence', 'sequence_rfgr',
            'sequence_signal', 'sequence_signal_rfgr', 'sequence_steadystate', 'sequence_steadystate_rfgr']
 
 
@@ -150,11 +155,12 @@ class _Saved(NamedTuple):
     code: int                 # the dtype code
     consts: tuple             # the constants' arguments g .. E1m1, pointing into ...
     alive: tuple              # ... these (g, E1, E2, E1m1; the signal: and rx)
-    every: Optional[int]      # None: the plain call
+    every: Optional[int]      # the call's integer argument: None: the plain call; the record stride; the moving call's step0
     rx: tuple                 # the signal: (rx's pointer or None,), and the coil count for an array; else ()
     likes: dict               # _likes of the operands whose gradients the backward shapes, by argument name
 
 
+SEG = 16                  # steps per checkpoint segment: mrphy_blochsim_rfgr_ck_every() (csrc/geom.hpp)
 _CONSTS = ('γ2πdt', 'E1', 'E2', 'E1_1')
 _MAPS = ('loc', 'Δf', 'b1Map')
 # The adjoint entry points: what each takes between the operands and ``work, work_bytes, N, nM, nT[, nC], stream``, by
@@ -163,6 +169,7 @@ _PULSE_OUT = ('gMi', 'grf', 'ggr')
 _AB_OUT = ('gA', 'gB', 'grf', 'ggr')
 _ADJOINT_ARGS = {
     'mrphy_blochsim_rfgr_bwd': ('gMo', *_PULSE_OUT),
+    'mrphy_blochsim_rfgr_moving_bwd': ('vdt', 'every', 'gMo', *_PULSE_OUT),         # (`every`: its step0, see _Saved)
     'mrphy_blochsim_rfgr_traj_bwd': ('gMt', 'every', *_PULSE_OUT),
     'mrphy_blochsim_rfgr_mc_bwd': ('gMo', *_PULSE_OUT),
     'mrphy_blochsim_rfgr_mc_traj_bwd': ('gMt', 'every', *_PULSE_OUT),
@@ -189,6 +196,9 @@ def _adjoint_name(family, spin, mc, mrx, traj):
     (the CONSTS builds form the map sums too), ``'maps_'`` or ``''``; ``mc``: parallel transmit, where a map or constants'
     gradient is never wanted (:func:`_decide_route`, :func:`_decide_ab_route`); the signal's builds take one receive coil
     and an array alike, ``mrx`` says which the plain one is asked for."""
+    if family == 'moving':      # one transmit coil, the pulse gradient only (:func:`_decide_moving_route`)
+        assert not (mc or spin or traj), "fused.blochsim_rfgr_moving: the adjoint w.r.t. Mi, rf, gr of one transmit coil"
+        return 'mrphy_blochsim_rfgr_moving_bwd'
     if family == 'signal':
         return 'mrphy_signal_rfgr_' + ('consts_' if spin == 'consts_' else 'mrx_' if mrx else '') + 'bwd'
     if family == 'ab':
@@ -197,10 +207,11 @@ def _adjoint_name(family, spin, mc, mrx, traj):
     return 'mrphy_blochsim_rfgr_' + (spin or ('mc_' if mc else '') + ('traj_' if traj else '')) + 'bwd'
 
 
-def _fused_adjoint(s, Mck, family, want, gMo=None, gMt=None, gsig=None, gA=None, gB=None):
-    r"""The one adjoint call of the three Functions: ``s`` the forward's :class:`_Saved`, ``Mck`` its checkpoints,
-    ``family`` 'blochsim', 'signal' or 'ab', ``want`` the gradients wanted by argument name, ``gMo``, ``gMt``, ``gsig``
-    (``ab``: ``gA``, ``gB``) the cotangents received (contiguous, of the kernels' dtype).  Returns the raw gradients
+def _fused_adjoint(s, Mck, family, want, gMo=None, gMt=None, gsig=None, gA=None, gB=None, vdt=None):
+    r"""The one adjoint call of the four Functions: ``s`` the forward's :class:`_Saved`, ``Mck`` its checkpoints,
+    ``family`` 'blochsim', 'moving', 'signal' or 'ab', ``want`` the gradients wanted by argument name, ``gMo``, ``gMt``,
+    ``gsig`` (``ab``: ``gA``, ``gB``) the cotangents received (contiguous, of the kernels' dtype), ``vdt`` the moving call's
+    displacement per step (its ``step0`` is ``s.every``).  Returns the raw gradients
     ``{name: tensor, or None where not wanted}``: per spin ``gMi`` (not ``ab``: it has no ``Mi``), ``gloc``, ``gBz`` (for
     ``Δf`` and ``γ_beff``), ``gb1``, ``gC``; per pulse ``grf`` `(N, 2, nT, nC)`, ``ggr`` `(N, 3, nT)`."""
     lib = _lib.require_library()
@@ -225,7 +236,7 @@ def _fused_adjoint(s, Mck, family, want, gMo=None, gMt=None, gsig=None, gA=None,
                  else lib.mrphy_blochsim_rfgr_bwd_workspace(s.code, p.N, p.nM, p.nT))
     work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
     vals = dict(out, gMo=gMo, gMt=gMt, gsig=gsig, gA=gA, gB=gB, every=s.every or 0, rx=s.rx[0] if s.rx else None,
-                nRx=s.rx[1] if mrx else 1)
+                nRx=s.rx[1] if mrx else 1, vdt=vdt)
     with torch.cuda.device(device):
         rc = getattr(lib, name)(s.code, Mck.data_ptr(), *p.k0_args(), *s.consts,
                                 *(_ptr(vals[k]) for k in _ADJOINT_ARGS[name]), work.data_ptr(), work.numel(),
@@ -641,6 +652,163 @@ with one transmit coil the fused adjoint returns the step constants' gradients p
         # (slowsims.blochsim is sims.blochsim unless T1, T2, γ or dt requires grad: then K3 returns their gradients too)
         return slowsims.blochsim(Mi, beff, T1=T1, T2=T2, γ=γ, dt=dt)
     return out
+
+
+class BlochSimRfGrMovingHIP(Function):
+    r"""``Mo = BlochSimRfGrMovingHIP.apply(Mi, rf, gr, pulse_on_spins, vdt, step0, γ2πdt, E1, E2, E1_1, want_ckpt)``
+
+    :class:`BlochSimRfGrHIP`'s plain call for spins that move: ``vdt`` `(N, *Nd, xyz)` contiguous, of the kernels' dtype,
+    is the displacement per step, ``step0`` the number of steps played before this call
+    (``mrphy_blochsim_rfgr_moving_fwd`` / ``_bwd``, one transmit coil).  Differentiable w.r.t. ``Mi``, ``rf`` and ``gr``;
+    ``want_ckpt`` is the caller's decision (:func:`_decide_moving_route`), as there."""
+
+    ARGS = ('Mi', 'rf', 'gr', 'p', 'vdt', 'step0', 'γ2πdt', 'E1', 'E2', 'E1_1', 'want_ckpt')
+
+    @staticmethod
+    def forward(ctx, Mi, rf, gr, p, vdt, step0, γ2πdt, E1, E2, E1_1, want_ckpt=False):
+        lib = _lib.require_library()
+        device, dtype = Mi.device, Mi.dtype
+        code, alive, consts, Mck, ckpt = _forward_prep(lib, p, γ2πdt, E1, E2, E1_1, dtype, device, bool(want_ckpt))
+        Mi_c = Mi.detach().contiguous()
+        Mo = torch.empty_like(Mi_c)
+        name = 'mrphy_blochsim_rfgr_moving_fwd'
+        with torch.cuda.device(device):
+            rc = getattr(lib, name)(code, Mi_c.data_ptr(), *p.k0_args(), *consts, vdt.data_ptr(), step0, Mo.data_ptr(),
+                                    *ckpt, p.N, p.nM, p.nT, p.nC, _host.current_stream(device))
+        _lib.check(rc, name)
+        if Mck is not None:                     # the checkpoints: a backward is wanted
+            ctx.save_for_backward(Mck)
+            ctx.saved = _Saved(p, code, consts, alive, step0, (), _likes(rf=rf, gr=gr))
+            ctx.vdt = vdt
+        return Mo
+
+    @staticmethod
+    def backward(ctx, grad_Mo):
+        ARGS = BlochSimRfGrMovingHIP.ARGS
+        want = dict(zip(ARGS, ctx.needs_input_grad))
+        if not any(want.values()):
+            return tuple(None for _ in ARGS)
+        s = ctx.saved
+        (Mck,) = ctx.saved_tensors
+        _host.require_invertible_relaxation(s.code, s.alive[1], s.alive[2], 'fused.blochsim_rfgr_moving')
+        gMo = grad_Mo.to(Mck.dtype).contiguous()
+        g = _fold_grads(_fused_adjoint(s, Mck, 'moving', want, gMo=gMo, vdt=ctx.vdt), s, want)
+        return tuple(g.get(k) for k in ARGS)
+
+
+def _decide_moving_route(*, nT, seg, one_coil, pulse_grad, other_grad):
+    r"""The route of :func:`blochsim_rfgr_moving` as a function of plain facts (``pulse_grad``: ``Mi``, ``rf`` or ``gr``
+    requires grad; ``other_grad``: ``vel``, ``loc``, ``Δf``, ``b1Map``, ``γ_beff``, ``T1``, ``T2``, ``γ``, ``dt`` or an entry
+    of ``consts`` does): ``('fused', want_ckpt)`` -- one transmit coil and either no gradient, at any length, or pulse
+    gradients over whole checkpoint segments; ``('split', n1)`` -- such gradients, more than one segment's steps and a
+    ragged last one: the first ``n1`` steps fused, the tail composed; ``('composed', None)`` -- everything else."""
+    if not one_coil or other_grad:
+        return 'composed', None
+    if not pulse_grad:
+        return 'fused', False
+    if nT % seg == 0:
+        return 'fused', True
+    if nT > seg:
+        return 'split', (nT // seg) * seg
+    return 'composed', None
+
+
+def _check_moving(Mi, gr, loc, vel, step0):
+    r"""The argument checks of :func:`blochsim_rfgr_moving` that need neither the device nor the library."""
+    if not isinstance(vel, Tensor) or vel.ndim != loc.ndim or vel.shape[-1] != 3 or \
+            vel.shape[0] not in (1, loc.shape[0]) or tuple(vel.shape[1:-1]) != tuple(loc.shape[1:-1]):
+        raise ValueError(f"mrphy_amd: `vel` must be (N ⊻ 1, *Nd, xyz) beside loc {tuple(loc.shape)}, got "
+                         f"{tuple(vel.shape) if isinstance(vel, Tensor) else vel!r}")
+    if isinstance(step0, bool) or not isinstance(step0, int) or step0 < 0:
+        raise ValueError(f"mrphy_amd: `step0` must be an int >= 0, got {step0!r}")
+    if Mi.dtype != torch.float64 and gr.shape[2] + step0 >= 1 << 23:
+        raise ValueError(f"mrphy_amd: nT + step0 = {gr.shape[2] + step0} must stay below 2**23 in fp32, where "
+                         "step0 + t + 1/2 is exact; use fp64 for longer pulses")
+
+
+def _vel_dt(vel, dt, loc):
+    r"""``vel·dt`` `(N, *Nd, xyz)` in ``loc``'s dtype: the displacement per step, formed in fp64 and rounded once (``dt`` is
+    `()` ⊻ `(N ⊻ 1,)`, right-padded).  Differentiable w.r.t. both."""
+    dt = _host.pad_trailing(torch.as_tensor(dt).to(vel.device), vel.ndim)
+    if vel.dtype == dt.dtype == loc.dtype:      # one multiplication in the data type is the fp64 product rounded once
+        return (vel * dt).expand(loc.shape)
+    return (vel.double() * dt.double()).to(loc.dtype).expand(loc.shape)
+
+
+def _moving_bz(gr, w, step0):
+    r"""What motion adds to the z component of ``rfgr2beff``'s field: ``(gr_t · w)(step0 + t + ½)`` `(N, *Nd, nT)` for
+    ``gr`` `(N ⊻ 1, xyz, nT)` and the displacement per step ``w`` `(N, *Nd, xyz)`.  Plain torch, differentiable."""
+    nT = gr.shape[2]
+    τ = (torch.arange(nT, dtype=torch.float64, device=w.device) + (step0 + 0.5)).to(w.dtype)
+    z = torch.matmul(w.reshape(w.shape[0], -1, 3), gr.to(device=w.device, dtype=w.dtype)) * τ
+    return z.reshape(tuple(w.shape[:-1]) + (nT,))
+
+
+@_host.half_via_float
+def blochsim_rfgr_moving(
+    Mi: Tensor, rf: Tensor, gr: Tensor, loc: Tensor, vel: Tensor, *, step0: int = 0,
+    Δf: Optional[Tensor] = None, b1Map: Optional[Tensor] = None, γ_beff: Tensor = γH,
+    T1: Optional[Tensor] = None, T2: Optional[Tensor] = None,
+    γ: Tensor = γH, dt: Tensor = dt0, consts: Optional[dict] = None
+) -> Tensor:
+    r""":func:`blochsim_rfgr` for spins that move at constant velocity while the pulse plays (flowing blood; the
+    reference declares ``SpinBolus`` for them, ``mobjs.py:968-973``, and gives it no body).  A spin that is at ``loc`` when
+    step 0 begins sees, during step ``t`` of this call, the gradient at its midpoint position
+
+        ``pos_t = loc + (vel·dt)·(step0 + t + ½)``,  ``Bz_t = gr_t · pos_t + Δf/γ_beff``
+
+    -- exact for a piecewise-constant gradient: with ``rf = 0`` and no relaxation the transverse phase is
+    ``-2π γ dt (m₀·loc + m₁·vel·dt)``, ``m₀ = Σ gr_t``, ``m₁ = Σ gr_t (step0 + t + ½)``.  ``Bxy`` is unchanged: a ``b1Map``
+    is sampled at ``loc`` (the map does not move with the spin).
+
+    ``vel``: `(N ⊻ 1, *Nd, xyz)`, "cm/s".  ``dt`` always sets the displacement ``vel·dt`` (formed in fp64, rounded once
+    to the data type), with ``consts=`` too.  ``step0``: the steps played before this call; a pulse chained over
+    several calls (``step0 = 0``, then ``step0 = n1`` on the rest) gives the single call's bits, because the position is
+    formed in closed form at every step, never as a running sum.  ``nT + step0`` must stay below ``2**23`` in fp32.
+    Everything else as :func:`blochsim_rfgr`; ``vel = 0`` gives its bits.
+
+    Routes.  One transmit coil, and no gradient or gradients among ``Mi``, ``rf``, ``gr``: the fused kernels K2v / K2vb
+    (``mrphy_blochsim_rfgr_moving_fwd`` / ``_bwd``), a pulse length that is not a multiple of 16 split into a fused part
+    and a composed tail of at most 15 steps at ``step0 + n1``.  Everything else -- parallel transmit, fewer than 16 steps
+    with a gradient, a gradient w.r.t. ``vel``, ``loc``, ``Δf``, ``b1Map``, ``γ_beff``, ``T1``, ``T2``, ``γ``, ``dt`` or
+    ``consts`` -- is composed: ``rfgr2beff`` at the static ``loc``, the moving part ``(gr_t · vel·dt)(step0 + t + ½)`` added to
+    its z component in torch, then ``blochsim``; autograd serves every operand there.  The composed forward equals the
+    kernels' to tolerance, not bit for bit (it rounds ``gr·loc`` and the moving part separately).
+
+    Out of scope: acceleration or arbitrary trajectories; the trajectory, signal and ``ab_rfgr`` forms for moving
+    spins; gradients w.r.t. ``vel``, ``loc`` and the maps inside the kernel; parallel transmit inside the kernel; a binding
+    of ``SpinBolus`` (there is no body to bind); a CPU path.
+    """
+    from . import beffective, sims, slowsims
+    _check_moving(Mi, gr, loc, vel, step0)
+    _host.require_device_tensor(Mi, 'Mi')
+    _host.require_device_tensor(vel, 'vel')
+    assert (T1 is None) == (T2 is None)
+    kw = dict(Δf=Δf, b1Map=b1Map, γ_beff=γ_beff, T1=T1, T2=T2, γ=γ, dt=dt, consts=consts)
+    f = _pulse_facts(rf, gr, loc, kw, Mi)
+    p = f.p
+    other_grad = f.maps_grad or f.consts_grad or any(_requires_grad(x) for x in (vel, γ_beff, dt))
+    route, arg = _decide_moving_route(nT=p.nT, seg=SEG, one_coil=f.one_coil, pulse_grad=f.pulse_grad,
+                                      other_grad=other_grad)
+    if route == 'split':
+        M1 = blochsim_rfgr_moving(Mi, rf[:, :, :arg], gr[:, :, :arg], loc, vel, step0=step0, **kw)
+        return blochsim_rfgr_moving(M1, rf[:, :, arg:], gr[:, :, arg:], loc, vel, step0=step0 + arg, **kw)
+    if route == 'composed':
+        beff = beffective.rfgr2beff(rf, gr, loc, Δf=Δf, b1Map=b1Map, γ=γ_beff, lazy=False)
+        z = _moving_bz(gr, _vel_dt(vel, dt, loc), step0)
+        beff = beff + torch.nn.functional.pad(z.unsqueeze(-1), (2, 0))      # out of place: beff may be saved upstream
+        if consts is not None:
+            return sims.blochsim_consts(Mi, beff, **consts)
+        return slowsims.blochsim(Mi, beff, T1=T1, T2=T2, γ=γ, dt=dt)
+    device, dtype = Mi.device, Mi.dtype
+    assert p.device == device and p.dtype == dtype, "Mi and loc must share device and dtype"
+    assert tuple(Mi.shape[:-1]) == (p.N,) + p.Nd
+    lib = _lib.require_library()
+    assert int(lib.mrphy_blochsim_rfgr_ck_every()) == SEG
+    γ2πdt, E1, E2, E1_1 = _step_constants(kw, False, 1 + len(p.Nd) + 2, device)
+    with torch.no_grad():
+        vdt = _vel_dt(vel.to(device), dt, loc).contiguous()
+    return BlochSimRfGrMovingHIP.apply(Mi, rf, gr, p, vdt, step0, γ2πdt, E1, E2, E1_1, arg)
 
 
 def _traj_ends(nT: int, every: int) -> list:
