@@ -91,7 +91,9 @@ extern "C" {
  *      mrphy_sequence_signal_fwd, mrphy_sequence_signal_bwd (the received signal of that sequence, and its adjoint);
  *      mrphy_sequence_steadystate_fwd, mrphy_sequence_steadystate_bwd (the steady state of that sequence played as one
  *      period, and its adjoint); mrphy_blochsim_rfgr_moving_fwd, mrphy_blochsim_rfgr_moving_bwd (K2 / K2b for spins that
- *      move at constant velocity). */
+ *      move at constant velocity); mrphy_blochsim_rfgr_shim_max_channels, mrphy_blochsim_rfgr_shim_bwd_workspace,
+ *      mrphy_blochsim_rfgr_shim_fwd, mrphy_blochsim_rfgr_shim_bwd (K2 / K2b with extra Bz field channels, and the adjoint
+ *      w.r.t. their waveforms). */
 #define MRPHY_ABI_VERSION 5
 
 #define MRPHY_F32      0  /* T = float,  CT = float                                          */
@@ -1353,6 +1355,68 @@ int mrphy_blochsim_rfgr_moving_bwd(int dtype,
                                    void* work, size_t work_bytes,
                                    int64_t N, int64_t nM, int64_t nT,
                                    void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * K2sh / K2shb  K2 / K2b with extra Bz field channels (ONE transmit coil: nC == 1, b1 (N, nM, 2) or NULL): fields whose
+ * shape in space is not linear and whose amplitude changes during the pulse (shim arrays, higher-order and concomitant
+ * terms, gradient nonlinearity, eddy currents, motion along given directions).  nS >= 1 channels, each a waveform times
+ * a map,
+ *     Bz_t = gr_t . loc + df / gamma + sum_k sh[k, t] shMap[k],
+ * sh (N, nS, nT) of the data type with batch stride sh_sn (0: one waveform set shared by the batch, as rf_sn), in any
+ * unit; shMap (N nM, nS) contiguous, of the data type, Gauss per that unit at each spin.  The sum is formed as K2's Bz
+ * followed by one FMA per channel in ascending k -- by the forward, the adjoint's recompute and its sweep alike -- so
+ * channels whose waveform or map is zero leave mrphy_blochsim_rfgr_fwd / _bwd's bits, and all-zero channels appended
+ * after the real ones change no bit of any output, whichever capacity serves the call.  Both hold for finite waveforms
+ * and maps, and up to the sign of a zero: 0 * inf is NaN, fma(s, 0, -0.0) is +0.0, and the channels between nS and the
+ * capacity re-read the last real channel's waveform against a zero map.  Bxy is K2's.
+ * mrphy_blochsim_rfgr_shim_max_channels(dtype): the most channels one launch takes (the kernels are built at the
+ * capacities 2, 4, 8; the smallest that holds nS runs); 0 for an unknown dtype code, as the workspace query then is.
+ * The adjoint returns grad_Mi (N, nM, 3), grad_rf (N, 2, nT, 1) and grad_lead (N, 3 + nS, nT): rows 0 .. 2 are grad_gr,
+ * row 3 + k is grad_sh[k, t] = sum over the spins of shMap[k] dL/dBz_t; each may be NULL (not wanted).  Its workspace
+ * is mrphy_blochsim_rfgr_shim_bwd_workspace(dtype, N, nM, nT, nS) bytes: (P, N, 5 + nS, nT) elements for the P persistent
+ * waves of mrphy_blochsim_rfgr_bwd.  Every other argument and the checkpoints are mrphy_blochsim_rfgr_fwd / _bwd's.
+ * Checks, in this order: dtype and sizes; the mode arguments -- nS < 1, nS above the capacity, nS nT >= 2^31, nC != 1, a
+ * ck_every that is no multiple of 8 with Mck given, nT % 16 != 0 in the adjoint -- MRPHY_EINVAL on an empty problem too; the
+ * empty problem (N nM == 0; the adjoint: N nM nT == 0) returns 0 and writes nothing; NULL sh or shMap or another
+ * required pointer is MRPHY_EINVAL; a short workspace MRPHY_ENOSPC.  Nothing is launched after a refusal.
+ * No atomics; the same inputs give the same bits.
+ * ------------------------------------------------------------------------------------------- */
+int mrphy_blochsim_rfgr_shim_max_channels(int dtype);
+size_t mrphy_blochsim_rfgr_shim_bwd_workspace(int dtype, int64_t N, int64_t nM, int64_t nT, int64_t nS);
+int mrphy_blochsim_rfgr_shim_fwd(int dtype,
+                                 const void* Mi,
+                                 const void* rf, int64_t rf_sn,
+                                 const void* gr, int64_t gr_sn,
+                                 const void* loc,
+                                 const void* df, int64_t df_sn, int64_t df_sm,
+                                 const void* gamma, int64_t gamma_sn, int64_t gamma_sm,
+                                 const void* b1,
+                                 const void* g,  int64_t g_sn,  int64_t g_sm,
+                                 const void* E1, int64_t E1_sn, int64_t E1_sm,
+                                 const void* E2, int64_t E2_sn, int64_t E2_sm,
+                                 const void* E1m1,
+                                 const void* sh, int64_t sh_sn, const void* shMap, int64_t nS,
+                                 void* Mo, void* Mck, int64_t ck_every,
+                                 int64_t N, int64_t nM, int64_t nT, int64_t nC,
+                                 void* stream);
+int mrphy_blochsim_rfgr_shim_bwd(int dtype,
+                                 const void* Mck,
+                                 const void* rf, int64_t rf_sn,
+                                 const void* gr, int64_t gr_sn,
+                                 const void* loc,
+                                 const void* df, int64_t df_sn, int64_t df_sm,
+                                 const void* gamma, int64_t gamma_sn, int64_t gamma_sm,
+                                 const void* b1,
+                                 const void* g,  int64_t g_sn,  int64_t g_sm,
+                                 const void* E1, int64_t E1_sn, int64_t E1_sm,
+                                 const void* E2, int64_t E2_sn, int64_t E2_sm,
+                                 const void* E1m1,
+                                 const void* sh, int64_t sh_sn, const void* shMap, int64_t nS,
+                                 const void* grad_Mo,
+                                 void* grad_Mi, void* grad_rf, void* grad_lead,
+                                 void* work, size_t work_bytes,
+                                 int64_t N, int64_t nM, int64_t nT,
+                                 void* stream);
 
 int mrphy_blochsim_ab(int dtype, const void* M, const void* A, const void* B, void* Mo,
                       int64_t rows, void* stream);

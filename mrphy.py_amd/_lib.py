@@ -131,6 +131,11 @@ PROTOTYPES = {
                                        + _WORK + _WORK + _SIZES),
     'mrphy_blochsim_rfgr_moving_fwd': (_int, _FUSED + [_vp, _i64] + [_vp, _vp, _i64] + [_i64] * 4 + [_vp]),   # vdt, step0
     'mrphy_blochsim_rfgr_moving_bwd': (_int, _FUSED + [_vp, _i64] + [_vp, _vp, _vp, _vp, _vp, _sz] + [_i64] * 3 + [_vp]),
+    'mrphy_blochsim_rfgr_shim_max_channels': (_int, [_int]),
+    'mrphy_blochsim_rfgr_shim_bwd_workspace': (_sz, [_int] + [_i64] * 4),
+    'mrphy_blochsim_rfgr_shim_fwd': (_int, _FUSED + [_vp, _i64, _vp, _i64] + [_vp, _vp, _i64] + [_i64] * 4 + [_vp]),  # sh, sh_sn, shMap, nS
+    'mrphy_blochsim_rfgr_shim_bwd': (_int, _FUSED + [_vp, _i64, _vp, _i64] + [_vp, _vp, _vp, _vp, _vp, _sz] + [_i64] * 3
+                                     + [_vp]),
     'mrphy_blochsim_ab': (_int, [_int, _vp, _vp, _vp, _vp, _i64, _vp]),
     'mrphy_blochsim_ab_bwd': (_int, [_int, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
@@ -154,6 +159,12 @@ UNITS = [(f, m) for f, masks in (
     ('tu_fused_moving_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_fused_moving_fwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_fused_consts_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
+    ('tu_fused_shim8_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
+    ('tu_fused_shim4_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
+    ('tu_fused_shim2_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
+    ('tu_fused_shim8_fwd.hip', (_F32, _F64, _C64, _P, _PC64)),
+    ('tu_fused_shim4_fwd.hip', (_F32, _F64, _C64, _P, _PC64)),
+    ('tu_fused_shim2_fwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_ab_rfgr_mc8_bwd.hip', (_F32, _C64, _P, _PC64)),          # fp64 stops at 4 coils (geom.hpp: AB_MC_MAXC_F64)
     ('tu_ab_rfgr_mc4_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_ab_rfgr_mc2_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
@@ -214,9 +225,12 @@ def unit_object(objdir: str, src: str, mask) -> str:
 # 15 % (64^3 x 2048: 0.81 -> 0.69 ms; tools/ab_libs_valu.py, profiles/r04_sched_ilp_ab.txt, r04_k2_ilp_ab.json).
 # The multi-coil and fp64 builds lose with it (registers), K2b is indifferent: they keep the default.
 _ILP = ('-mllvm', '-amdgpu-sched-strategy=max-ilp')
-# K2v's float builds take the schedule of the K2 builds they are measured against; its fp64 build keeps the default
+# K2v's and K2sh's float builds take the schedule of the K2 builds they are measured against; their fp64 builds keep
+# the default
 UNIT_FLAGS = {'tu_fused_fwd1.hip': _ILP,
-              **{('tu_fused_moving_fwd.hip', m): _ILP for m in (_F32, _C64, _P, _PC64)}}
+              **{(f, m): _ILP for m in (_F32, _C64, _P, _PC64)
+                 for f in ('tu_fused_moving_fwd.hip', 'tu_fused_shim2_fwd.hip', 'tu_fused_shim4_fwd.hip',
+                           'tu_fused_shim8_fwd.hip')}}
 
 
 def unit_command(src: str, mask, obj: str, extra=()) -> list:

@@ -66,6 +66,12 @@ inline bool moving_steps_ok(size_t ts, int64_t step0, int64_t nT)
     return ts == 8 || (step0 < ((int64_t)1 << 23) && nT < ((int64_t)1 << 23) - step0);
 }
 
+// K2sh / K2shb: 1 .. capacity channels, whose waveforms (nS, nT) the kernels index with an int (k_fused_shim.hpp: ShimCP)
+inline bool shim_channels_ok(size_t ts, int64_t nS, int64_t nT)
+{
+    return nS >= 1 && nS <= shim_max_channels(ts) && nS * nT <= INT32_MAX;
+}
+
 // Each plain entry point and its `_traj_` twin share one validation and dispatch.  `traj` tells them apart; what
 // differs is written out where it differs.  The launchers take a null Mt / grad_Mt for the plain kernels.  Order of
 // the checks, everywhere: dtype and sizes, the mode arguments, the empty problem (0), null pointers, the workspace.
@@ -186,6 +192,29 @@ int ab_rfgr_mc_bwd(const void* ABck, const PulseOps& in, const void* gA, const v
         return run_ab_rfgr_mc_bwd<8, T, CT>(ABck, in, gA, gB, grf, ggr, work, N, nM, nT, nC, st);
     return MRPHY_EINVAL;
 }
+
+// K2sh / K2shb: the unit of the smallest channel capacity 2, 4, 8 that holds nS (the caller has checked nS against the
+// data type's largest)
+#define MRPHY_SHIM_BY_CAPACITY(RUN, ...)                                                          \
+    do {                                                                                          \
+        if (nS <= 2) return RUN<2, T, CT>(__VA_ARGS__);                                           \
+        if (nS <= 4) return RUN<4, T, CT>(__VA_ARGS__);                                           \
+        if constexpr (shim_max_channels(sizeof(T)) >= 8) return RUN<8, T, CT>(__VA_ARGS__);       \
+        return MRPHY_EINVAL;                                                                      \
+    } while (0)
+template <typename T, typename CT>
+int rfgr_shim_fwd(const void* Mi, const PulseOps& in, const void* sh, int64_t sh_sn, const void* shMap, int64_t nS,
+                  void* Mo, void* Mck, int64_t ck_every, int64_t N, int64_t nM, int64_t nT, hipStream_t st)
+{
+    MRPHY_SHIM_BY_CAPACITY(run_rfgr_shim_fwd, Mi, in, sh, sh_sn, shMap, nS, Mo, Mck, ck_every, N, nM, nT, st);
+}
+template <typename T, typename CT>
+int rfgr_shim_bwd(const AdjointReq& r, const PulseOps& in, const void* sh, int64_t sh_sn, const void* shMap, int64_t nS,
+                  hipStream_t st)
+{
+    MRPHY_SHIM_BY_CAPACITY(run_rfgr_shim_bwd, r, in, sh, sh_sn, shMap, nS, st);
+}
+#undef MRPHY_SHIM_BY_CAPACITY
 }  // namespace
 
 // =============================================================================================
@@ -425,6 +454,56 @@ int mrphy_blochsim_rfgr_moving_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_P
     if (work_bytes < mrphy_blochsim_rfgr_bwd_workspace(dtype, N, nM, nT)) return MRPHY_ENOSPC;
     hipStream_t st = (hipStream_t)stream;
     MRPHY_DISPATCH(dtype, (run_rfgr_moving_bwd<T, CT>(r, in, vdt, step0, st)));
+}
+
+// K2sh / K2shb: the checks of the moving entry points in their order; the channel count against the data type's
+// capacity, the coil count, ck_every and (the adjoint) whole segments are mode arguments, refused on an empty problem
+// too; sh and shMap are required pointers
+int mrphy_blochsim_rfgr_shim_max_channels(int dtype)
+{
+    if (check_common(dtype, 0, 0, 0)) return 0;
+    return shim_max_channels(tsize(dtype));
+}
+
+size_t mrphy_blochsim_rfgr_shim_bwd_workspace(int dtype, int64_t N, int64_t nM, int64_t nT, int64_t nS)
+{
+    if (check_common(dtype, N, nM, nT) || N == 0 || nM == 0 || nT == 0 || nS < 0) return 0;   // an unknown dtype code among them
+    return (size_t)(k2b_waves(nM) * N * (5 + nS) * nT) * tsize(dtype);
+}
+
+int mrphy_blochsim_rfgr_shim_fwd(int dtype, const void* Mi, MRPHY_PULSE_OPS_PARAMS, const void* sh, int64_t sh_sn,
+                                 const void* shMap, int64_t nS, void* Mo, void* Mck, int64_t ck_every, int64_t N,
+                                 int64_t nM, int64_t nT, int64_t nC, void* stream)
+{
+    if (int e = check_common(dtype, N, nM, nT)) return e;
+    if (!shim_channels_ok(tsize(dtype), nS, nT) || nC != 1 || (Mck && (ck_every < 8 || ck_every % 8 != 0)))
+        return MRPHY_EINVAL;
+    if (N * nM == 0) return 0;                            // runs at nT == 0: Mo = Mi
+    if (!Mi || !Mo || !shMap || (nT > 0 && !sh)) return MRPHY_EINVAL;
+    const PulseOps in = MRPHY_PULSE_OPS;
+    if (int e = check_ops(in, nT > 0, false)) return e;
+    hipStream_t st = (hipStream_t)stream;
+    MRPHY_DISPATCH(dtype, (rfgr_shim_fwd<T, CT>(Mi, in, sh, sh_sn, shMap, nS, Mo, Mck, ck_every, N, nM, nT, st)));
+}
+
+int mrphy_blochsim_rfgr_shim_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PARAMS, const void* sh, int64_t sh_sn,
+                                 const void* shMap, int64_t nS, const void* grad_Mo, void* grad_Mi, void* grad_rf,
+                                 void* grad_lead, void* work, size_t work_bytes, int64_t N, int64_t nM, int64_t nT,
+                                 void* stream)
+{
+    void* const grad_gr = grad_lead;                                 // the request's lead buffer: (N, 3 + nS, nT)
+    MRPHY_ADJOINT_REQ(1);
+    r.gMo = grad_Mo;
+    if (int e = check_common(dtype, N, nM, nT)) return e;
+    if (!shim_channels_ok(tsize(dtype), nS, nT) || nT % SEG != 0)
+        return MRPHY_EINVAL;                                         // whole checkpoint segments only
+    if (N * nM * nT == 0) return 0;
+    if (!Mck || !grad_Mo || !work || !sh || !shMap) return MRPHY_EINVAL;
+    const PulseOps in = MRPHY_PULSE_OPS;
+    if (int e = check_ops(in, true, false)) return e;
+    if (work_bytes < mrphy_blochsim_rfgr_shim_bwd_workspace(dtype, N, nM, nT, nS)) return MRPHY_ENOSPC;
+    hipStream_t st = (hipStream_t)stream;
+    MRPHY_DISPATCH(dtype, (rfgr_shim_bwd<T, CT>(r, in, sh, sh_sn, shMap, nS, st)));
 }
 
 int64_t mrphy_blochsim_rfgr_mc_max_coils(void) { return K2B_MAXC; }

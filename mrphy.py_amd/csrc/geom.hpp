@@ -28,6 +28,9 @@ constexpr int64_t K2B_MC_MAX_WAVES = 256 * 8;     // 18 KB of LDS per wave -> 8 
 constexpr int AB_MC_MAXC_F32 = 8, AB_MC_MAXC_F64 = 4;
 constexpr int ab_mc_max_coils(size_t tsize) { return tsize == 8 ? AB_MC_MAXC_F64 : AB_MC_MAXC_F32; }
 static_assert(AB_MC_MAXC_F32 <= K2B_MAXC && AB_MC_MAXC_F64 <= K2B_MAXC, "K2abb-mc takes K2b-mc's workspace");
+// K2sh / K2shb (k_fused_shim.hpp): the largest channel capacity built (2, 4, 8) per data type, forward and adjoint alike
+constexpr int SHIM_MAXS_F32 = 8, SHIM_MAXS_F64 = 8;
+constexpr int shim_max_channels(size_t tsize) { return tsize == 8 ? SHIM_MAXS_F64 : SHIM_MAXS_F32; }
 constexpr int BWD_MAXC = 32;                      // K0 adjoint: largest coil capacity of the one-pass kernels
 
 // broadcastable per-spin constant (see mrphy_hip.h): element (n, s) at p[n * sn + s * sm]

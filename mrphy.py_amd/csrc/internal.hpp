@@ -111,6 +111,17 @@ int run_rfgr_moving_fwd(const void* Mi, PulseOps in, const void* vdt, int64_t st
 template <typename T, typename CT>
 int run_rfgr_moving_bwd(const AdjointReq& r, PulseOps in, const void* vdt, int64_t step0, hipStream_t st);
 
+// K2sh / K2shb (tu_fused_shim{2,4,8}_fwd.hip, _bwd.hip): K2 / K2b with nS <= MS extra Bz field channels, one transmit
+// coil.  sh (N|1, nS, nT) with batch stride sh_sn, shMap (N nM, nS).  The request is K2b's plain one with the lead buffer
+// (N, 3 + nS, nT) as ggr and the workspace of mrphy_blochsim_rfgr_shim_bwd_workspace
+template <int MS, typename T, typename CT>
+int run_rfgr_shim_fwd(const void* Mi, PulseOps in, const void* sh, int64_t sh_sn, const void* shMap, int64_t nS, void* Mo,
+                      void* Mck, int64_t ck_every, int64_t N, int64_t nM, int64_t nT, hipStream_t st);
+
+template <int MS, typename T, typename CT>
+int run_rfgr_shim_bwd(const AdjointReq& r, PulseOps in, const void* sh, int64_t sh_sn, const void* shMap, int64_t nS,
+                      hipStream_t st);
+
 template <typename T, typename CT>
 int run_beff2ab(const void* Beff, Bc g, Bc E1, Bc E2, const void* E1m1, void* A, void* B, void* hist,
                 int64_t N, int64_t nM, int64_t nT, hipStream_t st);

@@ -32,6 +32,11 @@ velocity-selective preparation, flow-compensated excitation, blood crossing a sl
 taken at the spin's midpoint position of that step, formed in registers (K2v), and the fused adjoint w.r.t. ``Mi``,
 ``rf``, ``gr`` re-forms it in its recompute and sweep (K2vb) -- no time-dependent ``Beff`` in memory.
 
+:func:`blochsim_rfgr_shim` is the same simulation with extra longitudinal field channels, each a waveform times a map
+at the spins (shim arrays, higher-order and concomitant terms, gradient nonlinearity, eddy currents): the lane keeps
+its maps in registers and adds one FMA per channel and step (K2sh), and the fused adjoint returns the gradient w.r.t.
+the waveforms beside those w.r.t. ``Mi``, ``rf``, ``gr`` (K2shb).
+
 :func:`signal_rfgr` is the same simulation again, returning what a receive coil measures: the transverse
 magnetisation summed over the spins at the trajectory's record steps (K2s, and the signal mode of K2b), without the
 per-spin records in memory; the coils of a receive array share one simulation per launch.
@@ -76,8 +81,8 @@ from . import _lib, _host
 from ._consts import γH, dt0
 from .beffective import _code
 
-__all__ = ['blochsim_rfgr', 'blochsim_rfgr_moving', 'blochsim_rfgr_traj', 'signal_rfgr', 'ab_rfgr', 'ab_steadystate',
-           'steadystate_rfgr', 'ab_train', 'train_rfgr', 'train_signal', 'train_signal_rfgr', 'ab_sequence', 'sequence_rfgr',
+__all__ = ['blochsim_rfgr', 'blochsim_rfgr_moving', 'blochsim_rfgr_shim', 'blochsim_rfgr_traj', 'signal_rfgr', 'ab_rfgr',
+           'ab_steadystate', 'steadystate_rfgr', 'ab_train', 'train_rfgr', 'train_signal', 'train_signal_rfgr', 'ab_sequence', 'sequence_rfgr',
            'sequence_signal', 'sequence_signal_rfgr', 'sequence_steadystate', 'sequence_steadystate_rfgr']
 
 
@@ -170,6 +175,9 @@ _AB_OUT = ('gA', 'gB', 'grf', 'ggr')
 _ADJOINT_ARGS = {
     'mrphy_blochsim_rfgr_bwd': ('gMo', *_PULSE_OUT),
     'mrphy_blochsim_rfgr_moving_bwd': ('vdt', 'every', 'gMo', *_PULSE_OUT),         # (`every`: its step0, see _Saved)
+    # (its integers under the table's two integer names -- `every`: sh's batch stride, `nRx`: nS; `ggr`: the lead buffer
+    # (N, 3 + nS, nT); the call is BlochSimRfGrShimHIP.backward's own, with its own workspace)
+    'mrphy_blochsim_rfgr_shim_bwd': ('sh', 'every', 'shMap', 'nRx', 'gMo', *_PULSE_OUT),
     'mrphy_blochsim_rfgr_traj_bwd': ('gMt', 'every', *_PULSE_OUT),
     'mrphy_blochsim_rfgr_mc_bwd': ('gMo', *_PULSE_OUT),
     'mrphy_blochsim_rfgr_mc_traj_bwd': ('gMt', 'every', *_PULSE_OUT),
@@ -809,6 +817,196 @@ def blochsim_rfgr_moving(
     with torch.no_grad():
         vdt = _vel_dt(vel.to(device), dt, loc).contiguous()
     return BlochSimRfGrMovingHIP.apply(Mi, rf, gr, p, vdt, step0, γ2πdt, E1, E2, E1_1, arg)
+
+
+class BlochSimRfGrShimHIP(Function):
+    r"""``Mo = BlochSimRfGrShimHIP.apply(Mi, rf, gr, sh, pulse_on_spins, shMap, γ2πdt, E1, E2, E1_1, want_ckpt)``
+
+    :class:`BlochSimRfGrHIP`'s plain call with ``nS`` extra Bz field channels: ``sh`` `(N ⊻ 1, nS, nT)` their waveforms,
+    ``shMap`` `(N, nM, nS)` contiguous, of the kernels' dtype, their maps (``mrphy_blochsim_rfgr_shim_fwd`` / ``_bwd``, one
+    transmit coil, ``nS`` within ``mrphy_blochsim_rfgr_shim_max_channels``).  Differentiable w.r.t. ``Mi``, ``rf``, ``gr`` and
+    ``sh``; ``want_ckpt`` is the caller's decision (:func:`_decide_shim_route`), as there."""
+
+    ARGS = ('Mi', 'rf', 'gr', 'sh', 'p', 'shMap', 'γ2πdt', 'E1', 'E2', 'E1_1', 'want_ckpt')
+
+    @staticmethod
+    def forward(ctx, Mi, rf, gr, sh, p, shMap, γ2πdt, E1, E2, E1_1, want_ckpt=False):
+        lib = _lib.require_library()
+        device, dtype = Mi.device, Mi.dtype
+        code, alive, consts, Mck, ckpt = _forward_prep(lib, p, γ2πdt, E1, E2, E1_1, dtype, device, bool(want_ckpt))
+        Mi_c = Mi.detach().contiguous()
+        Mo = torch.empty_like(Mi_c)
+        sh_c = sh.detach().to(device=device, dtype=dtype).contiguous()
+        nS = sh_c.shape[1]
+        sha = (sh_c.data_ptr(), sh_c.stride(0) if (sh_c.shape[0] == p.N and p.N > 1) else 0, shMap.data_ptr(), nS)
+        name = 'mrphy_blochsim_rfgr_shim_fwd'
+        with torch.cuda.device(device):
+            rc = getattr(lib, name)(code, Mi_c.data_ptr(), *p.k0_args(), *consts, *sha, Mo.data_ptr(), *ckpt,
+                                    p.N, p.nM, p.nT, p.nC, _host.current_stream(device))
+        _lib.check(rc, name)
+        if Mck is not None:                     # the checkpoints: a backward is wanted
+            ctx.save_for_backward(Mck)
+            ctx.saved = _Saved(p, code, consts, alive, None, (), _likes(rf=rf, gr=gr, sh=sh))
+            ctx.sh, ctx.shMap, ctx.sha = sh_c, shMap, sha
+        return Mo
+
+    @staticmethod
+    def backward(ctx, grad_Mo):
+        from .beffective import _fold_pulse_grad
+        ARGS = BlochSimRfGrShimHIP.ARGS
+        want = dict(zip(ARGS, ctx.needs_input_grad))
+        if not any(want.values()):
+            return tuple(None for _ in ARGS)
+        lib = _lib.require_library()
+        s = ctx.saved
+        (Mck,) = ctx.saved_tensors
+        p, device, nS = s.p, Mck.device, ctx.sha[3]
+        _host.require_invertible_relaxation(s.code, s.alive[1], s.alive[2], 'fused.blochsim_rfgr_shim')
+        gMo = grad_Mo.to(Mck.dtype).contiguous()
+        new = lambda w, *shape: torch.empty(shape, dtype=Mck.dtype, device=device) if w else None  # noqa: E731
+        gMi = new(want['Mi'], p.N, *p.Nd, 3)
+        grf = new(want['rf'], p.N, 2, p.nT, 1)
+        lead = new(want['gr'] or want['sh'], p.N, 3 + nS, p.nT)      # grad_gr's rows, then grad_sh's
+        if p.N * p.nM * p.nT == 0:              # no spin or no step: the library writes nothing (see _fused_adjoint)
+            for g in (grf, lead):
+                if g is not None:
+                    g.zero_()
+            if gMi is not None:
+                gMi.copy_(gMo.reshape(gMi.shape))
+        else:
+            nbytes = int(lib.mrphy_blochsim_rfgr_shim_bwd_workspace(s.code, p.N, p.nM, p.nT, nS))
+            work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+            name = 'mrphy_blochsim_rfgr_shim_bwd'
+            with torch.cuda.device(device):
+                vals = dict(zip(('sh', 'every', 'shMap', 'nRx'), ctx.sha), gMo=gMo, gMi=gMi, grf=grf, ggr=lead)
+                rc = getattr(lib, name)(s.code, Mck.data_ptr(), *p.k0_args(), *s.consts,
+                                        *(_ptr(vals[k]) for k in _ADJOINT_ARGS[name]), work.data_ptr(), work.numel(),
+                                        p.N, p.nM, p.nT, _host.current_stream(device))
+            _lib.check(rc, name)
+        g = dict(Mi=gMi)
+        if want['rf']:
+            g['rf'] = _fold_pulse_grad(grf, s.likes['rf'][0], s.likes['rf'][1], p.b1 is None)
+        if want['gr']:
+            g['gr'] = _fold_pulse_grad(lead[:, :3], s.likes['gr'][0], s.likes['gr'][1], False)
+        if want['sh']:
+            g['sh'] = _fold_pulse_grad(lead[:, 3:], s.likes['sh'][0], s.likes['sh'][1], False).to(s.likes['sh'][2])
+        return tuple(g.get(k) for k in ARGS)
+
+
+def _decide_shim_route(*, nT, seg, one_coil, nS, cap, pulse_grad, other_grad):
+    r"""The route of :func:`blochsim_rfgr_shim` as a function of plain facts (``nS >= 1`` channels, ``cap`` the most one
+    launch takes; ``pulse_grad``: ``Mi``, ``rf``, ``gr`` or ``sh`` requires grad; ``other_grad``: ``shMap``, ``loc``, ``Δf``,
+    ``b1Map``, ``γ_beff``, ``T1``, ``T2``, ``γ``, ``dt`` or an entry of ``consts`` does): ``('fused', want_ckpt)`` -- one
+    transmit coil, no more channels than the capacity and either no gradient, at any length, or pulse gradients over
+    whole checkpoint segments; ``('split', n1)`` -- such gradients, more than one segment's steps and a ragged last one:
+    the first ``n1`` steps fused, the tail composed; ``('composed', None)`` -- everything else."""
+    if not one_coil or nS > cap or other_grad:
+        return 'composed', None
+    if not pulse_grad:
+        return 'fused', False
+    if nT % seg == 0:
+        return 'fused', True
+    if nT > seg:
+        return 'split', (nT // seg) * seg
+    return 'composed', None
+
+
+def _check_shim(Mi, gr, loc, sh, shMap):
+    r"""The argument checks of :func:`blochsim_rfgr_shim` that need neither the device nor the library."""
+    N = loc.shape[0]
+    if not isinstance(sh, Tensor) or sh.ndim != 3 or sh.shape[0] not in (1, N):
+        raise ValueError(f"mrphy_amd: `sh` must be (N ⊻ 1, nS, nT) beside loc {tuple(loc.shape)}, got "
+                         f"{tuple(sh.shape) if isinstance(sh, Tensor) else sh!r}")
+    if not isinstance(shMap, Tensor) or shMap.ndim != loc.ndim or shMap.shape[0] not in (1, N) or \
+            tuple(shMap.shape[1:-1]) != tuple(loc.shape[1:-1]):
+        raise ValueError(f"mrphy_amd: `shMap` must be (N ⊻ 1, *Nd, nS) beside loc {tuple(loc.shape)}, got "
+                         f"{tuple(shMap.shape) if isinstance(shMap, Tensor) else shMap!r}")
+    if sh.shape[1] != shMap.shape[-1]:
+        raise ValueError(f"mrphy_amd: `sh` has {sh.shape[1]} channels, `shMap` {shMap.shape[-1]}")
+    if sh.shape[2] != gr.shape[2]:
+        raise ValueError(f"mrphy_amd: `sh` has {sh.shape[2]} steps, `gr` {gr.shape[2]}")
+
+
+def _shim_bz(sh, shMap):
+    r"""What the channels add to the z component of ``rfgr2beff``'s field: ``Σ_k sh[k, t]·shMap[k]`` `(N, *Nd, nT)` for
+    ``sh`` `(N ⊻ 1, nS, nT)` and ``shMap`` `(N ⊻ 1, *Nd, nS)`.  Plain torch, differentiable w.r.t. both."""
+    lead, nS = tuple(shMap.shape[:-1]), shMap.shape[-1]
+    z = torch.einsum('nmk,nkt->nmt', shMap.reshape(lead[0], -1, nS), sh.to(device=shMap.device, dtype=shMap.dtype))
+    return z.reshape((z.shape[0],) + lead[1:] + (sh.shape[2],))
+
+
+@_host.half_via_float
+def blochsim_rfgr_shim(
+    Mi: Tensor, rf: Tensor, gr: Tensor, loc: Tensor, sh: Tensor, shMap: Tensor, *,
+    Δf: Optional[Tensor] = None, b1Map: Optional[Tensor] = None, γ_beff: Tensor = γH,
+    T1: Optional[Tensor] = None, T2: Optional[Tensor] = None,
+    γ: Tensor = γH, dt: Tensor = dt0, consts: Optional[dict] = None
+) -> Tensor:
+    r""":func:`blochsim_rfgr` with ``nS`` extra longitudinal field channels, each a waveform times a map:
+
+        ``Bz_t = gr_t · loc + Σ_k sh[k, t]·shMap[k] + Δf/γ_beff``,  ``k < nS``
+
+    -- fields whose shape in space is not linear and whose amplitude changes during the pulse: shim-array and local-B0-coil
+    excitation, second-order and nonlinear gradient encoding, concomitant (Maxwell) fields (four channels,
+    ``(x²+y²)``, ``z²``, ``xz``, ``yz``, whose waveforms the caller forms from ``gr``), gradient nonlinearity, eddy-current
+    terms, and motion along given directions (``loc + Σ_k c_k(t)·d_k`` gives the channels ``gr_t·c_k(t)`` with maps
+    ``d_k``; :func:`blochsim_rfgr_moving` is the three-channel special case).  ``Bxy`` is unchanged.
+
+    ``sh``: `(N ⊻ 1, nS, nT)`, the channels' waveforms in any unit; ``shMap``: `(N ⊻ 1, *Nd, nS)`, Gauss per that unit at
+    each spin.  Everything else as :func:`blochsim_rfgr`; ``nS = 0`` returns its result.  The kernels form ``Bz_t`` as
+    :func:`blochsim_rfgr`'s value followed by one FMA per channel in ascending ``k``, so channels whose waveforms or maps
+    are all zero leave its bits -- in ``Mo`` and in the gradients w.r.t. ``Mi``, ``rf``, ``gr`` -- and all-zero channels
+    appended after the real ones change no bit of any result.  Both are statements about finite operands, up to the sign of
+    a zero: ``0·inf`` is NaN (a build of a larger capacity multiplies the last channel's samples by zero maps), and
+    ``fma(s, 0, -0.0)`` is ``+0.0``.
+
+    Routes.  One transmit coil, ``nS`` within the capacity (``mrphy_blochsim_rfgr_shim_max_channels``: 8), and no gradient
+    or gradients among ``Mi``, ``rf``, ``gr``, ``sh``: the fused kernels K2sh / K2shb (``mrphy_blochsim_rfgr_shim_fwd`` /
+    ``_bwd``), a pulse length that is not a multiple of 16 split into a fused part and a composed tail of at most 15
+    steps.  Everything else -- parallel transmit, more channels than the capacity, fewer than 16 steps with a gradient,
+    a gradient w.r.t. ``shMap``, ``loc``, ``Δf``, ``b1Map``, ``γ_beff``, ``T1``, ``T2``, ``γ``, ``dt`` or ``consts`` -- is
+    composed: ``rfgr2beff``, ``einsum(shMap, sh)`` added to its z component in torch, then ``blochsim``; autograd serves
+    every operand there.  The composed route equals the kernels to tolerance, not bit for bit.
+
+    Out of scope: gradients w.r.t. ``shMap`` and the other spin-side operands inside the kernel; parallel transmit
+    inside the kernel; more channels than the capacity in one launch; the trajectory, signal and ``ab_rfgr`` forms with
+    channels; a CPU path.
+    """
+    from . import beffective, sims, slowsims
+    _check_shim(Mi, gr, loc, sh, shMap)
+    kw = dict(Δf=Δf, b1Map=b1Map, γ_beff=γ_beff, T1=T1, T2=T2, γ=γ, dt=dt, consts=consts)
+    nS = sh.shape[1]
+    if nS == 0:
+        return blochsim_rfgr(Mi, rf, gr, loc, **kw)
+    _host.require_device_tensor(Mi, 'Mi')
+    _host.require_device_tensor(sh, 'sh')
+    _host.require_device_tensor(shMap, 'shMap')
+    assert (T1 is None) == (T2 is None)
+    f = _pulse_facts(rf, gr, loc, kw, Mi)
+    p = f.p
+    lib = _lib.require_library()
+    other_grad = f.maps_grad or f.consts_grad or any(_requires_grad(x) for x in (shMap, γ_beff))
+    route, arg = _decide_shim_route(nT=p.nT, seg=SEG, one_coil=f.one_coil, nS=nS,
+                                    cap=int(lib.mrphy_blochsim_rfgr_shim_max_channels(_code(p.dtype))),
+                                    pulse_grad=f.pulse_grad or _requires_grad(sh), other_grad=other_grad)
+    if route == 'split':
+        M1 = blochsim_rfgr_shim(Mi, rf[:, :, :arg], gr[:, :, :arg], loc, sh[:, :, :arg], shMap, **kw)
+        return blochsim_rfgr_shim(M1, rf[:, :, arg:], gr[:, :, arg:], loc, sh[:, :, arg:], shMap, **kw)
+    if route == 'composed':
+        beff = beffective.rfgr2beff(rf, gr, loc, Δf=Δf, b1Map=b1Map, γ=γ_beff, lazy=False)
+        z = _shim_bz(sh, shMap.to(device=beff.device, dtype=beff.dtype))
+        beff = beff + torch.nn.functional.pad(z.unsqueeze(-1), (2, 0))      # out of place: beff may be saved upstream
+        if consts is not None:
+            return sims.blochsim_consts(Mi, beff, **consts)
+        return slowsims.blochsim(Mi, beff, T1=T1, T2=T2, γ=γ, dt=dt)
+    device, dtype = Mi.device, Mi.dtype
+    assert p.device == device and p.dtype == dtype, "Mi and loc must share device and dtype"
+    assert tuple(Mi.shape[:-1]) == (p.N,) + p.Nd
+    assert int(lib.mrphy_blochsim_rfgr_ck_every()) == SEG
+    γ2πdt, E1, E2, E1_1 = _step_constants(kw, False, 1 + len(p.Nd) + 2, device)
+    with torch.no_grad():                       # (N, *Nd, nS) contiguous in the kernels' dtype, as vdt of the moving call
+        maps = shMap.to(device=device, dtype=dtype).expand((p.N,) + p.Nd + (nS,)).contiguous()
+    return BlochSimRfGrShimHIP.apply(Mi, rf, gr, sh, p, maps, γ2πdt, E1, E2, E1_1, arg)
 
 
 def _traj_ends(nT: int, every: int) -> list:
