@@ -745,10 +745,13 @@ def _vel_dt(vel, dt, loc):
 
 def _moving_bz(gr, w, step0):
     r"""What motion adds to the z component of ``rfgr2beff``'s field: ``(gr_t · w)(step0 + t + ½)`` `(N, *Nd, nT)` for
-    ``gr`` `(N ⊻ 1, xyz, nT)` and the displacement per step ``w`` `(N, *Nd, xyz)`.  Plain torch, differentiable."""
+    ``gr`` `(N ⊻ 1, xyz, nT)` and the displacement per step ``w`` `(N, *Nd, xyz)`.  Plain torch, differentiable.  The product
+    is formed on CONTIGUOUS copies: a batched product takes a view in whatever strides it has, and a permuted ``vel`` or a
+    time slice of a longer ``gr`` rounds differently (``grad_gr``, one ulp) from contiguous tensors of the same values -- the
+    tail of a split length then depended on the spelling of its operands (as :class:`_JoinAb`)."""
     nT = gr.shape[2]
     τ = (torch.arange(nT, dtype=torch.float64, device=w.device) + (step0 + 0.5)).to(w.dtype)
-    z = torch.matmul(w.reshape(w.shape[0], -1, 3), gr.to(device=w.device, dtype=w.dtype)) * τ
+    z = torch.matmul(w.reshape(w.shape[0], -1, 3).contiguous(), gr.to(device=w.device, dtype=w.dtype).contiguous()) * τ
     return z.reshape(tuple(w.shape[:-1]) + (nT,))
 
 
@@ -929,9 +932,12 @@ def _check_shim(Mi, gr, loc, sh, shMap):
 
 def _shim_bz(sh, shMap):
     r"""What the channels add to the z component of ``rfgr2beff``'s field: ``Σ_k sh[k, t]·shMap[k]`` `(N, *Nd, nT)` for
-    ``sh`` `(N ⊻ 1, nS, nT)` and ``shMap`` `(N ⊻ 1, *Nd, nS)`.  Plain torch, differentiable w.r.t. both."""
+    ``sh`` `(N ⊻ 1, nS, nT)` and ``shMap`` `(N ⊻ 1, *Nd, nS)`.  Plain torch, differentiable w.r.t. both.  On CONTIGUOUS copies,
+    as :func:`_moving_bz`: a permuted ``shMap`` or a slice of a longer ``sh`` otherwise changes the last bit of the sum, and of
+    ``grad_sh``."""
     lead, nS = tuple(shMap.shape[:-1]), shMap.shape[-1]
-    z = torch.einsum('nmk,nkt->nmt', shMap.reshape(lead[0], -1, nS), sh.to(device=shMap.device, dtype=shMap.dtype))
+    z = torch.einsum('nmk,nkt->nmt', shMap.reshape(lead[0], -1, nS).contiguous(),
+                     sh.to(device=shMap.device, dtype=shMap.dtype).contiguous())
     return z.reshape((z.shape[0],) + lead[1:] + (sh.shape[2],))
 
 

@@ -481,3 +481,96 @@ INTERP_GRIDS = (
     (1, 4e-6, 1e-6, 4),
     (3, 4e-6, 2e-5, 0),            # a dwell time longer than the pulse: an empty result
 )
+
+
+# ---------------------------------------------------------------------------------------------
+# The operand zoo and the zero-field case with the operands of fused.blochsim_rfgr_moving (``vel``) and
+# fused.blochsim_rfgr_shim (``sh``, ``shMap``) beside them (tests/test_moving_shim_operands.py, _cases_host.py)
+# ---------------------------------------------------------------------------------------------
+MOVSHIM_NS = {'compact_mixed': 2, 'scalars': 4, 'expanded': 6, 'cube': 7, 'cube_planes': 2, 'gamma_split': 4, 'views': 6,
+              'offset': 7}
+MOVSHIM_STEP_CM = 0.02                # |vel dt| per step, cm (tests/test_moving.py)
+
+
+def moving_shim_dense(v: dict):
+    r""":func:`fused_dense` of a variant of :func:`moving_shim_variants`, and ``vel`` `(N, nM, 3)`, ``sh`` `(N, nS, nT)`, ``shMap``
+    `(N, nM, nS)` contiguous in the data dtype (that of ``loc``), holding the numbers given."""
+    out = fused_dense(v)
+    N, nM = out['loc'].shape[:2]
+    dtype, nS = v['loc'].dtype, v['nS']
+    out['vel'] = v['vel'].to(dtype).expand((N,) + tuple(v['vel'].shape[1:])).reshape(N, nM, 3).contiguous()
+    out['sh'] = v['sh'].to(dtype).expand((N,) + tuple(v['sh'].shape[1:])).contiguous()
+    out['shMap'] = v['shMap'].to(dtype).expand((N,) + tuple(v['shMap'].shape[1:])).reshape(N, nM, nS).contiguous()
+    return out
+
+
+def moving_shim_variants(dtype, nC: int, nT: int = 48, seed: int = 53):
+    r""":func:`fused_operand_variants`'s eight spellings (``nC`` 0 or 1: the kernels take one transmit coil), each with a
+    velocity ``vel`` and ``nS`` = :data:`MOVSHIM_NS` field channels ``sh``, ``shMap`` in a spelling that goes with the variant's:
+    ``{name: (as_given, dense)}``, ``dense`` by :func:`moving_shim_dense`.
+
+        compact_mixed  vel (1, nM, 3)                  sh (N, 2, nT)                   shMap (1, nM, 2)
+        scalars        (N, 1, 3) expanded over nM      (1, 4, nT)                      (N, 1, 4) expanded over nM
+        expanded       (1, 1, 3) expanded to (N, nM)   (1, 6, nT) expanded over N      (1, nM, 6) expanded over N
+        cube           (N, *Nd, 3)                     (N, 7, nT)                      (N, *Nd, 7)
+        cube_planes    (1, *Nd, 3)                     (1, 2, nT)                      (1, 5, 1, 1, 2) expanded over the planes
+        gamma_split    fp64 whatever ``dtype`` (holding numbers ``dtype`` holds), nS = 4
+        views          (3, nM, N) permuted             channels 1..7, steps 4..4+nT of (N, 9, nT + 9)   (6, N, nM) permuted
+        offset         one element into a larger buffer, nS = 7
+
+    ``|vel dt| <= 0.02 cm`` per step with the variant's own ``dt`` (its largest entry), ``sh`` in +-1, ``shMap`` in +-2: the
+    amplitudes of ``tests/test_moving.py`` and ``test_shim.py``.  The new operands are drawn from a generator of their own
+    after :func:`fused_operand_variants` has returned: that function's tensors keep their bits."""
+    assert nC in (0, 1)
+    base = fused_operand_variants(dtype, nC, nT)
+    gen = torch.Generator(device='cpu').manual_seed(seed + 100 * nC + nT)
+    u = lambda *s: torch.rand(s, generator=gen, dtype=torch.float64) * 2 - 1    # noqa: E731
+    N, nM, Nd = FUSED_N, FUSED_NM, FUSED_ND
+    c = lambda x: x.to(dtype)                                                    # noqa: E731
+    out = {}
+    for name, (given, _) in base.items():
+        nS = MOVSHIM_NS[name]
+        amp = MOVSHIM_STEP_CM / float(given['dt'].double().max())
+        vel = lambda *s: c(u(*s, 3) * amp)                                       # noqa: E731
+        sh = lambda n, T=nT, k=nS: c(u(n, k, T))                                 # noqa: E731
+        mp = lambda *s: c(u(*s, nS) * 2)                                         # noqa: E731
+        if name == 'compact_mixed':
+            new = dict(vel=vel(1, nM), sh=sh(N), shMap=mp(1, nM))
+        elif name == 'scalars':
+            new = dict(vel=vel(N, 1).expand(N, nM, 3), sh=sh(1), shMap=mp(N, 1).expand(N, nM, nS))
+        elif name == 'expanded':
+            new = dict(vel=vel(1, 1).expand(N, nM, 3), sh=sh(1).expand(N, nS, nT), shMap=mp(1, nM).expand(N, nM, nS))
+        elif name == 'cube':
+            new = dict(vel=vel(N, *Nd), sh=sh(N), shMap=mp(N, *Nd))
+        elif name == 'cube_planes':
+            new = dict(vel=vel(1, *Nd), sh=sh(1), shMap=mp(1, Nd[0], 1, 1).expand(1, *Nd, nS))
+        elif name == 'gamma_split':      # fp64 operands beside `dtype` data: numbers that `dtype` holds, widened
+            new = dict(vel=vel(N, nM).double(), sh=sh(N).double(), shMap=mp(N, nM).double())
+        elif name == 'views':
+            new = dict(vel=c(u(3, nM, N) * amp).permute(2, 1, 0), sh=sh(N, nT + 9, 9)[:, 1:1 + nS, 4:4 + nT],
+                       shMap=c(u(nS, N, nM) * 2).permute(1, 2, 0))
+        else:
+            assert name == 'offset'
+            new = dict(vel=_after(vel(N, nM)), sh=_after(sh(N)), shMap=_after(mp(N, nM)))
+        v = dict(given, nS=nS, **new)
+        out[name] = (v, moving_shim_dense(v))
+    return out
+
+
+def moving_shim_zero_field(dtype, nC: int, nT: int = 48, seed: int = 59):
+    r""":func:`zero_field_case` with ``vel`` `(N, nM, 3)`, ``sh`` `(N, 3, nT)` and ``shMap`` `(N, nM, 3)`: ``vel = 0`` and
+    ``shMap = 0`` for the spins :data:`ZERO_SPINS`, ``sh = 0`` on the mask ``zero`` and on :data:`ZERO_RF_ONLY`, so that through the
+    moving call and through the channel call the same lanes are at exactly zero field on the same steps as in the static
+    case.  Returns ``(operands, zero)``."""
+    assert nC in (0, 1)
+    d, zero = zero_field_case(dtype, nC, nT)
+    gen = torch.Generator(device='cpu').manual_seed(seed + 100 * nC + nT)
+    u = lambda *s: torch.rand(s, generator=gen, dtype=torch.float64) * 2 - 1    # noqa: E731
+    N, nM, nS = FUSED_N, FUSED_NM, 3
+    vel, sh, mp = u(N, nM, 3) * (MOVSHIM_STEP_CM / dt0_val), u(N, nS, nT), u(N, nM, nS) * 2
+    sh[:, :, list(ZERO_RF_ONLY)] = 0
+    sh.movedim(2, 1)[zero] = 0
+    for n, s in ZERO_SPINS:
+        vel[n, s] = 0
+        mp[n, s] = 0
+    return dict(d, vel=vel.to(dtype), sh=sh.to(dtype), shMap=mp.to(dtype), nS=nS), zero
