@@ -72,6 +72,20 @@ inline bool shim_channels_ok(size_t ts, int64_t nS, int64_t nT)
     return nS >= 1 && nS <= shim_max_channels(ts) && nS * nT <= INT32_MAX;
 }
 
+// The Bz-extended builds (internal.hpp: MOVING, SHIM2 / 4 / 8), forward and adjoint: what the extension adds to a
+// validator's mode arguments (refused on an empty problem too) and to its required pointers.  Both hold for any other build.
+inline bool is_shim(AdjBuild b) { return b == AdjBuild::SHIM2 || b == AdjBuild::SHIM4 || b == AdjBuild::SHIM8; }
+inline bool ext_mode_ok(AdjBuild b, size_t ts, const BzExt& x, int64_t nT)
+{
+    if (b == AdjBuild::MOVING) return x.step0 >= 0 && moving_steps_ok(ts, x.step0, nT);
+    return !is_shim(b) || shim_channels_ok(ts, x.nS, nT);
+}
+inline bool ext_given(AdjBuild b, const BzExt& x, bool steps)       // (without a step no waveform is read)
+{
+    if (b == AdjBuild::MOVING) return x.vdt != nullptr;
+    return !is_shim(b) || (x.shMap && (x.sh || !steps));
+}
+
 // Each plain entry point and its `_traj_` twin share one validation and dispatch.  `traj` tells them apart; what
 // differs is written out where it differs.  The launchers take a null Mt / grad_Mt for the plain kernels.  Order of
 // the checks, everywhere: dtype and sizes, the mode arguments, the empty problem (0), null pointers, the workspace.
@@ -88,6 +102,32 @@ int rfgr_fwd(bool traj, int dtype, const void* Mi, const PulseOps& in, void* Mo,
     if (int e = check_ops(in, nT > 0, false)) return e;
     hipStream_t st = (hipStream_t)stream;
     MRPHY_DISPATCH(dtype, (run_rfgr_fwd<T, CT>(Mi, in, Mo, Mck, ck_every, Mt, every, N, nM, nT, nC, st)));
+}
+
+// K2v and K2sh: the checks of the plain forward in their order, for one transmit coil; the extension's mode arguments
+// (step0 and the range in which step0 + t + 1/2 is exact; the channel count against the data type's capacity) and its
+// required pointers (vdt; shMap, and sh if there is a step) join theirs
+int rfgr_ext_fwd(AdjBuild b, int dtype, const void* Mi, const PulseOps& in, const BzExt& x, void* Mo, void* Mck,
+                 int64_t ck_every, int64_t N, int64_t nM, int64_t nT, int64_t nC, void* stream)
+{
+    if (int e = check_common(dtype, N, nM, nT)) return e;
+    if (!ext_mode_ok(b, tsize(dtype), x, nT) || nC != 1 || (Mck && (ck_every < 8 || ck_every % 8 != 0)))
+        return MRPHY_EINVAL;
+    if (N * nM == 0) return 0;                            // runs at nT == 0: Mo = Mi
+    if (!Mi || !Mo || !ext_given(b, x, nT > 0)) return MRPHY_EINVAL;
+    if (int e = check_ops(in, nT > 0, false)) return e;
+    hipStream_t st = (hipStream_t)stream;
+#define MRPHY_EXT_FWD(B_) \
+    case AdjBuild::B_:    \
+        MRPHY_DISPATCH(dtype, (run_rfgr_ext_fwd<AdjBuild::B_, T, CT>(Mi, in, x, Mo, Mck, ck_every, N, nM, nT, st)))
+    switch (b) {
+        MRPHY_EXT_FWD(MOVING);
+        MRPHY_EXT_FWD(SHIM2);
+        MRPHY_EXT_FWD(SHIM4);
+        MRPHY_EXT_FWD(SHIM8);
+    default: return MRPHY_EINVAL;
+    }
+#undef MRPHY_EXT_FWD
 }
 
 // What an adjoint entry point packs besides MRPHY_PULSE_OPS: the request (geom.hpp: AdjointReq), once -- the part every
@@ -112,6 +152,10 @@ int dispatch_adjoint(AdjBuild b, int dtype, const AdjointReq& r, const PulseOps&
         MRPHY_ADJ(SIG_CONSTS4);
         MRPHY_ADJ(SIG_CONSTS8);
         MRPHY_ADJ(MC);
+        MRPHY_ADJ(MOVING);
+        MRPHY_ADJ(SHIM2);
+        MRPHY_ADJ(SHIM4);
+        MRPHY_ADJ(SHIM8);
     }
 #undef MRPHY_ADJ
     return MRPHY_EINVAL;
@@ -120,19 +164,21 @@ int dispatch_adjoint(AdjBuild b, int dtype, const AdjointReq& r, const PulseOps&
 // The adjoints of K2b / K2bt, builds PLAIN, MAPS, CONSTS and MC: grad_Mo (mode 0) or grad_Mt (modes 1, 2), exactly one of
 // them; a grad_b1 needs a b1 map to differentiate.  The plain call is the MAPS call without per-spin outputs.  `traj`:
 // a `_traj_` entry point, whose `every` counts whether or not grad_Mt is given.  The multi-coil build adds its coil
-// count, cannot do without a b1 map and has a workspace of its own.
+// count, cannot do without a b1 map and has a workspace of its own.  The builds MOVING and SHIM2 / 4 / 8 (K2vb, K2shb:
+// grad_Mo only) add their extension's mode arguments and required pointers, the shim builds their workspace.
 int rfgr_bwd(AdjBuild b, bool traj, int dtype, const AdjointReq& r, const PulseOps& in, size_t work_bytes, void* stream)
 {
     const bool mc = b == AdjBuild::MC;
     if (int e = check_common(dtype, r.N, r.nM, r.nT)) return e;
     if (r.nT % SEG != 0 || ((traj || r.gMt) && r.every < 1) || (r.gMo && r.gMt) || (r.gb1 && !in.b1) ||
-        (mc && (r.nC < 1 || r.nC > K2B_MAXC)))
+        (mc && (r.nC < 1 || r.nC > K2B_MAXC)) || !ext_mode_ok(b, tsize(dtype), r.ext, r.nT))
         return MRPHY_EINVAL;                                         // whole checkpoint segments only
     if (r.N * r.nM * r.nT == 0) return 0;
-    if (!r.Mck || !(r.gMo || r.gMt) || !r.work) return MRPHY_EINVAL;
+    if (!r.Mck || !(r.gMo || r.gMt) || !r.work || !ext_given(b, r.ext, true)) return MRPHY_EINVAL;
     if (int e = check_ops(in, true, mc)) return e;
-    if (work_bytes < (mc ? mrphy_blochsim_rfgr_mc_bwd_workspace(dtype, r.N, r.nM, r.nT, r.nC)
-                         : mrphy_blochsim_rfgr_bwd_workspace(dtype, r.N, r.nM, r.nT)))
+    if (work_bytes < (mc          ? mrphy_blochsim_rfgr_mc_bwd_workspace(dtype, r.N, r.nM, r.nT, r.nC)
+                      : is_shim(b) ? mrphy_blochsim_rfgr_shim_bwd_workspace(dtype, r.N, r.nM, r.nT, r.ext.nS)
+                                   : mrphy_blochsim_rfgr_bwd_workspace(dtype, r.N, r.nM, r.nT)))
         return MRPHY_ENOSPC;
     return dispatch_adjoint(b, dtype, r, in, stream);
 }
@@ -192,29 +238,6 @@ int ab_rfgr_mc_bwd(const void* ABck, const PulseOps& in, const void* gA, const v
         return run_ab_rfgr_mc_bwd<8, T, CT>(ABck, in, gA, gB, grf, ggr, work, N, nM, nT, nC, st);
     return MRPHY_EINVAL;
 }
-
-// K2sh / K2shb: the unit of the smallest channel capacity 2, 4, 8 that holds nS (the caller has checked nS against the
-// data type's largest)
-#define MRPHY_SHIM_BY_CAPACITY(RUN, ...)                                                          \
-    do {                                                                                          \
-        if (nS <= 2) return RUN<2, T, CT>(__VA_ARGS__);                                           \
-        if (nS <= 4) return RUN<4, T, CT>(__VA_ARGS__);                                           \
-        if constexpr (shim_max_channels(sizeof(T)) >= 8) return RUN<8, T, CT>(__VA_ARGS__);       \
-        return MRPHY_EINVAL;                                                                      \
-    } while (0)
-template <typename T, typename CT>
-int rfgr_shim_fwd(const void* Mi, const PulseOps& in, const void* sh, int64_t sh_sn, const void* shMap, int64_t nS,
-                  void* Mo, void* Mck, int64_t ck_every, int64_t N, int64_t nM, int64_t nT, hipStream_t st)
-{
-    MRPHY_SHIM_BY_CAPACITY(run_rfgr_shim_fwd, Mi, in, sh, sh_sn, shMap, nS, Mo, Mck, ck_every, N, nM, nT, st);
-}
-template <typename T, typename CT>
-int rfgr_shim_bwd(const AdjointReq& r, const PulseOps& in, const void* sh, int64_t sh_sn, const void* shMap, int64_t nS,
-                  hipStream_t st)
-{
-    MRPHY_SHIM_BY_CAPACITY(run_rfgr_shim_bwd, r, in, sh, sh_sn, shMap, nS, st);
-}
-#undef MRPHY_SHIM_BY_CAPACITY
 }  // namespace
 
 // =============================================================================================
@@ -420,22 +443,14 @@ int mrphy_blochsim_rfgr_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PARAMS, 
     return rfgr_bwd(AdjBuild::PLAIN, false, dtype, r, MRPHY_PULSE_OPS, work_bytes, stream);
 }
 
-// K2v / K2vb: the checks of mrphy_blochsim_rfgr_fwd / _bwd in their order; step0, the coil count and (the float types)
-// the range in which step0 + t + 1/2 is exact are mode arguments, refused on an empty problem too; vdt is a required
-// pointer
+// K2v / K2vb and K2sh / K2shb: the plain entry points' checks in their order (rfgr_ext_fwd, rfgr_bwd) with the extension's
+// own among them
 int mrphy_blochsim_rfgr_moving_fwd(int dtype, const void* Mi, MRPHY_PULSE_OPS_PARAMS, const void* vdt, int64_t step0,
                                    void* Mo, void* Mck, int64_t ck_every, int64_t N, int64_t nM, int64_t nT, int64_t nC,
                                    void* stream)
 {
-    if (int e = check_common(dtype, N, nM, nT)) return e;
-    if (step0 < 0 || nC != 1 || (Mck && (ck_every < 8 || ck_every % 8 != 0)) || !moving_steps_ok(tsize(dtype), step0, nT))
-        return MRPHY_EINVAL;
-    if (N * nM == 0) return 0;                            // runs at nT == 0: Mo = Mi
-    if (!Mi || !Mo || !vdt) return MRPHY_EINVAL;
-    const PulseOps in = MRPHY_PULSE_OPS;
-    if (int e = check_ops(in, nT > 0, false)) return e;
-    hipStream_t st = (hipStream_t)stream;
-    MRPHY_DISPATCH(dtype, (run_rfgr_moving_fwd<T, CT>(Mi, in, vdt, step0, Mo, Mck, ck_every, N, nM, nT, st)));
+    const BzExt x{vdt, step0, nullptr, 0, nullptr, 0};
+    return rfgr_ext_fwd(AdjBuild::MOVING, dtype, Mi, MRPHY_PULSE_OPS, x, Mo, Mck, ck_every, N, nM, nT, nC, stream);
 }
 
 int mrphy_blochsim_rfgr_moving_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PARAMS, const void* vdt, int64_t step0,
@@ -443,22 +458,10 @@ int mrphy_blochsim_rfgr_moving_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_P
                                    size_t work_bytes, int64_t N, int64_t nM, int64_t nT, void* stream)
 {
     MRPHY_ADJOINT_REQ(1);
-    r.gMo = grad_Mo;
-    if (int e = check_common(dtype, N, nM, nT)) return e;
-    if (step0 < 0 || nT % SEG != 0 || !moving_steps_ok(tsize(dtype), step0, nT))
-        return MRPHY_EINVAL;                                         // whole checkpoint segments only
-    if (N * nM * nT == 0) return 0;
-    if (!Mck || !grad_Mo || !work || !vdt) return MRPHY_EINVAL;
-    const PulseOps in = MRPHY_PULSE_OPS;
-    if (int e = check_ops(in, true, false)) return e;
-    if (work_bytes < mrphy_blochsim_rfgr_bwd_workspace(dtype, N, nM, nT)) return MRPHY_ENOSPC;
-    hipStream_t st = (hipStream_t)stream;
-    MRPHY_DISPATCH(dtype, (run_rfgr_moving_bwd<T, CT>(r, in, vdt, step0, st)));
+    r.gMo = grad_Mo; r.ext = BzExt{vdt, step0, nullptr, 0, nullptr, 0};
+    return rfgr_bwd(AdjBuild::MOVING, false, dtype, r, MRPHY_PULSE_OPS, work_bytes, stream);
 }
 
-// K2sh / K2shb: the checks of the moving entry points in their order; the channel count against the data type's
-// capacity, the coil count, ck_every and (the adjoint) whole segments are mode arguments, refused on an empty problem
-// too; sh and shMap are required pointers
 int mrphy_blochsim_rfgr_shim_max_channels(int dtype)
 {
     if (check_common(dtype, 0, 0, 0)) return 0;
@@ -475,15 +478,8 @@ int mrphy_blochsim_rfgr_shim_fwd(int dtype, const void* Mi, MRPHY_PULSE_OPS_PARA
                                  const void* shMap, int64_t nS, void* Mo, void* Mck, int64_t ck_every, int64_t N,
                                  int64_t nM, int64_t nT, int64_t nC, void* stream)
 {
-    if (int e = check_common(dtype, N, nM, nT)) return e;
-    if (!shim_channels_ok(tsize(dtype), nS, nT) || nC != 1 || (Mck && (ck_every < 8 || ck_every % 8 != 0)))
-        return MRPHY_EINVAL;
-    if (N * nM == 0) return 0;                            // runs at nT == 0: Mo = Mi
-    if (!Mi || !Mo || !shMap || (nT > 0 && !sh)) return MRPHY_EINVAL;
-    const PulseOps in = MRPHY_PULSE_OPS;
-    if (int e = check_ops(in, nT > 0, false)) return e;
-    hipStream_t st = (hipStream_t)stream;
-    MRPHY_DISPATCH(dtype, (rfgr_shim_fwd<T, CT>(Mi, in, sh, sh_sn, shMap, nS, Mo, Mck, ck_every, N, nM, nT, st)));
+    const BzExt x{nullptr, 0, sh, sh_sn, shMap, nS};
+    return rfgr_ext_fwd(shim_build(nS), dtype, Mi, MRPHY_PULSE_OPS, x, Mo, Mck, ck_every, N, nM, nT, nC, stream);
 }
 
 int mrphy_blochsim_rfgr_shim_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PARAMS, const void* sh, int64_t sh_sn,
@@ -493,17 +489,8 @@ int mrphy_blochsim_rfgr_shim_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PAR
 {
     void* const grad_gr = grad_lead;                                 // the request's lead buffer: (N, 3 + nS, nT)
     MRPHY_ADJOINT_REQ(1);
-    r.gMo = grad_Mo;
-    if (int e = check_common(dtype, N, nM, nT)) return e;
-    if (!shim_channels_ok(tsize(dtype), nS, nT) || nT % SEG != 0)
-        return MRPHY_EINVAL;                                         // whole checkpoint segments only
-    if (N * nM * nT == 0) return 0;
-    if (!Mck || !grad_Mo || !work || !sh || !shMap) return MRPHY_EINVAL;
-    const PulseOps in = MRPHY_PULSE_OPS;
-    if (int e = check_ops(in, true, false)) return e;
-    if (work_bytes < mrphy_blochsim_rfgr_shim_bwd_workspace(dtype, N, nM, nT, nS)) return MRPHY_ENOSPC;
-    hipStream_t st = (hipStream_t)stream;
-    MRPHY_DISPATCH(dtype, (rfgr_shim_bwd<T, CT>(r, in, sh, sh_sn, shMap, nS, st)));
+    r.gMo = grad_Mo; r.ext = BzExt{nullptr, 0, sh, sh_sn, shMap, nS};
+    return rfgr_bwd(shim_build(nS), false, dtype, r, MRPHY_PULSE_OPS, work_bytes, stream);
 }
 
 int64_t mrphy_blochsim_rfgr_mc_max_coils(void) { return K2B_MAXC; }

@@ -59,9 +59,18 @@ static_assert(sizeof(PulseOps) == 176 && sizeof(PulseOpsT<float>) == 176 && size
 template <typename T>
 inline PulseOpsT<T> typed(const PulseOps& o) { return __builtin_bit_cast(PulseOpsT<T>, o); }
 
-// Everything an adjoint call of the fused family (K2b, its trajectory, signal, MAPS, CONSTS and multi-coil builds)
-// carries besides PulseOps.  Each adjoint entry point of abi.hip packs it once; the validators, the launchers and the
-// kernel argument structs take it from there on.  A null pointer is "not given" (a cotangent) or "not wanted" (an output).
+// What a Bz-extended call carries besides PulseOps: the motion of K2v / K2vb or the field channels of K2sh / K2shb.  The
+// fields of the other extension are null / 0.
+struct BzExt {
+    const void* vdt;   int64_t step0; // motion: (N, nM, 3), the displacement per step; the steps played before this call
+    const void* sh;    int64_t sh_sn; // channels: the waveforms (N|1, nS, nT) and their batch stride (0: shared),
+    const void* shMap; int64_t nS;    // the maps (N nM, nS)
+};
+
+// Everything an adjoint call of the fused family (K2b, its trajectory, signal, MAPS, CONSTS, multi-coil, moving and shim
+// builds) carries besides PulseOps.  Each adjoint entry point of abi.hip packs it once; the validators, the launchers and
+// the kernel argument structs take it from there on.  A null pointer is "not given" (a cotangent) or "not wanted" (an
+// output).  The shim builds return grad_sh next to grad_gr: their ggr is the lead buffer (N, 3 + nS, nT).
 struct AdjointReq {
     const void* Mck;                  // (nT/SEG, N*nM, 3): the forward's checkpoints
     const void* gMo;                  // cotangents: grad_Mo (N, nM, 3) ...
@@ -72,6 +81,7 @@ struct AdjointReq {
     void *gloc, *gBz, *gb1, *gC;      // per-spin outputs: (N, nM, 3), (N, nM), (N, nM, 2), (N, nM, 4)
     void* work;
     int64_t N, nM, nT, nC;
+    BzExt ext;                        // the builds MOVING and SHIM2 / 4 / 8 (internal.hpp) only
 };
 
 inline int64_t hist_tiles(int64_t N, int64_t nM) { return (N * nM + WAVE - 1) / WAVE; }

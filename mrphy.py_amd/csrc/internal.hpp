@@ -12,6 +12,7 @@ namespace mrphy_i {
 using mrphy::Bc;
 using mrphy::PulseOps;
 using mrphy::AdjointReq;
+using mrphy::BzExt;
 using mrphy::HistParts;
 
 template <typename T, typename CT>
@@ -66,14 +67,30 @@ enum class AdjBuild {
     SIG_CONSTS1, SIG_CONSTS2, SIG_CONSTS4, SIG_CONSTS8,     // tu_signal_consts1 / 2 / 4 / 8_bwd.hip, one unit per capacity
                 // R >= nRx: K2bs that also returns gC; gsig is not null, rx may be null at R = 1 only
     MC,         // tu_fused_mc_bwd.hip: K2b / K2bt for nC <= K2B_MAXC transmit coils with their b1 map
+    MOVING,     // tu_fused_moving_bwd.hip: K2vb, K2b's mode 0 for spins at constant velocity (r.ext: vdt, step0)
+    SHIM2, SHIM4, SHIM8,    // tu_fused_shim2 / 4 / 8_bwd.hip, one unit per capacity MS >= nS: K2shb, K2b's mode 0 with nS extra
+                // Bz field channels (r.ext: sh, sh_sn, shMap, nS); ggr is the lead buffer (N, 3 + nS, nT), the workspace
+                // that of mrphy_blochsim_rfgr_shim_bwd_workspace
 };
 constexpr AdjBuild sig_consts_build(int R)
 {
     return R == 1 ? AdjBuild::SIG_CONSTS1 : R == 2 ? AdjBuild::SIG_CONSTS2 : R == 4 ? AdjBuild::SIG_CONSTS4
                                                                                       : AdjBuild::SIG_CONSTS8;
 }
+// K2sh / K2shb: the build of the smallest channel capacity 2, 4, 8 that holds nS (every data type has them all)
+constexpr AdjBuild shim_build(int64_t nS)
+{
+    return nS <= 2 ? AdjBuild::SHIM2 : nS <= 4 ? AdjBuild::SHIM4 : AdjBuild::SHIM8;
+}
+static_assert(mrphy::SHIM_MAXS_F32 == 8 && mrphy::SHIM_MAXS_F64 == 8, "shim_build: every capacity in every data type");
 template <AdjBuild B, typename T, typename CT>
 int run_fused_bwd(const AdjointReq& r, PulseOps in, hipStream_t st);
+
+// K2v and K2sh, the forwards of the builds MOVING and SHIM2 / 4 / 8 (tu_fused_moving_fwd.hip, tu_fused_shim2 / 4 / 8_fwd.hip):
+// K2 for spins at constant velocity, resp. with nS <= MS extra Bz field channels; one transmit coil, the extension by value
+template <AdjBuild B, typename T, typename CT>
+int run_rfgr_ext_fwd(const void* Mi, PulseOps in, BzExt x, void* Mo, void* Mck, int64_t ck_every, int64_t N, int64_t nM,
+                     int64_t nT, hipStream_t st);
 
 // K2ab / K2abb (tu_ab_rfgr_fwd.hip, tu_ab_rfgr_bwd.hip): Hargreaves' A, B of the fused family's operands, one transmit
 // coil, and the adjoint w.r.t. the pulse.  ABck (nCk, 4, N*nM, 3): the four columns' checkpoints, null for none
@@ -100,27 +117,6 @@ int run_ab_rfgr_mc_fwd(PulseOps in, void* A, void* B, void* ABck, int64_t ck_eve
 template <int MC, typename T, typename CT>
 int run_ab_rfgr_mc_bwd(const void* ABck, PulseOps in, const void* gA, const void* gB, void* grf, void* ggr, void* work,
                        int64_t N, int64_t nM, int64_t nT, int64_t nC, hipStream_t st);
-
-// K2v / K2vb (tu_fused_moving_fwd.hip, tu_fused_moving_bwd.hip): K2 / K2b for spins at constant velocity, one transmit
-// coil.  vdt (N, nM, 3): the displacement per step; step0: the steps played before this call.  The request is K2b's
-// plain one (gMo; gMi, grf, ggr; the workspace of mrphy_blochsim_rfgr_bwd_workspace)
-template <typename T, typename CT>
-int run_rfgr_moving_fwd(const void* Mi, PulseOps in, const void* vdt, int64_t step0, void* Mo, void* Mck,
-                        int64_t ck_every, int64_t N, int64_t nM, int64_t nT, hipStream_t st);
-
-template <typename T, typename CT>
-int run_rfgr_moving_bwd(const AdjointReq& r, PulseOps in, const void* vdt, int64_t step0, hipStream_t st);
-
-// K2sh / K2shb (tu_fused_shim{2,4,8}_fwd.hip, _bwd.hip): K2 / K2b with nS <= MS extra Bz field channels, one transmit
-// coil.  sh (N|1, nS, nT) with batch stride sh_sn, shMap (N nM, nS).  The request is K2b's plain one with the lead buffer
-// (N, 3 + nS, nT) as ggr and the workspace of mrphy_blochsim_rfgr_shim_bwd_workspace
-template <int MS, typename T, typename CT>
-int run_rfgr_shim_fwd(const void* Mi, PulseOps in, const void* sh, int64_t sh_sn, const void* shMap, int64_t nS, void* Mo,
-                      void* Mck, int64_t ck_every, int64_t N, int64_t nM, int64_t nT, hipStream_t st);
-
-template <int MS, typename T, typename CT>
-int run_rfgr_shim_bwd(const AdjointReq& r, PulseOps in, const void* sh, int64_t sh_sn, const void* shMap, int64_t nS,
-                      hipStream_t st);
 
 template <typename T, typename CT>
 int run_beff2ab(const void* Beff, Bc g, Bc E1, Bc E2, const void* E1m1, void* A, void* B, void* hist,

@@ -136,9 +136,10 @@ FusedBwdTrajArgs<T> fused_bwd_args(const AdjointReq& r, const PulseOps& in, int6
 
 // Host: the frame of every fused adjoint launch.  `waves` persistent one-wave blocks per batch entry; `kernel(grid)`
 // starts the caller's choice among its builds on that grid; then, if a pulse gradient is wanted, the second pass
-// sums the workspace rows of the grid's waves into ggr and the nC coils of grf.
+// sums the workspace rows of the grid's waves into the `lead` rows of ggr (grad_gr's three; K2shb: and grad_sh's) and
+// the nC coils of grf.
 template <typename T, typename K>
-int fused_bwd_launch(const AdjointReq& r, int64_t waves, hipStream_t st, K&& kernel)
+int fused_bwd_launch(const AdjointReq& r, int64_t waves, hipStream_t st, K&& kernel, int lead = 3)
 {
     dim3 grid;
     int e;
@@ -146,7 +147,7 @@ int fused_bwd_launch(const AdjointReq& r, int64_t waves, hipStream_t st, K&& ker
     kernel(grid);
     e = launch_status();
     if (e || !(r.grf || r.ggr)) return e;
-    return launch_p2<T>(r.work, r.ggr, 3, r.grf, r.nC, r.N, r.nT, grid.x, st);
+    return launch_p2<T>(r.work, r.ggr, lead, r.grf, r.nC, r.N, r.nT, grid.x, st);
 }
 
 template <bool RELAX, typename T, typename CT>

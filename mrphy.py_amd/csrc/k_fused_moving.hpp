@@ -2,7 +2,7 @@
 // Fragment: included INSIDE a translation unit's anonymous namespace, after host_common.hpp (HIP runtime,
 // include/mrphy_hip.h, geom.hpp, bloch_math.hpp, k_common.hpp).  Not a standalone header.
 #pragma once
-#include "k_fused_bwd_common.hpp"
+#include "k_fused_ext_fwd.hpp"
 
 // =============================================================================================
 // A spin that is at loc when step 0 begins and moves by w = vel dt per step sees, during step t of a call that starts
@@ -52,85 +52,28 @@ __device__ __forceinline__ void field_moving(T br, T bi, const PulseCP<T>& p, in
 }
 
 // ---------------------------------------------------------------------------------------------
-// K2v: the forward.  K2's frame (one block = one wave = 64 spins of one batch entry), operands, build axes CK x RELAX x
-// HB1 and step batches (8 steps, 4 in fp64, then a per-step tail).  The batch's tau is converted once; the steps add
-// their (compile-time) offset, which is exact.
+// K2v: the forward -- the frame of k_fused_ext_fwd.hpp with K2's step batches (8 steps, 4 in fp64).  The batch's tau is
+// converted once; the steps add their (compile-time) offset, which is exact.
 // ---------------------------------------------------------------------------------------------
 template <typename T>
-struct MovingFwdArgs {
-    const T* Mi;
-    PulseOpsT<T> in;
-    const T* vdt;  int64_t step0;                            // (N*nM, 3); steps played before this call
-    T* Mo;
-    T* Mck;  int64_t ck_every;
-    int64_t N, nM, nT;
+struct MovingExt {
+    struct Args { const T* vdt;  int64_t step0; };            // (N*nM, 3); steps played before this call
+    static Args args(const BzExt& x) { return {(const T*)x.vdt, x.step0}; }
+    static constexpr int BATCH = sizeof(T) == 8 ? 4 : 8;     // as K2's one-coil builds
+    using Lane = Motion<T>;
+    using Wave = int64_t;                                    // step0
+    using Tau = T;
+    static __device__ __forceinline__ Lane lane(const Args& x, int64_t row) { return load_motion<T>(x.vdt, row); }
+    static __device__ __forceinline__ Wave wave(const Args& x, int64_t, int64_t) { return x.step0; }
+    static __device__ __forceinline__ T batch(Wave step0, int64_t t) { return step_mid<T>(step0 + t); }
+    static __device__ __forceinline__ T step(T tb, int j) { return tb + T(j); }
+    template <bool HB1>
+    static __device__ __forceinline__ void field(T br, T bi, const PulseCP<T>& p, Wave, const Lane& w, int64_t t, T tau,
+                                                 const Spin<T>& sp, T& Bx, T& By, T& Bz)
+    {
+        field_moving<HB1>(br, bi, p, t, tau, sp, w, Bx, By, Bz);
+    }
 };
-
-template <typename T, typename CT, bool CK, bool RELAX, bool HB1>
-__global__ __launch_bounds__(WAVE) void k_bloch_rfgr_moving_fwd(MovingFwdArgs<T> a)
-{
-    constexpr int NS = sizeof(T) == 8 ? 4 : 8;               // as K2's one-coil builds
-    const int lane = threadIdx.x;
-    const int64_t n = blockIdx.y;
-    bool valid;
-    const int64_t s = lane_spin(blockIdx.x, lane, a.nM, valid);
-    const int64_t row = n * a.nM + s;
-    const SpinConst<T, CT> k = load_consts<T, CT>(a.in.g, a.in.E1, a.in.E2, a.in.E1m1, n, s);
-    T mx = a.Mi[row * 3], my = a.Mi[row * 3 + 1], mz = a.Mi[row * 3 + 2];
-    const Spin<T> sp = load_spin<T>(a.in, n, s, row);
-    const Motion<T> w = load_motion<T>(a.vdt, row);
-    T br, bi;
-    load_b1<HB1>(a.in.b1, row, br, bi);
-
-    const int64_t nT = a.nT, step0 = a.step0;
-    const PulseCP<T> pc = pulse_cp<T>(a.in, n, nT, 1);
-    const int64_t rows = a.N * a.nM;
-    // (the checkpoint build awaits the prologue's vector loads here, not in the loop header: k_fused_fwd.hpp)
-    if (CK) __builtin_amdgcn_s_waitcnt(0x0F70);              // vmcnt(0), expcnt / lgkmcnt untouched (gfx9 encoding)
-    int64_t ck_next = 0;
-    T* ckp = CK ? a.Mck + row * 3 : nullptr;
-    const int64_t ck_pitch = rows * 3;
-    int64_t t0 = 0;
-    for (; t0 + NS <= nT; t0 += NS) {
-        if (CK) ck_store(t0, valid, mx, my, mz, ckp, ck_pitch, ck_next, a.ck_every);
-        const T tb = step_mid<T>(step0 + t0);
-        T Bx[NS], By[NS], Bz[NS];
-#pragma unroll
-        for (int j = 0; j < NS; ++j) field_moving<HB1>(br, bi, pc, t0 + j, tb + T(j), sp, w, Bx[j], By[j], Bz[j]);
-        Rot<T> r[NS];
-        rot_prepare<T, CT, NS>(k, Bx, By, Bz, r);
-#pragma unroll
-        for (int j = 0; j < NS; ++j) rot_apply<RELAX, T, CT>(k, r[j], mx, my, mz);
-    }
-    for (; t0 < nT; ++t0) {                                   // nT % NS tail
-        if (CK) ck_store(t0, valid, mx, my, mz, ckp, ck_pitch, ck_next, a.ck_every);
-        T Bx[1], By[1], Bz[1];
-        field_moving<HB1>(br, bi, pc, t0, step_mid<T>(step0 + t0), sp, w, Bx[0], By[0], Bz[0]);
-        Rot<T> r[1];
-        rot_prepare<T, CT, 1>(k, Bx, By, Bz, r);
-        rot_apply<RELAX, T, CT>(k, r[0], mx, my, mz);
-    }
-    if (valid) { a.Mo[row * 3] = mx; a.Mo[row * 3 + 1] = my; a.Mo[row * 3 + 2] = mz; }
-}
-
-template <typename T, typename CT>
-int launch_k2v(const MovingFwdArgs<T>& a, hipStream_t st)
-{
-    // runs at nT == 0 too (Mo = Mi), as K2
-    dim3 grid;
-    int rc;
-    if (!fused_grid(a.N * a.nM, (a.nM + WAVE - 1) / WAVE, a.N, grid, rc)) return rc;
-#define MRPHY_K2V(CK_, RX_, HB_) \
-    hipLaunchKernelGGL((k_bloch_rfgr_moving_fwd<T, CT, CK_, RX_, HB_>), grid, dim3(WAVE), 0, st, a)
-#define MRPHY_K2V_HB(CK_, RX_) \
-    do { if (a.in.b1) MRPHY_K2V(CK_, RX_, true); else MRPHY_K2V(CK_, RX_, false); } while (0)
-    const bool ck = (a.Mck != nullptr), rx = (a.in.E1.p != nullptr);
-    if (ck) { if (rx) MRPHY_K2V_HB(true, true); else MRPHY_K2V_HB(true, false); }
-    else    { if (rx) MRPHY_K2V_HB(false, true); else MRPHY_K2V_HB(false, false); }
-#undef MRPHY_K2V_HB
-#undef MRPHY_K2V
-    return launch_status();
-}
 
 // ---------------------------------------------------------------------------------------------
 // K2vb: the adjoint w.r.t. Mi, rf, gr -- K2b's mode 0 (k_fused_bwd.hpp) with the moving field in the recompute and the
@@ -253,12 +196,12 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_moving_bwd(MovingBwdArgs<T>
 }
 
 template <typename T, typename CT>
-int launch_k2vb(const AdjointReq& r, const PulseOps& in, const void* vdt, int64_t step0, hipStream_t st)
+int launch_k2vb(const AdjointReq& r, const PulseOps& in, hipStream_t st)
 {
     return fused_bwd_launch<T>(r, k2b_waves(r.nM), st, [&](dim3 grid) {
         MovingBwdArgs<T> a;
         static_cast<FusedBwdArgs<T>&>(a) = fused_bwd_args<T>(r, in, grid.x);
-        a.vdt = (const T*)vdt; a.step0 = step0;
+        a.vdt = (const T*)r.ext.vdt; a.step0 = r.ext.step0;
 #define MRPHY_K2VB(RX_, HB_) \
     hipLaunchKernelGGL((k_bloch_rfgr_moving_bwd<T, CT, RX_, HB_>), grid, dim3(WAVE), 0, st, a)
         if (in.b1) { if (in.E1.p) MRPHY_K2VB(true, true);  else MRPHY_K2VB(false, true); }

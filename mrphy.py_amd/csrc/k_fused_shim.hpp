@@ -2,7 +2,7 @@
 // Fragment: included INSIDE a translation unit's anonymous namespace, after host_common.hpp (HIP runtime,
 // include/mrphy_hip.h, geom.hpp, bloch_math.hpp, k_common.hpp).  Not a standalone header.
 #pragma once
-#include "k_fused_bwd_common.hpp"
+#include "k_fused_ext_fwd.hpp"
 
 // =============================================================================================
 // nS channels, each a waveform sh[k, t] (wave-uniform, read with scalar loads as the pulse is) times a map shMap[k]
@@ -63,86 +63,38 @@ template <typename T, int MS>
 constexpr int shim_batch() { return (sizeof(T) == 8 ? 4 : 8) / (MS > 4 ? 2 : 1); }
 
 // ---------------------------------------------------------------------------------------------
-// K2sh: the forward.  K2's frame (one block = one wave = 64 spins of one batch entry), operands and build axes
-// CK x RELAX x HB1, at the capacities MS.
+// K2sh: the forward -- the frame of k_fused_ext_fwd.hpp at the capacities MS, shim_batch steps per batch.
 // ---------------------------------------------------------------------------------------------
-template <typename T>
-struct ShimFwdArgs {
-    const T* Mi;
-    PulseOpsT<T> in;
-    const T* sh;  int64_t sh_sn;                             // (N|1, nS, nT), batch stride (0: shared)
-    const T* shMap;  int64_t nS;                             // (N*nM, nS)
-    T* Mo;
-    T* Mck;  int64_t ck_every;
-    int64_t N, nM, nT;
+template <typename T, int MS>
+struct ShimExt {
+    struct Args {
+        const T* sh;  int64_t sh_sn;                         // (N|1, nS, nT), batch stride (0: shared)
+        const T* shMap;  int64_t nS;                         // (N*nM, nS)
+    };
+    static Args args(const BzExt& x) { return {(const T*)x.sh, x.sh_sn, (const T*)x.shMap, x.nS}; }
+    static constexpr int BATCH = shim_batch<T, MS>();
+    struct Lane { T sm[MS]; };
+    using Wave = ShimCP<T, MS>;
+    struct Tau {};                                           // the channels' field needs nothing of the batch
+    static __device__ __forceinline__ Lane lane(const Args& x, int64_t row)
+    {
+        Lane l;
+        load_shim_map<T, MS>(x.shMap, row, (int)x.nS, l.sm);
+        return l;
+    }
+    static __device__ __forceinline__ Wave wave(const Args& x, int64_t n, int64_t nT)
+    {
+        return shim_cp<T, MS>(x.sh, x.sh_sn, n, nT, (int)x.nS);
+    }
+    static __device__ __forceinline__ Tau batch(const Wave&, int64_t) { return {}; }
+    static __device__ __forceinline__ Tau step(Tau, int) { return {}; }
+    template <bool HB1>
+    static __device__ __forceinline__ void field(T br, T bi, const PulseCP<T>& p, const Wave& c, const Lane& l, int64_t t, Tau,
+                                                 const Spin<T>& sp, T& Bx, T& By, T& Bz)
+    {
+        field_shim<HB1, MS>(br, bi, p, c, t, sp, l.sm, Bx, By, Bz);
+    }
 };
-
-template <typename T, typename CT, bool CK, bool RELAX, bool HB1, int MS>
-__global__ __launch_bounds__(WAVE) void k_bloch_rfgr_shim_fwd(ShimFwdArgs<T> a)
-{
-    constexpr int NS = shim_batch<T, MS>();
-    const int lane = threadIdx.x;
-    const int64_t n = blockIdx.y;
-    bool valid;
-    const int64_t s = lane_spin(blockIdx.x, lane, a.nM, valid);
-    const int64_t row = n * a.nM + s;
-    const SpinConst<T, CT> k = load_consts<T, CT>(a.in.g, a.in.E1, a.in.E2, a.in.E1m1, n, s);
-    T mx = a.Mi[row * 3], my = a.Mi[row * 3 + 1], mz = a.Mi[row * 3 + 2];
-    const Spin<T> sp = load_spin<T>(a.in, n, s, row);
-    T sm[MS];
-    load_shim_map<T, MS>(a.shMap, row, (int)a.nS, sm);
-    T br, bi;
-    load_b1<HB1>(a.in.b1, row, br, bi);
-
-    const int64_t nT = a.nT;
-    const PulseCP<T> pc = pulse_cp<T>(a.in, n, nT, 1);
-    const ShimCP<T, MS> sc = shim_cp<T, MS>(a.sh, a.sh_sn, n, nT, (int)a.nS);
-    const int64_t rows = a.N * a.nM;
-    // (the checkpoint build awaits the prologue's vector loads here, not in the loop header: k_fused_fwd.hpp)
-    if (CK) __builtin_amdgcn_s_waitcnt(0x0F70);              // vmcnt(0), expcnt / lgkmcnt untouched (gfx9 encoding)
-    int64_t ck_next = 0;
-    T* ckp = CK ? a.Mck + row * 3 : nullptr;
-    const int64_t ck_pitch = rows * 3;
-    int64_t t0 = 0;
-    for (; t0 + NS <= nT; t0 += NS) {
-        if (CK) ck_store(t0, valid, mx, my, mz, ckp, ck_pitch, ck_next, a.ck_every);
-        T Bx[NS], By[NS], Bz[NS];
-#pragma unroll
-        for (int j = 0; j < NS; ++j) field_shim<HB1, MS>(br, bi, pc, sc, t0 + j, sp, sm, Bx[j], By[j], Bz[j]);
-        Rot<T> r[NS];
-        rot_prepare<T, CT, NS>(k, Bx, By, Bz, r);
-#pragma unroll
-        for (int j = 0; j < NS; ++j) rot_apply<RELAX, T, CT>(k, r[j], mx, my, mz);
-    }
-    for (; t0 < nT; ++t0) {                                   // nT % NS tail
-        if (CK) ck_store(t0, valid, mx, my, mz, ckp, ck_pitch, ck_next, a.ck_every);
-        T Bx[1], By[1], Bz[1];
-        field_shim<HB1, MS>(br, bi, pc, sc, t0, sp, sm, Bx[0], By[0], Bz[0]);
-        Rot<T> r[1];
-        rot_prepare<T, CT, 1>(k, Bx, By, Bz, r);
-        rot_apply<RELAX, T, CT>(k, r[0], mx, my, mz);
-    }
-    if (valid) { a.Mo[row * 3] = mx; a.Mo[row * 3 + 1] = my; a.Mo[row * 3 + 2] = mz; }
-}
-
-template <int MS, typename T, typename CT>
-int launch_k2sh(const ShimFwdArgs<T>& a, hipStream_t st)
-{
-    // runs at nT == 0 too (Mo = Mi), as K2
-    dim3 grid;
-    int rc;
-    if (!fused_grid(a.N * a.nM, (a.nM + WAVE - 1) / WAVE, a.N, grid, rc)) return rc;
-#define MRPHY_K2SH(CK_, RX_, HB_) \
-    hipLaunchKernelGGL((k_bloch_rfgr_shim_fwd<T, CT, CK_, RX_, HB_, MS>), grid, dim3(WAVE), 0, st, a)
-#define MRPHY_K2SH_HB(CK_, RX_) \
-    do { if (a.in.b1) MRPHY_K2SH(CK_, RX_, true); else MRPHY_K2SH(CK_, RX_, false); } while (0)
-    const bool ck = (a.Mck != nullptr), rx = (a.in.E1.p != nullptr);
-    if (ck) { if (rx) MRPHY_K2SH_HB(true, true); else MRPHY_K2SH_HB(true, false); }
-    else    { if (rx) MRPHY_K2SH_HB(false, true); else MRPHY_K2SH_HB(false, false); }
-#undef MRPHY_K2SH_HB
-#undef MRPHY_K2SH
-    return launch_status();
-}
 
 // ---------------------------------------------------------------------------------------------
 // K2shb: the adjoint w.r.t. Mi, rf, gr, sh.  K2b's persistent waves, checkpoints, prefetches, recompute and sweep with
@@ -316,21 +268,16 @@ __global__ __launch_bounds__(WAVE) void k_bloch_rfgr_shim_bwd(ShimBwdArgs<T> a)
 // The request is K2b's plain one with the lead buffer (N, 3 + nS, nT) in ggr's place; the second pass is K2b's with
 // nG = 3 + nS leading quantities
 template <int MS, typename T, typename CT>
-int launch_k2shb(const AdjointReq& r, const PulseOps& in, const void* sh, int64_t sh_sn, const void* shMap, int64_t nS,
-                 hipStream_t st)
+int launch_k2shb(const AdjointReq& r, const PulseOps& in, hipStream_t st)
 {
-    dim3 grid;
-    int e;
-    if (!fused_grid(r.N * r.nM * r.nT, k2b_waves(r.nM), r.N, grid, e)) return e;
-    ShimBwdArgs<T> a;
-    static_cast<FusedBwdArgs<T>&>(a) = fused_bwd_args<T>(r, in, grid.x);
-    a.sh = (const T*)sh; a.sh_sn = sh_sn; a.shMap = (const T*)shMap; a.nS = nS;
+    return fused_bwd_launch<T>(r, k2b_waves(r.nM), st, [&](dim3 grid) {
+        ShimBwdArgs<T> a;
+        static_cast<FusedBwdArgs<T>&>(a) = fused_bwd_args<T>(r, in, grid.x);
+        a.sh = (const T*)r.ext.sh; a.sh_sn = r.ext.sh_sn; a.shMap = (const T*)r.ext.shMap; a.nS = r.ext.nS;
 #define MRPHY_K2SHB(RX_, HB_) \
     hipLaunchKernelGGL((k_bloch_rfgr_shim_bwd<T, CT, RX_, HB_, MS>), grid, dim3(WAVE), 0, st, a)
-    if (in.b1) { if (in.E1.p) MRPHY_K2SHB(true, true);  else MRPHY_K2SHB(false, true); }
-    else       { if (in.E1.p) MRPHY_K2SHB(true, false); else MRPHY_K2SHB(false, false); }   // no b1 map: Bxy = rf
+        if (in.b1) { if (in.E1.p) MRPHY_K2SHB(true, true);  else MRPHY_K2SHB(false, true); }
+        else       { if (in.E1.p) MRPHY_K2SHB(true, false); else MRPHY_K2SHB(false, false); }   // no b1 map: Bxy = rf
 #undef MRPHY_K2SHB
-    e = launch_status();
-    if (e || !(r.grf || r.ggr)) return e;
-    return launch_p2<T>(r.work, r.ggr, 3 + (int)nS, r.grf, 1, r.N, r.nT, grid.x, st);
+    }, 3 + (int)r.ext.nS);
 }

@@ -91,6 +91,15 @@ def _ptr(x):
     return x.data_ptr() if isinstance(x, Tensor) else x
 
 
+def _launch(name, device, *args):
+    r"""Entry point ``name`` of the library on ``device`` and its current stream: ``args`` (a tensor passes as its
+    address) followed by the stream; a non-zero return code raises."""
+    lib = _lib.require_library()
+    with torch.cuda.device(device):
+        rc = getattr(lib, name)(*(_ptr(x) for x in args), _host.current_stream(device))
+    _lib.check(rc, name)
+
+
 def _forward_prep(lib, p, γ2πdt, E1, E2, E1_1, dtype, device, need):
     r"""What the two forwards share: the step constants and, if ``need``, the checkpoints the fused adjoint recomputes
     from.  Returns ``(code, alive, consts, Mck, ckpt)``: the dtype code, the constants' tensors (kept alive with
@@ -160,9 +169,12 @@ class _Saved(NamedTuple):
     code: int                 # the dtype code
     consts: tuple             # the constants' arguments g .. E1m1, pointing into ...
     alive: tuple              # ... these (g, E1, E2, E1m1; the signal: and rx)
-    every: Optional[int]      # the call's integer argument: None: the plain call; the record stride; the moving call's step0
+    every: Optional[int]      # None: the plain call; else the record stride
     rx: tuple                 # the signal: (rx's pointer or None,), and the coil count for an array; else ()
     likes: dict               # _likes of the operands whose gradients the backward shapes, by argument name
+    # a Bz-extended call: what it hands the library besides, by name and in the entry points' order (its tensors are kept
+    # alive here) -- vdt, step0 (moving); sh, sh_sn, shMap, nS (shim)
+    ext: dict = {}
 
 
 SEG = 16                  # steps per checkpoint segment: mrphy_blochsim_rfgr_ck_every() (csrc/geom.hpp)
@@ -174,10 +186,8 @@ _PULSE_OUT = ('gMi', 'grf', 'ggr')
 _AB_OUT = ('gA', 'gB', 'grf', 'ggr')
 _ADJOINT_ARGS = {
     'mrphy_blochsim_rfgr_bwd': ('gMo', *_PULSE_OUT),
-    'mrphy_blochsim_rfgr_moving_bwd': ('vdt', 'every', 'gMo', *_PULSE_OUT),         # (`every`: its step0, see _Saved)
-    # (its integers under the table's two integer names -- `every`: sh's batch stride, `nRx`: nS; `ggr`: the lead buffer
-    # (N, 3 + nS, nT); the call is BlochSimRfGrShimHIP.backward's own, with its own workspace)
-    'mrphy_blochsim_rfgr_shim_bwd': ('sh', 'every', 'shMap', 'nRx', 'gMo', *_PULSE_OUT),
+    'mrphy_blochsim_rfgr_moving_bwd': ('vdt', 'step0', 'gMo', *_PULSE_OUT),
+    'mrphy_blochsim_rfgr_shim_bwd': ('sh', 'sh_sn', 'shMap', 'nS', 'gMo', *_PULSE_OUT),   # (`ggr`: the lead buffer)
     'mrphy_blochsim_rfgr_traj_bwd': ('gMt', 'every', *_PULSE_OUT),
     'mrphy_blochsim_rfgr_mc_bwd': ('gMo', *_PULSE_OUT),
     'mrphy_blochsim_rfgr_mc_traj_bwd': ('gMt', 'every', *_PULSE_OUT),
@@ -190,6 +200,13 @@ _ADJOINT_ARGS = {
     'mrphy_ab_rfgr_mc_bwd': _AB_OUT,
     'mrphy_ab_rfgr_maps_bwd': (*_AB_OUT, 'gloc', 'gBz', 'gb1'),
     'mrphy_ab_rfgr_consts_bwd': (*_AB_OUT, 'gloc', 'gBz', 'gb1', 'gC'),
+}
+# The Bz-extended families -- one transmit coil, the pulse gradient only (:func:`_decide_ext_route`): the adjoint entry
+# point, its workspace query and what the query takes after ``code, N, nM, nT``, by the names of ``_Saved.ext``.  With
+# ``nS`` channels ``ggr`` is the lead buffer `(N, 3 + nS, nT)`: ``grad_gr``'s rows, then ``grad_sh``'s.
+_EXT_FAMILIES = {
+    'moving': ('mrphy_blochsim_rfgr_moving_bwd', 'mrphy_blochsim_rfgr_bwd_workspace', ()),
+    'shim': ('mrphy_blochsim_rfgr_shim_bwd', 'mrphy_blochsim_rfgr_shim_bwd_workspace', ('nS',)),
 }
 
 
@@ -204,9 +221,9 @@ def _adjoint_name(family, spin, mc, mrx, traj):
     (the CONSTS builds form the map sums too), ``'maps_'`` or ``''``; ``mc``: parallel transmit, where a map or constants'
     gradient is never wanted (:func:`_decide_route`, :func:`_decide_ab_route`); the signal's builds take one receive coil
     and an array alike, ``mrx`` says which the plain one is asked for."""
-    if family == 'moving':      # one transmit coil, the pulse gradient only (:func:`_decide_moving_route`)
-        assert not (mc or spin or traj), "fused.blochsim_rfgr_moving: the adjoint w.r.t. Mi, rf, gr of one transmit coil"
-        return 'mrphy_blochsim_rfgr_moving_bwd'
+    if family in _EXT_FAMILIES:
+        assert not (mc or spin or traj), f"fused.blochsim_rfgr_{family}: the adjoint w.r.t. the pulse of one transmit coil"
+        return _EXT_FAMILIES[family][0]
     if family == 'signal':
         return 'mrphy_signal_rfgr_' + ('consts_' if spin == 'consts_' else 'mrx_' if mrx else '') + 'bwd'
     if family == 'ab':
@@ -215,16 +232,17 @@ def _adjoint_name(family, spin, mc, mrx, traj):
     return 'mrphy_blochsim_rfgr_' + (spin or ('mc_' if mc else '') + ('traj_' if traj else '')) + 'bwd'
 
 
-def _fused_adjoint(s, Mck, family, want, gMo=None, gMt=None, gsig=None, gA=None, gB=None, vdt=None):
-    r"""The one adjoint call of the four Functions: ``s`` the forward's :class:`_Saved`, ``Mck`` its checkpoints,
-    ``family`` 'blochsim', 'moving', 'signal' or 'ab', ``want`` the gradients wanted by argument name, ``gMo``, ``gMt``,
-    ``gsig`` (``ab``: ``gA``, ``gB``) the cotangents received (contiguous, of the kernels' dtype), ``vdt`` the moving call's
-    displacement per step (its ``step0`` is ``s.every``).  Returns the raw gradients
-    ``{name: tensor, or None where not wanted}``: per spin ``gMi`` (not ``ab``: it has no ``Mi``), ``gloc``, ``gBz`` (for
-    ``Δf`` and ``γ_beff``), ``gb1``, ``gC``; per pulse ``grf`` `(N, 2, nT, nC)`, ``ggr`` `(N, 3, nT)`."""
+def _fused_adjoint(s, Mck, family, want, gMo=None, gMt=None, gsig=None, gA=None, gB=None):
+    r"""The one adjoint call of the six Functions: ``s`` the forward's :class:`_Saved`, ``Mck`` its checkpoints,
+    ``family`` 'blochsim', 'moving', 'shim', 'signal' or 'ab', ``want`` the gradients wanted by argument name, ``gMo``,
+    ``gMt``, ``gsig`` (``ab``: ``gA``, ``gB``) the cotangents received (contiguous, of the kernels' dtype).  Returns the raw
+    gradients ``{name: tensor, or None where not wanted}``: per spin ``gMi`` (not ``ab``: it has no ``Mi``), ``gloc``,
+    ``gBz`` (for ``Δf`` and ``γ_beff``), ``gb1``, ``gC``; per pulse ``grf`` `(N, 2, nT, nC)`, ``ggr`` `(N, 3, nT)` -- the shim
+    call's lead buffer `(N, 3 + nS, nT)`, there when ``gr`` or ``sh`` wants a gradient."""
     lib = _lib.require_library()
     p, device, full = s.p, Mck.device, (s.p.N,) + s.p.Nd
-    outs = dict(gMi=(want.get('Mi'), full + (3,)), grf=(want['rf'], (p.N, 2, p.nT, p.nC)), ggr=(want['gr'], (p.N, 3, p.nT)),
+    outs = dict(gMi=(want.get('Mi'), full + (3,)), grf=(want['rf'], (p.N, 2, p.nT, p.nC)),
+                ggr=(want['gr'] or want.get('sh'), (p.N, 3 + s.ext.get('nS', 0), p.nT)),
                 gloc=(want.get('loc'), full + (3,)), gBz=(want.get('Δf') or _need_γb(want, p), full),
                 gb1=(want.get('b1Map'), full + (2,)), gC=(any(want[k] for k in _CONSTS), full + (4,)))
     out = {k: torch.empty(shape, dtype=Mck.dtype, device=device) if w else None for k, (w, shape) in outs.items()}
@@ -239,29 +257,32 @@ def _fused_adjoint(s, Mck, family, want, gMo=None, gMt=None, gsig=None, gA=None,
     mc, mrx = p.nC != 1, len(s.rx) > 1
     name = _adjoint_name(family, 'consts_' if out['gC'] is not None else
                          'maps_' if any(out[k] is not None for k in ('gloc', 'gBz', 'gb1')) else '', mc, mrx, gMt is not None)
-    nbytes = int((lib.mrphy_ab_rfgr_mc_bwd_workspace if family == 'ab' else lib.mrphy_blochsim_rfgr_mc_bwd_workspace)(
-                     s.code, p.N, p.nM, p.nT, p.nC) if mc    # per-coil sums
-                 else lib.mrphy_blochsim_rfgr_bwd_workspace(s.code, p.N, p.nM, p.nT))
-    work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+    query, extra = _EXT_FAMILIES[family][1:] if family in _EXT_FAMILIES else (
+        ('mrphy_ab_rfgr_mc_bwd_workspace' if family == 'ab' else 'mrphy_blochsim_rfgr_mc_bwd_workspace', ('nC',)) if mc
+        else ('mrphy_blochsim_rfgr_bwd_workspace', ()))                      # (`mc`: per-coil sums)
     vals = dict(out, gMo=gMo, gMt=gMt, gsig=gsig, gA=gA, gB=gB, every=s.every or 0, rx=s.rx[0] if s.rx else None,
-                nRx=s.rx[1] if mrx else 1, vdt=vdt)
-    with torch.cuda.device(device):
-        rc = getattr(lib, name)(s.code, Mck.data_ptr(), *p.k0_args(), *s.consts,
-                                *(_ptr(vals[k]) for k in _ADJOINT_ARGS[name]), work.data_ptr(), work.numel(),
-                                p.N, p.nM, p.nT, *((p.nC,) if mc else ()), _host.current_stream(device))
-    _lib.check(rc, name)
+                nRx=s.rx[1] if mrx else 1, nC=p.nC, **s.ext)
+    nbytes = int(getattr(lib, query)(s.code, p.N, p.nM, p.nT, *(vals[k] for k in extra)))
+    work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+    _launch(name, device, s.code, Mck, *p.k0_args(), *s.consts, *(vals[k] for k in _ADJOINT_ARGS[name]), work, work.numel(),
+            p.N, p.nM, p.nT, *((p.nC,) if mc else ()))
     return out
 
 
 def _fold_grads(raw, s, want):
     r"""``{argument name: gradient}`` from the raw gradients of :func:`_fused_adjoint`, in the shapes and dtypes the
-    caller's operands had: ``Mi``, ``rf``, ``gr``, the step constants, the spin-side maps and ``γ_beff`` -- what the three
-    backwards return."""
+    caller's operands had: ``Mi``, ``rf``, ``gr``, the shim call's ``sh``, the step constants, the spin-side maps and
+    ``γ_beff`` -- what the backwards return."""
     from .beffective import _fold_pulse_grad
     g = dict(Mi=raw['gMi'])
-    for k, raw_k, no_b1 in (('rf', 'grf', s.p.b1 is None), ('gr', 'ggr', False)):
-        if raw[raw_k] is not None:
-            g[k] = _fold_pulse_grad(raw[raw_k], s.likes[k][0], s.likes[k][1], no_b1)
+    fold = lambda x, k, no_b1=False: _fold_pulse_grad(x, s.likes[k][0], s.likes[k][1], no_b1)  # noqa: E731
+    lead = raw['ggr']                           # grad_gr's three rows; the shim call's lead buffer: then grad_sh's
+    if raw['grf'] is not None:
+        g['rf'] = fold(raw['grf'], 'rf', s.p.b1 is None)
+    if lead is not None and want['gr']:
+        g['gr'] = fold(lead[:, :3], 'gr')
+    if lead is not None and want.get('sh'):
+        g['sh'] = fold(lead[:, 3:], 'sh').to(s.likes['sh'][2])
     if raw['gC'] is not None:
         g.update(zip(_CONSTS, _fold_const_grads(raw['gC'], s.p, [s.likes.get(k) for k in _CONSTS],
                                                 [want[k] for k in _CONSTS])))
@@ -304,13 +325,10 @@ class BlochSimRfGrHIP(Function):
         M = (torch.empty((-(-p.nT // every), p.N) + p.Nd + (3,), dtype=dtype, device=device) if traj
              else torch.empty_like(Mi_c))
         # the trajectory's Mo is optional (it equals the last record): not asked for
-        name, outs = (('mrphy_blochsim_rfgr_traj_fwd', (None, *ckpt, M.data_ptr(), every)) if traj
-                      else ('mrphy_blochsim_rfgr_fwd', (M.data_ptr(), *ckpt)))
-        with torch.cuda.device(device):
-            rc = getattr(lib, name)(code, Mi_c.data_ptr(), *p.k0_args(), *consts, *outs,
-                                    p.N, p.nM, p.nT, p.nC, _host.current_stream(device))
-        _lib.check(rc, name)
-        if Mck is not None:                     # the checkpoints: a backward is wanted
+        name, outs = (('mrphy_blochsim_rfgr_traj_fwd', (None, *ckpt, M, every)) if traj
+                      else ('mrphy_blochsim_rfgr_fwd', (M, *ckpt)))
+        _launch(name, device, code, Mi_c, *p.k0_args(), *consts, *outs, p.N, p.nM, p.nT, p.nC)
+        if Mck is not None:                    # the checkpoints: a backward is wanted
             ctx.save_for_backward(Mck)
             ctx.saved = _Saved(p, code, consts, alive, every, (), _likes(
                 rf=rf, gr=gr, loc=loc, Δf=Δf, b1Map=b1Map, γ_beff=γ_beff, γ2πdt=γ2πdt, E1=E1, E2=E2, E1_1=E1_1))
@@ -662,55 +680,63 @@ with one transmit coil the fused adjoint returns the step constants' gradients p
     return out
 
 
+def _ext_forward(ctx, name, Mi, p, step_consts, want_ckpt, ext, likes):
+    r"""The forward of the two Bz-extended Functions: :class:`BlochSimRfGrHIP`'s plain one with ``ext``'s values -- what the
+    entry point ``name`` takes between the constants and ``Mo``, by name and in its order -- which the backward gets as
+    ``_Saved.ext``."""
+    device, dtype = Mi.device, Mi.dtype
+    code, alive, consts, Mck, ckpt = _forward_prep(_lib.require_library(), p, *step_consts, dtype, device, bool(want_ckpt))
+    Mi_c = Mi.detach().contiguous()
+    Mo = torch.empty_like(Mi_c)
+    _launch(name, device, code, Mi_c, *p.k0_args(), *consts, *ext.values(), Mo, *ckpt, p.N, p.nM, p.nT, p.nC)
+    if Mck is not None:                         # the checkpoints: a backward is wanted
+        ctx.save_for_backward(Mck)
+        ctx.saved = _Saved(p, code, consts, alive, None, (), likes, ext)
+    return Mo
+
+
+def _ext_backward(ctx, Fn, family, grad_Mo):
+    r"""The backward of the two Bz-extended Functions ``Fn``: the one adjoint call of ``family`` and its folds."""
+    want = dict(zip(Fn.ARGS, ctx.needs_input_grad))
+    if not any(want.values()):
+        return tuple(None for _ in Fn.ARGS)
+    s = ctx.saved
+    (Mck,) = ctx.saved_tensors
+    _host.require_invertible_relaxation(s.code, s.alive[1], s.alive[2], 'fused.blochsim_rfgr_' + family)
+    gMo = grad_Mo.to(Mck.dtype).contiguous()
+    g = _fold_grads(_fused_adjoint(s, Mck, family, want, gMo=gMo), s, want)
+    return tuple(g.get(k) for k in Fn.ARGS)
+
+
 class BlochSimRfGrMovingHIP(Function):
     r"""``Mo = BlochSimRfGrMovingHIP.apply(Mi, rf, gr, pulse_on_spins, vdt, step0, γ2πdt, E1, E2, E1_1, want_ckpt)``
 
     :class:`BlochSimRfGrHIP`'s plain call for spins that move: ``vdt`` `(N, *Nd, xyz)` contiguous, of the kernels' dtype,
     is the displacement per step, ``step0`` the number of steps played before this call
     (``mrphy_blochsim_rfgr_moving_fwd`` / ``_bwd``, one transmit coil).  Differentiable w.r.t. ``Mi``, ``rf`` and ``gr``;
-    ``want_ckpt`` is the caller's decision (:func:`_decide_moving_route`), as there."""
+    ``want_ckpt`` is the caller's decision (:func:`_decide_ext_route`), as there."""
 
     ARGS = ('Mi', 'rf', 'gr', 'p', 'vdt', 'step0', 'γ2πdt', 'E1', 'E2', 'E1_1', 'want_ckpt')
 
     @staticmethod
     def forward(ctx, Mi, rf, gr, p, vdt, step0, γ2πdt, E1, E2, E1_1, want_ckpt=False):
-        lib = _lib.require_library()
-        device, dtype = Mi.device, Mi.dtype
-        code, alive, consts, Mck, ckpt = _forward_prep(lib, p, γ2πdt, E1, E2, E1_1, dtype, device, bool(want_ckpt))
-        Mi_c = Mi.detach().contiguous()
-        Mo = torch.empty_like(Mi_c)
-        name = 'mrphy_blochsim_rfgr_moving_fwd'
-        with torch.cuda.device(device):
-            rc = getattr(lib, name)(code, Mi_c.data_ptr(), *p.k0_args(), *consts, vdt.data_ptr(), step0, Mo.data_ptr(),
-                                    *ckpt, p.N, p.nM, p.nT, p.nC, _host.current_stream(device))
-        _lib.check(rc, name)
-        if Mck is not None:                     # the checkpoints: a backward is wanted
-            ctx.save_for_backward(Mck)
-            ctx.saved = _Saved(p, code, consts, alive, step0, (), _likes(rf=rf, gr=gr))
-            ctx.vdt = vdt
-        return Mo
+        return _ext_forward(ctx, 'mrphy_blochsim_rfgr_moving_fwd', Mi, p, (γ2πdt, E1, E2, E1_1), want_ckpt,
+                            dict(vdt=vdt, step0=step0), _likes(rf=rf, gr=gr))
 
     @staticmethod
     def backward(ctx, grad_Mo):
-        ARGS = BlochSimRfGrMovingHIP.ARGS
-        want = dict(zip(ARGS, ctx.needs_input_grad))
-        if not any(want.values()):
-            return tuple(None for _ in ARGS)
-        s = ctx.saved
-        (Mck,) = ctx.saved_tensors
-        _host.require_invertible_relaxation(s.code, s.alive[1], s.alive[2], 'fused.blochsim_rfgr_moving')
-        gMo = grad_Mo.to(Mck.dtype).contiguous()
-        g = _fold_grads(_fused_adjoint(s, Mck, 'moving', want, gMo=gMo, vdt=ctx.vdt), s, want)
-        return tuple(g.get(k) for k in ARGS)
+        return _ext_backward(ctx, BlochSimRfGrMovingHIP, 'moving', grad_Mo)
 
 
-def _decide_moving_route(*, nT, seg, one_coil, pulse_grad, other_grad):
-    r"""The route of :func:`blochsim_rfgr_moving` as a function of plain facts (``pulse_grad``: ``Mi``, ``rf`` or ``gr``
-    requires grad; ``other_grad``: ``vel``, ``loc``, ``Δf``, ``b1Map``, ``γ_beff``, ``T1``, ``T2``, ``γ``, ``dt`` or an entry
-    of ``consts`` does): ``('fused', want_ckpt)`` -- one transmit coil and either no gradient, at any length, or pulse
-    gradients over whole checkpoint segments; ``('split', n1)`` -- such gradients, more than one segment's steps and a
-    ragged last one: the first ``n1`` steps fused, the tail composed; ``('composed', None)`` -- everything else."""
-    if not one_coil or other_grad:
+def _decide_ext_route(*, nT, seg, one_coil, fits, pulse_grad, other_grad):
+    r"""The route of :func:`blochsim_rfgr_moving` and :func:`blochsim_rfgr_shim` as a function of plain facts (``fits``:
+    the kernels take the extension -- the ``nS >= 1`` channels are no more than one launch takes; motion always does;
+    ``pulse_grad``: ``Mi``, ``rf``, ``gr`` or ``sh`` requires grad; ``other_grad``: ``vel``, ``shMap``, ``loc``, ``Δf``,
+    ``b1Map``, ``γ_beff``, ``T1``, ``T2``, ``γ``, ``dt`` or an entry of ``consts`` does): ``('fused', want_ckpt)`` -- one
+    transmit coil, an extension that fits and either no gradient, at any length, or pulse gradients over whole checkpoint
+    segments; ``('split', n1)`` -- such gradients, more than one segment's steps and a ragged last one: the first ``n1``
+    steps fused, the tail composed; ``('composed', None)`` -- everything else."""
+    if not one_coil or not fits or other_grad:
         return 'composed', None
     if not pulse_grad:
         return 'fused', False
@@ -719,6 +745,44 @@ def _decide_moving_route(*, nT, seg, one_coil, pulse_grad, other_grad):
     if nT > seg:
         return 'split', (nT // seg) * seg
     return 'composed', None
+
+
+# The two routes under the names and facts they had as functions of their own (``nS`` channels against the capacity ``cap``
+# of one launch): host tests written against those names keep importing them.
+def _decide_moving_route(**facts):
+    return _decide_ext_route(fits=True, **facts)
+
+
+def _decide_shim_route(*, nS, cap, **facts):
+    return _decide_ext_route(fits=nS <= cap, **facts)
+
+
+def _bz_extended(Mi, rf, gr, loc, kw, *, fits, pulse_grad, other_grad, bz, again, apply):
+    r"""What :func:`blochsim_rfgr_moving` and :func:`blochsim_rfgr_shim` do once their own arguments are checked: the
+    facts, the route (:func:`_decide_ext_route`; ``fits`` as there, ``pulse_grad`` / ``other_grad``: an operand of the
+    extension's own wants a gradient the kernels form / do not form) and the route taken.  Split:
+    ``again(M, slice, n0)`` re-issues the call from ``M`` on that slice of the time axis, ``n0`` steps into the pulse.
+    Composed: ``rfgr2beff``, ``bz(beff)`` -- what the extension adds to its z component -- then ``blochsim``.  Fused:
+    ``apply(p, step_constants, want_ckpt)``, the extension's Function."""
+    from . import beffective, sims, slowsims
+    assert (kw['T1'] is None) == (kw['T2'] is None)
+    f = _pulse_facts(rf, gr, loc, kw, Mi)
+    p = f.p
+    route, arg = _decide_ext_route(nT=p.nT, seg=SEG, one_coil=f.one_coil, fits=fits, pulse_grad=f.pulse_grad or pulse_grad,
+                                   other_grad=f.maps_grad or f.consts_grad or other_grad)
+    if route == 'split':
+        return again(again(Mi, slice(None, arg), 0), slice(arg, None), arg)
+    if route == 'composed':
+        beff = beffective.rfgr2beff(rf, gr, loc, Δf=kw['Δf'], b1Map=kw['b1Map'], γ=kw['γ_beff'], lazy=False)
+        beff = beff + torch.nn.functional.pad(bz(beff).unsqueeze(-1), (2, 0))   # out of place: beff may be saved upstream
+        if kw['consts'] is not None:
+            return sims.blochsim_consts(Mi, beff, **kw['consts'])
+        return slowsims.blochsim(Mi, beff, T1=kw['T1'], T2=kw['T2'], γ=kw['γ'], dt=kw['dt'])
+    device, dtype = Mi.device, Mi.dtype
+    assert p.device == device and p.dtype == dtype, "Mi and loc must share device and dtype"
+    assert tuple(Mi.shape[:-1]) == (p.N,) + p.Nd
+    assert int(_lib.require_library().mrphy_blochsim_rfgr_ck_every()) == SEG
+    return apply(p, _step_constants(kw, False, 1 + len(p.Nd) + 2, device), arg)
 
 
 def _check_moving(Mi, gr, loc, vel, step0):
@@ -790,36 +854,21 @@ def blochsim_rfgr_moving(
     spins; gradients w.r.t. ``vel``, ``loc`` and the maps inside the kernel; parallel transmit inside the kernel; a binding
     of ``SpinBolus`` (there is no body to bind); a CPU path.
     """
-    from . import beffective, sims, slowsims
     _check_moving(Mi, gr, loc, vel, step0)
     _host.require_device_tensor(Mi, 'Mi')
     _host.require_device_tensor(vel, 'vel')
-    assert (T1 is None) == (T2 is None)
     kw = dict(Δf=Δf, b1Map=b1Map, γ_beff=γ_beff, T1=T1, T2=T2, γ=γ, dt=dt, consts=consts)
-    f = _pulse_facts(rf, gr, loc, kw, Mi)
-    p = f.p
-    other_grad = f.maps_grad or f.consts_grad or any(_requires_grad(x) for x in (vel, γ_beff, dt))
-    route, arg = _decide_moving_route(nT=p.nT, seg=SEG, one_coil=f.one_coil, pulse_grad=f.pulse_grad,
-                                      other_grad=other_grad)
-    if route == 'split':
-        M1 = blochsim_rfgr_moving(Mi, rf[:, :, :arg], gr[:, :, :arg], loc, vel, step0=step0, **kw)
-        return blochsim_rfgr_moving(M1, rf[:, :, arg:], gr[:, :, arg:], loc, vel, step0=step0 + arg, **kw)
-    if route == 'composed':
-        beff = beffective.rfgr2beff(rf, gr, loc, Δf=Δf, b1Map=b1Map, γ=γ_beff, lazy=False)
-        z = _moving_bz(gr, _vel_dt(vel, dt, loc), step0)
-        beff = beff + torch.nn.functional.pad(z.unsqueeze(-1), (2, 0))      # out of place: beff may be saved upstream
-        if consts is not None:
-            return sims.blochsim_consts(Mi, beff, **consts)
-        return slowsims.blochsim(Mi, beff, T1=T1, T2=T2, γ=γ, dt=dt)
-    device, dtype = Mi.device, Mi.dtype
-    assert p.device == device and p.dtype == dtype, "Mi and loc must share device and dtype"
-    assert tuple(Mi.shape[:-1]) == (p.N,) + p.Nd
-    lib = _lib.require_library()
-    assert int(lib.mrphy_blochsim_rfgr_ck_every()) == SEG
-    γ2πdt, E1, E2, E1_1 = _step_constants(kw, False, 1 + len(p.Nd) + 2, device)
-    with torch.no_grad():
-        vdt = _vel_dt(vel.to(device), dt, loc).contiguous()
-    return BlochSimRfGrMovingHIP.apply(Mi, rf, gr, p, vdt, step0, γ2πdt, E1, E2, E1_1, arg)
+
+    def apply(p, step_consts, want_ckpt):
+        with torch.no_grad():
+            vdt = _vel_dt(vel.to(Mi.device), dt, loc).contiguous()
+        return BlochSimRfGrMovingHIP.apply(Mi, rf, gr, p, vdt, step0, *step_consts, want_ckpt)
+
+    return _bz_extended(
+        Mi, rf, gr, loc, kw, fits=True, pulse_grad=False, other_grad=any(_requires_grad(x) for x in (vel, γ_beff, dt)),
+        bz=lambda beff: _moving_bz(gr, _vel_dt(vel, dt, loc), step0),
+        again=lambda M, sl, n0: blochsim_rfgr_moving(M, rf[:, :, sl], gr[:, :, sl], loc, vel, step0=step0 + n0, **kw),
+        apply=apply)
 
 
 class BlochSimRfGrShimHIP(Function):
@@ -828,90 +877,20 @@ class BlochSimRfGrShimHIP(Function):
     :class:`BlochSimRfGrHIP`'s plain call with ``nS`` extra Bz field channels: ``sh`` `(N ⊻ 1, nS, nT)` their waveforms,
     ``shMap`` `(N, nM, nS)` contiguous, of the kernels' dtype, their maps (``mrphy_blochsim_rfgr_shim_fwd`` / ``_bwd``, one
     transmit coil, ``nS`` within ``mrphy_blochsim_rfgr_shim_max_channels``).  Differentiable w.r.t. ``Mi``, ``rf``, ``gr`` and
-    ``sh``; ``want_ckpt`` is the caller's decision (:func:`_decide_shim_route`), as there."""
+    ``sh``; ``want_ckpt`` is the caller's decision (:func:`_decide_ext_route`), as there."""
 
     ARGS = ('Mi', 'rf', 'gr', 'sh', 'p', 'shMap', 'γ2πdt', 'E1', 'E2', 'E1_1', 'want_ckpt')
 
     @staticmethod
     def forward(ctx, Mi, rf, gr, sh, p, shMap, γ2πdt, E1, E2, E1_1, want_ckpt=False):
-        lib = _lib.require_library()
-        device, dtype = Mi.device, Mi.dtype
-        code, alive, consts, Mck, ckpt = _forward_prep(lib, p, γ2πdt, E1, E2, E1_1, dtype, device, bool(want_ckpt))
-        Mi_c = Mi.detach().contiguous()
-        Mo = torch.empty_like(Mi_c)
-        sh_c = sh.detach().to(device=device, dtype=dtype).contiguous()
-        nS = sh_c.shape[1]
-        sha = (sh_c.data_ptr(), sh_c.stride(0) if (sh_c.shape[0] == p.N and p.N > 1) else 0, shMap.data_ptr(), nS)
-        name = 'mrphy_blochsim_rfgr_shim_fwd'
-        with torch.cuda.device(device):
-            rc = getattr(lib, name)(code, Mi_c.data_ptr(), *p.k0_args(), *consts, *sha, Mo.data_ptr(), *ckpt,
-                                    p.N, p.nM, p.nT, p.nC, _host.current_stream(device))
-        _lib.check(rc, name)
-        if Mck is not None:                     # the checkpoints: a backward is wanted
-            ctx.save_for_backward(Mck)
-            ctx.saved = _Saved(p, code, consts, alive, None, (), _likes(rf=rf, gr=gr, sh=sh))
-            ctx.sh, ctx.shMap, ctx.sha = sh_c, shMap, sha
-        return Mo
+        sh_c = sh.detach().to(device=Mi.device, dtype=Mi.dtype).contiguous()
+        sh_sn = sh_c.stride(0) if (sh_c.shape[0] == p.N and p.N > 1) else 0
+        return _ext_forward(ctx, 'mrphy_blochsim_rfgr_shim_fwd', Mi, p, (γ2πdt, E1, E2, E1_1), want_ckpt,
+                            dict(sh=sh_c, sh_sn=sh_sn, shMap=shMap, nS=sh_c.shape[1]), _likes(rf=rf, gr=gr, sh=sh))
 
     @staticmethod
     def backward(ctx, grad_Mo):
-        from .beffective import _fold_pulse_grad
-        ARGS = BlochSimRfGrShimHIP.ARGS
-        want = dict(zip(ARGS, ctx.needs_input_grad))
-        if not any(want.values()):
-            return tuple(None for _ in ARGS)
-        lib = _lib.require_library()
-        s = ctx.saved
-        (Mck,) = ctx.saved_tensors
-        p, device, nS = s.p, Mck.device, ctx.sha[3]
-        _host.require_invertible_relaxation(s.code, s.alive[1], s.alive[2], 'fused.blochsim_rfgr_shim')
-        gMo = grad_Mo.to(Mck.dtype).contiguous()
-        new = lambda w, *shape: torch.empty(shape, dtype=Mck.dtype, device=device) if w else None  # noqa: E731
-        gMi = new(want['Mi'], p.N, *p.Nd, 3)
-        grf = new(want['rf'], p.N, 2, p.nT, 1)
-        lead = new(want['gr'] or want['sh'], p.N, 3 + nS, p.nT)      # grad_gr's rows, then grad_sh's
-        if p.N * p.nM * p.nT == 0:              # no spin or no step: the library writes nothing (see _fused_adjoint)
-            for g in (grf, lead):
-                if g is not None:
-                    g.zero_()
-            if gMi is not None:
-                gMi.copy_(gMo.reshape(gMi.shape))
-        else:
-            nbytes = int(lib.mrphy_blochsim_rfgr_shim_bwd_workspace(s.code, p.N, p.nM, p.nT, nS))
-            work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
-            name = 'mrphy_blochsim_rfgr_shim_bwd'
-            with torch.cuda.device(device):
-                vals = dict(zip(('sh', 'every', 'shMap', 'nRx'), ctx.sha), gMo=gMo, gMi=gMi, grf=grf, ggr=lead)
-                rc = getattr(lib, name)(s.code, Mck.data_ptr(), *p.k0_args(), *s.consts,
-                                        *(_ptr(vals[k]) for k in _ADJOINT_ARGS[name]), work.data_ptr(), work.numel(),
-                                        p.N, p.nM, p.nT, _host.current_stream(device))
-            _lib.check(rc, name)
-        g = dict(Mi=gMi)
-        if want['rf']:
-            g['rf'] = _fold_pulse_grad(grf, s.likes['rf'][0], s.likes['rf'][1], p.b1 is None)
-        if want['gr']:
-            g['gr'] = _fold_pulse_grad(lead[:, :3], s.likes['gr'][0], s.likes['gr'][1], False)
-        if want['sh']:
-            g['sh'] = _fold_pulse_grad(lead[:, 3:], s.likes['sh'][0], s.likes['sh'][1], False).to(s.likes['sh'][2])
-        return tuple(g.get(k) for k in ARGS)
-
-
-def _decide_shim_route(*, nT, seg, one_coil, nS, cap, pulse_grad, other_grad):
-    r"""The route of :func:`blochsim_rfgr_shim` as a function of plain facts (``nS >= 1`` channels, ``cap`` the most one
-    launch takes; ``pulse_grad``: ``Mi``, ``rf``, ``gr`` or ``sh`` requires grad; ``other_grad``: ``shMap``, ``loc``, ``Δf``,
-    ``b1Map``, ``γ_beff``, ``T1``, ``T2``, ``γ``, ``dt`` or an entry of ``consts`` does): ``('fused', want_ckpt)`` -- one
-    transmit coil, no more channels than the capacity and either no gradient, at any length, or pulse gradients over
-    whole checkpoint segments; ``('split', n1)`` -- such gradients, more than one segment's steps and a ragged last one:
-    the first ``n1`` steps fused, the tail composed; ``('composed', None)`` -- everything else."""
-    if not one_coil or nS > cap or other_grad:
-        return 'composed', None
-    if not pulse_grad:
-        return 'fused', False
-    if nT % seg == 0:
-        return 'fused', True
-    if nT > seg:
-        return 'split', (nT // seg) * seg
-    return 'composed', None
+        return _ext_backward(ctx, BlochSimRfGrShimHIP, 'shim', grad_Mo)
 
 
 def _check_shim(Mi, gr, loc, sh, shMap):
@@ -978,7 +957,6 @@ def blochsim_rfgr_shim(
     inside the kernel; more channels than the capacity in one launch; the trajectory, signal and ``ab_rfgr`` forms with
     channels; a CPU path.
     """
-    from . import beffective, sims, slowsims
     _check_shim(Mi, gr, loc, sh, shMap)
     kw = dict(Δf=Δf, b1Map=b1Map, γ_beff=γ_beff, T1=T1, T2=T2, γ=γ, dt=dt, consts=consts)
     nS = sh.shape[1]
@@ -987,32 +965,19 @@ def blochsim_rfgr_shim(
     _host.require_device_tensor(Mi, 'Mi')
     _host.require_device_tensor(sh, 'sh')
     _host.require_device_tensor(shMap, 'shMap')
-    assert (T1 is None) == (T2 is None)
-    f = _pulse_facts(rf, gr, loc, kw, Mi)
-    p = f.p
-    lib = _lib.require_library()
-    other_grad = f.maps_grad or f.consts_grad or any(_requires_grad(x) for x in (shMap, γ_beff))
-    route, arg = _decide_shim_route(nT=p.nT, seg=SEG, one_coil=f.one_coil, nS=nS,
-                                    cap=int(lib.mrphy_blochsim_rfgr_shim_max_channels(_code(p.dtype))),
-                                    pulse_grad=f.pulse_grad or _requires_grad(sh), other_grad=other_grad)
-    if route == 'split':
-        M1 = blochsim_rfgr_shim(Mi, rf[:, :, :arg], gr[:, :, :arg], loc, sh[:, :, :arg], shMap, **kw)
-        return blochsim_rfgr_shim(M1, rf[:, :, arg:], gr[:, :, arg:], loc, sh[:, :, arg:], shMap, **kw)
-    if route == 'composed':
-        beff = beffective.rfgr2beff(rf, gr, loc, Δf=Δf, b1Map=b1Map, γ=γ_beff, lazy=False)
-        z = _shim_bz(sh, shMap.to(device=beff.device, dtype=beff.dtype))
-        beff = beff + torch.nn.functional.pad(z.unsqueeze(-1), (2, 0))      # out of place: beff may be saved upstream
-        if consts is not None:
-            return sims.blochsim_consts(Mi, beff, **consts)
-        return slowsims.blochsim(Mi, beff, T1=T1, T2=T2, γ=γ, dt=dt)
-    device, dtype = Mi.device, Mi.dtype
-    assert p.device == device and p.dtype == dtype, "Mi and loc must share device and dtype"
-    assert tuple(Mi.shape[:-1]) == (p.N,) + p.Nd
-    assert int(lib.mrphy_blochsim_rfgr_ck_every()) == SEG
-    γ2πdt, E1, E2, E1_1 = _step_constants(kw, False, 1 + len(p.Nd) + 2, device)
-    with torch.no_grad():                       # (N, *Nd, nS) contiguous in the kernels' dtype, as vdt of the moving call
-        maps = shMap.to(device=device, dtype=dtype).expand((p.N,) + p.Nd + (nS,)).contiguous()
-    return BlochSimRfGrShimHIP.apply(Mi, rf, gr, sh, p, maps, γ2πdt, E1, E2, E1_1, arg)
+    cap = int(_lib.require_library().mrphy_blochsim_rfgr_shim_max_channels(_code(loc.dtype)))
+
+    def apply(p, step_consts, want_ckpt):
+        with torch.no_grad():                   # (N, *Nd, nS) contiguous in the kernels' dtype, as vdt of the moving call
+            maps = shMap.to(device=Mi.device, dtype=Mi.dtype).expand((p.N,) + p.Nd + (nS,)).contiguous()
+        return BlochSimRfGrShimHIP.apply(Mi, rf, gr, sh, p, maps, *step_consts, want_ckpt)
+
+    return _bz_extended(
+        Mi, rf, gr, loc, kw, fits=nS <= cap, pulse_grad=_requires_grad(sh),
+        other_grad=any(_requires_grad(x) for x in (shMap, γ_beff)),
+        bz=lambda beff: _shim_bz(sh, shMap.to(device=beff.device, dtype=beff.dtype)),
+        again=lambda M, sl, n0: blochsim_rfgr_shim(M, rf[:, :, sl], gr[:, :, sl], loc, sh[:, :, sl], shMap, **kw),
+        apply=apply)
 
 
 def _traj_ends(nT: int, every: int) -> list:
@@ -1325,15 +1290,6 @@ def _rx_operand(a, rx):
     nRx = r.shape[-1] if r.ndim == len(Nd) + 3 else 1
     r = r.expand((N,) + Nd + tuple(r.shape[1 + len(Nd):])).reshape(N, prod(Nd), 2, nRx).contiguous()
     return r, nRx
-
-
-def _launch(name, device, *args):
-    r"""Entry point ``name`` of the library on ``device`` and its current stream: ``args`` (a tensor passes as its
-    address) followed by the stream; a non-zero return code raises."""
-    lib = _lib.require_library()
-    with torch.cuda.device(device):
-        rc = getattr(lib, name)(*(_ptr(x) for x in args), _host.current_stream(device))
-    _lib.check(rc, name)
 
 
 def _grad_wanted(*operands) -> bool:

@@ -165,7 +165,8 @@ def test_fused_adjoint_table_agrees_with_the_prototypes():
     r"""``fused._ADJOINT_ARGS`` names what ``fused._fused_adjoint`` hands each adjoint entry point between the operands and
     the workspace.  Every entry point of the table, ``ab_rfgr``'s among them, must take exactly the call
     ``_fused_adjoint`` makes -- the dtype code, the checkpoints, ``k0_args()``, the constants' arguments (together
-    ``_lib._FUSED``), the table's entries (``every`` and ``nRx`` integers, everything else a pointer), ``work,
+    ``_lib._FUSED``), the table's entries (``every``, ``nRx``, ``step0``, ``sh_sn`` and ``nS`` integers, everything else a
+    pointer), ``work,
     work_bytes, N, nM, nT``, ``nC`` for the parallel-transmit ones, ``stream``: a wrong entry would shift every pointer
     after it, on the device."""
     from mrphy_amd.fused import _ADJOINT_ARGS
@@ -174,7 +175,8 @@ def test_fused_adjoint_table_agrees_with_the_prototypes():
     assert set(_ADJOINT_ARGS) == adjoints
     for name, between in _ADJOINT_ARGS.items():
         mc = '_mc_' in name
-        call = _lib._FUSED + [i64 if k in ('every', 'nRx') else vp for k in between] + [vp, sz] + [i64] * (3 + mc) + [vp]
+        between = [i64 if k in ('every', 'nRx', 'step0', 'sh_sn', 'nS') else vp for k in between]
+        call = _lib._FUSED + between + [vp, sz] + [i64] * (3 + mc) + [vp]
         argtypes = _lib.PROTOTYPES[name][1]
         assert len(call) == len(argtypes), name
         assert call == argtypes, name
@@ -183,8 +185,8 @@ def test_fused_adjoint_table_agrees_with_the_prototypes():
 class _RecordingCtx:
     r"""What a ``Function``'s ``forward`` / ``backward`` ask of their ``ctx``, without autograd."""
 
-    def __init__(self, n_inputs):
-        self.needs_input_grad = (True,) * n_inputs
+    def __init__(self, n_inputs, needs=None):
+        self.needs_input_grad = (True,) * n_inputs if needs is None else tuple(i in needs for i in range(n_inputs))
 
     def set_materialize_grads(self, flag):
         pass
@@ -193,17 +195,10 @@ class _RecordingCtx:
         self.saved_tensors = tensors
 
 
-@pytest.mark.parametrize('bare', (False, True), ids=('every_operand', 'no_optional_operand'))
-def test_train_family_arguments_agree_with_the_prototypes(monkeypatch, bare):
-    r"""The ten entry points of the train and the sequence family get their arguments from ``fused``'s operand helpers
-    (``_rest_operands``, ``_state_args``, ``_sequence_args`` with and without ``Mi``, ``_rx_operand``, ``_signal_buffers``,
-    ``_sweep_scratch``), joined by each ``Function``.  Their forwards and backwards run here on tiny CPU tensors with the
-    launch replaced by a recorder: every call must hand over exactly ``len(argtypes)`` arguments (the stream included),
-    ``None`` or an address where the prototype has a pointer and an ``int`` where it has an integer.  With every optional
-    operand absent its null pointers must still sit in pointer positions: a group dropped or kept by a wrong index --
-    the steady state takes ``_sequence_args``' tuple without ``Mi`` -- shifts a ``None`` onto an integer."""
+def _record_launches(monkeypatch):
+    r"""``fused._launch`` replaced by a recorder that checks each call against its prototype and launches nothing; returns
+    the list the entry points' names are appended to."""
     from mrphy_amd import fused
-    mrphy_amd.build()
     seen = []
 
     def record(name, device, *args):
@@ -219,6 +214,21 @@ def test_train_family_arguments_agree_with_the_prototypes(monkeypatch, bare):
         seen.append(name)
 
     monkeypatch.setattr(fused, '_launch', record)
+    return seen
+
+
+@pytest.mark.parametrize('bare', (False, True), ids=('every_operand', 'no_optional_operand'))
+def test_train_family_arguments_agree_with_the_prototypes(monkeypatch, bare):
+    r"""The ten entry points of the train and the sequence family get their arguments from ``fused``'s operand helpers
+    (``_rest_operands``, ``_state_args``, ``_sequence_args`` with and without ``Mi``, ``_rx_operand``, ``_signal_buffers``,
+    ``_sweep_scratch``), joined by each ``Function``.  Their forwards and backwards run here on tiny CPU tensors with the
+    launch replaced by a recorder: every call must hand over exactly ``len(argtypes)`` arguments (the stream included),
+    ``None`` or an address where the prototype has a pointer and an ``int`` where it has an integer.  With every optional
+    operand absent its null pointers must still sit in pointer positions: a group dropped or kept by a wrong index --
+    the steady state takes ``_sequence_args``' tuple without ``Mi`` -- shifts a ``None`` onto an integer."""
+    from mrphy_amd import fused
+    mrphy_amd.build()
+    seen = _record_launches(monkeypatch)
     f = torch.float32
     N, nM, K, P, nRx = 2, 3, 2, 2, 3
     A, B = torch.rand(P, N, nM, 3, 3, dtype=f), torch.rand(P, N, nM, 3, dtype=f)
@@ -244,6 +254,43 @@ def test_train_family_arguments_agree_with_the_prototypes(monkeypatch, bare):
     family = [f'mrphy_{name}_{way}' for name in ('ab_train', 'train_signal', 'ab_sequence', 'sequence_signal',
                                                   'sequence_steadystate') for way in ('fwd', 'bwd')]
     assert seen == family
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('bare', (False, True), ids=('every_operand', 'no_optional_operand'))
+@pytest.mark.parametrize('every', (None, 1), ids=('plain', 'every_1'))
+def test_fused_family_arguments_agree_with_the_prototypes(monkeypatch, every, bare):
+    r"""``BlochSimRfGrHIP`` (``every``: its plain or its trajectory entry points), ``BlochSimRfGrMovingHIP`` and
+    ``BlochSimRfGrShimHIP`` join ``k0_args()``, the constants' arguments, their own operands -- the two Bz-extended ones
+    from ``_Saved.ext`` -- and, backwards, the rows of ``fused._ADJOINT_ARGS``.  Forward then backward of each with the
+    launch replaced by the recorder above, with and without ``Δf``, ``b1Map`` and relaxation: ``None`` or an address where
+    the prototype has a pointer, an ``int`` where it has an integer, six entry points in order.  The pulse on the spins
+    refuses CPU tensors, hence the device; nothing is launched on it."""
+    from mrphy_amd import beffective, fused, sims
+    seen = _record_launches(monkeypatch)
+    dev, f = torch.device('cuda:0'), torch.float32
+    N, nM, nT, nS = 2, 3, 16, 3
+    r = lambda *s: torch.rand(s, dtype=f, device=dev)  # noqa: E731
+    opt = lambda x: None if bare else x  # noqa: E731
+    Mi, rf, gr, loc = r(N, nM, 3), r(N, 2, nT), r(N, 3, nT), r(N, nM, 3)
+    p = beffective._PulseOnSpins(rf, gr, loc, opt(r(N, nM)), opt(r(N, nM, 2)), mrphy_amd.γH)
+    consts = sims.relax_constants(opt(r(N, nM) + 1), opt(r(N, nM) + .1), mrphy_amd.γH, mrphy_amd.dt0, 4, dev)
+    vdt, sh, shMap = r(N, nM, 3), r(N, nS, nT), r(N, nM, nS)
+    gM = torch.ones(N, nM, 3, dtype=f, device=dev)
+    gMt = gM if every is None else torch.ones(nT, N, nM, 3, dtype=f, device=dev)
+    runs = (                                            # (the Function, its inputs, those that want a gradient, the cotangent)
+        (fused.BlochSimRfGrHIP, (Mi, rf, gr, p, *consts, True, every), (0, 1, 2), gMt),
+        (fused.BlochSimRfGrMovingHIP, (Mi, rf, gr, p, vdt, 32, *consts, True), (0, 1, 2), gM),
+        (fused.BlochSimRfGrShimHIP, (Mi, rf, gr, sh, p, shMap, *consts, True), (0, 1, 2, 3), gM),
+    )
+    for Fn, inputs, needs, cotangent in runs:
+        ctx = _RecordingCtx(len(inputs), needs)
+        Fn.forward(ctx, *inputs)
+        grads = Fn.backward(ctx, cotangent)
+        assert len(grads) == len(Fn.ARGS), Fn.__name__
+        assert [g is not None for g in grads] == [i in needs for i in range(len(Fn.ARGS))], Fn.__name__
+    traj = '' if every is None else 'traj_'
+    assert seen == [f'mrphy_blochsim_rfgr_{name}{way}' for name in (traj, 'moving_', 'shim_') for way in ('fwd', 'bwd')]
 
 
 def test_signatures_match_the_reference():

@@ -1,4 +1,4 @@
-r"""``fused.blochsim_rfgr_moving`` without a GPU: the routing decision ``fused._decide_moving_route`` over its truth table;
+r"""``fused.blochsim_rfgr_moving`` without a GPU: the routing decision ``fused._decide_ext_route`` over its truth table;
 the argument errors, each raised before the device or the library is needed; the composed route's moving-z helper
 against the closed form; the two entry points ``mrphy_blochsim_rfgr_moving_fwd`` / ``_bwd`` exported, declared and bound
 alike, and what they refuse before any launch."""
@@ -12,7 +12,7 @@ import torch
 
 import mrphy_amd
 from mrphy_amd import _lib, fused
-from mrphy_amd.fused import _decide_moving_route, _moving_bz, _vel_dt
+from mrphy_amd.fused import _decide_ext_route, _moving_bz, _vel_dt
 from util import FAKE, fused_ops
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -30,7 +30,7 @@ def test_route_truth_table(nT):
     such gradients, more than a segment and a ragged tail, at the last segment boundary; composed: everything else --
     parallel transmit, a gradient the kernels do not form, fewer than 16 steps with a gradient."""
     for one_coil, pulse_grad, other_grad in itertools.product((True, False), repeat=3):
-        got = _decide_moving_route(nT=nT, seg=SEG, one_coil=one_coil, pulse_grad=pulse_grad, other_grad=other_grad)
+        got = _decide_ext_route(nT=nT, seg=SEG, one_coil=one_coil, fits=True, pulse_grad=pulse_grad, other_grad=other_grad)
         if not one_coil or other_grad:
             want = ('composed', None)
         elif not pulse_grad:
@@ -42,9 +42,9 @@ def test_route_truth_table(nT):
         else:
             want = ('composed', None)
         assert got == want, (nT, one_coil, pulse_grad, other_grad)
-    assert _decide_moving_route(nT=40, seg=SEG, one_coil=True, pulse_grad=True, other_grad=False) == ('split', 32)
-    assert _decide_moving_route(nT=8, seg=SEG, one_coil=True, pulse_grad=True, other_grad=False) == ('composed', None)
-    assert _decide_moving_route(nT=8, seg=SEG, one_coil=True, pulse_grad=False, other_grad=False) == ('fused', False)
+    assert _decide_ext_route(nT=40, seg=SEG, one_coil=True, fits=True, pulse_grad=True, other_grad=False) == ('split', 32)
+    assert _decide_ext_route(nT=8, seg=SEG, one_coil=True, fits=True, pulse_grad=True, other_grad=False) == ('composed', None)
+    assert _decide_ext_route(nT=8, seg=SEG, one_coil=True, fits=True, pulse_grad=False, other_grad=False) == ('fused', False)
 
 
 # ---------------------------------------------------------------------------------------------

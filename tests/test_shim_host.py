@@ -1,4 +1,4 @@
-r"""``fused.blochsim_rfgr_shim`` without a GPU: the routing decision ``fused._decide_shim_route`` over its truth table; the
+r"""``fused.blochsim_rfgr_shim`` without a GPU: the routing decision ``fused._decide_ext_route`` over its truth table; the
 argument errors, each raised before the device or the library is needed; the composed route's channel-field helper; the
 four entry points ``mrphy_blochsim_rfgr_shim_*`` exported, declared and bound alike, the capacity and workspace queries,
 and what the two launching entry points refuse before any launch, in the order of their checks."""
@@ -10,7 +10,7 @@ import torch
 
 import mrphy_amd
 from mrphy_amd import _lib, fused
-from mrphy_amd.fused import _decide_shim_route, _shim_bz
+from mrphy_amd.fused import _decide_ext_route, _shim_bz
 from test_moving_host import _declared
 from util import FAKE, fused_ops
 
@@ -32,8 +32,8 @@ def test_route_truth_table(nT):
     16 steps with a gradient."""
     for one_coil, pulse_grad, other_grad in itertools.product((True, False), repeat=3):
         for nS, cap in ((1, 8), (3, 8), (8, 8), (9, 8), (5, 4), (4, 4), (17, 8)):
-            got = _decide_shim_route(nT=nT, seg=SEG, one_coil=one_coil, nS=nS, cap=cap, pulse_grad=pulse_grad,
-                                     other_grad=other_grad)
+            got = _decide_ext_route(nT=nT, seg=SEG, one_coil=one_coil, fits=nS <= cap, pulse_grad=pulse_grad,
+                                    other_grad=other_grad)
             if not one_coil or other_grad or nS > cap:
                 want = ('composed', None)
             elif not pulse_grad:
@@ -45,11 +45,11 @@ def test_route_truth_table(nT):
             else:
                 want = ('composed', None)
             assert got == want, (nT, one_coil, nS, cap, pulse_grad, other_grad)
-    kw = dict(seg=SEG, one_coil=True, nS=3, cap=8, other_grad=False)
-    assert _decide_shim_route(nT=40, pulse_grad=True, **kw) == ('split', 32)
-    assert _decide_shim_route(nT=8, pulse_grad=True, **kw) == ('composed', None)
-    assert _decide_shim_route(nT=8, pulse_grad=False, **kw) == ('fused', False)
-    assert _decide_shim_route(nT=48, pulse_grad=True, **dict(kw, nS=9)) == ('composed', None)
+    kw = dict(seg=SEG, one_coil=True, fits=3 <= 8, other_grad=False)
+    assert _decide_ext_route(nT=40, pulse_grad=True, **kw) == ('split', 32)
+    assert _decide_ext_route(nT=8, pulse_grad=True, **kw) == ('composed', None)
+    assert _decide_ext_route(nT=8, pulse_grad=False, **kw) == ('fused', False)
+    assert _decide_ext_route(nT=48, pulse_grad=True, **dict(kw, fits=9 <= 8)) == ('composed', None)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -25,11 +25,12 @@ import sys
 SHAPES = ((1, 1, 1), (2, 100, 2), (2, 100, 7), (2, 65, 'S+3'), (1, 257, 'S+3'), (2, 200, 40), (1, 300, 3), (2, 65, 1))
 
 
-def parent(trees, limit):
+def parent(trees, limit, script=__file__):
+    r"""``script --child`` in each tree; ``tools/moving_shim_bits.py`` runs its own child through this."""
     outs = []
     for tree in trees:
         try:
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), '--child'], cwd=tree, capture_output=True,
+            r = subprocess.run([sys.executable, os.path.abspath(script), '--child'], cwd=tree, capture_output=True,
                                text=True, timeout=limit)
         except subprocess.TimeoutExpired:
             sys.exit(f'{tree}: the child did not finish in {limit} s; nothing more is started')
@@ -122,7 +123,7 @@ def child():
     torch.cuda.synchronize()
 
 
-if __name__ == '__main__':
+def main(doc, child, script):
     if sys.argv[1:] == ['--child']:
         child()
     else:
@@ -132,5 +133,9 @@ if __name__ == '__main__':
             limit = float(args[i + 1])
             del args[i:i + 2]
         if len(args) != 2:
-            sys.exit(__doc__)
-        parent(args, limit)
+            sys.exit(doc)
+        parent(args, limit, script)
+
+
+if __name__ == '__main__':
+    main(__doc__, child, __file__)
