@@ -93,7 +93,8 @@ extern "C" {
  *      period, and its adjoint); mrphy_blochsim_rfgr_moving_fwd, mrphy_blochsim_rfgr_moving_bwd (K2 / K2b for spins that
  *      move at constant velocity); mrphy_blochsim_rfgr_shim_max_channels, mrphy_blochsim_rfgr_shim_bwd_workspace,
  *      mrphy_blochsim_rfgr_shim_fwd, mrphy_blochsim_rfgr_shim_bwd (K2 / K2b with extra Bz field channels, and the adjoint
- *      w.r.t. their waveforms). */
+ *      w.r.t. their waveforms); mrphy_blochsim_rfgr_jvp_max_dirs, mrphy_blochsim_rfgr_jvp_fwd (K2 with the forward-mode
+ *      tangents of Mo along up to 4 directions per launch). */
 #define MRPHY_ABI_VERSION 5
 
 #define MRPHY_F32      0  /* T = float,  CT = float                                          */
@@ -1417,6 +1418,50 @@ int mrphy_blochsim_rfgr_shim_bwd(int dtype,
                                  void* work, size_t work_bytes,
                                  int64_t N, int64_t nM, int64_t nT,
                                  void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * K2j  K2 with forward-mode tangents (ONE transmit coil: nC == 1, b1 (N, nM, 2) or NULL): Mo of mrphy_blochsim_rfgr_fwd,
+ * bit for bit, and dMo (D, N, nM, 3), the directional derivatives of Mo along D directions.  A direction is a set of
+ * tangents of the operands, one dense contiguous table of the data type per operand with a leading direction axis:
+ *     dMi (D, N, nM, 3)   drf (D, N, 2, nT)   dgr (D, N, 3, nT)
+ *     dloc (D, N, nM, 3)  ddf (D, N, nM)      db1 (D, N, nM, 2)
+ *     dE1, dE2, dE1m1 (D, N, nM)              (the tangents of the step constants E1, E2 and E1 - 1)
+ * Any of them may be NULL: a zero tangent.  The field's tangent is
+ *     Bx' + i By' = b1 rf' + b1' rf,   Bz' = gr' . loc + gr . loc' + df' / gamma
+ * (the kernel forms ddf / gamma from the gamma operand, as the primal does); there are no tangents of g, gamma.
+ * The primal step, its S(x), C(x) and their derivatives are formed once per step and shared by the directions, which a
+ * lane keeps in registers; the tangent's arithmetic is plain FMAs in the data type under every dtype code.  The
+ * arithmetic of a direction does not depend on D or on the other directions: dMo[d] has the bits of the call with that
+ * direction alone; a direction scaled by a power of two or negated scales or negates dMo[d] exactly, zero tangents
+ * give zeros.  Mo may be NULL (not wanted).
+ * mrphy_blochsim_rfgr_jvp_max_dirs(dtype): the most directions one launch takes (the kernels are built at the
+ * capacities 1, 2, 4; the smallest that holds D runs): 4; < 0 for an unknown dtype code.
+ * Checks, in this order: dtype and sizes; the mode arguments -- D < 1, D above the capacity, nC != 1, db1 without b1, ddf
+ * without gamma, dE1 / dE2 / dE1m1 without relaxation (E1 NULL) -- MRPHY_EINVAL on an empty problem too; the empty problem
+ * (N nM == 0) returns 0 and writes nothing; NULL Mi, dMo, loc, g, and rf or gr with nT > 0, are MRPHY_EINVAL, as are the
+ * operands mrphy_blochsim_rfgr_fwd refuses; N > 65535 is MRPHY_EINVAL.  Nothing is launched after a refusal.  nT == 0
+ * with spins runs: Mo = Mi, dMo = dMi (zeros without one).  No atomics, no workspace; the same inputs give the same bits.
+ * ------------------------------------------------------------------------------------------- */
+int mrphy_blochsim_rfgr_jvp_max_dirs(int dtype);
+int mrphy_blochsim_rfgr_jvp_fwd(int dtype,
+                                const void* Mi,
+                                const void* rf, int64_t rf_sn,
+                                const void* gr, int64_t gr_sn,
+                                const void* loc,
+                                const void* df, int64_t df_sn, int64_t df_sm,
+                                const void* gamma, int64_t gamma_sn, int64_t gamma_sm,
+                                const void* b1,
+                                const void* g,  int64_t g_sn,  int64_t g_sm,
+                                const void* E1, int64_t E1_sn, int64_t E1_sm,
+                                const void* E2, int64_t E2_sn, int64_t E2_sm,
+                                const void* E1m1,
+                                int64_t D,
+                                const void* dMi, const void* drf, const void* dgr,
+                                const void* dloc, const void* ddf, const void* db1,
+                                const void* dE1, const void* dE2, const void* dE1m1,
+                                void* Mo, void* dMo,
+                                int64_t N, int64_t nM, int64_t nT, int64_t nC,
+                                void* stream);
 
 int mrphy_blochsim_ab(int dtype, const void* M, const void* A, const void* B, void* Mo,
                       int64_t rows, void* stream);

@@ -136,6 +136,8 @@ PROTOTYPES = {
     'mrphy_blochsim_rfgr_shim_fwd': (_int, _FUSED + [_vp, _i64, _vp, _i64] + [_vp, _vp, _i64] + [_i64] * 4 + [_vp]),  # sh, sh_sn, shMap, nS
     'mrphy_blochsim_rfgr_shim_bwd': (_int, _FUSED + [_vp, _i64, _vp, _i64] + [_vp, _vp, _vp, _vp, _vp, _sz] + [_i64] * 3
                                      + [_vp]),
+    'mrphy_blochsim_rfgr_jvp_max_dirs': (_int, [_int]),
+    'mrphy_blochsim_rfgr_jvp_fwd': (_int, _FUSED + [_i64] + [_vp] * 9 + [_vp, _vp] + [_i64] * 4 + [_vp]),   # D, 9 tangents, Mo, dMo
     'mrphy_blochsim_ab': (_int, [_int, _vp, _vp, _vp, _vp, _i64, _vp]),
     'mrphy_blochsim_ab_bwd': (_int, [_int, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
@@ -165,6 +167,9 @@ UNITS = [(f, m) for f, masks in (
     ('tu_fused_shim8_fwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_fused_shim4_fwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_fused_shim2_fwd.hip', (_F32, _F64, _C64, _P, _PC64)),
+    ('tu_fused_jvp4_fwd.hip', (_F32, _F64, _C64, _P, _PC64)),
+    ('tu_fused_jvp2_fwd.hip', (_F32, _F64, _C64, _P, _PC64)),
+    ('tu_fused_jvp1_fwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_ab_rfgr_mc8_bwd.hip', (_F32, _C64, _P, _PC64)),          # fp64 stops at 4 coils (geom.hpp: AB_MC_MAXC_F64)
     ('tu_ab_rfgr_mc4_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_ab_rfgr_mc2_bwd.hip', (_F32, _F64, _C64, _P, _PC64)),

@@ -130,6 +130,28 @@ int rfgr_ext_fwd(AdjBuild b, int dtype, const void* Mi, const PulseOps& in, cons
 #undef MRPHY_EXT_FWD
 }
 
+// K2j: the checks of the plain forward in their order, for one transmit coil; the direction count against the data type's
+// capacity and the tangents that need an operand the call does not have (db1 a b1 map, ddf gamma, dE* relaxation) are
+// mode arguments; dMo is required, Mo is not.  The build is the smallest capacity 1, 2, 4 that holds D
+int rfgr_jvp(int dtype, const void* Mi, const PulseOps& in, const JvpTangents& tg, void* Mo, void* dMo, int64_t N,
+             int64_t nM, int64_t nT, int64_t nC, void* stream)
+{
+    if (int e = check_common(dtype, N, nM, nT)) return e;
+    if (tg.D < 1 || tg.D > jvp_max_dirs(tsize(dtype)) || nC != 1 || (tg.db1 && !in.b1) || (tg.ddf && !in.gam.p) ||
+        ((tg.dE1 || tg.dE2 || tg.dE1m1) && !in.E1.p))
+        return MRPHY_EINVAL;
+    if (N * nM == 0) return 0;                            // runs at nT == 0: Mo = Mi, dMo = dMi or zeros
+    if (!Mi || !dMo) return MRPHY_EINVAL;
+    if (int e = check_ops(in, nT > 0, false)) return e;
+    hipStream_t st = (hipStream_t)stream;
+#define MRPHY_JVP(MD_) MRPHY_DISPATCH(dtype, (run_rfgr_jvp<MD_, T, CT>(Mi, in, tg, Mo, dMo, N, nM, nT, st)))
+    if (tg.D == 1) { MRPHY_JVP(1); }
+    if (tg.D == 2) { MRPHY_JVP(2); }
+    MRPHY_JVP(4);
+#undef MRPHY_JVP
+}
+static_assert(JVP_MAXD_F32 == 4 && JVP_MAXD_F64 == 4, "rfgr_jvp: every capacity in every data type");
+
 // What an adjoint entry point packs besides MRPHY_PULSE_OPS: the request (geom.hpp: AdjointReq), once -- the part every
 // one of them has, under the same names; the cotangents and per-spin outputs it has itself it sets by name.
 #define MRPHY_ADJOINT_REQ(nC_) \
@@ -491,6 +513,21 @@ int mrphy_blochsim_rfgr_shim_bwd(int dtype, const void* Mck, MRPHY_PULSE_OPS_PAR
     MRPHY_ADJOINT_REQ(1);
     r.gMo = grad_Mo; r.ext = BzExt{nullptr, 0, sh, sh_sn, shMap, nS};
     return rfgr_bwd(shim_build(nS), false, dtype, r, MRPHY_PULSE_OPS, work_bytes, stream);
+}
+
+int mrphy_blochsim_rfgr_jvp_max_dirs(int dtype)
+{
+    if (check_common(dtype, 0, 0, 0)) return MRPHY_EINVAL;
+    return jvp_max_dirs(tsize(dtype));
+}
+
+int mrphy_blochsim_rfgr_jvp_fwd(int dtype, const void* Mi, MRPHY_PULSE_OPS_PARAMS, int64_t D, const void* dMi,
+                                const void* drf, const void* dgr, const void* dloc, const void* ddf, const void* db1,
+                                const void* dE1, const void* dE2, const void* dE1m1, void* Mo, void* dMo, int64_t N,
+                                int64_t nM, int64_t nT, int64_t nC, void* stream)
+{
+    const JvpTangents tg{D, dMi, drf, dgr, dloc, ddf, db1, dE1, dE2, dE1m1};
+    return rfgr_jvp(dtype, Mi, MRPHY_PULSE_OPS, tg, Mo, dMo, N, nM, nT, nC, stream);
 }
 
 int64_t mrphy_blochsim_rfgr_mc_max_coils(void) { return K2B_MAXC; }

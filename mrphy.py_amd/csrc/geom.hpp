@@ -31,6 +31,9 @@ static_assert(AB_MC_MAXC_F32 <= K2B_MAXC && AB_MC_MAXC_F64 <= K2B_MAXC, "K2abb-m
 // K2sh / K2shb (k_fused_shim.hpp): the largest channel capacity built (2, 4, 8) per data type, forward and adjoint alike
 constexpr int SHIM_MAXS_F32 = 8, SHIM_MAXS_F64 = 8;
 constexpr int shim_max_channels(size_t tsize) { return tsize == 8 ? SHIM_MAXS_F64 : SHIM_MAXS_F32; }
+// K2j (k_fused_jvp.hpp): the largest direction capacity built (1, 2, 4) per data type
+constexpr int JVP_MAXD_F32 = 4, JVP_MAXD_F64 = 4;
+constexpr int jvp_max_dirs(size_t tsize) { return tsize == 8 ? JVP_MAXD_F64 : JVP_MAXD_F32; }
 constexpr int BWD_MAXC = 32;                      // K0 adjoint: largest coil capacity of the one-pass kernels
 
 // broadcastable per-spin constant (see mrphy_hip.h): element (n, s) at p[n * sn + s * sm]
@@ -65,6 +68,15 @@ struct BzExt {
     const void* vdt;   int64_t step0; // motion: (N, nM, 3), the displacement per step; the steps played before this call
     const void* sh;    int64_t sh_sn; // channels: the waveforms (N|1, nS, nT) and their batch stride (0: shared),
     const void* shMap; int64_t nS;    // the maps (N nM, nS)
+};
+
+// What a forward-mode call (K2j) carries besides PulseOps: D directions, each a set of tangents of the operands.  Dense
+// tables of the data type with a leading direction axis; a null table is a zero tangent.
+struct JvpTangents {
+    int64_t D;
+    const void *dMi, *drf, *dgr;      // (D, N, nM, 3)  (D, N, 2, nT)  (D, N, 3, nT)
+    const void *dloc, *ddf, *db1;     // (D, N, nM, 3)  (D, N, nM)     (D, N, nM, 2)
+    const void *dE1, *dE2, *dE1m1;    // (D, N, nM) each
 };
 
 // Everything an adjoint call of the fused family (K2b, its trajectory, signal, MAPS, CONSTS, multi-coil, moving and shim

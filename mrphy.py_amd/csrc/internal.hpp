@@ -13,6 +13,7 @@ using mrphy::Bc;
 using mrphy::PulseOps;
 using mrphy::AdjointReq;
 using mrphy::BzExt;
+using mrphy::JvpTangents;
 using mrphy::HistParts;
 
 template <typename T, typename CT>
@@ -91,6 +92,12 @@ int run_fused_bwd(const AdjointReq& r, PulseOps in, hipStream_t st);
 template <AdjBuild B, typename T, typename CT>
 int run_rfgr_ext_fwd(const void* Mi, PulseOps in, BzExt x, void* Mo, void* Mck, int64_t ck_every, int64_t N, int64_t nM,
                      int64_t nT, hipStream_t st);
+
+// K2j (tu_fused_jvp1 / 2 / 4_fwd.hip, one unit per direction capacity MD >= tg.D): K2 with the forward-mode tangents of
+// Mo along tg.D directions; one transmit coil, Mo may be null
+template <int MD, typename T, typename CT>
+int run_rfgr_jvp(const void* Mi, PulseOps in, JvpTangents tg, void* Mo, void* dMo, int64_t N, int64_t nM, int64_t nT,
+                 hipStream_t st);
 
 // K2ab / K2abb (tu_ab_rfgr_fwd.hip, tu_ab_rfgr_bwd.hip): Hargreaves' A, B of the fused family's operands, one transmit
 // coil, and the adjoint w.r.t. the pulse.  ABck (nCk, 4, N*nM, 3): the four columns' checkpoints, null for none

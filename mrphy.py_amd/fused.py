@@ -37,6 +37,11 @@ at the spins (shim arrays, higher-order and concomitant terms, gradient nonlinea
 its maps in registers and adds one FMA per channel and step (K2sh), and the fused adjoint returns the gradient w.r.t.
 the waveforms beside those w.r.t. ``Mi``, ``rf``, ``gr`` (K2shb).
 
+:func:`blochsim_rfgr_jvp` is the same simulation in forward mode: ``Mo`` and its directional derivatives along up to
+four directions per launch -- tangents of ``Mi``, ``rf``, ``gr``, ``loc``, ``Δf``, ``b1Map``, ``T1``, ``T2`` -- carried in registers
+beside the magnetisation, each step's rotation and its derivative shared by the directions (K2j); :func:`sensitivity_rfgr`
+is one such call that returns per-spin sensitivity maps.
+
 :func:`signal_rfgr` is the same simulation again, returning what a receive coil measures: the transverse
 magnetisation summed over the spins at the trajectory's record steps (K2s, and the signal mode of K2b), without the
 per-spin records in memory; the coils of a receive array share one simulation per launch.
@@ -81,7 +86,7 @@ from . import _lib, _host
 from ._consts import γH, dt0
 from .beffective import _code
 
-__all__ = ['blochsim_rfgr', 'blochsim_rfgr_moving', 'blochsim_rfgr_shim', 'blochsim_rfgr_traj', 'signal_rfgr', 'ab_rfgr',
+__all__ = ['blochsim_rfgr', 'blochsim_rfgr_jvp', 'sensitivity_rfgr', 'blochsim_rfgr_moving', 'blochsim_rfgr_shim', 'blochsim_rfgr_traj', 'signal_rfgr', 'ab_rfgr',
            'ab_steadystate', 'steadystate_rfgr', 'ab_train', 'train_rfgr', 'train_signal', 'train_signal_rfgr', 'ab_sequence', 'sequence_rfgr',
            'sequence_signal', 'sequence_signal_rfgr', 'sequence_steadystate', 'sequence_steadystate_rfgr']
 
@@ -978,6 +983,183 @@ def blochsim_rfgr_shim(
         bz=lambda beff: _shim_bz(sh, shMap.to(device=beff.device, dtype=beff.dtype)),
         again=lambda M, sl, n0: blochsim_rfgr_shim(M, rf[:, :, sl], gr[:, :, sl], loc, sh[:, :, sl], shMap, **kw),
         apply=apply)
+
+
+# Forward mode (K2j).  The operands a direction may have a tangent of, and what each tangent's table is per spin / per step
+# after the batch axis: the entry point's argument order.
+_JVP_KEYS = ('Mi', 'rf', 'gr', 'loc', 'Δf', 'b1Map', 'T1', 'T2')
+_JVP_CONST_KEYS = ('E1', 'E2', 'E1_1')
+_JVP_TABLES = ('Mi', 'rf', 'gr', 'loc', 'Δf', 'b1Map', 'E1', 'E2', 'E1_1')
+
+
+def _check_tangents(Mi, rf, gr, loc, tangents, Δf, b1Map, T1, T2, consts):
+    r"""The argument checks of :func:`blochsim_rfgr_jvp` that need neither the device nor the library.  Returns ``(D,
+    {key: tangent (D, *full)})``: the direction count and each given tangent as a view broadcast to the FULL shape of its
+    operand -- ``(N, *Nd, xyz)`` for ``Mi`` and ``loc``, ``(N, xy, nT)`` / ``(N, xyz, nT)`` for ``rf`` / ``gr``, ``(N, *Nd, xy)``
+    for ``b1Map``, ``(N, *Nd)`` for ``Δf`` and the constants -- whatever axes of the operand itself are broadcast."""
+    if not isinstance(tangents, dict):
+        raise ValueError(f"mrphy_amd: `tangents` must be a dict of tensors with a leading direction axis, got {tangents!r}")
+    if rf.ndim == 4 and rf.shape[-1] != 1:
+        raise NotImplementedError('parallel transmit')
+    keys = _JVP_KEYS[:6] + (_JVP_CONST_KEYS if consts is not None else _JVP_KEYS[6:])
+    given = {k: v for k, v in tangents.items() if v is not None}
+    for k in given:
+        if k in ('T1', 'T2') and consts is not None:
+            raise ValueError(f"mrphy_amd: `tangents['{k}']` together with `consts=`: its keys are {_JVP_CONST_KEYS}")
+        if k not in keys:
+            raise ValueError(f"mrphy_amd: `tangents` has an unknown key {k!r}; the keys are {keys}")
+    if 'b1Map' in given and b1Map is None:
+        raise ValueError("mrphy_amd: `tangents['b1Map']` without a `b1Map`")
+    relax = consts.get('E1') is not None if consts is not None else T1 is not None
+    for k in ('T1', 'T2') + _JVP_CONST_KEYS:
+        if k in given and not relax:
+            raise ValueError(f"mrphy_amd: `tangents['{k}']` without relaxation (no `T1`, `T2` / `E1`, `E2`)")
+    if not given:
+        raise ValueError("mrphy_amd: `tangents` holds no direction")
+    N, Nd, nT = loc.shape[0], tuple(loc.shape[1:-1]), gr.shape[2]
+    spins = (N,) + Nd
+    full = dict(Mi=spins + (3,), loc=spins + (3,), rf=(N, 2, nT), gr=(N, 3, nT), b1Map=spins + (2,))
+    D, out = None, {}
+    for k, v in given.items():
+        if not isinstance(v, Tensor) or v.ndim < 1:
+            raise ValueError(f"mrphy_amd: `tangents['{k}']` must be a tensor with a leading direction axis, got {v!r}")
+        if D is None:
+            D = v.shape[0]
+        if v.shape[0] != D or D < 1:
+            raise ValueError(f"mrphy_amd: `tangents['{k}']` has {v.shape[0]} directions, the others {D}")
+        want = full.get(k, spins)
+        t = v.float() if v.dtype in (torch.float16, torch.bfloat16) else v      # (half tensors are computed in fp32)
+        if k in ('rf', 'b1Map') and t.ndim == len(want) + 2 and t.shape[-1] == 1:
+            t = t[..., 0]                           # the coil axis of one coil
+        if k not in full:                           # Δf and the constants: right-padded, as their operands are
+            while t.ndim > 1 + len(want) and t.shape[-1] == 1:
+                t = t[..., 0]
+            if t.ndim <= 1 + len(want):
+                t = _host.pad_trailing(t, 1 + len(want))
+        if t.ndim != 1 + len(want) or any(a not in (1, b) for a, b in zip(t.shape[1:], want)):
+            raise ValueError(f"mrphy_amd: `tangents['{k}']` {tuple(v.shape)} does not broadcast to (D, "
+                             f"{', '.join(map(str, want))})")
+        out[k] = t.expand((D,) + want)
+    return D, out
+
+
+def _relax_tangents(tan, kw, p):
+    r"""``{'E1': dE1, 'E2': dE2, 'E1_1': dE1m1}`` `(D, N, *Nd)` from the tangents of ``T1, T2``: ``dE = E·dt/T²·dT`` with the
+    ``E`` :func:`mrphy_amd.sims.relax_constants` gives, formed in fp64; ``E1 - 1`` moves as ``E1`` does."""
+    from . import sims
+    lead = 1 + len(p.Nd)
+    _, E1, E2, _ = sims.relax_constants(kw['T1'], kw['T2'], kw['γ'], kw['dt'], lead + 2, p.device)
+    out = {}
+    for k, E, e in (('T1', E1, 'E1'), ('T2', E2, 'E2')):
+        if k in tan:
+            dev = tan[k].device
+            spin = lambda x: _host.pad_trailing(torch.as_tensor(x).detach().to(dev).double(), lead + 2)[..., 0, 0]  # noqa: E731
+            T = spin(kw[k])
+            out[e] = tan[k].double() * (spin(E) * spin(kw['dt']) / (T * T))
+    if 'E1' in out:
+        out['E1_1'] = out['E1']
+    return out
+
+
+@_host.half_via_float
+def blochsim_rfgr_jvp(
+    Mi: Tensor, rf: Tensor, gr: Tensor, loc: Tensor, *, tangents: dict,
+    Δf: Optional[Tensor] = None, b1Map: Optional[Tensor] = None, γ_beff: Tensor = γH,
+    T1: Optional[Tensor] = None, T2: Optional[Tensor] = None,
+    γ: Tensor = γH, dt: Tensor = dt0, consts: Optional[dict] = None
+):
+    r"""``(Mo, dMo)``: :func:`blochsim_rfgr`'s ``Mo``, bit for bit, and its forward-mode tangents (Jacobian-vector
+    products) along ``D`` directions, ``dMo`` `(D, N, *Nd, xyz)`, from one pass of the fused kernel K2j
+    (``mrphy_blochsim_rfgr_jvp_fwd``) -- no checkpoints, no backward sweep, no finite differences.
+
+    ``tangents``: a dict with keys among ``'Mi', 'rf', 'gr', 'loc', 'Δf', 'b1Map', 'T1', 'T2'`` (with ``consts=``:
+    ``'E1', 'E2', 'E1_1'`` in place of ``'T1', 'T2'``).  Each value has a leading direction axis ``D``, the same for all
+    keys, followed by its operand's shape, where every broadcastable axis may be 1 (``drf`` `(D, 1, xy, nT)`; ``dT1``
+    `(D, N, *Nd)` beside a 0-dim ``T1``).  A missing key or ``None`` is a zero tangent.  ``dMo[d]`` is the derivative of
+    ``Mo`` along direction ``d``: for a per-spin quantity the Jacobian is block-diagonal per spin, so the direction "all
+    ones" returns the whole sensitivity map (:func:`sensitivity_rfgr`); for ``rf``, ``gr`` it is ``J·v`` of a
+    Gauss-Newton or CG step on the linearised excitation, the partner of the adjoint's ``Jᵀ·w``.
+
+    The kernel shares each primal step among up to ``mrphy_blochsim_rfgr_jvp_max_dirs`` (4) directions in registers;
+    more directions run in blocks of that many.  ``dMo[d]`` does not depend on which directions ride along: it has the
+    bits of the call with direction ``d`` alone, scales exactly with powers of two and is exactly zero for zero tangents.
+    The tangent arithmetic is plain FMAs in the data type in both fp32 modes.
+
+    Neither output requires grad and the inputs are detached: reverse-over-forward differentiation is not offered.
+    Not covered: tangents w.r.t. ``γ``, ``dt``, ``γ_beff``; parallel transmit (``NotImplementedError``: there is no
+    composed forward-mode route to fall back to); ``torch.func.jvp`` / ``torch.autograd.forward_ad`` through the
+    library's Functions; the trajectory, signal, A/B and train families; a CPU path."""
+    kw = dict(Δf=Δf, b1Map=b1Map, γ_beff=γ_beff, T1=T1, T2=T2, γ=γ, dt=dt, consts=consts)
+    assert (T1 is None) == (T2 is None)
+    D, tan = _check_tangents(Mi, rf, gr, loc, tangents, Δf, b1Map, T1, T2, consts)
+    _host.require_device_tensor(Mi, 'Mi')
+    for k, v in tan.items():
+        _host.require_device_tensor(v, f"tangents['{k}']")
+    with torch.no_grad():
+        if 'Δf' in tan and Δf is None:              # a tangent of the off-resonance at Δf = 0: the same field bits
+            kw['Δf'] = torch.zeros((), dtype=loc.dtype, device=loc.device)
+        f = _pulse_facts(rf, gr, loc, kw, Mi)
+        p = f.p
+        device, dtype = Mi.device, Mi.dtype
+        assert p.device == device and p.dtype == dtype, "Mi and loc must share device and dtype"
+        assert tuple(Mi.shape[:-1]) == (p.N,) + p.Nd and p.nC == 1
+        lib = _lib.require_library()
+        step_consts = _step_constants(kw, False, 1 + len(p.Nd) + 2, device)
+        code, alive, cargs, _, _ = _forward_prep(lib, p, *step_consts, dtype, device, False)
+        if consts is None:
+            tan.update(_relax_tangents(tan, kw, p))
+        tail = dict(Mi=(3,), loc=(3,), rf=(2, p.nT), gr=(3, p.nT), b1Map=(2,))
+        tables = [None if k not in tan else
+                  tan[k].detach().to(device=device, dtype=dtype)
+                  .reshape((D, p.N) + ((p.nM,) + tail.get(k, ()) if k not in ('rf', 'gr') else tail[k])).contiguous()
+                  for k in _JVP_TABLES]
+        Mi_c = Mi.detach().contiguous()
+        Mo = torch.empty_like(Mi_c)
+        dMo = torch.empty((D, p.N) + p.Nd + (3,), dtype=dtype, device=device)
+        cap = int(lib.mrphy_blochsim_rfgr_jvp_max_dirs(code))
+        assert cap >= 1
+        for d0 in range(0, D, cap):                 # blocks of the capacity; Mo from the first
+            n = min(cap, D - d0)
+            _launch('mrphy_blochsim_rfgr_jvp_fwd', device, code, Mi_c, *p.k0_args(), *cargs, n,
+                    *(None if t is None else t[d0:d0 + n] for t in tables), Mo if d0 == 0 else None, dMo[d0:d0 + n],
+                    p.N, p.nM, p.nT, p.nC)
+        del alive
+    return Mo, dMo
+
+
+_SENSITIVITIES = ('Δf', 'rf', 'T1', 'T2')
+
+
+def _sensitivity_directions(wrt, rf: Tensor, n_spin_axes: int) -> dict:
+    r"""The ``tangents`` of :func:`sensitivity_rfgr`: one direction per entry of ``wrt``, in its order.  ``'rf'``: ``drf = rf``
+    (the relative transmit scale); ``'Δf'``, ``'T1'``, ``'T2'``: ones, broadcast over the batch and the spins
+    `(D, 1, *1)`.  Every table is zero in the directions of the other entries.  Plain torch, any device."""
+    wrt = tuple(wrt)
+    D = len(wrt)
+    if D == 0 or len(set(wrt)) != D:
+        raise ValueError(f"mrphy_amd: `wrt` must name each sensitivity once, got {wrt!r}")
+    out = {}
+    for i, k in enumerate(wrt):
+        if k not in _SENSITIVITIES:
+            raise ValueError(f"mrphy_amd: `wrt` has an unknown entry {k!r}; the entries are {_SENSITIVITIES}")
+        if k == 'rf':
+            t = torch.zeros((D,) + tuple(rf.shape), dtype=rf.dtype, device=rf.device)
+            t[i] = rf.detach()
+        else:
+            t = torch.zeros((D,) + (1,) * n_spin_axes, dtype=rf.dtype, device=rf.device)
+            t[i] = 1
+        out[k] = t
+    return out
+
+
+def sensitivity_rfgr(Mi: Tensor, rf: Tensor, gr: Tensor, loc: Tensor, *, wrt=_SENSITIVITIES, **kw):
+    r"""``(Mo, {name: map})``: per-spin sensitivity maps `(N, *Nd, xyz)` of ``Mo``, one :func:`blochsim_rfgr_jvp` call with
+    one direction per entry of ``wrt``: ``'Δf'``: ``∂Mo/∂Δf`` per Hz; ``'rf'``: ``∂Mo/∂ln s`` at ``s = 1`` for ``rf → s·rf``,
+    the relative transmit scale (with or without a ``b1Map``); ``'T1'``, ``'T2'``: per second.  ``kw``: the keyword
+    arguments of :func:`blochsim_rfgr` (``T1``, ``T2`` must be given for their maps; not ``consts=``)."""
+    tangents = _sensitivity_directions(wrt, rf, loc.ndim - 1)
+    Mo, dMo = blochsim_rfgr_jvp(Mi, rf, gr, loc, tangents=tangents, **kw)
+    return Mo, {k: dMo[i] for i, k in enumerate(wrt)}
 
 
 def _traj_ends(nT: int, every: int) -> list:
