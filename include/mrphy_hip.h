@@ -94,7 +94,8 @@ extern "C" {
  *      move at constant velocity); mrphy_blochsim_rfgr_shim_max_channels, mrphy_blochsim_rfgr_shim_bwd_workspace,
  *      mrphy_blochsim_rfgr_shim_fwd, mrphy_blochsim_rfgr_shim_bwd (K2 / K2b with extra Bz field channels, and the adjoint
  *      w.r.t. their waveforms); mrphy_blochsim_rfgr_jvp_max_dirs, mrphy_blochsim_rfgr_jvp_fwd (K2 with the forward-mode
- *      tangents of Mo along up to 4 directions per launch). */
+ *      tangents of Mo along up to 4 directions per launch); mrphy_ab_sequence_jvp_max_dirs, mrphy_ab_sequence_jvp_fwd
+ *      (the sequence's records with their forward-mode tangents along up to 4 directions per launch). */
 #define MRPHY_ABI_VERSION 5
 
 #define MRPHY_F32      0  /* T = float,  CT = float                                          */
@@ -1214,7 +1215,42 @@ int mrphy_ab_sequence_bwd(int dtype, const void* A, const void* B, int64_t P, co
                           int64_t N, int64_t nM, int64_t K, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Ksqs  the received signal of Ksq's sequence: the transverse magnetisation of its records summed over the spins per
+ * Ksqj  Ksq with forward-mode tangents: Mt of mrphy_ab_sequence_fwd, bit for bit, and dMt (D,K,N,nM,3), time-major like
+ * Mt, the derivative of every record along D directions.  A .. cs_sn exactly as mrphy_ab_sequence_fwd.  A direction is
+ * a set of tangents of the operands, one dense contiguous table per operand with a leading direction axis:
+ *     per spin, of the data type:   dA (D,P,N,nM,3,3)   dB (D,P,N,nM,3)   dMi (D,N,nM,3)   dT1, dT2, ddf (D,N,nM)
+ *     block-uniform, ALWAYS fp64:   dphase (D,N|1,K) in rad   drest (D,N|1,K) in s
+ * dphase and drest are contiguous over K with the element stride *_sn between batch entries (0 broadcasts: the table is
+ * (D,1,K)).  Any of the eight may be NULL: a zero tangent.  A tangent of df may come without df (df counts as 0).
+ * The primal repetition is Ksq's own; per repetition the tangents of cos, sin, E1, E2 of the rest are products of those
+ * numbers (no transcendental function is called for a tangent), everything in fp64, each record rounded once on its
+ * store.  The arithmetic of a direction does not depend on D or on the other directions: dMt[d] has the bits of the call
+ * with that direction alone; a direction scaled by a power of two or negated scales or negates dMt[d] exactly; zero
+ * tangents give zeros; dA, dB of an entry the schedule never plays are never read.  Mt may be NULL (not wanted).
+ * mrphy_ab_sequence_jvp_max_dirs(dtype): the most directions one launch takes (the kernels are built at the capacities
+ * 1, 2, 4; the smallest that holds D runs): 4; < 0 for a dtype code other than MRPHY_F32, MRPHY_F64.
+ * Checks: those of mrphy_ab_sequence_fwd in its order, the empty problem (N*nM*K == 0) a success that looks at no pointer
+ * and writes nothing; then MRPHY_EINVAL for D < 1 or D above the capacity, for dT1 or dT2 without T1, for ddf, drest,
+ * dT1 or dT2 without rs, for a NULL dMt; MRPHY_EALIGN for a misaligned pointer (dphase, drest: 8).  Nothing is launched
+ * after a refusal.  No atomics, no workspace; the same inputs give the same bits.
+ * ------------------------------------------------------------------------------------------- */
+int mrphy_ab_sequence_jvp_max_dirs(int dtype);
+int mrphy_ab_sequence_jvp_fwd(int dtype, const void* A, const void* B, int64_t P, const void* pulse,
+                              const void* rs, int64_t rs_sn,
+                              const void* T1, int64_t T1_sn, int64_t T1_sm,
+                              const void* T2, int64_t T2_sn, int64_t T2_sm,
+                              const void* df, int64_t df_sn, int64_t df_sm,
+                              const void* Mi, int64_t Mi_sn, int64_t Mi_sm,
+                              const void* cs, int64_t cs_sn,
+                              int64_t D,
+                              const void* dA, const void* dB, const void* dMi,
+                              const void* dT1, const void* dT2, const void* ddf,
+                              const void* dphase, int64_t dphase_sn,
+                              const void* drest, int64_t drest_sn,
+                              void* Mt, void* dMt, int64_t N, int64_t nM, int64_t K, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Ksqs the received signal of Ksq's sequence: the transverse magnetisation of its records summed over the spins per
  * repetition, for nRx receive coils, inside the kernel -- Ktrs's frame around Ksq's repetition.  A .. cs_sn exactly as
  * mrphy_ab_sequence_fwd (the bank, the int32 schedule, the fp64 rs), rx .. work_bytes exactly as
  * mrphy_train_signal_fwd: rx (N,nM,2,nRx) or NULL with nRx == 1, 1 <= nRx <= mrphy_train_signal_max_rx(dtype),

@@ -120,6 +120,9 @@ PROTOTYPES = {
                                + _WORK + _SIZES),                                                  # ..., ck, 6 grads
     'mrphy_ab_sequence_bwd_workspace': (_sz, [_int] + [_i64] * 3),
     'mrphy_ab_sequence_fwd': (_int, _AB + _SEQ_HEAD + _REST + _STATE + [_vp] + _SIZES),
+    'mrphy_ab_sequence_jvp_max_dirs': (_int, [_int]),
+    'mrphy_ab_sequence_jvp_fwd': (_int, _AB + _SEQ_HEAD + _REST + _STATE + [_i64] + [_vp] * 6 + [_vp, _i64] * 2   # D, 8 tangents
+                                  + [_vp, _vp] + _SIZES),                                                        # Mt, dMt
     'mrphy_ab_sequence_bwd': (_int, _AB + _SEQ_HEAD + [_vp] + _REST + _STATE + [_vp] + [_vp] * 6 + _WORK + _SIZES),
     'mrphy_sequence_signal_workspace': (_sz, [_int] + [_i64] * 4),
     'mrphy_sequence_signal_bank_workspace': (_sz, [_int] + [_i64] * 3),
@@ -192,6 +195,9 @@ UNITS = [(f, m) for f, masks in (
     ('tu_beff2ab.hip', (_F32, _F64, _C64, _P, _PC64)),
     ('tu_rfgr2beff_fwd.hip', (_F32, _F64)),
     ('tu_rfgr2beff_bwd.hip', (_F32, _F64)),
+    ('tu_ab_sequence_jvp4.hip', (None,)),
+    ('tu_ab_sequence_jvp2.hip', (None,)),
+    ('tu_ab_sequence_jvp1.hip', (None,)),
     ('tu_aux.hip', (None,)),
     ('tu_ab_steady.hip', (None,)),
     ('tu_ab_train.hip', (None,)),

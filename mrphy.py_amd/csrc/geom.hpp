@@ -34,6 +34,9 @@ constexpr int shim_max_channels(size_t tsize) { return tsize == 8 ? SHIM_MAXS_F6
 // K2j (k_fused_jvp.hpp): the largest direction capacity built (1, 2, 4) per data type
 constexpr int JVP_MAXD_F32 = 4, JVP_MAXD_F64 = 4;
 constexpr int jvp_max_dirs(size_t tsize) { return tsize == 8 ? JVP_MAXD_F64 : JVP_MAXD_F32; }
+// Ksqj (k_ab_sequence_jvp.hpp): the largest direction capacity built (1, 2, 4) per data type
+constexpr int SEQ_JVP_MAXD_F32 = 4, SEQ_JVP_MAXD_F64 = 4;
+constexpr int seq_jvp_max_dirs(size_t tsize) { return tsize == 8 ? SEQ_JVP_MAXD_F64 : SEQ_JVP_MAXD_F32; }
 constexpr int BWD_MAXC = 32;                      // K0 adjoint: largest coil capacity of the one-pass kernels
 
 // broadcastable per-spin constant (see mrphy_hip.h): element (n, s) at p[n * sn + s * sm]
@@ -77,6 +80,26 @@ struct JvpTangents {
     const void *dMi, *drf, *dgr;      // (D, N, nM, 3)  (D, N, 2, nT)  (D, N, 3, nT)
     const void *dloc, *ddf, *db1;     // (D, N, nM, 3)  (D, N, nM)     (D, N, nM, 2)
     const void *dE1, *dE2, *dE1m1;    // (D, N, nM) each
+};
+
+// What a forward-mode call of the sequence (Ksqj) carries: the operands of mrphy_ab_sequence_fwd and D directions, each a
+// set of tangents of them.  Per spin, dense tables of the data type with a leading direction axis: dA (D, P, rows, 9),
+// dB (D, P, rows, 3), dMi (D, rows, 3), dT1, dT2, ddf (D, rows).  Block-uniform, fp64: dphase, drest (D, N|1, K) with the
+// element stride *_sn between batch entries (0 broadcasts; a direction is (sn ? N : 1) K elements).  A null table is a
+// zero tangent.
+struct SeqJvpCall {
+    const void *A, *B; int64_t P; const void* pulse;
+    const void* rs; int64_t rs_sn;
+    Bc T1, T2, df;
+    const void* Mi; int64_t Mi_sn, Mi_sm;
+    const void* cs; int64_t cs_sn;
+    int64_t D;
+    const void *dA, *dB, *dMi, *dT1, *dT2, *ddf;
+    const void* dphase; int64_t dphase_sn;
+    const void* drest;  int64_t drest_sn;
+    void* Mt;                         // (K, rows, 3) or null: not wanted
+    void* dMt;                        // (D, K, rows, 3)
+    int64_t N, nM, K;
 };
 
 // Everything an adjoint call of the fused family (K2b, its trajectory, signal, MAPS, CONSTS, multi-coil, moving and shim

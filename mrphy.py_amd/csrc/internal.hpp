@@ -14,6 +14,7 @@ using mrphy::PulseOps;
 using mrphy::AdjointReq;
 using mrphy::BzExt;
 using mrphy::JvpTangents;
+using mrphy::SeqJvpCall;
 using mrphy::HistParts;
 
 template <typename T, typename CT>
@@ -98,6 +99,11 @@ int run_rfgr_ext_fwd(const void* Mi, PulseOps in, BzExt x, void* Mo, void* Mck, 
 template <int MD, typename T, typename CT>
 int run_rfgr_jvp(const void* Mi, PulseOps in, JvpTangents tg, void* Mo, void* dMo, int64_t N, int64_t nM, int64_t nT,
                  hipStream_t st);
+
+// Ksqj (tu_ab_sequence_jvp1 / 2 / 4.hip, one unit per direction capacity MD >= c.D): Ksq with the forward-mode tangents
+// of its records along c.D directions; checked by mrphy_ab_sequence_jvp_fwd (tu_ab_sequence.hip)
+template <int MD, typename T>
+int run_ab_sequence_jvp(SeqJvpCall c, hipStream_t st);
 
 // K2ab / K2abb (tu_ab_rfgr_fwd.hip, tu_ab_rfgr_bwd.hip): Hargreaves' A, B of the fused family's operands, one transmit
 // coil, and the adjoint w.r.t. the pulse.  ABck (nCk, 4, N*nM, 3): the four columns' checkpoints, null for none

@@ -42,6 +42,10 @@ four directions per launch -- tangents of ``Mi``, ``rf``, ``gr``, ``loc``, ``Δf
 beside the magnetisation, each step's rotation and its derivative shared by the directions (K2j); :func:`sensitivity_rfgr`
 is one such call that returns per-spin sensitivity maps.
 
+:func:`ab_sequence_jvp` is forward mode for the sequence family: :func:`ab_sequence`'s records and their derivatives along
+up to four directions per launch -- tangents of ``A``, ``B``, ``Mi``, ``phase``, ``rest``, ``T1``, ``T2``, ``Δf`` -- from one pass (Ksqj);
+:func:`ab_rfgr_jvp` and :func:`sequence_rfgr_jvp` put :func:`blochsim_rfgr_jvp` in front of it, from ``rf`` and ``gr``.
+
 :func:`signal_rfgr` is the same simulation again, returning what a receive coil measures: the transverse
 magnetisation summed over the spins at the trajectory's record steps (K2s, and the signal mode of K2b), without the
 per-spin records in memory; the coils of a receive array share one simulation per launch.
@@ -88,6 +92,7 @@ from .beffective import _code
 
 __all__ = ['blochsim_rfgr', 'blochsim_rfgr_jvp', 'sensitivity_rfgr', 'blochsim_rfgr_moving', 'blochsim_rfgr_shim', 'blochsim_rfgr_traj', 'signal_rfgr', 'ab_rfgr',
            'ab_steadystate', 'steadystate_rfgr', 'ab_train', 'train_rfgr', 'train_signal', 'train_signal_rfgr', 'ab_sequence', 'sequence_rfgr',
+           'ab_sequence_jvp', 'ab_rfgr_jvp', 'sequence_rfgr_jvp',
            'sequence_signal', 'sequence_signal_rfgr', 'sequence_steadystate', 'sequence_steadystate_rfgr']
 
 
@@ -1088,7 +1093,8 @@ def blochsim_rfgr_jvp(
     Neither output requires grad and the inputs are detached: reverse-over-forward differentiation is not offered.
     Not covered: tangents w.r.t. ``γ``, ``dt``, ``γ_beff``; parallel transmit (``NotImplementedError``: there is no
     composed forward-mode route to fall back to); ``torch.func.jvp`` / ``torch.autograd.forward_ad`` through the
-    library's Functions; the trajectory, signal, A/B and train families; a CPU path."""
+    library's Functions; the trajectory and signal families (``A, B`` and the sequence: :func:`ab_rfgr_jvp`,
+    :func:`ab_sequence_jvp`); a CPU path."""
     kw = dict(Δf=Δf, b1Map=b1Map, γ_beff=γ_beff, T1=T1, T2=T2, γ=γ, dt=dt, consts=consts)
     assert (T1 is None) == (T2 is None)
     D, tan = _check_tangents(Mi, rf, gr, loc, tangents, Δf, b1Map, T1, T2, consts)
@@ -1917,6 +1923,13 @@ def _sequence_operands(A, B, pulse, n, phase, rest, T1, T2, Δf, Mi, period=Fals
     r"""``(N, Nd, sched, K)`` of :func:`ab_sequence`, :func:`sequence_signal` and :func:`sequence_steadystate`
     (``period``: ``K = 0`` is refused), every operand checked in the order the three document: the bank's shapes, the
     schedule, the length, ``rest``, ``rx`` where there is one, then what :func:`_check_train_operands` requires."""
+    N, Nd, sched, K = _sequence_shapes(A, B, pulse, n, phase, rest, period, rx)
+    _check_train_operands(A, B, N, Nd, Mi, rest, T1, T2, Δf)
+    return N, Nd, sched, K
+
+
+def _sequence_shapes(A, B, pulse, n, phase, rest, period=False, rx=None):
+    r"""The part of :func:`_sequence_operands` that looks at shapes and the schedule only, not at devices."""
     N, Nd = _train_spins(A, B, bank=True)
     sched = _sequence_schedule(pulse, A.shape[0])
     K = (_period_length if period else _sequence_length)(n, sched, phase, N)
@@ -1924,7 +1937,6 @@ def _sequence_operands(A, B, pulse, n, phase, rest, T1, T2, Δf, Mi, period=Fals
                              (rest.ndim == 2 and (rest.shape[0] not in (1, N) or rest.shape[1] != K))):
         raise ValueError(f"mrphy_amd: `rest` {tuple(rest.shape)} must be (), (N ⊻ 1,) or (N ⊻ 1, K) with N = {N}, K = {K}")
     _check_rx(rx, N, Nd, B.ndim - 1)
-    _check_train_operands(A, B, N, Nd, Mi, rest, T1, T2, Δf)
     return N, Nd, sched, K
 
 
@@ -2021,6 +2033,255 @@ def sequence_rfgr(
                                  consts=consts)
     return ab_sequence(A, B, pulse=sched, n=n, Mi=Mi, phase=phase, rest=rest, T1=T1, T2=T2,
                        Δf=Δf if Δf_rest is None else Δf_rest)
+
+
+# Forward mode of the sequence (Ksqj).  The operands a direction may have a tangent of, in the entry point's order.
+_SEQ_JVP_KEYS = ('A', 'B', 'Mi', 'T1', 'T2', 'Δf', 'phase', 'rest')
+
+
+def _given_tangents(tangents, keys):
+    r"""``(D, {key: tangent})`` of a ``tangents`` dict: the entries that are not ``None``, each a tensor with the same
+    leading direction axis ``D >= 1``, half tensors widened to fp32; a key outside ``keys`` is a ``ValueError``."""
+    if not isinstance(tangents, dict):
+        raise ValueError(f"mrphy_amd: `tangents` must be a dict of tensors with a leading direction axis, got {tangents!r}")
+    given = {k: v for k, v in tangents.items() if v is not None}
+    for k in given:
+        if k not in keys:
+            raise ValueError(f"mrphy_amd: `tangents` has an unknown key {k!r}; the keys are {tuple(keys)}")
+    if not given:
+        raise ValueError("mrphy_amd: `tangents` holds no direction")
+    D = None
+    for k, v in given.items():
+        if not isinstance(v, Tensor) or v.ndim < 1:
+            raise ValueError(f"mrphy_amd: `tangents['{k}']` must be a tensor with a leading direction axis, got {v!r}")
+        D = v.shape[0] if D is None else D
+        if v.shape[0] != D or D < 1:
+            raise ValueError(f"mrphy_amd: `tangents['{k}']` has {v.shape[0]} directions, the others {D}")
+        if v.dtype in (torch.float16, torch.bfloat16):
+            given[k] = v.float()
+    return D, given
+
+
+def _check_sequence_tangents(tangents, P, N, Nd, K, rest, T1, Δf):
+    r"""The argument checks of :func:`ab_sequence_jvp` that need neither the device nor the library.  Returns ``(D,
+    {key: tangent})`` with each given tangent as a view broadcast to ``(D, P, N, *Nd, 3, 3)`` / ``(D, P, N, *Nd, 3)`` for
+    ``A`` / ``B``, ``(D, N, *Nd, 3)`` for ``Mi``, ``(D, N, *Nd)`` for ``T1, T2, Δf`` and ``(D, N ⊻ 1, K)`` for ``phase`` and
+    ``rest`` (a duration that the repetitions share written out over ``K``)."""
+    D, given = _given_tangents(tangents, _SEQ_JVP_KEYS)
+    if 'rest' in given and rest is None:
+        raise ValueError("mrphy_amd: `tangents['rest']` without a `rest`")
+    for k in ('T1', 'T2'):
+        if k in given and T1 is None:
+            raise ValueError(f"mrphy_amd: `tangents['{k}']` without `T1`, `T2`")
+    if 'Δf' in given and rest is None:
+        raise ValueError("mrphy_amd: `tangents['Δf']` without a `rest`: nothing precesses")
+    spins = (N,) + Nd
+    full = dict(A=(P,) + spins + (3, 3), B=(P,) + spins + (3,), Mi=spins + (3,), T1=spins, T2=spins, Δf=spins)
+    out = {}
+    for k, t in given.items():
+        shape = tuple(t.shape)
+        if k in ('phase', 'rest'):
+            if k == 'rest' and t.ndim <= 2:               # (D,) ⊻ (D, N ⊻ 1): one duration for all repetitions
+                t = t.reshape(D, -1, 1)
+            ok = t.ndim == 3 and t.shape[1] in (1, N) and (t.shape[2] == K or (k == 'rest' and t.shape[2] == 1))
+            want = ('N ⊻ 1', 'K')
+            if ok:
+                t = t.expand(D, t.shape[1], K)
+        else:
+            want = full[k]
+            if k in ('T1', 'T2', 'Δf'):                   # right-padded, as their operands are
+                while t.ndim > 1 + len(want) and t.shape[-1] == 1:
+                    t = t[..., 0]
+                if t.ndim <= 1 + len(want):
+                    t = _host.pad_trailing(t, 1 + len(want))
+            ok = t.ndim == 1 + len(want) and all(a in (1, b) for a, b in zip(t.shape[1:], want))
+            if ok:
+                t = t.expand((D,) + want)
+        if not ok:
+            raise ValueError(f"mrphy_amd: `tangents['{k}']` {shape} does not broadcast to (D, {', '.join(map(str, want))})")
+        out[k] = t
+    return D, out
+
+
+@_host.half_via_float
+def ab_sequence_jvp(
+    A: Tensor, B: Tensor, *, tangents: dict, pulse=None, n: Optional[int] = None, Mi: Optional[Tensor] = None,
+    phase: Optional[Tensor] = None, rest: Optional[Tensor] = None, T1: Optional[Tensor] = None,
+    T2: Optional[Tensor] = None, Δf: Optional[Tensor] = None
+):
+    r"""``(Mt, dMt)``: :func:`ab_sequence`'s ``Mt`` `(N, *Nd, K, xyz)`, bit for bit, and its forward-mode tangents
+    (Jacobian-vector products) along ``D`` directions, ``dMt`` `(D, N, *Nd, K, xyz)`: the derivative of every record of
+    the transient, from one pass of one kernel (Ksqj, ``mrphy_ab_sequence_jvp_fwd``) -- no backward sweep, no finite
+    differences.  Operands exactly as :func:`ab_sequence`.
+
+    ``tangents``: a dict with keys among ``'A', 'B', 'Mi', 'phase', 'rest', 'T1', 'T2', 'Δf'``, as in
+    :func:`blochsim_rfgr_jvp`: each value has a leading direction axis ``D``, the same for all keys, followed by its
+    operand's shape in any form the operand may take, where every broadcastable axis may be 1 (``dT1`` `(D, N, *Nd)`
+    beside a 0-dim ``T1``; ``drest`` `(D,)`, `(D, N ⊻ 1)` or `(D, N ⊻ 1, K)`).  A missing key or ``None`` is a zero
+    tangent.  ``Mi`` and ``phase`` may have a tangent without being given (their absences are the values ``(0, 0, 1)`` and
+    ``0``), ``Δf`` may while ``rest`` is given (it counts as 0); ``rest``, ``T1``, ``T2`` need their operand.  For a per-spin
+    quantity the Jacobian is block-diagonal per spin, so the direction "all ones" returns the whole sensitivity map
+    ``∂M_k/∂T1`` of every spin and repetition -- what a Cramér-Rao analysis of a schedule starts from, where reverse mode
+    needs ``3·K`` backward passes --, and ``dMt`` along a direction ``v`` is the ``J·v`` of a Gauss-Newton step, the
+    partner of the adjoint's ``Jᵀ·w``.
+
+    The kernel carries up to ``mrphy_ab_sequence_jvp_max_dirs`` (4) directions beside the state; more run in blocks of
+    that many, ``Mt`` from the first.  The tangents of the rest's ``cos, sin, E1, E2`` are products of those numbers: no
+    transcendental function is called for a tangent.  ``dMt[d]`` has the bits of the call with direction ``d`` alone,
+    scales exactly with powers of two, is exactly zero for zero tangents, and a tangent on a bank entry the schedule
+    never plays contributes exact zeros.  fp64 inside, one rounding per record, as :func:`ab_sequence`.
+
+    The argument checks come in this order: the bank's shapes, the schedule, the length and ``rest`` as
+    :func:`ab_sequence` makes them, the tangents (``ValueError``: an unknown key, unequal ``D``, no direction, a shape that
+    does not broadcast, a tangent whose operand is missing), then devices and dtypes.  Neither output requires grad and
+    the inputs are detached: reverse-over-forward is not offered.  Not covered: ``torch.func.jvp`` /
+    ``torch.autograd.forward_ad`` through the library's Functions; tangents of :func:`sequence_signal`,
+    :func:`sequence_steadystate`, :func:`ab_steadystate`; a schedule per batch entry; a CPU path."""
+    N, Nd, sched, K = _sequence_shapes(A, B, pulse, n, phase, rest)
+    D, tan = _check_sequence_tangents(tangents, A.shape[0], N, Nd, K, rest, T1, Δf)
+    _check_train_operands(A, B, N, Nd, Mi, rest, T1, T2, Δf)
+    for k, v in tan.items():
+        _host.require_device_tensor(v, f"tangents['{k}']")
+    with torch.no_grad():
+        device, dtype = A.device, A.dtype
+        a, b = A.detach().contiguous(), B.detach().contiguous()
+        sched_dev = None if sched is None else sched.to(device)
+        rs = _rest_table(a, rest, K)
+        mi, cs = _state_operands(a[0], Mi, phase)
+        N, Nd, nM, code, keep, head, tail = _sequence_args(a, rs, T1, T2, Δf, mi, cs, sched_dev)
+        P, rows = a.shape[0], N * nM
+        per_spin = dict(A=(D, P, rows, 9), B=(D, P, rows, 3), Mi=(D, rows, 3), T1=(D, rows), T2=(D, rows), Δf=(D, rows))
+        tables = [None if k not in tan else tan[k].detach().to(device=device, dtype=dtype).reshape(per_spin[k]).contiguous()
+                  for k in _SEQ_JVP_KEYS[:6]]
+        # the block-uniform tables: rounded to the data type and widened, as rs is
+        uniform = [None if k not in tan else tan[k].detach().to(device=device, dtype=dtype).double().contiguous()
+                   for k in ('phase', 'rest')]
+        Mt = torch.empty((K,) + tuple(b.shape[1:]), dtype=dtype, device=device)
+        dMt = torch.empty((D, K) + tuple(b.shape[1:]), dtype=dtype, device=device)
+        lib = _lib.require_library()
+        cap = int(lib.mrphy_ab_sequence_jvp_max_dirs(code))
+        assert cap >= 1
+        for d0 in range(0, D, cap):                 # blocks of the capacity; Mt from the first
+            nd = min(cap, D - d0)
+            blk = lambda t: None if t is None else t[d0:d0 + nd]  # noqa: E731
+            uni = [x for t in uniform for x in ((None, 0) if t is None else (blk(t), _over_n(t[0], N)))]
+            _launch('mrphy_ab_sequence_jvp_fwd', device, code, a, b, *head, *tail, nd, *(blk(t) for t in tables), *uni,
+                    Mt if d0 == 0 else None, dMt[d0:d0 + nd], N, nM, K)
+        del keep
+    return Mt.movedim(0, -2), dMt.movedim(1, -2)
+
+
+def _over_bank(x, P, N, axis=0):
+    r"""A spin-side operand (``axis = 0``) or its tangent (``axis = 1``, after the direction axis) for a batch of ``P·N``
+    entries: repeated over ``P`` where it has the batch axis ``N > 1`` at ``axis``, left to broadcast where it has not."""
+    if not isinstance(x, Tensor) or x.ndim <= axis or x.shape[axis] != N or N == 1:
+        return x
+    lead = tuple(x.shape[:axis])
+    return x.unsqueeze(axis).expand(lead + (P,) + tuple(x.shape[axis:])).flatten(axis, axis + 1)
+
+
+@_host.half_via_float
+def ab_rfgr_jvp(
+    rf: Tensor, gr: Tensor, loc: Tensor, *, tangents: dict,
+    Δf: Optional[Tensor] = None, b1Map: Optional[Tensor] = None, γ_beff: Tensor = γH,
+    T1: Optional[Tensor] = None, T2: Optional[Tensor] = None,
+    γ: Tensor = γH, dt: Tensor = dt0, consts: Optional[dict] = None
+):
+    r"""``(A, B, dA, dB)``: :func:`ab_rfgr`'s ``A`` `(N, *Nd, xyz, 3)`, ``B`` `(N, *Nd, xyz)` (its bits) and their
+    forward-mode tangents ``dA`` `(D, N, *Nd, xyz, 3)`, ``dB`` `(D, N, *Nd, xyz)` along ``D`` directions.  A composition,
+    no kernel of its own: ONE :func:`blochsim_rfgr_jvp` call on the batch ``4·N`` with ``Mi ∈ {0, e_x, e_y, e_z}``, whose
+    ``dMo`` are the tangents of ``B`` and of ``A e_j + B``: ``dB = dMo|₀``, ``dA[..., :, j] = dMo|e_j − dMo|₀``.
+    ``tangents``: :func:`blochsim_rfgr_jvp`'s keys without ``'Mi'``.  Its limits are inherited: one transmit coil
+    (``NotImplementedError('parallel transmit')``) and ``4·N ≤ 65535``.  In fp32 the difference rounds at the level of
+    ``|dMo|``, as any column of ``A`` obtained from two simulations does."""
+    if rf.ndim == 4 and rf.shape[-1] != 1:
+        raise NotImplementedError('parallel transmit')
+    if isinstance(tangents, dict) and tangents.get('Mi') is not None:
+        raise ValueError(f"mrphy_amd: `tangents` has an unknown key 'Mi': A and B do not depend on a state; the keys are "
+                         f"{_JVP_KEYS[1:]}")
+    kw = dict(Δf=Δf, b1Map=b1Map, γ_beff=γ_beff, T1=T1, T2=T2, γ=γ, dt=dt, consts=consts)
+    N, Nd = loc.shape[0], tuple(loc.shape[1:-1])
+    side = lambda x: _over_bank(x, 4, N)  # noqa: E731
+    over = lambda x: x.expand((4,) + tuple(x.shape)).flatten(0, 1)  # noqa: E731
+    Mi = torch.zeros((4, N) + Nd + (3,), dtype=loc.dtype, device=loc.device)
+    for j in range(3):
+        Mi[1 + j, ..., j] = 1
+    tan = {k: _over_bank(v, 4, N, axis=1) for k, v in (tangents.items() if isinstance(tangents, dict) else ())}
+    kw4 = {k: side(v) for k, v in kw.items() if k != 'consts'}
+    kw4['consts'] = None if consts is None else {k: side(v) for k, v in consts.items()}
+    _, dMo = blochsim_rfgr_jvp(Mi.flatten(0, 1), over(rf) if rf.shape[0] == N else rf, over(gr) if gr.shape[0] == N else gr,
+                               over(loc), tangents=tan if isinstance(tangents, dict) else tangents, **kw4)
+    with torch.no_grad():
+        det = lambda x: x.detach() if isinstance(x, Tensor) else x  # noqa: E731
+        A, B = ab_rfgr(det(rf), det(gr), det(loc), **{k: det(v) for k, v in kw.items() if k != 'consts'},
+                       consts=None if consts is None else {k: det(v) for k, v in consts.items()})
+    dMo = dMo.unflatten(1, (4, N))
+    dB = dMo[:, 0]
+    dA = torch.stack([dMo[:, 1 + j] - dB for j in range(3)], dim=-1)
+    return A, B, dA, dB
+
+
+_SEQ_RFGR_BANK_KEYS = ('rf', 'gr', 'loc', 'b1Map', 'Δf', 'T1', 'T2')
+_SEQ_RFGR_TRAIN_KEYS = ('Mi', 'phase', 'rest')
+
+
+@_host.half_via_float
+def sequence_rfgr_jvp(
+    rf: Tensor, gr: Tensor, loc: Tensor, *, tangents: dict,
+    pulse=None, n: Optional[int] = None, Mi: Optional[Tensor] = None, phase: Optional[Tensor] = None,
+    rest: Optional[Tensor] = None, T1: Optional[Tensor] = None, T2: Optional[Tensor] = None,
+    Δf: Optional[Tensor] = None, b1Map: Optional[Tensor] = None, γ_beff: Tensor = γH,
+    γ: Tensor = γH, dt: Tensor = dt0, consts: Optional[dict] = None, Δf_rest: Optional[Tensor] = None
+):
+    r"""``(Mt, dMt)`` of :func:`sequence_rfgr` in forward mode: ONE :func:`ab_rfgr_jvp` call on the batch ``P·N`` forms
+    the bank ``A, B`` `(P, N, *Nd, …)` and its tangents, :func:`ab_sequence_jvp` follows.  Operands exactly as
+    :func:`sequence_rfgr`.  ``tangents``: a dict with one leading direction axis ``D`` for all keys:
+
+      - ``'rf'`` `(D, P, N, xy, nT)`, ``'gr'`` `(D, P ⊻ 1, N, xyz, nT)`, ``'loc'``, ``'b1Map'`` feed the bank;
+      - ``'T1'``, ``'T2'``, ``'Δf'`` feed both the pulses and the rests -- with ``Δf_rest`` given, ``'Δf'`` feeds only the
+        pulses and the key ``'Δf_rest'`` the rests;
+      - ``'Mi'``, ``'phase'``, ``'rest'`` feed the train.
+
+    Any broadcastable axis may be 1.  The limits of :func:`ab_rfgr_jvp` are inherited with the batch ``P·N``: one
+    transmit coil, ``4·P·N ≤ 65535``; ``consts=`` carries no tangents here.  Returns ``Mt`` `(N, *Nd, K, xyz)` and
+    ``dMt`` `(D, N, *Nd, K, xyz)`."""
+    if rf.ndim == 5 and rf.shape[-1] != 1:
+        raise NotImplementedError('parallel transmit')
+    assert rf.ndim in (4, 5) and gr.ndim == 4 and gr.shape[0] in (1, rf.shape[0]) and gr.shape[1] == rf.shape[1], \
+        f"rf {tuple(rf.shape)} must be (P, N, xy, nT[, 1]) and gr {tuple(gr.shape)} (P ⊻ 1, N, xyz, nT)"
+    P, N = rf.shape[0], rf.shape[1]
+    sched = _sequence_schedule(pulse, P)          # before any work on the device
+    rest_key = 'Δf' if Δf_rest is None else 'Δf_rest'
+    keys = _SEQ_RFGR_BANK_KEYS + _SEQ_RFGR_TRAIN_KEYS + (('Δf_rest',) if Δf_rest is not None else ())
+    D, given = _given_tangents(tangents, keys)
+    bank = {k: given[k] for k in _SEQ_RFGR_BANK_KEYS if k in given}
+    for k, lead in (('rf', P), ('gr', gr.shape[0])):     # the bank axis of the pulse tangents, flattened into the batch
+        if k in bank:
+            t = bank[k]
+            op = rf if k == 'rf' else gr
+            if t.ndim != op.ndim + 1 or any(a not in (1, b) for a, b in zip(t.shape[1:], op.shape)):
+                raise ValueError(f"mrphy_amd: `tangents['{k}']` {tuple(t.shape)} does not broadcast to (D, "
+                                 f"{', '.join(map(str, op.shape))})")
+            bank[k] = t.expand((D, P) + tuple(op.shape[1:])).flatten(1, 2)
+    for k in ('loc', 'b1Map', 'Δf', 'T1', 'T2'):
+        if k in bank:
+            bank[k] = _over_bank(bank[k], P, N, axis=1)
+    side = lambda x: _over_bank(x, P, N)  # noqa: E731
+    over = lambda x: x.expand((P,) + tuple(x.shape)).flatten(0, 1)  # noqa: E731
+    ops = dict(Δf=side(Δf), b1Map=side(b1Map), γ_beff=side(γ_beff), T1=side(T1), T2=side(T2), γ=side(γ), dt=side(dt),
+               consts=None if consts is None else {k: side(v) for k, v in consts.items()})
+    rf_b, gr_b = rf.flatten(0, 1), over(gr[0]) if gr.shape[0] == 1 else gr.flatten(0, 1)
+    train = {k: given[k] for k in _SEQ_RFGR_TRAIN_KEYS + ('T1', 'T2') if k in given}
+    if rest_key in given:
+        train['Δf'] = given[rest_key]
+    if bank:
+        A, B, dA, dB = ab_rfgr_jvp(rf_b, gr_b, over(loc), tangents=bank, **ops)
+        train['A'], train['B'] = dA.unflatten(1, (P, N)), dB.unflatten(1, (P, N))
+    else:
+        with torch.no_grad():
+            A, B = ab_rfgr(rf_b, gr_b, over(loc), **ops)
+    return ab_sequence_jvp(A.unflatten(0, (P, N)), B.unflatten(0, (P, N)), tangents=train, pulse=sched, n=n, Mi=Mi,
+                           phase=phase, rest=rest, T1=T1, T2=T2, Δf=Δf if Δf_rest is None else Δf_rest)
 
 
 def _signal_buffers(query, code, b, mi, rx, nRx, K, want_ckpt):
